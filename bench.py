@@ -2,9 +2,18 @@
 """Headline benchmark: composite-llk evaluations/s over a (split x mi-rate) grid at
 128 merged PSMC intervals (BASELINE.json `metric`, configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warmup steps, times EXACTLY K steps once and prints the line: `value`, `ms_per_step` and the
+headline fields.  Everything else it can measure - the single-batch pass and the roofline, the secondary legs (single_call,
+host_abi, llk_kernel; with several ranks the other scaling and the strong search) and the CPU baselines with their parity
+samples - runs only with --full.
+--dump-outputs DIR writes what the timed path returned in its LAST timed step (rank 0's lane of that step) as float64 .npy
+files: llk.npy [n, R], jafs.npy [n, 7], status.npy [n] (the int32 codes, exact in float64), candidates.npy [n] (the rows of
+the workload's grid they belong to); above 64 MB in all a fixed, seeded sample of the rows is written instead.  The inputs are
+seeded: the same arguments give the same inputs on every run.
 
 Started WITHOUT torchrun and with --gpus N > 1 (no WORLD_SIZE in the environment) this process never touches the
 GPU: it starts the second command line as a child (one rank per GPU), forwards rank 0's single JSON line and
@@ -18,12 +27,13 @@ batch: the 4 096-point grid of config 2 (64 split indices x 64 rates of one band
 What the line says ("make the bench line say what it measures"):
   value / ms_per_step      whole-job rate with `config.batches_in_flight` independent batches overlapped on as many
                            engine contexts + HIP streams (a batch alone is latency-bound by its longest
-                           lambda-correction chain); W warmup steps, then EXACTLY K steps between barriers, repeated
-                           until the timed regions add up to >= --min-seconds, median repetition reported
-  single_batch             the same step issued strictly one after another on ONE stream: the per-grid latency and
+                           lambda-correction chain); W warmup steps, then EXACTLY K steps between barriers (timed once;
+                           --min-seconds S repeats the K-step region until the regions add up to >= S and reports the
+                           median repetition)
+  single_batch (--full)    the same step issued strictly one after another on ONE stream: the per-grid latency and
                            rate (this is the figure to compare with "one grid sweep" as BASELINE.json words config 2)
-  roofline                 dominant kernel, HIP events on its launch stream during the single-batch pass
-  cpu_baseline             the NumPy/SciPy oracle on a bounded sample, in a CHILD PROCESS that never touched the GPU
+  roofline (--full)        dominant kernel, HIP events on its launch stream during the single-batch pass
+  cpu_baseline (--full)    the NumPy/SciPy oracle on a bounded sample, in a CHILD PROCESS that never touched the GPU
 
 --scaling weak (default): every rank its own grid, one all_gather of llk per batch (RCCL).
 --scaling strong: ONE grid (use --workload config4 | config5, the 8-GPU configurations of BASELINE.json) sharded
@@ -65,6 +75,8 @@ sys.path.insert(0, ROOT)
 # lanes - two or three lanes two batches deep take the same time; 16 lanes 2.22e7).
 DEFAULT_STREAMS = 20 if (int(os.environ.get("WORLD_SIZE", "1")) <= 1 and "--force-dist" not in sys.argv) else 17
 HW_QUEUES = 22                 # the cap misti_lanes.cpp sets (a 24th ACTIVE queue is a cliff: profiles/r06_hw_queue_cliff.txt); --hw-queues overrides it
+LEG_MIN_SECONDS = 0.25         # --full: the single-batch pass and the secondary legs repeat their timed regions to this (unless --min-seconds)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: above this, a seeded sample of the rows
 
 
 def _early_streams():
@@ -105,14 +117,20 @@ def parse(argv=None):
     ap.add_argument("--pretend-world", type=int, default=0,
                     help="single GPU, --scaling strong: evaluate the shard rank 0 of an N-rank run would own (a per-rank cost model, not a scaling "
                          "curve; the line says so in config.pretend_world and counts only that shard's candidates)")
-    ap.add_argument("--min-seconds", type=float, default=0.25, help="repeat the K-step timed loop until the timed regions add up to this; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also the single-batch pass and roofline, the secondary legs and the CPU baselines (a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64; a seeded sample of rows above 64 MB)")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the K-step timed region of the headline leg until the regions add up to this and report the median "
+                         "(default: the K steps are timed once); the --full legs repeat theirs to %.2f s unless this is given" % LEG_MIN_SECONDS)
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline sample (wall)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--fit", default="", choices=("", "cpfit", "default"),
                     help="override the workload's fitting mode: cpfit (--cpfit) or default (the reference's default: expected coalescence time)")
     ap.add_argument("--bh-niter", type=int, default=0, help="config3-basinhopping: hops per start (default: SciPy's 100, as the reference's Solve(globalOpt=True))")
     ap.add_argument("--bh-starts", type=int, default=0, help="config3-search / config3-basinhopping: number of random starts (default: 16 384, BASELINE config 3)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the single_call / host_abi / strong blocks (headline leg only)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full without the single_call / host_abi / llk_kernel / strong blocks (headline leg, single-batch pass, CPU baselines)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the all_gather path even with one rank (rehearsal)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU (tests/test_bench_launcher_cpu.py): ranks rendezvous over gloo, shard a stub grid with "
@@ -126,7 +144,25 @@ def parse(argv=None):
     ap.add_argument("--streams", type=int, default=DEFAULT_STREAMS,
                     help="HIP streams the steps are issued on round-robin: independent batches overlap (1 = strictly serial)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when this process starts the ranks itself (default: a free one)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)      # the ranks of launch_ranks run in ROOT
+    return a
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every array as path/<name>.npy in float64, rows in common.  Above DUMP_MAX_BYTES a fixed sample of the rows
+    (numpy's default_rng(0), sorted) is written instead, and rows.npy names them."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_row = sum(v.nbytes for v in arrays.values()) / max(1, n)
+    if per_row * n > DUMP_MAX_BYTES:
+        budget = DUMP_MAX_BYTES - 256 * (len(arrays) + 1)          # .npy headers
+        keep = np.sort(np.random.default_rng(0).choice(n, size=int(budget // (per_row + 8)), replace=False))
+        arrays = dict({k: v[keep] for k, v in arrays.items()}, rows=keep.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def _free_port():
@@ -143,6 +179,8 @@ def launch_ranks(a):
     `parallel -j 20` over OS processes, /root/reference/README.md:110-115)."""
     port = a.master_port or _free_port()
     args = [x for x in sys.argv[1:]]
+    if a.dump_outputs:
+        args += ["--dump-outputs", a.dump_outputs]          # absolute: the ranks run in ROOT (argparse keeps the last one)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + args
     env = dict(os.environ)
@@ -355,6 +393,10 @@ def main():
 
     spec = lambda *args: truth_spectrum(*args, device=local_rank)
     if a.workload in ("config3-search", "config3-basinhopping"):
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs: grid workloads only (a search's results are summarised in its line)")
+        if a.min_seconds is None:
+            a.min_seconds = LEG_MIN_SECONDS
         from misti_amd import search_bench
         return search_bench.run(a, spec, dev, local_rank, rank, world, json_fd)
 
@@ -363,9 +405,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    leg_min_seconds = LEG_MIN_SECONDS if a.min_seconds is None else a.min_seconds
+
     def leg(workload, scaling, steps, warmup, min_seconds, n_streams, serial_pass=True, keep=False):
         """One measured leg: `steps` steps of `workload` round-robin on n_streams lanes (weak: every rank its own grid;
-        strong: ONE grid sharded over the ranks), W warmup steps first, the K-step region repeated until min_seconds."""
+        strong: ONE grid sharded over the ranks), W warmup steps first, the K-step region repeated until min_seconds (0: timed
+        once).  The serial pass (single batch, per-kernel durations) repeats its region until leg_min_seconds."""
         w = build_workload(workload, spec)
         strong = scaling == "strong"
         shards = None
@@ -500,6 +545,8 @@ def main():
         dt = statistics.median(dts)
         res = {"w": w, "mine": mine, "n": n, "n_total": n_total, "R": R, "P": P, "strong": strong, "bucket": bucket,
                "dts": dts, "dt": dt, "issue": host_issue[0], "steps": steps, "n_streams": len(lanes)}
+        last = lanes[(steps - 1) % len(lanes)]            # the lane of the last timed step: its buffers hold what that step returned
+        res.update(llk=last.llk[:n].cpu().numpy(), jafs=last.jafs.cpu().numpy(), status=last.status.cpu().numpy())
         job_cands = n_total if strong else world * n          # candidates all ranks evaluate per step
         if strong and a.pretend_world > 1 and world == 1:
             job_cands = n                                     # a per-rank cost model: only rank 0's shard is evaluated, only it is counted
@@ -510,15 +557,13 @@ def main():
             serial = lanes[0]
             eng = serial.eng
             k_serial = max(4, min(steps, 16))
-            dts_serial = repeated([serial], k_serial, 2, min_seconds)
+            dts_serial = repeated([serial], k_serial, 2, leg_min_seconds)
             res["dt_serial"], res["k_serial"], res["repeats_serial"] = statistics.median(dts_serial), k_serial, len(dts_serial)
             eng.enable_timing(True)
             eng.kernel_times(reset=True)
             timed([serial], k_serial)
             res["kms"], res["kn"] = eng.kernel_times(reset=True)
             eng.enable_timing(False)
-        res["status"] = lanes[0].status.cpu().numpy()
-        res["llk"] = lanes[0].llk[:n].cpu().numpy()
         chains_mine = len(chain_lengths(w, mine))
         if use_dist:
             t = torch.zeros(world, dtype=torch.int64, device=dev)
@@ -664,11 +709,12 @@ def main():
         return b
 
     n_streams = max(1, a.streams)
-    main_leg = leg(a.workload, a.scaling, a.steps, a.warmup, a.min_seconds, n_streams)
+    main_leg = leg(a.workload, a.scaling, a.steps, a.warmup, a.min_seconds or 0.0, n_streams, serial_pass=a.full)
     w, mine, n, R, dt, dts = main_leg["w"], main_leg["mine"], main_leg["n"], main_leg["R"], main_leg["dt"], main_leg["dts"]
     strong, bucket, job_cands, value = main_leg["strong"], main_leg["bucket"], main_leg["job_cands"], main_leg["value"]
     status, llk = main_leg["status"], main_leg["llk"]
-    kms, kn, dt_serial, k_serial = main_leg["kms"], main_leg["kn"], main_leg["dt_serial"], main_leg["k_serial"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"llk": llk, "jafs": main_leg["jafs"], "status": status, "candidates": mine})
 
     metric = "composite-llk evals/sec over (split×mi) grid, 128 merged PSMC intervals"
     try:                                              # the exact string of BASELINE.json when it is at hand
@@ -688,7 +734,8 @@ def main():
                                    "every rank its own grid, all_gather of llk (RCCL), one collective per %d batches of a lane" % bucket) if world > 1 else "1 GPU"},
         "timing": {"repeats": len(dts), "timed_region_s_median": dt, "timed_region_s_total": sum(dts),
                    "timed_region_s_min": min(dts), "timed_region_s_max": max(dts),
-                   "note": "value and ms_per_step are the MEDIAN repetition of the K-step timed region (each between barriers, max over ranks)"},
+                   "note": "value and ms_per_step are the K-step timed region between barriers (max over ranks); with --min-seconds, the MEDIAN "
+                           "repetition of that region"},
     }
     out_spectra_per_s = job_cands * a.steps / dt
 
@@ -699,7 +746,7 @@ def main():
     # measured headline is on stdout, and a launcher can still tell a run that hung in a secondary leg from a clean one.
     extra = {}
     watchdog = None
-    if not a.no_extra_legs and world > 1:
+    if a.full and not a.no_extra_legs and world > 1:
         import threading
         headline_only = dict(out, extra_legs={"error": "a secondary leg did not finish within %d s on every rank; headline leg only" % EXTRA_LEGS_TIMEOUT_S})
 
@@ -710,7 +757,7 @@ def main():
         watchdog = threading.Timer(EXTRA_LEGS_TIMEOUT_S, expire)
         watchdog.daemon = True
         watchdog.start()
-    if not a.no_extra_legs:
+    if a.full and not a.no_extra_legs:
         short = max(8, min(a.steps, 64))
         if world > 1:
             # both scalings in one line: the headline leg is one of them, the other one here
@@ -728,7 +775,7 @@ def main():
                 return bool(flag.item() > 0)
             leg_failed = False
             try:                                   # a secondary leg must never cost the headline line (the same code runs on every rank)
-                o_leg = leg("config5" if other == "strong" else "config2", other, short, min(a.warmup, 16), a.min_seconds, n_streams, serial_pass=False)
+                o_leg = leg("config5" if other == "strong" else "config2", other, short, min(a.warmup, 16), leg_min_seconds, n_streams, serial_pass=False)
                 extra[other] = block(o_leg, "ONE config-5 grid (65 536 candidates, 2 048 chains) sharded over the ranks, %s" % ("whole chains per rank" if a.shard == "chain" else "interleaved") if other == "strong"
                                      else "every rank its own config-2 grid")
             except Exception as e:                 # noqa: BLE001
@@ -761,7 +808,7 @@ def main():
         elif a.workload == "config2":
             # ONE call on ONE stream at the overlapped rate: 16 config-2 grids with distinct rate axes in one batch
             try:
-                s_leg = leg("config2x16", "weak", max(4, min(a.steps, 32)), 4, a.min_seconds, 1, serial_pass=True)
+                s_leg = leg("config2x16", "weak", max(4, min(a.steps, 32)), 4, leg_min_seconds, 1, serial_pass=True)
                 extra["single_call"] = block(s_leg, "16 config-2 grids with distinct rate axes (65 536 candidates, 1 024 chains) as ONE misti_eval_batch_dev "
                                                     "call per step, strictly one after another on ONE stream")
             except Exception as e:                 # noqa: BLE001
@@ -781,47 +828,49 @@ def main():
         watchdog.cancel()
     if rank == 0:
         out.update(extra)
-        out["single_batch"] = {"value": job_cands * R * k_serial / dt_serial, "ms_per_step": 1e3 * dt_serial / k_serial, "steps": k_serial,
-                               "streams": 1, "repeats": main_leg["repeats_serial"],
-                               "note": "the same step issued strictly one after another on one stream: one grid's latency, bounded by its "
-                                       "longest lambda-correction chain (up to ~900 dependent residual evaluations in the runaway corner of "
-                                       "the grid); `value` above overlaps config.batches_in_flight such batches"}
-        out["serial"] = out["single_batch"]          # round-1 name of the same block
-        # ---- roofline of the dominant kernel -----------------------------------------
-        per_ms = {k: (kms[k] / kn[k] if kn[k] else 0.0) for k in kms}          # ms per launch, HIP events on the launch stream
-        dom = max(("correct", "spectrum"), key=lambda k: per_ms[k])
-        ab = algorithmic_bytes(w, R, mine)
-        achieved = ab[dom] / (per_ms[dom] * 1e-3) / 1e9 if per_ms[dom] > 0 else 0.0
-        out["roofline"] = roofline_block(a.workload, world, dom, per_ms, ab, achieved, n)
-        if "llk_kernel" in out:
-            out["roofline"]["llk_kernel"] = out.pop("llk_kernel")       # the HBM-write-bound kernel reported separately
-        v = out["roofline"].get("valu")
-        if v and v.get("wave_insts"):
-            # the same counters at the rate of the headline leg: launches of the dominant kernel per second x its wave-instructions x 4 cycles,
-            # against all SIMD cycles of the chip - what share of the fp64 issue slots the OVERLAPPED run keeps busy
-            launches_per_s = a.steps / dt
-            second_insts = (out["roofline"].get("second_kernel") or {}).get("wave_insts") or 0.0
-            v["frac_at_value_dominant_kernel"] = 4.0 * v["wave_insts"] * launches_per_s / (N_SIMD * GPU_CLOCK_HZ)
-            v["frac_at_value"] = 4.0 * (v["wave_insts"] + second_insts) * launches_per_s / (N_SIMD * GPU_CLOCK_HZ)
-            v["frac_at_value_note"] = ("chip-wide share of fp64 VALU issue slots during the timed region of `value` (%d batches in flight): wave-instructions of "
-                                       "the dominant kernel AND of the batch's other large kernel, x 4 cycles, x launches per second" % n_streams)
-        # secondary figure SURVEY 8d asks for: the flop model of an UNSHARED evaluation (what the reference computes per
-        # candidate: ~16 sparse generator applications of 2 x 220 flop per two-population interval, ~5 kflop of 3x3
-        # exponentials per migrating interval, 0.1 kflop per one-population interval) x distinct spectra per second,
-        # against the fp64 vector peak.  Chain and trunk sharing EXECUTE far fewer flops than this model counts.
-        s_int = np.floor(w.split_time).astype(np.int64)
-        flop_per_spectrum = float(np.mean(s_int * (16 * 440 + 5000) + (w.numT - s_int) * 100))
-        eq_tflops = out_spectra_per_s * flop_per_spectrum / 1e12
-        out["roofline"]["fp64_equivalent"] = {"flop_per_spectrum_model": flop_per_spectrum, "equivalent": eq_tflops, "peak": FP64_VALU_PEAK_TFLOPS,
-                                              "unit": "TFLOP/s", "frac": eq_tflops / FP64_VALU_PEAK_TFLOPS,
-                                              "note": "reference-equivalent work per second (SURVEY 8d model of an unshared evaluation), not executed flops; no credit claimed"}
+        if a.full:                                   # the single-batch pass of the headline leg: its latency and the roofline
+            kms, kn, dt_serial, k_serial = main_leg["kms"], main_leg["kn"], main_leg["dt_serial"], main_leg["k_serial"]
+            out["single_batch"] = {"value": job_cands * R * k_serial / dt_serial, "ms_per_step": 1e3 * dt_serial / k_serial, "steps": k_serial,
+                                   "streams": 1, "repeats": main_leg["repeats_serial"],
+                                   "note": "the same step issued strictly one after another on one stream: one grid's latency, bounded by its "
+                                           "longest lambda-correction chain (up to ~900 dependent residual evaluations in the runaway corner of "
+                                           "the grid); `value` above overlaps config.batches_in_flight such batches"}
+            out["serial"] = out["single_batch"]          # round-1 name of the same block
+            # ---- roofline of the dominant kernel -----------------------------------------
+            per_ms = {k: (kms[k] / kn[k] if kn[k] else 0.0) for k in kms}          # ms per launch, HIP events on the launch stream
+            dom = max(("correct", "spectrum"), key=lambda k: per_ms[k])
+            ab = algorithmic_bytes(w, R, mine)
+            achieved = ab[dom] / (per_ms[dom] * 1e-3) / 1e9 if per_ms[dom] > 0 else 0.0
+            out["roofline"] = roofline_block(a.workload, world, dom, per_ms, ab, achieved, n)
+            if "llk_kernel" in out:
+                out["roofline"]["llk_kernel"] = out.pop("llk_kernel")       # the HBM-write-bound kernel reported separately
+            v = out["roofline"].get("valu")
+            if v and v.get("wave_insts"):
+                # the same counters at the rate of the headline leg: launches of the dominant kernel per second x its wave-instructions x 4 cycles,
+                # against all SIMD cycles of the chip - what share of the fp64 issue slots the OVERLAPPED run keeps busy
+                launches_per_s = a.steps / dt
+                second_insts = (out["roofline"].get("second_kernel") or {}).get("wave_insts") or 0.0
+                v["frac_at_value_dominant_kernel"] = 4.0 * v["wave_insts"] * launches_per_s / (N_SIMD * GPU_CLOCK_HZ)
+                v["frac_at_value"] = 4.0 * (v["wave_insts"] + second_insts) * launches_per_s / (N_SIMD * GPU_CLOCK_HZ)
+                v["frac_at_value_note"] = ("chip-wide share of fp64 VALU issue slots during the timed region of `value` (%d batches in flight): wave-instructions of "
+                                           "the dominant kernel AND of the batch's other large kernel, x 4 cycles, x launches per second" % n_streams)
+            # secondary figure SURVEY 8d asks for: the flop model of an UNSHARED evaluation (what the reference computes per
+            # candidate: ~16 sparse generator applications of 2 x 220 flop per two-population interval, ~5 kflop of 3x3
+            # exponentials per migrating interval, 0.1 kflop per one-population interval) x distinct spectra per second,
+            # against the fp64 vector peak.  Chain and trunk sharing EXECUTE far fewer flops than this model counts.
+            s_int = np.floor(w.split_time).astype(np.int64)
+            flop_per_spectrum = float(np.mean(s_int * (16 * 440 + 5000) + (w.numT - s_int) * 100))
+            eq_tflops = out_spectra_per_s * flop_per_spectrum / 1e12
+            out["roofline"]["fp64_equivalent"] = {"flop_per_spectrum_model": flop_per_spectrum, "equivalent": eq_tflops, "peak": FP64_VALU_PEAK_TFLOPS,
+                                                  "unit": "TFLOP/s", "frac": eq_tflops / FP64_VALU_PEAK_TFLOPS,
+                                                  "note": "reference-equivalent work per second (SURVEY 8d model of an unshared evaluation), not executed flops; no credit claimed"}
         ok = status == 0
         out["status_fraction"] = {"ok": float(ok.mean()), "correction_failed": float((status == 2).mean()),
                                   "stiff": float((status == 6).mean()), "numeric": float((status == 5).mean())}
         out["spectrum_evals_per_s"] = out_spectra_per_s
         out["host_issue_ms_per_step"] = 1e3 * main_leg["issue"] / a.steps
         # ---- CPU baseline: the oracle on this box's host cores, bounded sample, in a child process ----------
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cores = min(os.cpu_count() or 1, 16)
             per_core = 12.0                                                  # evals/s/core, order of magnitude (measured ~18)
             m = int(max(cores, min(n, a.cpu_seconds * per_core * cores)))

@@ -103,7 +103,11 @@ def test_c_example_reaches_the_overlapped_rate(tmp_path):
     from test_host_cpu import _build_c_example
     path = workloads.dump_text("config2", str(tmp_path / "config2.txt"))
     exe = _build_c_example(tmp_path, "lanes_throughput", hip_runtime=True)
-    r = subprocess.run([exe, path, "20", "400"], capture_output=True, text=True, timeout=300)
+    # the library sets its queue cap only where the environment names none (misti_lanes.cpp): a GPU_MAX_HW_QUEUES inherited from the
+    # caller (4, HIP's default) would put twenty lanes on four queues, so the run gets the library's own cap explicitly
+    import os
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="22")
+    r = subprocess.run([exe, path, "20", "400"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     out = dict(l.split(" = ") for l in r.stdout.splitlines() if " = " in l)
     from parity import record

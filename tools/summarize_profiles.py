@@ -109,7 +109,7 @@ def main():
                 counters.setdefault(k, {}).update(d)
         if not counters:
             continue
-        note = ("rocprofv3 --pmc passes (separate runs: FETCH_SIZE / WRITE_SIZE / SQ_* / SQ_THREAD_CYCLES_VALU ...) of `bench.py --workload %s --streams 1 --steps 4 "
+        note = ("rocprofv3 --pmc passes (separate runs: FETCH_SIZE / WRITE_SIZE / SQ_* / SQ_THREAD_CYCLES_VALU ...) of `bench.py --full --workload %s --streams 1 --steps 4 "
                 "--no-extra-legs`; values of each kernel's last launch (a timed bench batch). "
                 "FETCH_SIZE / WRITE_SIZE are KB as rocprofv3 reports them; on gfx950 FETCH_SIZE counts wide coalesced reads at half "
                 "their bytes (MI355X_MICROARCH.md, HBM section): doubled before comparing with a byte count. SQ_WAVE_CYCLES / SQ_WAIT_* / "
@@ -152,7 +152,7 @@ def main():
         rec = {"kernel": "misti::llk_kernel", "spectra": 65536, "replicates": 1000, "WRITE_SIZE_KB": llk["WRITE_SIZE"], "FETCH_SIZE_KB": llk.get("FETCH_SIZE"),
                "write_bytes": w, "fetch_bytes_corrected": f, "hbm_bytes_per_launch": w + f, "algorithmic_bytes": 8.0 * 65536 * 1000 + 56.0 * 65536 + 72.0 * 1000,
                "grid_size": llk.get("grid_size"), "build_id": build_id,
-               "note": "rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE (separate passes) of `bench.py --workload config4 --streams 1 --steps 4`: the LAST launch of "
+               "note": "rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE (separate passes) of `bench.py --full --workload config4 --streams 1 --steps 4`: the LAST launch of "
                        "misti::llk_kernel = misti_llk_dev on 65 536 spectra x 1 000 replicates; KB as reported, FETCH_SIZE doubled (gfx950: MI355X_MICROARCH.md); "
                        "16-byte-per-lane streaming stores, for which WRITE_SIZE is exact"}
         json.dump(rec, open(os.path.join(dst, "%s_pmc_llk.json" % tag), "w"), indent=1)
@@ -164,7 +164,7 @@ def main():
         for k, d in pmc_last(os.path.join(src, sub)).items():
             dcnt.setdefault(k, {}).update(d)
     if dcnt:
-        json.dump({"note": "rocprofv3 --pmc passes of `bench.py --workload config2 --fit default --streams 1 --steps 4`: per kernel, its last launch", "build_id": build_id,
+        json.dump({"note": "rocprofv3 --pmc passes of `bench.py --full --workload config2 --fit default --streams 1 --steps 4`: per kernel, its last launch", "build_id": build_id,
                    "counters": dcnt}, open(os.path.join(dst, "%s_pmc_config2_default.json" % tag), "w"), indent=1)
         print("wrote %s_pmc_config2_default.json" % tag)
     stats_csv(os.path.join(src, "trace_serial_config2_default"), os.path.join(dst, "%s_kernel_stats_serial_config2_default.csv" % tag))
