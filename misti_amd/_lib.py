@@ -19,7 +19,7 @@ STATUS_TEXT = {
     3: "Infinite coalescent time (two populations in the last interval)",
     4: "Split time / band / pulse structure invalid for this candidate",
     5: "Non-finite intermediate or iteration cap",
-    6: "Stiff interval: the contour solver (rate x length > 96) did not converge",
+    6: "Stiff interval: the contour solve failed and rate x length exceeds 256 series sub-steps of 96",
 }
 MAX_BANDS, MAX_PULSES, MAX_PARAMS, MAX_NUMT = 8, 8, 16, 255
 LANE_ANY, MAX_LANES = -1, 64

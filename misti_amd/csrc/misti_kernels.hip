@@ -60,9 +60,15 @@ __constant__ double c_qmax[QMAX_TABLE];
 //    N = 28 nodes (14 conjugate pairs; truncation 3.89^-N, measured error < 1e-15 here),
 //    each shifted system solved by Jacobi sweeps with the same sparse row gather (the
 //    coalescence part of the generator is nilpotent, so the sweeps terminate in <= 7 steps
-//    unless migration is strong in both directions).  Cost is independent of q.
+//    unless migration is strong in both directions).  Cost is independent of q.  Where the sweeps
+//    diverge or do not settle (two-way migration, mu T >~ 8) the series takes the interval in
+//    ceil(q / Q_SWITCH) sub-steps, up to SUBSTEP_MAX (MISTI_STIFF beyond).
 constexpr double Q_SWITCH = 96.0;
 constexpr int JACOBI_MAX = 600;
+constexpr int JACOBI_WATCH = 32;     // sweeps before the wave-wide stop and divergence tests start
+constexpr int JACOBI_FLOOR = 48;     // sweeps from which a change within 1e-14 of the largest component is converged
+constexpr double JACOBI_BLOWUP = 1e12;   // an iterate this large: the sweeps diverge
+constexpr int SUBSTEP_MAX = 256;     // series sub-steps where the contour solve fails: q up to 256 Q_SWITCH, MISTI_STIFF beyond
 constexpr long long FOLLOW_SPIN_LIMIT = 1LL << 22;   // polls (~1 us each) before a following trunk wave gives up
 
 // ---------------------------------------------------------------- helpers ----
@@ -2101,6 +2107,58 @@ __device__ __forceinline__ void ancient_project(double* xbuf, int lane, double& 
     x = nx;
 }
 
+// Uniformisation series of one (sub-)interval of length T with q = (largest exit rate) x T <= Q_SWITCH (up to rounding):
+// M T = N - q I, p_{k+1} = N p_k/(k+1), i_{k+1} = (T p_k + q i_k)/(k+1); x <- e^{M T} x, wint <- int_0^T e^{M s} x ds
+// (this lane's state).  dT: this state's exit rate x T; cf: the generator's off-diagonal entries of this row x T.
+__device__ __forceinline__ void series_step(const TwoPopRow& R, double* xbuf, int lane, double q, double T, double dT, const double* cf,
+                                            double& x, double& wint) {
+    const double dg = q - dT;
+    const double eq = exp(-q);
+    double p = eq * x, ii = 0.0;
+    double accp = p, acci = 0.0;
+    // the number of terms from q alone (q is the same in every lane): see c_qmax
+    int K = 1;
+    for (int c = 0; c < QMAX_TABLE / 64; ++c) {
+        const unsigned long long below = __ballot(c_qmax[1 + 64 * c + lane] < q);
+        K += __popcll(below);
+        if (below != ~0ull) break;
+    }
+    double inv_next = c_inv[1];
+    for (int k = 1; k <= K; ++k) {
+        const double inv = inv_next;
+        inv_next = c_inv[k + 1];
+        // (the four source states: an LDS write and four reads; the same gather through ds_bpermute was measured slower - config 3's
+        // kernel 2 1.27 -> 1.62 ms)
+        xbuf[lane] = p;
+        lds_fence();
+        double r0 = xbuf[R.srcl[0]], r1 = xbuf[R.srcl[1]], r2 = xbuf[R.srcl[2]], r3 = xbuf[R.srcl[3]];
+        lds_fence();
+        double pn = (dg * p + ((cf[0] * r0 + cf[1] * r1) + (cf[2] * r2 + cf[3] * r3))) * inv;
+        ii = (T * p + q * ii) * inv;
+        p = pn;
+        accp += p; acci += ii;
+    }
+    x = accp; wint = acci;
+}
+
+// The series over n_sub equal sub-steps of an interval (q / n_sub <= Q_SWITCH each): end state and occupation integral
+// accumulate.  Out of line: only intervals whose contour solve failed come here, and inlined it would cost the spectrum
+// kernel registers on its hot path.  Returns (e^{M T} x, int_0^T e^{M s} x ds) of this lane's state.
+__device__ __noinline__ double2 series_substeps(int s0, int s1, int s2, int s3, double c0, double c1, double c2, double c3, double* xbuf,
+                                                int lane, int n_sub, double q, double T, double dT, double x) {
+    TwoPopRow R;
+    R.srcl[0] = s0; R.srcl[1] = s1; R.srcl[2] = s2; R.srcl[3] = s3;
+    const double f = 1.0 / n_sub;
+    const double cf[MAXNZ] = {c0 * f, c1 * f, c2 * f, c3 * f};
+    double wint = 0.0;
+    for (int j = 0; j < n_sub; ++j) {
+        double wj;
+        series_step(R, xbuf, lane, q * f, T * f, dT * f, cf, x, wj);
+        wint += wj;
+    }
+    return make_double2(x, wint);
+}
+
 // One interval of the two-population loop (JAFSpectrum :483-502): pulse at the start of the
 // interval, then x <- exp(M T) x and the occupation integral added to w_pre / w_post.
 // lcb: this wave's (smoothed) rates in LDS.  Returns MISTI_OK / MISTI_NUMERIC / MISTI_STIFF.
@@ -2128,12 +2186,12 @@ __device__ __forceinline__ int twopop_interval(const TwoPopRow& R, const DevMode
         x = nx;
     }
     double la0 = lcb[2 * t], la1 = lcb[2 * t + 1];
-    double T = G.T(t);
+    const double T = G.T(t);
     // largest total exit rate over the 44 states (4 lineages dominate)
     double r40 = 6 * la0 + 4 * mu0, r04 = 6 * la1 + 4 * mu1;
     double r31 = 3 * la0 + 3 * mu0 + mu1, r13 = 3 * la1 + 3 * mu1 + mu0;
     double r22 = la0 + la1 + 2 * mu0 + 2 * mu1;
-    double q = T * fmax(fmax(r40, r04), fmax(fmax(r31, r13), r22));
+    const double q = T * fmax(fmax(r40, r04), fmax(fmax(r31, r13), r22));
     if (!(q < 1e300)) return MISTI_NUMERIC;
     double rate[4] = {la0, la1, mu0, mu1};
     double cf[MAXNZ];
@@ -2141,65 +2199,70 @@ __device__ __forceinline__ int twopop_interval(const TwoPopRow& R, const DevMode
     const double dT = (R.dc0 * la0 + R.dc1 * la1 + R.dc2 * mu0 + R.dc3 * mu1) * T;   // exit rate x T of this state
     double wint = 0.0;
     if (q <= Q_SWITCH) {
-        // uniformisation: M T = N - q I, p_{k+1} = N p_k/(k+1), i_{k+1} = (T p_k + q i_k)/(k+1)
-        const double dg = q - dT;
-        const double eq = exp(-q);
-        double p = eq * x, ii = 0.0;
-        double accp = p, acci = 0.0;
-        // the number of terms from q alone (q is the same in every lane): see c_qmax
-        int K = 1;
-        for (int c = 0; c < QMAX_TABLE / 64; ++c) {
-            const unsigned long long below = __ballot(c_qmax[1 + 64 * c + lane] < q);
-            K += __popcll(below);
-            if (below != ~0ull) break;
-        }
-        double inv_next = c_inv[1];
-        for (int k = 1; k <= K; ++k) {
-            const double inv = inv_next;
-            inv_next = c_inv[k + 1];
-            // (the four source states: an LDS write and four reads; the same gather through ds_bpermute was measured slower - config 3's
-            // kernel 2 1.27 -> 1.62 ms)
-            xbuf[lane] = p;
-            lds_fence();
-            double r0 = xbuf[R.srcl[0]], r1 = xbuf[R.srcl[1]], r2 = xbuf[R.srcl[2]], r3 = xbuf[R.srcl[3]];
-            lds_fence();
-            double pn = (dg * p + ((cf[0] * r0 + cf[1] * r1) + (cf[2] * r2 + cf[3] * r3))) * inv;
-            ii = (T * p + q * ii) * inv;
-            p = pn;
-            accp += p; acci += ii;
-        }
-        x = accp; wint = acci;
+        series_step(R, xbuf, lane, q, T, dT, cf, x, wint);
     } else {
         // Talbot contour, conjugate pairs folded: f = 2 Re sum_{k upper} (-c_k) (z_k - M T)^-1 x
         double accp = 0.0, acci = 0.0;
-        bool stalled = false;
-        for (int nd = 0; nd < TALBOT_HALF; ++nd) {
+        bool solved = true;
+        for (int nd = 0; nd < TALBOT_HALF && solved; ++nd) {
             const double zr = c_tab.tal_zr[nd], zi = c_tab.tal_zi[nd], cr = c_tab.tal_cr[nd], ci = c_tab.tal_ci[nd];
             const double ar = zr + dT, ai = zi;
             const double den = 1.0 / (ar * ar + ai * ai);
             const double ir = ar * den, im = -ai * den;              // 1 / (z + D_i)
             double xr = x * ir, xi = x * im;
-            int it = 0;
-            for (; it < JACOBI_MAX; ++it) {
+            // Stop test: every lane's change below 4e-16 of its own value.  Past JACOBI_WATCH sweeps (the coalescence part is
+            // nilpotent: a solve that is not done by then has two-way migration), every 8th sweep, against the wave's largest component
+            // instead - a lane-relative test never fires where a small component alternates between two roundings - and from
+            // JACOBI_FLOOR sweeps on 1e-14 of it is accepted (the rounding floor of such a limit cycle).  An iterate above
+            // JACOBI_BLOWUP diverges (spectral radius > 1 at nodes left of the origin; the right-hand side is a probability
+            // vector, and the contour sum of iterates that large would have lost every digit anyway); that, or no end in
+            // JACOBI_MAX sweeps: the interval is taken by the series in sub-steps instead.
+            // one sweep; d: this lane's change, sz: its new magnitude
+            auto sweep = [&](double& d, double& sz) {
                 xbuf[lane] = xr; xbuf[64 + lane] = xi;
                 lds_fence();
                 double sr = x + ((cf[0] * xbuf[R.srcl[0]] + cf[1] * xbuf[R.srcl[1]]) + (cf[2] * xbuf[R.srcl[2]] + cf[3] * xbuf[R.srcl[3]]));
                 double si = (cf[0] * xbuf[64 + R.srcl[0]] + cf[1] * xbuf[64 + R.srcl[1]]) + (cf[2] * xbuf[64 + R.srcl[2]] + cf[3] * xbuf[64 + R.srcl[3]]);
                 lds_fence();
                 double nr = sr * ir - si * im, ni = sr * im + si * ir;
-                bool moving = (fabs(nr - xr) + fabs(ni - xi)) > 4e-16 * (fabs(nr) + fabs(ni)) + 1e-300;
+                d = fabs(nr - xr) + fabs(ni - xi);
+                sz = fabs(nr) + fabs(ni);
                 xr = nr; xi = ni;
-                if (!__any(moving)) break;
+            };
+            int it = 0;
+            for (; it < JACOBI_WATCH; ++it) {               // the common case, kept tight
+                double d, sz;
+                sweep(d, sz);
+                if (!__any(d > 4e-16 * sz + 1e-300)) break;
             }
-            if (it >= JACOBI_MAX) stalled = true;
+            if (it == JACOBI_WATCH) {
+                for (; it < JACOBI_MAX; ++it) {
+                    double d, sz;
+                    sweep(d, sz);
+                    if (!__any(d > 4e-16 * sz + 1e-300)) break;
+                    if (it & 7) continue;                       // (every 8th sweep: the wave reduction costs)
+                    for (int o = 32; o > 0; o >>= 1) sz = fmax(sz, __shfl_xor(sz, o, 64));
+                    if (!(sz <= JACOBI_BLOWUP)) { it = JACOBI_MAX; break; }
+                    if (!__any(d > (it < JACOBI_FLOOR ? 4e-16 : 1e-14) * sz + 1e-300)) break;
+                }
+            }
+            if (it >= JACOBI_MAX) { solved = false; break; }
             const double wr = -(cr * xr - ci * xi), wi = -(cr * xi + ci * xr);
             const double zz = 1.0 / (zr * zr + zi * zi);
             const double gr = T * zr * zz, gi = -T * zi * zz;        // T / z
             accp += 2.0 * wr;
             acci += 2.0 * (wr * gr - wi * gi);
         }
-        if (stalled) return MISTI_STIFF;
-        x = accp; wint = acci;
+        if (solved) {
+            x = accp; wint = acci;
+        } else {
+            // the series over n sub-steps of q / n <= Q_SWITCH each: end state and occupation integral accumulate, every
+            // term stays non-negative
+            const int n_sub = (int)ceil(q / Q_SWITCH);
+            if (n_sub > SUBSTEP_MAX) return MISTI_STIFF;
+            const double2 r = series_substeps(R.srcl[0], R.srcl[1], R.srcl[2], R.srcl[3], cf[0], cf[1], cf[2], cf[3], xbuf, lane, n_sub, q, T, dT, x);
+            x = r.x; wint = r.y;
+        }
     }
     if (t < m.sample_date) w_pre += wint; else w_post += wint;
     return MISTI_OK;
