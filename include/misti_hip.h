@@ -226,6 +226,26 @@ int misti_nm_solve(misti_ctx* ctx, int64_t n_start, const double* starts, double
                    double xatol, double fatol, int32_t maxiter,
                    double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
+/* misti_nm_solve with a split time and a data row PER START: start s is SciPy's Nelder-Mead on -JAFSLikelihood at split_times[s]
+ * against row rows[s] of the replicate table.  Replaces the bootstrap profiles of the reference's test.bs scripts
+ * (test.bs/san_din.bs.sh:27-36 and its siblings: `for bs in 0..100; for st in 15..25: MiSTI.py ... ${st} -bs ${bs} -mi ... --cpfit`,
+ * one MigrationInference.Solve - MigrationInference.py:718-733 - per (replicate, split) pair and process) with ONE batched
+ * search over all pairs (and starts): every evaluation batch of the search carries points of many splits and rows, then one
+ * small kernel scores each point against its own row - the same bits as the inline replicate epilogue, so start s returns
+ * exactly what misti_nm_solve(starts[s], split_times[s], jsfs + 8 rows[s]) returns.  Starts that share initial values also
+ * share the chains of their initial simplices (computed once, up to the largest split).  Host buffers; synchronous;
+ * misti_nm_last_stats / misti_nm_last_spec_iterations report on it.
+ *   starts       [n_start][n_param]   (n_param >= 1)
+ *   split_times  [n_start]            finite, fractional allowed (an invalid one gives its start llh = -inf)
+ *   rows         [n_start]            0 <= rows[s] < n_rep
+ *   jsfs         [n_rep][8]           the replicate table (row 0 of a -bs file: the data)
+ *   xatol .. status                   as misti_nm_solve
+ * MISTI_E_ARG, before anything touches the device, for a NULL pointer, n_rep < 1, a row out of range, a non-finite split time
+ * or maxiter < 1. */
+int misti_nm_solve_rows(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                        int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                        double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
+
 /* Batched basin hopping: scipy.optimize.basinhopping(func, x0, niter, T, stepsize, minimizer_kwargs=dict(method='Nelder-Mead'),
  * interval, target_accept_rate, stepwise_factor, rng=...) for n_start starts at once - the reference's global search,
  * MigrationInference.Solve(globalOpt=True) (MigrationInference.py:723-725: T = 0.5, Nelder-Mead with SciPy's defaults, i.e.

@@ -17,6 +17,10 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               given split time follow each candidate's split
     --grid-mi K LO HI N       N log-spaced values for the K-th optimised parameter
     --all-bs                  evaluate every row of the JSFS file as a replicate
+    --grid-solve              with --grid-st and/or --all-bs: for every (row, split) pair the reference's Solve from the
+                              -mi/-pu initial values (the --grid-mi mesh points as starts: the best per pair), all pairs
+                              in ONE batched search on the device; per pair the line MiSTI.py:240 prints (the test.bs
+                              loops' order: row outer, split inner), then the 97.5 % t-interval of bs_conf_int.ipynb
     --gpus N                  the sweep on N GPUs of the node: this process starts N ranks (one per GPU, torch.distributed over
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
@@ -71,7 +75,47 @@ def build_parser():
     p.add_argument("--all-bs", action="store_true", help="evaluate every JSFS row as a bootstrap replicate")
     p.add_argument("--gpus", type=int, default=1, help="grid mode: start this many ranks, one per GPU (replaces `parallel -j N ./MiSTI.py ...`)")
     p.add_argument("--devices", type=str, default="", help="grid mode: comma-separated device list evaluated from this one process (misti_create_multi)")
+    p.add_argument("--grid-solve", action="store_true",
+                   help="with --grid-st / --all-bs: optimise every (replicate, split) pair as the test.bs loops do, in one batched search")
     return p
+
+
+def grid_solve_error(a):
+    """Why ``--grid-solve`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if not a.grid_solve:
+        return None
+    if not (a.grid_st or a.all_bs):
+        return "--grid-solve optimises every (replicate, split) pair: it needs --grid-st and/or --all-bs"
+    if a.gpus > 1 or a.devices:
+        return "--grid-solve runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    if not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
+        return "--grid-solve needs at least one optimised parameter (-mi ... 1 or -pu ... 1)"
+    return None
+
+
+def result_line(bs_id, split, times, scale_time, mi, x, llh):
+    """The result line of one fitted model, exactly as MiSTI.py:240 prints it (what the test.bs scripts grep): ``times`` is the
+    interval grid after a fractional split has been inserted (MigrationInference.__init__ extends it in place)."""
+    fixed = [float(el[3]) for el in mi if int(el[4]) == 0]
+    fixed_s = "fixed = [" + ", ".join(str(v) for v in fixed) + "]" if fixed else ""
+    opt_s = "optim = [" + ", ".join(str(v) for v in x) + "]" if len(x) > 0 else ""
+    mig_s = fixed_s + "\t" + opt_s if fixed_s and opt_s else fixed_s + opt_s
+    return " ".join(str(v) for v in ("bs_id =", bs_id, "\tsplitT =", split, "\ttime =", sum(times[0:ceil(split)]) * scale_time,
+                                     "\tmigration rates", mig_s, "\tllh =", llh))
+
+
+def split_grid_times(times, split):
+    """The interval lengths as MigrationInference.__init__ leaves them for ``split`` (MigrationInference.py:89-99): a fractional
+    split cuts its interval in two."""
+    times = list(times)
+    frac = split % 1
+    s = int(split)
+    if frac != 0.0 and s < len(times):              # (a split beyond the grid has no model: its pairs carry llh = -inf)
+        t1 = frac * times[s]
+        t2 = times[s] - t1
+        times[s] = t1
+        times.insert(s + 1, t2)
+    return times
 
 
 def _evaluator(a, inp, bands, pulses, k, device):
@@ -88,8 +132,10 @@ def _evaluator(a, inp, bands, pulses, k, device):
     return e.evaluate, e.close
 
 
-def grid_mode(a, inp, rows):
-    """Batched sweep: one Engine, candidates = split values x parameter grid, replicates = JSFS rows."""
+def grid_model(a):
+    """What grid mode and --grid-solve share: the split values, the band and pulse records (bands ending at the given split time
+    follow each candidate's split under --grid-st), the number of optimised parameters, and one axis per parameter (its -mi/-pu
+    initial value, or its --grid-mi mesh)."""
     st0 = a.st
     splits = [st0]
     if a.grid_st:
@@ -115,6 +161,12 @@ def grid_mode(a, inp, rows):
     axes = [np.array([v]) for v in init]
     for g in a.grid_mi:
         axes[int(g[0])] = np.logspace(np.log10(float(g[1])), np.log10(float(g[2])), int(g[3]))
+    return splits, bands, pulses, k, axes
+
+
+def grid_mode(a, inp, rows):
+    """Batched sweep: one Engine, candidates = split values x parameter grid, replicates = JSFS rows."""
+    splits, bands, pulses, k, axes = grid_model(a)
     mesh = np.meshgrid(np.array(splits), *axes, indexing="ij")
     split = mesh[0].ravel()
     params = np.stack([m.ravel() for m in mesh[1:]], axis=1) if k else None
@@ -162,9 +214,47 @@ def grid_mode(a, inp, rows):
     return 0
 
 
+def grid_solve(a, inp, rows):
+    """The bootstrap profiles of the reference's test.bs scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
+    -mi ...``, one Solve per pair) as ONE batched search: every (row, split, start) triple is a start of misti_nm_solve_rows."""
+    from .optimize import bootstrap_profile, bootstrap_profile_interval
+    splits, bands, pulses, k, axes = grid_model(a)
+    starts = np.stack([m.ravel() for m in np.meshgrid(*axes, indexing="ij")], axis=1)
+    data = np.array(rows if a.all_bs else [rows[a.bsMode] if a.bsMode >= 0 else np.sum(rows, axis=0)], dtype=float)
+    ids = list(range(data.shape[0])) if a.all_bs else [a.bsMode]
+    flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    t0 = time.time()
+    with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
+        prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000)
+    dt = time.time() - t0
+    for r in range(data.shape[0]):
+        for p, st in enumerate(splits):
+            print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, prof["x"][r, p], prof["llh"][r, p]))
+    iv = bootstrap_profile_interval(prof["llh"], splits, prof["x"])
+    print()
+    if iv["data_split"] is None:
+        print("grid-solve: bs_id =", ids[0], "has no finite llh at any split")
+    else:
+        print("grid-solve: bs_id =", ids[0], "best splitT =", iv["data_split"], "optim = [" + ", ".join(str(v) for v in iv["data_x"]) + "]",
+              "llh =", iv["data_llh"])
+    if iv["interval"] is None:
+        print("grid-solve: no bootstrap interval (%d bootstrap rows with a best split; at least 2 needed)" % iv["n_boot"])
+    else:
+        print("grid-solve: bootstrap best splitT mean =", iv["mean"], "97.5%% t-interval = [%r, %r]" % tuple(float(v) for v in iv["interval"]),
+              "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
+    n = prof["llh"].size
+    print("grid-solve: %d pairs x %d starts in one search, %.3f s; %d pairs ended on the iteration cap, %d without a value"
+          % (n, starts.shape[0], dt, int((prof["status"] == 2).sum()), int((~np.isfinite(prof["llh"])).sum())))
+    return 0
+
+
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
+    why = grid_solve_error(a)
+    if why:
+        print(why, file=sys.stderr)
+        return 2
     # the two ways of using several GPUs exclude each other: N ranks that each opened the whole device list would run N x D contexts
     if a.gpus > 1 and a.devices:
         print("--gpus (one rank per GPU) and --devices (a device list in one process) exclude each other", file=sys.stderr)
@@ -207,6 +297,8 @@ def main(argv=None):
     fout = os.path.join(a.wd, a.fout) if a.fout else ""
     inp = mio.read_psmc(f1, f2, a.sdate, a.rd, units)
     inp.divergenceTime = a.st
+    if a.grid_solve:
+        return grid_solve(a, inp, rows)
     if a.grid_st or a.grid_mi or a.all_bs:
         return grid_mode(a, inp, rows)
 
@@ -218,13 +310,8 @@ def main(argv=None):
     sol = mig.Solve(a.tol)
     print(sol)
     print("\nParameter estimates:")
-    fixed = [float(el[3]) for el in a.mi if int(el[4]) == 0]
-    fixed_s = "fixed = [" + ", ".join(str(v) for v in fixed) + "]" if fixed else ""
-    opt_s = "optim = [" + ", ".join(str(v) for v in sol[0]) + "]" if len(sol[0]) > 0 else ""
-    mig_s = fixed_s + "\t" + opt_s if fixed_s and opt_s else fixed_s + opt_s
     # inp.times was extended in place by a fractional split, as in the reference (MiSTI.py:240)
-    print("bs_id =", a.bsMode, "\tsplitT =", inp.divergenceTime, "\ttime =",
-          sum(inp.times[0:ceil(inp.divergenceTime)]) * inp.scaleTime, "\tmigration rates", mig_s, "\tllh =", sol[1])
+    print(result_line(a.bsMode, inp.divergenceTime, inp.times, inp.scaleTime, a.mi, sol[0], sol[1]))
     print("\n")
     t2 = time.time()
     if sol[1] == -10 ** 9:

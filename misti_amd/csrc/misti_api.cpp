@@ -956,6 +956,15 @@ struct NmWork {
     double *d_row = nullptr;         // [8]    the data JSFS
     double *extra_f64 = nullptr;     // whatever the caller asked for beyond the minimiser's own state
     int32_t *idx[2] = {nullptr, nullptr}, *cnt = nullptr, *extra_i32 = nullptr;
+    // rows path (misti_nm_solve_rows, st.row_of set): a batch is evaluated without replicates into rjafs / rstatus, then
+    // llk_rows_kernel scores every candidate against its own row of the table
+    const double* table = nullptr;   // [n_rep][8]
+    const double* consts = nullptr;  // [n_rep]  llh_const of every row
+    double* rjafs = nullptr;         // [M][7]   M = the largest batch: max(S (N + 1), spec_cap (4 + N))
+    int32_t* rstatus = nullptr;      // [M]
+    int32_t* rows0 = nullptr;        // the per-slot row arrays row0 | row1 | row2 | row3 | ps_row, contiguous
+    size_t rows_n = 0;
+    bool whole = false;              // every split time of the rows path is an integer
 };
 
 // Live starts up to which an iteration is speculative (misti_nm.hip): all 4 + N points of a start in one batch, as long as the
@@ -1019,14 +1028,26 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     const size_t S = (size_t)st.S, V = (size_t)N + 1;
     st.maxiter = maxiter; st.maxfun = maxfun; st.xatol = xatol; st.fatol = fatol; st.split = split_time;
     hipStream_t sm = c->stream;
-    // what the search knows about its own batches: one split time for every point (empty slots carry -1), distinct points
+    const bool rows = st.row_of != nullptr;
+    // what the search knows about its own batches: one split time for every point (empty slots carry -1), distinct points.
+    // The rows path knows less: its chains end at different splits (not one length), and every start from the same initial
+    // values submits the same initial simplex - one chain for all of them, computed once up to the largest split (shared).
     static const int hint_mask = [] { const char* e = getenv("MISTI_NM_HINTS"); return e ? atoi(e) : 7; }();       // diagnostic: which hints the search passes on
-    const unsigned nm_hints = ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH) & (unsigned)hint_mask;
+    const unsigned nm_hints = (rows ? (w.whole ? RUN_INTEGER_SPLITS : 0u)
+                                    : ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH)) & (unsigned)hint_mask;
+    // one engine batch of the search: its values against the one data row, or (rows path) each against its own row
+    auto eval = [&](int64_t n, const double* split, const double* params, const int32_t* row, double* llk) -> int {
+        if (!rows) return run_dev(c, n, split, params, nullptr, 1, w.d_row, llk, nullptr, nullptr, nullptr, nullptr, nm_hints);
+        if (int r = run_dev(c, n, split, params, nullptr, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints)) return r;
+        HIP_TRY(misti::launch_llk_rows(n, w.rjafs, w.rstatus, row, w.table, w.consts, llk, c->unfolded, sm));
+        return 0;
+    };
     int32_t* cnt = w.cnt;
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
     HIP_TRY(hipMemsetAsync(st.split1, 0xBF, S * sizeof(double), sm));          // all-0xBF bytes: a negative double = "no point in this slot"
+    if (rows) HIP_TRY(hipMemsetAsync(w.rows0, 0, w.rows_n * sizeof(int32_t), sm));   // row 0 in every slot nothing has written yet
     HIP_TRY(misti::launch_nm_init(st, w.d_starts, sm));
-    if (int r = run_dev(c, (int64_t)(S * V), st.split0, st.sim, nullptr, 1, w.d_row, w.llk0, nullptr, nullptr, nullptr, nullptr, nm_hints)) return r;
+    if (int r = eval((int64_t)(S * V), st.split0, st.sim, st.row0, w.llk0)) return r;
     int cur = 0;
     st.idx_next = w.idx[cur]; st.count_next = cnt + cur;
     HIP_TRY(misti::launch_nm_begin(st, w.llk0, sm));
@@ -1061,7 +1082,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             // of the NEXT iteration and drops the count of live starts into the host's pinned word (nm_spec_step_kernel: the live
             // starts of a speculative iteration fit one workgroup); only the first speculative iteration launches a points kernel
             if (!spec_primed) { HIP_TRY(misti::launch_nm_spec_points(st, bound, sm)); spec_primed = true; }
-            if (int r = run_dev(c, bound * K, st.ps_split, st.ps, nullptr, 1, w.d_row, w.llk_spec, nullptr, nullptr, nullptr, nullptr, nm_hints)) return r;
+            if (int r = eval(bound * K, st.ps_split, st.ps, st.ps_row, w.llk_spec)) return r;
             // (no memsets here: the points step zeroes the next slot counter, and the reflection-split array is only read by the
             //  three-batch path, which a search never returns to - the number of live starts only falls)
             misti::NmState nx = st;
@@ -1069,11 +1090,11 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             HIP_TRY(misti::launch_nm_spec_step(st, nx, bound, w.llk_spec, (int32_t*)&live_host[slot], sm));
             ++spec_iters;
         } else {
-            if (int r = run_dev(c, bound, st.split1, st.p1, nullptr, 1, w.d_row, w.llk1, nullptr, nullptr, nullptr, nullptr, nm_hints)) return r;
+            if (int r = eval(bound, st.split1, st.p1, st.row1, w.llk1)) return r;
             HIP_TRY(misti::launch_nm_reflect(st, bound, w.llk1, sm));
-            if (int r = run_dev(c, bound, st.split2, st.p2, nullptr, 1, w.d_row, w.llk2, nullptr, nullptr, nullptr, nullptr, nm_hints)) return r;
+            if (int r = eval(bound, st.split2, st.p2, st.row2, w.llk2)) return r;
             HIP_TRY(misti::launch_nm_accept(st, bound, w.llk2, sm));
-            if (int r = run_dev(c, bound * N, st.split3, st.p3, nullptr, 1, w.d_row, w.llk3, nullptr, nullptr, nullptr, nullptr, nm_hints)) return r;
+            if (int r = eval(bound * N, st.split3, st.p3, st.row3, w.llk3)) return r;
             HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
             HIP_TRY(hipMemsetAsync(st.split1, 0xBF, (size_t)bound * sizeof(double), sm));
             HIP_TRY(misti::launch_nm_finish(st, bound, w.llk3, sm));
@@ -1121,6 +1142,64 @@ int misti_nm_solve(misti_ctx* c, int64_t n_start, const double* starts, double s
     if (nit) HIP_TRY(hipMemcpyAsync(nit, w.st.nit, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     if (nfev) HIP_TRY(hipMemcpyAsync(nfev, w.st.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     if (status) HIP_TRY(hipMemcpyAsync(status, w.st.shrunk, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipStreamSynchronize(sm));
+    return 0;
+}
+
+int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                        int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                        double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    // every argument is checked before the first HIP call
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
+    const int N = c->dm.n_param;
+    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
+    if (!starts || !split_times || !rows || !jsfs || !x || !llh) return fail(MISTI_E_ARG, "starts / split_times / rows / jsfs / x / llh is NULL");
+    if (n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)n_rep);
+    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
+    if (n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
+    bool whole = true;
+    for (int64_t s = 0; s < n_start; ++s) {
+        if (rows[s] < 0 || rows[s] >= n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)rows[s], (long long)n_rep);
+        if (!std::isfinite(split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+        if (split_times[s] != std::floor(split_times[s])) whole = false;
+    }
+    if (n_start == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = (size_t)n_start, V = (size_t)N + 1, R = (size_t)n_rep;
+    const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
+    const size_t M = S * V > cap * K ? S * V : cap * K;                         // the largest batch of the search
+    const size_t rows_n = S * V + 2 * S + S * N + cap * K;                       // row0 | row1 | row2 | row3 | ps_row
+    NmWork w;
+    if (int r = nm_prepare(c, n_start, w, S + R * 8 + R + M * 7, S + rows_n + M)) return r;
+    misti::NmState& st = w.st;
+    double* d = w.extra_f64;
+    double* d_split = d; d += S;
+    double* d_table = d; d += R * 8;
+    double* d_consts = d; d += R;
+    w.rjafs = d;
+    int32_t* q = w.extra_i32;
+    int32_t* d_rowof = q; q += S;
+    w.rows0 = q; w.rows_n = rows_n;
+    st.row0 = q; q += S * V; st.row1 = q; q += S; st.row2 = q; q += S; st.row3 = q; q += S * N; st.ps_row = q; q += cap * K;
+    w.rstatus = q;
+    st.split_of = d_split; st.row_of = d_rowof;
+    w.table = d_table; w.consts = d_consts; w.whole = whole;
+    hipStream_t sm = c->stream;
+    HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_split, split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_rowof, rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_table, jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(misti::launch_llh_const(n_rep, d_table, d_consts, c->unfolded, sm));          // once per call, every row
+    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
+    if (int r = nm_run(c, w, 0.0, xatol, fatol, maxiter, INT64_MAX)) return r;
+    HIP_TRY(hipMemcpyAsync(x, w.d_starts, S * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(llh, w.d_llh, S * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (nit) HIP_TRY(hipMemcpyAsync(nit, st.nit, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, st.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (status) HIP_TRY(hipMemcpyAsync(status, st.shrunk, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     HIP_TRY(hipStreamSynchronize(sm));
     return 0;
 }

@@ -112,7 +112,9 @@ struct NmState {
     int maxiter;
     int64_t maxfun;
     double xatol, fatol;
-    double split;           // the split time every point is evaluated at
+    double split;           // the split time every point is evaluated at (unless split_of is set)
+    const double* split_of; // [S] or NULL: the split time of each start's points (misti_nm_solve_rows); NULL: `split` for all
+    const int32_t* row_of;  // [S] or NULL: the replicate row of each start's points; set together with split_of
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)
@@ -132,9 +134,14 @@ struct NmState {
     double* split1;         // [S]       ... of the reflection batch (negative: no point in this slot)
     double* split2;         // [S]
     double* split3;         // [S * N]
+    int32_t* row0;          // [S * V]   replicate row per engine candidate of the four batches, beside split0..3 (NULL unless row_of
+    int32_t* row1;          // [S]       is set; empty slots carry row 0)
+    int32_t* row2;          // [S]
+    int32_t* row3;          // [S * N]
     // speculative iterations (few live starts: latency-bound): every point SciPy COULD ask for in the iteration, one batch
     double* ps;             // [spec_cap][4 + N][N]  reflection, expansion, outside / inside contraction, the N shrunk vertices
     double* ps_split;       // [spec_cap * (4 + N)]
+    int32_t* ps_row;        // [spec_cap * (4 + N)]  or NULL (row_of unset)
     int64_t spec_cap;       // live starts up to which an iteration is speculative
     const int32_t* idx_cur; // [S] slot -> start of the iteration in progress
     const int32_t* count_cur;   // [1] its number of live starts
@@ -219,5 +226,9 @@ hipError_t launch_argmax(int64_t n_cand, int64_t n_rep, const double* llk, int32
 hipError_t launch_llh_const(int64_t n_rep, const double* jsfs, double* consts, int unfolded, hipStream_t stream);
 hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs,
                       const double* consts, double* llk, int unfolded, hipStream_t stream);
+// llk[c] = the log-likelihood of candidate c against ITS OWN replicate row[c] (-inf where status[c] != MISTI_OK): the rows path of
+// the batched search (misti_nm_solve_rows).  Same expressions as the inline epilogue and llk_kernel: the same bits.
+hipError_t launch_llk_rows(int64_t n, const double* jafs, const int32_t* status, const int32_t* row, const double* jsfs,
+                           const double* consts, double* llk, int unfolded, hipStream_t stream);
 
 }  // namespace misti

@@ -3348,6 +3348,29 @@ hipError_t launch_llh_const(int64_t n_rep, const double* jsfs, double* consts, i
     return hipGetLastError();
 }
 
+// One replicate per candidate (misti_nm_solve_rows: every start of the batched search has its own bootstrap row): thread = candidate,
+// llk[c] = llk_of(row[c]) from log_class of its own spectrum.  Same expressions as llk_of / log_class (the inline epilogue of
+// spectrum_kernel and llk_kernel): the same bits as the single-row search's values.  A candidate without a value (status != OK;
+// empty slots carry row 0) reads no row.
+__global__ __launch_bounds__(256)
+void llk_rows_kernel(int64_t n, const double* __restrict__ jafs, const int32_t* __restrict__ status, const int32_t* __restrict__ row,
+                     const double* __restrict__ jsfs, const double* __restrict__ consts, double* __restrict__ llk, int unfolded) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    if (status[c] != MISTI_OK) { llk[c] = -INFINITY; return; }
+    const int64_t r = row[c];
+    double lj[7];
+    for (int i = 0; i < 7; ++i) lj[i] = log_class(jafs + c * 7, i, unfolded);
+    llk[c] = llk_of(jsfs + r * 8, consts[r], lj, unfolded);
+}
+
+hipError_t launch_llk_rows(int64_t n, const double* jafs, const int32_t* status, const int32_t* row, const double* jsfs,
+                           const double* consts, double* llk, int unfolded, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(llk_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, jafs, status, row, jsfs, consts, llk, unfolded);
+    return hipGetLastError();
+}
+
 hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs,
                       const double* consts, double* llk, int unfolded, hipStream_t stream) {
     if (n_cand <= 0 || n_rep <= 0) return hipSuccess;

@@ -271,3 +271,54 @@ def _scan_best(engine, split_values, jsfs_rows, params=None):
     engine.argmax_dev(n, R, llk.data_ptr(), best.data_ptr())
     engine.sync()
     return best.cpu().numpy().astype(np.int64)
+
+
+def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter=1000):
+    """The bootstrap profiles of the reference's ``test.bs`` scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
+    -mi ...``: one ``MigrationInference.Solve`` per (replicate, split) pair, MigrationInference.py:718-733 of the reference) in ONE
+    ``misti_nm_solve_rows`` call: every (row, split, start) triple is a start of the batched search.  ``jsfs_rows`` is ``[R][8]``,
+    ``split_values`` ``[P]``, ``starts`` ``[Q][N]``.  Per (row, split) the best start is kept (ties: the lowest start index).
+    Returns dict(x[R][P][N], llh[R][P], nit / nfev / status / start[R][P], and the search's work counters)."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.asarray(split_values, dtype=float).reshape(-1)
+    starts = np.atleast_2d(np.asarray(starts, dtype=float))
+    R, P, (Q, N) = rows.shape[0], splits.size, starts.shape
+    r_of, p_of, q_of = (a.ravel() for a in np.meshgrid(np.arange(R), np.arange(P), np.arange(Q), indexing="ij"))
+    res = engine.nm_solve_rows(starts[q_of], splits[p_of], r_of.astype(np.int32), rows, tol=tol, maxiter=maxiter)
+    llh = res["llh"].reshape(R, P, Q)
+    best = np.argmax(np.where(np.isnan(llh), -np.inf, llh), axis=2)              # first maximum: the lowest start index
+    pick = lambda a: np.take_along_axis(a.reshape(R, P, Q, *a.shape[1:]), best.reshape(R, P, 1, *([1] * (a.ndim - 1))), axis=2)[:, :, 0]
+    out = dict(x=pick(res["x"]), llh=pick(res["llh"]), nit=pick(res["nit"]), nfev=pick(res["nfev"]), status=pick(res["status"]), start=best)
+    out.update({k: res[k] for k in ("iterations_issued", "slots", "speculative_iterations")})
+    return out
+
+
+def bootstrap_profile_interval(llh, split_values, x=None):
+    """The reduction of the reference's ``test.bs/bs_conf_int.ipynb`` (``conf_int_bs``) over a profile table ``llh[R][P]`` (row 0 the
+    data, rows 1.. the bootstrap replicates; split p = ``split_values[p]``): per row the split of its largest llh (the first on ties,
+    np.argmax), row 0 reported on its own - its split, llh and, given ``x[R][P][N]``, rates - and over rows 1..R-1
+    ``scipy.stats.t.interval(0.975, B - 1, loc=mean, scale=sem)`` of their best splits.  A row without a finite llh has no best
+    split: it is left out (and counted).  Fewer than two bootstrap rows with a best split: no interval.
+    Returns dict(best_split[R] (nan: none), data_split / data_llh / data_x (None: none), mean, interval ((lo, hi) or None),
+    n_boot, n_excluded)."""
+    from scipy import stats
+    llh = np.atleast_2d(np.asarray(llh, dtype=float))
+    splits = np.asarray(split_values, dtype=float).reshape(-1)
+    finite = np.isfinite(llh)
+    has = finite.any(axis=1)
+    idx = np.argmax(np.where(finite, llh, -np.inf), axis=1)
+    best = np.where(has, splits[idx], np.nan)
+    out = dict(best_split=best, data_split=None, data_llh=None, data_x=None, mean=None, interval=None)
+    if has[0]:
+        out["data_split"] = float(splits[idx[0]])
+        out["data_llh"] = float(llh[0, idx[0]])
+        if x is not None:
+            out["data_x"] = np.asarray(x)[0, idx[0]]
+    a = best[1:][has[1:]]
+    out["n_boot"], out["n_excluded"] = int(a.size), int((~has[1:]).sum())
+    if a.size >= 1:
+        out["mean"] = float(np.mean(a))
+    if a.size >= 2:
+        with np.errstate(invalid="ignore"):               # every replicate on one split: sem = 0, the interval is (nan, nan) as there
+            out["interval"] = tuple(float(v) for v in stats.t.interval(0.975, len(a) - 1, loc=np.mean(a), scale=stats.sem(a)))
+    return out
