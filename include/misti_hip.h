@@ -246,6 +246,22 @@ int misti_nm_solve_rows(misti_ctx* ctx, int64_t n_start, const double* starts, c
                         int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                         double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
+/* misti_nm_solve_rows with band bounds PER START as well: start s is SciPy's Nelder-Mead at split_times[s] against row rows[s], with the
+ * model's -mi bands starting and ending where band_bounds[s] says (as misti_eval_batch's band_bounds: end == -1 = the start's split
+ * index).  Replaces the boundary profiles "when did migration start or stop" - the test.bs scripts' `-mi 1 4 ${st} ${j} 1` loops with
+ * a loop over the boundary added, one Engine per bound set and one Solve per model there - with ONE batched search: every batch of
+ * the search carries each point's own bounds.  Starts with equal bounds and equal initial values share the chains of their initial
+ * simplices; starts with different bounds never share a chain (the chain key holds the bounds).  Start s returns exactly what
+ * misti_nm_solve(starts[s], split_times[s], jsfs + 8 rows[s]) returns on a context whose model carries band_bounds[s].
+ *   band_bounds  [n_start][n_band][2] or NULL   NULL: exactly misti_nm_solve_rows.  Ignored when the model has no band.
+ *                Bounds that break SetModel's checks (MigrationInference.py:237-255: start >= sample date, start < end, end inside
+ *                the grid, no overlap within a population) are no argument error: that start gets llh = -inf, its neighbours are
+ *                unaffected (as for an invalid split time).
+ *   other arguments, errors, synchronisation and statistics as misti_nm_solve_rows. */
+int misti_nm_solve_bounds(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                          const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                          double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
+
 /* Batched basin hopping: scipy.optimize.basinhopping(func, x0, niter, T, stepsize, minimizer_kwargs=dict(method='Nelder-Mead'),
  * interval, target_accept_rate, stepwise_factor, rng=...) for n_start starts at once - the reference's global search,
  * MigrationInference.Solve(globalOpt=True) (MigrationInference.py:723-725: T = 0.5, Nelder-Mead with SciPy's defaults, i.e.

@@ -25,6 +25,14 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
                               thread per entry)
+    --sweep NAME V1 V2 ...    the recipe's `::: NAME V1 V2 ...` (repeatable): {NAME} stands in the positional split time and in the
+                              start, end and rate fields of -mi (misti_amd/sweep.py).  Without --grid-solve (every -mi / -pu fixed,
+                              flag 0: an optimised one is refused, the reference would fit it) every model of the product (first
+                              sweep outermost) times the JSFS rows (-bs N or --all-bs) is evaluated in ONE batch with per-candidate
+                              band bounds, and every model prints the MiSTI.py:240 line; with --grid-solve (required as soon as a
+                              parameter is optimised) the time
+                              variables make the models, the rate variables of optimised bands the starts, and every (row, model)
+                              pair is optimised in ONE batched search (misti_nm_solve_bounds)
 """
 from __future__ import annotations
 
@@ -38,6 +46,7 @@ import numpy as np
 
 from . import io as mio
 from .engine import BatchResult, Engine, MigrationInference
+from .sweep import split_arg, sweep_error
 
 
 RANK_MODULE = "misti_amd.cli"       # what `--gpus N` starts N times (a test driver that wraps this module names itself here)
@@ -48,7 +57,7 @@ def build_parser():
     p.add_argument("fpsmc1", help="psmc file 1")
     p.add_argument("fpsmc2", help="psmc file 2")
     p.add_argument("fjafs", help="joint allele frequency spectrum file")
-    p.add_argument("st", type=float, help="split time")
+    p.add_argument("st", type=split_arg, help="split time (or {NAME} of a --sweep)")
     p.add_argument("-o", "--fout", default="", help="output file, default is stdout")
     p.add_argument("-wd", default="", help="working directory (path to data files)")
     p.add_argument("-tol", type=float, default=1e-4, help="optimisation precision (default is 1e-4)")
@@ -77,6 +86,8 @@ def build_parser():
     p.add_argument("--devices", type=str, default="", help="grid mode: comma-separated device list evaluated from this one process (misti_create_multi)")
     p.add_argument("--grid-solve", action="store_true",
                    help="with --grid-st / --all-bs: optimise every (replicate, split) pair as the test.bs loops do, in one batched search")
+    p.add_argument("--sweep", nargs="+", action="append", default=[], metavar=("NAME", "V"),
+                   help="the GNU-parallel recipe's `::: NAME V1 V2 ...`: {NAME} in the split time or in -mi start / end / rate fields")
     return p
 
 
@@ -84,7 +95,7 @@ def grid_solve_error(a):
     """Why ``--grid-solve`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
     if not a.grid_solve:
         return None
-    if not (a.grid_st or a.all_bs):
+    if not (a.grid_st or a.all_bs or a.sweep):
         return "--grid-solve optimises every (replicate, split) pair: it needs --grid-st and/or --all-bs"
     if a.gpus > 1 or a.devices:
         return "--grid-solve runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
@@ -248,10 +259,127 @@ def grid_solve(a, inp, rows):
     return 0
 
 
+def _sweep_models(a, inp, plan):
+    """Which models of the sweep the reference would have run (SetModel's checks; it exits in PrintError for the others), and the
+    Engine for them: band records with the bounds of the first of them (every batch passes its own)."""
+    from .sweep import structure_error
+    pops = [b[0] for b in plan.bands]
+    numT = len(inp.lambdas)
+    ok = np.array([structure_error(plan.split[m], plan.bounds[m], pops, inp.sampleDateDiscr, numT) is None for m in range(plan.n_model)],
+                  dtype=bool)
+    if not ok.any():
+        return ok, None
+    first = int(np.argmax(ok))
+    flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    eng = Engine(inp.times, inp.lambdas, plan.engine_bands(first), plan.pulses, n_param=plan.n_param, sample_date=inp.sampleDateDiscr,
+                 mixture_th=a.mth, device=a.device, **flags)
+    return ok, eng
+
+
+def _data_rows(a, rows):
+    """The JSFS rows of a batched run and their bs_id: every row (--all-bs), row -bs N, or the sum of all rows (as the single run)."""
+    if a.all_bs:
+        return np.array(rows, dtype=float), list(range(len(rows)))
+    one = rows[a.bsMode] if a.bsMode >= 0 else [sum(r[i] for r in rows) for i in range(8)]
+    return np.array([one], dtype=float), [a.bsMode]
+
+
+def _model_text(plan, m, names):
+    return " ".join("%s = %s" % (n, plan.assign[m][n]) for n in names)
+
+
+def _print_sweep_interval(plan, ids, llh, x=None):
+    """The bs_conf_int.ipynb reduction per swept variable (optimize.sweep_interval) of a printed table llh[R][M]."""
+    from .optimize import sweep_interval
+    iv = sweep_interval(llh, plan.values, x)
+    if iv["data_model"] is None:
+        print("sweep: bs_id =", ids[0], "has no finite llh at any model")
+    else:
+        m = iv["data_model"]
+        opt = "" if x is None else " optim = [" + ", ".join(str(v) for v in iv["data_x"]) + "]"
+        print("sweep: bs_id =", ids[0], "best model", _model_text(plan, m, plan.model_names) + opt, "llh =", iv["data_llh"])
+    for n, v in zip(plan.model_names, iv["variables"]):
+        if v["interval"] is None:
+            print("sweep: %s: no bootstrap interval (%d bootstrap rows with a best model; at least 2 needed)" % (n, v["n_boot"]))
+        else:
+            print("sweep: %s bootstrap mean =" % n, v["mean"], "97.5%% t-interval = [%r, %r]" % tuple(float(t) for t in v["interval"]),
+                  "over %d replicates (%d without a value excluded)" % (v["n_boot"], v["n_excluded"]))
+
+
+def sweep_eval(a, inp, rows):
+    """The GNU-parallel recipe (README.md:110-115 of the reference) in ONE evaluation: every model of the sweep x every JSFS row,
+    per-candidate band bounds; per model the MiSTI.py:240 line the single run prints (rows outermost, then the sweeps in the order
+    given), nothing for a model the reference would have exited on."""
+    from .sweep import expand
+    plan = expand(a)
+    data, ids = _data_rows(a, rows)
+    t0 = time.time()
+    ok, eng = _sweep_models(a, inp, plan)
+    M, R = plan.n_model, data.shape[0]
+    llh = np.full((R, M), -np.inf)
+    status = np.full(M, 4, dtype=np.int32)
+    if eng is not None:
+        sel = np.where(ok)[0]
+        with eng:
+            res = eng.evaluate(plan.split[sel], plan.params[sel] if plan.n_param else None, data, band_bounds=plan.bounds[sel])
+        llh[:, sel] = res.llk.T
+        status[sel] = res.status
+    dt = time.time() - t0
+    # no line where the reference exits: SetModel's checks, or an infinite coalescent time (JAFSpectrum's PrintError)
+    shown = ok & (status != 3) & (status != 4)
+    for r in range(R):
+        for m in np.where(shown)[0]:
+            print(result_line(ids[r], float(plan.split[m]), split_grid_times(inp.times, plan.split[m]), inp.scaleTime, plan.mi[m],
+                              plan.params[m, :plan.k], float(llh[r, m])))
+    print()
+    table = np.where(shown[None, :], llh, -np.inf)
+    if np.isfinite(table).any():
+        r, m = np.unravel_index(np.argmax(np.where(np.isfinite(table), table, -np.inf)), table.shape)
+        print("sweep: best model", _model_text(plan, m, plan.names), "bs_id =", ids[r], "llh =", float(table[r, m]))
+    else:
+        print("sweep: no model has a finite llh")
+    if a.all_bs and R > 1:
+        _print_sweep_interval(plan, ids, table)
+    print("sweep: %d models x %d rows in one evaluation, %.3f s; %d models skipped (SetModel's checks or no finite coalescent time)"
+          % (M, R, dt, int((~shown).sum())))
+    return 0
+
+
+def sweep_solve(a, inp, rows):
+    """--grid-solve with --sweep: the boundary profiles ("when did migration start or stop") as ONE batched search - every
+    (row, model, start) triple is a start of misti_nm_solve_bounds, the best start kept per (row, model)."""
+    from .optimize import sweep_profile
+    from .sweep import expand
+    plan = expand(a)
+    data, ids = _data_rows(a, rows)
+    t0 = time.time()
+    ok, eng = _sweep_models(a, inp, plan)
+    M, R = plan.n_model, data.shape[0]
+    llh = np.full((R, M), -np.inf)
+    x = np.full((R, M, plan.k), np.nan)
+    status = np.zeros((R, M), dtype=np.int32)
+    sel = np.where(ok)[0]
+    if eng is not None:
+        with eng:
+            prof = sweep_profile(eng, [(plan.split[m], plan.bounds[m]) for m in sel], data, plan.starts, tol=a.tol, maxiter=1000)
+        llh[:, sel], x[:, sel], status[:, sel] = prof["llh"], prof["x"], prof["status"]
+    dt = time.time() - t0
+    for r in range(R):
+        for m in sel:
+            print(result_line(ids[r], float(plan.split[m]), split_grid_times(inp.times, plan.split[m]), inp.scaleTime, plan.mi[m], x[r, m],
+                              float(llh[r, m])))
+    print()
+    _print_sweep_interval(plan, ids, llh, x)
+    print("sweep: %d (row, model) pairs x %d starts in one search, %.3f s; %d models skipped (SetModel's checks), %d pairs ended on "
+          "the iteration cap, %d without a value" % (R * len(sel), plan.starts.shape[0], dt, M - len(sel),
+                                                     int((status[:, sel] == 2).sum()), int((~np.isfinite(llh[:, sel])).sum())))
+    return 0
+
+
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = grid_solve_error(a)
+    why = sweep_error(a) or grid_solve_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
@@ -296,6 +424,8 @@ def main(argv=None):
           "order as populations appear in the joint allele frequency spectrum.")
     fout = os.path.join(a.wd, a.fout) if a.fout else ""
     inp = mio.read_psmc(f1, f2, a.sdate, a.rd, units)
+    if a.sweep:
+        return sweep_solve(a, inp, rows) if a.grid_solve else sweep_eval(a, inp, rows)
     inp.divergenceTime = a.st
     if a.grid_solve:
         return grid_solve(a, inp, rows)

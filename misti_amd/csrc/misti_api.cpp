@@ -965,6 +965,9 @@ struct NmWork {
     int32_t* rows0 = nullptr;        // the per-slot row arrays row0 | row1 | row2 | row3 | ps_row, contiguous
     size_t rows_n = 0;
     bool whole = false;              // every split time of the rows path is an integer
+    // bounds path (misti_nm_solve_bounds, st.bounds_of set): every batch hands the engine its per-slot band bounds
+    int32_t* bnd0 = nullptr;         // the per-slot bound arrays bnd0 | bnd1 | bnd2 | bnd3 | ps_bnd, contiguous
+    size_t bnd_n = 0;
 };
 
 // Live starts up to which an iteration is speculative (misti_nm.hip): all 4 + N points of a start in one batch, as long as the
@@ -1032,13 +1035,18 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     // what the search knows about its own batches: one split time for every point (empty slots carry -1), distinct points.
     // The rows path knows less: its chains end at different splits (not one length), and every start from the same initial
     // values submits the same initial simplex - one chain for all of them, computed once up to the largest split (shared).
+    // The bounds path (a rows path with per-start band bounds) keeps exactly the rows path's set.  RUN_INTEGER_SPLITS speaks of
+    // split times alone: bounds are whole interval indices and never add a fractional interval (and the hint is verified on the
+    // device).  RUN_UNSHARED stays off: starts with the same initial values AND the same bounds still share their chains (the
+    // chain key holds the bounds).  RUN_ONE_LENGTH stays off: the splits differ, and so do the chain lengths.
     static const int hint_mask = [] { const char* e = getenv("MISTI_NM_HINTS"); return e ? atoi(e) : 7; }();       // diagnostic: which hints the search passes on
     const unsigned nm_hints = (rows ? (w.whole ? RUN_INTEGER_SPLITS : 0u)
                                     : ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH)) & (unsigned)hint_mask;
     // one engine batch of the search: its values against the one data row, or (rows path) each against its own row
-    auto eval = [&](int64_t n, const double* split, const double* params, const int32_t* row, double* llk) -> int {
+    // (bounds path: with each slot's own band bounds - NULL on the other paths)
+    auto eval = [&](int64_t n, const double* split, const double* params, const int32_t* row, const int32_t* bnd, double* llk) -> int {
         if (!rows) return run_dev(c, n, split, params, nullptr, 1, w.d_row, llk, nullptr, nullptr, nullptr, nullptr, nm_hints);
-        if (int r = run_dev(c, n, split, params, nullptr, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints)) return r;
+        if (int r = run_dev(c, n, split, params, bnd, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints)) return r;
         HIP_TRY(misti::launch_llk_rows(n, w.rjafs, w.rstatus, row, w.table, w.consts, llk, c->unfolded, sm));
         return 0;
     };
@@ -1046,8 +1054,9 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
     HIP_TRY(hipMemsetAsync(st.split1, 0xBF, S * sizeof(double), sm));          // all-0xBF bytes: a negative double = "no point in this slot"
     if (rows) HIP_TRY(hipMemsetAsync(w.rows0, 0, w.rows_n * sizeof(int32_t), sm));   // row 0 in every slot nothing has written yet
+    if (w.bnd_n) HIP_TRY(hipMemsetAsync(w.bnd0, 0, w.bnd_n * sizeof(int32_t), sm));  // and all-zero bounds (what put_none writes)
     HIP_TRY(misti::launch_nm_init(st, w.d_starts, sm));
-    if (int r = eval((int64_t)(S * V), st.split0, st.sim, st.row0, w.llk0)) return r;
+    if (int r = eval((int64_t)(S * V), st.split0, st.sim, st.row0, st.bnd0, w.llk0)) return r;
     int cur = 0;
     st.idx_next = w.idx[cur]; st.count_next = cnt + cur;
     HIP_TRY(misti::launch_nm_begin(st, w.llk0, sm));
@@ -1082,7 +1091,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             // of the NEXT iteration and drops the count of live starts into the host's pinned word (nm_spec_step_kernel: the live
             // starts of a speculative iteration fit one workgroup); only the first speculative iteration launches a points kernel
             if (!spec_primed) { HIP_TRY(misti::launch_nm_spec_points(st, bound, sm)); spec_primed = true; }
-            if (int r = eval(bound * K, st.ps_split, st.ps, st.ps_row, w.llk_spec)) return r;
+            if (int r = eval(bound * K, st.ps_split, st.ps, st.ps_row, st.ps_bnd, w.llk_spec)) return r;
             // (no memsets here: the points step zeroes the next slot counter, and the reflection-split array is only read by the
             //  three-batch path, which a search never returns to - the number of live starts only falls)
             misti::NmState nx = st;
@@ -1090,11 +1099,11 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             HIP_TRY(misti::launch_nm_spec_step(st, nx, bound, w.llk_spec, (int32_t*)&live_host[slot], sm));
             ++spec_iters;
         } else {
-            if (int r = eval(bound, st.split1, st.p1, st.row1, w.llk1)) return r;
+            if (int r = eval(bound, st.split1, st.p1, st.row1, st.bnd1, w.llk1)) return r;
             HIP_TRY(misti::launch_nm_reflect(st, bound, w.llk1, sm));
-            if (int r = eval(bound, st.split2, st.p2, st.row2, w.llk2)) return r;
+            if (int r = eval(bound, st.split2, st.p2, st.row2, st.bnd2, w.llk2)) return r;
             HIP_TRY(misti::launch_nm_accept(st, bound, w.llk2, sm));
-            if (int r = eval(bound * N, st.split3, st.p3, st.row3, w.llk3)) return r;
+            if (int r = eval(bound * N, st.split3, st.p3, st.row3, st.bnd3, w.llk3)) return r;
             HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
             HIP_TRY(hipMemsetAsync(st.split1, 0xBF, (size_t)bound * sizeof(double), sm));
             HIP_TRY(misti::launch_nm_finish(st, bound, w.llk3, sm));
@@ -1146,9 +1155,15 @@ int misti_nm_solve(misti_ctx* c, int64_t n_start, const double* starts, double s
     return 0;
 }
 
-int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
-                        int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
-                        double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+}  // extern "C"
+
+namespace {
+
+// misti_nm_solve_rows (band_bounds NULL) and misti_nm_solve_bounds: one implementation.  Without bounds nothing of the bounds path
+// is allocated or written, and the search runs exactly the rows path's instructions.
+int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                       const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
     // every argument is checked before the first HIP call
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
@@ -1172,8 +1187,12 @@ int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, con
     const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
     const size_t M = S * V > cap * K ? S * V : cap * K;                         // the largest batch of the search
     const size_t rows_n = S * V + 2 * S + S * N + cap * K;                       // row0 | row1 | row2 | row3 | ps_row
+    // bounds path: the per-start bound sets, then one bound set per slot of every batch (none for a model without bands: the
+    // engine has nothing to apply them to)
+    const size_t NB2 = band_bounds ? 2 * (size_t)c->dm.n_band : 0;
+    const size_t bnd_n = NB2 * (S * V + 2 * S + S * N + cap * K);               // bnd0 | bnd1 | bnd2 | bnd3 | ps_bnd
     NmWork w;
-    if (int r = nm_prepare(c, n_start, w, S + R * 8 + R + M * 7, S + rows_n + M)) return r;
+    if (int r = nm_prepare(c, n_start, w, S + R * 8 + R + M * 7, S + rows_n + M + S * NB2 + bnd_n)) return r;
     misti::NmState& st = w.st;
     double* d = w.extra_f64;
     double* d_split = d; d += S;
@@ -1184,13 +1203,21 @@ int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, con
     int32_t* d_rowof = q; q += S;
     w.rows0 = q; w.rows_n = rows_n;
     st.row0 = q; q += S * V; st.row1 = q; q += S; st.row2 = q; q += S; st.row3 = q; q += S * N; st.ps_row = q; q += cap * K;
-    w.rstatus = q;
+    w.rstatus = q; q += M;
+    int32_t* d_bounds = nullptr;
+    if (NB2) {
+        d_bounds = q; q += S * NB2;
+        w.bnd0 = q; w.bnd_n = bnd_n;
+        st.bnd0 = q; q += S * V * NB2; st.bnd1 = q; q += S * NB2; st.bnd2 = q; q += S * NB2; st.bnd3 = q; q += S * N * NB2; st.ps_bnd = q;
+        st.bounds_of = d_bounds; st.nb2 = (int)NB2;
+    }
     st.split_of = d_split; st.row_of = d_rowof;
     w.table = d_table; w.consts = d_consts; w.whole = whole;
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_split, split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_rowof, rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_table, jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(misti::launch_llh_const(n_rep, d_table, d_consts, c->unfolded, sm));          // once per call, every row
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
@@ -1202,6 +1229,25 @@ int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, con
     if (status) HIP_TRY(hipMemcpyAsync(status, st.shrunk, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     HIP_TRY(hipStreamSynchronize(sm));
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                        int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                        double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    return nm_solve_rows_impl(c, n_start, starts, split_times, rows, nullptr, n_rep, jsfs, xatol, fatol, maxiter, x, llh, nit, nfev, status);
+}
+
+int misti_nm_solve_bounds(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                          const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                          double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    // bounds that break SetModel's checks are no argument error: the engine gives that start's points status MISTI_BAD_STRUCTURE
+    // (llh = -inf), as it does for an invalid split; a model without bands has nothing to apply them to (as misti_eval_batch)
+    return nm_solve_rows_impl(c, n_start, starts, split_times, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs,
+                              xatol, fatol, maxiter, x, llh, nit, nfev, status);
 }
 
 int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,

@@ -115,6 +115,8 @@ struct NmState {
     double split;           // the split time every point is evaluated at (unless split_of is set)
     const double* split_of; // [S] or NULL: the split time of each start's points (misti_nm_solve_rows); NULL: `split` for all
     const int32_t* row_of;  // [S] or NULL: the replicate row of each start's points; set together with split_of
+    const int32_t* bounds_of;   // [S][nb2] or NULL: the band bounds of each start's points (misti_nm_solve_bounds); only with row_of
+    int nb2;                // 2 n_band: int32 per bound set (bounds_of set)
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)
@@ -138,10 +140,15 @@ struct NmState {
     int32_t* row1;          // [S]       is set; empty slots carry row 0)
     int32_t* row2;          // [S]
     int32_t* row3;          // [S * N]
+    int32_t* bnd0;          // [S * V][nb2]  band bounds per engine candidate of the four batches, beside row0..3 (NULL unless bounds_of
+    int32_t* bnd1;          // [S][nb2]      is set; empty slots carry zeros)
+    int32_t* bnd2;          // [S][nb2]
+    int32_t* bnd3;          // [S * N][nb2]
     // speculative iterations (few live starts: latency-bound): every point SciPy COULD ask for in the iteration, one batch
     double* ps;             // [spec_cap][4 + N][N]  reflection, expansion, outside / inside contraction, the N shrunk vertices
     double* ps_split;       // [spec_cap * (4 + N)]
     int32_t* ps_row;        // [spec_cap * (4 + N)]  or NULL (row_of unset)
+    int32_t* ps_bnd;        // [spec_cap * (4 + N)][nb2]  or NULL (bounds_of unset)
     int64_t spec_cap;       // live starts up to which an iteration is speculative
     const int32_t* idx_cur; // [S] slot -> start of the iteration in progress
     const int32_t* count_cur;   // [1] its number of live starts

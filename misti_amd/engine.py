@@ -276,6 +276,35 @@ class Engine:
         return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
                     speculative_iterations=int(spec.value))
 
+    def nm_solve_bounds(self, starts, split_times, rows, jsfs, band_bounds, tol=1e-4, maxiter=1000):
+        """``misti_nm_solve_bounds``: ``nm_solve_rows`` with the band bounds PER START as well - start s is SciPy's Nelder-Mead at
+        ``split_times[s]`` against ``jsfs[rows[s]]`` with the model's bands starting and ending at ``band_bounds[s]``
+        (``[n_start][n_band][2]`` ints, ``end == -1``: the start's split index), all starts in one batched search (the boundary
+        profiles "when did migration start or stop": one ``Engine`` per bound set and one ``Solve`` per model otherwise).  Bounds
+        that break SetModel's checks give that start ``llh = -inf``.  ``band_bounds=None`` is ``nm_solve_rows``.
+        Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` on an engine whose
+        bands carry ``band_bounds[s]``, bit for bit."""
+        st = _f64(starts, (-1, self.n_param))
+        S = st.shape[0]
+        split = _f64(split_times, (S,))
+        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
+        table = _f64(jsfs, (-1, 8))
+        bb = None
+        if band_bounds is not None and self.n_band:
+            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(S, self.n_band, 2)
+        x = np.empty((S, self.n_param))
+        llh = np.empty(S)
+        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        _lib.check(self._lib.misti_nm_solve_bounds(self._ctx, S, ptr(st), ptr(split), ptr(row), ptr(bb), table.shape[0], ptr(table), float(tol),
+                                                   float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
+        stats = (C.c_int64 * 2)()
+        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
+        spec = C.c_int64(0)
+        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
+        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
+                    speculative_iterations=int(spec.value))
+
     def basinhopping(self, starts, split_time, jsfs_row, rngs, niter=100, T=0.5, stepsize=0.5, interval=50, target_accept_rate=0.5,
                      stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
         """``misti_basinhopping``: ``scipy.optimize.basinhopping(-JAFSLikelihood, x0, niter, T, stepsize,

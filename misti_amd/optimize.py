@@ -281,10 +281,18 @@ def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter
     Returns dict(x[R][P][N], llh[R][P], nit / nfev / status / start[R][P], and the search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_values, dtype=float).reshape(-1)
+    return _best_start_profile(lambda r_of, p_of, st: engine.nm_solve_rows(st, splits[p_of], r_of, rows, tol=tol, maxiter=maxiter),
+                               rows.shape[0], splits.size, starts)
+
+
+def _best_start_profile(search, R, P, starts):
+    """What bootstrap_profile and sweep_profile share: ``search(r_of, p_of, starts)`` runs ONE batched search over every
+    (row, point, start) triple (row outermost, start innermost; ``r_of`` int32), then per (row, point) the best start is kept - the
+    first maximum, i.e. the lowest start index on ties; NaN never wins."""
     starts = np.atleast_2d(np.asarray(starts, dtype=float))
-    R, P, (Q, N) = rows.shape[0], splits.size, starts.shape
+    Q = starts.shape[0]
     r_of, p_of, q_of = (a.ravel() for a in np.meshgrid(np.arange(R), np.arange(P), np.arange(Q), indexing="ij"))
-    res = engine.nm_solve_rows(starts[q_of], splits[p_of], r_of.astype(np.int32), rows, tol=tol, maxiter=maxiter)
+    res = search(r_of.astype(np.int32), p_of, starts[q_of])
     llh = res["llh"].reshape(R, P, Q)
     best = np.argmax(np.where(np.isnan(llh), -np.inf, llh), axis=2)              # first maximum: the lowest start index
     pick = lambda a: np.take_along_axis(a.reshape(R, P, Q, *a.shape[1:]), best.reshape(R, P, 1, *([1] * (a.ndim - 1))), axis=2)[:, :, 0]
@@ -321,4 +329,41 @@ def bootstrap_profile_interval(llh, split_values, x=None):
     if a.size >= 2:
         with np.errstate(invalid="ignore"):               # every replicate on one split: sem = 0, the interval is (nan, nan) as there
             out["interval"] = tuple(float(v) for v in stats.t.interval(0.975, len(a) - 1, loc=np.mean(a), scale=stats.sem(a)))
+    return out
+
+
+def sweep_profile(engine, models, jsfs_rows, starts, tol=1e-4, maxiter=1000):
+    """``bootstrap_profile`` with a MODEL axis instead of a split axis: ``models`` is a list of ``(split, band_bounds[n_band][2])``
+    (end -1: the model's split index) - the boundary profiles "when did migration start or stop" (the test.bs scripts' Solve per
+    (replicate, split) pair with a loop over a band boundary added, one Engine per boundary there) in ONE ``misti_nm_solve_bounds``
+    call: every (row, model, start) triple is a start of the batched search.  ``jsfs_rows`` is ``[R][8]``, ``starts`` ``[Q][N]``.
+    Per (row, model) the best start is kept (ties: the lowest start index).
+    Returns dict(x[R][M][N], llh[R][M], nit / nfev / status / start[R][M], and the search's work counters)."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.array([float(m[0]) for m in models], dtype=float)
+    bounds = np.array([np.asarray(m[1], dtype=np.int32).reshape(-1, 2) for m in models], dtype=np.int32).reshape(len(models), -1, 2)
+    return _best_start_profile(lambda r_of, m_of, st: engine.nm_solve_bounds(st, splits[m_of], r_of, rows, bounds[m_of], tol=tol, maxiter=maxiter),
+                               rows.shape[0], splits.size, starts)
+
+
+def sweep_interval(llh, values, x=None):
+    """The ``test.bs/bs_conf_int.ipynb`` reduction of a sweep table ``llh[R][M]`` (row 0 the data, rows 1.. the bootstrap replicates;
+    model m has the value ``values[m][v]`` of swept variable v) for every swept variable: per row the FIRST model with the largest
+    llh, row 0 reported on its own, and over rows 1..R-1 the mean and the 97.5 % t-interval of that model's value of each variable.
+    Per variable exactly ``bootstrap_profile_interval`` with the variable's values as the split axis (same helper, same exclusions:
+    a row without a finite llh is left out and counted) - so with only the split swept it IS ``bootstrap_profile_interval``.
+    Returns dict(best_model[R] (-1: none), data_model / data_llh / data_x (None: none), variables: one
+    ``bootstrap_profile_interval`` dict per variable (its ``best_split`` / ``data_split`` are that variable's values), n_boot, n_excluded)."""
+    llh = np.atleast_2d(np.asarray(llh, dtype=float))
+    values = np.asarray(values, dtype=float).reshape(llh.shape[1], -1)
+    finite = np.isfinite(llh)
+    has = finite.any(axis=1)
+    idx = np.argmax(np.where(finite, llh, -np.inf), axis=1)
+    out = dict(best_model=np.where(has, idx, -1), data_model=None, data_llh=None, data_x=None,
+               variables=[bootstrap_profile_interval(llh, values[:, v], x) for v in range(values.shape[1])],
+               n_boot=int(has[1:].sum()), n_excluded=int((~has[1:]).sum()))
+    if has[0]:
+        out["data_model"], out["data_llh"] = int(idx[0]), float(llh[0, idx[0]])
+        if x is not None:
+            out["data_x"] = np.asarray(x)[0, idx[0]]
     return out

@@ -2,7 +2,8 @@
 """Bitwise A/B of two builds of the library (run on the GPU box).
 
     python -m misti_amd.build --out /tmp/variant.so -DSOMETHING        # a variant build
-    MISTI_LIB_AB=1 MISTI_LIB=/tmp/variant.so python tools/ab_compare.py dump a.npz    # 300 random models + configs 2 and 3: llk, status, rates, spectra
+    MISTI_LIB_AB=1 MISTI_LIB=/tmp/variant.so python tools/ab_compare.py dump a.npz    # 300 random models + configs 2 and 3: llk, status, rates, spectra;
+                                                                       # then misti_nm_solve, misti_nm_solve_rows and misti_basinhopping on fixed starts
     python tools/ab_compare.py dump b.npz                              # the in-tree build
     python tools/ab_compare.py cmp a.npz b.npz                         # arrays that differ in any bit
 
@@ -34,8 +35,41 @@ def dump(path):
         with Engine(w.times, w.lh, **w.engine_kwargs()) as e:
             r = e.evaluate(w.split_time[:n], w.params[:n], w.jsfs, want_lc=True)
         out[name + "_llk"] = r.llk; out[name + "_st"] = r.status; out[name + "_lc"] = r.lc; out[name + "_j"] = r.jafs
+    out.update(searches())
     np.savez(path, **out)
     print("saved", len(out), "arrays")
+
+
+def searches():
+    """misti_nm_solve, misti_nm_solve_rows and misti_basinhopping on a fixed set of starts: config 3's model with its band ends
+    following the split, a seeded bootstrap table and a few splits (AB_SEARCHES=0 leaves them out)."""
+    import random
+    from misti_amd import io as mio, synth, workloads
+    from misti_amd.engine import Engine, truth_spectrum
+    out = {}
+    if os.environ.get("AB_SEARCHES", "1") == "0":
+        return out
+    w = workloads.config3(lambda *a: truth_spectrum(*a), n_start=4)
+    kw = w.engine_kwargs()
+    kw["bands"] = [(p, s, -1, v, k) for p, s, e, v, k in w.bands]
+    table = np.array(mio.bootstrap_table(synth.chunk_rows(w.jsfs[0], 20), 4, random.Random(3)), dtype=np.float64)
+    start = np.array([b[3] for b in kw["bands"]])
+    starts = np.vstack([start, [0.3, 0.02], [0.05, 0.5], start * 2])
+    splits = np.array([62.0, 63.5, 64.0, 65.0, 9.0])
+    with Engine(w.times, w.lh, **kw) as e:
+        for i, st in enumerate((64.0, 63.5)):
+            r = e.nm_solve(starts, st, table[0])
+            for f in ("x", "llh", "nit", "nfev", "status"):
+                out["nm%d_%s" % (i, f)] = r[f]
+        rows = np.array([0, 1, 2, 3, 4], dtype=np.int32)
+        r = e.nm_solve_rows(np.tile(start, (splits.size, 1)), splits, rows, table, maxiter=300)
+        for f in ("x", "llh", "nit", "nfev", "status"):
+            out["rows_%s" % f] = r[f]
+        r = e.basinhopping(starts[:2], 64.0, table[0], [11, 12], niter=3, nm_maxiter=100)
+        for f, v in r.items():
+            if isinstance(v, np.ndarray):
+                out["bh_%s" % f] = v
+    return out
 
 
 def cmp(pa, pb):
