@@ -174,6 +174,31 @@ int misti_eval_batch_dev(misti_ctx* ctx, int64_t n_cand,
                          int64_t n_rep, const double* d_jsfs,
                          double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status);
 
+/* misti_eval_batch / misti_eval_batch_dev with a TIME PER CANDIDATE for every -pu pulse of the model.  Replaces the pulse-date scans
+ * "when did the admixture pulse happen" - the GNU-parallel recipe with `-pu 2 {t} {f} 0` in the place of a band, one MiSTI.py
+ * process (one MigrationInference, SetModel :259-279) per (st, t, fraction) grid point - with ONE batch: pulse times of different
+ * candidates travel together, as split times and band bounds do.
+ *   pulse_times  [n_cand][n_pulse] int32 or NULL   pulse_times[c][p] replaces pulses[p].time for candidate c: an interval index
+ *                on the candidate's OWN grid (after the extra interval of a fractional split has been inserted, as band starts).
+ *                NULL, or a model without pulses: exactly misti_eval_batch (misti_eval_batch_dev) - the same launches and bits.
+ *                Checked per candidate as SetModel and misti_create check the model's: time >= sample date, time < numT + 1,
+ *                no two pulses of the candidate at one time; a candidate that breaks one gets MISTI_BAD_STRUCTURE and -inf, its
+ *                neighbours are unaffected.  A time at or beyond the candidate's split index is valid and never applied (the
+ *                reference's loops run over t < splitT).  Candidates that differ in a pulse time never share a lambda-correction
+ *                chain (the pulse acts on the pair state, CorrectLambdas :315-323); candidates with equal times still do.
+ *   other arguments as misti_eval_batch (misti_eval_batch_dev).
+ * Per-candidate pulse times exist on these two entry points and on misti_nm_solve_pulses only: the lanes (misti_lanes_*), the
+ * device-list (misti_multi_*) and forward-map (misti_forward_rates*) entry points apply the model's own times, and the iterates of
+ * the solver trace are those of the chain's representative as before. */
+int misti_eval_batch_pulses(misti_ctx* ctx, int64_t n_cand,
+                            const double* split_time, const double* params, const int32_t* band_bounds, const int32_t* pulse_times,
+                            int64_t n_rep, const double* jsfs,
+                            double* llk, double* jafs, double* lc, double* pr, int32_t* status);
+int misti_eval_batch_pulses_dev(misti_ctx* ctx, int64_t n_cand,
+                                const double* d_split_time, const double* d_params, const int32_t* d_band_bounds,
+                                const int32_t* d_pulse_times, int64_t n_rep, const double* d_jsfs,
+                                double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status);
+
 /* What the CALLER knows about the batches it issues on this context from now on (0 clears).  A batch is four launches on one stream and,
  * with many contexts' batches in flight, every launch boundary costs a round of the queue scheduler (~0.4 ms measured with 20 busy
  * queues): the launch that only exists for fractional split times is not made when the caller says there are none.
@@ -260,6 +285,18 @@ int misti_nm_solve_rows(misti_ctx* ctx, int64_t n_start, const double* starts, c
  *   other arguments, errors, synchronisation and statistics as misti_nm_solve_rows. */
 int misti_nm_solve_bounds(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                          double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
+
+/* misti_nm_solve_bounds with pulse times PER START as well (as misti_eval_batch_pulses' pulse_times).  Replaces the pulse-date
+ * profile with an optimised fraction - `-pu 2 {t} f 1` under a loop over t, one Engine and one Solve per time there - with ONE
+ * batched search.  Start s returns exactly what misti_nm_solve(starts[s], split_times[s], jsfs + 8 rows[s]) returns on a context
+ * whose model carries band_bounds[s] and pulse_times[s].
+ *   pulse_times  [n_start][n_pulse] or NULL   NULL: exactly misti_nm_solve_bounds.  Ignored when the model has no pulse.  Times
+ *                that break the checks are no argument error: that start gets llh = -inf, its neighbours are unaffected.
+ *   other arguments, errors (MISTI_E_ARG before anything touches the device), synchronisation and statistics as misti_nm_solve_rows. */
+int misti_nm_solve_pulses(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                          const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                          double xatol, double fatol, int32_t maxiter,
                           double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
 /* Batched basin hopping: scipy.optimize.basinhopping(func, x0, niter, T, stepsize, minimizer_kwargs=dict(method='Nelder-Mead'),

@@ -33,6 +33,11 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               parameter is optimised) the time
                               variables make the models, the rate variables of optimised bands the starts, and every (row, model)
                               pair is optimised in ONE batched search (misti_nm_solve_bounds)
+    --sweep-pu NAME V1 V2 ... a sweep variable of the pulses (repeatable): {NAME} stands in the time field or in the fraction field
+                              of -pu - `-pu 2 {t} {f} 0`, "when did the admixture pulse happen".  The models are the product of the
+                              --sweep variables, then the --sweep-pu variables (last innermost); every batch carries per-candidate
+                              pulse times (misti_eval_batch_pulses; with --grid-solve misti_nm_solve_pulses, the fractions of an
+                              optimised pulse being the starts)
 """
 from __future__ import annotations
 
@@ -88,6 +93,8 @@ def build_parser():
                    help="with --grid-st / --all-bs: optimise every (replicate, split) pair as the test.bs loops do, in one batched search")
     p.add_argument("--sweep", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="the GNU-parallel recipe's `::: NAME V1 V2 ...`: {NAME} in the split time or in -mi start / end / rate fields")
+    p.add_argument("--sweep-pu", nargs="+", action="append", default=[], metavar=("NAME", "V"),
+                   help="a sweep variable of the pulses: {NAME} in the time field or in the fraction field of -pu")
     return p
 
 
@@ -95,11 +102,11 @@ def grid_solve_error(a):
     """Why ``--grid-solve`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
     if not a.grid_solve:
         return None
-    if not (a.grid_st or a.all_bs or a.sweep):
+    if not (a.grid_st or a.all_bs or a.sweep or a.sweep_pu):
         return "--grid-solve optimises every (replicate, split) pair: it needs --grid-st and/or --all-bs"
     if a.gpus > 1 or a.devices:
         return "--grid-solve runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
-    if not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
+    if not (a.sweep or a.sweep_pu) and not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
         return "--grid-solve needs at least one optimised parameter (-mi ... 1 or -pu ... 1)"
     return None
 
@@ -261,17 +268,17 @@ def grid_solve(a, inp, rows):
 
 def _sweep_models(a, inp, plan):
     """Which models of the sweep the reference would have run (SetModel's checks; it exits in PrintError for the others), and the
-    Engine for them: band records with the bounds of the first of them (every batch passes its own)."""
+    Engine for them: band and pulse records with the bounds and times of the first of them (every batch passes its own)."""
     from .sweep import structure_error
     pops = [b[0] for b in plan.bands]
     numT = len(inp.lambdas)
-    ok = np.array([structure_error(plan.split[m], plan.bounds[m], pops, inp.sampleDateDiscr, numT) is None for m in range(plan.n_model)],
-                  dtype=bool)
+    ok = np.array([structure_error(plan.split[m], plan.bounds[m], pops, inp.sampleDateDiscr, numT, plan.pulse_times[m], plan.pulse_values[m])
+                   is None for m in range(plan.n_model)], dtype=bool)
     if not ok.any():
         return ok, None
     first = int(np.argmax(ok))
     flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
-    eng = Engine(inp.times, inp.lambdas, plan.engine_bands(first), plan.pulses, n_param=plan.n_param, sample_date=inp.sampleDateDiscr,
+    eng = Engine(inp.times, inp.lambdas, plan.engine_bands(first), plan.engine_pulses(first), n_param=plan.n_param, sample_date=inp.sampleDateDiscr,
                  mixture_th=a.mth, device=a.device, **flags)
     return ok, eng
 
@@ -321,7 +328,8 @@ def sweep_eval(a, inp, rows):
     if eng is not None:
         sel = np.where(ok)[0]
         with eng:
-            res = eng.evaluate(plan.split[sel], plan.params[sel] if plan.n_param else None, data, band_bounds=plan.bounds[sel])
+            res = eng.evaluate(plan.split[sel], plan.params[sel] if plan.n_param else None, data, band_bounds=plan.bounds[sel],
+                               pulse_times=plan.pulse_times[sel] if plan.pulse_swept else None)
         llh[:, sel] = res.llk.T
         status[sel] = res.status
     dt = time.time() - t0
@@ -347,7 +355,8 @@ def sweep_eval(a, inp, rows):
 
 def sweep_solve(a, inp, rows):
     """--grid-solve with --sweep: the boundary profiles ("when did migration start or stop") as ONE batched search - every
-    (row, model, start) triple is a start of misti_nm_solve_bounds, the best start kept per (row, model)."""
+    (row, model, start) triple is a start of misti_nm_solve_bounds (misti_nm_solve_pulses when a pulse time is swept), the best
+    start kept per (row, model)."""
     from .optimize import sweep_profile
     from .sweep import expand
     plan = expand(a)
@@ -361,7 +370,8 @@ def sweep_solve(a, inp, rows):
     sel = np.where(ok)[0]
     if eng is not None:
         with eng:
-            prof = sweep_profile(eng, [(plan.split[m], plan.bounds[m]) for m in sel], data, plan.starts, tol=a.tol, maxiter=1000)
+            models = [(plan.split[m], plan.bounds[m]) + ((plan.pulse_times[m],) if plan.pulse_swept else ()) for m in sel]
+            prof = sweep_profile(eng, models, data, plan.starts, tol=a.tol, maxiter=1000)
         llh[:, sel], x[:, sel], status[:, sel] = prof["llh"], prof["x"], prof["status"]
     dt = time.time() - t0
     for r in range(R):
@@ -424,7 +434,7 @@ def main(argv=None):
           "order as populations appear in the joint allele frequency spectrum.")
     fout = os.path.join(a.wd, a.fout) if a.fout else ""
     inp = mio.read_psmc(f1, f2, a.sdate, a.rd, units)
-    if a.sweep:
+    if a.sweep or a.sweep_pu:
         return sweep_solve(a, inp, rows) if a.grid_solve else sweep_eval(a, inp, rows)
     inp.divergenceTime = a.st
     if a.grid_solve:

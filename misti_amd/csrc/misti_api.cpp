@@ -98,7 +98,7 @@ struct misti_ctx {
     size_t table_clean[2] = {0, 0};     // table size each set is known to be clean for (0: not clean)
     DevBuf ws_trunk;                    // per chain: 44-state records before every interval (trunk kernel -> kernel 2)
     DevBuf ws_chain_f64, ws_chain_i32;  // chain buffers (kernel 1 -> kernel 2) and the chain table
-    DevBuf st_split, st_params, st_bounds, st_jsfs, st_llk, st_jafs, st_lc, st_pr, st_status;   // staging for the host-buffer form
+    DevBuf st_split, st_params, st_bounds, st_pulses, st_jsfs, st_llk, st_jafs, st_lc, st_pr, st_status;   // staging for the host-buffer form
     PinBuf pin_in, pin_out;             // pinned staging of misti_eval_batch: inputs packed, outputs packed
     std::vector<char> heap_in, heap_out;   // pageable staging of the indexed form beyond PIN_STAGE_MAX (kept here: they outlive an error return's drain)
     bool trace = false;                 // solver trace (misti_enable_solver_trace)
@@ -271,7 +271,7 @@ int record_end(misti_ctx* c, int which, hipEvent_t a, hipEvent_t b) {
 //   RUN_ONE_LENGTH      every chain has the same number of intervals: the chains need no sorting by length
 enum : unsigned { RUN_INTEGER_SPLITS = 1u, RUN_UNSHARED = 2u, RUN_ONE_LENGTH = 4u };
 int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const double* d_params, const int32_t* d_bounds, int64_t n_rep, const double* d_jsfs,
-                 double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status, unsigned hints) {
+                 double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status, unsigned hints, const int32_t* d_pulses) {
     if (n_cand < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative batch size");
     if (n_cand == 0) return 0;
     if (!d_split) return fail(MISTI_E_ARG, "split_time is NULL");
@@ -328,6 +328,7 @@ int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const doub
         cb.hint = c->hint_dev;
         cb.simd_load = c->tune.pairing ? pair_table(c->device) : nullptr;
         cb.bounds = c->dm.n_band > 0 ? d_bounds : nullptr;
+        cb.pulse_times = c->dm.n_pulse > 0 ? d_pulses : nullptr;
         cb.integer_splits = (hints & RUN_INTEGER_SPLITS) ? 1 : 0;
         cb.post_lam = nullptr;
         cb.post_word = nullptr;
@@ -480,8 +481,8 @@ int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const doub
 // know the batch's stream) while the next batch's set-up rewrites the chain buffers they read.  So: on any failure the side stream is
 // drained before the error is reported.
 int run_dev(misti_ctx* c, int64_t n_cand, const double* d_split, const double* d_params, const int32_t* d_bounds, int64_t n_rep, const double* d_jsfs,
-            double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status, unsigned hints = 0) {
-    const int r = run_dev_impl(c, n_cand, d_split, d_params, d_bounds, n_rep, d_jsfs, d_llk, d_jafs, d_lc, d_pr, d_status, hints);
+            double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status, unsigned hints = 0, const int32_t* d_pulses = nullptr) {
+    const int r = run_dev_impl(c, n_cand, d_split, d_params, d_bounds, n_rep, d_jsfs, d_llk, d_jafs, d_lc, d_pr, d_status, hints, d_pulses);
     if (r != 0 && c->side_stream) {
         const std::string why = g_err;
         (void)hipStreamSynchronize(c->side_stream);
@@ -675,7 +676,7 @@ int misti_destroy(misti_ctx* c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     (void)hipGetLastError();
     for (auto* b : {&c->model_f64, &c->model_i32, &c->consts, &c->ws_jafs, &c->ws_status, &c->ws_chain_f64, &c->ws_chain_i32, &c->ws_order, &c->ws_diag, &c->ws_trunk, &c->ws_solver, &c->ws_iters, &c->ws_post,
-                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32})
+                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32})
         b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -733,6 +734,13 @@ int misti_eval_batch_dev(misti_ctx* c, int64_t n_cand, const double* d_split, co
     return run_dev(c, n_cand, d_split, d_params, d_bounds, n_rep, d_jsfs, d_llk, d_jafs, d_lc, d_pr, d_status);
 }
 
+int misti_eval_batch_pulses_dev(misti_ctx* c, int64_t n_cand, const double* d_split, const double* d_params, const int32_t* d_bounds,
+                                const int32_t* d_pulse_times, int64_t n_rep, const double* d_jsfs, double* d_llk, double* d_jafs, double* d_lc,
+                                double* d_pr, int32_t* d_status) {
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    return run_dev(c, n_cand, d_split, d_params, d_bounds, n_rep, d_jsfs, d_llk, d_jafs, d_lc, d_pr, d_status, 0u, d_pulse_times);
+}
+
 int misti_llk_dev(misti_ctx* c, int64_t n_cand, const double* d_jafs, const int32_t* d_status, int64_t n_rep, const double* d_jsfs, double* d_llk) {
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_cand < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative batch size");
@@ -764,7 +772,8 @@ int misti_argmax_dev(misti_ctx* c, int64_t n_cand, int64_t n_rep, const double* 
 
 namespace {
 int eval_batch_host(misti_ctx* c, int64_t n_cand, const double* split, const double* params, const int32_t* band_bounds, int64_t n_rep, const double* jsfs,
-                    double* llk, double* jafs, double* lc, double* pr, int32_t* status, const int64_t* idx = nullptr);
+                    double* llk, double* jafs, double* lc, double* pr, int32_t* status, const int64_t* idx = nullptr,
+                    const int32_t* pulse_times = nullptr);
 int eval_batch_drained(misti_ctx* c, int r) {
     // An error between the first asynchronous copy and the final wait leaves DMAs reading the context's pinned input block or
     // writing its pinned output block: the next call would overwrite what they read.  Drain the stream before reporting.
@@ -787,6 +796,13 @@ int misti_eval_batch(misti_ctx* c, int64_t n_cand, const double* split, const do
     return eval_batch_drained(c, eval_batch_host(c, n_cand, split, params, band_bounds, n_rep, jsfs, llk, jafs, lc, pr, status));
 }
 
+// misti_eval_batch with a time per candidate for every pulse of the model; NULL (or a model without pulses) is misti_eval_batch.
+int misti_eval_batch_pulses(misti_ctx* c, int64_t n_cand, const double* split, const double* params, const int32_t* band_bounds,
+                            const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double* llk, double* jafs, double* lc, double* pr,
+                            int32_t* status) {
+    return eval_batch_drained(c, eval_batch_host(c, n_cand, split, params, band_bounds, n_rep, jsfs, llk, jafs, lc, pr, status, nullptr, pulse_times));
+}
+
 // misti_eval_batch on the rows idx[0 .. n) of the caller's arrays: inputs are GATHERED from those rows into the context's staging
 // block and every output row i is SCATTERED to row idx[i] - what a context of misti_multi_eval_batch does with its shard of a
 // batch (misti_multi.cpp), without a staging copy of the shard in between.  jsfs is shared (not indexed).  Not part of the public ABI.
@@ -807,7 +823,7 @@ int misti_eval_batch_indexed_(misti_ctx* c, int64_t n, const int64_t* idx, const
 namespace {
 
 int eval_batch_host(misti_ctx* c, int64_t n_cand, const double* split, const double* params, const int32_t* band_bounds, int64_t n_rep, const double* jsfs,
-                    double* llk, double* jafs, double* lc, double* pr, int32_t* status, const int64_t* idx) {
+                    double* llk, double* jafs, double* lc, double* pr, int32_t* status, const int64_t* idx, const int32_t* pulse_times) {
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_cand < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative batch size");
     if (n_cand == 0) return 0;
@@ -818,12 +834,14 @@ int eval_batch_host(misti_ctx* c, int64_t n_cand, const double* split, const dou
     HIP_TRY(hipSetDevice(c->device));
     const size_t nc = (size_t)n_cand, nr = (size_t)n_rep;
     const bool with_bounds = band_bounds && c->dm.n_band > 0;
+    const bool with_pulses = pulse_times && c->dm.n_pulse > 0;
+    const size_t b_pulses = with_pulses ? nc * (size_t)c->dm.n_pulse * sizeof(int32_t) : 0;
     const size_t b_split = nc * sizeof(double), b_par = P > 0 ? nc * P * sizeof(double) : 0;
     const size_t b_bounds = with_bounds ? nc * 2 * (size_t)c->dm.n_band * sizeof(int32_t) : 0, b_jsfs = nr * 8 * sizeof(double);
     const size_t lc_n = nc * (size_t)(numT + 1) * 2, pr_n = nc * (size_t)(numT + 2) * 6;
     const size_t b_llk = nr ? nc * nr * sizeof(double) : 0, b_jafs = jafs ? nc * 7 * sizeof(double) : 0, b_lc = lc ? lc_n * sizeof(double) : 0;
     const size_t b_pr = pr ? pr_n * sizeof(double) : 0, b_status = status ? nc * sizeof(int32_t) : 0;
-    const size_t in_bytes = b_split + b_par + b_bounds + b_jsfs, out_bytes = b_llk + b_jafs + b_lc + b_pr + b_status;
+    const size_t in_bytes = b_split + b_par + b_bounds + b_pulses + b_jsfs, out_bytes = b_llk + b_jafs + b_lc + b_pr + b_status;
     // The caller's buffers are pageable: inputs are packed into ONE pinned block (a CPU memcpy of tens of KB), copied by truly
     // asynchronous DMAs; outputs come back into one pinned block and are handed over after the single wait at the end.
     const bool pinned = in_bytes <= PIN_STAGE_MAX && out_bytes <= PIN_STAGE_MAX &&
@@ -856,6 +874,8 @@ int eval_batch_host(misti_ctx* c, int64_t n_cand, const double* split, const dou
     if (int r = h2d(c->st_params, params, b_par, (size_t)P * sizeof(double), off)) return r;
     if (int r = h2d(c->st_bounds, band_bounds, b_bounds, 2 * (size_t)c->dm.n_band * sizeof(int32_t), off)) return r;
     if (int r = h2d(c->st_jsfs, jsfs, b_jsfs, 0, off)) return r;
+    // last: its size need not be a multiple of 8, and nothing behind it is read as doubles
+    if (int r = h2d(c->st_pulses, pulse_times, b_pulses, (size_t)c->dm.n_pulse * sizeof(int32_t), off)) return r;
     if (nr) HIP_TRY(c->st_llk.reserve(nc * nr * sizeof(double)));
     HIP_TRY(c->st_jafs.reserve(nc * 7 * sizeof(double)));
     HIP_TRY(c->st_status.reserve(nc * sizeof(int32_t)));
@@ -870,7 +890,8 @@ int eval_batch_host(misti_ctx* c, int64_t n_cand, const double* split, const dou
     int r = run_dev(c, n_cand, c->st_split.as<double>(), P > 0 ? c->st_params.as<double>() : nullptr,
                     with_bounds ? c->st_bounds.as<int32_t>() : nullptr, n_rep,
                     nr ? c->st_jsfs.as<double>() : nullptr, nr ? c->st_llk.as<double>() : nullptr, c->st_jafs.as<double>(),
-                    lc ? c->st_lc.as<double>() : nullptr, pr ? c->st_pr.as<double>() : nullptr, c->st_status.as<int32_t>(), whole ? RUN_INTEGER_SPLITS : 0u);
+                    lc ? c->st_lc.as<double>() : nullptr, pr ? c->st_pr.as<double>() : nullptr, c->st_status.as<int32_t>(), whole ? RUN_INTEGER_SPLITS : 0u,
+                    with_pulses ? c->st_pulses.as<int32_t>() : nullptr);
     if (r) return r;
     char* hout = pinned ? static_cast<char*>(c->pin_out.p) : (idx ? heap_out.data() : nullptr);
     struct Back { void* user; size_t off, bytes, row; };
@@ -968,6 +989,9 @@ struct NmWork {
     // bounds path (misti_nm_solve_bounds, st.bounds_of set): every batch hands the engine its per-slot band bounds
     int32_t* bnd0 = nullptr;         // the per-slot bound arrays bnd0 | bnd1 | bnd2 | bnd3 | ps_bnd, contiguous
     size_t bnd_n = 0;
+    // pulses path (misti_nm_solve_pulses, st.pulses_of set): ... and its per-slot pulse times
+    int32_t* put0 = nullptr;         // the per-slot pulse-time arrays put0 | put1 | put2 | put3 | ps_put, contiguous
+    size_t put_n = 0;
 };
 
 // Live starts up to which an iteration is speculative (misti_nm.hip): all 4 + N points of a start in one batch, as long as the
@@ -1043,10 +1067,11 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     const unsigned nm_hints = (rows ? (w.whole ? RUN_INTEGER_SPLITS : 0u)
                                     : ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH)) & (unsigned)hint_mask;
     // one engine batch of the search: its values against the one data row, or (rows path) each against its own row
-    // (bounds path: with each slot's own band bounds - NULL on the other paths)
-    auto eval = [&](int64_t n, const double* split, const double* params, const int32_t* row, const int32_t* bnd, double* llk) -> int {
+    // (bounds path: with each slot's own band bounds, pulses path: with its own pulse times - NULL on the other paths)
+    auto eval = [&](int64_t n, const double* split, const double* params, const int32_t* row, const int32_t* bnd, const int32_t* put,
+                    double* llk) -> int {
         if (!rows) return run_dev(c, n, split, params, nullptr, 1, w.d_row, llk, nullptr, nullptr, nullptr, nullptr, nm_hints);
-        if (int r = run_dev(c, n, split, params, bnd, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints)) return r;
+        if (int r = run_dev(c, n, split, params, bnd, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints, put)) return r;
         HIP_TRY(misti::launch_llk_rows(n, w.rjafs, w.rstatus, row, w.table, w.consts, llk, c->unfolded, sm));
         return 0;
     };
@@ -1055,8 +1080,9 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     HIP_TRY(hipMemsetAsync(st.split1, 0xBF, S * sizeof(double), sm));          // all-0xBF bytes: a negative double = "no point in this slot"
     if (rows) HIP_TRY(hipMemsetAsync(w.rows0, 0, w.rows_n * sizeof(int32_t), sm));   // row 0 in every slot nothing has written yet
     if (w.bnd_n) HIP_TRY(hipMemsetAsync(w.bnd0, 0, w.bnd_n * sizeof(int32_t), sm));  // and all-zero bounds (what put_none writes)
+    if (w.put_n) HIP_TRY(hipMemsetAsync(w.put0, 0, w.put_n * sizeof(int32_t), sm));  // and all-zero pulse times
     HIP_TRY(misti::launch_nm_init(st, w.d_starts, sm));
-    if (int r = eval((int64_t)(S * V), st.split0, st.sim, st.row0, st.bnd0, w.llk0)) return r;
+    if (int r = eval((int64_t)(S * V), st.split0, st.sim, st.row0, st.bnd0, st.put0, w.llk0)) return r;
     int cur = 0;
     st.idx_next = w.idx[cur]; st.count_next = cnt + cur;
     HIP_TRY(misti::launch_nm_begin(st, w.llk0, sm));
@@ -1091,7 +1117,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             // of the NEXT iteration and drops the count of live starts into the host's pinned word (nm_spec_step_kernel: the live
             // starts of a speculative iteration fit one workgroup); only the first speculative iteration launches a points kernel
             if (!spec_primed) { HIP_TRY(misti::launch_nm_spec_points(st, bound, sm)); spec_primed = true; }
-            if (int r = eval(bound * K, st.ps_split, st.ps, st.ps_row, st.ps_bnd, w.llk_spec)) return r;
+            if (int r = eval(bound * K, st.ps_split, st.ps, st.ps_row, st.ps_bnd, st.ps_put, w.llk_spec)) return r;
             // (no memsets here: the points step zeroes the next slot counter, and the reflection-split array is only read by the
             //  three-batch path, which a search never returns to - the number of live starts only falls)
             misti::NmState nx = st;
@@ -1099,11 +1125,11 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             HIP_TRY(misti::launch_nm_spec_step(st, nx, bound, w.llk_spec, (int32_t*)&live_host[slot], sm));
             ++spec_iters;
         } else {
-            if (int r = eval(bound, st.split1, st.p1, st.row1, st.bnd1, w.llk1)) return r;
+            if (int r = eval(bound, st.split1, st.p1, st.row1, st.bnd1, st.put1, w.llk1)) return r;
             HIP_TRY(misti::launch_nm_reflect(st, bound, w.llk1, sm));
-            if (int r = eval(bound, st.split2, st.p2, st.row2, st.bnd2, w.llk2)) return r;
+            if (int r = eval(bound, st.split2, st.p2, st.row2, st.bnd2, st.put2, w.llk2)) return r;
             HIP_TRY(misti::launch_nm_accept(st, bound, w.llk2, sm));
-            if (int r = eval(bound * N, st.split3, st.p3, st.row3, st.bnd3, w.llk3)) return r;
+            if (int r = eval(bound * N, st.split3, st.p3, st.row3, st.bnd3, st.put3, w.llk3)) return r;
             HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
             HIP_TRY(hipMemsetAsync(st.split1, 0xBF, (size_t)bound * sizeof(double), sm));
             HIP_TRY(misti::launch_nm_finish(st, bound, w.llk3, sm));
@@ -1159,28 +1185,38 @@ int misti_nm_solve(misti_ctx* c, int64_t n_start, const double* starts, double s
 
 namespace {
 
-// misti_nm_solve_rows (band_bounds NULL) and misti_nm_solve_bounds: one implementation.  Without bounds nothing of the bounds path
-// is allocated or written, and the search runs exactly the rows path's instructions.
+// What the rows searches ask of their arguments whatever the context is (nothing here reads it).
+int nm_rows_args(int64_t n_start, const double* starts, const double* split_times, const int32_t* rows, int64_t n_rep, const double* jsfs,
+                 int32_t maxiter, const double* x, const double* llh) {
+    if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
+    if (!starts || !split_times || !rows || !jsfs || !x || !llh) return fail(MISTI_E_ARG, "starts / split_times / rows / jsfs / x / llh is NULL");
+    if (n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)n_rep);
+    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    for (int64_t s = 0; s < n_start; ++s) {
+        if (rows[s] < 0 || rows[s] >= n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)rows[s], (long long)n_rep);
+        if (!std::isfinite(split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+    }
+    return 0;
+}
+
+// misti_nm_solve_rows (band_bounds NULL), misti_nm_solve_bounds and misti_nm_solve_pulses (pulse_times set): one implementation.
+// Without bounds nothing of the bounds path is allocated or written, without pulse times nothing of the pulses path, and the search
+// runs exactly the rows path's (the bounds path's) instructions.
 int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                        const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
-                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status, const int32_t* pulse_times = nullptr) {
     // every argument is checked before the first HIP call
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
     const int N = c->dm.n_param;
     if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    if (!starts || !split_times || !rows || !jsfs || !x || !llh) return fail(MISTI_E_ARG, "starts / split_times / rows / jsfs / x / llh is NULL");
-    if (n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)n_rep);
-    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
     if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
     if (n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
     bool whole = true;
-    for (int64_t s = 0; s < n_start; ++s) {
-        if (rows[s] < 0 || rows[s] >= n_rep)
-            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)rows[s], (long long)n_rep);
-        if (!std::isfinite(split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+    for (int64_t s = 0; s < n_start; ++s)
         if (split_times[s] != std::floor(split_times[s])) whole = false;
-    }
     if (n_start == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = (size_t)n_start, V = (size_t)N + 1, R = (size_t)n_rep;
@@ -1191,8 +1227,11 @@ int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, cons
     // engine has nothing to apply them to)
     const size_t NB2 = band_bounds ? 2 * (size_t)c->dm.n_band : 0;
     const size_t bnd_n = NB2 * (S * V + 2 * S + S * N + cap * K);               // bnd0 | bnd1 | bnd2 | bnd3 | ps_bnd
+    // pulses path: the same for the pulse times (none for a model without pulses)
+    const size_t NP = pulse_times ? (size_t)c->dm.n_pulse : 0;
+    const size_t put_n = NP * (S * V + 2 * S + S * N + cap * K);                // put0 | put1 | put2 | put3 | ps_put
     NmWork w;
-    if (int r = nm_prepare(c, n_start, w, S + R * 8 + R + M * 7, S + rows_n + M + S * NB2 + bnd_n)) return r;
+    if (int r = nm_prepare(c, n_start, w, S + R * 8 + R + M * 7, S + rows_n + M + S * NB2 + bnd_n + S * NP + put_n)) return r;
     misti::NmState& st = w.st;
     double* d = w.extra_f64;
     double* d_split = d; d += S;
@@ -1210,6 +1249,14 @@ int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, cons
         w.bnd0 = q; w.bnd_n = bnd_n;
         st.bnd0 = q; q += S * V * NB2; st.bnd1 = q; q += S * NB2; st.bnd2 = q; q += S * NB2; st.bnd3 = q; q += S * N * NB2; st.ps_bnd = q;
         st.bounds_of = d_bounds; st.nb2 = (int)NB2;
+        q = st.ps_bnd + cap * K * NB2;
+    }
+    int32_t* d_pulses = nullptr;
+    if (NP) {
+        d_pulses = q; q += S * NP;
+        w.put0 = q; w.put_n = put_n;
+        st.put0 = q; q += S * V * NP; st.put1 = q; q += S * NP; st.put2 = q; q += S * NP; st.put3 = q; q += S * N * NP; st.ps_put = q;
+        st.pulses_of = d_pulses; st.np = (int)NP;
     }
     st.split_of = d_split; st.row_of = d_rowof;
     w.table = d_table; w.consts = d_consts; w.whole = whole;
@@ -1218,6 +1265,7 @@ int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, cons
     HIP_TRY(hipMemcpyAsync(d_split, split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_rowof, rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_table, jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(misti::launch_llh_const(n_rep, d_table, d_consts, c->unfolded, sm));          // once per call, every row
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
@@ -1248,6 +1296,17 @@ int misti_nm_solve_bounds(misti_ctx* c, int64_t n_start, const double* starts, c
     // (llh = -inf), as it does for an invalid split; a model without bands has nothing to apply them to (as misti_eval_batch)
     return nm_solve_rows_impl(c, n_start, starts, split_times, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs,
                               xatol, fatol, maxiter, x, llh, nit, nfev, status);
+}
+
+int misti_nm_solve_pulses(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                          const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double xatol, double fatol,
+                          int32_t maxiter, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    // times that break SetModel's checks are no argument error either: that start's points get MISTI_BAD_STRUCTURE (llh = -inf);
+    // a model without pulses has nothing to apply them to (as misti_eval_batch_pulses).  The arguments that do not depend on the
+    // context are checked first: their errors are reported without one.
+    if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
+    return nm_solve_rows_impl(c, n_start, starts, split_times, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs,
+                              xatol, fatol, maxiter, x, llh, nit, nfev, status, c && c->dm.n_pulse > 0 ? pulse_times : nullptr);
 }
 
 int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,

@@ -86,6 +86,7 @@ struct ChainBufs {
     int32_t integer_splits; // the caller (or the host-buffer entry point, which sees them) says no split time has a fractional part: no tail launch was
                             // made, and a candidate that has one after all is refused (spectrum_kernel)
     const int32_t* bounds;  // [n][n_band][2] per-candidate (start, end) of every band, or NULL: the model's
+    const int32_t* pulse_times;   // [n][n_pulse] per-candidate time of every pulse, or NULL: the model's
     double* post_lam;       // [n][numT+1] default fit: rates after the split (postsplit_kernel -> spectrum kernel)
     int32_t* post_word;     // [n][numT+1] their solver words, or NULL (trace off)
     // solver trace (misti_enable_solver_trace), all NULL when off
@@ -117,6 +118,8 @@ struct NmState {
     const int32_t* row_of;  // [S] or NULL: the replicate row of each start's points; set together with split_of
     const int32_t* bounds_of;   // [S][nb2] or NULL: the band bounds of each start's points (misti_nm_solve_bounds); only with row_of
     int nb2;                // 2 n_band: int32 per bound set (bounds_of set)
+    const int32_t* pulses_of;   // [S][np] or NULL: the pulse times of each start's points (misti_nm_solve_pulses); only with row_of
+    int np;                 // n_pulse: int32 per pulse-time set (pulses_of set)
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)
@@ -144,11 +147,16 @@ struct NmState {
     int32_t* bnd1;          // [S][nb2]      is set; empty slots carry zeros)
     int32_t* bnd2;          // [S][nb2]
     int32_t* bnd3;          // [S * N][nb2]
+    int32_t* put0;          // [S * V][np]   pulse times per engine candidate of the four batches, beside bnd0..3 (NULL unless pulses_of
+    int32_t* put1;          // [S][np]       is set; empty slots carry zeros)
+    int32_t* put2;          // [S][np]
+    int32_t* put3;          // [S * N][np]
     // speculative iterations (few live starts: latency-bound): every point SciPy COULD ask for in the iteration, one batch
     double* ps;             // [spec_cap][4 + N][N]  reflection, expansion, outside / inside contraction, the N shrunk vertices
     double* ps_split;       // [spec_cap * (4 + N)]
     int32_t* ps_row;        // [spec_cap * (4 + N)]  or NULL (row_of unset)
     int32_t* ps_bnd;        // [spec_cap * (4 + N)][nb2]  or NULL (bounds_of unset)
+    int32_t* ps_put;        // [spec_cap * (4 + N)][np]   or NULL (pulses_of unset)
     int64_t spec_cap;       // live starts up to which an iteration is speculative
     const int32_t* idx_cur; // [S] slot -> start of the iteration in progress
     const int32_t* count_cur;   // [1] its number of live starts

@@ -160,6 +160,7 @@ struct Model {
     int split;
     double pv[4];          // the first parameters, cached in registers (a sweep has 1-3)
     const int32_t* bb = nullptr;   // [n_band][2] this candidate's (start, end) of every band, or NULL: the model's
+    const int32_t* pt = nullptr;   // [n_pulse] this candidate's pulse times, or NULL: the model's
     __device__ __forceinline__ void cache() { for (int i = 0; i < 4; ++i) pv[i] = (i < m->n_param) ? par[i] : 0.0; }
     __device__ __forceinline__ double param(int i) const {
         return i == 0 ? pv[0] : i == 1 ? pv[1] : i == 2 ? pv[2] : i == 3 ? pv[3] : par[i];
@@ -181,7 +182,7 @@ struct Model {
         pu0 = 0.0; pu1 = 0.0;
         for (int b = 0; b < m->n_pulse; ++b) {
             const misti_pulse_t& P = m->pulses[b];
-            if (t == P.time) {
+            if (t == (pt ? pt[b] : P.time)) {
                 double v = P.param >= 0 ? param(P.param) : P.value;
                 if (P.pop == 0) pu0 = v; else pu1 = v;
             }
@@ -1336,7 +1337,20 @@ __device__ __forceinline__ bool bands_valid(const DevModel& m, const int32_t* bb
     return ok;
 }
 
-__device__ __forceinline__ int setup_candidate(const DevModel& m, double st, const double* par, Grid& G, const int32_t* bb = nullptr) {
+// SetModel's checks on this candidate's own pulse times (MigrationInference.py:259-279) with the grid bound of validate_model
+// (misti_api.cpp): time >= sample date, time < numT + 1, no two pulses at one time.  A time at or beyond the split is valid and
+// never applied (the reference's loops run over t < splitT).
+__device__ __forceinline__ bool pulses_valid(const DevModel& m, const int32_t* pt) {
+    bool ok = true;
+    for (int b = 0; b < m.n_pulse; ++b) {
+        if (pt[b] < m.sample_date || pt[b] >= m.numT + 1) ok = false;
+        for (int c = 0; c < b; ++c) if (pt[c] == pt[b]) ok = false;
+    }
+    return ok;
+}
+
+__device__ __forceinline__ int setup_candidate(const DevModel& m, double st, const double* par, Grid& G, const int32_t* bb = nullptr,
+                                               const int32_t* pt = nullptr) {
     int status = MISTI_OK;
     G.times = m.times; G.lh = m.lh; G.numT0 = m.numT;
     double fl = floor(st);
@@ -1349,6 +1363,7 @@ __device__ __forceinline__ int setup_candidate(const DevModel& m, double st, con
         else { G.ins = s; G.split = s + 1; G.numT = m.numT + 1; }
     }
     if (status == MISTI_OK && m.n_band > 0 && !bands_valid(m, bb, G.split)) status = MISTI_BAD_STRUCTURE;
+    if (status == MISTI_OK && pt && !pulses_valid(m, pt)) status = MISTI_BAD_STRUCTURE;
     // construction errors (PrintError + exit in the reference's __init__/SetModel) come before the guard of JAFSLikelihood (:569-572)
     if (status == MISTI_OK) for (int i = 0; i < m.n_param; ++i) if (par[i] < 0) status = MISTI_NEG_PARAM;
     if (status == MISTI_OK && G.split >= G.numT) status = MISTI_INF_COAL;
@@ -1489,6 +1504,7 @@ void correct_body(const DevModel& m, int64_t n_items, const ChainBufs& cb, const
     double* tr_w;     // tr_w[6 (t + 1) + j]  pair state after interval t
     PairState ps;
     const int32_t* bb = cb.bounds ? cb.bounds + cand * 2 * m.n_band : nullptr;
+    const int32_t* pt = cb.pulse_times ? cb.pulse_times + cand * m.n_pulse : nullptr;
     int32_t* sv_w = nullptr;   // sv_w[t]  solver word of interval t (trace on)
     double* it_w = nullptr;    // it_w[(t * MISTI_TRACE_MAX_ITER + i) * 2 + k]  trial points of the unbounded solve of interval t
     if (!TAIL) {
@@ -1509,7 +1525,7 @@ void correct_body(const DevModel& m, int64_t n_items, const ChainBufs& cb, const
             ps.p[0][0] = r[0]; ps.p[1][0] = r[1]; ps.p[0][1] = r[2]; ps.p[1][1] = r[3]; ps.p[0][2] = r[4]; ps.p[1][2] = r[5];
         } else if (sub == 0) { tr_w[0] = 1; tr_w[1] = 0; tr_w[2] = 0; tr_w[3] = 1; tr_w[4] = 0; tr_w[5] = 0; }
     } else {
-        status = setup_candidate(m, split_time[cand], par, G, bb);
+        status = setup_candidate(m, split_time[cand], par, G, bb, pt);
         if (sub == 0) cb.tail_status[cand] = MISTI_OK;
         if (status != MISTI_OK || G.ins < 0) return;               // nothing to do: no fractional split
         if (cb.tail_solver) sv_w = cb.tail_solver + cand - G.ins;
@@ -1525,6 +1541,7 @@ void correct_body(const DevModel& m, int64_t n_items, const ChainBufs& cb, const
     G.times = lds; G.lh = lds + (m.numT - 1);
     Model mod{&m, par, G.split, {0, 0, 0, 0}};
     mod.bb = bb;
+    mod.pt = pt;
     mod.cache();
     const bool correct = !(m.flags & MISTI_TRUE_EPS);
     const int max_nfev = 200;                    // 100 * n (least_squares.py)
@@ -2338,6 +2355,7 @@ void trunk_body(const DevModel& m, int64_t n_cand, const double* __restrict__ pa
     G.times = m.times; G.lh = m.lh; G.numT0 = m.numT; G.numT = m.numT; G.split = Lt; G.ins = -1; G.frac = 0.0;
     Model mod{&m, par, Lt, {0, 0, 0, 0}};
     mod.bb = cb.bounds ? cb.bounds + (int64_t)cb.rep[ch] * 2 * m.n_band : nullptr;
+    mod.pt = cb.pulse_times ? cb.pulse_times + (int64_t)cb.rep[ch] * m.n_pulse : nullptr;
     mod.cache();
     const double* lc_ch = cb.lc + ch * (int64_t)m.numT * 2;
     for (int i = lane; i < 2 * (m.numT + 1); i += 64) lcb[i] = ((i >> 1) < Lt) ? lc_ch[i] : 0.0;
@@ -2392,6 +2410,7 @@ void trunk_follow(const DevModel& m, int64_t n_cand, const double* __restrict__ 
     G.times = m.times; G.lh = m.lh; G.numT0 = m.numT; G.numT = m.numT; G.split = len; G.ins = -1; G.frac = 0.0;
     Model mod{&m, par, len, {0, 0, 0, 0}};
     mod.bb = cb.bounds ? cb.bounds + (int64_t)cb.rep[ch] * 2 * m.n_band : nullptr;
+    mod.pt = cb.pulse_times ? cb.pulse_times + (int64_t)cb.rep[ch] * m.n_pulse : nullptr;
     mod.cache();
     for (int i = lane; i < 2 * (m.numT + 1); i += 64) lcb[i] = 0.0;
     lds_fence();
@@ -2550,7 +2569,8 @@ void postsplit_kernel(DevModel m, int64_t n_cand, const double* __restrict__ spl
     Grid G;
     const double* par = params ? params + cand * m.n_param : nullptr;
     const int32_t* bb = cb.bounds ? cb.bounds + cand * 2 * m.n_band : nullptr;
-    if (setup_candidate(m, split_time[cand], par, G, bb) != MISTI_OK) return;
+    const int32_t* pt = cb.pulse_times ? cb.pulse_times + cand * m.n_pulse : nullptr;
+    if (setup_candidate(m, split_time[cand], par, G, bb, pt) != MISTI_OK) return;
     if (t < G.split || t >= G.numT - 1) return;
     const int64_t ch = chain_of(cb, cand);
     const int nfull = (G.ins >= 0) ? G.ins : G.split;
@@ -2609,11 +2629,13 @@ void spectrum_kernel(DevModel m, int64_t n_cand, const int32_t* __restrict__ ord
     const double* par = params ? params + cand * m.n_param : nullptr;
     Grid G;
     const int32_t* bb = cb.bounds ? cb.bounds + cand * 2 * m.n_band : nullptr;
-    int status = setup_candidate(m, split_time[cand], par, G, bb);
+    const int32_t* pt = cb.pulse_times ? cb.pulse_times + cand * m.n_pulse : nullptr;
+    int status = setup_candidate(m, split_time[cand], par, G, bb, pt);
     // a batch issued under "no fractional split times" (misti_set_hints; no tail launch was made) that has one after all: refused, never wrong
     if (status == MISTI_OK && cb.integer_splits && G.ins >= 0) status = MISTI_BAD_STRUCTURE;
     Model mod{&m, par, G.split, {0, 0, 0, 0}};
     mod.bb = bb;
+    mod.pt = pt;
     mod.cache();
     // ---- this candidate's share of its chain (+ its own tail interval after a fractional split)
     const int64_t ch = (int64_t)__builtin_amdgcn_readfirstlane((int)chain_of(cb, cand));
@@ -2916,7 +2938,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 __global__ __launch_bounds__(256)
 void setup_kernel(DevModel m, int64_t n, const double* __restrict__ params, const double* __restrict__ split_time, ChainBufs cb,
                   int cand_blocks, int32_t* __restrict__ order, int64_t n_rep, const double* __restrict__ jsfs, double* __restrict__ consts, int unfolded) {
-    const int numT = m.numT, P = m.n_param, NB2 = cb.bounds ? 2 * m.n_band : 0;
+    const int numT = m.numT, P = m.n_param, NB2 = cb.bounds ? 2 * m.n_band : 0, NPU = cb.pulse_times ? m.n_pulse : 0;
     if ((int)blockIdx.x > cand_blocks) {
         const int64_t r = (int64_t)((int)blockIdx.x - cand_blocks - 1) * blockDim.x + threadIdx.x;
         if (r < n_rep) consts[r] = llh_const_of(jsfs + r * 8, unfolded);
@@ -2978,12 +3000,15 @@ void setup_kernel(DevModel m, int64_t n, const double* __restrict__ params, cons
     if (i < n) {
         if (cb.unsorted & 1) order[i] = (int32_t)i;
         // the key: the parameter bits and, with per-candidate band bounds, the (start, end) pairs as given (end == -1
-        // stays symbolic: members of a chain may differ in their split, never in where a band starts or ends)
+        // stays symbolic: members of a chain may differ in their split, never in where a band starts or ends) and, with
+        // per-candidate pulse times, the times as given (the pulse acts on the pair state, CorrectLambdas :315-323)
         uint64_t h = 0x243f6a8885a308d3ull;
         const double* a = params + i * P;
         const int32_t* ab = cb.bounds ? cb.bounds + i * NB2 : nullptr;
         for (int k = 0; k < P; ++k) h = mix64(h ^ (uint64_t)__double_as_longlong(a[k]));
         if (ab) for (int k = 0; k < NB2; ++k) h = mix64(h ^ (uint64_t)(uint32_t)ab[k]);
+        const int32_t* ap = cb.pulse_times ? cb.pulse_times + i * NPU : nullptr;
+        if (ap) for (int k = 0; k < NPU; ++k) h = mix64(h ^ (uint64_t)(uint32_t)ap[k]);
         const double st = split_time[i];
         // a candidate without a valid split time (an EMPTY SLOT of a batched search: negative) starts probing at a slot of its own:
         // thousands of them carry one and the same parameter vector, and their inserts would queue on one table entry (measured:
@@ -3005,6 +3030,7 @@ void setup_kernel(DevModel m, int64_t n, const double* __restrict__ params, cons
             bool same = true;
             for (int k = 0; k < P; ++k) if (__double_as_longlong(a[k]) != __double_as_longlong(b[k])) same = false;
             if (ab) { const int32_t* bbp = cb.bounds + (int64_t)(prev - 1) * NB2; for (int k = 0; k < NB2; ++k) if (ab[k] != bbp[k]) same = false; }
+            if (ap) { const int32_t* pp = cb.pulse_times + (int64_t)(prev - 1) * NPU; for (int k = 0; k < NPU; ++k) if (ap[k] != pp[k]) same = false; }
             if (same) break;
             sl = (sl + 1) & cb.tmask;
         }
@@ -3014,7 +3040,7 @@ void setup_kernel(DevModel m, int64_t n, const double* __restrict__ params, cons
         atomicMax(&cb.slot_len[sl], need);
         // from which interval on this candidate reads its chain's trunk (candidates without a value read nothing)
         Grid G;
-        if (setup_candidate(m, st, P ? a : nullptr, G, ab) == MISTI_OK) {
+        if (setup_candidate(m, st, P ? a : nullptr, G, ab, ap) == MISTI_OK) {
             int t_own = trunk_leave(m, G);
             t_own = t_own < 0 ? 0 : (t_own > numT - 1 ? numT - 1 : t_own);
             atomicMax(&cb.slot_keep[sl], numT - t_own);

@@ -44,20 +44,23 @@ __device__ __forceinline__ double rn(double v) { __asm__ volatile("" : "+v"(v));
 // a*x - b*y with a rounding after each product and after the difference (NumPy elementwise semantics)
 __device__ __forceinline__ double lin2(double a, double x, double b, double y) { return rn(a * x) - rn(b * y); }
 
-// The split time, replicate row and band bounds of start s's points: one split for all starts (misti_nm_solve), or per start
-// (misti_nm_solve_rows: row_of set, and with it the per-slot row arrays; misti_nm_solve_bounds: bounds_of set as well, and the
-// per-slot bound arrays).  Slot j of a batch takes them with put_point, an empty slot (or a point the start does not need) a
-// negative split, row 0 and all-zero bounds with put_none: no row index ever leaves the table, and a negative split is refused
-// (setup_candidate) before any bound of its slot is read.  Without bounds_of / row_of nothing but the split is written.
-__device__ __forceinline__ void put_point(const NmState& st, double* split, int32_t* row, int32_t* bnd, int64_t j, int64_t s) {
+// The split time, replicate row, band bounds and pulse times of start s's points: one split for all starts (misti_nm_solve), or
+// per start (misti_nm_solve_rows: row_of set, and with it the per-slot row arrays; misti_nm_solve_bounds: bounds_of set as well,
+// and the per-slot bound arrays; misti_nm_solve_pulses: pulses_of set, and the per-slot pulse-time arrays).  Slot j of a batch
+// takes them with put_point, an empty slot (or a point the start does not need) a negative split, row 0, all-zero bounds and
+// all-zero pulse times with put_none: no row index ever leaves the table, and a negative split is refused (setup_candidate)
+// before any bound or time of its slot is read.  Without bounds_of / pulses_of / row_of nothing but the split is written.
+__device__ __forceinline__ void put_point(const NmState& st, double* split, int32_t* row, int32_t* bnd, int32_t* put, int64_t j, int64_t s) {
     split[j] = st.split_of ? st.split_of[s] : st.split;
     if (st.row_of) row[j] = st.row_of[s];
     if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) bnd[j * st.nb2 + k] = st.bounds_of[s * st.nb2 + k];
+    if (st.pulses_of) for (int k = 0; k < st.np; ++k) put[j * st.np + k] = st.pulses_of[s * st.np + k];
 }
-__device__ __forceinline__ void put_none(const NmState& st, double* split, int32_t* row, int32_t* bnd, int64_t j) {
+__device__ __forceinline__ void put_none(const NmState& st, double* split, int32_t* row, int32_t* bnd, int32_t* put, int64_t j) {
     split[j] = -1.0;
     if (st.row_of) row[j] = 0;
     if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) bnd[j * st.nb2 + k] = 0;
+    if (st.pulses_of) for (int k = 0; k < st.np; ++k) put[j * st.np + k] = 0;
 }
 
 // numpy.argsort on <= 17 values: insertion sort (stable), NaN last
@@ -121,7 +124,7 @@ __device__ void next_reflection(const NmState& st, int64_t s) {
     st.idx_next[slot] = (int32_t)s;
     double* p1 = st.p1 + (int64_t)slot * N;
     for (int k = 0; k < N; ++k) p1[k] = lin2(1.0 + NM_RHO, centroid(x, N, k), NM_RHO, x[N * N + k]);     // xr
-    put_point(st, st.split1, st.row1, st.bnd1, slot, s);
+    put_point(st, st.split1, st.row1, st.bnd1, st.put1, slot, s);
 }
 
 }  // namespace
@@ -139,7 +142,7 @@ void nm_init_kernel(NmState st, const double* __restrict__ starts) {
             if (i == k + 1) y = (y != 0.0) ? rn((1.0 + NM_NONZDELT) * y) : NM_ZDELT;
             x[i * N + k] = y;
         }
-        put_point(st, st.split0, st.row0, st.bnd0, s * V + i, s);
+        put_point(st, st.split0, st.row0, st.bnd0, st.put0, s * V + i, s);
     }
     st.nit[s] = 1; st.nfev[s] = 0; st.done[s] = -1;
 }
@@ -163,7 +166,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= bound) return;
     const int N = st.N, V = N + 1;
-    if (i >= st.count_cur[0]) { put_none(st, st.split2, st.row2, st.bnd2, i); return; }         // no start in this slot
+    if (i >= st.count_cur[0]) { put_none(st, st.split2, st.row2, st.bnd2, st.put2, i); return; }         // no start in this slot
     const int64_t s = st.idx_cur[i];
     double* p2 = st.p2 + i * N;
     const double* f = st.fsim + s * V;
@@ -188,7 +191,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     st.kind[s] = kind;
     const bool second = kind != NM_REFLECT && kind != NM_CUT;
     if (!second) for (int k = 0; k < N; ++k) p2[k] = 0.0;
-    if (second) put_point(st, st.split2, st.row2, st.bnd2, i, s); else put_none(st, st.split2, st.row2, st.bnd2, i);
+    if (second) put_point(st, st.split2, st.row2, st.bnd2, st.put2, i, s); else put_none(st, st.split2, st.row2, st.bnd2, st.put2, i);
 }
 
 // the second value is in: replace the worst vertex, or shrink (then the N shrunk vertices are the third batch)
@@ -198,7 +201,7 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
     if (i >= bound) return;
     const int N = st.N, V = N + 1;
     double* p3 = st.p3 + i * (int64_t)N * N;
-    if (i >= st.count_cur[0]) { for (int j = 0; j < N; ++j) put_none(st, st.split3, st.row3, st.bnd3, i * N + j); return; }
+    if (i >= st.count_cur[0]) { for (int j = 0; j < N; ++j) put_none(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j); return; }
     const int64_t s = st.idx_cur[i];
     double* f = st.fsim + s * V;
     double* x = st.sim + s * (int64_t)V * N;
@@ -234,7 +237,7 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
     st.shrunk[s] = shrink ? 1 + n_eval : 0;
     for (int j = 0; j < N; ++j) {
         const bool live = shrink && j < n_eval;
-        if (live) put_point(st, st.split3, st.row3, st.bnd3, i * N + j, s); else put_none(st, st.split3, st.row3, st.bnd3, i * N + j);
+        if (live) put_point(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j, s); else put_none(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j);
         if (!live) for (int k = 0; k < N; ++k) p3[j * N + k] = 0.0;
     }
 }
@@ -273,7 +276,8 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
     double* sp = st.ps_split + i * K;
     int32_t* rw = st.ps_row ? st.ps_row + i * K : nullptr;
     int32_t* bw = st.ps_bnd ? st.ps_bnd + i * K * st.nb2 : nullptr;
-    if (i >= st.count_cur[0]) { for (int j = 0; j < K; ++j) { put_none(st, sp, rw, bw, j); for (int k = 0; k < N; ++k) pt[j * N + k] = 0.0; } return; }
+    int32_t* pw = st.ps_put ? st.ps_put + i * K * st.np : nullptr;
+    if (i >= st.count_cur[0]) { for (int j = 0; j < K; ++j) { put_none(st, sp, rw, bw, pw, j); for (int k = 0; k < N; ++k) pt[j * N + k] = 0.0; } return; }
     const int64_t s = st.idx_cur[i];
     const double* x = st.sim + s * (int64_t)V * N;
     const double* p1 = st.p1 + i * N;
@@ -285,7 +289,7 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
         pt[3 * N + k] = rn((1.0 - NM_PSI) * xb) + rn(NM_PSI * w);                         // xcc
         for (int j = 1; j < V; ++j) pt[(3 + j) * N + k] = x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k]));   // shrunk vertex j
     }
-    for (int j = 0; j < K; ++j) put_point(st, sp, rw, bw, j, s);
+    for (int j = 0; j < K; ++j) put_point(st, sp, rw, bw, pw, j, s);
 }
 
 __global__ __launch_bounds__(256)

@@ -112,6 +112,7 @@ class Engine:
         bands = list(bands)
         pulses = list(pulses)
         self.n_band = len(bands)
+        self.n_pulse = len(pulses)
         b_arr = (_lib.Band * max(1, len(bands)))()
         for i, (pop, start, end, value, param) in enumerate(bands):
             b_arr[i] = _lib.Band(int(pop), int(start), int(end), int(param), float(value))
@@ -149,11 +150,15 @@ class Engine:
         self.close()
 
     # -- host-buffer evaluation ----------------------------------------------
-    def evaluate(self, split_time, params=None, jsfs=None, want_lc=False, want_pr=False, band_bounds=None):
+    def evaluate(self, split_time, params=None, jsfs=None, want_lc=False, want_pr=False, band_bounds=None, pulse_times=None):
         """``misti_eval_batch``: NumPy in, NumPy out (copies over PCIe).
 
         ``band_bounds`` ([n][n_band][2] ints, optional): per-candidate (start, end) of every band, replacing the
-        model's (``end == -1``: the candidate's split index) - the README's ``::: st ... ::: mc ...`` sweep in one call."""
+        model's (``end == -1``: the candidate's split index) - the README's ``::: st ... ::: mc ...`` sweep in one call.
+
+        ``pulse_times`` ([n][n_pulse] ints, optional): per-candidate time of every pulse, replacing the model's
+        (``misti_eval_batch_pulses``) - the same recipe with ``-pu 2 {t} {f} 0`` in the place of a band.  An index on the
+        candidate's own grid; a candidate whose times break SetModel's checks gets status 4 and -inf."""
         split = _f64(np.atleast_1d(split_time))
         n = split.shape[0]
         P = self.n_param
@@ -171,8 +176,13 @@ class Engine:
         bb = None
         if band_bounds is not None and self.n_band:
             bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(n, self.n_band, 2)
-        _lib.check(self._lib.misti_eval_batch(self._ctx, n, ptr(split), ptr(par), ptr(bb), R, ptr(rows), ptr(llk), ptr(jafs),
-                                              ptr(lc), ptr(pr), ptr(status)))
+        if pulse_times is not None and self.n_pulse:
+            pt = np.ascontiguousarray(pulse_times, dtype=np.int32).reshape(n, self.n_pulse)
+            _lib.check(self._lib.misti_eval_batch_pulses(self._ctx, n, ptr(split), ptr(par), ptr(bb), ptr(pt), R, ptr(rows), ptr(llk),
+                                                         ptr(jafs), ptr(lc), ptr(pr), ptr(status)))
+        else:
+            _lib.check(self._lib.misti_eval_batch(self._ctx, n, ptr(split), ptr(par), ptr(bb), R, ptr(rows), ptr(llk), ptr(jafs),
+                                                  ptr(lc), ptr(pr), ptr(status)))
         return BatchResult(llk, jafs, status, lc, pr, self.last_diag(n) if n else np.zeros(0))
 
     def forward_rates(self, split_time, params=None, want_pr=False, hold_mu=False):
@@ -215,9 +225,14 @@ class Engine:
         has one after all gets status 4 for that candidate, never a wrong value)."""
         _lib.check(self._lib.misti_set_hints(self._ctx, _lib.HINT_INTEGER_SPLITS if integer_splits else 0))
 
-    def evaluate_dev(self, n_cand, d_split, d_params, n_rep, d_jsfs, d_llk, d_jafs=0, d_lc=0, d_pr=0, d_status=0, d_bounds=0):
-        """``misti_eval_batch_dev``: raw device addresses (ints); asynchronous."""
+    def evaluate_dev(self, n_cand, d_split, d_params, n_rep, d_jsfs, d_llk, d_jafs=0, d_lc=0, d_pr=0, d_status=0, d_bounds=0, d_pulse_times=0):
+        """``misti_eval_batch_dev``: raw device addresses (ints); asynchronous.  With ``d_pulse_times`` ([n][n_pulse] int32 on the
+        device): ``misti_eval_batch_pulses_dev``."""
         v = lambda p: C.c_void_p(int(p)) if p else None
+        if d_pulse_times:
+            _lib.check(self._lib.misti_eval_batch_pulses_dev(self._ctx, int(n_cand), v(d_split), v(d_params), v(d_bounds), v(d_pulse_times),
+                                                             int(n_rep), v(d_jsfs), v(d_llk), v(d_jafs), v(d_lc), v(d_pr), v(d_status)))
+            return
         _lib.check(self._lib.misti_eval_batch_dev(self._ctx, int(n_cand), v(d_split), v(d_params), v(d_bounds), int(n_rep), v(d_jsfs),
                                                   v(d_llk), v(d_jafs), v(d_lc), v(d_pr), v(d_status)))
 
@@ -298,6 +313,36 @@ class Engine:
         ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
         _lib.check(self._lib.misti_nm_solve_bounds(self._ctx, S, ptr(st), ptr(split), ptr(row), ptr(bb), table.shape[0], ptr(table), float(tol),
                                                    float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
+        stats = (C.c_int64 * 2)()
+        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
+        spec = C.c_int64(0)
+        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
+        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
+                    speculative_iterations=int(spec.value))
+
+    def nm_solve_pulses(self, starts, split_times, rows, jsfs, band_bounds, pulse_times, tol=1e-4, maxiter=1000):
+        """``misti_nm_solve_pulses``: ``nm_solve_bounds`` with the pulse times PER START as well (``[n_start][n_pulse]`` ints, on
+        the start's own grid) - the pulse-date profile with an optimised fraction, ``-pu 2 {t} f 1`` under a loop over t, in one
+        batched search.  Times that break SetModel's checks give that start ``llh = -inf``.  ``pulse_times=None`` is
+        ``nm_solve_bounds``.
+        Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` on an engine whose
+        model carries ``band_bounds[s]`` and ``pulse_times[s]``, bit for bit."""
+        st = _f64(starts, (-1, self.n_param))
+        S = st.shape[0]
+        split = _f64(split_times, (S,))
+        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
+        table = _f64(jsfs, (-1, 8))
+        bb = pt = None
+        if band_bounds is not None and self.n_band:
+            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(S, self.n_band, 2)
+        if pulse_times is not None and self.n_pulse:
+            pt = np.ascontiguousarray(pulse_times, dtype=np.int32).reshape(S, self.n_pulse)
+        x = np.empty((S, self.n_param))
+        llh = np.empty(S)
+        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        _lib.check(self._lib.misti_nm_solve_pulses(self._ctx, S, ptr(st), ptr(split), ptr(row), ptr(bb), ptr(pt), table.shape[0], ptr(table),
+                                                   float(tol), float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
         stats = (C.c_int64 * 2)()
         _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
         spec = C.c_int64(0)

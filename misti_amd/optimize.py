@@ -337,13 +337,21 @@ def sweep_profile(engine, models, jsfs_rows, starts, tol=1e-4, maxiter=1000):
     (end -1: the model's split index) - the boundary profiles "when did migration start or stop" (the test.bs scripts' Solve per
     (replicate, split) pair with a loop over a band boundary added, one Engine per boundary there) in ONE ``misti_nm_solve_bounds``
     call: every (row, model, start) triple is a start of the batched search.  ``jsfs_rows`` is ``[R][8]``, ``starts`` ``[Q][N]``.
-    Per (row, model) the best start is kept (ties: the lowest start index).
+    Per (row, model) the best start is kept (ties: the lowest start index).  A model may carry its own pulse times as a third
+    element, ``(split, band_bounds, pulse_times[n_pulse])`` - the pulse-date profile "when did the pulse happen"; with any third
+    element the call is ``misti_nm_solve_pulses``.
     Returns dict(x[R][M][N], llh[R][M], nit / nfev / status / start[R][M], and the search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.array([float(m[0]) for m in models], dtype=float)
     bounds = np.array([np.asarray(m[1], dtype=np.int32).reshape(-1, 2) for m in models], dtype=np.int32).reshape(len(models), -1, 2)
-    return _best_start_profile(lambda r_of, m_of, st: engine.nm_solve_bounds(st, splits[m_of], r_of, rows, bounds[m_of], tol=tol, maxiter=maxiter),
-                               rows.shape[0], splits.size, starts)
+    if any(len(m) > 2 for m in models):
+        if not all(len(m) > 2 for m in models):
+            raise ValueError("sweep_profile: either every model carries pulse times or none does")
+        times = np.array([np.asarray(m[2], dtype=np.int32).reshape(-1) for m in models], dtype=np.int32).reshape(len(models), -1)
+        search = lambda r_of, m_of, st: engine.nm_solve_pulses(st, splits[m_of], r_of, rows, bounds[m_of], times[m_of], tol=tol, maxiter=maxiter)
+    else:
+        search = lambda r_of, m_of, st: engine.nm_solve_bounds(st, splits[m_of], r_of, rows, bounds[m_of], tol=tol, maxiter=maxiter)
+    return _best_start_profile(search, rows.shape[0], splits.size, starts)
 
 
 def sweep_interval(llh, values, x=None):
