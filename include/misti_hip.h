@@ -299,6 +299,38 @@ int misti_nm_solve_pulses(misti_ctx* ctx, int64_t n_start, const double* starts,
                           double xatol, double fatol, int32_t maxiter,
                           double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
+/* The split time as a COORDINATE of the search: every simplex has n_param + 1 coordinates, the model's optimised parameters in the
+ * reference's mu order and, last, the split time; start s is SciPy's Nelder-Mead from starts[s] against row rows[s] on
+ *     f(mu, st) = -JAFSLikelihood(mu) of a model at split time st
+ * as misti_eval_batch evaluates it for a fractional st (MigrationInference.__init__ :89-99: the interval the split falls in is cut in
+ * two).  Replaces the scans of the test.bs scripts - `for st in A..Z` around `MiSTI.py ... ${st} -bs ${bs}`, the arg-max taken per
+ * bootstrap row afterwards, an answer on the PSMC grid - with ONE batched search per call, one start per (row, initial values,
+ * initial split); and it is the only search a model without an optimised parameter has (the `*no.mig.sh` scripts): n_param == 0 is
+ * allowed here, and only here, as a one-coordinate search.
+ * What it is not: the reference has no such search, so there is no reference run to agree with.  The parity target is SciPy's
+ * Nelder-Mead on this engine's own objective (same initial simplex - 5 % or 0.00025 per coordinate, the split included -, same
+ * decisions, xatol over all coordinates alike, the split in grid-index units), and the engine's parity contract is the objective's.
+ * The objective is piecewise in the split (band ends and smoothing runs follow its index); Nelder-Mead is defined on such a function.
+ *   starts       [n_start][n_param + 1]  initial parameters, then the initial split time
+ *   rows         [n_start]               replicate row per start, as misti_nm_solve_rows
+ *   band_bounds  [n_start][n_band][2] or NULL   per start, as misti_nm_solve_bounds (end == -1: the POINT's own split index)
+ *   pulse_times  [n_start][n_pulse] or NULL     per start, as misti_nm_solve_pulses
+ *   n_rep, jsfs, xatol, fatol, maxiter          as misti_nm_solve_rows
+ *   x            [n_start][n_param + 1]  best vertex, the fitted split time last
+ *   llh .. status                        as misti_nm_solve
+ * A point whose split the engine refuses - negative, beyond the grid, no finite coalescent time, bands or pulses broken at that
+ * split - has no value and scores +inf for the optimiser, exactly as -inf from misti_eval_batch would; it is never an argument
+ * error, and other starts are unaffected (a start none of whose points ever has a value returns llh = -inf; a simplex
+ * just beyond the grid may reflect back into it, as SciPy's would).
+ * MISTI_E_LIMIT for a model with n_param + 1 > MISTI_MAX_PARAMS, MISTI_E_ARG for a NULL pointer, n_rep < 1, a row out of range, a
+ * non-finite start coordinate or maxiter < 1 - all before anything touches the device.  Synchronisation and statistics
+ * (misti_nm_last_stats, misti_nm_last_spec_iterations) as misti_nm_solve_rows.
+ * Out of scope: basin hopping, the lanes, the device-list (misti_multi_*) forms and the forward map keep a fixed split per start. */
+int misti_nm_solve_split(misti_ctx* ctx, int64_t n_start, const double* starts, const int32_t* rows,
+                         const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                         double xatol, double fatol, int32_t maxiter,
+                         double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
+
 /* Batched basin hopping: scipy.optimize.basinhopping(func, x0, niter, T, stepsize, minimizer_kwargs=dict(method='Nelder-Mead'),
  * interval, target_accept_rate, stepwise_factor, rng=...) for n_start starts at once - the reference's global search,
  * MigrationInference.Solve(globalOpt=True) (MigrationInference.py:723-725: T = 0.5, Nelder-Mead with SciPy's defaults, i.e.

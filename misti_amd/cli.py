@@ -21,6 +21,12 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               -mi/-pu initial values (the --grid-mi mesh points as starts: the best per pair), all pairs
                               in ONE batched search on the device; per pair the line MiSTI.py:240 prints (the test.bs
                               loops' order: row outer, split inner), then the 97.5 % t-interval of bs_conf_int.ipynb
+    --fit-st                  with --grid-st A B [STEP] (the INITIAL splits) and optionally --all-bs: the split time fitted, not
+                              scanned - for every row one Nelder-Mead search over (optimised parameters, split time) from every
+                              (start, initial split) pair, all in ONE batched search (misti_nm_solve_split); per row the MiSTI.py:240
+                              line of the best search with the fitted, fractional splitT, then (--all-bs) the t-interval of
+                              bs_conf_int.ipynb over the fitted splits.  Needs no optimised -mi / -pu: a model without one is a
+                              one-coordinate search.  Not offered with --sweep, --sweep-pu, --gpus N > 1 or --devices
     --gpus N                  the sweep on N GPUs of the node: this process starts N ranks (one per GPU, torch.distributed over
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
@@ -91,6 +97,8 @@ def build_parser():
     p.add_argument("--devices", type=str, default="", help="grid mode: comma-separated device list evaluated from this one process (misti_create_multi)")
     p.add_argument("--grid-solve", action="store_true",
                    help="with --grid-st / --all-bs: optimise every (replicate, split) pair as the test.bs loops do, in one batched search")
+    p.add_argument("--fit-st", action="store_true",
+                   help="with --grid-st (the initial splits) / --all-bs: fit the split time per row as a coordinate of one batched search")
     p.add_argument("--sweep", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="the GNU-parallel recipe's `::: NAME V1 V2 ...`: {NAME} in the split time or in -mi start / end / rate fields")
     p.add_argument("--sweep-pu", nargs="+", action="append", default=[], metavar=("NAME", "V"),
@@ -108,6 +116,21 @@ def grid_solve_error(a):
         return "--grid-solve runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
     if not (a.sweep or a.sweep_pu) and not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
         return "--grid-solve needs at least one optimised parameter (-mi ... 1 or -pu ... 1)"
+    return None
+
+
+def fit_st_error(a):
+    """Why ``--fit-st`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if not a.fit_st:
+        return None
+    if a.sweep or a.sweep_pu:
+        return "--fit-st fits the split time of ONE model: --sweep / --sweep-pu are not offered with it"
+    if a.gpus > 1 or a.devices:
+        return "--fit-st runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    if a.grid_solve:
+        return "--fit-st fits the split time, --grid-solve scans it: give one of them"
+    if not a.grid_st:
+        return "--fit-st needs --grid-st A B [STEP]: the initial split times of its searches"
     return None
 
 
@@ -266,6 +289,37 @@ def grid_solve(a, inp, rows):
     return 0
 
 
+def fit_st(a, inp, rows):
+    """--fit-st: the split time as a coordinate - per JSFS row one search over (optimised parameters, split) from every (start,
+    initial split) pair, all in ONE misti_nm_solve_split call; the best search per row is printed."""
+    from .optimize import split_fit, split_fit_interval
+    splits, bands, pulses, k, axes = grid_model(a)
+    starts = np.stack([m.ravel() for m in np.meshgrid(*axes, indexing="ij")], axis=1) if k else np.empty((1, 0))
+    data, ids = _data_rows(a, rows)
+    flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    t0 = time.time()
+    with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
+        fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000)
+    dt = time.time() - t0
+    for r in range(data.shape[0]):
+        st = float(fit["split"][r])
+        if not np.isfinite(fit["llh"][r]):
+            print("fit-st: bs_id =", ids[r], "has no finite llh from any start")
+            continue
+        print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, fit["x"][r, :k], fit["llh"][r]))
+    print()
+    if a.all_bs:
+        iv = split_fit_interval(fit["split"], fit["llh"])
+        if iv["interval"] is None:
+            print("fit-st: no bootstrap interval (%d bootstrap rows with a fitted split; at least 2 needed)" % iv["n_boot"])
+        else:
+            print("fit-st: bootstrap fitted splitT mean =", iv["mean"], "95%% t-interval = [%r, %r]" % iv["interval"],
+                  "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
+    print("fit-st: %d rows x %d (start, initial split) pairs in one search, %.3f s; %d rows ended on the iteration cap, %d without a value"
+          % (data.shape[0], starts.shape[0] * len(splits), dt, int((fit["status"] == 2).sum()), int((~np.isfinite(fit["llh"])).sum())))
+    return 0
+
+
 def _sweep_models(a, inp, plan):
     """Which models of the sweep the reference would have run (SetModel's checks; it exits in PrintError for the others), and the
     Engine for them: band and pulse records with the bounds and times of the first of them (every batch passes its own)."""
@@ -389,7 +443,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = sweep_error(a) or grid_solve_error(a)
+    why = fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
@@ -437,6 +491,8 @@ def main(argv=None):
     if a.sweep or a.sweep_pu:
         return sweep_solve(a, inp, rows) if a.grid_solve else sweep_eval(a, inp, rows)
     inp.divergenceTime = a.st
+    if a.fit_st:
+        return fit_st(a, inp, rows)
     if a.grid_solve:
         return grid_solve(a, inp, rows)
     if a.grid_st or a.grid_mi or a.all_bs:

@@ -1003,8 +1003,9 @@ int64_t nm_spec_cap(int N) {
     return misti::FOLLOW_MAX_CHAINS / (4 + N);
 }
 
-int nm_prepare(misti_ctx* c, int64_t n_start, NmWork& w, size_t extra_f64 = 0, size_t extra_i32 = 0) {
-    const int N = c->dm.n_param;
+// `coords`: the simplex's coordinates - the model's parameters (0), or one more: the split time behind them (misti_nm_solve_split).
+int nm_prepare(misti_ctx* c, int64_t n_start, NmWork& w, size_t extra_f64 = 0, size_t extra_i32 = 0, int coords = 0) {
+    const int N = coords > 0 ? coords : c->dm.n_param;
     const size_t S = (size_t)n_start, V = (size_t)N + 1;
     const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
     // one allocation per type: simplices and points | counters and slot tables
@@ -1063,6 +1064,9 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     // split times alone: bounds are whole interval indices and never add a fractional interval (and the hint is verified on the
     // device).  RUN_UNSHARED stays off: starts with the same initial values AND the same bounds still share their chains (the
     // chain key holds the bounds).  RUN_ONE_LENGTH stays off: the splits differ, and so do the chain lengths.
+    // The split as a coordinate (misti_nm_solve_split) is a rows path whose splits are never known to be whole (w.whole is false):
+    // no hint at all - points of different starts with equal parameter bits and bounds still share a chain, computed to the largest
+    // split among them.
     static const int hint_mask = [] { const char* e = getenv("MISTI_NM_HINTS"); return e ? atoi(e) : 7; }();       // diagnostic: which hints the search passes on
     const unsigned nm_hints = (rows ? (w.whole ? RUN_INTEGER_SPLITS : 0u)
                                     : ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH)) & (unsigned)hint_mask;
@@ -1075,6 +1079,9 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
         HIP_TRY(misti::launch_llk_rows(n, w.rjafs, w.rstatus, row, w.table, w.consts, llk, c->unfolded, sm));
         return 0;
     };
+    // split as a coordinate (st.fit_split): the engine reads a batch's parameter vectors from the compact array beside its splits,
+    // not from the points themselves (NULL for a model without parameters, as misti_eval_batch allows)
+    auto pts = [&](const double* points, const double* par) -> const double* { return st.fit_split ? (N > 1 ? par : nullptr) : points; };
     int32_t* cnt = w.cnt;
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
     HIP_TRY(hipMemsetAsync(st.split1, 0xBF, S * sizeof(double), sm));          // all-0xBF bytes: a negative double = "no point in this slot"
@@ -1082,7 +1089,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     if (w.bnd_n) HIP_TRY(hipMemsetAsync(w.bnd0, 0, w.bnd_n * sizeof(int32_t), sm));  // and all-zero bounds (what put_none writes)
     if (w.put_n) HIP_TRY(hipMemsetAsync(w.put0, 0, w.put_n * sizeof(int32_t), sm));  // and all-zero pulse times
     HIP_TRY(misti::launch_nm_init(st, w.d_starts, sm));
-    if (int r = eval((int64_t)(S * V), st.split0, st.sim, st.row0, st.bnd0, st.put0, w.llk0)) return r;
+    if (int r = eval((int64_t)(S * V), st.split0, pts(st.sim, st.par0), st.row0, st.bnd0, st.put0, w.llk0)) return r;
     int cur = 0;
     st.idx_next = w.idx[cur]; st.count_next = cnt + cur;
     HIP_TRY(misti::launch_nm_begin(st, w.llk0, sm));
@@ -1117,7 +1124,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             // of the NEXT iteration and drops the count of live starts into the host's pinned word (nm_spec_step_kernel: the live
             // starts of a speculative iteration fit one workgroup); only the first speculative iteration launches a points kernel
             if (!spec_primed) { HIP_TRY(misti::launch_nm_spec_points(st, bound, sm)); spec_primed = true; }
-            if (int r = eval(bound * K, st.ps_split, st.ps, st.ps_row, st.ps_bnd, st.ps_put, w.llk_spec)) return r;
+            if (int r = eval(bound * K, st.ps_split, pts(st.ps, st.ps_par), st.ps_row, st.ps_bnd, st.ps_put, w.llk_spec)) return r;
             // (no memsets here: the points step zeroes the next slot counter, and the reflection-split array is only read by the
             //  three-batch path, which a search never returns to - the number of live starts only falls)
             misti::NmState nx = st;
@@ -1125,11 +1132,11 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             HIP_TRY(misti::launch_nm_spec_step(st, nx, bound, w.llk_spec, (int32_t*)&live_host[slot], sm));
             ++spec_iters;
         } else {
-            if (int r = eval(bound, st.split1, st.p1, st.row1, st.bnd1, st.put1, w.llk1)) return r;
+            if (int r = eval(bound, st.split1, pts(st.p1, st.par1), st.row1, st.bnd1, st.put1, w.llk1)) return r;
             HIP_TRY(misti::launch_nm_reflect(st, bound, w.llk1, sm));
-            if (int r = eval(bound, st.split2, st.p2, st.row2, st.bnd2, st.put2, w.llk2)) return r;
+            if (int r = eval(bound, st.split2, pts(st.p2, st.par2), st.row2, st.bnd2, st.put2, w.llk2)) return r;
             HIP_TRY(misti::launch_nm_accept(st, bound, w.llk2, sm));
-            if (int r = eval(bound * N, st.split3, st.p3, st.row3, st.bnd3, st.put3, w.llk3)) return r;
+            if (int r = eval(bound * N, st.split3, pts(st.p3, st.par3), st.row3, st.bnd3, st.put3, w.llk3)) return r;
             HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
             HIP_TRY(hipMemsetAsync(st.split1, 0xBF, (size_t)bound * sizeof(double), sm));
             HIP_TRY(misti::launch_nm_finish(st, bound, w.llk3, sm));
@@ -1200,22 +1207,45 @@ int nm_rows_args(int64_t n_start, const double* starts, const double* split_time
     return 0;
 }
 
+// ... and of misti_nm_solve_split, whose starts carry their initial split time as their last coordinate (`coords` per start).
+int nm_split_args(int64_t n_start, int coords, const double* starts, const int32_t* rows, int64_t n_rep, const double* jsfs, int32_t maxiter,
+                  const double* x, const double* llh) {
+    if (!starts || !rows || !jsfs || !x || !llh) return fail(MISTI_E_ARG, "starts / rows / jsfs / x / llh is NULL");
+    if (n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)n_rep);
+    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    for (int64_t s = 0; s < n_start; ++s) {
+        if (rows[s] < 0 || rows[s] >= n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)rows[s], (long long)n_rep);
+        for (int k = 0; k < coords; ++k)
+            if (!std::isfinite(starts[s * coords + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
+    }
+    return 0;
+}
+
 // misti_nm_solve_rows (band_bounds NULL), misti_nm_solve_bounds and misti_nm_solve_pulses (pulse_times set): one implementation.
 // Without bounds nothing of the bounds path is allocated or written, without pulse times nothing of the pulses path, and the search
 // runs exactly the rows path's (the bounds path's) instructions.
+// misti_nm_solve_split (fit_split; split_times NULL) as well: the simplices have one coordinate more, the split time behind the model's
+// parameters, `starts` and `x` are [n_start][n_param + 1], and every workspace is sized for N = n_param + 1.  Only there a model
+// without a parameter has a search.  Without fit_split nothing of it is allocated or written.
 int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                        const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
-                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status, const int32_t* pulse_times = nullptr) {
+                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status, const int32_t* pulse_times = nullptr,
+                       bool fit_split = false) {
     // every argument is checked before the first HIP call
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
-    const int N = c->dm.n_param;
+    const int N = c->dm.n_param + (fit_split ? 1 : 0);
     if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
+    // the sort's local arrays hold MISTI_MAX_PARAMS + 1 vertices (misti_nm.hip: sort_simplex)
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
+    if (fit_split) {
+        if (int r = nm_split_args(n_start, N, starts, rows, n_rep, jsfs, maxiter, x, llh)) return r;
+    } else if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
     if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
     if (n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
-    bool whole = true;
-    for (int64_t s = 0; s < n_start; ++s)
+    bool whole = !fit_split;                     // a fitted split is whole by accident only: never the integer-splits hint
+    for (int64_t s = 0; whole && s < n_start; ++s)
         if (split_times[s] != std::floor(split_times[s])) whole = false;
     if (n_start == 0) return 0;
     HIP_TRY(hipSetDevice(c->device));
@@ -1230,14 +1260,23 @@ int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, cons
     // pulses path: the same for the pulse times (none for a model without pulses)
     const size_t NP = pulse_times ? (size_t)c->dm.n_pulse : 0;
     const size_t put_n = NP * (S * V + 2 * S + S * N + cap * K);                // put0 | put1 | put2 | put3 | ps_put
+    // split path: one parameter vector per slot of every batch (no width for a model without parameters), and no split per start
+    const size_t NQ = fit_split ? (size_t)N - 1 : 0;
+    const size_t par_n = NQ * (S * V + 2 * S + S * N + cap * K);                // par0 | par1 | par2 | par3 | ps_par
     NmWork w;
-    if (int r = nm_prepare(c, n_start, w, S + R * 8 + R + M * 7, S + rows_n + M + S * NB2 + bnd_n + S * NP + put_n)) return r;
+    if (int r = nm_prepare(c, n_start, w, (fit_split ? 0 : S) + R * 8 + R + M * 7 + par_n, S + rows_n + M + S * NB2 + bnd_n + S * NP + put_n,
+                           fit_split ? N : 0)) return r;
     misti::NmState& st = w.st;
     double* d = w.extra_f64;
-    double* d_split = d; d += S;
+    double* d_split = nullptr;
+    if (!fit_split) { d_split = d; d += S; }
     double* d_table = d; d += R * 8;
     double* d_consts = d; d += R;
-    w.rjafs = d;
+    w.rjafs = d; d += M * 7;
+    if (fit_split) {
+        st.fit_split = 1;
+        st.par0 = d; d += S * V * NQ; st.par1 = d; d += S * NQ; st.par2 = d; d += S * NQ; st.par3 = d; d += S * N * NQ; st.ps_par = d;
+    }
     int32_t* q = w.extra_i32;
     int32_t* d_rowof = q; q += S;
     w.rows0 = q; w.rows_n = rows_n;
@@ -1262,7 +1301,7 @@ int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, cons
     w.table = d_table; w.consts = d_consts; w.whole = whole;
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_split, split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (!fit_split) HIP_TRY(hipMemcpyAsync(d_split, split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_rowof, rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
@@ -1307,6 +1346,15 @@ int misti_nm_solve_pulses(misti_ctx* c, int64_t n_start, const double* starts, c
     if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
     return nm_solve_rows_impl(c, n_start, starts, split_times, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs,
                               xatol, fatol, maxiter, x, llh, nit, nfev, status, c && c->dm.n_pulse > 0 ? pulse_times : nullptr);
+}
+
+int misti_nm_solve_split(misti_ctx* c, int64_t n_start, const double* starts, const int32_t* rows, const int32_t* band_bounds,
+                         const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
+                         double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    // a point whose split the engine refuses (negative, beyond the grid, no finite coalescent time, bands or pulses broken at it) is no
+    // argument error: the engine gives it no value and the optimiser +inf, as SciPy sees -JAFSLikelihood = inf
+    return nm_solve_rows_impl(c, n_start, starts, nullptr, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs, xatol, fatol, maxiter,
+                              x, llh, nit, nfev, status, c && c->dm.n_pulse > 0 ? pulse_times : nullptr, true);
 }
 
 int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,

@@ -120,6 +120,10 @@ struct NmState {
     int nb2;                // 2 n_band: int32 per bound set (bounds_of set)
     const int32_t* pulses_of;   // [S][np] or NULL: the pulse times of each start's points (misti_nm_solve_pulses); only with row_of
     int np;                 // n_pulse: int32 per pulse-time set (pulses_of set)
+    int fit_split;          // 1 (misti_nm_solve_split; only with row_of): the LAST of the N coordinates is the point's split time and the first
+                            // N - 1 are the model's parameters - every point laid out for a batch leaves its split in the slot's split and its
+                            // parameters in the compact par arrays below, which the engine batch reads instead of the point arrays.  0: nothing
+                            // of this is written or read
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)
@@ -151,12 +155,17 @@ struct NmState {
     int32_t* put1;          // [S][np]       is set; empty slots carry zeros)
     int32_t* put2;          // [S][np]
     int32_t* put3;          // [S * N][np]
+    double* par0;           // [S * V][N - 1]  the engine's parameter vectors of the four batches, beside split0..3 (fit_split only; NULL for a
+    double* par1;           // [S][N - 1]      model without a parameter: N == 1, the arrays have no width)
+    double* par2;           // [S][N - 1]
+    double* par3;           // [S * N][N - 1]
     // speculative iterations (few live starts: latency-bound): every point SciPy COULD ask for in the iteration, one batch
     double* ps;             // [spec_cap][4 + N][N]  reflection, expansion, outside / inside contraction, the N shrunk vertices
     double* ps_split;       // [spec_cap * (4 + N)]
     int32_t* ps_row;        // [spec_cap * (4 + N)]  or NULL (row_of unset)
     int32_t* ps_bnd;        // [spec_cap * (4 + N)][nb2]  or NULL (bounds_of unset)
     int32_t* ps_put;        // [spec_cap * (4 + N)][np]   or NULL (pulses_of unset)
+    double* ps_par;         // [spec_cap * (4 + N)][N - 1]  (fit_split only)
     int64_t spec_cap;       // live starts up to which an iteration is speculative
     const int32_t* idx_cur; // [S] slot -> start of the iteration in progress
     const int32_t* count_cur;   // [1] its number of live starts

@@ -50,6 +50,8 @@ __device__ __forceinline__ double lin2(double a, double x, double b, double y) {
 // takes them with put_point, an empty slot (or a point the start does not need) a negative split, row 0, all-zero bounds and
 // all-zero pulse times with put_none: no row index ever leaves the table, and a negative split is refused (setup_candidate)
 // before any bound or time of its slot is read.  Without bounds_of / pulses_of / row_of nothing but the split is written.
+// misti_nm_solve_split (fit_split) takes row, bounds and times the same way; the split put_point leaves is then replaced by the
+// point's own (put_coords below).
 __device__ __forceinline__ void put_point(const NmState& st, double* split, int32_t* row, int32_t* bnd, int32_t* put, int64_t j, int64_t s) {
     split[j] = st.split_of ? st.split_of[s] : st.split;
     if (st.row_of) row[j] = st.row_of[s];
@@ -61,6 +63,19 @@ __device__ __forceinline__ void put_none(const NmState& st, double* split, int32
     if (st.row_of) row[j] = 0;
     if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) bnd[j * st.nb2 + k] = 0;
     if (st.pulses_of) for (int k = 0; k < st.np; ++k) put[j * st.np + k] = 0;
+}
+
+// The split as a coordinate (misti_nm_solve_split, st.fit_split): point `pt` of N coordinates goes to slot j of a batch as the split
+// time pt[N - 1] (over what put_point left there) and the parameter vector pt[0 .. N - 2] in the compact array the engine reads.
+// A slot without a point keeps put_none's negative split; put_no_coords gives it all-zero parameters, as the point arrays carry.
+__device__ __forceinline__ void put_coords(const NmState& st, double* split, double* par, int64_t j, const double* pt) {
+    const int P = st.N - 1;
+    split[j] = pt[P];
+    for (int k = 0; k < P; ++k) par[j * P + k] = pt[k];
+}
+__device__ __forceinline__ void put_no_coords(const NmState& st, double* par, int64_t j) {
+    const int P = st.N - 1;
+    for (int k = 0; k < P; ++k) par[j * P + k] = 0.0;
 }
 
 // numpy.argsort on <= 17 values: insertion sort (stable), NaN last
@@ -125,6 +140,7 @@ __device__ void next_reflection(const NmState& st, int64_t s) {
     double* p1 = st.p1 + (int64_t)slot * N;
     for (int k = 0; k < N; ++k) p1[k] = lin2(1.0 + NM_RHO, centroid(x, N, k), NM_RHO, x[N * N + k]);     // xr
     put_point(st, st.split1, st.row1, st.bnd1, st.put1, slot, s);
+    if (st.fit_split) put_coords(st, st.split1, st.par1, slot, p1);
 }
 
 }  // namespace
@@ -143,6 +159,7 @@ void nm_init_kernel(NmState st, const double* __restrict__ starts) {
             x[i * N + k] = y;
         }
         put_point(st, st.split0, st.row0, st.bnd0, st.put0, s * V + i, s);
+        if (st.fit_split) put_coords(st, st.split0, st.par0, s * V + i, x + i * N);
     }
     st.nit[s] = 1; st.nfev[s] = 0; st.done[s] = -1;
 }
@@ -192,6 +209,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     const bool second = kind != NM_REFLECT && kind != NM_CUT;
     if (!second) for (int k = 0; k < N; ++k) p2[k] = 0.0;
     if (second) put_point(st, st.split2, st.row2, st.bnd2, st.put2, i, s); else put_none(st, st.split2, st.row2, st.bnd2, st.put2, i);
+    if (st.fit_split) { if (second) put_coords(st, st.split2, st.par2, i, p2); else put_no_coords(st, st.par2, i); }
 }
 
 // the second value is in: replace the worst vertex, or shrink (then the N shrunk vertices are the third batch)
@@ -239,6 +257,7 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
         const bool live = shrink && j < n_eval;
         if (live) put_point(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j, s); else put_none(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j);
         if (!live) for (int k = 0; k < N; ++k) p3[j * N + k] = 0.0;
+        if (st.fit_split) { if (live) put_coords(st, st.split3, st.par3, i * N + j, p3 + j * N); else put_no_coords(st, st.par3, i * N + j); }
     }
 }
 
@@ -277,7 +296,11 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
     int32_t* rw = st.ps_row ? st.ps_row + i * K : nullptr;
     int32_t* bw = st.ps_bnd ? st.ps_bnd + i * K * st.nb2 : nullptr;
     int32_t* pw = st.ps_put ? st.ps_put + i * K * st.np : nullptr;
-    if (i >= st.count_cur[0]) { for (int j = 0; j < K; ++j) { put_none(st, sp, rw, bw, pw, j); for (int k = 0; k < N; ++k) pt[j * N + k] = 0.0; } return; }
+    double* qw = st.fit_split ? st.ps_par + i * K * (N - 1) : nullptr;
+    if (i >= st.count_cur[0]) {
+        for (int j = 0; j < K; ++j) { put_none(st, sp, rw, bw, pw, j); for (int k = 0; k < N; ++k) pt[j * N + k] = 0.0; if (st.fit_split) put_no_coords(st, qw, j); }
+        return;
+    }
     const int64_t s = st.idx_cur[i];
     const double* x = st.sim + s * (int64_t)V * N;
     const double* p1 = st.p1 + i * N;
@@ -290,6 +313,7 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
         for (int j = 1; j < V; ++j) pt[(3 + j) * N + k] = x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k]));   // shrunk vertex j
     }
     for (int j = 0; j < K; ++j) put_point(st, sp, rw, bw, pw, j, s);
+    if (st.fit_split) for (int j = 0; j < K; ++j) put_coords(st, sp, qw, j, pt + j * N);
 }
 
 __global__ __launch_bounds__(256)

@@ -350,6 +350,37 @@ class Engine:
         return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
                     speculative_iterations=int(spec.value))
 
+    def nm_solve_split(self, starts, rows, table, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
+        """``misti_nm_solve_split``: the split time as the LAST coordinate of every simplex - ``starts`` is ``[S][n_param + 1]``
+        (initial parameters, then the initial split), start s is SciPy's Nelder-Mead over (parameters, split) against
+        ``table[rows[s]]`` (``[n_rep][8]``), all starts in one batched search.  Replaces the ``for st in A..Z`` scans of the
+        reference's ``test.bs`` scripts with a fitted, fractional split, and gives a model without an optimised parameter
+        (``n_param == 0``) its only search.  ``band_bounds`` / ``pulse_times`` per start as in ``nm_solve_pulses`` (band end -1: the
+        point's own split index).  A point whose split the engine refuses scores +inf; a start without any value has ``llh = -inf``.
+        Returns what ``nm_solve`` returns with ``x[S][n_param + 1]``, plus ``split`` (= ``x[:, -1]``)."""
+        N = self.n_param + 1
+        st = _f64(starts, (-1, N))
+        S = st.shape[0]
+        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
+        tab = _f64(table, (-1, 8))
+        bb = pt = None
+        if band_bounds is not None and self.n_band:
+            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(S, self.n_band, 2)
+        if pulse_times is not None and self.n_pulse:
+            pt = np.ascontiguousarray(pulse_times, dtype=np.int32).reshape(S, self.n_pulse)
+        x = np.empty((S, N))
+        llh = np.empty(S)
+        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        _lib.check(self._lib.misti_nm_solve_split(self._ctx, S, ptr(st), ptr(row), ptr(bb), ptr(pt), tab.shape[0], ptr(tab),
+                                                  float(tol), float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
+        stats = (C.c_int64 * 2)()
+        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
+        spec = C.c_int64(0)
+        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
+        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, split=x[:, -1].copy(), iterations_issued=int(stats[0]),
+                    slots=int(stats[1]), speculative_iterations=int(spec.value))
+
     def basinhopping(self, starts, split_time, jsfs_row, rngs, niter=100, T=0.5, stepsize=0.5, interval=50, target_accept_rate=0.5,
                      stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
         """``misti_basinhopping``: ``scipy.optimize.basinhopping(-JAFSLikelihood, x0, niter, T, stepsize,

@@ -332,6 +332,54 @@ def bootstrap_profile_interval(llh, split_values, x=None):
     return out
 
 
+def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
+    """The split time FITTED per row instead of scanned (the ``for st in A..Z`` loops of the reference's ``test.bs`` scripts and the
+    arg-max over them): for every row of ``jsfs_rows`` (``[R][8]``) one search from every (start, initial split) pair - ``starts``
+    ``[Q][n_param]`` (ignored for a model without an optimised parameter), ``split_starts`` ``[P]`` - with the split as the last
+    coordinate of the simplex, all R x Q x P searches in ONE ``misti_nm_solve_split`` call (row outermost, initial split innermost).
+    Per row the best search is kept (``_best_start_profile``'s rule: the first maximum, NaN never wins).  ``band_bounds``
+    (``[n_band][2]``, end -1: the point's own split index) and ``pulse_times`` (``[n_pulse]``) apply to every search.
+    Returns dict(x[R][n_param + 1], split[R], llh[R], nit / nfev / status / start[R] (index into the (start, split) pairs), and the
+    search's work counters)."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.asarray(split_starts, dtype=float).reshape(-1)
+    P = engine.n_param
+    st = np.asarray(starts, dtype=float).reshape(-1, P) if P else np.empty((1, 0))
+    pairs = np.hstack([np.repeat(st, splits.size, axis=0), np.tile(splits, st.shape[0])[:, None]])       # [Q x P][n_param + 1]
+    tile = lambda a, shape: None if a is None else np.asarray(a, dtype=np.int32).reshape(shape)
+
+    def search(r_of, p_of, x0):
+        bb, pt = tile(band_bounds, (1, -1, 2)), tile(pulse_times, (1, -1))
+        return engine.nm_solve_split(x0, r_of, rows, band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
+                                     pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0), tol=tol, maxiter=maxiter)
+    out = _best_start_profile(search, rows.shape[0], 1, pairs)
+    out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+    out["split"] = out["x"][:, -1].copy()
+    return out
+
+
+def split_fit_interval(split, llh, level=0.95):
+    """The ``test.bs/bs_conf_int.ipynb`` reduction over FITTED splits: ``split[R]`` and ``llh[R]`` per row (row 0 the data, rows 1..
+    the bootstrap replicates, as ``split_fit`` returns them); row 0 is reported on its own, and over rows 1..R-1 the Student-t
+    interval (``_t_interval``) of their fitted, fractional splits.  A row without a finite llh (or split) has no fitted split: it is
+    left out and counted, as in ``bootstrap_profile_interval``.  Fewer than two bootstrap rows with a value: no interval.
+    Returns dict(best_split[R] (nan: none), data_split / data_llh (None: none), mean, interval ((lo, hi) or None), n_boot, n_excluded)."""
+    split = np.asarray(split, dtype=float).reshape(-1)
+    llh = np.asarray(llh, dtype=float).reshape(-1)
+    has = np.isfinite(llh) & np.isfinite(split)
+    out = dict(best_split=np.where(has, split, np.nan), data_split=None, data_llh=None, mean=None, interval=None)
+    if has[0]:
+        out["data_split"], out["data_llh"] = float(split[0]), float(llh[0])
+    b = split[1:][has[1:]]
+    out["n_boot"], out["n_excluded"] = int(b.size), int((~has[1:]).sum())
+    if b.size >= 1:
+        out["mean"] = float(b.mean())
+    if b.size >= 2:
+        mean, (lo, hi), _ = _t_interval(b, level)
+        out["interval"] = (float(lo), float(hi))
+    return out
+
+
 def sweep_profile(engine, models, jsfs_rows, starts, tol=1e-4, maxiter=1000):
     """``bootstrap_profile`` with a MODEL axis instead of a split axis: ``models`` is a list of ``(split, band_bounds[n_band][2])``
     (end -1: the model's split index) - the boundary profiles "when did migration start or stop" (the test.bs scripts' Solve per
