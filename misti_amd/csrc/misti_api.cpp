@@ -4,6 +4,7 @@
 //   MigrationInference.__init__ / SetModel   MigrationInference.py:41-289   -> misti_create
 //   JAFSLikelihood                           MigrationInference.py:566-614  -> misti_eval_batch*
 // No CPU fallback: every compute entry point needs a HIP device.
+#include <cassert>
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -968,30 +969,35 @@ int misti_forward_rates(misti_ctx* c, int64_t n_cand, const double* split, const
 
 namespace {
 
+using misti::NmBatch;
+using misti::NM_BATCHES;
+
+// Bump allocation over one buffer.  A workspace's layout is ONE sequence of take() calls, run twice: over a null base to learn the
+// size, then over the buffer to assign the pointers - size and layout cannot disagree.
+template <class T>
+struct Carver {
+    T* base = nullptr;
+    size_t n = 0;
+    T* take(size_t k) { T* p = base ? base + n : nullptr; n += k; return p; }
+};
+
 // Device-resident state of one batched Nelder-Mead run, carved from the context's nm buffers.
 struct NmWork {
     misti::NmState st{};
-    double *llk0 = nullptr, *llk1 = nullptr, *llk2 = nullptr, *llk3 = nullptr, *llk_spec = nullptr;
+    size_t slots[NM_BATCHES] = {};   // slots of every batch of the search, and of all of them
+    size_t n_slots = 0;
+    double* llk[NM_BATCHES] = {};    // [slots] the engine's values of every batch
     double *d_starts = nullptr;      // [S][N] in: start points; out: best vertices
     double *d_llh = nullptr;         // [S]    out: their log-likelihood
     double *d_row = nullptr;         // [8]    the data JSFS
-    double *extra_f64 = nullptr;     // whatever the caller asked for beyond the minimiser's own state
-    int32_t *idx[2] = {nullptr, nullptr}, *cnt = nullptr, *extra_i32 = nullptr;
-    // rows path (misti_nm_solve_rows, st.row_of set): a batch is evaluated without replicates into rjafs / rstatus, then
-    // llk_rows_kernel scores every candidate against its own row of the table
+    int32_t *idx[2] = {nullptr, nullptr}, *cnt = nullptr;
+    // rows path (st.row_of set): a batch is evaluated without replicates into rjafs / rstatus, then llk_rows_kernel scores every
+    // candidate against its own row of the table
     const double* table = nullptr;   // [n_rep][8]
     const double* consts = nullptr;  // [n_rep]  llh_const of every row
     double* rjafs = nullptr;         // [M][7]   M = the largest batch: max(S (N + 1), spec_cap (4 + N))
     int32_t* rstatus = nullptr;      // [M]
-    int32_t* rows0 = nullptr;        // the per-slot row arrays row0 | row1 | row2 | row3 | ps_row, contiguous
-    size_t rows_n = 0;
     bool whole = false;              // every split time of the rows path is an integer
-    // bounds path (misti_nm_solve_bounds, st.bounds_of set): every batch hands the engine its per-slot band bounds
-    int32_t* bnd0 = nullptr;         // the per-slot bound arrays bnd0 | bnd1 | bnd2 | bnd3 | ps_bnd, contiguous
-    size_t bnd_n = 0;
-    // pulses path (misti_nm_solve_pulses, st.pulses_of set): ... and its per-slot pulse times
-    int32_t* put0 = nullptr;         // the per-slot pulse-time arrays put0 | put1 | put2 | put3 | ps_put, contiguous
-    size_t put_n = 0;
 };
 
 // Live starts up to which an iteration is speculative (misti_nm.hip): all 4 + N points of a start in one batch, as long as the
@@ -1003,19 +1009,43 @@ int64_t nm_spec_cap(int N) {
     return misti::FOLLOW_MAX_CHAINS / (4 + N);
 }
 
-// `coords`: the simplex's coordinates - the model's parameters (0), or one more: the split time behind them (misti_nm_solve_split).
-int nm_prepare(misti_ctx* c, int64_t n_start, NmWork& w, size_t extra_f64 = 0, size_t extra_i32 = 0, int coords = 0) {
-    const int N = coords > 0 ? coords : c->dm.n_param;
+// One array per batch of the search, `width` elements per slot.  The five of them lie back to back: nm_run clears a whole kind with
+// ONE memset over n_slots (a memset per batch would be four launches more per kind), so a kind is carved here and nowhere else.
+template <class T>
+void nm_per_slot(NmWork& w, T* NmBatch::*arr, Carver<T>& from, size_t width) {
+    for (int b = 0; b < NM_BATCHES; ++b) w.st.b[b].*arr = from.take(w.slots[b] * width);
+    const NmBatch &first = w.st.b[0], &last = w.st.b[NM_BATCHES - 1];
+    assert(!(first.*arr) || last.*arr + w.slots[NM_BATCHES - 1] * width == first.*arr + w.n_slots * width);
+}
+
+// The minimiser's own state for n_start simplices of N coordinates, then whatever `extra` takes behind it: one allocation per type
+// (simplices, points and values | counters and slot tables).
+template <class Extra>
+int nm_prepare(misti_ctx* c, int64_t n_start, int N, NmWork& w, Extra&& extra) {
     const size_t S = (size_t)n_start, V = (size_t)N + 1;
     const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
-    // one allocation per type: simplices and points | counters and slot tables
-    const size_t f64_n = S * V * N * 2 + S * V + S * N * 2 + S * N * N + S + S * V + 2 * S + S * N      // state + split arrays
-                         + S * V + 2 * S + S * N                                                           // llk of the four batches
-                         + S * N + S + 8                                                                   // inputs / outputs, jsfs row
-                         + cap * K * (N + 2) + extra_f64;                                                  // speculative points, their splits and values
-    const size_t i32_n = 7 * S + 4 + extra_i32;
-    HIP_TRY(c->nm_f64.reserve(f64_n * sizeof(double)));
-    HIP_TRY(c->nm_i32.reserve(i32_n * sizeof(int32_t)));
+    misti::NmState& st = w.st;
+    st.S = n_start; st.N = N; st.spec_cap = (int64_t)cap;
+    const size_t slots[NM_BATCHES] = {S * V, S, S, S * N, cap * K};
+    w.n_slots = 0;
+    for (int b = 0; b < NM_BATCHES; ++b) { w.slots[b] = slots[b]; w.n_slots += slots[b]; }
+    auto layout = [&](Carver<double>& f, Carver<int32_t>& q) {
+        nm_per_slot(w, &NmBatch::pts, f, N);
+        st.sim = st.b[misti::NM_B_INIT].pts;            // the initial batch is the simplices themselves
+        st.scratch = f.take(S * V * N); st.fsim = f.take(S * V); st.fxr = f.take(S);
+        nm_per_slot(w, &NmBatch::split, f, 1);
+        for (int b = 0; b < NM_BATCHES; ++b) w.llk[b] = f.take(w.slots[b]);
+        w.d_starts = f.take(S * N); w.d_llh = f.take(S); w.d_row = f.take(8);
+        st.nit = q.take(S); st.nfev = q.take(S); st.done = q.take(S); st.kind = q.take(S); st.shrunk = q.take(S);
+        w.idx[0] = q.take(S); w.idx[1] = q.take(S);
+        w.cnt = q.take(4);                              // [2] live starts of the iteration in progress / of the next one
+        extra(f, q);
+    };
+    Carver<double> f;
+    Carver<int32_t> q;
+    layout(f, q);
+    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
+    HIP_TRY(c->nm_i32.reserve(q.n * sizeof(int32_t)));
     if (!c->nm_live_host) {
         if (hipHostMalloc((void**)&c->nm_live_host, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
@@ -1023,27 +1053,9 @@ int nm_prepare(misti_ctx* c, int64_t n_start, NmWork& w, size_t extra_f64 = 0, s
             return fail(MISTI_E_HIP, "pinned allocation for the live-start count failed");
         }
     }
-    misti::NmState& st = w.st;
-    st.S = n_start; st.N = N;
-    double* d = c->nm_f64.as<double>();
-    st.sim = d; d += S * V * N; st.scratch = d; d += S * V * N; st.fsim = d; d += S * V;
-    st.p1 = d; d += S * N; st.p2 = d; d += S * N; st.p3 = d; d += S * N * N; st.fxr = d; d += S;
-    st.split0 = d; d += S * V; st.split1 = d; d += S; st.split2 = d; d += S; st.split3 = d; d += S * N;
-    w.llk0 = d; d += S * V;
-    w.llk1 = d; d += S;
-    w.llk2 = d; d += S;
-    w.llk3 = d; d += S * N;
-    w.d_starts = d; d += S * N;
-    w.d_llh = d; d += S;
-    w.d_row = d; d += 8;
-    st.ps = d; d += cap * K * N; st.ps_split = d; d += cap * K; w.llk_spec = d; d += cap * K;
-    st.spec_cap = (int64_t)cap;
-    w.extra_f64 = d;
-    int32_t* q = c->nm_i32.as<int32_t>();
-    st.nit = q; q += S; st.nfev = q; q += S; st.done = q; q += S; st.kind = q; q += S; st.shrunk = q; q += S;
-    w.idx[0] = q; w.idx[1] = q + S; q += 2 * S;
-    w.cnt = q; q += 4;                       // [2] live starts of the iteration in progress / of the next one
-    w.extra_i32 = q;
+    f = Carver<double>{c->nm_f64.as<double>()};
+    q = Carver<int32_t>{c->nm_i32.as<int32_t>()};
+    layout(f, q);
     return 0;
 }
 
@@ -1051,7 +1063,8 @@ int nm_prepare(misti_ctx* c, int64_t n_start, NmWork& w, size_t extra_f64 = 0, s
 // SciPy's counters in st.nit / st.nfev and the termination status in st.shrunk (0 converged, 1 evaluation budget, 2 iteration
 // budget).  Asynchronous except for the 4-byte live counts; results are complete when the stream is.
 int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fatol, int32_t maxiter, int64_t maxfun) {
-    misti::NmState& st = w.st;
+    using namespace misti;
+    NmState& st = w.st;
     const int N = st.N;
     const size_t S = (size_t)st.S, V = (size_t)N + 1;
     st.maxiter = maxiter; st.maxfun = maxfun; st.xatol = xatol; st.fatol = fatol; st.split = split_time;
@@ -1070,29 +1083,31 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     static const int hint_mask = [] { const char* e = getenv("MISTI_NM_HINTS"); return e ? atoi(e) : 7; }();       // diagnostic: which hints the search passes on
     const unsigned nm_hints = (rows ? (w.whole ? RUN_INTEGER_SPLITS : 0u)
                                     : ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH)) & (unsigned)hint_mask;
-    // one engine batch of the search: its values against the one data row, or (rows path) each against its own row
-    // (bounds path: with each slot's own band bounds, pulses path: with its own pulse times - NULL on the other paths)
-    auto eval = [&](int64_t n, const double* split, const double* params, const int32_t* row, const int32_t* bnd, const int32_t* put,
-                    double* llk) -> int {
-        if (!rows) return run_dev(c, n, split, params, nullptr, 1, w.d_row, llk, nullptr, nullptr, nullptr, nullptr, nm_hints);
-        if (int r = run_dev(c, n, split, params, bnd, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints, put)) return r;
-        HIP_TRY(misti::launch_llk_rows(n, w.rjafs, w.rstatus, row, w.table, w.consts, llk, c->unfolded, sm));
+    // the first n slots of one batch through the engine: their values against the one data row, or (rows path) each against its own
+    // row, with each slot's own band bounds and pulse times where the batch carries them.  With the split as a coordinate the engine
+    // reads the batch's compact parameter vectors, not the points (NULL for a model without parameters, as misti_eval_batch allows)
+    auto eval = [&](int which, int64_t n) -> int {
+        const NmBatch& b = st.b[which];
+        const double* params = st.fit_split ? b.par : b.pts;
+        if (!rows) return run_dev(c, n, b.split, params, nullptr, 1, w.d_row, w.llk[which], nullptr, nullptr, nullptr, nullptr, nm_hints);
+        if (int r = run_dev(c, n, b.split, params, b.bnd, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints, b.put)) return r;
+        HIP_TRY(launch_llk_rows(n, w.rjafs, w.rstatus, b.row, w.table, w.consts, w.llk[which], c->unfolded, sm));
         return 0;
     };
-    // split as a coordinate (st.fit_split): the engine reads a batch's parameter vectors from the compact array beside its splits,
-    // not from the points themselves (NULL for a model without parameters, as misti_eval_batch allows)
-    auto pts = [&](const double* points, const double* par) -> const double* { return st.fit_split ? (N > 1 ? par : nullptr) : points; };
     int32_t* cnt = w.cnt;
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
-    HIP_TRY(hipMemsetAsync(st.split1, 0xBF, S * sizeof(double), sm));          // all-0xBF bytes: a negative double = "no point in this slot"
-    if (rows) HIP_TRY(hipMemsetAsync(w.rows0, 0, w.rows_n * sizeof(int32_t), sm));   // row 0 in every slot nothing has written yet
-    if (w.bnd_n) HIP_TRY(hipMemsetAsync(w.bnd0, 0, w.bnd_n * sizeof(int32_t), sm));  // and all-zero bounds (what put_none writes)
-    if (w.put_n) HIP_TRY(hipMemsetAsync(w.put0, 0, w.put_n * sizeof(int32_t), sm));  // and all-zero pulse times
-    HIP_TRY(misti::launch_nm_init(st, w.d_starts, sm));
-    if (int r = eval((int64_t)(S * V), st.split0, pts(st.sim, st.par0), st.row0, st.bnd0, st.put0, w.llk0)) return r;
+    HIP_TRY(hipMemsetAsync(st.b[NM_B_REFLECT].split, 0xBF, S * sizeof(double), sm));    // all-0xBF bytes: a negative double = "no point in this slot"
+    // what put_none writes, in every slot nothing has written yet: row 0, all-zero bounds and pulse times (each kind's five arrays
+    // lie back to back: nm_per_slot)
+    const NmBatch& b0 = st.b[NM_B_INIT];
+    if (b0.row) HIP_TRY(hipMemsetAsync(b0.row, 0, w.n_slots * sizeof(int32_t), sm));
+    if (b0.bnd) HIP_TRY(hipMemsetAsync(b0.bnd, 0, w.n_slots * st.nb2 * sizeof(int32_t), sm));
+    if (b0.put) HIP_TRY(hipMemsetAsync(b0.put, 0, w.n_slots * st.np * sizeof(int32_t), sm));
+    HIP_TRY(launch_nm_init(st, w.d_starts, sm));
+    if (int r = eval(NM_B_INIT, (int64_t)(S * V))) return r;
     int cur = 0;
     st.idx_next = w.idx[cur]; st.count_next = cnt + cur;
-    HIP_TRY(misti::launch_nm_begin(st, w.llk0, sm));
+    HIP_TRY(launch_nm_begin(st, w.llk[NM_B_INIT], sm));
     // The host runs at most two iterations ahead of the device: before issuing iteration k it waits for the event of
     // iteration k - 2 and reads the count of live starts that iteration left in pinned memory (4 bytes; nothing else of
     // the search leaves the device).  That count bounds the live starts of iteration k from above - the number only falls -
@@ -1121,25 +1136,24 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
         const bool spec = bound <= st.spec_cap;
         if (spec) {
             // speculative iteration: every point SciPy could ask for, one batch, one decision kernel - which also lays out the points
-            // of the NEXT iteration and drops the count of live starts into the host's pinned word (nm_spec_step_kernel: the live
-            // starts of a speculative iteration fit one workgroup); only the first speculative iteration launches a points kernel
-            if (!spec_primed) { HIP_TRY(misti::launch_nm_spec_points(st, bound, sm)); spec_primed = true; }
-            if (int r = eval(bound * K, st.ps_split, pts(st.ps, st.ps_par), st.ps_row, st.ps_bnd, st.ps_put, w.llk_spec)) return r;
-            // (no memsets here: the points step zeroes the next slot counter, and the reflection-split array is only read by the
+            // of the NEXT iteration (it sees the two lists swapped) and drops the count of live starts into the host's pinned word
+            // (nm_spec_step_kernel: the live starts of a speculative iteration fit one workgroup); only the first speculative iteration
+            // launches a points kernel
+            if (!spec_primed) { HIP_TRY(launch_nm_spec_points(st, bound, sm)); spec_primed = true; }
+            if (int r = eval(NM_B_SPEC, bound * K)) return r;
+            // (no memsets here: the points step zeroes the next slot counter, and the reflection batch's splits are only read by the
             //  three-batch path, which a search never returns to - the number of live starts only falls)
-            misti::NmState nx = st;
-            nx.idx_cur = st.idx_next; nx.count_cur = st.count_next; nx.idx_next = w.idx[cur]; nx.count_next = cnt + cur;
-            HIP_TRY(misti::launch_nm_spec_step(st, nx, bound, w.llk_spec, (int32_t*)&live_host[slot], sm));
+            HIP_TRY(launch_nm_spec_step(st, bound, w.llk[NM_B_SPEC], (int32_t*)&live_host[slot], sm));
             ++spec_iters;
         } else {
-            if (int r = eval(bound, st.split1, pts(st.p1, st.par1), st.row1, st.bnd1, st.put1, w.llk1)) return r;
-            HIP_TRY(misti::launch_nm_reflect(st, bound, w.llk1, sm));
-            if (int r = eval(bound, st.split2, pts(st.p2, st.par2), st.row2, st.bnd2, st.put2, w.llk2)) return r;
-            HIP_TRY(misti::launch_nm_accept(st, bound, w.llk2, sm));
-            if (int r = eval(bound * N, st.split3, pts(st.p3, st.par3), st.row3, st.bnd3, st.put3, w.llk3)) return r;
+            if (int r = eval(NM_B_REFLECT, bound)) return r;
+            HIP_TRY(launch_nm_reflect(st, bound, w.llk[NM_B_REFLECT], sm));
+            if (int r = eval(NM_B_SECOND, bound)) return r;
+            HIP_TRY(launch_nm_accept(st, bound, w.llk[NM_B_SECOND], sm));
+            if (int r = eval(NM_B_SHRINK, bound * N)) return r;
             HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
-            HIP_TRY(hipMemsetAsync(st.split1, 0xBF, (size_t)bound * sizeof(double), sm));
-            HIP_TRY(misti::launch_nm_finish(st, bound, w.llk3, sm));
+            HIP_TRY(hipMemsetAsync(st.b[NM_B_REFLECT].split, 0xBF, (size_t)bound * sizeof(double), sm));
+            HIP_TRY(launch_nm_finish(st, bound, w.llk[NM_B_SHRINK], sm));
         }
         if (!spec) HIP_TRY(hipMemcpyAsync((void*)&live_host[slot], cnt + (cur ^ 1), sizeof(int32_t), hipMemcpyDeviceToHost, sm));
         HIP_TRY(hipEventRecord(ev[slot], sm));
@@ -1151,7 +1165,118 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     c->nm_slots += slots;
     c->nm_spec_iterations += spec_iters;
     // results (device buffers reused: best vertices over the starts)
-    HIP_TRY(misti::launch_nm_result(st, w.d_starts, w.d_llh, st.shrunk, sm));
+    HIP_TRY(launch_nm_result(st, w.d_starts, w.d_llh, st.shrunk, sm));
+    return 0;
+}
+
+// Best vertices and their log-likelihoods to the host, with the search's own counters where the caller wants them.  Asynchronous.
+int nm_copy_back(misti_ctx* c, const NmWork& w, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    const size_t S = (size_t)w.st.S;
+    hipStream_t sm = c->stream;
+    HIP_TRY(hipMemcpyAsync(x, w.d_starts, S * w.st.N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(llh, w.d_llh, S * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (nit) HIP_TRY(hipMemcpyAsync(nit, w.st.nit, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, w.st.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (status) HIP_TRY(hipMemcpyAsync(status, w.st.shrunk, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    return 0;
+}
+
+// One batched search, as its entry point describes it.
+struct NmSearch {
+    int64_t n_start;
+    const double* starts;            // [n_start][N]
+    enum { ONE_SPLIT, SPLIT_PER_START, SPLIT_FITTED } split;
+    double split_time;               // ONE_SPLIT (misti_nm_solve): the split of every start, `jsfs` is the one data row [8], and nothing below
+                                     // `jsfs` applies - the search the engine evaluates with its replicate epilogue inline
+    const double* split_times;       // SPLIT_PER_START: [n_start].  SPLIT_FITTED: the split is the last of the N = n_param + 1 coordinates
+    const int32_t* rows;             // [n_start] each start's row of ...
+    int64_t n_rep;
+    const double* jsfs;              // ... the table [n_rep][8]: the rows path, llk_rows_kernel behind every batch
+    const int32_t* band_bounds;      // [n_start][n_band][2] or NULL; ignored when the model has no band (as misti_eval_batch)
+    const int32_t* pulse_times;      // [n_start][n_pulse] or NULL; ignored when the model has no pulse (as misti_eval_batch_pulses)
+    double xatol, fatol;
+    int32_t maxiter;
+    double *x, *llh;
+    int32_t *nit, *nfev, *status;
+};
+
+// All five searches.  Every argument is checked before the first HIP call, in one order: what does not depend on the context, the
+// context, what needs the model.  Bounds or times that break SetModel's checks, and a fitted split the engine refuses, are no argument
+// errors: the engine gives such a point status MISTI_BAD_STRUCTURE and no value, the optimiser +inf - as SciPy sees -JAFSLikelihood.
+// A path that is not taken allocates and writes nothing: without bounds nothing of the bounds path, and so on.
+int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
+    const bool rows_path = q.split != NmSearch::ONE_SPLIT, fit_split = q.split == NmSearch::SPLIT_FITTED;
+    const bool per_start = q.split == NmSearch::SPLIT_PER_START;
+    if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
+    if (!q.starts || !q.jsfs || !q.x || !q.llh || (rows_path && !q.rows) || (per_start && !q.split_times))
+        return fail(MISTI_E_ARG, "starts / %s / x / llh is NULL", !rows_path ? "jsfs_row" : (per_start ? "split_times / rows / jsfs" : "rows / jsfs"));
+    if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
+    if (q.maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    bool whole = per_start;                      // a fitted split is whole by accident only: never the integer-splits hint
+    for (int64_t s = 0; rows_path && s < q.n_start; ++s) {
+        if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
+        if (!per_start) continue;
+        if (!std::isfinite(q.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+        if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
+    }
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    const int N = c->dm.n_param + (fit_split ? 1 : 0);
+    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
+    // the sort's local arrays hold MISTI_MAX_PARAMS + 1 vertices (misti_nm.hip: sort_simplex)
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
+    for (int64_t s = 0; fit_split && s < q.n_start; ++s)
+        for (int k = 0; k < N; ++k)
+            if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
+    if (q.n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
+    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
+    if (q.n_start == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = (size_t)q.n_start, V = (size_t)N + 1, R = (size_t)q.n_rep;
+    const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
+    const size_t M = S * V > cap * K ? S * V : cap * K;                         // the largest batch of the search
+    // int32 per bound set and per pulse-time set (none for a model without bands / pulses: the engine has nothing to apply them to),
+    // doubles per compact parameter vector (no width for a model without parameters)
+    const size_t NB2 = rows_path && q.band_bounds ? 2 * (size_t)c->dm.n_band : 0;
+    const size_t NP = rows_path && q.pulse_times ? (size_t)c->dm.n_pulse : 0;
+    const size_t NQ = fit_split ? (size_t)N - 1 : 0;
+    NmWork w;
+    misti::NmState& st = w.st;
+    double *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
+    int32_t *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
+    // rows path: what each start hands its points, then one of it per slot of every batch
+    auto rows_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        if (!rows_path) return;
+        if (per_start) d_split = f.take(S);
+        d_table = f.take(R * 8); d_consts = f.take(R); w.rjafs = f.take(M * 7);
+        if (NQ) nm_per_slot(w, &NmBatch::par, f, NQ);
+        d_rowof = i.take(S);
+        nm_per_slot(w, &NmBatch::row, i, 1);
+        w.rstatus = i.take(M);
+        if (NB2) { d_bounds = i.take(S * NB2); nm_per_slot(w, &NmBatch::bnd, i, NB2); }
+        if (NP) { d_pulses = i.take(S * NP); nm_per_slot(w, &NmBatch::put, i, NP); }
+    };
+    if (int r = nm_prepare(c, q.n_start, N, w, rows_layout)) return r;
+    st.fit_split = fit_split ? 1 : 0;
+    st.split_of = d_split; st.row_of = d_rowof;
+    st.bounds_of = d_bounds; st.nb2 = (int)NB2;
+    st.pulses_of = d_pulses; st.np = (int)NP;
+    w.table = d_table; w.consts = d_consts; w.whole = whole;
+    hipStream_t sm = c->stream;
+    HIP_TRY(hipMemcpyAsync(w.d_starts, q.starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (!rows_path) HIP_TRY(hipMemcpyAsync(w.d_row, q.jsfs, 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (per_start) HIP_TRY(hipMemcpyAsync(d_split, q.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (rows_path) HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (rows_path) {
+        HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+        HIP_TRY(misti::launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));      // once per call, every row
+    }
+    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
+    if (int r = nm_run(c, w, rows_path ? 0.0 : q.split_time, q.xatol, q.fatol, q.maxiter, INT64_MAX)) return r;
+    if (int r = nm_copy_back(c, w, q.x, q.llh, q.nit, q.nfev, q.status)) return r;
+    HIP_TRY(hipStreamSynchronize(sm));
     return 0;
 }
 
@@ -1162,199 +1287,36 @@ extern "C" {
 int misti_nm_solve(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
                    double xatol, double fatol, int32_t maxiter,
                    double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
-    if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
-    if (n_start == 0) return 0;
-    const int N = c->dm.n_param;
-    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    if (!starts || !jsfs_row || !x || !llh) return fail(MISTI_E_ARG, "starts / jsfs_row / x / llh is NULL");
-    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
-    if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)n_start;
-    NmWork w;
-    if (int r = nm_prepare(c, n_start, w)) return r;
-    hipStream_t sm = c->stream;
-    HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(w.d_row, jsfs_row, 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    if (int r = nm_run(c, w, split_time, xatol, fatol, maxiter, INT64_MAX)) return r;
-    HIP_TRY(hipMemcpyAsync(x, w.d_starts, S * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(llh, w.d_llh, S * sizeof(double), hipMemcpyDeviceToHost, sm));
-    if (nit) HIP_TRY(hipMemcpyAsync(nit, w.st.nit, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, w.st.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (status) HIP_TRY(hipMemcpyAsync(status, w.st.shrunk, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipStreamSynchronize(sm));
-    return 0;
+    return nm_solve_impl(c, {n_start, starts, NmSearch::ONE_SPLIT, split_time, nullptr, nullptr, 1, jsfs_row, nullptr, nullptr,
+                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
 }
-
-}  // extern "C"
-
-namespace {
-
-// What the rows searches ask of their arguments whatever the context is (nothing here reads it).
-int nm_rows_args(int64_t n_start, const double* starts, const double* split_times, const int32_t* rows, int64_t n_rep, const double* jsfs,
-                 int32_t maxiter, const double* x, const double* llh) {
-    if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
-    if (!starts || !split_times || !rows || !jsfs || !x || !llh) return fail(MISTI_E_ARG, "starts / split_times / rows / jsfs / x / llh is NULL");
-    if (n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)n_rep);
-    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
-    for (int64_t s = 0; s < n_start; ++s) {
-        if (rows[s] < 0 || rows[s] >= n_rep)
-            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)rows[s], (long long)n_rep);
-        if (!std::isfinite(split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
-    }
-    return 0;
-}
-
-// ... and of misti_nm_solve_split, whose starts carry their initial split time as their last coordinate (`coords` per start).
-int nm_split_args(int64_t n_start, int coords, const double* starts, const int32_t* rows, int64_t n_rep, const double* jsfs, int32_t maxiter,
-                  const double* x, const double* llh) {
-    if (!starts || !rows || !jsfs || !x || !llh) return fail(MISTI_E_ARG, "starts / rows / jsfs / x / llh is NULL");
-    if (n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)n_rep);
-    if (maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
-    for (int64_t s = 0; s < n_start; ++s) {
-        if (rows[s] < 0 || rows[s] >= n_rep)
-            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)rows[s], (long long)n_rep);
-        for (int k = 0; k < coords; ++k)
-            if (!std::isfinite(starts[s * coords + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
-    }
-    return 0;
-}
-
-// misti_nm_solve_rows (band_bounds NULL), misti_nm_solve_bounds and misti_nm_solve_pulses (pulse_times set): one implementation.
-// Without bounds nothing of the bounds path is allocated or written, without pulse times nothing of the pulses path, and the search
-// runs exactly the rows path's (the bounds path's) instructions.
-// misti_nm_solve_split (fit_split; split_times NULL) as well: the simplices have one coordinate more, the split time behind the model's
-// parameters, `starts` and `x` are [n_start][n_param + 1], and every workspace is sized for N = n_param + 1.  Only there a model
-// without a parameter has a search.  Without fit_split nothing of it is allocated or written.
-int nm_solve_rows_impl(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
-                       const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
-                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status, const int32_t* pulse_times = nullptr,
-                       bool fit_split = false) {
-    // every argument is checked before the first HIP call
-    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
-    if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
-    const int N = c->dm.n_param + (fit_split ? 1 : 0);
-    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    // the sort's local arrays hold MISTI_MAX_PARAMS + 1 vertices (misti_nm.hip: sort_simplex)
-    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
-    if (fit_split) {
-        if (int r = nm_split_args(n_start, N, starts, rows, n_rep, jsfs, maxiter, x, llh)) return r;
-    } else if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
-    if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
-    if (n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
-    bool whole = !fit_split;                     // a fitted split is whole by accident only: never the integer-splits hint
-    for (int64_t s = 0; whole && s < n_start; ++s)
-        if (split_times[s] != std::floor(split_times[s])) whole = false;
-    if (n_start == 0) return 0;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)n_start, V = (size_t)N + 1, R = (size_t)n_rep;
-    const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
-    const size_t M = S * V > cap * K ? S * V : cap * K;                         // the largest batch of the search
-    const size_t rows_n = S * V + 2 * S + S * N + cap * K;                       // row0 | row1 | row2 | row3 | ps_row
-    // bounds path: the per-start bound sets, then one bound set per slot of every batch (none for a model without bands: the
-    // engine has nothing to apply them to)
-    const size_t NB2 = band_bounds ? 2 * (size_t)c->dm.n_band : 0;
-    const size_t bnd_n = NB2 * (S * V + 2 * S + S * N + cap * K);               // bnd0 | bnd1 | bnd2 | bnd3 | ps_bnd
-    // pulses path: the same for the pulse times (none for a model without pulses)
-    const size_t NP = pulse_times ? (size_t)c->dm.n_pulse : 0;
-    const size_t put_n = NP * (S * V + 2 * S + S * N + cap * K);                // put0 | put1 | put2 | put3 | ps_put
-    // split path: one parameter vector per slot of every batch (no width for a model without parameters), and no split per start
-    const size_t NQ = fit_split ? (size_t)N - 1 : 0;
-    const size_t par_n = NQ * (S * V + 2 * S + S * N + cap * K);                // par0 | par1 | par2 | par3 | ps_par
-    NmWork w;
-    if (int r = nm_prepare(c, n_start, w, (fit_split ? 0 : S) + R * 8 + R + M * 7 + par_n, S + rows_n + M + S * NB2 + bnd_n + S * NP + put_n,
-                           fit_split ? N : 0)) return r;
-    misti::NmState& st = w.st;
-    double* d = w.extra_f64;
-    double* d_split = nullptr;
-    if (!fit_split) { d_split = d; d += S; }
-    double* d_table = d; d += R * 8;
-    double* d_consts = d; d += R;
-    w.rjafs = d; d += M * 7;
-    if (fit_split) {
-        st.fit_split = 1;
-        st.par0 = d; d += S * V * NQ; st.par1 = d; d += S * NQ; st.par2 = d; d += S * NQ; st.par3 = d; d += S * N * NQ; st.ps_par = d;
-    }
-    int32_t* q = w.extra_i32;
-    int32_t* d_rowof = q; q += S;
-    w.rows0 = q; w.rows_n = rows_n;
-    st.row0 = q; q += S * V; st.row1 = q; q += S; st.row2 = q; q += S; st.row3 = q; q += S * N; st.ps_row = q; q += cap * K;
-    w.rstatus = q; q += M;
-    int32_t* d_bounds = nullptr;
-    if (NB2) {
-        d_bounds = q; q += S * NB2;
-        w.bnd0 = q; w.bnd_n = bnd_n;
-        st.bnd0 = q; q += S * V * NB2; st.bnd1 = q; q += S * NB2; st.bnd2 = q; q += S * NB2; st.bnd3 = q; q += S * N * NB2; st.ps_bnd = q;
-        st.bounds_of = d_bounds; st.nb2 = (int)NB2;
-        q = st.ps_bnd + cap * K * NB2;
-    }
-    int32_t* d_pulses = nullptr;
-    if (NP) {
-        d_pulses = q; q += S * NP;
-        w.put0 = q; w.put_n = put_n;
-        st.put0 = q; q += S * V * NP; st.put1 = q; q += S * NP; st.put2 = q; q += S * NP; st.put3 = q; q += S * N * NP; st.ps_put = q;
-        st.pulses_of = d_pulses; st.np = (int)NP;
-    }
-    st.split_of = d_split; st.row_of = d_rowof;
-    w.table = d_table; w.consts = d_consts; w.whole = whole;
-    hipStream_t sm = c->stream;
-    HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (!fit_split) HIP_TRY(hipMemcpyAsync(d_split, split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_rowof, rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_table, jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(misti::launch_llh_const(n_rep, d_table, d_consts, c->unfolded, sm));          // once per call, every row
-    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    if (int r = nm_run(c, w, 0.0, xatol, fatol, maxiter, INT64_MAX)) return r;
-    HIP_TRY(hipMemcpyAsync(x, w.d_starts, S * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(llh, w.d_llh, S * sizeof(double), hipMemcpyDeviceToHost, sm));
-    if (nit) HIP_TRY(hipMemcpyAsync(nit, st.nit, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, st.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (status) HIP_TRY(hipMemcpyAsync(status, st.shrunk, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipStreamSynchronize(sm));
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
 
 int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                         int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                         double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_rows_impl(c, n_start, starts, split_times, rows, nullptr, n_rep, jsfs, xatol, fatol, maxiter, x, llh, nit, nfev, status);
+    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, nullptr, nullptr,
+                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
 }
 
 int misti_nm_solve_bounds(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                           double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    // bounds that break SetModel's checks are no argument error: the engine gives that start's points status MISTI_BAD_STRUCTURE
-    // (llh = -inf), as it does for an invalid split; a model without bands has nothing to apply them to (as misti_eval_batch)
-    return nm_solve_rows_impl(c, n_start, starts, split_times, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs,
-                              xatol, fatol, maxiter, x, llh, nit, nfev, status);
+    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, band_bounds, nullptr,
+                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
 }
 
 int misti_nm_solve_pulses(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double xatol, double fatol,
                           int32_t maxiter, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    // times that break SetModel's checks are no argument error either: that start's points get MISTI_BAD_STRUCTURE (llh = -inf);
-    // a model without pulses has nothing to apply them to (as misti_eval_batch_pulses).  The arguments that do not depend on the
-    // context are checked first: their errors are reported without one.
-    if (int r = nm_rows_args(n_start, starts, split_times, rows, n_rep, jsfs, maxiter, x, llh)) return r;
-    return nm_solve_rows_impl(c, n_start, starts, split_times, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs,
-                              xatol, fatol, maxiter, x, llh, nit, nfev, status, c && c->dm.n_pulse > 0 ? pulse_times : nullptr);
+    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, band_bounds, pulse_times,
+                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
 }
 
 int misti_nm_solve_split(misti_ctx* c, int64_t n_start, const double* starts, const int32_t* rows, const int32_t* band_bounds,
                          const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                          double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    // a point whose split the engine refuses (negative, beyond the grid, no finite coalescent time, bands or pulses broken at it) is no
-    // argument error: the engine gives it no value and the optimiser +inf, as SciPy sees -JAFSLikelihood = inf
-    return nm_solve_rows_impl(c, n_start, starts, nullptr, rows, c && c->dm.n_band > 0 ? band_bounds : nullptr, n_rep, jsfs, xatol, fatol, maxiter,
-                              x, llh, nit, nfev, status, c && c->dm.n_pulse > 0 ? pulse_times : nullptr, true);
+    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_FITTED, 0.0, nullptr, rows, n_rep, jsfs, band_bounds, pulse_times,
+                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
 }
 
 int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
@@ -1372,18 +1334,19 @@ int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, doub
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = (size_t)n_start, U = S * (size_t)niter * (size_t)(N + 1);
     NmWork w;
-    if (int r = nm_prepare(c, n_start, w, S * N * 3 + S * 3 + U, 7 * S)) return r;
     misti::BhState bh{};
     bh.S = n_start; bh.N = N;
     bh.beta = T != 0.0 ? 1.0 / T : INFINITY;
     bh.target = target_accept_rate; bh.factor = stepwise_factor; bh.interval = interval;
-    double* d = w.extra_f64;
-    bh.x_cur = d; d += S * N; bh.x_best = d; d += S * N;
-    double* d_trial = d; d += S * N;
-    bh.f_cur = d; d += S; bh.f_best = d; d += S; bh.stepsize = d; d += S;
-    double* d_uni = d;
-    int32_t* q = w.extra_i32;
-    bh.ok_cur = q; q += S; bh.ok_best = q; q += S; bh.nstep = q; q += S; bh.naccept = q; q += S; bh.nfev = q; q += S; bh.failures = q; q += S; bh.accepted = q;
+    double *d_trial = nullptr, *d_uni = nullptr;
+    auto bh_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        bh.x_cur = f.take(S * N); bh.x_best = f.take(S * N); d_trial = f.take(S * N);
+        bh.f_cur = f.take(S); bh.f_best = f.take(S); bh.stepsize = f.take(S);
+        d_uni = f.take(U);
+        bh.ok_cur = i.take(S); bh.ok_best = i.take(S); bh.nstep = i.take(S); bh.naccept = i.take(S);
+        bh.nfev = i.take(S); bh.failures = i.take(S); bh.accepted = i.take(S);
+    };
+    if (int r = nm_prepare(c, n_start, N, w, bh_layout)) return r;
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(w.d_row, jsfs_row, 8 * sizeof(double), hipMemcpyHostToDevice, sm));
@@ -1404,8 +1367,7 @@ int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, doub
         HIP_TRY(misti::launch_bh_update(bh, w.st, w.d_starts, w.d_llh, w.st.shrunk, hop, niter, d_uni, sm));
     }
     HIP_TRY(misti::launch_bh_result(bh, w.d_starts, w.d_llh, sm));
-    HIP_TRY(hipMemcpyAsync(x, w.d_starts, S * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(llh, w.d_llh, S * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (int r = nm_copy_back(c, w, x, llh, nullptr, nullptr, nullptr)) return r;
     if (nfev) HIP_TRY(hipMemcpyAsync(nfev, bh.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     if (failures) HIP_TRY(hipMemcpyAsync(failures, bh.failures, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     if (accepted) HIP_TRY(hipMemcpyAsync(accepted, bh.accepted, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));

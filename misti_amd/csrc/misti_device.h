@@ -107,6 +107,23 @@ __device__ __forceinline__ int chain_len(const ChainBufs& cb, int64_t ch) { retu
 // Batched Nelder-Mead (misti_nm.hip): everything a start owns, in HBM.  V = N + 1 vertices.
 enum { NM_NONE = 0, NM_REFLECT = 1, NM_EXPAND = 2, NM_CONTRACT = 3, NM_INSIDE = 4,
        NM_CUT = 5 };        // the evaluation budget (maxfev) ran out before the iteration's second point: SciPy abandons the iteration there
+// One engine batch of the search: what each of its slots hands the engine.  Everything a start passes on to its points beyond their
+// coordinates is a field here - and nowhere else.  The five batches' arrays of one kind are one contiguous block, in the order of the
+// enum below (the host clears a kind with one memset).
+struct NmBatch {
+    double* pts;            // [slots][N]      the points
+    double* split;          // [slots]         their split times (negative: no point in this slot)
+    int32_t* row;           // [slots]         their replicate rows (NULL unless row_of is set; empty slots carry row 0)
+    int32_t* bnd;           // [slots][nb2]    their band bounds (NULL unless bounds_of is set; empty slots carry zeros)
+    int32_t* put;           // [slots][np]     their pulse times (NULL unless pulses_of is set; empty slots carry zeros)
+    double* par;            // [slots][N - 1]  the engine's parameter vectors (fit_split only; NULL otherwise, and for a model without a
+                            //                 parameter: N == 1, the array has no width)
+};
+// The batches of a search and their slots: the initial simplices [S * V] (pts is `sim` itself); per iteration, live starts compacted,
+// the reflection points [S], the expansion / contraction points [S] and the shrunk vertices [S * N]; or, speculative iterations (few
+// live starts: latency-bound), every point SciPy COULD ask for in the iteration as one batch [spec_cap * (4 + N)]: per live start the
+// reflection, expansion, outside / inside contraction and the N shrunk vertices.
+enum { NM_B_INIT, NM_B_REFLECT, NM_B_SECOND, NM_B_SHRINK, NM_B_SPEC, NM_BATCHES };
 struct NmState {
     int64_t S;              // starts
     int N;                  // parameters
@@ -122,8 +139,8 @@ struct NmState {
     int np;                 // n_pulse: int32 per pulse-time set (pulses_of set)
     int fit_split;          // 1 (misti_nm_solve_split; only with row_of): the LAST of the N coordinates is the point's split time and the first
                             // N - 1 are the model's parameters - every point laid out for a batch leaves its split in the slot's split and its
-                            // parameters in the compact par arrays below, which the engine batch reads instead of the point arrays.  0: nothing
-                            // of this is written or read
+                            // parameters in the batch's compact `par`, which the engine reads instead of the points.  0: nothing of this is
+                            // written or read
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)
@@ -135,40 +152,10 @@ struct NmState {
     int32_t* kind;          // [S] NM_* of the iteration in progress
     int32_t* shrunk;        // [S] 0: no shrink in the iteration in progress; 1 + n: a shrink of which n vertices were evaluated (n < N: the budget
                             //     ran out inside it - vertex n + 1 is moved but keeps its old value, the rest is untouched, as in SciPy)
-    // per slot of the iteration's batches (live starts compacted)
-    double* p1;             // [S][N]    reflection points
-    double* p2;             // [S][N]    expansion / contraction points
-    double* p3;             // [S][N][N] shrunk vertices
-    double* split0;         // [S * V]   split time per engine candidate of the initial batch
-    double* split1;         // [S]       ... of the reflection batch (negative: no point in this slot)
-    double* split2;         // [S]
-    double* split3;         // [S * N]
-    int32_t* row0;          // [S * V]   replicate row per engine candidate of the four batches, beside split0..3 (NULL unless row_of
-    int32_t* row1;          // [S]       is set; empty slots carry row 0)
-    int32_t* row2;          // [S]
-    int32_t* row3;          // [S * N]
-    int32_t* bnd0;          // [S * V][nb2]  band bounds per engine candidate of the four batches, beside row0..3 (NULL unless bounds_of
-    int32_t* bnd1;          // [S][nb2]      is set; empty slots carry zeros)
-    int32_t* bnd2;          // [S][nb2]
-    int32_t* bnd3;          // [S * N][nb2]
-    int32_t* put0;          // [S * V][np]   pulse times per engine candidate of the four batches, beside bnd0..3 (NULL unless pulses_of
-    int32_t* put1;          // [S][np]       is set; empty slots carry zeros)
-    int32_t* put2;          // [S][np]
-    int32_t* put3;          // [S * N][np]
-    double* par0;           // [S * V][N - 1]  the engine's parameter vectors of the four batches, beside split0..3 (fit_split only; NULL for a
-    double* par1;           // [S][N - 1]      model without a parameter: N == 1, the arrays have no width)
-    double* par2;           // [S][N - 1]
-    double* par3;           // [S * N][N - 1]
-    // speculative iterations (few live starts: latency-bound): every point SciPy COULD ask for in the iteration, one batch
-    double* ps;             // [spec_cap][4 + N][N]  reflection, expansion, outside / inside contraction, the N shrunk vertices
-    double* ps_split;       // [spec_cap * (4 + N)]
-    int32_t* ps_row;        // [spec_cap * (4 + N)]  or NULL (row_of unset)
-    int32_t* ps_bnd;        // [spec_cap * (4 + N)][nb2]  or NULL (bounds_of unset)
-    int32_t* ps_put;        // [spec_cap * (4 + N)][np]   or NULL (pulses_of unset)
-    double* ps_par;         // [spec_cap * (4 + N)][N - 1]  (fit_split only)
+    NmBatch b[NM_BATCHES];  // per slot of the batches; the kernels index it with constants only (a by-value argument stays in registers)
     int64_t spec_cap;       // live starts up to which an iteration is speculative
-    const int32_t* idx_cur; // [S] slot -> start of the iteration in progress
-    const int32_t* count_cur;   // [1] its number of live starts
+    int32_t* idx_cur;       // [S] slot -> start of the iteration in progress (read only; the next iteration's idx_next)
+    int32_t* count_cur;     // [1] its number of live starts
     int32_t* idx_next;      // [S] slot -> start of the next iteration (filled by the kernel that ends this one)
     int32_t* count_next;    // [1]
 };
@@ -179,7 +166,7 @@ hipError_t launch_nm_accept(const NmState& st, int64_t bound, const double* llk2
 hipError_t launch_nm_finish(const NmState& st, int64_t bound, const double* llk3, hipStream_t stream);
 hipError_t launch_nm_result(const NmState& st, double* x, double* llh, int32_t* status, hipStream_t stream);
 hipError_t launch_nm_spec_points(const NmState& st, int64_t bound, hipStream_t stream);
-hipError_t launch_nm_spec_step(const NmState& st, const NmState& nx, int64_t bound, const double* llk, int32_t* live_host, hipStream_t stream);
+hipError_t launch_nm_spec_step(const NmState& st, int64_t bound, const double* llk, int32_t* live_host, hipStream_t stream);
 hipError_t launch_nm_spec_finish(const NmState& st, int64_t bound, const double* llk, hipStream_t stream);
 
 // Batched basin hopping (scipy.optimize.basinhopping with Nelder-Mead as the local minimiser; reference semantics

@@ -44,38 +44,32 @@ __device__ __forceinline__ double rn(double v) { __asm__ volatile("" : "+v"(v));
 // a*x - b*y with a rounding after each product and after the difference (NumPy elementwise semantics)
 __device__ __forceinline__ double lin2(double a, double x, double b, double y) { return rn(a * x) - rn(b * y); }
 
-// The split time, replicate row, band bounds and pulse times of start s's points: one split for all starts (misti_nm_solve), or
-// per start (misti_nm_solve_rows: row_of set, and with it the per-slot row arrays; misti_nm_solve_bounds: bounds_of set as well,
-// and the per-slot bound arrays; misti_nm_solve_pulses: pulses_of set, and the per-slot pulse-time arrays).  Slot j of a batch
-// takes them with put_point, an empty slot (or a point the start does not need) a negative split, row 0, all-zero bounds and
-// all-zero pulse times with put_none: no row index ever leaves the table, and a negative split is refused (setup_candidate)
-// before any bound or time of its slot is read.  Without bounds_of / pulses_of / row_of nothing but the split is written.
-// misti_nm_solve_split (fit_split) takes row, bounds and times the same way; the split put_point leaves is then replaced by the
-// point's own (put_coords below).
-__device__ __forceinline__ void put_point(const NmState& st, double* split, int32_t* row, int32_t* bnd, int32_t* put, int64_t j, int64_t s) {
-    split[j] = st.split_of ? st.split_of[s] : st.split;
-    if (st.row_of) row[j] = st.row_of[s];
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) bnd[j * st.nb2 + k] = st.bounds_of[s * st.nb2 + k];
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) put[j * st.np + k] = st.pulses_of[s * st.np + k];
-}
-__device__ __forceinline__ void put_none(const NmState& st, double* split, int32_t* row, int32_t* bnd, int32_t* put, int64_t j) {
-    split[j] = -1.0;
-    if (st.row_of) row[j] = 0;
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) bnd[j * st.nb2 + k] = 0;
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) put[j * st.np + k] = 0;
-}
-
-// The split as a coordinate (misti_nm_solve_split, st.fit_split): point `pt` of N coordinates goes to slot j of a batch as the split
-// time pt[N - 1] (over what put_point left there) and the parameter vector pt[0 .. N - 2] in the compact array the engine reads.
-// A slot without a point keeps put_none's negative split; put_no_coords gives it all-zero parameters, as the point arrays carry.
-__device__ __forceinline__ void put_coords(const NmState& st, double* split, double* par, int64_t j, const double* pt) {
+// What a slot of a batch hands the engine beside its point.  put_point: slot j of batch b carries start s's point pt (the slot's entry
+// of b.pts, already written) - the start's split time, replicate row, band bounds and pulse times: one split for all starts (misti_nm_solve), or per
+// start (misti_nm_solve_rows: row_of set; misti_nm_solve_bounds: bounds_of as well; misti_nm_solve_pulses: pulses_of).  With the split
+// as a coordinate (misti_nm_solve_split, fit_split) the split is the point's own last coordinate and the coordinates before it go to
+// the compact parameter array the engine reads.  Arrays of a path that is not taken are NULL and nothing is written to them.
+__device__ __forceinline__ void put_point(const NmState& st, const NmBatch& b, int64_t j, int64_t s, const double* pt) {
     const int P = st.N - 1;
-    split[j] = pt[P];
-    for (int k = 0; k < P; ++k) par[j * P + k] = pt[k];
+    b.split[j] = st.split_of ? st.split_of[s] : st.split;
+    if (st.row_of) b.row[j] = st.row_of[s];
+    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[j * st.nb2 + k] = st.bounds_of[s * st.nb2 + k];
+    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[j * st.np + k] = st.pulses_of[s * st.np + k];
+    if (st.fit_split) { b.split[j] = pt[P]; for (int k = 0; k < P; ++k) b.par[j * P + k] = pt[k]; }
 }
-__device__ __forceinline__ void put_no_coords(const NmState& st, double* par, int64_t j) {
+// put_none: slot j carries no point (a start that needs none in this phase) - a negative split, row 0, all-zero bounds, pulse times and
+// parameters, a zeroed point: no row index ever leaves the table, and a negative split is refused (setup_candidate) before any bound or
+// time of its slot is read.  pt: the slot's entry of b.pts, or NULL for a slot that has no START either: such a slot keeps whatever
+// point and parameters it held.
+__device__ __forceinline__ void put_none(const NmState& st, const NmBatch& b, int64_t j, double* pt) {
     const int P = st.N - 1;
-    for (int k = 0; k < P; ++k) par[j * P + k] = 0.0;
+    b.split[j] = -1.0;
+    if (st.row_of) b.row[j] = 0;
+    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[j * st.nb2 + k] = 0;
+    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[j * st.np + k] = 0;
+    if (!pt) return;
+    for (int k = 0; k < st.N; ++k) pt[k] = 0.0;
+    if (st.fit_split) for (int k = 0; k < P; ++k) b.par[j * P + k] = 0.0;
 }
 
 // numpy.argsort on <= 17 values: insertion sort (stable), NaN last
@@ -137,10 +131,10 @@ __device__ void next_reflection(const NmState& st, int64_t s) {
     }
     const int slot = atomicAdd(st.count_next, 1);           // which slot a start gets never matters: a point's value does not depend on the batch
     st.idx_next[slot] = (int32_t)s;
-    double* p1 = st.p1 + (int64_t)slot * N;
+    const NmBatch& b = st.b[NM_B_REFLECT];
+    double* p1 = b.pts + (int64_t)slot * N;
     for (int k = 0; k < N; ++k) p1[k] = lin2(1.0 + NM_RHO, centroid(x, N, k), NM_RHO, x[N * N + k]);     // xr
-    put_point(st, st.split1, st.row1, st.bnd1, st.put1, slot, s);
-    if (st.fit_split) put_coords(st, st.split1, st.par1, slot, p1);
+    put_point(st, b, slot, s, p1);
 }
 
 }  // namespace
@@ -158,8 +152,7 @@ void nm_init_kernel(NmState st, const double* __restrict__ starts) {
             if (i == k + 1) y = (y != 0.0) ? rn((1.0 + NM_NONZDELT) * y) : NM_ZDELT;
             x[i * N + k] = y;
         }
-        put_point(st, st.split0, st.row0, st.bnd0, st.put0, s * V + i, s);
-        if (st.fit_split) put_coords(st, st.split0, st.par0, s * V + i, x + i * N);
+        put_point(st, st.b[NM_B_INIT], s * V + i, s, x + i * N);
     }
     st.nit[s] = 1; st.nfev[s] = 0; st.done[s] = -1;
 }
@@ -183,9 +176,10 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= bound) return;
     const int N = st.N, V = N + 1;
-    if (i >= st.count_cur[0]) { put_none(st, st.split2, st.row2, st.bnd2, st.put2, i); return; }         // no start in this slot
+    const NmBatch& b = st.b[NM_B_SECOND];
+    if (i >= st.count_cur[0]) { put_none(st, b, i, nullptr); return; }         // no start in this slot
     const int64_t s = st.idx_cur[i];
-    double* p2 = st.p2 + i * N;
+    double* p2 = b.pts + i * N;
     const double* f = st.fsim + s * V;
     const double* x = st.sim + s * (int64_t)V * N;
     const double fxr = objective(llk1[i]);
@@ -206,10 +200,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     }
     if (kind != NM_REFLECT && (int64_t)st.nfev[s] >= st.maxfun) kind = NM_CUT;      // the second point's evaluation is refused
     st.kind[s] = kind;
-    const bool second = kind != NM_REFLECT && kind != NM_CUT;
-    if (!second) for (int k = 0; k < N; ++k) p2[k] = 0.0;
-    if (second) put_point(st, st.split2, st.row2, st.bnd2, st.put2, i, s); else put_none(st, st.split2, st.row2, st.bnd2, st.put2, i);
-    if (st.fit_split) { if (second) put_coords(st, st.split2, st.par2, i, p2); else put_no_coords(st, st.par2, i); }
+    if (kind != NM_REFLECT && kind != NM_CUT) put_point(st, b, i, s, p2); else put_none(st, b, i, p2);
 }
 
 // the second value is in: replace the worst vertex, or shrink (then the N shrunk vertices are the third batch)
@@ -218,13 +209,14 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= bound) return;
     const int N = st.N, V = N + 1;
-    double* p3 = st.p3 + i * (int64_t)N * N;
-    if (i >= st.count_cur[0]) { for (int j = 0; j < N; ++j) put_none(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j); return; }
+    const NmBatch& b = st.b[NM_B_SHRINK];
+    double* p3 = b.pts + i * (int64_t)N * N;
+    if (i >= st.count_cur[0]) { for (int j = 0; j < N; ++j) put_none(st, b, i * N + j, nullptr); return; }
     const int64_t s = st.idx_cur[i];
     double* f = st.fsim + s * V;
     double* x = st.sim + s * (int64_t)V * N;
-    const double* p1 = st.p1 + i * N;
-    const double* p2 = st.p2 + i * N;
+    const double* p1 = st.b[NM_B_REFLECT].pts + i * N;
+    const double* p2 = st.b[NM_B_SECOND].pts + i * N;
     const int kind = st.kind[s];
     bool shrink = false;
     const double fxr = st.fxr[s];
@@ -253,12 +245,8 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
             }
     }
     st.shrunk[s] = shrink ? 1 + n_eval : 0;
-    for (int j = 0; j < N; ++j) {
-        const bool live = shrink && j < n_eval;
-        if (live) put_point(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j, s); else put_none(st, st.split3, st.row3, st.bnd3, st.put3, i * N + j);
-        if (!live) for (int k = 0; k < N; ++k) p3[j * N + k] = 0.0;
-        if (st.fit_split) { if (live) put_coords(st, st.split3, st.par3, i * N + j, p3 + j * N); else put_no_coords(st, st.par3, i * N + j); }
-    }
+    for (int j = 0; j < n_eval; ++j) put_point(st, b, i * N + j, s, p3 + j * N);
+    for (int j = n_eval; j < N; ++j) put_none(st, b, i * N + j, p3 + j * N);
 }
 
 // shrink values are in: end of the iteration (count, sort) and the top of the next one
@@ -291,19 +279,12 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
     if (i == 0) st.count_next[0] = 0;          // the slot counter the next finish fills (later in stream order): no memset launch for it
     if (i >= bound) return;
     const int N = st.N, V = N + 1, K = 4 + N;
-    double* pt = st.ps + i * (int64_t)K * N;
-    double* sp = st.ps_split + i * K;
-    int32_t* rw = st.ps_row ? st.ps_row + i * K : nullptr;
-    int32_t* bw = st.ps_bnd ? st.ps_bnd + i * K * st.nb2 : nullptr;
-    int32_t* pw = st.ps_put ? st.ps_put + i * K * st.np : nullptr;
-    double* qw = st.fit_split ? st.ps_par + i * K * (N - 1) : nullptr;
-    if (i >= st.count_cur[0]) {
-        for (int j = 0; j < K; ++j) { put_none(st, sp, rw, bw, pw, j); for (int k = 0; k < N; ++k) pt[j * N + k] = 0.0; if (st.fit_split) put_no_coords(st, qw, j); }
-        return;
-    }
+    const NmBatch& b = st.b[NM_B_SPEC];           // start i's points are its slots i * K + j
+    double* pt = b.pts + i * (int64_t)K * N;
+    if (i >= st.count_cur[0]) { for (int j = 0; j < K; ++j) put_none(st, b, i * K + j, pt + j * N); return; }
     const int64_t s = st.idx_cur[i];
     const double* x = st.sim + s * (int64_t)V * N;
-    const double* p1 = st.p1 + i * N;
+    const double* p1 = st.b[NM_B_REFLECT].pts + i * N;
     for (int k = 0; k < N; ++k) {
         const double xb = centroid(x, N, k), w = x[N * N + k];
         pt[0 * N + k] = p1[k];                                                            // xr (next_reflection)
@@ -312,8 +293,7 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
         pt[3 * N + k] = rn((1.0 - NM_PSI) * xb) + rn(NM_PSI * w);                         // xcc
         for (int j = 1; j < V; ++j) pt[(3 + j) * N + k] = x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k]));   // shrunk vertex j
     }
-    for (int j = 0; j < K; ++j) put_point(st, sp, rw, bw, pw, j, s);
-    if (st.fit_split) for (int j = 0; j < K; ++j) put_coords(st, sp, qw, j, pt + j * N);
+    for (int j = 0; j < K; ++j) put_point(st, b, i * K + j, s, pt + j * N);
 }
 
 __global__ __launch_bounds__(256)
@@ -325,7 +305,7 @@ __device__ __forceinline__ void spec_finish(const NmState& st, int64_t bound, co
     const int64_t s = st.idx_cur[i];
     double* f = st.fsim + s * V;
     double* x = st.sim + s * (int64_t)V * N;
-    const double* pt = st.ps + i * (int64_t)K * N;
+    const double* pt = st.b[NM_B_SPEC].pts + i * (int64_t)K * N;
     const double* v = llk + i * K;
     const double fxr = objective(v[0]);
     int nfev = st.nfev[s] + 1;
@@ -371,14 +351,16 @@ void nm_spec_finish_kernel(NmState st, int64_t bound, const double* __restrict__
 // straight into the host's pinned word: possible because a speculative iteration has at most 1 024 / (4 + N) <= 204 live starts - one
 // workgroup, whose barrier stands for the kernel boundary between the two (the compaction of the live starts is an atomic counter over
 // the threads).  Per iteration of the search's long tail that is two launches and a 4-byte copy less: ~25 of ~560 microseconds.
-// `nx` is the state as the NEXT iteration sees it (the lists swapped).
+// The next iteration sees the state with its two lists swapped.
 __global__ __launch_bounds__(256)
-void nm_spec_step_kernel(NmState st, NmState nx, int64_t bound, const double* __restrict__ llk, volatile int32_t* live_host) {
+void nm_spec_step_kernel(NmState st, int64_t bound, const double* __restrict__ llk, volatile int32_t* live_host) {
     const int64_t i = threadIdx.x;
     spec_finish(st, bound, llk, i);
     __threadfence_block();
     __syncthreads();
     if (i == 0 && live_host) *live_host = st.count_next[0];
+    NmState nx = st;
+    nx.idx_cur = st.idx_next; nx.count_cur = st.count_next; nx.idx_next = st.idx_cur; nx.count_next = st.count_cur;
     spec_points(nx, bound, i);
 }
 
@@ -497,9 +479,9 @@ hipError_t launch_nm_spec_points(const NmState& st, int64_t bound, hipStream_t s
     hipLaunchKernelGGL(nm_spec_points_kernel, nm_grid(bound), dim3(256), 0, stream, st, bound);
     return hipGetLastError();
 }
-hipError_t launch_nm_spec_step(const NmState& st, const NmState& nx, int64_t bound, const double* llk, int32_t* live_host, hipStream_t stream) {
+hipError_t launch_nm_spec_step(const NmState& st, int64_t bound, const double* llk, int32_t* live_host, hipStream_t stream) {
     if (bound > 256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nm_spec_step_kernel, dim3(1), dim3(256), 0, stream, st, nx, bound, llk, live_host);
+    hipLaunchKernelGGL(nm_spec_step_kernel, dim3(1), dim3(256), 0, stream, st, bound, llk, live_host);
     return hipGetLastError();
 }
 hipError_t launch_nm_spec_finish(const NmState& st, int64_t bound, const double* llk, hipStream_t stream) {

@@ -248,48 +248,57 @@ class Engine:
     def sync(self):
         _lib.check(self._lib.misti_sync(self._ctx))
 
-    def nm_solve(self, starts, split_time, jsfs_row, tol=1e-4, maxiter=1000):
-        """``misti_nm_solve``: SciPy-exact Nelder-Mead from every row of ``starts`` with the simplices resident in
-        HBM (``MigrationInference.Solve`` for many starts; reference semantics :718-733).
-        Returns dict(x[S][P], llh[S], nit[S], nfev[S], status[S]) - status 0 converged, 2 iteration budget."""
-        st = _f64(starts, (-1, self.n_param))
-        S = st.shape[0]
-        row = _f64(jsfs_row, (8,))
-        x = np.empty((S, self.n_param))
-        llh = np.empty(S)
-        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(self._lib.misti_nm_solve(self._ctx, S, ptr(st), float(split_time), ptr(row), float(tol), float(tol), int(maxiter),
-                                            ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
+    def _nm_stats(self):
+        """Work counters of the last search on this context: iterations issued, their batch slots, speculative iterations."""
         stats = (C.c_int64 * 2)()
         _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
         spec = C.c_int64(0)
         _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
-        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
-                    speculative_iterations=int(spec.value))
+        return dict(iterations_issued=int(stats[0]), slots=int(stats[1]), speculative_iterations=int(spec.value))
+
+    # what each search takes between `starts` and the tolerances, in its prototype's order (include/misti_hip.h)
+    _NM_TAKES = {"misti_nm_solve": ("split_time", "jsfs_row"),
+                 "misti_nm_solve_rows": ("split_times", "rows", "table"),
+                 "misti_nm_solve_bounds": ("split_times", "rows", "band_bounds", "table"),
+                 "misti_nm_solve_pulses": ("split_times", "rows", "band_bounds", "pulse_times", "table"),
+                 "misti_nm_solve_split": ("rows", "band_bounds", "pulse_times", "table")}
+
+    def _nm_search(self, symbol, starts, tol, maxiter, **given):
+        """Every ``misti_nm_solve*``: shapes the inputs ``_NM_TAKES[symbol]`` names, allocates the results, calls ``symbol`` and returns
+        the results with the work counters.  ``misti_nm_solve_split``'s starts carry the split as one coordinate more.  Band bounds and
+        pulse times that are ``None``, or that the model has no band / pulse for, go as NULL."""
+        N = self.n_param + (1 if symbol == "misti_nm_solve_split" else 0)
+        st = _f64(starts, (-1, N))
+        S = st.shape[0]
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
+        shaped = {"split_time": lambda v: [float(v)],
+                  "jsfs_row": lambda v: [ptr(_f64(v, (8,)))],
+                  "split_times": lambda v: [ptr(_f64(v, (S,)))],
+                  "rows": lambda v: [ptr(i32(v, (S,)))],
+                  "band_bounds": lambda v: [ptr(i32(v, (S, self.n_band, 2)) if v is not None and self.n_band else None)],
+                  "pulse_times": lambda v: [ptr(i32(v, (S, self.n_pulse)) if v is not None and self.n_pulse else None)],
+                  "table": lambda v: [_f64(v, (-1, 8)).shape[0], ptr(_f64(v, (-1, 8)))]}
+        args = [a for name in self._NM_TAKES[symbol] for a in shaped[name](given[name])]
+        x = np.empty((S, N))
+        llh = np.empty(S)
+        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
+        _lib.check(getattr(self._lib, symbol)(self._ctx, S, ptr(st), *args, float(tol), float(tol), int(maxiter),
+                                              ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
+        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, **self._nm_stats())
+
+    def nm_solve(self, starts, split_time, jsfs_row, tol=1e-4, maxiter=1000):
+        """``misti_nm_solve``: SciPy-exact Nelder-Mead from every row of ``starts`` with the simplices resident in
+        HBM (``MigrationInference.Solve`` for many starts; reference semantics :718-733).
+        Returns dict(x[S][P], llh[S], nit[S], nfev[S], status[S]) - status 0 converged, 2 iteration budget."""
+        return self._nm_search("misti_nm_solve", starts, tol, maxiter, split_time=split_time, jsfs_row=jsfs_row)
 
     def nm_solve_rows(self, starts, split_times, rows, jsfs, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_rows``: ``nm_solve`` with a split time and a replicate row PER START - start s is SciPy's
         Nelder-Mead at ``split_times[s]`` against ``jsfs[rows[s]]``, all starts in one batched search (the bootstrap profiles of
         the reference's ``test.bs`` scripts, one ``Solve`` per (replicate, split) pair there).  ``jsfs`` is ``[n_rep][8]``.
         Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` bit for bit."""
-        st = _f64(starts, (-1, self.n_param))
-        S = st.shape[0]
-        split = _f64(split_times, (S,))
-        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
-        table = _f64(jsfs, (-1, 8))
-        x = np.empty((S, self.n_param))
-        llh = np.empty(S)
-        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(self._lib.misti_nm_solve_rows(self._ctx, S, ptr(st), ptr(split), ptr(row), table.shape[0], ptr(table), float(tol), float(tol),
-                                                 int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
-        stats = (C.c_int64 * 2)()
-        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
-        spec = C.c_int64(0)
-        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
-        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
-                    speculative_iterations=int(spec.value))
+        return self._nm_search("misti_nm_solve_rows", starts, tol, maxiter, split_times=split_times, rows=rows, table=jsfs)
 
     def nm_solve_bounds(self, starts, split_times, rows, jsfs, band_bounds, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_bounds``: ``nm_solve_rows`` with the band bounds PER START as well - start s is SciPy's Nelder-Mead at
@@ -299,26 +308,8 @@ class Engine:
         that break SetModel's checks give that start ``llh = -inf``.  ``band_bounds=None`` is ``nm_solve_rows``.
         Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` on an engine whose
         bands carry ``band_bounds[s]``, bit for bit."""
-        st = _f64(starts, (-1, self.n_param))
-        S = st.shape[0]
-        split = _f64(split_times, (S,))
-        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
-        table = _f64(jsfs, (-1, 8))
-        bb = None
-        if band_bounds is not None and self.n_band:
-            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(S, self.n_band, 2)
-        x = np.empty((S, self.n_param))
-        llh = np.empty(S)
-        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        _lib.check(self._lib.misti_nm_solve_bounds(self._ctx, S, ptr(st), ptr(split), ptr(row), ptr(bb), table.shape[0], ptr(table), float(tol),
-                                                   float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
-        stats = (C.c_int64 * 2)()
-        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
-        spec = C.c_int64(0)
-        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
-        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
-                    speculative_iterations=int(spec.value))
+        return self._nm_search("misti_nm_solve_bounds", starts, tol, maxiter, split_times=split_times, rows=rows, band_bounds=band_bounds,
+                               table=jsfs)
 
     def nm_solve_pulses(self, starts, split_times, rows, jsfs, band_bounds, pulse_times, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_pulses``: ``nm_solve_bounds`` with the pulse times PER START as well (``[n_start][n_pulse]`` ints, on
@@ -327,28 +318,8 @@ class Engine:
         ``nm_solve_bounds``.
         Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` on an engine whose
         model carries ``band_bounds[s]`` and ``pulse_times[s]``, bit for bit."""
-        st = _f64(starts, (-1, self.n_param))
-        S = st.shape[0]
-        split = _f64(split_times, (S,))
-        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
-        table = _f64(jsfs, (-1, 8))
-        bb = pt = None
-        if band_bounds is not None and self.n_band:
-            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(S, self.n_band, 2)
-        if pulse_times is not None and self.n_pulse:
-            pt = np.ascontiguousarray(pulse_times, dtype=np.int32).reshape(S, self.n_pulse)
-        x = np.empty((S, self.n_param))
-        llh = np.empty(S)
-        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        _lib.check(self._lib.misti_nm_solve_pulses(self._ctx, S, ptr(st), ptr(split), ptr(row), ptr(bb), ptr(pt), table.shape[0], ptr(table),
-                                                   float(tol), float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
-        stats = (C.c_int64 * 2)()
-        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
-        spec = C.c_int64(0)
-        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
-        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, iterations_issued=int(stats[0]), slots=int(stats[1]),
-                    speculative_iterations=int(spec.value))
+        return self._nm_search("misti_nm_solve_pulses", starts, tol, maxiter, split_times=split_times, rows=rows, table=jsfs,
+                               band_bounds=band_bounds, pulse_times=pulse_times)
 
     def nm_solve_split(self, starts, rows, table, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_split``: the split time as the LAST coordinate of every simplex - ``starts`` is ``[S][n_param + 1]``
@@ -358,28 +329,10 @@ class Engine:
         (``n_param == 0``) its only search.  ``band_bounds`` / ``pulse_times`` per start as in ``nm_solve_pulses`` (band end -1: the
         point's own split index).  A point whose split the engine refuses scores +inf; a start without any value has ``llh = -inf``.
         Returns what ``nm_solve`` returns with ``x[S][n_param + 1]``, plus ``split`` (= ``x[:, -1]``)."""
-        N = self.n_param + 1
-        st = _f64(starts, (-1, N))
-        S = st.shape[0]
-        row = np.ascontiguousarray(np.asarray(rows).reshape(S), dtype=np.int32)
-        tab = _f64(table, (-1, 8))
-        bb = pt = None
-        if band_bounds is not None and self.n_band:
-            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(S, self.n_band, 2)
-        if pulse_times is not None and self.n_pulse:
-            pt = np.ascontiguousarray(pulse_times, dtype=np.int32).reshape(S, self.n_pulse)
-        x = np.empty((S, N))
-        llh = np.empty(S)
-        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        _lib.check(self._lib.misti_nm_solve_split(self._ctx, S, ptr(st), ptr(row), ptr(bb), ptr(pt), tab.shape[0], ptr(tab),
-                                                  float(tol), float(tol), int(maxiter), ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
-        stats = (C.c_int64 * 2)()
-        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
-        spec = C.c_int64(0)
-        _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
-        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, split=x[:, -1].copy(), iterations_issued=int(stats[0]),
-                    slots=int(stats[1]), speculative_iterations=int(spec.value))
+        r = self._nm_search("misti_nm_solve_split", starts, tol, maxiter, rows=rows, table=table, band_bounds=band_bounds,
+                            pulse_times=pulse_times)
+        r["split"] = r["x"][:, -1].copy()
+        return r
 
     def basinhopping(self, starts, split_time, jsfs_row, rngs, niter=100, T=0.5, stepsize=0.5, interval=50, target_accept_rate=0.5,
                      stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
@@ -401,9 +354,8 @@ class Engine:
                                                 float(target_accept_rate), float(stepwise_factor), float(xatol), float(fatol),
                                                 int(nm_maxiter if nm_maxiter is not None else 200 * N), int(nm_maxfev if nm_maxfev is not None else 200 * N),
                                                 ptr(uni), ptr(x), ptr(llh), ptr(nfev), ptr(failures), ptr(accepted)))
-        stats = (C.c_int64 * 2)()
-        _lib.check(self._lib.misti_nm_last_stats(self._ctx, stats))
-        return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, iterations_issued=int(stats[0]), slots=int(stats[1]))
+        stats = self._nm_stats()
+        return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, iterations_issued=stats["iterations_issued"], slots=stats["slots"])
 
     def enable_solver_trace(self, on=True):
         """Record, for the following batches, SciPy-comparable solver statistics per candidate and interval
