@@ -4,7 +4,9 @@
   1. a split-time scan x bootstrap replicates with the likelihood table kept on the device
      (`Engine.evaluate_dev` + `misti_argmax_dev` via `optimize.bootstrap_scan_dev`), i.e. what the bash loops of
      the reference's test.bs/*.sh + bs_conf_int.ipynb do with one MiSTI.py process per (split, replicate);
-  2. many independent scans overlapped on a pool of lanes (`lanes.LanePool`).
+  2. the same scan WITHOUT the table: the three best splits per replicate, reduced where the values are computed
+     (`optimize.scan_best`: `misti_eval_batch_dev` without replicates + `misti_scan_best_dev`);
+  3. many independent scans overlapped on a pool of lanes (`lanes.LanePool`).
 
     python examples/bootstrap_scan.py
 """
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from misti_amd import io as mio, synth                      # noqa: E402
 from misti_amd.engine import Engine, truth_spectrum         # noqa: E402
 from misti_amd.lanes import LanePool                        # noqa: E402
-from misti_amd.optimize import bootstrap_scan_dev           # noqa: E402
+from misti_amd.optimize import bootstrap_scan_dev, scan_best   # noqa: E402
 
 
 def main():
@@ -37,8 +39,11 @@ def main():
         t0 = time.perf_counter()
         mean, (lo, hi), best = bootstrap_scan_dev(e, splits, table)
         dt = time.perf_counter() - t0
+        top, top_llk, _ = scan_best(e, splits, None, table, k=3)                   # [201][3]: no [33 x 201] table anywhere
     print("split scan %d values x %d replicates: best split %.2f, 95%% interval [%.2f, %.2f]  (%.1f ms, %d llk values)"
           % (len(splits), len(table), mean, lo, hi, 1e3 * dt, len(splits) * len(table)))
+    assert (splits[top[:, 0]] == best).all()
+    print("the data row's three best splits: %s (llk %s)" % (splits[top[0]], top_llk[0]))
 
     # the same scan for 40 different resampled tables, overlapped on 8 lanes
     rng = np.random.default_rng(0)

@@ -220,6 +220,22 @@ int misti_llk_dev(misti_ctx* ctx, int64_t n_cand, const double* d_jafs, const in
  * candidate has a value.  d_best_llk may be NULL.  Asynchronous on the context's stream. */
 int misti_argmax_dev(misti_ctx* ctx, int64_t n_cand, int64_t n_rep, const double* d_llk, int32_t* d_best, double* d_best_llk);
 
+/* The k best candidates per replicate WITHOUT the table: the values misti_llk_dev would write (the same bits) are compared where
+ * they are computed and never stored - memory is O(n_rep x k), nothing of size n_cand x n_rep is allocated.  Arguments as for
+ * misti_llk_dev (device pointers; d_status may be NULL: all OK; llh_const per row is computed inside); the spectra come from any
+ * evaluation with n_rep == 0 (misti_eval_batch_dev, misti_eval_batch_pulses_dev).
+ * Order rule, per replicate r: of the candidates with a value v > -inf (a status other than 0 has none; NaN never qualifies) those
+ * with the largest values, value descending and candidate index ascending on equal values; d_best[r][0..k) their indices,
+ * d_best_llk[r][0..k) (may be NULL) their values; places beyond the last such candidate hold -1 / -inf.  A total order: the result
+ * does not depend on how the library cuts the candidates into workgroups.  k == 1 is misti_llk_dev followed by misti_argmax_dev.
+ * MISTI_E_ARG for k outside 1 ... MISTI_SCAN_MAX_BEST, a negative count or a NULL d_jafs / d_jsfs / d_best with work to do,
+ * MISTI_E_LIMIT for n_cand > INT32_MAX - before anything touches the device.  n_rep == 0 writes nothing; n_cand == 0 fills
+ * -1 / -inf.  Asynchronous on the context's stream. */
+#define MISTI_SCAN_MAX_BEST 8
+int misti_scan_best_dev(misti_ctx* ctx, int64_t n_cand, const double* d_jafs, const int32_t* d_status,
+                        int64_t n_rep, const double* d_jsfs, int32_t k,
+                        int32_t* d_best /* [n_rep][k] */, double* d_best_llk /* [n_rep][k] or NULL */);
+
 /* Diagnostic of the last batch evaluated on this context (either form): per candidate the
  * largest corrected rate x interval length before smoothing (NaN where the candidate has no
  * value, 0 with MISTI_TRUE_EPS).  From ~5 upwards the correction's residual is nearly flat in

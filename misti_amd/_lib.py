@@ -25,6 +25,7 @@ MAX_BANDS, MAX_PULSES, MAX_PARAMS, MAX_NUMT = 8, 8, 16, 255
 LANE_ANY, MAX_LANES = -1, 64
 ABI_VERSION = 6
 TRACE_MAX_CAND, TRACE_MAX_ITER = 64, 200
+SCAN_MAX_BEST = 8
 
 
 class Band(C.Structure):
@@ -90,6 +91,7 @@ SYMBOLS = {
     "misti_forward_rates": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_forward_rates_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_argmax_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_scan_best_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "misti_last_diag": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "misti_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "misti_kernel_times": (C.c_int, [C.c_void_p, _PD, C.POINTER(C.c_int64), C.c_int]),

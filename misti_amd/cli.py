@@ -27,6 +27,15 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               line of the best search with the fitted, fractional splitT, then (--all-bs) the t-interval of
                               bs_conf_int.ipynb over the fitted splits.  Needs no optimised -mi / -pu: a model without one is a
                               one-coordinate search.  Not offered with --sweep, --sweep-pu, --gpus N > 1 or --devices
+    --top K                   with --grid-st and/or --grid-mi (K = 1 ... 8): grid mode evaluates WITHOUT replicates and reduces on the device
+                              (misti_scan_best_dev) - the [candidates x rows] likelihood table is never made; per row its K best
+                              candidates are printed (one line each, grid mode's format: K lines per row in place of one per
+                              candidate), then the best: line, the bootstrap interval from the rows' first places and the timing line.
+                              Not offered with --gpus N > 1, --devices, --grid-solve, --fit-st, --sweep or --sweep-pu
+    --polish                  with --top K and at least one optimised -mi / -pu: after the scan ONE batched search whose starts are
+                              the K listed candidates of every row (optimize.scan_polish); per row the MiSTI.py:240 line of its
+                              best polished search, as --grid-solve prints its pairs - K searches per row where --grid-solve runs
+                              one from every (split, start) pair
     --gpus N                  the sweep on N GPUs of the node: this process starts N ranks (one per GPU, torch.distributed over
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
@@ -99,6 +108,10 @@ def build_parser():
                    help="with --grid-st / --all-bs: optimise every (replicate, split) pair as the test.bs loops do, in one batched search")
     p.add_argument("--fit-st", action="store_true",
                    help="with --grid-st (the initial splits) / --all-bs: fit the split time per row as a coordinate of one batched search")
+    p.add_argument("--top", type=int, default=None, metavar="K",
+                   help="grid mode (--grid-st / --grid-mi): keep the K best candidates per row (1 ... 8), reduced on the device without the table")
+    p.add_argument("--polish", action="store_true",
+                   help="with --top K: one batched search from the K listed candidates of every row; per row its best polished search")
     p.add_argument("--sweep", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="the GNU-parallel recipe's `::: NAME V1 V2 ...`: {NAME} in the split time or in -mi start / end / rate fields")
     p.add_argument("--sweep-pu", nargs="+", action="append", default=[], metavar=("NAME", "V"),
@@ -131,6 +144,29 @@ def fit_st_error(a):
         return "--fit-st fits the split time, --grid-solve scans it: give one of them"
     if not a.grid_st:
         return "--fit-st needs --grid-st A B [STEP]: the initial split times of its searches"
+    return None
+
+
+def top_error(a):
+    """Why ``--top`` / ``--polish`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.top is None and not a.polish:
+        return None
+    if a.top is None:
+        return "--polish polishes the candidates --top K lists: give --top K"
+    if not 1 <= a.top <= 8:
+        return "--top K keeps at most 8 candidates per row: K must be 1 ... 8 (got %d)" % a.top
+    if a.sweep or a.sweep_pu:
+        return "--top reduces the grid of --grid-st / --grid-mi: --sweep / --sweep-pu are not offered with it"
+    if a.fit_st:
+        return "--top lists scanned candidates, --fit-st fits the split time: give one of them"
+    if a.grid_solve:
+        return "--top lists scanned candidates (--polish searches from them), --grid-solve searches from every pair: give one of them"
+    if not (a.grid_st or a.grid_mi):
+        return "--top applies to grid mode: it needs --grid-st and/or --grid-mi"
+    if a.gpus > 1 or a.devices:
+        return "--top runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    if a.polish and not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
+        return "--polish needs at least one optimised parameter (-mi ... 1 or -pu ... 1)"
     return None
 
 
@@ -252,6 +288,59 @@ def grid_mode(a, inp, rows):
               % (mean, lo, hi, data.shape[0]))
     print("Evaluated %d candidates x %d replicates in %.3f s (%.0f llk evals/s); %.1f%% without a value"
           % (len(split), data.shape[0], dt, res.llk.size / dt, 100 * res.fraction_failed))
+    return 0
+
+
+def grid_top(a, inp, rows):
+    """Grid mode with --top K: the same candidates and rows, evaluated without replicates and reduced on the device to the K best
+    candidates per row (optimize.scan_best); with --polish one batched search from those (optimize.scan_polish)."""
+    from .optimize import _t_interval, scan_best, scan_polish
+    splits, bands, pulses, k, axes = grid_model(a)
+    mesh = np.meshgrid(np.array(splits), *axes, indexing="ij")
+    split = mesh[0].ravel()
+    params = np.stack([m.ravel() for m in mesh[1:]], axis=1) if k else None
+    data, ids = _data_rows(a, rows)
+    flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    t0 = time.time()
+    with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
+        if a.polish:
+            pol = scan_polish(e, split, params, data, a.top, tol=a.tol, maxiter=1000)
+            best, best_llk, status = pol["best"], pol["best_llk"], pol["scan_status"]
+        else:
+            best, best_llk, status = scan_best(e, split, params, data, a.top)
+    dt = time.time() - t0
+    R = data.shape[0]
+    for r in range(R):
+        for j in range(a.top):
+            c = best[r, j]
+            if c < 0:
+                continue
+            pstr = "" if params is None else "\t".join("%.6g" % v for v in params[c])
+            print("bs_id =", ids[r], "\tsplitT =", split[c], "\tparams", pstr, "\tllh =", best_llk[r, j], "\tstatus =", int(status[c]))
+    has = best[:, 0] >= 0
+    if has.any():
+        # grid mode's best: the first maximum of the table in candidate-major order - the lowest candidate, then the lowest row
+        top = best_llk[:, 0].max()
+        c, r = min((best[r, 0], r) for r in range(R) if has[r] and best_llk[r, 0] == top)
+        print("\nbest: splitT =", split[c], "params =", None if params is None else list(params[c]), "replicate =", r, "llh =", best_llk[r, 0])
+    else:
+        print("\nbest: no candidate has a value")
+    if a.all_bs and len(splits) > 1 and R > 1:
+        # grid mode's interval (test.bs/bs_conf_int.ipynb) from the rows' first places; a row without a value counts as candidate 0, as there
+        mean, (lo, hi), _ = _t_interval(split[np.where(has, best[:, 0], 0)], 0.95)
+        print("bootstrap: best splitT per replicate mean = %.6g, 95%% interval = [%.6g, %.6g] over %d replicates" % (mean, lo, hi, R))
+    if a.polish:
+        print()
+        for r in range(R):
+            if not np.isfinite(pol["llh"][r]):
+                print("polish: bs_id =", ids[r], "has no finite llh from any listed candidate")
+                continue
+            st = float(pol["split"][r])
+            print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, pol["x"][r], pol["llh"][r]))
+        print("polish: %d searches in one batched search (%d rows x at most %d listed candidates); %d rows ended on the iteration cap"
+              % (pol["searches"]["cand"].size, R, a.top, int((pol["status"] == 2).sum())))
+    print("Evaluated %d candidates x %d replicates in %.3f s (%.0f llk evals/s); %.1f%% without a value"
+          % (len(split), R, dt, len(split) * R / dt, 100 * float((status != 0).mean())))
     return 0
 
 
@@ -443,7 +532,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
+    why = top_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
@@ -495,6 +584,8 @@ def main(argv=None):
         return fit_st(a, inp, rows)
     if a.grid_solve:
         return grid_solve(a, inp, rows)
+    if a.top is not None:
+        return grid_top(a, inp, rows)
     if a.grid_st or a.grid_mi or a.all_bs:
         return grid_mode(a, inp, rows)
 

@@ -87,6 +87,7 @@ struct misti_ctx {
     hipStream_t stream = nullptr;
     DevBuf model_f64, model_i32;        // times | lh ; run_start | run_end
     DevBuf consts;                      // llh_const per replicate
+    DevBuf scan_v, scan_i;              // misti_scan_best_dev: the slices' lists [slices][width][n_rep], values and indices
     DevBuf ws_jafs, ws_status;          // spectra / status when the caller passes NULL
     DevBuf ws_order;                    // dispatch order (heaviest candidates first)
     DevBuf ws_diag;                     // per candidate: largest corrected rate x interval length of the last batch
@@ -677,7 +678,7 @@ int misti_destroy(misti_ctx* c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     (void)hipGetLastError();
     for (auto* b : {&c->model_f64, &c->model_i32, &c->consts, &c->ws_jafs, &c->ws_status, &c->ws_chain_f64, &c->ws_chain_i32, &c->ws_order, &c->ws_diag, &c->ws_trunk, &c->ws_solver, &c->ws_iters, &c->ws_post,
-                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32})
+                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i})
         b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -766,6 +767,28 @@ int misti_argmax_dev(misti_ctx* c, int64_t n_cand, int64_t n_rep, const double* 
     if (n_cand > INT32_MAX) return fail(MISTI_E_LIMIT, "n_cand too large");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(misti::launch_argmax(n_cand, n_rep, d_llk, d_best, d_best_llk, c->stream));
+    return 0;
+}
+
+int misti_scan_best_dev(misti_ctx* c, int64_t n_cand, const double* d_jafs, const int32_t* d_status, int64_t n_rep, const double* d_jsfs, int32_t k,
+                        int32_t* d_best, double* d_best_llk) {
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (k < 1 || k > MISTI_SCAN_MAX_BEST) return fail(MISTI_E_ARG, "k must be 1 ... %d (got %d)", MISTI_SCAN_MAX_BEST, (int)k);
+    if (n_cand < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative batch size");
+    if (n_rep == 0) return 0;
+    if (!d_best || (n_cand > 0 && (!d_jafs || !d_jsfs))) return fail(MISTI_E_ARG, "jafs / jsfs / best is NULL");
+    if (n_cand > INT32_MAX) return fail(MISTI_E_LIMIT, "n_cand too large");
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t slices = misti::scan_best_slices(n_cand, n_rep, c->tune);
+    const size_t part = (size_t)slices * (size_t)misti::scan_best_width(k) * (size_t)n_rep;
+    if (n_cand > 0) {
+        HIP_TRY(c->consts.reserve((size_t)n_rep * sizeof(double)));
+        HIP_TRY(c->scan_v.reserve(part * sizeof(double)));
+        HIP_TRY(c->scan_i.reserve(part * sizeof(int32_t)));
+        HIP_TRY(misti::launch_llh_const(n_rep, d_jsfs, c->consts.as<double>(), c->unfolded, c->stream));
+    }
+    HIP_TRY(misti::launch_scan_best(n_cand, d_jafs, d_status, n_rep, d_jsfs, c->consts.as<double>(), k, d_best, d_best_llk, slices,
+                                    c->scan_v.as<double>(), c->scan_i.as<int32_t>(), c->unfolded, c->stream));
     return 0;
 }
 

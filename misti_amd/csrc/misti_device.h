@@ -217,6 +217,7 @@ struct Tuning {
     int k2_single_waves = -1;  // MISTI_K2_SINGLE_WAVES: 1 / 0 forces kernel 2's workgroups to one / four waves (-1: chosen per batch, run_dev)
     int busy_contexts = -1;    // MISTI_FOLLOW_BUSY_CONTEXTS: other contexts with a batch in flight from which on a batch of more than
                                // FOLLOW_BUSY_CHAINS chains is packed (-1: FOLLOW_BUSY_CONTEXTS; 0: never look, always the latency shape)
+    int scan_slices = 0;       // MISTI_SCAN_SLICES: forces the number of candidate slices of misti_scan_best_dev (0: scan_best_slices' choice)
 };
 Tuning read_tuning();
 int64_t trunk_capacity(int64_t n_cand, const Tuning& tn);
@@ -234,6 +235,13 @@ hipError_t launch_spectrum(const DevModel& m, int64_t n_cand, const int32_t* ord
 hipError_t launch_forward(const DevModel& m, int64_t n_cand, const double* split, const double* params, int hold_mu, double* lh_out, double* pr_out,
                           int32_t* status, hipStream_t stream);
 hipError_t launch_argmax(int64_t n_cand, int64_t n_rep, const double* llk, int32_t* best, double* best_llk, hipStream_t stream);
+// The k best candidates per replicate without the table (misti_scan_best_dev): llk_kernel's values reduced where they are computed.
+// `slices` = scan_best_slices(...) lists of width scan_best_width(k) go through part_v / part_i ([slices][width][n_rep] each), then one
+// merge launch writes best[n_rep][k] / best_llk[n_rep][k] (NULL: not wanted).  n_cand == 0 (slices == 0): -1 / -inf everywhere.
+int scan_best_width(int k);
+int64_t scan_best_slices(int64_t n_cand, int64_t n_rep, const Tuning& tn);
+hipError_t launch_scan_best(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs, const double* consts,
+                            int k, int32_t* best, double* best_llk, int64_t slices, double* part_v, int32_t* part_i, int unfolded, hipStream_t stream);
 hipError_t launch_llh_const(int64_t n_rep, const double* jsfs, double* consts, int unfolded, hipStream_t stream);
 hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs,
                       const double* consts, double* llk, int unfolded, hipStream_t stream);

@@ -3187,6 +3187,143 @@ hipError_t launch_argmax(int64_t n_cand, int64_t n_rep, const double* llk, int32
     return hipGetLastError();
 }
 
+// The K best candidates per replicate WITHOUT the table (misti_scan_best_dev): llk_kernel's values - the same expressions, the same
+// bits - compared where they are computed and never stored.  Order: value descending, candidate index ascending on equal values;
+// only v > -inf qualifies (false for NaN: argmax_kernel's rule).  That is a total order, so the result does not depend on how the
+// candidates are cut into slices.
+// One place of a sorted K-list: `v` goes in front of every entry it beats, the entries behind it move down one place and the last
+// one leaves.  K is a compile-time constant and every index below is one too: the list is 3 K registers, not an indexed local array.
+template <int K>
+__device__ __forceinline__ void best_insert(double (&bv)[K], int32_t (&bi)[K], double v, int32_t c) {
+#pragma unroll
+    for (int j = K - 1; j >= 1; --j) {
+        const bool here = v > bv[j], above = v > bv[j - 1];
+        bv[j] = above ? bv[j - 1] : (here ? v : bv[j]);
+        bi[j] = above ? bi[j - 1] : (here ? c : bi[j]);
+    }
+    if (v > bv[0]) { bv[0] = v; bi[0] = c; }
+}
+
+// thread = one replicate (class counts, constant and K-list in registers); blockIdx.y = a SLICE of `per_slice` consecutive candidates,
+// walked in chunks of SCAN_CHUNK whose class logs and no-value flags the block stages in LDS as llk_kernel does.  A slice walks its
+// candidates in index order and takes a value only where it is strictly larger, so equal values stay in index order.  Each slice
+// leaves its list in part_v / part_i [slice][K][n_rep] (the replicate innermost: coalesced here and in the merge).
+constexpr int SCAN_CHUNK = 64;
+template <bool UNFOLDED, int K>
+__global__ __launch_bounds__(256)
+void scan_best_kernel(int64_t n_cand, int64_t per_slice, const double* __restrict__ jafs, const int32_t* __restrict__ status,
+                      int64_t n_rep, const double* __restrict__ jsfs, const double* __restrict__ consts,
+                      double* __restrict__ part_v, int32_t* __restrict__ part_i) {
+    constexpr int NF = UNFOLDED ? 7 : 4;
+    __shared__ double lj[SCAN_CHUNK][8];              // [7] = 1.0 where the candidate has no value (status != OK), else 0.0
+    const int64_t s0 = (int64_t)blockIdx.y * per_slice;
+    const int64_t s1 = s0 + per_slice < n_cand ? s0 + per_slice : n_cand;
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t rr = r < n_rep ? r : n_rep - 1;      // a lane beyond the table repeats the last row (never stored)
+    double f[NF];
+    {
+        const double* d = jsfs + rr * 8 + 1;
+        if (UNFOLDED) { for (int i = 0; i < 7; ++i) f[i] = d[i]; }
+        else { f[0] = d[0] + d[6]; f[1] = d[1] + d[5]; f[2] = d[2] + d[4]; f[3] = d[3]; }
+    }
+    const double cst = consts[rr];
+    double bv[K];
+    int32_t bi[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { bv[j] = -INFINITY; bi[j] = -1; }
+    for (int64_t c0 = s0; c0 < s1; c0 += SCAN_CHUNK) {
+        const int nc = (int)(s1 - c0 < SCAN_CHUNK ? s1 - c0 : SCAN_CHUNK);
+        __syncthreads();                              // the previous chunk has been walked by every wave
+        for (int i = threadIdx.x; i < nc * 8; i += blockDim.x) {
+            const int c = i >> 3, k = i & 7;
+            double v;
+            if (k < 7) v = log_class(jafs + (c0 + c) * 7, k, UNFOLDED ? 1 : 0);
+            else v = (status && status[c0 + c] != MISTI_OK) ? 1.0 : 0.0;
+            lj[c][k] = v;
+        }
+        __syncthreads();
+        for (int c = 0; c < nc; ++c) {
+            double a = cst;
+#pragma unroll
+            for (int i = 0; i < NF; ++i) a = fma(f[i], lj[c][i], a);
+            if (lj[c][7] != 0.0) a = -INFINITY;
+            if (a > bv[K - 1]) best_insert<K>(bv, bi, a, (int32_t)(c0 + c));      // false for NaN and for -inf
+        }
+    }
+    if (r >= n_rep) return;
+    const int64_t base = (int64_t)blockIdx.y * K * n_rep + r;
+#pragma unroll
+    for (int j = 0; j < K; ++j) { part_v[base + j * n_rep] = bv[j]; part_i[base + j * n_rep] = bi[j]; }
+}
+
+// thread = one replicate: folds the slices' lists together in slice order (ascending candidate indices, so again a value is taken
+// only where it is strictly larger) and writes the first k places as best[r][k] / best_llk[r][k]; no slice at all: -1 / -inf.
+template <int K>
+__global__ __launch_bounds__(256)
+void scan_merge_kernel(int slices, int64_t n_rep, const double* __restrict__ part_v, const int32_t* __restrict__ part_i, int k,
+                       int32_t* __restrict__ best, double* __restrict__ best_llk) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rep) return;
+    double bv[K];
+    int32_t bi[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { bv[j] = -INFINITY; bi[j] = -1; }
+    for (int s = 0; s < slices; ++s) {
+        const int64_t base = (int64_t)s * K * n_rep + r;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const double v = part_v[base + j * n_rep];
+            if (v > bv[K - 1]) best_insert<K>(bv, bi, v, part_i[base + j * n_rep]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j < k) {
+            best[r * k + j] = bi[j];
+            if (best_llk) best_llk[r * k + j] = bv[j];
+        }
+}
+
+int scan_best_width(int k) { return k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : 8)); }
+
+// Slices of a scan: as many as give the chip about a thousand workgroups (four per compute unit) together with the replicate
+// blocks - one when the replicates alone do - and no slice shorter than a quarter chunk (a slice's list costs a merge step).
+int64_t scan_best_slices(int64_t n_cand, int64_t n_rep, const Tuning& tn) {
+    if (n_cand <= 0 || n_rep <= 0) return 0;
+    const int64_t rep_blocks = (n_rep + 255) / 256;
+    int64_t slices = tn.scan_slices > 0 ? tn.scan_slices : (1024 + rep_blocks - 1) / rep_blocks;
+    const int64_t most = tn.scan_slices > 0 ? n_cand : (n_cand + SCAN_CHUNK / 4 - 1) / (SCAN_CHUNK / 4);
+    if (slices > most) slices = most;
+    if (slices > 65535) slices = 65535;                                     // gridDim.y limit
+    const int64_t per_slice = (n_cand + slices - 1) / slices;
+    return (n_cand + per_slice - 1) / per_slice;                            // no empty slice behind the last candidate
+}
+
+template <int K>
+static void launch_scan_best_t(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs, const double* consts,
+                               int k, int32_t* best, double* best_llk, int64_t slices, double* part_v, int32_t* part_i, int unfolded, hipStream_t stream) {
+    const unsigned rep_blocks = (unsigned)((n_rep + 255) / 256);
+    if (slices > 0) {
+        const int64_t per_slice = (n_cand + slices - 1) / slices;
+        const dim3 grid(rep_blocks, (unsigned)slices);
+        if (unfolded) hipLaunchKernelGGL((scan_best_kernel<true, K>), grid, dim3(256), 0, stream, n_cand, per_slice, jafs, status, n_rep, jsfs, consts, part_v, part_i);
+        else hipLaunchKernelGGL((scan_best_kernel<false, K>), grid, dim3(256), 0, stream, n_cand, per_slice, jafs, status, n_rep, jsfs, consts, part_v, part_i);
+    }
+    hipLaunchKernelGGL(scan_merge_kernel<K>, dim3(rep_blocks), dim3(256), 0, stream, (int)slices, n_rep, part_v, part_i, k, best, best_llk);
+}
+
+hipError_t launch_scan_best(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs, const double* consts,
+                            int k, int32_t* best, double* best_llk, int64_t slices, double* part_v, int32_t* part_i, int unfolded, hipStream_t stream) {
+    if (n_rep <= 0) return hipSuccess;
+    switch (scan_best_width(k)) {
+        case 1: launch_scan_best_t<1>(n_cand, jafs, status, n_rep, jsfs, consts, k, best, best_llk, slices, part_v, part_i, unfolded, stream); break;
+        case 2: launch_scan_best_t<2>(n_cand, jafs, status, n_rep, jsfs, consts, k, best, best_llk, slices, part_v, part_i, unfolded, stream); break;
+        case 4: launch_scan_best_t<4>(n_cand, jafs, status, n_rep, jsfs, consts, k, best, best_llk, slices, part_v, part_i, unfolded, stream); break;
+        default: launch_scan_best_t<8>(n_cand, jafs, status, n_rep, jsfs, consts, k, best, best_llk, slices, part_v, part_i, unfolded, stream); break;
+    }
+    return hipGetLastError();
+}
+
 // ----------------------------------------------------------- launchers -------
 hipError_t upload_tables(const DevTables& t) {
     static double inv[INV_TABLE];
@@ -3246,6 +3383,7 @@ Tuning read_tuning() {
     t.k2_single_waves = getenv("MISTI_K2_SINGLE_WAVES") ? num("MISTI_K2_SINGLE_WAVES") : -1;
     t.pairing = !(getenv("MISTI_FOLLOW_PAIRING") && getenv("MISTI_FOLLOW_PAIRING")[0] == '0');
     t.two_phase = !(getenv("MISTI_TWO_PHASE") && getenv("MISTI_TWO_PHASE")[0] == '0');
+    t.scan_slices = num("MISTI_SCAN_SLICES");
     return t;
 }
 

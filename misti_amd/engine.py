@@ -245,6 +245,14 @@ class Engine:
         v = lambda p: C.c_void_p(int(p)) if p else None
         _lib.check(self._lib.misti_argmax_dev(self._ctx, int(n_cand), int(n_rep), v(d_llk), v(d_best), v(d_best_llk)))
 
+    def scan_best_dev(self, n_cand, d_jafs, d_status, n_rep, d_jsfs, k, d_best, d_best_llk=0):
+        """``misti_scan_best_dev``: per replicate the ``k`` best candidates (``d_best[n_rep][k]`` int32, ``d_best_llk[n_rep][k]``), value
+        descending and index ascending on ties, -1 / -inf where fewer have a value - from spectra alone, without the ``[n_cand][n_rep]``
+        table (raw device addresses; asynchronous).  ``k = 1`` is ``llk_dev`` followed by ``argmax_dev``."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _lib.check(self._lib.misti_scan_best_dev(self._ctx, int(n_cand), v(d_jafs), v(d_status), int(n_rep), v(d_jsfs), int(k), v(d_best),
+                                                 v(d_best_llk)))
+
     def sync(self):
         _lib.check(self._lib.misti_sync(self._ctx))
 

@@ -273,6 +273,117 @@ def _scan_best(engine, split_values, jsfs_rows, params=None):
     return best.cpu().numpy().astype(np.int64)
 
 
+def best_k_per_replicate(llk, k):
+    """The order rule of ``misti_scan_best_dev`` stated on the host, for a table ``llk[n_cand][n_rep]``: per replicate (column) the
+    candidates that have a value - ``v > -inf``; NaN never qualifies - ordered by value descending and by candidate index ascending
+    on equal values, the first ``k`` of them.  Returns ``(best[n_rep][k]`` int64, ``best_llk[n_rep][k])``; places beyond the last
+    candidate with a value hold -1 / -inf.  ``k = 1`` is ``dist.best_per_replicate``."""
+    llk = np.asarray(llk, dtype=np.float64)
+    llk = llk.reshape(llk.shape[0], -1)
+    n, R = llk.shape
+    k = int(k)
+    with np.errstate(invalid="ignore"):
+        has = llk > -np.inf
+    key = np.where(has, -llk, np.inf)                       # ascending; a STABLE sort leaves equal values in index order
+    order = np.argsort(key, axis=0, kind="stable")[:k]
+    best = np.full((R, k), -1, dtype=np.int64)
+    best_llk = np.full((R, k), -np.inf)
+    m = order.shape[0]
+    listed = np.take_along_axis(has, order, axis=0).T       # [R][m]
+    best[:, :m] = np.where(listed, order.T, -1)
+    best_llk[:, :m] = np.where(listed, np.take_along_axis(llk, order, axis=0).T, -np.inf)
+    return best, best_llk
+
+
+def _per_candidate(a, n, shape):
+    """int32 ``[n, *shape]`` from per-candidate values, or from one set that every candidate shares."""
+    a = np.asarray(a, dtype=np.int32)
+    return np.broadcast_to(a.reshape((-1,) + shape), (n,) + shape).copy()
+
+
+def scan_best(engine, split, params, jsfs_rows, k=1, band_bounds=None, pulse_times=None):
+    """Scan and keep the ``k`` best candidates per replicate WITHOUT the likelihood table: one evaluation without replicates into
+    device spectra and statuses (``misti_eval_batch_dev``; with ``pulse_times`` ``misti_eval_batch_pulses_dev``), then
+    ``misti_scan_best_dev`` - device memory is ``O(n_cand + n_rep * k)``, and only the lists and the statuses come back.
+    ``split`` is ``[n]``, ``params`` ``[n][n_param]``, ``jsfs_rows`` ``[R][8]``, ``band_bounds`` (``[n][n_band][2]``) and
+    ``pulse_times`` (``[n][n_pulse]``) per candidate as in ``Engine.evaluate`` (one set is shared by every candidate).
+    Returns ``(best[R][k]`` int64, ``best_llk[R][k]``, ``status[n])`` under ``best_k_per_replicate``'s rule."""
+    import torch
+    dev = torch.device("cuda", engine.device)
+    k = int(k)
+    split_h = np.asarray(split, dtype=float).reshape(-1)
+    n = split_h.size
+    rows = torch.as_tensor(np.asarray(jsfs_rows, dtype=float).reshape(-1, 8), device=dev).contiguous()
+    R = rows.shape[0]
+    d_split = torch.as_tensor(split_h, device=dev)
+    par = bb = pt = None
+    if engine.n_param:
+        par = torch.as_tensor(np.asarray(params, dtype=float).reshape(n, engine.n_param), device=dev).contiguous()
+    if band_bounds is not None and engine.n_band:
+        bb = torch.as_tensor(_per_candidate(band_bounds, n, (engine.n_band, 2)), device=dev)
+    if pulse_times is not None and engine.n_pulse:
+        pt = torch.as_tensor(_per_candidate(pulse_times, n, (engine.n_pulse,)), device=dev)
+    jafs = torch.empty((n, 7), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    best = torch.empty((R, k), dtype=torch.int32, device=dev)
+    best_llk = torch.empty((R, k), dtype=torch.float64, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    torch.cuda.current_stream(dev).synchronize()      # the engine's stream is non-blocking: inputs must have landed
+    engine.evaluate_dev(n, ptr(d_split), ptr(par), 0, 0, 0, d_jafs=ptr(jafs), d_status=ptr(status), d_bounds=ptr(bb), d_pulse_times=ptr(pt))
+    engine.scan_best_dev(n, ptr(jafs), ptr(status), R, ptr(rows), k, ptr(best), ptr(best_llk))
+    engine.sync()
+    return best.cpu().numpy().astype(np.int64), best_llk.cpu().numpy(), status.cpu().numpy()
+
+
+def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
+    """Scan, keep the ``k`` best candidates per replicate, polish those: ``scan_best``, then ONE batched search whose starts are the
+    listed candidates - row r's j-th place is a start with that candidate's parameters, split, band bounds and pulse times against
+    row r (row outermost, place innermost; a -1 place gives no start) - through ``misti_nm_solve_pulses`` / ``_bounds`` / ``_rows``,
+    whichever the given arrays need.  Per row the best polished search is kept (``_best_start_profile``'s rule: the first maximum,
+    NaN never wins).  Where ``--grid-solve`` searches from every (row, split, start) triple, this searches from ``k`` per row.
+    Returns dict(best[R][k], best_llk[R][k], scan_status[n] (the scan's), x[R][n_param], split[R], llh[R], nit / nfev / status[R],
+    place[R] (which place of the row's list was kept; a row without a start: -1, with x nan, llh -inf, status -1), searches (every
+    search: row, place, cand, x, llh, nit, nfev, status), and the search's work counters)."""
+    N = engine.n_param
+    if N < 1:
+        raise ValueError("scan_polish polishes optimised parameters: the model has none (n_param == 0)")
+    split = np.asarray(split, dtype=float).reshape(-1)
+    n = split.size
+    params = np.asarray(params, dtype=float).reshape(n, N)
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    R = rows.shape[0]
+    best, best_llk, scan_status = scan_best(engine, split, params, rows, k, band_bounds, pulse_times)
+    r_of, j_of = np.nonzero(best >= 0)                                    # row outermost, place innermost
+    cand = best[r_of, j_of]
+    bb = _per_candidate(band_bounds, n, (engine.n_band, 2))[cand] if band_bounds is not None and engine.n_band else None
+    pt = _per_candidate(pulse_times, n, (engine.n_pulse,))[cand] if pulse_times is not None and engine.n_pulse else None
+    if cand.size == 0:
+        res = dict(x=np.empty((0, N)), llh=np.empty(0), nit=np.empty(0, dtype=np.int32), nfev=np.empty(0, dtype=np.int32),
+                   status=np.empty(0, dtype=np.int32), iterations_issued=0, slots=0, speculative_iterations=0)
+    elif pt is not None:
+        res = engine.nm_solve_pulses(params[cand], split[cand], r_of.astype(np.int32), rows, bb, pt, tol=tol, maxiter=maxiter)
+    elif bb is not None:
+        res = engine.nm_solve_bounds(params[cand], split[cand], r_of.astype(np.int32), rows, bb, tol=tol, maxiter=maxiter)
+    else:
+        res = engine.nm_solve_rows(params[cand], split[cand], r_of.astype(np.int32), rows, tol=tol, maxiter=maxiter)
+    llh = np.full(best.shape, -np.inf)
+    llh[r_of, j_of] = np.where(np.isnan(res["llh"]), -np.inf, res["llh"])
+    place = np.where((best >= 0).any(axis=1), np.argmax(llh, axis=1), -1)           # first maximum: the lowest place
+    at = np.full(best.shape, -1, dtype=np.int64)
+    at[r_of, j_of] = np.arange(cand.size)
+    kept = at[np.arange(R), np.maximum(place, 0)]                                    # index of the kept search (-1: none)
+    has = kept >= 0
+    out = dict(best=best, best_llk=best_llk, scan_status=scan_status, place=place,
+               x=np.full((R, N), np.nan), split=np.full(R, np.nan), llh=np.full(R, -np.inf),
+               nit=np.zeros(R, dtype=np.int32), nfev=np.zeros(R, dtype=np.int32), status=np.full(R, -1, dtype=np.int32))
+    for f in ("x", "llh", "nit", "nfev", "status"):
+        out[f][has] = res[f][kept[has]]
+    out["split"][has] = split[cand[kept[has]]]
+    out["searches"] = dict(row=r_of, place=j_of, cand=cand, **{f: res[f] for f in ("x", "llh", "nit", "nfev", "status")})
+    out.update({f: res[f] for f in ("iterations_issued", "slots", "speculative_iterations")})
+    return out
+
+
 def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter=1000):
     """The bootstrap profiles of the reference's ``test.bs`` scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
     -mi ...``: one ``MigrationInference.Solve`` per (replicate, split) pair, MigrationInference.py:718-733 of the reference) in ONE
