@@ -386,12 +386,18 @@ int misti_nm_last_spec_iterations(misti_ctx* ctx, int64_t* n);
  * as many processes as cores (MiSTI.py:213-214 under `parallel -j`, README.md:110-115).
  *   - batches of one lane run in submission order, batches of different lanes overlap on the device;
  *   - results are bit for bit those of a single context (a batch never depends on what else is in flight);
- *   - own streams map one to one onto hardware queues, of which the HIP runtime opens GPU_MAX_HW_QUEUES per process (default 4):
- *     unless the variable is already set, loading this library sets it to 22 - the runtime reads it when it initialises, i.e. at the
- *     process's first HIP call.  22 because the device runs 23 queues beside each other and time-slices them from the 24th ACTIVE one
- *     on (a burst of twenty batches then takes 10 ms instead of 2.7); under the cap, streams beyond it share queues instead - slower
- *     (their batches serialise), never the cliff.  A process whose runtime was initialised earlier with fewer queues still gets
- *     correct results, at a lower overlapped rate.
+ *   - a lane wants a hardware queue of its own: streams that share a queue are serialised.  The HIP runtime keeps one pool of queues
+ *     per stream priority and opens at most GPU_MAX_HW_QUEUES in each (default 4).  Unless the variable is already set, loading this
+ *     library sets it to 22 - the runtime reads it when it initialises, i.e. at the process's first HIP call.  22 because the device
+ *     runs 23 queues beside each other and time-slices them from the 24th ACTIVE one on (a burst of twenty batches then takes 10 ms
+ *     instead of 2.7); under the cap, streams beyond it share queues instead - slower (their batches serialise), never the cliff.
+ *   - where the limit is smaller than the pool - the caller's environment names one, or the runtime was initialised before this library
+ *     was loaded - misti_create_lanes deals the lanes' streams over the stream priorities the device reports (three: twelve queues at a
+ *     limit of 4, never more than 22 in all; the default priority is filled first, a pool that fits into it is not spread at all).  Twenty
+ *     lanes at a limit of 4: 2.3e7 evaluations/s where one level gives 0.9e7 and 22 queues 3.8e7.  The priorities are a way to more
+ *     queues, not an order among the lanes: while the chip has room a low-priority batch starts as soon and takes as long as a
+ *     high-priority one.  MISTI_LANE_PRIORITIES=0 in the environment at misti_create_lanes keeps every lane on the default priority.
+ *     The limit is taken from GPU_MAX_HW_QUEUES as the environment names it then (else 4).  Results never depend on any of this.
  * Threading: like a context, a misti_lanes object is used by one host thread at a time. */
 typedef struct misti_lanes misti_lanes;
 int misti_create_lanes(const misti_model_t* model, int device, int n_lanes, misti_lanes** out);   /* 1 <= n_lanes <= MISTI_MAX_LANES */

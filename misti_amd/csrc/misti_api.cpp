@@ -530,7 +530,10 @@ int misti_tables(int32_t* gen, int32_t* jaf) {
     return 0;
 }
 
-int misti_create(const misti_model_t* model, int device, misti_ctx** out) {
+// internal (misti_lanes.cpp): misti_create with the context's own stream on a stream priority of the caller's choice (a value of
+// hipDeviceGetStreamPriorityRange; 0 is the default).  The runtime keeps one pool of hardware queues per priority, which is how a lane
+// pool reaches more queues than GPU_MAX_HW_QUEUES.  The side stream of two-phase batches is created at the default priority as before.
+int misti_create_prio_(const misti_model_t* model, int device, int priority, misti_ctx** out) {
     if (!out) return fail(MISTI_E_ARG, "out is NULL");
     *out = nullptr;
     if (int r = validate_model(model)) return r;
@@ -596,7 +599,8 @@ int misti_create(const misti_model_t* model, int device, misti_ctx** out) {
             if (t.gen1[i][j] != want1[i][j]) return fail(MISTI_E_ARG, "one-population generator mismatch at (%d,%d)", i, j);
 
         const int numT = model->numT;
-        HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        if (priority == 0) HIP_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        else HIP_TRY(hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, priority));
         if (hipHostMalloc((void**)&c->hint_host, 4 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
             c->hint_host[0] = c->hint_host[1] = c->hint_host[2] = 0;
             if (hipHostGetDevicePointer((void**)&c->hint_dev, c->hint_host, 0) != hipSuccess) c->hint_dev = nullptr;
@@ -661,6 +665,8 @@ int misti_create(const misti_model_t* model, int device, misti_ctx** out) {
     *out = c;
     return 0;
 }
+
+int misti_create(const misti_model_t* model, int device, misti_ctx** out) { return misti_create_prio_(model, device, 0, out); }
 
 int misti_destroy(misti_ctx* c) {
     if (!c) return 0;

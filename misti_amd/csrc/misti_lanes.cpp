@@ -16,6 +16,11 @@
 #include "../../include/misti_hip.h"
 
 extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp: sets the calling thread's misti_last_error
+// misti_api.cpp: misti_create on a stream priority.  This and the runtime's priority range are the only things here beyond the public
+// single-context entry points and the event calls, and both are WEAK references: the library always has them; the host-only build of
+// this file against stand-ins (tests/multi_host) has not, and is then a pool on one level made by misti_create, as before the plan.
+extern "C" int misti_create_prio_(const misti_model_t* model, int device, int priority, misti_ctx** out) __attribute__((weak));
+extern "C" hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) __attribute__((weak));
 
 namespace {
 
@@ -28,25 +33,85 @@ int faill(int code, const char* fmt, ...) {
     return misti_set_error_(code, buf);
 }
 
-// One hardware queue per lane: the HIP runtime opens GPU_MAX_HW_QUEUES queues per process (default 4) and reads the variable when it
-// initialises - at the process's first HIP call, which for a C caller comes after this library was loaded.  Never overrides a value
-// the user has set; MISTI_KEEP_HW_QUEUES=1 leaves the environment alone.
+// A hardware queue per lane where the runtime grants one.  The HIP runtime keeps one pool of hardware queues PER STREAM PRIORITY and
+// opens at most GPU_MAX_HW_QUEUES queues in each (default 4; it says so itself at AMD_LOG_LEVEL=3: "Number of allocated hardware queues
+// with low priority: 4, with normal priority: 4, with high priority: 4, maximum per priority is: 4").  It reads the variable when it
+// initialises - at the process's first HIP call, which for a C caller comes after this library was loaded - so the constructor below
+// asks for 22 where the environment names nothing.  Never overrides a value the user has set; MISTI_KEEP_HW_QUEUES=1 leaves the
+// environment alone.
+// Where the limit is smaller than the pool (a GPU_MAX_HW_QUEUES inherited from the caller, or a runtime that was up before this
+// library was loaded), streams that share a queue are serialised packet by packet: twenty lanes on four queues run four batches at a
+// time.  lane_plan() below then deals the lanes over the priority levels the device reports - three levels of four queues are twelve
+// queues, twelve long kernels beside each other where there were four (tools/ub/queue_burst.hip, profiles/lane_priorities_queue_burst.txt;
+// a kernel on the low level starts as soon and takes as long as one on the high level while the chip has room).
+// MISTI_LANE_PRIORITIES=0 keeps every lane on the default level.
 // 22, not "as many as possible": the device runs 23 queues beside each other, and with a 24th ACTIVE one a burst of batches takes 10 ms
 // instead of 2.7 (the scheduler starts time-slicing the queues; measured round 6, profiles/r06_hw_queue_cliff.txt: 22 lanes + the null
 // stream 2.9 ms, 23 lanes 10.4 ms when the runtime may open 32).  Capped at 22 the runtime never opens the 24th: streams beyond the cap
 // SHARE queues (24 lanes: 4.3 ms) - and what else a process creates (the null stream, RCCL's and PyTorch's own streams) cannot push a
-// lane pool over the edge.
+// lane pool over the edge.  The plan keeps the same cap over all levels together.
+constexpr int POOL_MAX_QUEUES = 22;
+constexpr int HIP_DEFAULT_HW_QUEUES = 4;
+
 __attribute__((constructor)) void misti_lanes_queue_env() {
     const char* keep = std::getenv("MISTI_KEEP_HW_QUEUES");
     if (keep && keep[0] && keep[0] != '0') return;
     (void)setenv("GPU_MAX_HW_QUEUES", "22", 0);
 }
 
+// Which priority level each of `n_lanes` lanes goes on: level 0 is the default priority, `q` the runtime's queue limit per level,
+// `n_levels` what the device reports, `cap` the most distinct queues the pool may occupy.  A level with n lanes occupies min(n, q)
+// queues (the runtime deals a level's streams over its queues).  Pure: no HIP call, no environment, the same answer every time.
+//  - n_lanes + 1 <= q (a queue for every lane beside the null stream) or one level: every lane on the default level.
+//  - else the levels are given queues in order, the default level first, q each until min(n_lanes, cap) are dealt; each queue gets one
+//    lane; lanes beyond the queues go to the levels that have all q queues (a level with fewer must not grow: every further lane there
+//    would open a further queue), evenly, the default level last - its queues also carry the process's null stream.
+//    So no queue carries more than ceil(n_lanes / queues) lanes - except where the cap leaves a level with fewer than q queues: that
+//    level keeps one lane per queue and the full levels carry the rest.
+//  - consecutive lanes go on different levels, so that a caller who issues round-robin reaches every queue early.
+void lane_plan(int n_lanes, int q, int n_levels, int cap, std::vector<int>& level) {
+    level.assign((size_t)n_lanes, 0);
+    if (q < 1) q = 1;
+    if (n_levels <= 1 || n_lanes + 1 <= q) return;
+    std::vector<int> lanes_on((size_t)n_levels, 0);
+    int queues = n_lanes < cap ? n_lanes : cap, full = 0;
+    for (int l = 0; l < n_levels && queues > 0; ++l) {
+        lanes_on[(size_t)l] = queues < q ? queues : q;
+        queues -= lanes_on[(size_t)l];
+        full += lanes_on[(size_t)l] == q;
+    }
+    int placed = 0;
+    for (int n : lanes_on) placed += n;
+    if (full == 0) { lanes_on[0] += n_lanes - placed; placed = n_lanes; }        // cap < q: one level, as without a plan
+    for (int l = full - 1; placed < n_lanes; l = l > 0 ? l - 1 : full - 1) { ++lanes_on[(size_t)l]; ++placed; }
+    int l = 0;
+    for (int i = 0; i < n_lanes; ++i) {
+        while (lanes_on[(size_t)l] == 0) l = (l + 1) % n_levels;
+        level[(size_t)i] = l;
+        --lanes_on[(size_t)l];
+        l = (l + 1) % n_levels;
+    }
+}
+
+// The plan of a pool that is created now: the queue limit as the environment names it (else HIP's own), MISTI_LANE_PRIORITIES=0.
+void lane_levels(int n_lanes, int n_levels, std::vector<int>& level) {
+    const char* e = std::getenv("GPU_MAX_HW_QUEUES");
+    int q = e ? std::atoi(e) : 0;
+    if (q < 1) q = HIP_DEFAULT_HW_QUEUES;
+    const char* p = std::getenv("MISTI_LANE_PRIORITIES");
+    if (p && p[0] == '0' && !p[1]) n_levels = 1;
+    lane_plan(n_lanes, q, n_levels, POOL_MAX_QUEUES, level);
+}
+
+// Level 0 is the default priority (0), levels 1, 2, ... the lower priorities (larger numbers) down to `least`, then the higher ones.
+int level_priority(int level, int least) { return level <= least ? level : least - level; }
+
 }  // namespace
 
 struct misti_lanes {
     int device = 0;
     std::vector<misti_ctx*> ctx;
+    std::vector<int> level;               // each lane's priority level (lane_plan)
     std::vector<hipStream_t> stream;      // each context's own stream (misti_get_stream at creation)
     std::vector<hipEvent_t> done;         // recorded behind every batch of the lane: "nothing in flight" is a query of it
     std::vector<char> used;               // the lane has had a batch (its event has been recorded)
@@ -98,9 +163,18 @@ int misti_create_lanes(const misti_model_t* model, int device, int n_lanes, mist
     const int r = guarded("misti_create_lanes", [&]() -> int {
         L = new misti_lanes;
         L->device = device;
+        // the levels the device has (least = the lowest priority = the largest number); a device that cannot be asked has one, and the
+        // first context reports what is wrong with it
+        int least = 0, greatest = 0;
+        if (!misti_create_prio_ || !hipDeviceGetStreamPriorityRange || hipSetDevice(device) != hipSuccess ||
+            hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = 0; }
+        if (least < 0) least = 0;
+        if (greatest > 0) greatest = 0;
+        lane_levels(n_lanes, least - greatest + 1, L->level);
         for (int i = 0; i < n_lanes; ++i) {
             misti_ctx* c = nullptr;
-            if (int q = misti_create(model, device, &c)) return q;            // the message is the context's
+            const int lv = L->level[(size_t)i];
+            if (int q = lv ? misti_create_prio_(model, device, level_priority(lv, least), &c) : misti_create(model, device, &c)) return q;   // the message is the context's
             L->ctx.push_back(c);
             void* s = nullptr;
             if (int q = misti_get_stream(c, &s)) return q;
@@ -125,6 +199,25 @@ int misti_destroy_lanes(misti_lanes* L) {
     if (!L) return 0;
     release(L);
     return 0;
+}
+
+// internal (tests): the plan without a device.  `queues_per_level` > 0: lane_plan itself with that limit and `max_queues`;
+// 0: what misti_create_lanes would do in this environment on a device with `n_levels` levels.  levels[n_lanes] receives each lane's level.
+int misti_lane_plan_(int n_lanes, int queues_per_level, int n_levels, int max_queues, int* levels) {
+    if (n_lanes < 1 || n_lanes > MISTI_MAX_LANES || n_levels < 1 || !levels) return faill(MISTI_E_ARG, "misti_lane_plan_: bad argument");
+    return guarded("misti_lane_plan_", [&]() -> int {
+        std::vector<int> level;
+        if (queues_per_level > 0) lane_plan(n_lanes, queues_per_level, n_levels, max_queues, level);
+        else lane_levels(n_lanes, n_levels, level);
+        for (int i = 0; i < n_lanes; ++i) levels[i] = level[(size_t)i];
+        return 0;
+    });
+}
+
+// internal (tests): the priority level lane i's stream was created on (0: the default level); < 0: no such lane
+int misti_lanes_level_(misti_lanes* L, int i) {
+    if (!L || i < 0 || i >= (int)L->level.size()) return faill(MISTI_E_ARG, "no such lane");
+    return L->level[(size_t)i];
 }
 
 int misti_lanes_size(misti_lanes* L) { return L ? (int)L->ctx.size() : 0; }

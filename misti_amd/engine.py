@@ -446,6 +446,14 @@ class Lanes:
         e.numT, e.n_param, e.n_band, e.device, e.unfolded = self.numT, self.n_param, self.n_band, self.device, False
         return e
 
+    def level(self, i):
+        """The stream-priority level lane i was created on (0: the default level).  The library deals the lanes over the levels where
+        the runtime's queue limit per level is smaller than the pool (misti_lanes.cpp); an internal entry point, for tests and tools."""
+        r = int(self._lib.misti_lanes_level_(self._h, C.c_int(int(i))))
+        if r < 0:
+            _lib.check(r)
+        return r
+
     def set_hints(self, integer_splits=False):
         _lib.check(self._lib.misti_lanes_set_hints(self._h, _lib.HINT_INTEGER_SPLITS if integer_splits else 0))
 

@@ -4,9 +4,10 @@ One batch is latency-bound (its longest lambda-correction chain is as sequential
 solver: ~1.9 ms for the 4 096-point headline grid while 64 of 1 024 SIMDs are busy), so throughput
 comes from having many independent batches in flight - bootstrap scans of several data sets, grids
 of several models, the vertices of several optimisers.  A lane is one engine context with its own
-non-blocking HIP stream (own streams map one-to-one onto hardware queues, 24 per
-process; torch's pooled streams share them); batches submitted to different lanes overlap on the GPU,
-batches of one lane run in submission order.
+non-blocking HIP stream (own streams map onto hardware queues, one each while the
+runtime's limit allows - where it does not, the library deals the lanes over the stream-priority levels,
+each of which has a queue pool of its own; torch's pooled streams share queues); batches submitted to
+different lanes overlap on the GPU, batches of one lane run in submission order.
 
     pool = LanePool(times, lh, bands, pulses, n_param=1, cpfit=True, smooth=True, lanes=20)
     tickets = [pool.submit(split_k, params_k, jsfs_k) for k in range(100)]      # device tensors, asynchronous
@@ -21,7 +22,8 @@ import os
 import numpy as np
 
 # the HIP runtime reads this when it initialises: one hardware queue per lane needs more than its default of 4
-# (no effect if the runtime is already up - then export it before starting Python)
+# (no effect if the runtime is already up or the caller's environment names a value - the library then spreads the
+# lanes over the priority levels' queue pools, three times the limit)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "22")       # 22: misti_lanes.cpp says why not more
 
 from .engine import Lanes

@@ -91,13 +91,24 @@ def main():
     print("# %s: %d steps on %d lanes, best of %d repetitions; ms from the first launch" % (a.workload, a.steps, L, a.reps))
     print("# wall (first launch -> torch.cuda.synchronize returns) %.3f ms = %.3e evals/s; host issue %.3f ms; last batch ends (device) %.3f ms -> the tail behind it %.3f ms"
           % (best["wall"], a.steps * n * R / best["wall"] * 1e3, best["issue"], max(best["end"]), best["wall"] - max(best["end"])))
-    print("# step lane issued start end duration" + ("  chains+setup spectrum" if a.stage_timing else ""))
+    # the stream-priority level of every lane (misti_lanes.cpp: lane_plan); a build from before the plan has every lane on level 0
+    level = [pool.level(i) if hasattr(pool._lib, "misti_lanes_level_") else 0 for i in range(L)]
+    edges = sorted([(t, 1) for t in best["start"]] + [(t, -1) for t in best["end"]], key=lambda x: (x[0], x[1]))
+    depth = most = 0
+    for _, d in edges:
+        depth += d
+        most = max(most, depth)
+    print("# GPU_MAX_HW_QUEUES=%s; most batches in flight at one moment: %d" % (os.environ.get("GPU_MAX_HW_QUEUES"), most))
+    for lv in sorted(set(level)):
+        dur = [best["end"][k] - best["start"][k] for k in range(a.steps) if level[k % L] == lv]
+        print("# level %d: %d lanes, %d batches, start to end %.3f ms mean, %.3f .. %.3f" % (lv, level.count(lv), len(dur), sum(dur) / len(dur), min(dur), max(dur)))
+    print("# step lane level issued start end duration" + ("  chains+setup spectrum" if a.stage_timing else ""))
     for k in range(a.steps):
         extra = ""
         if a.stage_timing and k < L:
             st = best["stages"][k % L]
             extra = "  %.3f %.3f" % (st["correct"], st["spectrum"])
-        print("%2d %2d %.3f %.3f %.3f %.3f%s" % (k, k % L, best["issued"][k], best["start"][k], best["end"][k], best["end"][k] - best["start"][k], extra))
+        print("%2d %2d %d %.3f %.3f %.3f %.3f%s" % (k, k % L, level[k % L], best["issued"][k], best["start"][k], best["end"][k], best["end"][k] - best["start"][k], extra))
     pool.close()
 
 

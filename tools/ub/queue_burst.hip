@@ -33,13 +33,35 @@ int main(int argc, char** argv) {
     const int wait_mode = argc > 2 ? atoi(argv[2]) : 0;
     if (argc > 3) hipSetDeviceFlags(atoi(argv[3]) ? hipDeviceScheduleSpin : hipDeviceScheduleBlockingSync);
     const int use_graph = argc > 4 ? atoi(argv[4]) : 0;      // 1: the launches of a stream are ONE captured graph (hipGraphLaunch per stream)
+    // argv[6]: how the streams are created.  0 hipStreamCreateWithFlags (the default level);  1 hipStreamCreateWithPriority, every stream on
+    // the default level;  2 hipStreamCreateWithPriority, stream i on level i % (number of levels hipDeviceGetStreamPriorityRange reports) -
+    // the runtime keeps one pool of GPU_MAX_HW_QUEUES hardware queues PER LEVEL.  With 1 or 2 every line is followed by the number of long
+    // kernels that ran beside each other (from the stamps) and, per level, when its long kernels started and how long they took start to end.
+    const int prio_mode = argc > 6 ? atoi(argv[6]) : 0;
+    int prio_least = 0, prio_greatest = 0;                   // least = lowest priority = the LARGEST number
+    hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
+    const int n_levels = prio_least - prio_greatest + 1;
+    if (prio_mode) printf("stream priorities %d (greatest) .. %d (least): %d levels; streams %s\n", prio_greatest, prio_least, n_levels,
+                          prio_mode == 2 ? "dealt over the levels" : "all on level 0");
+    // level 0 is the default priority (0), then the lower ones, then the higher ones
+    auto level_priority = [&](int level) {
+        std::vector<int> order{0};
+        for (int p = 1; p <= prio_least; ++p) order.push_back(p);
+        for (int p = -1; p >= prio_greatest; --p) order.push_back(p);
+        return order[(size_t)level % order.size()];
+    };
     hipStream_t join;
     hipStreamCreateWithFlags(&join, hipStreamNonBlocking);
     std::vector<hipEvent_t> evs(32);
     for (auto& e : evs) hipEventCreateWithFlags(&e, hipEventDisableTiming);
     for (int N : {4, 12, 20}) {
         std::vector<hipStream_t> st(N);
-        for (auto& s : st) hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        std::vector<int> prio(N, 0);
+        for (int i = 0; i < N; ++i) {
+            if (!prio_mode) { hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking); continue; }
+            prio[i] = prio_mode == 2 ? level_priority(i % n_levels) : 0;
+            hipStreamCreateWithPriority(&st[i], hipStreamNonBlocking, prio[i]);
+        }
         for (auto& sh : shapes) {
             std::vector<hipGraphExec_t> gx(N, nullptr);
             if (use_graph) {
@@ -57,7 +79,7 @@ int main(int argc, char** argv) {
                 hipDeviceSynchronize();
             }
             double best = 1e30;
-            std::vector<double> starts;
+            std::vector<double> starts, ends;
             for (int rep = 0; rep < 5; ++rep) {
                 hipDeviceSynchronize();
                 const auto t0 = std::chrono::steady_clock::now();
@@ -85,9 +107,11 @@ int main(int argc, char** argv) {
                 if (ms < best) {
                     best = ms;
                     starts.clear();
+                    ends.clear();
                     long long first = stamps[0];
                     for (int i = 0; i < N; ++i) first = std::min(first, stamps[2 * i]);
                     for (int i = 0; i < N; ++i) starts.push_back((stamps[2 * i] - first) / 100.0);
+                    for (int i = 0; i < N; ++i) ends.push_back((stamps[2 * i + 1] - first) / 100.0);
                     long long last = 0;
                     for (int i = 0; i < N; ++i) last = std::max(last, stamps[2 * i + 1]);
                     starts.push_back((last - first) / 100.0);
@@ -100,6 +124,25 @@ int main(int argc, char** argv) {
                    N, sh[0], sh[1], best, starts[N + 2], starts[N], starts[N + 1]);
             if (argc > 5) { printf("  long-kernel starts [us]:"); for (int i = 0; i < N; ++i) printf(" %.0f", starts[i]); }
             printf("\n");
+            if (prio_mode) {
+                int beside = 0;                              // the most long kernels running at one moment: counted at every start
+                for (int i = 0; i < N; ++i) {
+                    int n = 0;
+                    for (int j = 0; j < N; ++j) n += starts[j] <= starts[i] && starts[i] < ends[j];
+                    beside = std::max(beside, n);
+                }
+                printf("    long kernels beside each other: %d of %d;", beside, N);
+                for (int p = prio_greatest; p <= prio_least; ++p) {
+                    int n = 0;
+                    double s0 = 1e30, s1 = 0, dur = 0, dmax = 0;
+                    for (int i = 0; i < N; ++i) if (prio[i] == p) {
+                        ++n; s0 = std::min(s0, starts[i]); s1 = std::max(s1, starts[i]);
+                        dur += ends[i] - starts[i]; dmax = std::max(dmax, ends[i] - starts[i]);
+                    }
+                    if (n) printf("  priority %d: %d streams, starts %.0f .. %.0f us, start to end mean %.0f max %.0f us;", p, n, s0, s1, dur / n, dmax);
+                }
+                printf("\n");
+            }
         }
         for (auto& s : st) hipStreamDestroy(s);
     }
