@@ -236,6 +236,32 @@ int misti_scan_best_dev(misti_ctx* ctx, int64_t n_cand, const double* d_jafs, co
                         int64_t n_rep, const double* d_jsfs, int32_t k,
                         int32_t* d_best /* [n_rep][k] */, double* d_best_llk /* [n_rep][k] or NULL */);
 
+/* The PROFILE likelihood per group and replicate WITHOUT the table: every candidate c carries a group label d_group[c] - the value
+ * of one scanned quantity, or of a pair of them - and per replicate r and group g the best candidate of the group is kept: the curve
+ * "llh against split time" of every bootstrap row, with everything else that was scanned maximised out.  Memory: nothing of size
+ * n_cand x n_rep is allocated; the context keeps O(n_cand + n_group) integers (the group index, built on the device without a host
+ * synchronisation) and the partial results of the library's cut of the work (slices x n_group x n_rep), grown on demand.
+ * Arguments as for misti_scan_best_dev (device pointers; d_status may be NULL: all OK; llh_const per row is computed inside; the
+ * spectra come from any evaluation with n_rep == 0).
+ * Rule:
+ *   - the value of candidate c for row r is the value misti_llk_dev would write, the same bits;
+ *   - a candidate takes part in group g = d_group[c] only if 0 <= g < n_group; any other label means "in no group": it is
+ *     skipped, never an error and never an out-of-range access;
+ *   - d_prof_llk[r][g] is the largest value v > -inf among the group's candidates (NaN never qualifies; a status other than 0
+ *     gives no value), d_prof_best[r][g] (may be NULL) the LOWEST candidate index that attains it;
+ *   - a group with no such candidate holds -inf / -1;
+ *   - the comparison is a total order, value descending and then index ascending: the result depends neither on the order in
+ *     which candidates are walked nor on how the library cuts the work.
+ * n_group == 1 is misti_scan_best_dev with k == 1; labels 0 ... n_cand - 1 give the transposed table.
+ * MISTI_E_ARG for n_group < 1, a negative count or a NULL d_jafs / d_jsfs / d_group / d_prof_llk with work to do, MISTI_E_LIMIT for
+ * n_cand > INT32_MAX or n_group > MISTI_SCAN_MAX_GROUPS - before anything touches the device.  n_rep == 0 writes nothing;
+ * n_cand == 0 fills -inf / -1.  Asynchronous on the context's stream. */
+#define MISTI_SCAN_MAX_GROUPS 65535
+int misti_scan_profile_dev(misti_ctx* ctx, int64_t n_cand, const double* d_jafs, const int32_t* d_status,
+                           const int32_t* d_group /* [n_cand] */, int32_t n_group,
+                           int64_t n_rep, const double* d_jsfs,
+                           double* d_prof_llk /* [n_rep][n_group] */, int32_t* d_prof_best /* [n_rep][n_group] or NULL */);
+
 /* Diagnostic of the last batch evaluated on this context (either form): per candidate the
  * largest corrected rate x interval length before smoothing (NaN where the candidate has no
  * value, 0 with MISTI_TRUE_EPS).  From ~5 upwards the correction's residual is nearly flat in

@@ -26,6 +26,7 @@ LANE_ANY, MAX_LANES = -1, 64
 ABI_VERSION = 6
 TRACE_MAX_CAND, TRACE_MAX_ITER = 64, 200
 SCAN_MAX_BEST = 8
+SCAN_MAX_GROUPS = 65535
 
 
 class Band(C.Structure):
@@ -92,6 +93,7 @@ SYMBOLS = {
     "misti_forward_rates_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_argmax_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_scan_best_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "misti_scan_profile_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_last_diag": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "misti_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "misti_kernel_times": (C.c_int, [C.c_void_p, _PD, C.POINTER(C.c_int64), C.c_int]),

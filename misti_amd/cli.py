@@ -36,6 +36,15 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               the K listed candidates of every row (optimize.scan_polish); per row the MiSTI.py:240 line of its
                               best polished search, as --grid-solve prints its pairs - K searches per row where --grid-solve runs
                               one from every (split, start) pair
+    --profile AXIS [AXIS]     with --grid-st and/or --grid-mi: the PROFILE likelihood along one scanned axis, or the surface over two -
+                              AXIS is `st` or the index K of an optimised parameter as --grid-mi K names it.  Grid mode evaluates
+                              WITHOUT replicates and reduces on the device (misti_scan_profile_dev; the table is never made): per row
+                              and per value of the axis one line with the best llh over every other scanned quantity and the candidate
+                              that attains it, then the best: line, for one axis a support: line per row (the axis values within
+                              --profile-drop D of the row's maximum; D defaults to half the 95 % point of chi-square with one degree of
+                              freedom - a likelihood-ratio support interval of a composite likelihood, not a confidence interval), with
+                              --all-bs and axis st the bootstrap interval, and the timing line.  Not offered with --top, --polish,
+                              --fit-st, --grid-solve, --sweep, --sweep-pu, --gpus N > 1 or --devices
     --gpus N                  the sweep on N GPUs of the node: this process starts N ranks (one per GPU, torch.distributed over
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
@@ -112,6 +121,10 @@ def build_parser():
                    help="grid mode (--grid-st / --grid-mi): keep the K best candidates per row (1 ... 8), reduced on the device without the table")
     p.add_argument("--polish", action="store_true",
                    help="with --top K: one batched search from the K listed candidates of every row; per row its best polished search")
+    p.add_argument("--profile", nargs="+", default=None, metavar="AXIS",
+                   help="grid mode: the profile likelihood per row along one scanned axis (st, or K of --grid-mi K) or over two, reduced on the device without the table")
+    p.add_argument("--profile-drop", type=float, default=None, metavar="D",
+                   help="with --profile AXIS: the support: line lists the axis values within D of the row's maximum (default: chi2.ppf(0.95, 1) / 2)")
     p.add_argument("--sweep", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="the GNU-parallel recipe's `::: NAME V1 V2 ...`: {NAME} in the split time or in -mi start / end / rate fields")
     p.add_argument("--sweep-pu", nargs="+", action="append", default=[], metavar=("NAME", "V"),
@@ -167,6 +180,42 @@ def top_error(a):
         return "--top runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
     if a.polish and not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
         return "--polish needs at least one optimised parameter (-mi ... 1 or -pu ... 1)"
+    return None
+
+
+def profile_error(a):
+    """Why ``--profile`` / ``--profile-drop`` cannot run with these options (checked before any file is read or the GPU is touched), or
+    None."""
+    if a.profile is None:
+        if a.profile_drop is not None:
+            return "--profile-drop sets the support interval of a profile: give --profile AXIS"
+        return None
+    if len(a.profile) > 2:
+        return "--profile takes one axis (a curve) or two axes (a surface): at most two, got %d" % len(a.profile)
+    scanned = {int(g[0]) for g in a.grid_mi if g[0].isdigit()}     # (a malformed --grid-mi is for grid mode to refuse, not for this check)
+    for axis in a.profile:
+        if axis == "st":
+            if not a.grid_st:
+                return "--profile st: the split time is not scanned - give --grid-st A B [STEP]"
+        elif axis.isdigit():
+            if int(axis) not in scanned:
+                return "--profile %s: parameter %s is not scanned - give --grid-mi %s LO HI N" % (axis, axis, axis)
+        else:
+            return "--profile %s: unknown axis - an axis is st or the index K of an optimised parameter (--grid-mi K)" % axis
+    if len(set(a.profile)) != len(a.profile):
+        return "--profile %s %s names the same axis twice" % tuple(a.profile)
+    if a.profile_drop is not None and not a.profile_drop >= 0:
+        return "--profile-drop must not be negative (got %g)" % a.profile_drop
+    if a.top is not None or a.polish:
+        return "--profile keeps the best candidate per axis value, --top / --polish the best per row: give one of them"
+    if a.fit_st:
+        return "--profile reduces a scanned grid, --fit-st fits the split time: give one of them"
+    if a.grid_solve:
+        return "--profile reduces a scanned grid, --grid-solve searches from every pair: give one of them"
+    if a.sweep or a.sweep_pu:
+        return "--profile reduces the grid of --grid-st / --grid-mi: --sweep / --sweep-pu are not offered with it"
+    if a.gpus > 1 or a.devices:
+        return "--profile runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
     return None
 
 
@@ -339,6 +388,70 @@ def grid_top(a, inp, rows):
             print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, pol["x"][r], pol["llh"][r]))
         print("polish: %d searches in one batched search (%d rows x at most %d listed candidates); %d rows ended on the iteration cap"
               % (pol["searches"]["cand"].size, R, a.top, int((pol["status"] == 2).sum())))
+    print("Evaluated %d candidates x %d replicates in %.3f s (%.0f llk evals/s); %.1f%% without a value"
+          % (len(split), R, dt, len(split) * R / dt, 100 * float((status != 0).mean())))
+    return 0
+
+
+def grid_profile(a, inp, rows):
+    """Grid mode with --profile: the same candidates and rows, evaluated without replicates and reduced on the device to the best
+    candidate per row and per value of the named axis or pair of axes (optimize.scan_profile; the labels are optimize.axis_groups of
+    the grid's shape: the split is its outermost axis, parameter K its axis 1 + K)."""
+    from .optimize import _t_interval, axis_groups, profile_interval, scan_profile
+    splits, bands, pulses, k, axes = grid_model(a)
+    mesh = np.meshgrid(np.array(splits), *axes, indexing="ij")
+    split = mesh[0].ravel()
+    params = np.stack([m.ravel() for m in mesh[1:]], axis=1) if k else None
+    data, ids = _data_rows(a, rows)
+    which = [0 if t == "st" else 1 + int(t) for t in a.profile]
+    names = ["st" if t == "st" else "p" + t for t in a.profile]
+    values = [np.asarray(mesh[w]).ravel() for w in which]                 # per candidate: its value on each named axis
+    group, G = axis_groups(mesh[0].shape, which)
+    flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    t0 = time.time()
+    with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
+        prof, best, status = scan_profile(e, split, params, data, group, G)
+    dt = time.time() - t0
+    R = data.shape[0]
+    at = np.full(G, -1, dtype=np.int64)                                   # any member of each group: it carries the group's axis values
+    at[group] = np.arange(group.size)
+    text = lambda t, v: str(v) if t == "st" else "%.6g" % v
+    for r in range(R):
+        for g in range(G):
+            where = " \t".join("%s = %s" % (nm, text(t, v[at[g]])) for nm, t, v in zip(names, a.profile, values))
+            c = best[r, g]
+            if c < 0:                                                     # (the group has no value: llh = -inf and no candidate)
+                print("bs_id =", ids[r], "\tprofile", where, "\tllh =", prof[r, g])
+                continue
+            pstr = "" if params is None else "\t".join("%.6g" % v for v in params[c])
+            print("bs_id =", ids[r], "\tprofile", where, "\tllh =", prof[r, g], "\tsplitT =", split[c], "\tparams", pstr, "\tstatus =", int(status[c]))
+    has = (best >= 0).any(axis=1)
+    # per row the lowest candidate that attains the row's maximum: the table's first maximum of that row
+    top = prof.max(axis=1)
+    first = np.array([best[r][prof[r] == top[r]].min() if has[r] else -1 for r in range(R)], dtype=np.int64)
+    if has.any():
+        # grid mode's best: the first maximum of the table in candidate-major order - the lowest candidate, then the lowest row
+        c, r = min((first[r], r) for r in range(R) if top[r] == top.max())
+        print("\nbest: splitT =", split[c], "params =", None if params is None else list(params[c]), "replicate =", r, "llh =", top[r])
+    else:
+        print("\nbest: no candidate has a value")                       # (as --top prints it; grid mode names candidate 0 with llh = -inf there)
+    if len(a.profile) == 1:
+        drop = a.profile_drop
+        if drop is None:
+            from scipy import stats
+            drop = 0.5 * stats.chi2.ppf(0.95, 1)
+        axis_values = np.asarray(splits if a.profile[0] == "st" else axes[int(a.profile[0])], dtype=float)
+        iv = profile_interval(prof, axis_values, drop)
+        for r in range(R):
+            if not has[r]:
+                print("support: bs_id =", ids[r], "has no value at any %s" % names[0])
+                continue
+            print("support: bs_id =", ids[r], "best %s =" % names[0], text(a.profile[0], iv["best"][r]), "llh =", iv["llh"][r],
+                  "within %.6g of it: %s in [%s, %s]" % (drop, names[0], text(a.profile[0], iv["lo"][r]), text(a.profile[0], iv["hi"][r])))
+    if a.all_bs and "st" in a.profile and len(splits) > 1 and R > 1:
+        # grid mode's interval (test.bs/bs_conf_int.ipynb) from the rows' arg-max; a row without a value counts as candidate 0, as there
+        mean, (lo, hi), _ = _t_interval(split[np.where(has, first, 0)], 0.95)
+        print("bootstrap: best splitT per replicate mean = %.6g, 95%% interval = [%.6g, %.6g] over %d replicates" % (mean, lo, hi, R))
     print("Evaluated %d candidates x %d replicates in %.3f s (%.0f llk evals/s); %.1f%% without a value"
           % (len(split), R, dt, len(split) * R / dt, 100 * float((status != 0).mean())))
     return 0
@@ -532,7 +645,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = top_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
+    why = profile_error(a) or top_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
@@ -586,6 +699,8 @@ def main(argv=None):
         return grid_solve(a, inp, rows)
     if a.top is not None:
         return grid_top(a, inp, rows)
+    if a.profile is not None:
+        return grid_profile(a, inp, rows)
     if a.grid_st or a.grid_mi or a.all_bs:
         return grid_mode(a, inp, rows)
 

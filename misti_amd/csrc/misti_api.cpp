@@ -88,6 +88,7 @@ struct misti_ctx {
     DevBuf model_f64, model_i32;        // times | lh ; run_start | run_end
     DevBuf consts;                      // llh_const per replicate
     DevBuf scan_v, scan_i;              // misti_scan_best_dev: the slices' lists [slices][width][n_rep], values and indices
+    DevBuf prof_v, prof_i, prof_idx;    // misti_scan_profile_dev: the slices' pairs [slices][n_group][n_rep]; first [n_group + 1] | cursor [n_group] | members [n_cand]
     DevBuf ws_jafs, ws_status;          // spectra / status when the caller passes NULL
     DevBuf ws_order;                    // dispatch order (heaviest candidates first)
     DevBuf ws_diag;                     // per candidate: largest corrected rate x interval length of the last batch
@@ -684,7 +685,7 @@ int misti_destroy(misti_ctx* c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     (void)hipGetLastError();
     for (auto* b : {&c->model_f64, &c->model_i32, &c->consts, &c->ws_jafs, &c->ws_status, &c->ws_chain_f64, &c->ws_chain_i32, &c->ws_order, &c->ws_diag, &c->ws_trunk, &c->ws_solver, &c->ws_iters, &c->ws_post,
-                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i})
+                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx})
         b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -795,6 +796,31 @@ int misti_scan_best_dev(misti_ctx* c, int64_t n_cand, const double* d_jafs, cons
     }
     HIP_TRY(misti::launch_scan_best(n_cand, d_jafs, d_status, n_rep, d_jsfs, c->consts.as<double>(), k, d_best, d_best_llk, slices,
                                     c->scan_v.as<double>(), c->scan_i.as<int32_t>(), c->unfolded, c->stream));
+    return 0;
+}
+
+int misti_scan_profile_dev(misti_ctx* c, int64_t n_cand, const double* d_jafs, const int32_t* d_status, const int32_t* d_group, int32_t n_group,
+                           int64_t n_rep, const double* d_jsfs, double* d_prof_llk, int32_t* d_prof_best) {
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (n_group < 1) return fail(MISTI_E_ARG, "n_group must be at least 1 (got %d)", (int)n_group);
+    if (n_cand < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative batch size");
+    if (n_group > MISTI_SCAN_MAX_GROUPS) return fail(MISTI_E_LIMIT, "n_group beyond MISTI_SCAN_MAX_GROUPS = %d (got %d)", MISTI_SCAN_MAX_GROUPS, (int)n_group);
+    if (n_cand > INT32_MAX) return fail(MISTI_E_LIMIT, "n_cand too large");
+    if (n_rep == 0) return 0;
+    if (!d_prof_llk || (n_cand > 0 && (!d_jafs || !d_jsfs || !d_group))) return fail(MISTI_E_ARG, "jafs / jsfs / group / prof_llk is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t slices = misti::scan_profile_slices(n_cand, n_group, n_rep, c->tune);
+    if (n_cand > 0) {
+        const size_t part = (size_t)slices * (size_t)n_group * (size_t)n_rep;
+        HIP_TRY(c->consts.reserve((size_t)n_rep * sizeof(double)));
+        HIP_TRY(c->prof_v.reserve(part * sizeof(double)));
+        HIP_TRY(c->prof_i.reserve(part * sizeof(int32_t)));
+        HIP_TRY(c->prof_idx.reserve(misti::scan_profile_index_size(n_cand, n_group) * sizeof(int32_t)));
+        HIP_TRY(misti::launch_llh_const(n_rep, d_jsfs, c->consts.as<double>(), c->unfolded, c->stream));
+    }
+    // (the buffers are passed as they are: without candidates they may be NULL, and no address is derived from them here)
+    HIP_TRY(misti::launch_scan_profile(n_cand, d_jafs, d_status, d_group, n_group, n_rep, d_jsfs, c->consts.as<double>(), d_prof_llk, d_prof_best, slices,
+                                       c->prof_idx.as<int32_t>(), c->prof_v.as<double>(), c->prof_i.as<int32_t>(), c->unfolded, c->stream));
     return 0;
 }
 

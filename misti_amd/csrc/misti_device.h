@@ -217,7 +217,7 @@ struct Tuning {
     int k2_single_waves = -1;  // MISTI_K2_SINGLE_WAVES: 1 / 0 forces kernel 2's workgroups to one / four waves (-1: chosen per batch, run_dev)
     int busy_contexts = -1;    // MISTI_FOLLOW_BUSY_CONTEXTS: other contexts with a batch in flight from which on a batch of more than
                                // FOLLOW_BUSY_CHAINS chains is packed (-1: FOLLOW_BUSY_CONTEXTS; 0: never look, always the latency shape)
-    int scan_slices = 0;       // MISTI_SCAN_SLICES: forces the number of candidate slices of misti_scan_best_dev (0: scan_best_slices' choice)
+    int scan_slices = 0;       // MISTI_SCAN_SLICES: forces the number of candidate slices of misti_scan_best_dev / misti_scan_profile_dev (0: scan_best_slices' / scan_profile_slices' choice)
 };
 Tuning read_tuning();
 int64_t trunk_capacity(int64_t n_cand, const Tuning& tn);
@@ -242,6 +242,17 @@ int scan_best_width(int k);
 int64_t scan_best_slices(int64_t n_cand, int64_t n_rep, const Tuning& tn);
 hipError_t launch_scan_best(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs, const double* consts,
                             int k, int32_t* best, double* best_llk, int64_t slices, double* part_v, int32_t* part_i, int unfolded, hipStream_t stream);
+// The profile per group and replicate without the table (misti_scan_profile_dev): per (replicate, group) the best candidate of the
+// group, llk_kernel's values under the scan's total order.  `index` (scan_profile_index_size(...) integers: first [n_group + 1],
+// cursor [n_group], members [n_cand]) is the group index, built on the device: count, exclusive scan, scatter; `slices` =
+// scan_profile_slices(...) pairs per (group, replicate) go through part_v / part_i ([slices][n_group][n_rep] each), then one merge
+// launch writes prof_llk[n_rep][n_group] / prof_best (NULL: not wanted).  n_cand == 0 (slices == 0): -inf / -1 everywhere; index,
+// part_v and part_i may then be NULL and only the outputs are touched.
+int64_t scan_profile_slices(int64_t n_cand, int64_t n_group, int64_t n_rep, const Tuning& tn);
+size_t scan_profile_index_size(int64_t n_cand, int64_t n_group);
+hipError_t launch_scan_profile(int64_t n_cand, const double* jafs, const int32_t* status, const int32_t* group, int32_t n_group,
+                               int64_t n_rep, const double* jsfs, const double* consts, double* prof_llk, int32_t* prof_best,
+                               int64_t slices, int32_t* index, double* part_v, int32_t* part_i, int unfolded, hipStream_t stream);
 hipError_t launch_llh_const(int64_t n_rep, const double* jsfs, double* consts, int unfolded, hipStream_t stream);
 hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status, int64_t n_rep, const double* jsfs,
                       const double* consts, double* llk, int unfolded, hipStream_t stream);

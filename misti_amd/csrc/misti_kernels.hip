@@ -3324,6 +3324,207 @@ hipError_t launch_scan_best(int64_t n_cand, const double* jafs, const int32_t* s
     return hipGetLastError();
 }
 
+// The PROFILE per group and replicate WITHOUT the table (misti_scan_profile_dev): every candidate carries a group label, and per
+// (replicate, group) the best candidate of that group is kept - a segmented form of the scan above, llk_kernel's values again (the
+// same expressions, the same bits).  Order: value descending, candidate index ascending on equal values, only v > -inf qualifies.
+// Three small index kernels bucket the candidates by label on the device (no host synchronisation): a count per group, an
+// exclusive scan over the groups, a scatter into a member list.  The scatter order inside a group is whatever order the atomics
+// arrive in, so the reduction compares (value, index) pairs as a total order and never relies on the order of the walk.
+// count[g] = members of group g; a label outside 0 ... n_group - 1 is in no group.
+__global__ __launch_bounds__(256)
+void profile_count_kernel(int64_t n_cand, const int32_t* __restrict__ group, int32_t n_group, int32_t* __restrict__ count) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_cand) return;
+    const int32_t g = group[c];
+    if (g >= 0 && g < n_group) atomicAdd(&count[g], 1);
+}
+
+// One workgroup: first[0 ... n_group] = the exclusive scan of count[0 ... n_group), and count[g] = first[g] (the scatter's cursor).
+// A thread sums a contiguous run of groups, the 256 run sums are scanned in LDS, then every thread walks its run again.
+__global__ __launch_bounds__(256)
+void profile_offsets_kernel(int32_t n_group, int32_t* __restrict__ count, int32_t* __restrict__ first) {
+    __shared__ int32_t run[256];
+    const int per = (n_group + 255) / 256;
+    const int g0 = (int)threadIdx.x * per;
+    const int g1 = g0 + per < n_group ? g0 + per : n_group;
+    int32_t sum = 0;
+    for (int g = g0; g < g1; ++g) sum += count[g];
+    run[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int32_t below = (int)threadIdx.x >= d ? run[threadIdx.x - d] : 0;
+        __syncthreads();
+        run[threadIdx.x] += below;
+        __syncthreads();
+    }
+    int32_t acc = run[threadIdx.x] - sum;              // members of every group in front of this run
+    for (int g = g0; g < g1; ++g) {
+        const int32_t n = count[g];
+        first[g] = acc;
+        count[g] = acc;
+        acc += n;
+    }
+    if (threadIdx.x == 255) first[n_group] = run[255];
+}
+
+// members[first[g] ... first[g + 1]) = the candidates of group g, in the order their atomics arrive.
+__global__ __launch_bounds__(256)
+void profile_scatter_kernel(int64_t n_cand, const int32_t* __restrict__ group, int32_t n_group, int32_t* __restrict__ cursor,
+                            int32_t* __restrict__ members) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_cand) return;
+    const int32_t g = group[c];
+    if (g >= 0 && g < n_group) members[atomicAdd(&cursor[g], 1)] = (int32_t)c;
+}
+
+// thread = one replicate (class counts, constant and ONE (best value, best index) pair in registers); blockIdx.y = a group,
+// blockIdx.z = a SLICE of that group's member list (slice s of a list of n walks members s * per ... with per = ceil(n / slices)),
+// walked in chunks of SCAN_CHUNK whose class logs, no-value flags and candidate indices the block gathers into LDS through the member
+// list.  Each (slice, group) leaves its pair in part_v / part_i [slice][group][n_rep] (the replicate innermost: coalesced here and in
+// the merge); a slice of an empty group, or beyond a short list, leaves -inf / -1.  Replicate blocks beyond gridDim.x are walked by
+// the same workgroup (a launch never exceeds the grid limits however many rows there are).
+template <bool UNFOLDED>
+__global__ __launch_bounds__(256)
+void scan_profile_kernel(int32_t n_group, const int32_t* __restrict__ first, const int32_t* __restrict__ members,
+                         const double* __restrict__ jafs, const int32_t* __restrict__ status,
+                         int64_t n_rep, const double* __restrict__ jsfs, const double* __restrict__ consts,
+                         double* __restrict__ part_v, int32_t* __restrict__ part_i) {
+    constexpr int NF = UNFOLDED ? 7 : 4;
+    __shared__ double lj[SCAN_CHUNK][8];              // [7] = 1.0 where the candidate has no value (status != OK), else 0.0
+    __shared__ int32_t lc[SCAN_CHUNK];                // the candidate's index
+    const int32_t g = (int32_t)blockIdx.y;
+    const int64_t m0 = first[g];
+    const int64_t n_mem = first[g + 1] - m0;
+    const int64_t per = (n_mem + gridDim.z - 1) / gridDim.z;
+    const int64_t s0 = (int64_t)blockIdx.z * per < n_mem ? (int64_t)blockIdx.z * per : n_mem;
+    const int64_t s1 = s0 + per < n_mem ? s0 + per : n_mem;
+    const int64_t rep_blocks = (n_rep + 255) / 256;
+    for (int64_t rb = blockIdx.x; rb < rep_blocks; rb += gridDim.x) {
+        const int64_t r = rb * 256 + threadIdx.x;
+        const int64_t rr = r < n_rep ? r : n_rep - 1;  // a lane beyond the table repeats the last row (never stored)
+        double f[NF];
+        {
+            const double* d = jsfs + rr * 8 + 1;
+            if (UNFOLDED) { for (int i = 0; i < 7; ++i) f[i] = d[i]; }
+            else { f[0] = d[0] + d[6]; f[1] = d[1] + d[5]; f[2] = d[2] + d[4]; f[3] = d[3]; }
+        }
+        const double cst = consts[rr];
+        double bv = -INFINITY;
+        int32_t bi = -1;
+        for (int64_t c0 = s0; c0 < s1; c0 += SCAN_CHUNK) {
+            const int nc = (int)(s1 - c0 < SCAN_CHUNK ? s1 - c0 : SCAN_CHUNK);
+            __syncthreads();                          // the previous chunk has been walked by every wave
+            for (int i = threadIdx.x; i < nc * 8; i += blockDim.x) {
+                const int c = i >> 3, k = i & 7;
+                const int64_t cand = members[m0 + c0 + c];
+                double v;
+                if (k < 7) v = log_class(jafs + cand * 7, k, UNFOLDED ? 1 : 0);
+                else { v = (status && status[cand] != MISTI_OK) ? 1.0 : 0.0; lc[c] = (int32_t)cand; }
+                lj[c][k] = v;
+            }
+            __syncthreads();
+            for (int c = 0; c < nc; ++c) {
+                double a = cst;
+#pragma unroll
+                for (int i = 0; i < NF; ++i) a = fma(f[i], lj[c][i], a);
+                if (lj[c][7] != 0.0) a = -INFINITY;
+                const int32_t ci = lc[c];
+                if (a > bv || (a == bv && ci < bi)) { bv = a; bi = ci; }      // false for NaN; -inf equals only the empty pair, whose -1 no index is below
+            }
+        }
+        if (r < n_rep) {
+            const int64_t at = ((int64_t)blockIdx.z * n_group + g) * n_rep + r;
+            part_v[at] = bv;
+            part_i[at] = bi;
+        }
+    }
+}
+
+// A tile of 32 replicates x 32 groups per pass: the slices' pairs are read with the replicate innermost and folded under the same
+// total order, turned through LDS and written with the group innermost as prof_llk[n_rep][n_group] / prof_best (NULL: not wanted).
+// No slice at all (no candidate): -inf / -1.  Tiles beyond the grid are walked by the same workgroup.
+__global__ __launch_bounds__(256)
+void profile_merge_kernel(int slices, int32_t n_group, int64_t n_rep, const double* __restrict__ part_v, const int32_t* __restrict__ part_i,
+                          double* __restrict__ prof_llk, int32_t* __restrict__ prof_best) {
+    __shared__ double tv[32][33];
+    __shared__ int32_t ti[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                  // 32 x 8
+    const int64_t rep_tiles = (n_rep + 31) / 32;
+    const int64_t g0 = (int64_t)blockIdx.y * 32;
+    for (int64_t rt = blockIdx.x; rt < rep_tiles; rt += gridDim.x) {
+        const int64_t r0 = rt * 32;
+        __syncthreads();                              // the previous tile has been written out
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t g = g0 + ty + 8 * j, r = r0 + tx;
+            double bv = -INFINITY;
+            int32_t bi = -1;
+            if (g < n_group && r < n_rep)
+                for (int s = 0; s < slices; ++s) {
+                    const int64_t at = ((int64_t)s * n_group + g) * n_rep + r;
+                    const double v = part_v[at];
+                    const int32_t ci = part_i[at];
+                    if (v > bv || (v == bv && ci < bi)) { bv = v; bi = ci; }
+                }
+            tv[ty + 8 * j][tx] = bv;
+            ti[ty + 8 * j][tx] = bi;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t g = g0 + tx, r = r0 + ty + 8 * j;
+            if (g < n_group && r < n_rep) {
+                prof_llk[r * n_group + g] = tv[tx][ty + 8 * j];
+                if (prof_best) prof_best[r * n_group + g] = ti[tx][ty + 8 * j];
+            }
+        }
+    }
+}
+
+// Slices of a profile: as many as give the chip about a thousand workgroups together with the replicate blocks and the groups - one
+// when those alone do - and no slice shorter than a quarter chunk of the AVERAGE group (the groups' sizes are known on the device
+// only; a slice beyond a short list costs one merge step).  MISTI_SCAN_SLICES forces the number as it does for the scan.
+constexpr int64_t PROFILE_MOST_BLOCKS = (int64_t)1 << 22;                  // workgroups of one launch at most: 2^30 threads
+int64_t scan_profile_slices(int64_t n_cand, int64_t n_group, int64_t n_rep, const Tuning& tn) {
+    if (n_cand <= 0 || n_rep <= 0 || n_group <= 0) return 0;
+    const int64_t blocks = (n_rep + 255) / 256 * n_group;
+    int64_t slices = tn.scan_slices > 0 ? tn.scan_slices : (1024 + blocks - 1) / blocks;
+    const int64_t average = (n_cand + n_group - 1) / n_group;
+    const int64_t most = tn.scan_slices > 0 ? n_cand : (average + SCAN_CHUNK / 4 - 1) / (SCAN_CHUNK / 4);
+    if (slices > most) slices = most;
+    if (slices > 65535) slices = 65535;                                     // gridDim.z limit
+    if (slices > PROFILE_MOST_BLOCKS / n_group) slices = PROFILE_MOST_BLOCKS / n_group;      // (groups x slices) fit one launch
+    return slices;
+}
+
+// first [n_group + 1] | cursor [n_group] | members [n_cand]
+size_t scan_profile_index_size(int64_t n_cand, int64_t n_group) { return 2 * (size_t)n_group + 1 + (size_t)n_cand; }
+
+hipError_t launch_scan_profile(int64_t n_cand, const double* jafs, const int32_t* status, const int32_t* group, int32_t n_group,
+                               int64_t n_rep, const double* jsfs, const double* consts, double* prof_llk, int32_t* prof_best,
+                               int64_t slices, int32_t* index, double* part_v, int32_t* part_i, int unfolded, hipStream_t stream) {
+    if (n_rep <= 0) return hipSuccess;
+    if (slices > 0) {                                 // there are candidates, and `index` is a buffer: only here are addresses derived from it
+        int32_t* first = index;
+        int32_t* cursor = first + n_group + 1;
+        int32_t* members = cursor + n_group;
+        hipError_t e = hipMemsetAsync(cursor, 0, (size_t)n_group * sizeof(int32_t), stream);
+        if (e != hipSuccess) return e;
+        const dim3 cand_grid((unsigned)((n_cand + 255) / 256));
+        hipLaunchKernelGGL(profile_count_kernel, cand_grid, dim3(256), 0, stream, n_cand, group, n_group, cursor);
+        hipLaunchKernelGGL(profile_offsets_kernel, dim3(1), dim3(256), 0, stream, n_group, cursor, first);
+        hipLaunchKernelGGL(profile_scatter_kernel, cand_grid, dim3(256), 0, stream, n_cand, group, n_group, cursor, members);
+        const int64_t rep_blocks = (n_rep + 255) / 256, most = PROFILE_MOST_BLOCKS / ((int64_t)n_group * slices);
+        const dim3 grid((unsigned)(rep_blocks < most ? rep_blocks : (most > 1 ? most : 1)), (unsigned)n_group, (unsigned)slices);
+        if (unfolded) hipLaunchKernelGGL(scan_profile_kernel<true>, grid, dim3(256), 0, stream, n_group, first, members, jafs, status, n_rep, jsfs, consts, part_v, part_i);
+        else hipLaunchKernelGGL(scan_profile_kernel<false>, grid, dim3(256), 0, stream, n_group, first, members, jafs, status, n_rep, jsfs, consts, part_v, part_i);
+    }
+    const int64_t rep_tiles = (n_rep + 31) / 32, group_tiles = ((int64_t)n_group + 31) / 32, room = PROFILE_MOST_BLOCKS / group_tiles;
+    hipLaunchKernelGGL(profile_merge_kernel, dim3((unsigned)(rep_tiles < room ? rep_tiles : room), (unsigned)group_tiles), dim3(256), 0, stream,
+                       (int)slices, n_group, n_rep, part_v, part_i, prof_llk, prof_best);
+    return hipGetLastError();
+}
+
 // ----------------------------------------------------------- launchers -------
 hipError_t upload_tables(const DevTables& t) {
     static double inv[INV_TABLE];

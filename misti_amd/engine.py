@@ -253,6 +253,15 @@ class Engine:
         _lib.check(self._lib.misti_scan_best_dev(self._ctx, int(n_cand), v(d_jafs), v(d_status), int(n_rep), v(d_jsfs), int(k), v(d_best),
                                                  v(d_best_llk)))
 
+    def scan_profile_dev(self, n_cand, d_jafs, d_status, d_group, n_group, n_rep, d_jsfs, d_prof_llk, d_prof_best=0):
+        """``misti_scan_profile_dev``: per replicate and group the best candidate of the group (``d_prof_llk[n_rep][n_group]``,
+        ``d_prof_best[n_rep][n_group]`` int32) among the candidates labelled ``d_group[c] == g`` (int32; a label outside
+        ``0 ... n_group - 1`` is in no group), value descending and index ascending on ties, -inf / -1 for a group without a value - from
+        spectra alone, without the ``[n_cand][n_rep]`` table (raw device addresses; asynchronous)."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _lib.check(self._lib.misti_scan_profile_dev(self._ctx, int(n_cand), v(d_jafs), v(d_status), v(d_group), int(n_group), int(n_rep), v(d_jsfs),
+                                                    v(d_prof_llk), v(d_prof_best)))
+
     def sync(self):
         _lib.check(self._lib.misti_sync(self._ctx))
 

@@ -384,6 +384,119 @@ def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_tim
     return out
 
 
+def profile_per_group(llk, group, n_group):
+    """The rule of ``misti_scan_profile_dev`` stated on the host, for a table ``llk[n_cand][n_rep]`` and one label per candidate:
+    candidate ``c`` takes part in group ``group[c]`` only if ``0 <= group[c] < n_group`` (any other label: in no group); per
+    replicate and group the largest value ``v > -inf`` among the group's candidates - NaN never qualifies - and the LOWEST candidate
+    index that attains it; a group without such a candidate holds -inf / -1.  Returns ``(prof_llk[n_rep][n_group]``,
+    ``prof_best[n_rep][n_group]`` int64).  One group is ``best_k_per_replicate(llk, 1)``."""
+    llk = np.asarray(llk, dtype=np.float64)
+    llk = llk.reshape(llk.shape[0], -1)
+    n, R = llk.shape
+    group = np.asarray(group, dtype=np.int64).reshape(-1)
+    G = int(n_group)
+    if group.size != n:
+        raise ValueError("one label per candidate: %d labels for %d candidates" % (group.size, n))
+    if G < 1:
+        raise ValueError("n_group must be at least 1")
+    prof_llk = np.full((R, G), -np.inf)
+    prof_best = np.full((R, G), -1, dtype=np.int64)
+    for c in range(n):                                       # ascending index and a strict comparison: the lowest index keeps a tie
+        g = group[c]
+        if not 0 <= g < G:
+            continue
+        with np.errstate(invalid="ignore"):
+            wins = llk[c] > prof_llk[:, g]                   # false for NaN and for -inf
+        prof_llk[wins, g] = llk[c, wins]
+        prof_best[wins, g] = c
+    return prof_llk, prof_best
+
+
+def axis_groups(shape, axes):
+    """Group labels for the candidates of a C-ordered product grid of ``shape`` (what ``numpy.meshgrid(..., indexing="ij")`` and a
+    ``ravel`` make): ``axes`` is one axis, or a tuple of two or more, and a candidate's label is its index along that axis - for
+    several axes the row-major index over them in the order given, so a two-dimensional profile SURFACE is the same call with
+    ``n_group = shape[i] * shape[j]``.  Returns ``(group[prod(shape)]`` int32, ``n_group)``."""
+    shape = tuple(int(s) for s in shape)
+    axes = (int(axes),) if np.isscalar(axes) else tuple(int(a) for a in axes)
+    if not axes or len(set(axes)) != len(axes) or any(not 0 <= a < len(shape) for a in axes):
+        raise ValueError("axes must be distinct axes of a %d-axis grid (got %r)" % (len(shape), axes))
+    index = np.indices(shape)
+    label = np.zeros(shape, dtype=np.int64)
+    n_group = 1
+    for a in axes:
+        label = label * shape[a] + index[a]
+        n_group *= shape[a]
+    return label.ravel().astype(np.int32), n_group
+
+
+def scan_profile(engine, split, params, jsfs_rows, group, n_group, band_bounds=None, pulse_times=None):
+    """Scan and keep, per replicate and GROUP of candidates, the group's best candidate WITHOUT the likelihood table: one evaluation
+    without replicates into device spectra and statuses, exactly as ``scan_best`` does it, then ``misti_scan_profile_dev`` - device
+    memory is ``O(n_cand + n_rep * n_group)``, and only the profile and the statuses come back.  ``group`` is one int label per
+    candidate (``axis_groups`` makes them for a product grid; a label outside ``0 ... n_group - 1`` is in no group); the other
+    arguments as for ``scan_best``.  Returns ``(prof_llk[R][n_group]``, ``prof_best[R][n_group]`` int64, ``status[n])`` under
+    ``profile_per_group``'s rule."""
+    import torch
+    dev = torch.device("cuda", engine.device)
+    split_h = np.asarray(split, dtype=float).reshape(-1)
+    n = split_h.size
+    G = int(n_group)
+    label = np.ascontiguousarray(np.asarray(group).reshape(-1), dtype=np.int32)
+    if label.size != n:
+        raise ValueError("one label per candidate: %d labels for %d candidates" % (label.size, n))
+    rows = torch.as_tensor(np.asarray(jsfs_rows, dtype=float).reshape(-1, 8), device=dev).contiguous()
+    R = rows.shape[0]
+    d_split = torch.as_tensor(split_h, device=dev)
+    d_group = torch.as_tensor(label, device=dev)
+    par = bb = pt = None
+    if engine.n_param:
+        par = torch.as_tensor(np.asarray(params, dtype=float).reshape(n, engine.n_param), device=dev).contiguous()
+    if band_bounds is not None and engine.n_band:
+        bb = torch.as_tensor(_per_candidate(band_bounds, n, (engine.n_band, 2)), device=dev)
+    if pulse_times is not None and engine.n_pulse:
+        pt = torch.as_tensor(_per_candidate(pulse_times, n, (engine.n_pulse,)), device=dev)
+    jafs = torch.empty((n, 7), dtype=torch.float64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    prof_llk = torch.empty((R, G), dtype=torch.float64, device=dev)
+    prof_best = torch.empty((R, G), dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    torch.cuda.current_stream(dev).synchronize()      # the engine's stream is non-blocking: inputs must have landed
+    engine.evaluate_dev(n, ptr(d_split), ptr(par), 0, 0, 0, d_jafs=ptr(jafs), d_status=ptr(status), d_bounds=ptr(bb), d_pulse_times=ptr(pt))
+    engine.scan_profile_dev(n, ptr(jafs), ptr(status), ptr(d_group), G, R, ptr(rows), ptr(prof_llk), ptr(prof_best))
+    engine.sync()
+    return prof_llk.cpu().numpy(), prof_best.cpu().numpy().astype(np.int64), status.cpu().numpy()
+
+
+def profile_interval(prof_llk, values, drop):
+    """Per row of a one-axis profile ``prof_llk[R][G]`` (group ``g`` stands for ``values[g]``): the value of the first maximal group
+    and that maximum, and the smallest and the largest ``values[g]`` among the groups with ``prof_llk[r][g] >= max - drop``.  A row
+    without any value (nothing above -inf; NaN never counts) gives NaN in all four.
+    What this is: a likelihood-ratio SUPPORT interval - the values whose profile log-likelihood lies within ``drop`` of the best one.
+    The likelihood here is a composite one (sites are treated as independent), so ``drop = chi2.ppf(0.95, 1) / 2`` does NOT make it a
+    calibrated 95 % confidence interval; the bootstrap t-interval (``bootstrap_split_interval``) remains the confidence statement.
+    The interval is the hull of the supported values: a profile with two separated supported stretches is covered by one interval.
+    Returns dict(best[R], llh[R], lo[R], hi[R])."""
+    p = np.asarray(prof_llk, dtype=np.float64)
+    p = p.reshape(-1, p.shape[-1])
+    values = np.asarray(values, dtype=np.float64).reshape(-1)
+    if values.size != p.shape[1]:
+        raise ValueError("one value per group: %d values for %d groups" % (values.size, p.shape[1]))
+    if not drop >= 0:
+        raise ValueError("drop must be >= 0")
+    with np.errstate(invalid="ignore"):
+        p = np.where(p > -np.inf, p, -np.inf)                # NaN never counts
+    R = p.shape[0]
+    top = p.max(axis=1) if p.shape[1] else np.full(R, -np.inf)
+    has = top > -np.inf
+    first = np.argmax(p, axis=1) if p.shape[1] else np.zeros(R, dtype=np.int64)      # the first maximum
+    out = dict(best=np.full(R, np.nan), llh=np.full(R, np.nan), lo=np.full(R, np.nan), hi=np.full(R, np.nan))
+    for r in np.where(has)[0]:
+        inside = values[p[r] >= top[r] - drop]
+        out["best"][r], out["llh"][r], out["lo"][r], out["hi"][r] = values[first[r]], top[r], inside.min(), inside.max()
+    return out
+
+
 def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter=1000):
     """The bootstrap profiles of the reference's ``test.bs`` scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
     -mi ...``: one ``MigrationInference.Solve`` per (replicate, split) pair, MigrationInference.py:718-733 of the reference) in ONE
