@@ -367,7 +367,8 @@ int misti_nm_solve_pulses(misti_ctx* ctx, int64_t n_start, const double* starts,
  * MISTI_E_LIMIT for a model with n_param + 1 > MISTI_MAX_PARAMS, MISTI_E_ARG for a NULL pointer, n_rep < 1, a row out of range, a
  * non-finite start coordinate or maxiter < 1 - all before anything touches the device.  Synchronisation and statistics
  * (misti_nm_last_stats, misti_nm_last_spec_iterations) as misti_nm_solve_rows.
- * Out of scope: basin hopping, the lanes, the device-list (misti_multi_*) forms and the forward map keep a fixed split per start. */
+ * Basin hopping over the same coordinates: misti_basinhopping_split.  Out of scope: the lanes, the device-list (misti_multi_*) forms
+ * and the forward map keep a fixed split per start. */
 int misti_nm_solve_split(misti_ctx* ctx, int64_t n_start, const double* starts, const int32_t* rows,
                          const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
                          double xatol, double fatol, int32_t maxiter,
@@ -392,6 +393,57 @@ int misti_basinhopping(misti_ctx* ctx, int64_t n_start, const double* starts, do
                        int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                        double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                        double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
+
+/* misti_basinhopping with a split time and a replicate row PER START, and band bounds and pulse times per start as well: start s is
+ * SciPy's basinhopping around Nelder-Mead at split_times[s] against row rows[s], with the model's bands at band_bounds[s] and its
+ * pulses at pulse_times[s].  Replaces the reference's global search run as its bootstrap workflow runs everything - test.bs: one
+ * process, one MigrationInference and one Solve(globalOpt=True) per (row, split) pair - with ONE call: the hops of all starts go in
+ * step, every minimisation of a hop is one batched search (misti_nm_solve_pulses' machinery and its one host path).  Start s returns,
+ * bit for bit, what misti_basinhopping(starts[s], split_times[s], jsfs + 8 rows[s], the same uniforms) returns on a context whose
+ * model carries band_bounds[s] and pulse_times[s]: x, llh, nfev, failures and accepted.
+ *   starts       [n_start][n_param]   (n_param >= 1)
+ *   split_times  [n_start]            finite, fractional allowed
+ *   rows         [n_start]            0 <= rows[s] < n_rep
+ *   band_bounds  [n_start][n_band][2] or NULL   NULL: the model's own, exactly as in misti_nm_solve_pulses
+ *   pulse_times  [n_start][n_pulse] or NULL     NULL: the model's own
+ *   n_rep, jsfs                       the replicate table [n_rep][8]
+ *   niter .. nm_maxfev, x .. accepted as misti_basinhopping
+ *   uniforms     [n_start][niter][n_param + 1]
+ * A point, or a whole hop, that the engine refuses - a negative rate, a split off the grid, bounds or times broken at that split -
+ * has no value and scores +inf; it is never an argument error and the other starts are unaffected (a start none of whose points has
+ * a value returns llh = -inf and counts every minimisation as failed, as SciPy does on an objective that returns inf: the Metropolis
+ * test treats inf - inf as Python's min(0, nan) does).
+ * MISTI_E_ARG, before anything touches the device, for a NULL pointer, n_rep < 1, a row out of range, a non-finite split time,
+ * niter < 0, or nm_maxiter, nm_maxfev or interval below 1; MISTI_E_LIMIT for too many starts.  n_start == 0 returns 0.  Host
+ * buffers; synchronous; misti_nm_last_stats / misti_nm_last_spec_iterations report on the call (all its minimisations together). */
+int misti_basinhopping_rows(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                            const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                            int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
+                            double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
+                            double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
+
+/* Basin hopping with the split time as a COORDINATE: every simplex has n_param + 1 coordinates, the split last, as in
+ * misti_nm_solve_split, and the random displacement moves the split like any other coordinate (SciPy's RandomDisplacement: one
+ * stepsize for all, the split in grid-index units).  Replaces the handful of initial splits a local fit of the split needs on its
+ * piecewise objective (`--fit-st --grid-st 15 25 5`, the best kept) - and, per bootstrap row, the `for st in A..Z` scans of the
+ * test.bs scripts around Solve(globalOpt=True) - with ONE global search per (row, start); n_param == 0 is allowed here: the global
+ * search of the `*no.mig.sh` models.
+ * What it is not: the reference has no such search, so there is no reference run to agree with.  The parity target is
+ * scipy.optimize.basinhopping(T, stepsize, interval, minimizer_kwargs = Nelder-Mead) on this engine's own objective over (parameters,
+ * split), no value scoring +inf; SciPy's defaults for the minimiser are maxiter = maxfev = 200 x (n_param + 1).
+ *   starts       [n_start][n_param + 1]  initial parameters, then the initial split time (all finite)
+ *   rows, band_bounds, pulse_times, n_rep, jsfs   as misti_nm_solve_split
+ *   uniforms     [n_start][niter][n_param + 2]   per hop n_param + 1 for the displacement, then one for the Metropolis test
+ *   x            [n_start][n_param + 1]  lowest successful minimum, the fitted split last
+ *   other arguments, refused points, synchronisation and statistics as misti_basinhopping_rows.
+ * MISTI_E_LIMIT for n_param + 1 > MISTI_MAX_PARAMS or too many starts; MISTI_E_ARG as misti_basinhopping_rows, a non-finite start
+ * coordinate in the place of the split time - all before anything touches the device.
+ * Out of scope: hops out of step (a start taking its next hop while others still minimise), the lanes and the device-list forms. */
+int misti_basinhopping_split(misti_ctx* ctx, int64_t n_start, const double* starts, const int32_t* rows,
+                             const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                             int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
+                             double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
+                             double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
 
 /* Work counters of the last misti_nm_solve on this context: [0] iterations issued, [1] batch slots over all iterations
  * (live starts plus the slack of the two-iterations-old count that sizes the batches; x (2 + n_param) = candidates

@@ -27,6 +27,17 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               line of the best search with the fitted, fractional splitT, then (--all-bs) the t-interval of
                               bs_conf_int.ipynb over the fitted splits.  Needs no optimised -mi / -pu: a model without one is a
                               one-coordinate search.  Not offered with --sweep, --sweep-pu, --gpus N > 1 or --devices
+    --hops N                  with --fit-st or --grid-solve (N >= 1): every search becomes the reference's GLOBAL search, Solve(globalOpt=True) -
+                              scipy.optimize.basinhopping with N hops, T = 0.5 and SciPy's defaults for the Nelder-Mead minimiser
+                              (xatol = fatol = 1e-4, 200 iterations and evaluations per coordinate) - all searches in ONE batched call
+                              (misti_basinhopping_split / misti_basinhopping_rows); with --fit-st the hops move the split as well.
+                              The lines are those of the mode without hops, each followed by its accepted hops and failed
+                              minimisations, and one line states hops, step and seed.  -tol does not apply (the reference's global
+                              search ignores it too: MigrationInference.py:723-725).  Not offered with --sweep, --sweep-pu,
+                              --gpus N > 1 or --devices
+    --hop-step S              with --hops (refused without): the initial step size of the random displacement (default 0.5; the split
+                              in grid-index units)
+    --hop-seed K              with --hops (refused without): search j of a row draws from numpy.random.default_rng([K, j]) (default 0)
     --top K                   with --grid-st and/or --grid-mi (K = 1 ... 8): grid mode evaluates WITHOUT replicates and reduces on the device
                               (misti_scan_best_dev) - the [candidates x rows] likelihood table is never made; per row its K best
                               candidates are printed (one line each, grid mode's format: K lines per row in place of one per
@@ -117,6 +128,10 @@ def build_parser():
                    help="with --grid-st / --all-bs: optimise every (replicate, split) pair as the test.bs loops do, in one batched search")
     p.add_argument("--fit-st", action="store_true",
                    help="with --grid-st (the initial splits) / --all-bs: fit the split time per row as a coordinate of one batched search")
+    p.add_argument("--hops", type=int, default=None, metavar="N",
+                   help="with --fit-st / --grid-solve: basin hopping with N hops (T = 0.5, SciPy's minimiser defaults; -tol does not apply) in place of the local search")
+    p.add_argument("--hop-step", type=float, default=None, metavar="S", help="with --hops: initial step size of the random displacement (default 0.5)")
+    p.add_argument("--hop-seed", type=int, default=None, metavar="K", help="with --hops: seed of the searches' generators (default 0)")
     p.add_argument("--top", type=int, default=None, metavar="K",
                    help="grid mode (--grid-st / --grid-mi): keep the K best candidates per row (1 ... 8), reduced on the device without the table")
     p.add_argument("--polish", action="store_true",
@@ -158,6 +173,37 @@ def fit_st_error(a):
     if not a.grid_st:
         return "--fit-st needs --grid-st A B [STEP]: the initial split times of its searches"
     return None
+
+
+def hops_error(a):
+    """Why ``--hops`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.hops is None:
+        if a.hop_step is not None or a.hop_seed is not None:
+            return "--hop-step / --hop-seed set the hops of --hops N: give --hops N"
+        return None
+    if a.hops < 1:
+        return "--hops N: the number of hops must be at least 1 (got %d)" % a.hops
+    if a.sweep or a.sweep_pu:
+        return "--hops searches ONE model globally: --sweep / --sweep-pu are not offered with it"
+    if not (a.fit_st or a.grid_solve):
+        return "--hops makes the searches of --fit-st or --grid-solve global: give one of them"
+    if a.gpus > 1 or a.devices:
+        return "--hops runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    if a.hop_step is not None and not a.hop_step > 0:
+        return "--hop-step must be positive (got %g)" % a.hop_step
+    if a.hop_seed is not None and a.hop_seed < 0:
+        return "--hop-seed must not be negative (got %d)" % a.hop_seed
+    return None
+
+
+def _hop_step_seed(a):
+    """--hop-step and --hop-seed, or their defaults: SciPy's step size 0.5, seed 0."""
+    return (0.5 if a.hop_step is None else a.hop_step), (0 if a.hop_seed is None else a.hop_seed)
+
+
+def _hops_text(res, *at):
+    """What follows a result line under --hops: the accepted hops and the failed minimisations of the search it reports."""
+    return " \thops accepted = %d \tfailed minimisations = %d" % (int(res["accepted"][at]), int(res["failures"][at]))
 
 
 def top_error(a):
@@ -460,19 +506,24 @@ def grid_profile(a, inp, rows):
 def grid_solve(a, inp, rows):
     """The bootstrap profiles of the reference's test.bs scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
     -mi ...``, one Solve per pair) as ONE batched search: every (row, split, start) triple is a start of misti_nm_solve_rows."""
-    from .optimize import bootstrap_profile, bootstrap_profile_interval
+    from .optimize import bootstrap_profile, bootstrap_profile_global, bootstrap_profile_interval
     splits, bands, pulses, k, axes = grid_model(a)
     starts = np.stack([m.ravel() for m in np.meshgrid(*axes, indexing="ij")], axis=1)
     data = np.array(rows if a.all_bs else [rows[a.bsMode] if a.bsMode >= 0 else np.sum(rows, axis=0)], dtype=float)
     ids = list(range(data.shape[0])) if a.all_bs else [a.bsMode]
     flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    hop_step, hop_seed = _hop_step_seed(a)
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
-        prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000)
+        if a.hops:
+            prof = bootstrap_profile_global(e, splits, data, starts, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step)
+        else:
+            prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000)
     dt = time.time() - t0
     for r in range(data.shape[0]):
         for p, st in enumerate(splits):
-            print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, prof["x"][r, p], prof["llh"][r, p]))
+            print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, prof["x"][r, p], prof["llh"][r, p])
+                  + (_hops_text(prof, r, p) if a.hops else ""))
     iv = bootstrap_profile_interval(prof["llh"], splits, prof["x"])
     print()
     if iv["data_split"] is None:
@@ -486,6 +537,11 @@ def grid_solve(a, inp, rows):
         print("grid-solve: bootstrap best splitT mean =", iv["mean"], "97.5%% t-interval = [%r, %r]" % tuple(float(v) for v in iv["interval"]),
               "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
     n = prof["llh"].size
+    if a.hops:
+        print("grid-solve: basin hopping with %d hops, step %g, seed %d" % (a.hops, hop_step, hop_seed))
+        print("grid-solve: %d pairs x %d starts in one global search, %.3f s; %d pairs with a failed minimisation, %d without a value"
+              % (n, starts.shape[0], dt, int((prof["failures"] > 0).sum()), int((~np.isfinite(prof["llh"])).sum())))
+        return 0
     print("grid-solve: %d pairs x %d starts in one search, %.3f s; %d pairs ended on the iteration cap, %d without a value"
           % (n, starts.shape[0], dt, int((prof["status"] == 2).sum()), int((~np.isfinite(prof["llh"])).sum())))
     return 0
@@ -494,21 +550,26 @@ def grid_solve(a, inp, rows):
 def fit_st(a, inp, rows):
     """--fit-st: the split time as a coordinate - per JSFS row one search over (optimised parameters, split) from every (start,
     initial split) pair, all in ONE misti_nm_solve_split call; the best search per row is printed."""
-    from .optimize import split_fit, split_fit_interval
+    from .optimize import split_fit, split_fit_global, split_fit_interval
     splits, bands, pulses, k, axes = grid_model(a)
     starts = np.stack([m.ravel() for m in np.meshgrid(*axes, indexing="ij")], axis=1) if k else np.empty((1, 0))
     data, ids = _data_rows(a, rows)
     flags = dict(cpfit=a.cpfit, true_eps=a.trueEPS, smooth=not a.nosmooth, unfolded=a.uf)
+    hop_step, hop_seed = _hop_step_seed(a)
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
-        fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000)
+        if a.hops:
+            fit = split_fit_global(e, data, starts, splits, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step)
+        else:
+            fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000)
     dt = time.time() - t0
     for r in range(data.shape[0]):
         st = float(fit["split"][r])
         if not np.isfinite(fit["llh"][r]):
             print("fit-st: bs_id =", ids[r], "has no finite llh from any start")
             continue
-        print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, fit["x"][r, :k], fit["llh"][r]))
+        print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, fit["x"][r, :k], fit["llh"][r])
+              + (_hops_text(fit, r) if a.hops else ""))
     print()
     if a.all_bs:
         iv = split_fit_interval(fit["split"], fit["llh"])
@@ -517,6 +578,11 @@ def fit_st(a, inp, rows):
         else:
             print("fit-st: bootstrap fitted splitT mean =", iv["mean"], "95%% t-interval = [%r, %r]" % iv["interval"],
                   "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
+    if a.hops:
+        print("fit-st: basin hopping with %d hops, step %g, seed %d" % (a.hops, hop_step, hop_seed))
+        print("fit-st: %d rows x %d (start, initial split) pairs in one global search, %.3f s; %d rows with a failed minimisation, %d without a value"
+              % (data.shape[0], starts.shape[0] * len(splits), dt, int((fit["failures"] > 0).sum()), int((~np.isfinite(fit["llh"])).sum())))
+        return 0
     print("fit-st: %d rows x %d (start, initial split) pairs in one search, %.3f s; %d rows ended on the iteration cap, %d without a value"
           % (data.shape[0], starts.shape[0] * len(splits), dt, int((fit["status"] == 2).sum()), int((~np.isfinite(fit["llh"])).sum())))
     return 0
@@ -645,7 +711,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = profile_error(a) or top_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
+    why = profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2

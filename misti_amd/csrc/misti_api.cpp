@@ -1236,6 +1236,18 @@ int nm_copy_back(misti_ctx* c, const NmWork& w, double* x, double* llh, int32_t*
     return 0;
 }
 
+// The hops of a basin-hopping call around a search (misti_basinhopping*): SciPy's basinhopping arguments, the caller's uniforms and
+// the runner's own counters.  The minimiser's iteration budget is the search's maxiter.
+struct NmHops {
+    int32_t niter;
+    double T, stepsize;
+    int32_t interval;
+    double target_accept_rate, stepwise_factor;
+    int64_t nm_maxfev;
+    const double* uniforms;          // [n_start][niter][N + 1]
+    int32_t *nfev, *failures, *accepted;
+};
+
 // One batched search, as its entry point describes it.
 struct NmSearch {
     int64_t n_start;
@@ -1253,21 +1265,27 @@ struct NmSearch {
     int32_t maxiter;
     double *x, *llh;
     int32_t *nit, *nfev, *status;
+    const NmHops* hops = nullptr;    // basin hopping around the search; NULL: the search alone
 };
 
-// All five searches.  Every argument is checked before the first HIP call, in one order: what does not depend on the context, the
-// context, what needs the model.  Bounds or times that break SetModel's checks, and a fitted split the engine refuses, are no argument
-// errors: the engine gives such a point status MISTI_BAD_STRUCTURE and no value, the optimiser +inf - as SciPy sees -JAFSLikelihood.
-// A path that is not taken allocates and writes nothing: without bounds nothing of the bounds path, and so on.
-int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
+// The arguments of every search, and of basin hopping around one, checked before the first HIP call, in one order: what does not
+// depend on the context, the context, what needs the model.  Bounds or times that break SetModel's checks, and a fitted split the
+// engine refuses, are no argument errors: the engine gives such a point status MISTI_BAD_STRUCTURE and no value, the optimiser
+// +inf - as SciPy sees -JAFSLikelihood.  Leaves the number of coordinates in N and, in `whole`, whether every split time of the
+// rows path is an integer.
+int nm_check(const misti_ctx* c, const NmSearch& q, int& N, bool& whole) {
     const bool rows_path = q.split != NmSearch::ONE_SPLIT, fit_split = q.split == NmSearch::SPLIT_FITTED;
     const bool per_start = q.split == NmSearch::SPLIT_PER_START;
+    const NmHops* h = q.hops;
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
     if (!q.starts || !q.jsfs || !q.x || !q.llh || (rows_path && !q.rows) || (per_start && !q.split_times))
         return fail(MISTI_E_ARG, "starts / %s / x / llh is NULL", !rows_path ? "jsfs_row" : (per_start ? "split_times / rows / jsfs" : "rows / jsfs"));
     if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
-    if (q.maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
-    bool whole = per_start;                      // a fitted split is whole by accident only: never the integer-splits hint
+    if (!h && q.maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    if (h && h->niter < 0) return fail(MISTI_E_ARG, "negative number of hops");
+    if (h && h->niter > 0 && !h->uniforms) return fail(MISTI_E_ARG, "uniforms is NULL");
+    if (h && (q.maxiter < 1 || h->nm_maxfev < 1 || h->interval < 1)) return fail(MISTI_E_ARG, "nm_maxiter, nm_maxfev and interval must be >= 1");
+    whole = per_start;                           // a fitted split is whole by accident only: never the integer-splits hint
     for (int64_t s = 0; rows_path && s < q.n_start; ++s) {
         if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
             return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
@@ -1276,16 +1294,28 @@ int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
         if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
     }
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
-    const int N = c->dm.n_param + (fit_split ? 1 : 0);
+    N = c->dm.n_param + (fit_split ? 1 : 0);
     if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
     // the sort's local arrays hold MISTI_MAX_PARAMS + 1 vertices (misti_nm.hip: sort_simplex)
     if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
+    // (the limits before the scan of the starts: a call that is refused for its size does not read n_start x N doubles first)
+    if (q.n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
+    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
     for (int64_t s = 0; fit_split && s < q.n_start; ++s)
         for (int k = 0; k < N; ++k)
             if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
-    if (q.n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
-    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
-    if (q.n_start == 0) return 0;
+    return 0;
+}
+
+// The device state of a checked search with n_start >= 1: the minimiser's state, behind it what each start hands its points on the rows
+// path (split, row, bounds, pulse times; one of each per slot of every batch; the compact parameter array of a fitted split; the
+// table), behind that whatever `extra` takes - still the same two allocations.  Uploads the caller's arrays, issues llh_const over
+// the table and clears the context's work counters.  A path that is not taken allocates and writes nothing: without bounds nothing
+// of the bounds path, and so on.
+template <class Extra>
+int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extra&& extra) {
+    const bool rows_path = q.split != NmSearch::ONE_SPLIT, fit_split = q.split == NmSearch::SPLIT_FITTED;
+    const bool per_start = q.split == NmSearch::SPLIT_PER_START;
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = (size_t)q.n_start, V = (size_t)N + 1, R = (size_t)q.n_rep;
     const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
@@ -1295,21 +1325,22 @@ int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
     const size_t NB2 = rows_path && q.band_bounds ? 2 * (size_t)c->dm.n_band : 0;
     const size_t NP = rows_path && q.pulse_times ? (size_t)c->dm.n_pulse : 0;
     const size_t NQ = fit_split ? (size_t)N - 1 : 0;
-    NmWork w;
     misti::NmState& st = w.st;
     double *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
     int32_t *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
     // rows path: what each start hands its points, then one of it per slot of every batch
     auto rows_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
-        if (!rows_path) return;
-        if (per_start) d_split = f.take(S);
-        d_table = f.take(R * 8); d_consts = f.take(R); w.rjafs = f.take(M * 7);
-        if (NQ) nm_per_slot(w, &NmBatch::par, f, NQ);
-        d_rowof = i.take(S);
-        nm_per_slot(w, &NmBatch::row, i, 1);
-        w.rstatus = i.take(M);
-        if (NB2) { d_bounds = i.take(S * NB2); nm_per_slot(w, &NmBatch::bnd, i, NB2); }
-        if (NP) { d_pulses = i.take(S * NP); nm_per_slot(w, &NmBatch::put, i, NP); }
+        if (rows_path) {
+            if (per_start) d_split = f.take(S);
+            d_table = f.take(R * 8); d_consts = f.take(R); w.rjafs = f.take(M * 7);
+            if (NQ) nm_per_slot(w, &NmBatch::par, f, NQ);
+            d_rowof = i.take(S);
+            nm_per_slot(w, &NmBatch::row, i, 1);
+            w.rstatus = i.take(M);
+            if (NB2) { d_bounds = i.take(S * NB2); nm_per_slot(w, &NmBatch::bnd, i, NB2); }
+            if (NP) { d_pulses = i.take(S * NP); nm_per_slot(w, &NmBatch::put, i, NP); }
+        }
+        extra(f, i);
     };
     if (int r = nm_prepare(c, q.n_start, N, w, rows_layout)) return r;
     st.fit_split = fit_split ? 1 : 0;
@@ -1329,10 +1360,79 @@ int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
         HIP_TRY(misti::launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));      // once per call, every row
     }
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    if (int r = nm_run(c, w, rows_path ? 0.0 : q.split_time, q.xatol, q.fatol, q.maxiter, INT64_MAX)) return r;
+    return 0;
+}
+
+// All five searches.
+int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
+    int N = 0;
+    bool whole = false;
+    if (int r = nm_check(c, q, N, whole)) return r;
+    if (q.n_start == 0) return 0;
+    NmWork w;
+    if (int r = nm_setup(c, q, N, whole, w, [](Carver<double>&, Carver<int32_t>&) {})) return r;
+    if (int r = nm_run(c, w, q.split == NmSearch::ONE_SPLIT ? q.split_time : 0.0, q.xatol, q.fatol, q.maxiter, INT64_MAX)) return r;
     if (int r = nm_copy_back(c, w, q.x, q.llh, q.nit, q.nfev, q.status)) return r;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Basin hopping around a checked search with n_start >= 1 (all three misti_basinhopping*): SciPy's runner per start, all starts in
+// step - the initial minimisation, then per hop the displacement (bh_step), the minimisation of every trial point and the Metropolis
+// test (bh_update).  The hop state lies behind the search's own in the same two allocations; with the split as a coordinate it is
+// displaced like any other (bh.N counts it).
+int bh_run(misti_ctx* c, const NmSearch& q, int N, bool whole) {
+    const NmHops& h = *q.hops;
+    const int niter = h.niter;
+    const size_t S = (size_t)q.n_start, U = S * (size_t)niter * (size_t)(N + 1);
+    NmWork w;
+    misti::BhState bh{};
+    bh.S = q.n_start; bh.N = N;
+    bh.beta = h.T != 0.0 ? 1.0 / h.T : INFINITY;
+    bh.target = h.target_accept_rate; bh.factor = h.stepwise_factor; bh.interval = h.interval;
+    double *d_trial = nullptr, *d_uni = nullptr;
+    auto bh_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        bh.x_cur = f.take(S * N); bh.x_best = f.take(S * N); d_trial = f.take(S * N);
+        bh.f_cur = f.take(S); bh.f_best = f.take(S); bh.stepsize = f.take(S);
+        d_uni = f.take(U);
+        bh.ok_cur = i.take(S); bh.ok_best = i.take(S); bh.nstep = i.take(S); bh.naccept = i.take(S);
+        bh.nfev = i.take(S); bh.failures = i.take(S); bh.accepted = i.take(S);
+    };
+    if (int r = nm_setup(c, q, N, whole, w, bh_layout)) return r;
+    hipStream_t sm = c->stream;
+    if (U) HIP_TRY(hipMemcpyAsync(d_uni, h.uniforms, U * sizeof(double), hipMemcpyHostToDevice, sm));
+    {
+        std::vector<double> st0(S, h.stepsize);
+        HIP_TRY(hipMemcpyAsync(bh.stepsize, st0.data(), S * sizeof(double), hipMemcpyHostToDevice, sm));
+        HIP_TRY(hipStreamSynchronize(sm));                  // st0 is a local
+    }
+    const double split_time = q.split == NmSearch::ONE_SPLIT ? q.split_time : 0.0;
+    // BasinHoppingRunner.__init__: the initial minimisation from the start itself
+    if (int r = nm_run(c, w, split_time, q.xatol, q.fatol, q.maxiter, h.nm_maxfev)) return r;
+    HIP_TRY(misti::launch_bh_update(bh, w.st, w.d_starts, w.d_llh, w.st.shrunk, -1, niter, d_uni, sm));
+    for (int hop = 0; hop < niter; ++hop) {                 // one_cycle, all starts in step
+        HIP_TRY(misti::launch_bh_step(bh, hop, niter, d_uni, d_trial, sm));
+        HIP_TRY(hipMemcpyAsync(w.d_starts, d_trial, S * N * sizeof(double), hipMemcpyDeviceToDevice, sm));
+        if (int r = nm_run(c, w, split_time, q.xatol, q.fatol, q.maxiter, h.nm_maxfev)) return r;
+        HIP_TRY(misti::launch_bh_update(bh, w.st, w.d_starts, w.d_llh, w.st.shrunk, hop, niter, d_uni, sm));
+    }
+    HIP_TRY(misti::launch_bh_result(bh, w.d_starts, w.d_llh, sm));
+    if (int r = nm_copy_back(c, w, q.x, q.llh, nullptr, nullptr, nullptr)) return r;
+    if (h.nfev) HIP_TRY(hipMemcpyAsync(h.nfev, bh.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (h.failures) HIP_TRY(hipMemcpyAsync(h.failures, bh.failures, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (h.accepted) HIP_TRY(hipMemcpyAsync(h.accepted, bh.accepted, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
     HIP_TRY(hipStreamSynchronize(sm));
     return 0;
+}
+
+// misti_basinhopping_rows / misti_basinhopping_split: the search's arguments and the hops' in nm_check's order, then the hops.
+int bh_impl(misti_ctx* c, NmSearch q, const NmHops& h) {
+    q.hops = &h;
+    int N = 0;
+    bool whole = false;
+    if (int r = nm_check(c, q, N, whole)) return r;
+    if (q.n_start == 0) return 0;
+    return bh_run(c, q, N, whole);
 }
 
 }  // namespace
@@ -1378,6 +1478,7 @@ int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, doub
                        int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                        double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                        double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
+    // (this entry point's own order of checks, older than nm_check's: the context first, no starts before the pointers)
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_start < 0 || niter < 0) return fail(MISTI_E_ARG, "negative number of starts / hops");
     if (n_start == 0) return 0;
@@ -1386,48 +1487,29 @@ int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, doub
     if (!starts || !jsfs_row || !x || !llh || (niter > 0 && !uniforms)) return fail(MISTI_E_ARG, "starts / jsfs_row / uniforms / x / llh is NULL");
     if (nm_maxiter < 1 || nm_maxfev < 1 || interval < 1) return fail(MISTI_E_ARG, "nm_maxiter, nm_maxfev and interval must be >= 1");
     if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)n_start, U = S * (size_t)niter * (size_t)(N + 1);
-    NmWork w;
-    misti::BhState bh{};
-    bh.S = n_start; bh.N = N;
-    bh.beta = T != 0.0 ? 1.0 / T : INFINITY;
-    bh.target = target_accept_rate; bh.factor = stepwise_factor; bh.interval = interval;
-    double *d_trial = nullptr, *d_uni = nullptr;
-    auto bh_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
-        bh.x_cur = f.take(S * N); bh.x_best = f.take(S * N); d_trial = f.take(S * N);
-        bh.f_cur = f.take(S); bh.f_best = f.take(S); bh.stepsize = f.take(S);
-        d_uni = f.take(U);
-        bh.ok_cur = i.take(S); bh.ok_best = i.take(S); bh.nstep = i.take(S); bh.naccept = i.take(S);
-        bh.nfev = i.take(S); bh.failures = i.take(S); bh.accepted = i.take(S);
-    };
-    if (int r = nm_prepare(c, n_start, N, w, bh_layout)) return r;
-    hipStream_t sm = c->stream;
-    HIP_TRY(hipMemcpyAsync(w.d_starts, starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(w.d_row, jsfs_row, 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (U) HIP_TRY(hipMemcpyAsync(d_uni, uniforms, U * sizeof(double), hipMemcpyHostToDevice, sm));
-    {
-        std::vector<double> st0(S, stepsize);
-        HIP_TRY(hipMemcpyAsync(bh.stepsize, st0.data(), S * sizeof(double), hipMemcpyHostToDevice, sm));
-        HIP_TRY(hipStreamSynchronize(sm));                  // st0 is a local
-    }
-    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    // BasinHoppingRunner.__init__: the initial minimisation from the start itself
-    if (int r = nm_run(c, w, split_time, xatol, fatol, nm_maxiter, nm_maxfev)) return r;
-    HIP_TRY(misti::launch_bh_update(bh, w.st, w.d_starts, w.d_llh, w.st.shrunk, -1, niter, d_uni, sm));
-    for (int hop = 0; hop < niter; ++hop) {                 // one_cycle, all starts in step
-        HIP_TRY(misti::launch_bh_step(bh, hop, niter, d_uni, d_trial, sm));
-        HIP_TRY(hipMemcpyAsync(w.d_starts, d_trial, S * N * sizeof(double), hipMemcpyDeviceToDevice, sm));
-        if (int r = nm_run(c, w, split_time, xatol, fatol, nm_maxiter, nm_maxfev)) return r;
-        HIP_TRY(misti::launch_bh_update(bh, w.st, w.d_starts, w.d_llh, w.st.shrunk, hop, niter, d_uni, sm));
-    }
-    HIP_TRY(misti::launch_bh_result(bh, w.d_starts, w.d_llh, sm));
-    if (int r = nm_copy_back(c, w, x, llh, nullptr, nullptr, nullptr)) return r;
-    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, bh.nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (failures) HIP_TRY(hipMemcpyAsync(failures, bh.failures, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (accepted) HIP_TRY(hipMemcpyAsync(accepted, bh.accepted, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipStreamSynchronize(sm));
-    return 0;
+    const NmHops h{niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted};
+    return bh_run(c, {n_start, starts, NmSearch::ONE_SPLIT, split_time, nullptr, nullptr, 1, jsfs_row, nullptr, nullptr,
+                      xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr, &h}, N, false);
+}
+
+int misti_basinhopping_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                            const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                            int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
+                            double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
+                            double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
+    return bh_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, band_bounds, pulse_times,
+                       xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr},
+                   {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
+}
+
+int misti_basinhopping_split(misti_ctx* c, int64_t n_start, const double* starts, const int32_t* rows,
+                             const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                             int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
+                             double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
+                             double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
+    return bh_impl(c, {n_start, starts, NmSearch::SPLIT_FITTED, 0.0, nullptr, rows, n_rep, jsfs, band_bounds, pulse_times,
+                       xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr},
+                   {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
 }
 
 int misti_nm_last_stats(misti_ctx* c, int64_t stats[2]) {

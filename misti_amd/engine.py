@@ -374,6 +374,60 @@ class Engine:
         stats = self._nm_stats()
         return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, iterations_issued=stats["iterations_issued"], slots=stats["slots"])
 
+    def _bh_search(self, symbol, starts, rows, table, rngs, split_times, band_bounds, pulse_times, niter, T, stepsize, interval,
+                   target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev):
+        """``misti_basinhopping_rows`` / ``misti_basinhopping_split``: shapes the inputs, draws the uniforms, calls ``symbol`` and returns
+        the results with the work counters.  ``split_times`` is None for the split form, whose starts carry the split as one coordinate
+        more.  Band bounds and pulse times that are ``None``, or that the model has no band / pulse for, go as NULL."""
+        N = self.n_param + (1 if split_times is None else 0)
+        st = _f64(starts, (-1, N))
+        S = st.shape[0]
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
+        tab = _f64(table, (-1, 8))
+        per_start = [] if split_times is None else [ptr(_f64(split_times, (S,)))]
+        r_of = i32(rows, (S,))
+        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
+        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
+        uni = draw_uniforms(rngs, S, max(int(niter), 0), N)          # (a negative niter is the library's to refuse)
+        x = np.empty((S, N))
+        llh = np.empty(S)
+        nfev, failures, accepted = (np.empty(S, dtype=np.int32) for _ in range(3))
+        _lib.check(getattr(self._lib, symbol)(self._ctx, S, ptr(st), *per_start, ptr(r_of), ptr(bb), ptr(pt), tab.shape[0], ptr(tab),
+                                              int(niter), float(T), float(stepsize), int(interval), float(target_accept_rate),
+                                              float(stepwise_factor), float(xatol), float(fatol),
+                                              int(nm_maxiter if nm_maxiter is not None else 200 * N),
+                                              int(nm_maxfev if nm_maxfev is not None else 200 * N),
+                                              ptr(uni), ptr(x), ptr(llh), ptr(nfev), ptr(failures), ptr(accepted)))
+        return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, **self._nm_stats())
+
+    def basinhopping_rows(self, starts, split_times, rows, table, rngs, band_bounds=None, pulse_times=None, niter=100, T=0.5, stepsize=0.5,
+                          interval=50, target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
+        """``misti_basinhopping_rows``: ``basinhopping`` with a split time and a replicate row PER START - start s is SciPy's
+        ``basinhopping`` around Nelder-Mead at ``split_times[s]`` against ``table[rows[s]]`` (``[n_rep][8]``), with the model's bands at
+        ``band_bounds[s]`` (``[S][n_band][2]``) and its pulses at ``pulse_times[s]`` (``[S][n_pulse]``) where given - the reference's
+        ``Solve(globalOpt=True)`` for every (row, split) pair of its ``test.bs`` workflow in one call.  ``rngs`` as ``basinhopping``;
+        ``nm_maxiter`` and ``nm_maxfev`` default to ``200 x n_param``.  A start the engine refuses throughout has ``llh = -inf``.
+        Returns what ``basinhopping`` returns plus ``speculative_iterations``; start s equals
+        ``basinhopping(starts[s:s+1], split_times[s], table[rows[s]], [rngs[s]])`` on an engine whose model carries ``band_bounds[s]`` and
+        ``pulse_times[s]``, bit for bit."""
+        return self._bh_search("misti_basinhopping_rows", starts, rows, table, rngs, np.asarray(split_times, dtype=np.float64), band_bounds,
+                               pulse_times, niter, T, stepsize, interval, target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev)
+
+    def basinhopping_split(self, starts, rows, table, rngs, band_bounds=None, pulse_times=None, niter=100, T=0.5, stepsize=0.5, interval=50,
+                           target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
+        """``misti_basinhopping_split``: basin hopping with the split time as the LAST coordinate - ``starts`` is ``[S][n_param + 1]``,
+        start s is ``scipy.optimize.basinhopping`` around Nelder-Mead over (parameters, split) against ``table[rows[s]]``; the random
+        displacement moves the split like any other coordinate (one ``stepsize``, the split in grid-index units), so the uniforms are
+        drawn for ``n_param + 1`` coordinates, and ``nm_maxiter`` / ``nm_maxfev`` default to ``200 x (n_param + 1)``.  The global
+        counterpart of ``nm_solve_split`` on its piecewise objective, and the global search of a model without an optimised
+        parameter.  ``band_bounds`` / ``pulse_times`` per start as in ``nm_solve_split``.
+        Returns what ``basinhopping_rows`` returns with ``x[S][n_param + 1]``, plus ``split`` (= ``x[:, -1]``)."""
+        r = self._bh_search("misti_basinhopping_split", starts, rows, table, rngs, None, band_bounds, pulse_times, niter, T, stepsize, interval,
+                            target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev)
+        r["split"] = r["x"][:, -1].copy()
+        return r
+
     def enable_solver_trace(self, on=True):
         """Record, for the following batches, SciPy-comparable solver statistics per candidate and interval
         (``misti_enable_solver_trace``; see ``solver_trace``)."""

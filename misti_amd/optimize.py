@@ -509,10 +509,11 @@ def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter
                                rows.shape[0], splits.size, starts)
 
 
-def _best_start_profile(search, R, P, starts):
+def _best_start_profile(search, R, P, starts, per_start=("nit", "nfev", "status")):
     """What bootstrap_profile and sweep_profile share: ``search(r_of, p_of, starts)`` runs ONE batched search over every
     (row, point, start) triple (row outermost, start innermost; ``r_of`` int32), then per (row, point) the best start is kept - the
-    first maximum, i.e. the lowest start index on ties; NaN never wins."""
+    first maximum, i.e. the lowest start index on ties; NaN never wins.  ``per_start``: the search's per-start results kept beside
+    ``x`` and ``llh``."""
     starts = np.atleast_2d(np.asarray(starts, dtype=float))
     Q = starts.shape[0]
     r_of, p_of, q_of = (a.ravel() for a in np.meshgrid(np.arange(R), np.arange(P), np.arange(Q), indexing="ij"))
@@ -520,9 +521,39 @@ def _best_start_profile(search, R, P, starts):
     llh = res["llh"].reshape(R, P, Q)
     best = np.argmax(np.where(np.isnan(llh), -np.inf, llh), axis=2)              # first maximum: the lowest start index
     pick = lambda a: np.take_along_axis(a.reshape(R, P, Q, *a.shape[1:]), best.reshape(R, P, 1, *([1] * (a.ndim - 1))), axis=2)[:, :, 0]
-    out = dict(x=pick(res["x"]), llh=pick(res["llh"]), nit=pick(res["nit"]), nfev=pick(res["nfev"]), status=pick(res["status"]), start=best)
+    out = dict(x=pick(res["x"]), llh=pick(res["llh"]), **{k: pick(res[k]) for k in per_start}, start=best)
     out.update({k: res[k] for k in ("iterations_issued", "slots", "speculative_iterations")})
     return out
+
+
+_HOP_RESULTS = ("nfev", "failures", "accepted")
+
+
+def _hop_generators(seed, R, n):
+    """The generators of a ``*_global`` call of R rows x n searches per row, in the flattened (row, point, start) order: search j of
+    every row (point outermost, start innermost) draws from a fresh ``numpy.random.default_rng([seed, j])``.  j does not count the
+    rows: what a row's searches draw does not depend on how many rows the call holds, or on which (the rows of a bootstrap share
+    their random numbers - only the data differ between them)."""
+    return [np.random.default_rng([int(seed), j]) for _ in range(R) for j in range(n)]
+
+
+def bootstrap_profile_global(engine, split_values, jsfs_rows, starts, seed=0, niter=100, T=0.5, stepsize=0.5, **hop_options):
+    """``bootstrap_profile`` with hops: per (row, split, start) triple the reference's global search - ``Solve(globalOpt=True)``,
+    ``scipy.optimize.basinhopping(T=0.5, Nelder-Mead)``, MigrationInference.py:723-725 of the reference - instead of its local one, all
+    triples in ONE ``misti_basinhopping_rows`` call.  Same triple layout (row outermost, start innermost) and the same best-start rule.
+    The generator of search j is ``numpy.random.default_rng([seed, j])``, j = the search's index in the flattened (row, point, start)
+    order taken WITHIN its row (``_hop_generators``), so a row's result does not depend on which other rows are in the call.
+    ``hop_options``: ``interval``, ``target_accept_rate``, ``stepwise_factor``, ``xatol``, ``fatol``, ``nm_maxiter``, ``nm_maxfev`` of
+    ``Engine.basinhopping_rows`` (SciPy's defaults).
+    Returns dict(x[R][P][N], llh[R][P], nfev / failures / accepted / start[R][P], and the search's work counters)."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.asarray(split_values, dtype=float).reshape(-1)
+    R = rows.shape[0]
+
+    def search(r_of, p_of, st):
+        gens = _hop_generators(seed, R, r_of.size // R)
+        return engine.basinhopping_rows(st, splits[p_of], r_of, rows, gens, niter=niter, T=T, stepsize=stepsize, **hop_options)
+    return _best_start_profile(search, R, splits.size, starts, _HOP_RESULTS)
 
 
 def bootstrap_profile_interval(llh, split_values, x=None):
@@ -577,6 +608,37 @@ def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_t
         return engine.nm_solve_split(x0, r_of, rows, band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
                                      pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0), tol=tol, maxiter=maxiter)
     out = _best_start_profile(search, rows.shape[0], 1, pairs)
+    out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+    out["split"] = out["x"][:, -1].copy()
+    return out
+
+
+def split_fit_global(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_times=None, seed=0, niter=100, T=0.5, stepsize=0.5,
+                     **hop_options):
+    """``split_fit`` with hops: per row one basin-hopping search over (optimised parameters, split) from every (start, initial split)
+    pair - the answer to an objective that is piecewise in the split, where a local simplex search stops at the first kink it meets -
+    all R x Q x P searches in ONE ``misti_basinhopping_split`` call.  Same layout of the triples (row outermost, initial split
+    innermost), same best-search rule (``_best_start_profile``).  The generator of search j is
+    ``numpy.random.default_rng([seed, j])``, j = the search's index in the flattened (row, point, start) order taken WITHIN its row
+    (``_hop_generators``), so a row's result does not depend on which other rows are in the call.  ``hop_options`` as
+    ``bootstrap_profile_global`` (``nm_maxiter`` / ``nm_maxfev`` default to ``200 x (n_param + 1)``).
+    Returns dict(x[R][n_param + 1], split[R], llh[R], nfev / failures / accepted / start[R], and the search's work counters);
+    ``split_fit_interval`` takes ``split`` and ``llh`` unchanged."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.asarray(split_starts, dtype=float).reshape(-1)
+    P = engine.n_param
+    st = np.asarray(starts, dtype=float).reshape(-1, P) if P else np.empty((1, 0))
+    pairs = np.hstack([np.repeat(st, splits.size, axis=0), np.tile(splits, st.shape[0])[:, None]])       # [Q x P][n_param + 1]
+    tile = lambda a, shape: None if a is None else np.asarray(a, dtype=np.int32).reshape(shape)
+    R = rows.shape[0]
+
+    def search(r_of, p_of, x0):
+        bb, pt = tile(band_bounds, (1, -1, 2)), tile(pulse_times, (1, -1))
+        gens = _hop_generators(seed, R, r_of.size // R)
+        return engine.basinhopping_split(x0, r_of, rows, gens, band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
+                                         pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0),
+                                         niter=niter, T=T, stepsize=stepsize, **hop_options)
+    out = _best_start_profile(search, R, 1, pairs, _HOP_RESULTS)
     out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
     out["split"] = out["x"][:, -1].copy()
     return out
