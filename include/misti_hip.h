@@ -454,6 +454,78 @@ int misti_nm_last_stats(misti_ctx* ctx, int64_t stats[2]);
  * from the values it would have asked for - one chain latency per iteration instead of three; nfev stays SciPy's count. */
 int misti_nm_last_spec_iterations(misti_ctx* ctx, int64_t* n);
 
+/* ---- curvature at a fitted point ---------------------------------------------------------------- */
+/* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
+ * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)
+ * (MigrationInference.py:600-609; S the class spectrum, four classes folded, seven unfolded), so the gradient and the Hessian of
+ * EVERY row are contractions of that row's class counts with the first and second derivatives of L_k = log S_k, and those do not
+ * depend on the data.  The reference has no counterpart: it reports the fitted rates and nothing about how well they are determined.
+ * Stencil and rule (fixed; stated in NumPy as misti_amd.optimize.curvature_stencil / curvature_from_spectra, whose order of
+ * floating-point operations the kernels follow):
+ *   - a point is D = n_param >= 1 parameters x, a FIXED split time and optionally its own band bounds and pulse times; the split is
+ *     not a differentiated coordinate (the objective is piecewise in it);
+ *   - steps h_i = max(rel_step |x_i|, abs_step), both step arguments finite and not negative, at least one positive;
+ *   - a point with x_i - h_i < 0 for some i (or h_i == 0: a rate of 0 under abs_step == 0) has no two-sided stencil: status
+ *     MISTI_CURV_BOUNDARY, none of its stencil points is evaluated (one-sided stencils are out of scope);
+ *   - M = 1 + 2 D^2 candidates: 0 the centre; 1 + 2i is +h_i, 2 + 2i is -h_i; for the pairs i < j in lexicographic order, of rank
+ *     q, 1 + 2D + 4q + {0, 1, 2, 3} are (+h_i, +h_j), (+h_i, -h_j), (-h_i, +h_j), (-h_i, -h_j);
+ *   - dL_k/dx_i = (L_k(+i) - L_k(-i)) / (2 h_i);  d2L_k/dx_i^2 = (L_k(+i) - 2 L_k(0) + L_k(-i)) / h_i^2;
+ *     d2L_k/dx_i dx_j = (L_k(++) - L_k(+-) - L_k(-+) + L_k(--)) / (4 h_i h_j), both triangles written from one computed value: the
+ *     Hessian is bitwise symmetric;
+ *   - a stencil candidate has no value if its engine status is not 0 or a class value is not positive and finite; the point then
+ *     carries the status of the FIRST such candidate in stencil order (MISTI_NUMERIC where that candidate's status was 0) and every
+ *     output of the point is NaN; neighbouring points are unaffected.
+ * The default relative step of the Python layer and the command line (1e-2) is an UNMEASURED choice; it is an argument everywhere. */
+#define MISTI_CURV_BOUNDARY 7   /* point status only (the engine's candidate statuses end at 6): no two-sided stencil at this point */
+
+/* Assembly and contraction alone, from stencil spectra the caller made (device pointers; asynchronous on the context's stream): what
+ * misti_curvature runs behind its evaluations, and testable without the chain kernels.  D = the context's n_param, M = 1 + 2 D^2.
+ *   d_jafs         [n_point][M][7]     spectra of every point's stencil, in stencil order
+ *   d_status       [n_point][M] or NULL   their engine statuses (NULL: all 0)
+ *   d_h            [n_point][D]        the steps (positive)
+ *   d_rows         [n_point] or NULL   replicate row per point, 0 <= row < n_rep (NOT checked here: the indices live on the device);
+ *                                      NULL: no contraction, d_grad and d_hess must be NULL
+ *   n_rep, d_jsfs  the replicate table [n_rep][8] (read only with d_rows)
+ *   d_dlog         [n_point][D][7] or NULL      dL_k/dx_i; a folded model uses classes 0..3 (0+6, 1+5, 2+4, 3), entries 4..6 are 0
+ *   d_d2log        [n_point][D][D][7] or NULL   d2L_k/dx_i dx_j
+ *   d_grad         [n_point][D] or NULL         sum_k d_k dL_k/dx_i over the classes in ascending order, the class counts of the
+ *                                               point's row formed as the replicate epilogue forms them (folded: d0+d6, d1+d5, d2+d4, d3)
+ *   d_hess         [n_point][D][D] or NULL      sum_k d_k d2L_k/dx_i dx_j
+ *   d_point_status [n_point]                    0, or the status of the first stencil candidate without a value
+ * MISTI_E_ARG for n_param == 0, a negative count, a NULL d_jafs / d_h / d_point_status with work to do, d_grad or d_hess without
+ * d_rows, d_rows with n_rep < 1 or a NULL d_jsfs; MISTI_E_LIMIT for n_point x M > INT32_MAX - before anything touches the device.
+ * n_point == 0 returns 0. */
+int misti_curvature_assemble_dev(misti_ctx* ctx, int64_t n_point, const double* d_jafs, const int32_t* d_status, const double* d_h,
+                                 const int32_t* d_rows, int64_t n_rep, const double* d_jsfs,
+                                 double* d_dlog, double* d_d2log, double* d_grad, double* d_hess, int32_t* d_point_status);
+
+/* The whole of it for n_point points (host buffers; synchronous; of the misti_nm_solve_pulses family): the stencil is laid out on
+ * the device (the candidates of boundary points are never emitted: a compacted index built on the device), evaluated through the
+ * batch path without replicates - whole points packed into engine batches, a point is never split - then assembled and contracted
+ * with each point's own row.
+ *   x            [n_point][n_param]   the points (n_param >= 1), finite
+ *   split_times  [n_point]            finite, fractional allowed (a split the engine refuses gives that point the engine's status)
+ *   rows         [n_point]            0 <= rows[p] < n_rep
+ *   band_bounds  [n_point][n_band][2] or NULL   per point, as misti_nm_solve_bounds (NULL, or a model without bands: the model's)
+ *   pulse_times  [n_point][n_pulse] or NULL     per point, as misti_nm_solve_pulses
+ *   n_rep, jsfs  the replicate table [n_rep][8]
+ *   rel_step, abs_step   the steps (see above)
+ *   batch_limit  most candidates per engine batch; 0: the library's choice; below M: MISTI_E_ARG.  Results do not depend on it
+ *   llh0         [n_point] or NULL          the centre's log-likelihood against rows[p]: bit for bit misti_eval_batch's value
+ *   grad         [n_point][D] or NULL       gradient of the log-likelihood of rows[p]
+ *   hess         [n_point][D][D] or NULL    its Hessian
+ *   dlog         [n_point][D][7] or NULL    A = dL_k/dx_i: the score covariance over bootstrap rows is A Cov(d) A^T
+ *   point_status [n_point]                  0, MISTI_CURV_BOUNDARY, or the engine's status of the first stencil candidate without a
+ *                                           value; every other output of such a point is NaN
+ * MISTI_E_ARG for a NULL x / split_times / rows / jsfs / point_status, n_rep < 1, a row out of range, a non-finite x or split time,
+ * steps that are not finite, negative or both 0, n_param == 0 or 0 < batch_limit < M; MISTI_E_LIMIT where n_point x M exceeds
+ * INT32_MAX - all before anything touches the device.  n_point == 0 returns 0.
+ * Out of scope: the lanes and the device-list (misti_multi_*) forms, the split as a differentiated coordinate, one-sided stencils. */
+int misti_curvature(misti_ctx* ctx, int64_t n_point, const double* x, const double* split_times, const int32_t* rows,
+                    const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
+                    double rel_step, double abs_step, int64_t batch_limit,
+                    double* llh0, double* grad, double* hess, double* dlog, int32_t* point_status);
+
 /* ---- lanes: many batches in flight on ONE device ------------------------------------------------ */
 /* One batch is latency-bound: its longest lambda-correction chain is as sequential as the reference's solver (the 4 096-point headline
  * grid keeps 64 of the chip's 1 024 SIMDs busy for 1.4 ms), so THROUGHPUT comes from independent batches in flight - the grids of

@@ -21,6 +21,8 @@ STATUS_TEXT = {
     5: "Non-finite intermediate or iteration cap",
     6: "Stiff interval: the contour solve failed and rate x length exceeds 256 series sub-steps of 96",
 }
+NUMERIC = 5
+CURV_BOUNDARY = 7        # point status of misti_curvature only: no two-sided stencil at this point (STATUS_TEXT stays the engine's)
 MAX_BANDS, MAX_PULSES, MAX_PARAMS, MAX_NUMT = 8, 8, 16, 255
 LANE_ANY, MAX_LANES = -1, 64
 ABI_VERSION = 6
@@ -100,6 +102,10 @@ SYMBOLS = {
     "misti_argmax_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_scan_best_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "misti_scan_profile_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_curvature_assemble_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_curvature": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_double, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_last_diag": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "misti_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "misti_kernel_times": (C.c_int, [C.c_void_p, _PD, C.POINTER(C.c_int64), C.c_int]),

@@ -56,6 +56,17 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               freedom - a likelihood-ratio support interval of a composite likelihood, not a confidence interval), with
                               --all-bs and axis st the bootstrap interval, and the timing line.  Not offered with --top, --polish,
                               --fit-st, --grid-solve, --sweep, --sweep-pu, --gpus N > 1 or --devices
+    --se                      with --grid-solve (also with --all-bs) or with the plain single-model Solve: after the fit, the curvature
+                              of the log-likelihood at every fitted point (misti_curvature: one stencil of 1 + 2 n^2 evaluations per
+                              point, the split held fixed) - per fitted rate the standard error from the observed information
+                              inv(-H), the correlation matrix and the condition number of -H, one `se:` line per printed fit; a fit
+                              whose -H is not positive definite (a flat direction, a rate on its boundary) says so instead.  With at
+                              least three bootstrap rows (--all-bs, or -bs N on a file of 1 + B rows: row 0 is the data, the rest
+                              resamples) also the sandwich standard error H^-1 (A C A^T) H^-1 of a composite likelihood, C the
+                              covariance of the class counts over those rows.  Not offered with --gpus N > 1, --devices, --fit-st,
+                              --hops, --sweep or --sweep-pu; grid mode needs --grid-solve for it.  Every other line stays as it is
+    --se-step REL             with --se (refused without): the relative step of the stencil, h_i = REL x |rate_i| (default 1e-2: an
+                              unmeasured choice)
     --gpus N                  the sweep on N GPUs of the node: this process starts N ranks (one per GPU, torch.distributed over
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
@@ -140,11 +151,66 @@ def build_parser():
                    help="grid mode: the profile likelihood per row along one scanned axis (st, or K of --grid-mi K) or over two, reduced on the device without the table")
     p.add_argument("--profile-drop", type=float, default=None, metavar="D",
                    help="with --profile AXIS: the support: line lists the axis values within D of the row's maximum (default: chi2.ppf(0.95, 1) / 2)")
+    p.add_argument("--se", action="store_true",
+                   help="with --grid-solve or the single-model Solve: standard errors and correlations of the fitted rates from the Hessian at the fit "
+                        "(and the sandwich standard error with at least three bootstrap rows)")
+    p.add_argument("--se-step", type=float, default=None, metavar="REL", help="with --se: relative step of the stencil (default 1e-2)")
     p.add_argument("--sweep", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="the GNU-parallel recipe's `::: NAME V1 V2 ...`: {NAME} in the split time or in -mi start / end / rate fields")
     p.add_argument("--sweep-pu", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="a sweep variable of the pulses: {NAME} in the time field or in the fraction field of -pu")
     return p
+
+
+def se_error(a):
+    """Why ``--se`` / ``--se-step`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if not a.se:
+        if a.se_step is not None:
+            return "--se-step sets the stencil's step of --se: give --se"
+        return None
+    if a.sweep or a.sweep_pu:
+        return "--se reports the curvature at the fit of ONE model: --sweep / --sweep-pu are not offered with it"
+    if a.gpus > 1 or a.devices:
+        return "--se runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    if a.fit_st:
+        return "--se holds the split time fixed (the objective is piecewise in it): --fit-st is not offered with it"
+    if a.hops is not None:
+        return "--se follows the local search of --grid-solve or of the single model: --hops is not offered with it"
+    if not a.grid_solve and (a.grid_st or a.grid_mi or a.all_bs or a.top is not None or a.profile is not None):
+        return "--se reports the curvature at a FITTED point: with --grid-st / --grid-mi / --all-bs it needs --grid-solve"
+    if a.se_step is not None and not (a.se_step > 0 and np.isfinite(a.se_step)):
+        return "--se-step must be positive and finite (got %g)" % a.se_step
+    if not any(int(el[4]) for el in a.mi) and not any(int(el[3]) for el in a.pu):
+        return "--se needs at least one optimised parameter (-mi ... 1 or -pu ... 1)"
+    return None
+
+
+def _se_step(a):
+    """--se-step, or its default: optimize.CURV_REL_STEP (1e-2, an unmeasured choice)."""
+    from .optimize import CURV_REL_STEP
+    return CURV_REL_STEP if a.se_step is None else a.se_step
+
+
+def print_se(labels, cur, table=None, unfolded=False):
+    """The ``se:`` lines of --se: per fitted point (``labels[p]``: what names it, ``cur``: Engine.curvature at the fits) the standard
+    errors from the observed information, the correlation matrix and the condition number of -H; with ``table`` (row 0 the data,
+    at least three bootstrap rows behind it) the sandwich standard errors as well.  Numbers are printed with repr: they read back exactly."""
+    from .optimize import correlation, observed_covariance, sandwich_covariance, standard_errors
+    obs = observed_covariance(cur.hess)
+    se, corr = standard_errors(obs["cov"]), correlation(obs["cov"])
+    sand = standard_errors(sandwich_covariance(cur.hess, cur.dlog, table, unfolded=unfolded)) if table is not None else None
+    vec = lambda v: "[" + ", ".join(repr(float(t)) for t in v) + "]"
+    for p, label in enumerate(labels):
+        if cur.status[p] == 7:
+            print("se:", label, "\tno two-sided stencil: a fitted rate lies within its step of 0 (status 7)")
+        elif cur.status[p] != 0:
+            print("se:", label, "\tno value at a stencil point (status %d)" % int(cur.status[p]))
+        elif not obs["ok"][p]:
+            print("se:", label, "\t-H is not positive definite (eigenvalues %s): no standard error - a flat direction or a point that is no maximum"
+                  % vec(obs["eigenvalues"][p]))
+        else:
+            print("se:", label, "\tse =", vec(se[p]), "\tcorr =", "[" + ", ".join(vec(r) for r in corr[p]) + "]", "\tcond = %.6g" % obs["cond"][p],
+                  ("\tsandwich se = " + vec(sand[p])) if sand is not None else "")
 
 
 def grid_solve_error(a):
@@ -519,11 +585,20 @@ def grid_solve(a, inp, rows):
             prof = bootstrap_profile_global(e, splits, data, starts, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step)
         else:
             prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000)
+        if a.se:
+            # one stencil per printed fit, all of them in one call: row outermost, split innermost, as the lines
+            R_, P_ = data.shape[0], len(splits)
+            cur = e.curvature(prof["x"].reshape(R_ * P_, k), np.tile(np.asarray(splits, dtype=float), R_), np.repeat(np.arange(R_), P_), data,
+                              rel_step=_se_step(a))
     dt = time.time() - t0
     for r in range(data.shape[0]):
         for p, st in enumerate(splits):
             print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, prof["x"][r, p], prof["llh"][r, p])
                   + (_hops_text(prof, r, p) if a.hops else ""))
+    if a.se:
+        print()
+        print_se(["bs_id = %s \tsplitT = %s" % (ids[r], st) for r in range(data.shape[0]) for st in splits], cur,
+                 data if a.all_bs and data.shape[0] >= 4 else None, a.uf)
     iv = bootstrap_profile_interval(prof["llh"], splits, prof["x"])
     print()
     if iv["data_split"] is None:
@@ -711,7 +786,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
+    why = se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
@@ -780,6 +855,12 @@ def main(argv=None):
     print("\nParameter estimates:")
     # inp.times was extended in place by a fractional split, as in the reference (MiSTI.py:240)
     print(result_line(a.bsMode, inp.divergenceTime, inp.times, inp.scaleTime, a.mi, sol[0], sol[1]))
+    if a.se and sol[1] != -10 ** 9:
+        # a -bs N run on a bootstrap table (row 0 the data, resamples behind it) has the rows the sandwich needs; the sum of all rows has not
+        boot = np.array(rows, dtype=float) if a.bsMode >= 0 and len(rows) >= 4 else None
+        cur = mig._engine.curvature([list(sol[0])], [a.st], [max(a.bsMode, 0)] if boot is not None else [0],
+                                    boot if boot is not None else [inputSFS], rel_step=_se_step(a))
+        print_se(["bs_id = %s \tsplitT = %s" % (a.bsMode, a.st)], cur, boot, a.uf)
     print("\n")
     t2 = time.time()
     if sol[1] == -10 ** 9:

@@ -261,4 +261,22 @@ hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status,
 hipError_t launch_llk_rows(int64_t n, const double* jafs, const int32_t* status, const int32_t* row, const double* jsfs,
                            const double* consts, double* llk, int unfolded, hipStream_t stream);
 
+// Curvature at a point (misti_curvature, misti_curvature_assemble_dev): a point of D parameters has M = 1 + 2 D^2 stencil candidates.
+// launch_curv_stencil: h[P][D] and point_status[P] (MISTI_CURV_BOUNDARY or 0), slot[P] (the point's rank among the points that have a
+// stencil, -1 without: an exclusive scan on the device), and the candidates of those points in compacted arrays c_* ([cap * M] rows;
+// c_bounds / c_pulses with nb2 / np integers per row, NULL with 0); `cap` is the host's own count of such points and bounds every write.
+hipError_t launch_curv_stencil(int64_t n_point, int D, const double* x, const double* split, const int32_t* bounds, int nb2,
+                               const int32_t* pulses, int np, double rel_step, double abs_step, int64_t cap, double* h, int32_t* point_status,
+                               int32_t* slot, double* c_split, double* c_params, int32_t* c_bounds, int32_t* c_pulses, hipStream_t stream);
+// dlog[P][D][7] / d2log[P][D][D][7] (either may be NULL) and point_status[P] from the stencil's spectra jafs[.][M][7] and statuses
+// (NULL: all OK); point p's spectra start at row slot[p] * M (slot NULL: p * M), a point with slot[p] < 0 keeps pre_status[p].
+hipError_t launch_curv_assemble(int64_t n_point, int D, int unfolded, const double* jafs, const int32_t* status, const double* h,
+                                const int32_t* slot, const int32_t* pre_status, double* dlog, double* d2log, int32_t* point_status,
+                                hipStream_t stream);
+// grad[P][D] / hess[P][D][D]: dlog / d2log contracted with the class counts of row[p]; with llh0 (then jafs, slot and consts are
+// needed too) the log-likelihood of every point's centre against its row, llk_rows_kernel's bits.
+hipError_t launch_curv_contract(int64_t n_point, int D, int unfolded, const double* dlog, const double* d2log, const int32_t* point_status,
+                                const int32_t* row, const double* jsfs, double* grad, double* hess, const double* jafs, const int32_t* slot,
+                                const double* consts, double* llh0, hipStream_t stream);
+
 }  // namespace misti

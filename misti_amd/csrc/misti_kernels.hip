@@ -12,6 +12,8 @@
 //                           own intervals after the trunk, collapse, one-population closed form,
 //                           normalisation, llk of up to 8 replicates  (llk_kernel beyond that)
 // fp64 throughout, no MFMA (the per-interval matrices are 3x3 / 44x44 with ~200 non-zeros).
+// Behind the batch, on its spectra: llk_kernel / llk_rows_kernel, the scans (scan_best, scan_profile) and the curvature at a point
+// (curv_*_kernel: stencil, derivatives of the class logs, contraction with a row's counts - end of this file).
 //
 // Reference path restated here (cites: /root/reference):
 //   JAFSLikelihood  MigrationInference.py:566-614     driver, status codes
@@ -3751,6 +3753,244 @@ hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status,
         if (unfolded) hipLaunchKernelGGL(llk_kernel<true>, grid, dim3(256), 0, stream, nc, (int)chunk, jafs + c0 * 7, status ? status + c0 : nullptr, n_rep, jsfs, consts, llk + c0 * n_rep);
         else hipLaunchKernelGGL(llk_kernel<false>, grid, dim3(256), 0, stream, nc, (int)chunk, jafs + c0 * 7, status ? status + c0 : nullptr, n_rep, jsfs, consts, llk + c0 * n_rep);
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------- curvature at a point --
+// Hessians of the log-likelihood by central differences of L_k = log S_k over a fixed stencil (misti_curvature,
+// misti_curvature_assemble_dev; the rule is optimize.curvature_stencil / optimize.curvature_from_spectra, operation for operation).
+// A point has D parameters and M = 1 + 2 D^2 stencil candidates: 0 the centre, 1 + 2i / 2 + 2i the steps +h_i / -h_i, and for the
+// q-th pair i < j (lexicographic) 1 + 2D + 4q + {0, 1, 2, 3} the steps (+,+), (+,-), (-,+), (-,-).
+__host__ __device__ __forceinline__ int curv_pair_rank(int i, int j, int D) { return i * D - i * (i + 1) / 2 + (j - i - 1); }
+
+// thread = point: h[p][i] = max(rel |x_i|, abs); a point with a step that leaves the positive half-line (x_i - h_i < 0), or with no
+// step at all (h_i == 0: a rate of 0 under a purely relative step), has no two-sided stencil: MISTI_CURV_BOUNDARY.
+__global__ __launch_bounds__(256)
+void curv_steps_kernel(int64_t n_point, int D, const double* __restrict__ x, double rel_step, double abs_step,
+                       double* __restrict__ h, int32_t* __restrict__ point_status) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_point) return;
+    bool boundary = false;
+    for (int i = 0; i < D; ++i) {
+        const double xi = x[p * D + i];
+        const double hi = fmax(rel_step * fabs(xi), abs_step);
+        h[p * D + i] = hi;
+        boundary = boundary || xi - hi < 0.0 || hi == 0.0;
+    }
+    point_status[p] = boundary ? MISTI_CURV_BOUNDARY : MISTI_OK;
+}
+
+// One workgroup: slot[p] = the number of points in front of p that have a stencil (their rank in the compacted candidate arrays),
+// -1 for a boundary point.  A thread sums a contiguous run of points, the 256 run sums are scanned in LDS, then every thread walks
+// its run again (profile_offsets_kernel's scheme).
+__global__ __launch_bounds__(256)
+void curv_slots_kernel(int64_t n_point, const int32_t* __restrict__ point_status, int32_t* __restrict__ slot) {
+    __shared__ int32_t run[256];
+    const int64_t per = (n_point + 255) / 256;
+    const int64_t p0 = (int64_t)threadIdx.x * per < n_point ? (int64_t)threadIdx.x * per : n_point;
+    const int64_t p1 = p0 + per < n_point ? p0 + per : n_point;
+    int32_t sum = 0;
+    for (int64_t p = p0; p < p1; ++p) sum += point_status[p] == MISTI_OK ? 1 : 0;
+    run[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int32_t below = (int)threadIdx.x >= d ? run[threadIdx.x - d] : 0;
+        __syncthreads();
+        run[threadIdx.x] += below;
+        __syncthreads();
+    }
+    int32_t acc = run[threadIdx.x] - sum;
+    for (int64_t p = p0; p < p1; ++p) {
+        const bool live = point_status[p] == MISTI_OK;
+        slot[p] = live ? acc : -1;
+        acc += live ? 1 : 0;
+    }
+}
+
+// thread = (point, stencil index): candidate slot[p] * M + m of the compacted arrays gets the point's split, bounds and pulse times
+// and its parameters moved by the stencil's steps.  A boundary point emits nothing; `cap` (the host's own count of points with a
+// stencil) bounds every write.
+__global__ __launch_bounds__(256)
+void curv_stencil_kernel(int64_t n_point, int D, int M, const double* __restrict__ x, const double* __restrict__ split,
+                         const int32_t* __restrict__ bounds, int nb2, const int32_t* __restrict__ pulses, int np,
+                         const double* __restrict__ h, const int32_t* __restrict__ slot, int64_t cap,
+                         double* __restrict__ c_split, double* __restrict__ c_params, int32_t* __restrict__ c_bounds,
+                         int32_t* __restrict__ c_pulses) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_point * M) return;
+    const int64_t p = t / M;
+    const int m = (int)(t - p * M);
+    const int64_t s = slot[p];
+    if (s < 0 || s >= cap) return;
+    // which coordinates move, and in which direction
+    int a = -1, b = -1;
+    double sa = 0.0, sb = 0.0;
+    if (m >= 1 && m < 1 + 2 * D) { a = (m - 1) >> 1; sa = ((m - 1) & 1) ? -1.0 : 1.0; }
+    else if (m >= 1 + 2 * D) {
+        const int q = (m - 1 - 2 * D) >> 2, w = (m - 1 - 2 * D) & 3;
+        int i = 0, left = q;
+        while (left >= D - 1 - i) { left -= D - 1 - i; ++i; }
+        a = i; b = i + 1 + left;
+        sa = (w & 2) ? -1.0 : 1.0;
+        sb = (w & 1) ? -1.0 : 1.0;
+    }
+    const int64_t c = s * M + m;
+    c_split[c] = split[p];
+    for (int i = 0; i < D; ++i) {
+        const double xi = x[p * D + i], hi = h[p * D + i];
+        double v = xi;
+        if (i == a) v = sa > 0.0 ? xi + hi : xi - hi;
+        if (i == b) v = sb > 0.0 ? xi + hi : xi - hi;
+        c_params[c * D + i] = v;
+    }
+    for (int i = 0; i < nb2; ++i) c_bounds[c * nb2 + i] = bounds[p * nb2 + i];
+    for (int i = 0; i < np; ++i) c_pulses[c * np + i] = pulses[p * np + i];
+}
+
+// One wave per point (workgroup = one wave; points beyond the grid are walked by the same wave).  The wave reads the point's M
+// spectra - contiguous, lanes over (candidate, class) - and leaves the logs of the K class values in LDS (K = 4 folded, 7 unfolded;
+// log_class's expression); a candidate without a value (status != 0, or a class value that is not positive and finite) makes the
+// point fail with the status of the FIRST such candidate in stencil order (MISTI_NUMERIC where that candidate's status was 0).  Then
+// lanes over (i, k) write dlog[p][i][k] and lanes over (i, j >= i, k) write d2log[p][i][j][k] and d2log[p][j][i][k] from one value.
+// Entries K ... 6 are 0; every output of a failed point is NaN.  slot (may be NULL: point p's spectra are rows p M ... of jafs)
+// names the point's place in compacted arrays, -1 where it has none: its status is then pre_status[p] (MISTI_CURV_BOUNDARY).
+// dlog / d2log may be NULL (not wanted).  LDS: M x K doubles.
+__global__ __launch_bounds__(64)
+void curv_assemble_kernel(int64_t n_point, int D, int M, int unfolded, const double* __restrict__ jafs, const int32_t* __restrict__ status,
+                          const double* __restrict__ h, const int32_t* __restrict__ slot, const int32_t* __restrict__ pre_status,
+                          double* __restrict__ dlog, double* __restrict__ d2log, int32_t* __restrict__ point_status) {
+    extern __shared__ double curv_L[];
+    const int K = unfolded ? 7 : 4;
+    const int lane = threadIdx.x;
+    for (int64_t p = blockIdx.x; p < n_point; p += gridDim.x) {
+        const int64_t s = slot ? (int64_t)slot[p] : p;
+        int st = MISTI_OK;
+        __syncthreads();                              // the previous point's logs have been read by every lane
+        if (s < 0) st = pre_status[p];
+        else {
+            const double* J = jafs + s * M * 7;
+            const int32_t* cs = status ? status + s * M : nullptr;
+            int first = INT_MAX;                      // the first candidate without a value this lane has seen
+            for (int idx = lane; idx < M * K; idx += 64) {
+                const int m = idx / K, k = idx - m * K;
+                const double S = unfolded ? J[m * 7 + k] : (k < 3 ? J[m * 7 + k] + J[m * 7 + 6 - k] : J[m * 7 + 3]);
+                const bool ok = S > 0.0 && isfinite(S) && !(cs && cs[m] != MISTI_OK);
+                if (!ok && m < first) first = m;
+                curv_L[idx] = log(S);
+            }
+            for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(first, d, 64); first = o < first ? o : first; }
+            if (first != INT_MAX) st = (cs && cs[first] != MISTI_OK) ? cs[first] : MISTI_NUMERIC;
+        }
+        __syncthreads();
+        if (lane == 0) point_status[p] = st;
+        const double* hp = h + p * D;
+        if (dlog) {
+            double* out = dlog + p * D * 7;
+            for (int idx = lane; idx < D * 7; idx += 64) {
+                const int i = idx / 7, k = idx - i * 7;
+                double v = 0.0;
+                if (st != MISTI_OK) v = NAN;
+                else if (k < K) v = (curv_L[(1 + 2 * i) * K + k] - curv_L[(2 + 2 * i) * K + k]) / (2.0 * hp[i]);
+                out[idx] = v;
+            }
+        }
+        if (d2log) {
+            double* out = d2log + p * D * D * 7;
+            for (int idx = lane; idx < D * D * 7; idx += 64) {
+                const int ij = idx / 7, k = idx - ij * 7;
+                const int i = ij / D, j = ij - i * D;
+                if (j < i) continue;                  // written by the lane that has (j, i)
+                double v = 0.0;
+                if (st != MISTI_OK) v = NAN;
+                else if (k < K) {
+                    if (i == j) {
+                        const double lp = curv_L[(1 + 2 * i) * K + k], l0 = curv_L[k], lm = curv_L[(2 + 2 * i) * K + k];
+                        v = ((lp - 2.0 * l0) + lm) / (hp[i] * hp[i]);
+                    } else {
+                        const int c = 1 + 2 * D + 4 * curv_pair_rank(i, j, D);
+                        const double lpp = curv_L[c * K + k], lpm = curv_L[(c + 1) * K + k], lmp = curv_L[(c + 2) * K + k], lmm = curv_L[(c + 3) * K + k];
+                        v = (((lpp - lpm) - lmp) + lmm) / ((4.0 * hp[i]) * hp[j]);
+                    }
+                }
+                out[(i * D + j) * 7 + k] = v;
+                out[(j * D + i) * 7 + k] = v;
+            }
+        }
+    }
+}
+
+// thread = one entry of (grad[p][D], hess[p][D][D]): the sum over the classes, ascending, of the row's class counts - formed as the
+// replicate epilogue forms them (llk_of) - times dlog / d2log; products and sums are rounded one by one (no fused multiply-add: the
+// rule in optimize.curvature_contract is written without one).  NaN for a point without a value.  With llh0 given the thread of
+// entry 0 also writes the log-likelihood of the point's centre against its row: llk_rows_kernel's expressions (the same bits as
+// misti_eval_batch's), NaN for a point without a value.
+__global__ __launch_bounds__(256)
+void curv_contract_kernel(int64_t n_point, int D, int unfolded, const double* __restrict__ dlog, const double* __restrict__ d2log,
+                          const int32_t* __restrict__ point_status, const int32_t* __restrict__ row, const double* __restrict__ jsfs,
+                          double* __restrict__ grad, double* __restrict__ hess,
+                          const double* __restrict__ jafs, const int32_t* __restrict__ slot, int M, const double* __restrict__ consts,
+                          double* __restrict__ llh0) {
+    const int E = D + D * D;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_point * E) return;
+    const int64_t p = t / E;
+    const int e = (int)(t - p * E);
+    const bool ok = point_status[p] == MISTI_OK;
+    const double* d = jsfs + (int64_t)row[p] * 8 + 1;
+    double f[7];
+    int K;
+    if (unfolded) { K = 7; for (int i = 0; i < 7; ++i) f[i] = d[i]; }
+    else { K = 4; f[0] = d[0] + d[6]; f[1] = d[1] + d[5]; f[2] = d[2] + d[4]; f[3] = d[3]; }
+    const double* v = e < D ? dlog + (p * D + e) * 7 : d2log + (p * D * D + (e - D)) * 7;
+    double acc = 0.0;
+    for (int k = 0; k < K; ++k) acc = __dadd_rn(acc, __dmul_rn(f[k], v[k]));
+    if (!ok) acc = NAN;
+    if (e < D) grad[p * D + e] = acc;
+    else hess[p * D * D + (e - D)] = acc;
+    if (e == 0 && llh0) {
+        double l = NAN;
+        if (ok) {
+            const double* J = jafs + (int64_t)slot[p] * M * 7;
+            double lj[7];
+            for (int i = 0; i < 7; ++i) lj[i] = log_class(J, i, unfolded);
+            l = llk_of(jsfs + (int64_t)row[p] * 8, consts[row[p]], lj, unfolded);
+        }
+        llh0[p] = l;
+    }
+}
+
+hipError_t launch_curv_stencil(int64_t n_point, int D, const double* x, const double* split, const int32_t* bounds, int nb2,
+                               const int32_t* pulses, int np, double rel_step, double abs_step, int64_t cap, double* h, int32_t* point_status,
+                               int32_t* slot, double* c_split, double* c_params, int32_t* c_bounds, int32_t* c_pulses, hipStream_t stream) {
+    if (n_point <= 0) return hipSuccess;
+    const int M = 1 + 2 * D * D;
+    hipLaunchKernelGGL(curv_steps_kernel, dim3((unsigned)((n_point + 255) / 256)), dim3(256), 0, stream, n_point, D, x, rel_step, abs_step, h, point_status);
+    hipLaunchKernelGGL(curv_slots_kernel, dim3(1), dim3(256), 0, stream, n_point, point_status, slot);
+    if (cap > 0)
+        hipLaunchKernelGGL(curv_stencil_kernel, dim3((unsigned)((n_point * M + 255) / 256)), dim3(256), 0, stream, n_point, D, M, x, split, bounds, nb2,
+                           pulses, np, h, slot, cap, c_split, c_params, c_bounds, c_pulses);
+    return hipGetLastError();
+}
+
+hipError_t launch_curv_assemble(int64_t n_point, int D, int unfolded, const double* jafs, const int32_t* status, const double* h,
+                                const int32_t* slot, const int32_t* pre_status, double* dlog, double* d2log, int32_t* point_status,
+                                hipStream_t stream) {
+    if (n_point <= 0) return hipSuccess;
+    const int M = 1 + 2 * D * D;
+    const size_t lds = (size_t)M * (unfolded ? 7 : 4) * sizeof(double);           // at most 513 x 7 doubles (D = MISTI_MAX_PARAMS): 28 KB
+    const int64_t blocks = n_point < 65536 ? n_point : 65536;
+    hipLaunchKernelGGL(curv_assemble_kernel, dim3((unsigned)blocks), dim3(64), lds, stream, n_point, D, M, unfolded, jafs, status, h, slot, pre_status,
+                       dlog, d2log, point_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_curv_contract(int64_t n_point, int D, int unfolded, const double* dlog, const double* d2log, const int32_t* point_status,
+                                const int32_t* row, const double* jsfs, double* grad, double* hess, const double* jafs, const int32_t* slot,
+                                const double* consts, double* llh0, hipStream_t stream) {
+    if (n_point <= 0) return hipSuccess;
+    const int64_t threads = n_point * (D + D * D);
+    hipLaunchKernelGGL(curv_contract_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, n_point, D, unfolded, dlog, d2log,
+                       point_status, row, jsfs, grad, hess, jafs, slot, 1 + 2 * D * D, consts, llh0);
     return hipGetLastError();
 }
 

@@ -30,7 +30,7 @@ import numpy as np
 from . import _lib
 from ._lib import CPFIT, SMOOTH, TRUE_EPS, UNFOLDED, MistiError, STATUS_TEXT
 
-__all__ = ["Engine", "MigrationInference", "ModelError", "BatchResult"]
+__all__ = ["Engine", "MigrationInference", "ModelError", "BatchResult", "CurvatureResult"]
 
 
 class ModelError(SystemExit):
@@ -56,6 +56,17 @@ class BatchResult:
     @property
     def fraction_failed(self):
         return float((self.status != 0).mean()) if self.status.size else 0.0
+
+
+class CurvatureResult:
+    """Outputs of ``Engine.curvature``: per point ``llh0[P]`` (the centre's log-likelihood against its row), ``grad[P][D]`` and
+    ``hess[P][D][D]`` of that row's log-likelihood, ``dlog[P][D][7]`` (the derivatives of the class logs: the score covariance over
+    bootstrap rows is ``dlog Cov(d) dlog^T``), the steps ``h[P][D]`` and ``status[P]`` (0, 7 = no two-sided stencil at this point, or
+    the engine's status of the first stencil candidate without a value; every other output of such a point is NaN)."""
+    __slots__ = ("llh0", "grad", "hess", "dlog", "h", "status")
+
+    def __init__(self, llh0, grad, hess, dlog, h, status):
+        self.llh0, self.grad, self.hess, self.dlog, self.h, self.status = llh0, grad, hess, dlog, h, status
 
 
 def _f64(a, shape=None):
@@ -261,6 +272,41 @@ class Engine:
         v = lambda p: C.c_void_p(int(p)) if p else None
         _lib.check(self._lib.misti_scan_profile_dev(self._ctx, int(n_cand), v(d_jafs), v(d_status), v(d_group), int(n_group), int(n_rep), v(d_jsfs),
                                                     v(d_prof_llk), v(d_prof_best)))
+
+    def curvature(self, x, split_times, rows, table, band_bounds=None, pulse_times=None, rel_step=1e-2, abs_step=0.0, batch_limit=0):
+        """``misti_curvature``: gradient and Hessian of the log-likelihood at every point ``x[P][n_param]`` (split ``split_times[p]``
+        held fixed, row ``rows[p]`` of ``table[n_rep][8]``, optionally the point's own ``band_bounds[P][n_band][2]`` and
+        ``pulse_times[P][n_pulse]``) by central differences of the class logs over ``optimize.curvature_stencil``'s
+        ``1 + 2 n_param^2`` candidates per point - laid out on the device, evaluated through the batch path in batches of at most
+        ``batch_limit`` candidates (0: the library's choice; whole points only), assembled and contracted there.  ``rel_step`` /
+        ``abs_step``: ``h_i = max(rel_step |x_i|, abs_step)``; the default 1e-2 is an unmeasured choice.  A point with
+        ``x_i - h_i < 0`` gets status 7 and is not evaluated.  Returns a ``CurvatureResult``; ``optimize.observed_covariance`` /
+        ``sandwich_covariance`` / ``standard_errors`` take it from there."""
+        D = self.n_param
+        xs = _f64(x, (-1, D)) if D else _f64(x)
+        P = xs.shape[0] if D else 0
+        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        st = _f64(np.broadcast_to(np.asarray(split_times, dtype=np.float64), (P,)))
+        r_of = i32(np.broadcast_to(np.asarray(rows), (P,)), (P,))
+        tab = _f64(table, (-1, 8))
+        bb = i32(band_bounds, (P, self.n_band, 2)) if band_bounds is not None and self.n_band else None
+        pt = i32(pulse_times, (P, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
+        llh0, grad, hess, dlog = np.empty(P), np.empty((P, D)), np.empty((P, D, D)), np.empty((P, D, 7))
+        status = np.empty(P, dtype=np.int32)
+        _lib.check(self._lib.misti_curvature(self._ctx, P, ptr(xs), ptr(st), ptr(r_of), ptr(bb), ptr(pt), tab.shape[0], ptr(tab),
+                                             float(rel_step), float(abs_step), int(batch_limit), ptr(llh0), ptr(grad), ptr(hess), ptr(dlog), ptr(status)))
+        h = np.maximum(float(rel_step) * np.abs(xs), float(abs_step))             # curv_steps_kernel's two operations
+        return CurvatureResult(llh0, grad, hess, dlog, h, status)
+
+    def curvature_assemble_dev(self, n_point, d_jafs, d_status, d_h, d_rows, n_rep, d_jsfs, d_dlog=0, d_d2log=0, d_grad=0, d_hess=0, d_point_status=0):
+        """``misti_curvature_assemble_dev``: ``dlog[P][D][7]``, ``d2log[P][D][D][7]`` and the point statuses from stencil spectra
+        ``d_jafs[P][M][7]`` (``d_status[P][M]`` or 0: all OK) and steps ``d_h[P][D]``, and with ``d_rows[P]`` (int32) the contraction
+        ``grad[P][D]`` / ``hess[P][D][D]`` with each point's row of ``d_jsfs[n_rep][8]`` - ``optimize.curvature_from_spectra`` and
+        ``curvature_contract`` on the device (raw device addresses; asynchronous)."""
+        v = lambda p: C.c_void_p(int(p)) if p else None
+        _lib.check(self._lib.misti_curvature_assemble_dev(self._ctx, int(n_point), v(d_jafs), v(d_status), v(d_h), v(d_rows), int(n_rep), v(d_jsfs),
+                                                          v(d_dlog), v(d_d2log), v(d_grad), v(d_hess), v(d_point_status)))
 
     def sync(self):
         _lib.check(self._lib.misti_sync(self._ctx))

@@ -709,3 +709,211 @@ def sweep_interval(llh, values, x=None):
         if x is not None:
             out["data_x"] = np.asarray(x)[0, idx[0]]
     return out
+
+
+# ---- curvature at a fitted point: Hessians, observed information, the sandwich covariance ---------------------------------------------
+# For a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta) (MigrationInference.py:600-609 of the
+# reference; S the class spectrum).  Gradient and Hessian of EVERY row are therefore contractions of the row's class counts with the
+# first and second derivatives of L_k = log S_k, which do not depend on the data; the derivatives of log S are what is differenced,
+# not the llk values themselves: those are ~1e6 x log S (the counts), and their differences would carry the counts' rounding.
+# The two functions below ARE the rule of misti_curvature / misti_curvature_assemble_dev (include/misti_hip.h): the kernels perform
+# the same floating-point operations in the same order.
+CURV_BOUNDARY = 7         # MISTI_CURV_BOUNDARY
+CURV_NUMERIC = 5          # MISTI_NUMERIC
+CURV_REL_STEP = 1e-2      # default relative step: an UNMEASURED choice (no study of truncation against the engine's noise yet)
+
+
+def curvature_size(D):
+    """Stencil candidates of a point of D parameters: the centre, 2 D single steps, 4 per pair."""
+    return 1 + 2 * int(D) * int(D)
+
+
+def curvature_stencil(x, rel_step=CURV_REL_STEP, abs_step=0.0):
+    """The stencil of ``misti_curvature``.  ``x`` is ``[P][D]`` (or ``[D]``: one point).  Steps ``h_i = max(rel_step |x_i|, abs_step)``;
+    ``M = 1 + 2 D^2`` points per stencil: 0 the centre; ``1 + 2i`` is ``+h_i``, ``2 + 2i`` is ``-h_i``; for the pairs ``i < j`` in
+    lexicographic order, of rank q, ``1 + 2D + 4q + (0, 1, 2, 3)`` are ``(+h_i, +h_j)``, ``(+h_i, -h_j)``, ``(-h_i, +h_j)``,
+    ``(-h_i, -h_j)``.  A point with some ``x_i - h_i < 0`` (or ``h_i == 0``: a rate of 0 under a purely relative step) is a BOUNDARY
+    point: it has no two-sided stencil, and the engine evaluates none of its stencil points (they are laid out here all the same).
+    Returns ``(points[P][M][D], h[P][D], boundary[P] bool)``."""
+    x = np.atleast_2d(np.asarray(x, dtype=np.float64))
+    rel_step, abs_step = float(rel_step), float(abs_step)
+    if not (np.isfinite(rel_step) and np.isfinite(abs_step) and rel_step >= 0 and abs_step >= 0 and (rel_step > 0 or abs_step > 0)):
+        raise ValueError("rel_step and abs_step must be finite and not negative, and one of them positive")
+    if not np.isfinite(x).all():
+        raise ValueError("x must be finite")
+    P, D = x.shape
+    if D < 1:
+        raise ValueError("a point needs at least one parameter")
+    h = np.maximum(rel_step * np.abs(x), abs_step)
+    boundary = ((x - h < 0) | (h == 0)).any(axis=1)
+    pts = np.repeat(x[:, None, :], curvature_size(D), axis=1)
+    up, down = x + h, x - h
+    for i in range(D):
+        pts[:, 1 + 2 * i, i] = up[:, i]
+        pts[:, 2 + 2 * i, i] = down[:, i]
+    q = 0
+    for i in range(D):
+        for j in range(i + 1, D):
+            c = 1 + 2 * D + 4 * q
+            for w, (si, sj) in enumerate(((up, up), (up, down), (down, up), (down, down))):
+                pts[:, c + w, i] = si[:, i]
+                pts[:, c + w, j] = sj[:, j]
+            q += 1
+    return pts, h, boundary
+
+
+def _class_values(jafs, unfolded):
+    """The class values the likelihood takes the logs of: all 7, or folded 0+6, 1+5, 2+4 and 3 (``engine._classes``)."""
+    j = np.asarray(jafs, dtype=np.float64)
+    if unfolded:
+        return j
+    return np.stack([j[..., 0] + j[..., 6], j[..., 1] + j[..., 5], j[..., 2] + j[..., 4], j[..., 3]], axis=-1)
+
+
+def curvature_from_spectra(jafs, status, h, unfolded):
+    """Derivatives of ``L_k = log S_k`` from the spectra of a stencil: ``jafs[P][M][7]``, ``status[P][M]`` (None: all 0), ``h[P][D]``.
+
+        dL_k/dx_i        = (L_k(+i) - L_k(-i)) / (2 h_i)
+        d2L_k/dx_i^2     = ((L_k(+i) - 2 L_k(0)) + L_k(-i)) / (h_i h_i)
+        d2L_k/dx_i dx_j  = (((L_k(++) - L_k(+-)) - L_k(-+)) + L_k(--)) / ((4 h_i) h_j)     one value for both triangles
+
+    (the brackets are the order of the floating-point operations).  Folded models use classes 0..3 and leave entries 4..6 at 0.  A
+    stencil candidate has no value if its status is not 0 or one of its class values is not positive and finite; the point's status
+    is then that of the FIRST such candidate in stencil order (5, MISTI_NUMERIC, where that candidate's status was 0) and all its
+    derivatives are NaN.  Returns ``(dlog[P][D][7], d2log[P][D][D][7], point_status[P] int32)``."""
+    jafs = np.asarray(jafs, dtype=np.float64)
+    h = np.atleast_2d(np.asarray(h, dtype=np.float64))
+    P, D = h.shape
+    M = curvature_size(D)
+    jafs = jafs.reshape(P, M, 7)
+    st = np.zeros((P, M), dtype=np.int32) if status is None else np.asarray(status, dtype=np.int32).reshape(P, M)
+    S = _class_values(jafs, unfolded)
+    K = S.shape[-1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        bad = (st != 0) | ~((S > 0) & np.isfinite(S)).all(axis=2)
+        L = np.log(S)
+    point_status = np.zeros(P, dtype=np.int32)
+    for p in np.where(bad.any(axis=1))[0]:
+        m = int(np.argmax(bad[p]))
+        point_status[p] = st[p, m] if st[p, m] != 0 else CURV_NUMERIC
+    dlog = np.zeros((P, D, 7))
+    d2log = np.zeros((P, D, D, 7))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        q = 0
+        for i in range(D):
+            hi = h[:, i, None]
+            lp, lm = L[:, 1 + 2 * i], L[:, 2 + 2 * i]
+            dlog[:, i, :K] = (lp - lm) / (2.0 * hi)
+            d2log[:, i, i, :K] = ((lp - 2.0 * L[:, 0]) + lm) / (hi * hi)
+            for j in range(i + 1, D):
+                c = 1 + 2 * D + 4 * q
+                v = (((L[:, c] - L[:, c + 1]) - L[:, c + 2]) + L[:, c + 3]) / ((4.0 * hi) * h[:, j, None])
+                d2log[:, i, j, :K] = v
+                d2log[:, j, i, :K] = v
+                q += 1
+    dlog[point_status != 0] = np.nan
+    d2log[point_status != 0] = np.nan
+    return dlog, d2log, point_status
+
+
+def class_counts(table, unfolded):
+    """``[R][7]`` class counts of the rows of a replicate table ``[R][8]`` as the replicate epilogue forms them (folded: d0+d6,
+    d1+d5, d2+d4, d3, then zeros)."""
+    d = np.asarray(table, dtype=np.float64).reshape(-1, 8)[:, 1:]
+    if unfolded:
+        return d.copy()
+    f = np.zeros_like(d)
+    f[:, 0], f[:, 1], f[:, 2], f[:, 3] = d[:, 0] + d[:, 6], d[:, 1] + d[:, 5], d[:, 2] + d[:, 4], d[:, 3]
+    return f
+
+
+def curvature_contract(dlog, d2log, table, rows, unfolded):
+    """``grad[P][D] = sum_k d_k dlog[.][k]`` and ``hess[P][D][D] = sum_k d_k d2log[.][k]`` for row ``rows[p]`` of ``table[R][8]``: the sum
+    over the classes in ascending order from 0.0, every product and every sum rounded on its own (what ``curv_contract_kernel`` does)."""
+    dlog, d2log = np.asarray(dlog, dtype=np.float64), np.asarray(d2log, dtype=np.float64)
+    f = class_counts(table, unfolded)[np.asarray(rows, dtype=np.int64).reshape(-1)]
+    grad = np.zeros(dlog.shape[:2])
+    hess = np.zeros(d2log.shape[:3])
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(7 if unfolded else 4):
+            grad = grad + f[:, k, None] * dlog[:, :, k]
+            hess = hess + f[:, k, None, None] * d2log[:, :, :, k]
+    return grad, hess
+
+
+def observed_covariance(hess):
+    """Inverse of the observed information, ``inv(-H)``, per point of ``hess[P][D][D]`` (or one ``[D][D]``).  Where ``-H`` is not
+    positive definite (an eigenvalue that is not positive, or not finite) the point sits on a saddle, a boundary or a flat
+    direction - the "runaway" rates of DESIGN.md section 2 - and has no such covariance: NaN, and the point is flagged.  For a
+    COMPOSITE likelihood this is not the covariance of the estimate (``sandwich_covariance`` is); it is its curvature.
+    Returns dict(cov[P][D][D], ok[P] bool, cond[P]: largest / smallest eigenvalue of -H (inf or NaN where not positive definite),
+    eigenvalues[P][D] of -H ascending)."""
+    H = np.asarray(hess, dtype=np.float64)
+    H = H.reshape((-1,) + H.shape[-2:])
+    P, D = H.shape[0], H.shape[1]
+    cov = np.full((P, D, D), np.nan)
+    ok = np.zeros(P, dtype=bool)
+    cond = np.full(P, np.nan)
+    eig = np.full((P, D), np.nan)
+    for p in range(P):
+        if not np.isfinite(H[p]).all():
+            continue
+        info = -0.5 * (H[p] + H[p].T)
+        w = np.linalg.eigvalsh(info)
+        eig[p] = w
+        if w[0] > 0:
+            ok[p] = True
+            cond[p] = w[-1] / w[0]
+            cov[p] = np.linalg.inv(info)
+        else:
+            cond[p] = np.inf
+    return dict(cov=cov, ok=ok, cond=cond, eigenvalues=eig)
+
+
+def score_covariance(dlog, table, rows=slice(1, None), unfolded=False):
+    """``A C A^T`` per point: the covariance of the score over bootstrap rows, with ``A = dlog[P][D][7]`` and ``C`` the sample
+    covariance (``ddof = 1``) of the class counts over ``table[rows]`` - by default every row but row 0, which in a ``-bs`` file is the
+    data (the sum of the chunks), not a resample.  Needs at least two rows."""
+    A = np.asarray(dlog, dtype=np.float64)
+    A = A.reshape((-1,) + A.shape[-2:])
+    f = class_counts(np.asarray(table, dtype=np.float64).reshape(-1, 8)[rows], unfolded)
+    if f.shape[0] < 2:
+        raise ValueError("the score covariance needs at least two bootstrap rows (got %d)" % f.shape[0])
+    Cm = np.atleast_2d(np.cov(f, rowvar=False, ddof=1))
+    return np.einsum("pik,kl,pjl->pij", A, Cm, A)
+
+
+def sandwich_covariance(hess, dlog, table, rows=slice(1, None), unfolded=False):
+    """The sandwich (Godambe) covariance ``H^-1 (A C A^T) H^-1`` per point of ``hess[P][D][D]``, ``dlog[P][D][7]``: what a composite
+    likelihood - linked sites treated as independent - reports in the place of ``inv(-H)``; the middle is ``score_covariance`` over
+    the bootstrap rows of ``table``, computed on the host.  The bootstrap rows must be resamples of the SAME size as the row the
+    Hessian was taken against (a ``-bs`` file's are).  NaN where ``H`` is singular or not finite.  Returns ``cov[P][D][D]``."""
+    H = np.asarray(hess, dtype=np.float64)
+    H = H.reshape((-1,) + H.shape[-2:])
+    J = score_covariance(dlog, table, rows, unfolded)
+    out = np.full(H.shape, np.nan)
+    for p in range(H.shape[0]):
+        if not (np.isfinite(H[p]).all() and np.isfinite(J[p]).all()):
+            continue
+        try:
+            Hi = np.linalg.inv(H[p])
+        except np.linalg.LinAlgError:
+            continue
+        out[p] = Hi @ J[p] @ Hi.T
+    return out
+
+
+def standard_errors(cov):
+    """Square roots of the diagonal of ``cov[...][D][D]``; NaN where an entry is negative or NaN."""
+    c = np.asarray(cov, dtype=np.float64)
+    d = np.diagonal(c, axis1=-2, axis2=-1)
+    with np.errstate(invalid="ignore"):
+        return np.sqrt(np.where(d >= 0, d, np.nan))
+
+
+def correlation(cov):
+    """The correlation matrix of ``cov[...][D][D]`` (NaN where a variance is not positive)."""
+    c = np.asarray(cov, dtype=np.float64)
+    se = standard_errors(c)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return c / (se[..., :, None] * se[..., None, :])
