@@ -445,6 +445,45 @@ int misti_basinhopping_split(misti_ctx* ctx, int64_t n_start, const double* star
                              double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                              double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
 
+/* ---- the box: SciPy's bounds= on the batched searches -------------------------------------------- */
+/* The general form of the search, with box constraints: start s is
+ *     scipy.optimize.minimize(f, starts[s], method='Nelder-Mead', bounds=Bounds(box_lo, box_hi), options=dict(xatol, fatol, maxiter))
+ * on this engine's objective, bit for bit (SciPy 1.15.3, _minimize_neldermead): the start is clipped to the box; the 5 % / 0.00025
+ * simplex is built from the clipped start, a vertex beyond an upper bound is reflected into the interior (2 hi - x) and the simplex
+ * clipped; every reflection, expansion, contraction and shrunk vertex is clipped - numpy.clip per coordinate - before the objective
+ * sees it.  Without a box the only limit of a search is the engine's refusal of a point (a negative rate, a split off the grid: +inf);
+ * with one, rates can be capped, a fitted split kept inside a range, and a coordinate held fixed (lo == hi).  The word "bounds" is
+ * taken (band bounds per start), hence "box".
+ *   split_times  [n_start], or NULL             set: a split per start and N = n_param coordinates (misti_nm_solve_pulses' search);
+ *                                               NULL: the split is the LAST of N = n_param + 1 coordinates (misti_nm_solve_split's
+ *                                               search) and is clipped like any other
+ *   starts       [n_start][N]                   a start outside its box is no error: it is clipped (SciPy only warns)
+ *   rows, n_rep, jsfs, band_bounds, pulse_times as misti_nm_solve_pulses / misti_nm_solve_split
+ *   n_box        1 or n_start                   one box for every start, or a box per start
+ *   box_lo, box_hi  [n_box][N]                  -inf / +inf: no bound on that side; lo == hi: the coordinate is held fixed
+ *   xatol .. status                             as misti_nm_solve; x lies inside the box
+ * A box of (-inf, +inf) throughout returns the bytes of misti_nm_solve_pulses / misti_nm_solve_split.
+ * MISTI_E_ARG, before anything touches the device: what the search without a box refuses, n_box neither 1 nor n_start, a NULL box
+ * pointer, a NaN bound, or a lower bound greater than its upper bound (the message names the box and the coordinate; SciPy raises
+ * ValueError there).  Synchronisation and statistics as misti_nm_solve_rows. */
+int misti_nm_solve_box(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                       int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
+                       int64_t n_box, const double* box_lo, const double* box_hi,
+                       double xatol, double fatol, int32_t maxiter,
+                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
+
+/* Basin hopping around the boxed search: scipy.optimize.basinhopping(..., minimizer_kwargs=dict(method='Nelder-Mead',
+ * bounds=Bounds(box_lo, box_hi))) per start.  As in SciPy the random displacement itself is not clipped - a trial point may leave the
+ * box - and the minimisation that starts from it clips it.  The search's arguments as misti_nm_solve_box, the hops' as
+ * misti_basinhopping_rows (uniforms [n_start][niter][N + 1]); results, errors and statistics as misti_basinhopping_rows /
+ * misti_basinhopping_split plus the box's own argument errors. */
+int misti_basinhopping_box(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                           int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
+                           int64_t n_box, const double* box_lo, const double* box_hi,
+                           int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
+                           double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
+                           double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
+
 /* Work counters of the last misti_nm_solve on this context: [0] iterations issued, [1] batch slots over all iterations
  * (live starts plus the slack of the two-iterations-old count that sizes the batches; x (2 + n_param) = candidates
  * handed to the engine after the initial simplices). */

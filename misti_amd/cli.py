@@ -38,6 +38,11 @@ and the GNU-parallel recipe of ``README.md:110-115``):
     --hop-step S              with --hops (refused without): the initial step size of the random displacement (default 0.5; the split
                               in grid-index units)
     --hop-seed K              with --hops (refused without): search j of a row draws from numpy.random.default_rng([K, j]) (default 0)
+    --box K LO HI             with --grid-solve, --fit-st or --polish, with or without --hops; repeatable: every search runs inside a box -
+                              SciPy's Nelder-Mead with bounds= (misti_nm_solve_box / misti_basinhopping_box): LO <= parameter K <= HI, K the
+                              index of an optimised parameter as --grid-mi K names it, or `st` for the fitted split of --fit-st.  inf and
+                              -inf are accepted, LO = HI holds the coordinate fixed, a coordinate without a --box is unbounded; a start
+                              outside the box is clipped into it.  Refused anywhere else, and `st` without --fit-st
     --top K                   with --grid-st and/or --grid-mi (K = 1 ... 8): grid mode evaluates WITHOUT replicates and reduces on the device
                               (misti_scan_best_dev) - the [candidates x rows] likelihood table is never made; per row its K best
                               candidates are printed (one line each, grid mode's format: K lines per row in place of one per
@@ -143,6 +148,13 @@ def build_parser():
                    help="with --fit-st / --grid-solve: basin hopping with N hops (T = 0.5, SciPy's minimiser defaults; -tol does not apply) in place of the local search")
     p.add_argument("--hop-step", type=float, default=None, metavar="S", help="with --hops: initial step size of the random displacement (default 0.5)")
     p.add_argument("--hop-seed", type=int, default=None, metavar="K", help="with --hops: seed of the searches' generators (default 0)")
+    p.add_argument("--box", nargs=3, action="append", default=[], metavar=("K", "LO", "HI"),
+                   help="with --grid-solve / --fit-st / --polish: keep optimised parameter K (or `st`: the fitted split of --fit-st) within [LO, HI] "
+                        "in every search (SciPy's bounds=; inf / -inf accepted); repeatable")
+    # `--box K -inf HI`: argparse takes an argument that starts with `-` for an option unless it looks like a negative number (and no
+    # option of this parser does); -inf is one
+    import re
+    p._negative_number_matcher = re.compile(r"^-\d+$|^-\d*\.\d+$|^-inf$")
     p.add_argument("--top", type=int, default=None, metavar="K",
                    help="grid mode (--grid-st / --grid-mi): keep the K best candidates per row (1 ... 8), reduced on the device without the table")
     p.add_argument("--polish", action="store_true",
@@ -270,6 +282,53 @@ def _hop_step_seed(a):
 def _hops_text(res, *at):
     """What follows a result line under --hops: the accepted hops and the failed minimisations of the search it reports."""
     return " \thops accepted = %d \tfailed minimisations = %d" % (int(res["accepted"][at]), int(res["failures"][at]))
+
+
+def box_error(a):
+    """Why ``--box`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if not a.box:
+        return None
+    if not (a.grid_solve or a.fit_st or a.polish):
+        return "--box constrains the searches of --grid-solve, --fit-st or --polish: give one of them"
+    if a.sweep or a.sweep_pu:
+        return "--box constrains the searches of ONE model: --sweep / --sweep-pu are not offered with it"
+    k = sum(1 for el in a.mi if int(el[4])) + sum(1 for el in a.pu if int(el[3]))
+    seen = set()
+    for name, lo, hi in a.box:
+        if name == "st":
+            if not a.fit_st:
+                return "--box st bounds the FITTED split: it needs --fit-st (--grid-st scans the splits it is given)"
+        elif not name.isdigit() or int(name) >= k:
+            return "--box %s: no such coordinate - K is the index of an optimised parameter (0 ... %d here) or st" % (name, k - 1)
+        if name in seen:
+            return "--box %s is given twice" % name
+        seen.add(name)
+        try:
+            lo, hi = float(lo), float(hi)
+        except ValueError:
+            return "--box %s %s %s: LO and HI are numbers (inf and -inf are accepted)" % (name, lo, hi)
+        if lo != lo or hi != hi:
+            return "--box %s: a bound is NaN" % name
+        if lo > hi:
+            return "--box %s: the lower bound %g is greater than the upper bound %g" % (name, lo, hi)
+    return None
+
+
+def _box(a, k):
+    """The ``(lo, hi)`` of the --box options over the k optimised parameters - and, under --fit-st, the split as one coordinate more -
+    or None without a --box; a coordinate that no --box names is unbounded."""
+    if not a.box:
+        return None
+    N = k + (1 if a.fit_st else 0)
+    lo, hi = np.full(N, -np.inf), np.full(N, np.inf)
+    for name, l, h in a.box:
+        i = k if name == "st" else int(name)
+        lo[i], hi[i] = float(l), float(h)
+    return lo, hi
+
+
+def _box_text(a):
+    return "box: " + ", ".join("%s in [%g, %g]" % (name, float(l), float(h)) for name, l, h in a.box)
 
 
 def top_error(a):
@@ -465,7 +524,7 @@ def grid_top(a, inp, rows):
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
         if a.polish:
-            pol = scan_polish(e, split, params, data, a.top, tol=a.tol, maxiter=1000)
+            pol = scan_polish(e, split, params, data, a.top, tol=a.tol, maxiter=1000, box=_box(a, k))
             best, best_llk, status = pol["best"], pol["best_llk"], pol["scan_status"]
         else:
             best, best_llk, status = scan_best(e, split, params, data, a.top)
@@ -498,6 +557,8 @@ def grid_top(a, inp, rows):
                 continue
             st = float(pol["split"][r])
             print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, pol["x"][r], pol["llh"][r]))
+        if a.box:
+            print("polish:", _box_text(a))
         print("polish: %d searches in one batched search (%d rows x at most %d listed candidates); %d rows ended on the iteration cap"
               % (pol["searches"]["cand"].size, R, a.top, int((pol["status"] == 2).sum())))
     print("Evaluated %d candidates x %d replicates in %.3f s (%.0f llk evals/s); %.1f%% without a value"
@@ -582,9 +643,9 @@ def grid_solve(a, inp, rows):
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
         if a.hops:
-            prof = bootstrap_profile_global(e, splits, data, starts, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step)
+            prof = bootstrap_profile_global(e, splits, data, starts, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
-            prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000)
+            prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000, box=_box(a, k))
         if a.se:
             # one stencil per printed fit, all of them in one call: row outermost, split innermost, as the lines
             R_, P_ = data.shape[0], len(splits)
@@ -612,6 +673,8 @@ def grid_solve(a, inp, rows):
         print("grid-solve: bootstrap best splitT mean =", iv["mean"], "97.5%% t-interval = [%r, %r]" % tuple(float(v) for v in iv["interval"]),
               "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
     n = prof["llh"].size
+    if a.box:
+        print("grid-solve:", _box_text(a))
     if a.hops:
         print("grid-solve: basin hopping with %d hops, step %g, seed %d" % (a.hops, hop_step, hop_seed))
         print("grid-solve: %d pairs x %d starts in one global search, %.3f s; %d pairs with a failed minimisation, %d without a value"
@@ -634,9 +697,9 @@ def fit_st(a, inp, rows):
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
         if a.hops:
-            fit = split_fit_global(e, data, starts, splits, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step)
+            fit = split_fit_global(e, data, starts, splits, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
-            fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000)
+            fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000, box=_box(a, k))
     dt = time.time() - t0
     for r in range(data.shape[0]):
         st = float(fit["split"][r])
@@ -653,6 +716,8 @@ def fit_st(a, inp, rows):
         else:
             print("fit-st: bootstrap fitted splitT mean =", iv["mean"], "95%% t-interval = [%r, %r]" % iv["interval"],
                   "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
+    if a.box:
+        print("fit-st:", _box_text(a))
     if a.hops:
         print("fit-st: basin hopping with %d hops, step %g, seed %d" % (a.hops, hop_step, hop_seed))
         print("fit-st: %d rows x %d (start, initial split) pairs in one global search, %.3f s; %d rows with a failed minimisation, %d without a value"
@@ -786,7 +851,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a)
+    why = se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2

@@ -1267,6 +1267,9 @@ struct NmSearch {
     double *x, *llh;
     int32_t *nit, *nfev, *status;
     const NmHops* hops = nullptr;    // basin hopping around the search; NULL: the search alone
+    bool box = false;                // misti_nm_solve_box / misti_basinhopping_box: SciPy's bounds=Bounds(box_lo, box_hi) on every minimisation
+    int64_t n_box = 0;               // 1: one box for every start; n_start: a box per start
+    const double *box_lo = nullptr, *box_hi = nullptr;      // [n_box][N]
 };
 
 // The arguments of every search, and of basin hopping around one, checked before the first HIP call, in one order: what does not
@@ -1305,12 +1308,23 @@ int nm_check(const misti_ctx* c, const NmSearch& q, int& N, bool& whole) {
     for (int64_t s = 0; fit_split && s < q.n_start; ++s)
         for (int k = 0; k < N; ++k)
             if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
+    // the box: lo == hi holds a coordinate fixed, +-inf leaves a side open, and a start outside its box is clipped (SciPy only warns)
+    if (q.box) {
+        if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld starts)", (long long)q.n_box, (long long)q.n_start);
+        if (!q.box_lo || !q.box_hi) return fail(MISTI_E_ARG, "box_lo / box_hi is NULL");
+        for (int64_t b = 0; b < q.n_box; ++b)
+            for (int k = 0; k < N; ++k) {
+                const double lo = q.box_lo[b * N + k], hi = q.box_hi[b * N + k];
+                if (lo != lo || hi != hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is NaN", (long long)b, k);
+                if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
+            }
+    }
     return 0;
 }
 
 // The device state of a checked search with n_start >= 1: the minimiser's state, behind it what each start hands its points on the rows
 // path (split, row, bounds, pulse times; one of each per slot of every batch; the compact parameter array of a fitted split; the
-// table), behind that whatever `extra` takes - still the same two allocations.  Uploads the caller's arrays, issues llh_const over
+// table), the box arrays of a boxed search, behind that whatever `extra` takes - still the same two allocations.  Uploads the caller's arrays, issues llh_const over
 // the table and clears the context's work counters.  A path that is not taken allocates and writes nothing: without bounds nothing
 // of the bounds path, and so on.
 template <class Extra>
@@ -1329,6 +1343,8 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
     misti::NmState& st = w.st;
     double *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
     int32_t *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
+    const size_t NX = q.box ? (size_t)q.n_box * (size_t)N : 0;                  // doubles per box array
+    double *d_lo = nullptr, *d_hi = nullptr;
     // rows path: what each start hands its points, then one of it per slot of every batch
     auto rows_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
         if (rows_path) {
@@ -1341,6 +1357,7 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
             if (NB2) { d_bounds = i.take(S * NB2); nm_per_slot(w, &NmBatch::bnd, i, NB2); }
             if (NP) { d_pulses = i.take(S * NP); nm_per_slot(w, &NmBatch::put, i, NP); }
         }
+        if (NX) { d_lo = f.take(NX); d_hi = f.take(NX); }
         extra(f, i);
     };
     if (int r = nm_prepare(c, q.n_start, N, w, rows_layout)) return r;
@@ -1348,6 +1365,7 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
     st.split_of = d_split; st.row_of = d_rowof;
     st.bounds_of = d_bounds; st.nb2 = (int)NB2;
     st.pulses_of = d_pulses; st.np = (int)NP;
+    st.box_lo = d_lo; st.box_hi = d_hi; st.box_per_start = q.box && q.n_box != 1 ? 1 : 0;
     w.table = d_table; w.consts = d_consts; w.whole = whole;
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(w.d_starts, q.starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
@@ -1356,6 +1374,10 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
     if (rows_path) HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
     if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NX) {
+        HIP_TRY(hipMemcpyAsync(d_lo, q.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+        HIP_TRY(hipMemcpyAsync(d_hi, q.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+    }
     if (rows_path) {
         HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
         HIP_TRY(misti::launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));      // once per call, every row
@@ -1436,6 +1458,17 @@ int bh_impl(misti_ctx* c, NmSearch q, const NmHops& h) {
     return bh_run(c, q, N, whole);
 }
 
+// The general form of the search: a split per start (split_times set) or the split as the last coordinate (NULL), rows, bounds and
+// pulse times per start, and a box.
+NmSearch box_search(int64_t n_start, const double* starts, const double* split_times, const int32_t* rows, int64_t n_rep, const double* jsfs,
+                    const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_box, const double* box_lo, const double* box_hi,
+                    double xatol, double fatol, int32_t maxiter, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    NmSearch q{n_start, starts, split_times ? NmSearch::SPLIT_PER_START : NmSearch::SPLIT_FITTED, 0.0, split_times, rows, n_rep, jsfs,
+               band_bounds, pulse_times, xatol, fatol, maxiter, x, llh, nit, nfev, status};
+    q.box = true; q.n_box = n_box; q.box_lo = box_lo; q.box_hi = box_hi;
+    return q;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1510,6 +1543,25 @@ int misti_basinhopping_split(misti_ctx* c, int64_t n_start, const double* starts
                              double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
     return bh_impl(c, {n_start, starts, NmSearch::SPLIT_FITTED, 0.0, nullptr, rows, n_rep, jsfs, band_bounds, pulse_times,
                        xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr},
+                   {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
+}
+
+int misti_nm_solve_box(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                       int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
+                       int64_t n_box, const double* box_lo, const double* box_hi, double xatol, double fatol, int32_t maxiter,
+                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    return nm_solve_impl(c, box_search(n_start, starts, split_times, rows, n_rep, jsfs, band_bounds, pulse_times, n_box, box_lo, box_hi,
+                                       xatol, fatol, maxiter, x, llh, nit, nfev, status));
+}
+
+int misti_basinhopping_box(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                           int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
+                           int64_t n_box, const double* box_lo, const double* box_hi,
+                           int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
+                           double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
+                           double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
+    return bh_impl(c, box_search(n_start, starts, split_times, rows, n_rep, jsfs, band_bounds, pulse_times, n_box, box_lo, box_hi,
+                                 xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr),
                    {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
 }
 

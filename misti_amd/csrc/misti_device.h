@@ -141,6 +141,12 @@ struct NmState {
                             // N - 1 are the model's parameters - every point laid out for a batch leaves its split in the slot's split and its
                             // parameters in the batch's compact `par`, which the engine reads instead of the points.  0: nothing of this is
                             // written or read
+    // The box (misti_nm_solve_box / misti_basinhopping_box): SciPy's Nelder-Mead with bounds=Bounds(lo, hi).  Every point the search lays
+    // out is clipped to [lo, hi] per coordinate before put_point() reads it, a fitted split (coordinate N - 1) like any other.  Both NULL:
+    // no box - nothing of it is allocated, read or written, and a kernel branches on it by one wave-uniform pointer test.
+    const double* box_lo;   // [N], or [S][N] with box_per_start; NULL: no box
+    const double* box_hi;   // the same shape; NULL together with box_lo
+    int box_per_start;      // 1: start s has its own box, rows s of the two arrays; 0: one box for every start
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)

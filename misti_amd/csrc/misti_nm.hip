@@ -19,6 +19,14 @@
 // (which keeps its old value) - the simplex is sorted and the loop ends with warnflag 1.  Restated here per evaluation
 // (NM_CUT, NmState::shrunk): nfev never exceeds maxfev.
 //
+// The box (NmState::box_lo / box_hi; misti_nm_solve_box, misti_basinhopping_box): SciPy's bounds=Bounds(lo, hi) for this method is a rule
+// of a dozen lines, restated here point by point - x0 is clipped, the initial simplex is built from the clipped x0, a vertex beyond its
+// upper bound is reflected into the interior (2 ub - x, one rounding after the product) and the simplex clipped, and every reflection,
+// expansion, contraction and shrunk vertex is clipped (np.clip per coordinate: box_clip) before put_point() hands it on; with the split
+// as a coordinate the split is clipped like any other.  The speculative path clips the same expressions: same bits.  Basin hopping's
+// displacement is not clipped (SciPy's is not): the minimisation that starts from the trial point clips it.  Without a box both pointers
+// are NULL and every kernel does what it did, behind one wave-uniform pointer test per point.
+//
 // Arithmetic: SciPy evaluates  (1 + rho) * xbar - rho * worst  etc. with one rounding per operation.  The library is
 // built with -ffp-contract=fast (which ignores contraction pragmas, and HIP's __dmul_rn / __dadd_rn are plain operators
 // in a header), so every product that feeds a sum passes through rn(): an empty asm the compiler cannot see through,
@@ -40,6 +48,20 @@ __device__ __forceinline__ double objective(double llk) { return (llk == llk && 
 
 // the value as rounded so far: opaque to the optimiser, so a product passed through it is never contracted into an fma
 __device__ __forceinline__ double rn(double v) { __asm__ volatile("" : "+v"(v)); return v; }
+
+// numpy.clip(x, lo, hi) = minimum(maximum(x, lo), hi) on one coordinate: a NaN passes through (fmin / fmax would drop it), an x equal to
+// a bound comes back as the bound itself (a zero takes the bound's sign, as NumPy's does), +-inf bounds never bind.  lo <= hi, neither NaN.
+__device__ __forceinline__ double box_clip(double x, double lo, double hi) {
+    double t = x > lo ? x : lo;
+    t = t < hi ? t : hi;
+    return x != x ? x : t;
+}
+// Where start s's box begins in box_lo / box_hi, and coordinate k of one of its points clipped to it (SciPy: np.clip(x, lower_bound,
+// upper_bound) on every point before func sees it); without a box the value as it is.
+__device__ __forceinline__ int64_t box_of(const NmState& st, int64_t s) { return st.box_per_start ? s * st.N : 0; }
+__device__ __forceinline__ double boxed(const NmState& st, int64_t o, int k, double v) {
+    return st.box_lo ? box_clip(v, st.box_lo[o + k], st.box_hi[o + k]) : v;
+}
 
 // a*x - b*y with a rounding after each product and after the difference (NumPy elementwise semantics)
 __device__ __forceinline__ double lin2(double a, double x, double b, double y) { return rn(a * x) - rn(b * y); }
@@ -133,7 +155,8 @@ __device__ void next_reflection(const NmState& st, int64_t s) {
     st.idx_next[slot] = (int32_t)s;
     const NmBatch& b = st.b[NM_B_REFLECT];
     double* p1 = b.pts + (int64_t)slot * N;
-    for (int k = 0; k < N; ++k) p1[k] = lin2(1.0 + NM_RHO, centroid(x, N, k), NM_RHO, x[N * N + k]);     // xr
+    const int64_t o = box_of(st, s);
+    for (int k = 0; k < N; ++k) p1[k] = boxed(st, o, k, lin2(1.0 + NM_RHO, centroid(x, N, k), NM_RHO, x[N * N + k]));     // xr
     put_point(st, b, slot, s, p1);
 }
 
@@ -146,10 +169,16 @@ void nm_init_kernel(NmState st, const double* __restrict__ starts) {
     if (s >= st.S) return;
     const int N = st.N, V = N + 1;
     double* x = st.sim + s * (int64_t)V * N;
+    const int64_t o = box_of(st, s);
     for (int i = 0; i < V; ++i) {
         for (int k = 0; k < N; ++k) {
-            double y = starts[s * N + k];
+            double y = boxed(st, o, k, starts[s * N + k]);             // SciPy clips x0 before it builds the simplex
             if (i == k + 1) y = (y != 0.0) ? rn((1.0 + NM_NONZDELT) * y) : NM_ZDELT;
+            if (st.box_lo) {                                           // a vertex beyond the upper bound is reflected into the interior
+                const double hi = st.box_hi[o + k];                    // (sim > ub -> 2 ub - sim), then the whole simplex is clipped
+                if (y > hi) y = rn(2.0 * hi) - y;
+                y = box_clip(y, st.box_lo[o + k], hi);
+            }
             x[i * N + k] = y;
         }
         put_point(st, st.b[NM_B_INIT], s * V + i, s, x + i * N);
@@ -185,18 +214,19 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     const double fxr = objective(llk1[i]);
     st.fxr[s] = fxr;
     st.nfev[s] += 1;
+    const int64_t o = box_of(st, s);
     int kind;
     if (fxr < f[0]) {
         kind = NM_EXPAND;
-        for (int k = 0; k < N; ++k) p2[k] = lin2(1.0 + NM_RHO * NM_CHI, centroid(x, N, k), NM_RHO * NM_CHI, x[N * N + k]);
+        for (int k = 0; k < N; ++k) p2[k] = boxed(st, o, k, lin2(1.0 + NM_RHO * NM_CHI, centroid(x, N, k), NM_RHO * NM_CHI, x[N * N + k]));
     } else if (fxr < f[N - 1]) {
         kind = NM_REFLECT;                                  // fsim[-2]: accepted as it is
     } else if (fxr < f[N]) {
         kind = NM_CONTRACT;
-        for (int k = 0; k < N; ++k) p2[k] = lin2(1.0 + NM_PSI * NM_RHO, centroid(x, N, k), NM_PSI * NM_RHO, x[N * N + k]);
+        for (int k = 0; k < N; ++k) p2[k] = boxed(st, o, k, lin2(1.0 + NM_PSI * NM_RHO, centroid(x, N, k), NM_PSI * NM_RHO, x[N * N + k]));
     } else {
         kind = NM_INSIDE;                                   // (1 - psi) * xbar + psi * sim[-1]
-        for (int k = 0; k < N; ++k) p2[k] = rn((1.0 - NM_PSI) * centroid(x, N, k)) + rn(NM_PSI * x[N * N + k]);
+        for (int k = 0; k < N; ++k) p2[k] = boxed(st, o, k, rn((1.0 - NM_PSI) * centroid(x, N, k)) + rn(NM_PSI * x[N * N + k]));
     }
     if (kind != NM_REFLECT && (int64_t)st.nfev[s] >= st.maxfun) kind = NM_CUT;      // the second point's evaluation is refused
     st.kind[s] = kind;
@@ -237,9 +267,10 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
         const int64_t left = st.maxfun - (int64_t)st.nfev[s];
         n_eval = left >= N ? N : (left > 0 ? (int)left : 0);
         const int n_move = n_eval < N ? n_eval + 1 : N;      // SciPy moves sim[j] before the call that is refused
+        const int64_t o = box_of(st, s);
         for (int j = 1; j <= n_move; ++j)
             for (int k = 0; k < N; ++k) {
-                const double v = x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k]));   // sim[0] + sigma (sim[j] - sim[0])
+                const double v = boxed(st, o, k, x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k])));   // sim[0] + sigma (sim[j] - sim[0]), clipped
                 x[j * N + k] = v;
                 if (j <= n_eval) p3[(j - 1) * N + k] = v;
             }
@@ -285,13 +316,14 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
     const int64_t s = st.idx_cur[i];
     const double* x = st.sim + s * (int64_t)V * N;
     const double* p1 = st.b[NM_B_REFLECT].pts + i * N;
+    const int64_t o = box_of(st, s);
     for (int k = 0; k < N; ++k) {
         const double xb = centroid(x, N, k), w = x[N * N + k];
-        pt[0 * N + k] = p1[k];                                                            // xr (next_reflection)
-        pt[1 * N + k] = lin2(1.0 + NM_RHO * NM_CHI, xb, NM_RHO * NM_CHI, w);              // xe
-        pt[2 * N + k] = lin2(1.0 + NM_PSI * NM_RHO, xb, NM_PSI * NM_RHO, w);              // xc
-        pt[3 * N + k] = rn((1.0 - NM_PSI) * xb) + rn(NM_PSI * w);                         // xcc
-        for (int j = 1; j < V; ++j) pt[(3 + j) * N + k] = x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k]));   // shrunk vertex j
+        pt[0 * N + k] = p1[k];                                                            // xr (next_reflection: clipped there)
+        pt[1 * N + k] = boxed(st, o, k, lin2(1.0 + NM_RHO * NM_CHI, xb, NM_RHO * NM_CHI, w));              // xe
+        pt[2 * N + k] = boxed(st, o, k, lin2(1.0 + NM_PSI * NM_RHO, xb, NM_PSI * NM_RHO, w));              // xc
+        pt[3 * N + k] = boxed(st, o, k, rn((1.0 - NM_PSI) * xb) + rn(NM_PSI * w));                         // xcc
+        for (int j = 1; j < V; ++j) pt[(3 + j) * N + k] = boxed(st, o, k, x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k])));   // shrunk vertex j
     }
     for (int j = 0; j < K; ++j) put_point(st, b, i * K + j, s, pt + j * N);
 }

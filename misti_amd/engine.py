@@ -76,6 +76,15 @@ def _f64(a, shape=None):
     return a
 
 
+def _box_args(box, N):
+    """``(lo, hi)``, each ``[N]`` or ``[S][N]``, as the ``n_box, box_lo, box_hi`` arguments of ``misti_nm_solve_box``."""
+    lo, hi = (_f64(a) for a in box)
+    if lo.shape != hi.shape or lo.ndim not in (1, 2) or lo.shape[-1] != N:
+        raise ValueError("box: lo and hi must both be [%d] or [S][%d] (got %s and %s)" % (N, N, lo.shape, hi.shape))
+    lo, hi = lo.reshape(-1, N), hi.reshape(-1, N)
+    return [lo.shape[0], lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)]
+
+
 def _model_struct(times, lh, bands, pulses, n_param, cpfit, true_eps, smooth, unfolded, sample_date, mixture_th):
     """(misti_model_t, objects that must stay alive while it is used) from the constructor arguments Engine / Lanes share."""
     times = _f64(times)
@@ -324,20 +333,23 @@ class Engine:
                  "misti_nm_solve_rows": ("split_times", "rows", "table"),
                  "misti_nm_solve_bounds": ("split_times", "rows", "band_bounds", "table"),
                  "misti_nm_solve_pulses": ("split_times", "rows", "band_bounds", "pulse_times", "table"),
-                 "misti_nm_solve_split": ("rows", "band_bounds", "pulse_times", "table")}
+                 "misti_nm_solve_split": ("rows", "band_bounds", "pulse_times", "table"),
+                 "misti_nm_solve_box": ("split_times", "rows", "table", "band_bounds", "pulse_times", "box")}
 
     def _nm_search(self, symbol, starts, tol, maxiter, **given):
         """Every ``misti_nm_solve*``: shapes the inputs ``_NM_TAKES[symbol]`` names, allocates the results, calls ``symbol`` and returns
         the results with the work counters.  ``misti_nm_solve_split``'s starts carry the split as one coordinate more.  Band bounds and
         pulse times that are ``None``, or that the model has no band / pulse for, go as NULL."""
-        N = self.n_param + (1 if symbol == "misti_nm_solve_split" else 0)
+        fitted = symbol == "misti_nm_solve_split" or (symbol == "misti_nm_solve_box" and given["split_times"] is None)
+        N = self.n_param + (1 if fitted else 0)
         st = _f64(starts, (-1, N))
         S = st.shape[0]
         ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
         i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
         shaped = {"split_time": lambda v: [float(v)],
                   "jsfs_row": lambda v: [ptr(_f64(v, (8,)))],
-                  "split_times": lambda v: [ptr(_f64(v, (S,)))],
+                  "split_times": lambda v: [ptr(_f64(v, (S,)) if v is not None else None)],       # None: misti_nm_solve_box with a fitted split
+                  "box": lambda v: _box_args(v, N),
                   "rows": lambda v: [ptr(i32(v, (S,)))],
                   "band_bounds": lambda v: [ptr(i32(v, (S, self.n_band, 2)) if v is not None and self.n_band else None)],
                   "pulse_times": lambda v: [ptr(i32(v, (S, self.n_pulse)) if v is not None and self.n_pulse else None)],
@@ -397,6 +409,19 @@ class Engine:
         r["split"] = r["x"][:, -1].copy()
         return r
 
+    def nm_solve_box(self, starts, rows, table, box, split_times=None, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
+        """``misti_nm_solve_box``: the batched search with box constraints - start s is ``scipy.optimize.minimize(f, starts[s],
+        method='Nelder-Mead', bounds=Bounds(lo, hi))`` on the engine's objective, bit for bit.  ``box`` is ``(lo, hi)``, each ``[N]`` (one
+        box for every start) or ``[S][N]`` (a box per start); ``-inf`` / ``inf`` leave a side open, ``lo == hi`` holds a coordinate fixed, a
+        start outside its box is clipped.  ``split_times=None``: the split is the LAST coordinate, ``starts`` is ``[S][n_param + 1]``
+        (``nm_solve_split``'s search, the split clipped like any other coordinate); ``split_times`` given: a split per start,
+        ``starts`` is ``[S][n_param]`` (``nm_solve_pulses``' search).  ``optimize.box_initial_simplex`` / ``box_clip`` state the rule.
+        Returns what ``nm_solve_split`` returns (``split``: the fitted splits, or ``split_times`` themselves)."""
+        r = self._nm_search("misti_nm_solve_box", starts, tol, maxiter, split_times=split_times, rows=rows, table=table,
+                            band_bounds=band_bounds, pulse_times=pulse_times, box=box)
+        r["split"] = r["x"][:, -1].copy() if split_times is None else np.array(split_times, dtype=np.float64).reshape(-1)
+        return r
+
     def basinhopping(self, starts, split_time, jsfs_row, rngs, niter=100, T=0.5, stepsize=0.5, interval=50, target_accept_rate=0.5,
                      stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
         """``misti_basinhopping``: ``scipy.optimize.basinhopping(-JAFSLikelihood, x0, niter, T, stepsize,
@@ -421,10 +446,12 @@ class Engine:
         return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, iterations_issued=stats["iterations_issued"], slots=stats["slots"])
 
     def _bh_search(self, symbol, starts, rows, table, rngs, split_times, band_bounds, pulse_times, niter, T, stepsize, interval,
-                   target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev):
+                   target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev, box=None):
         """``misti_basinhopping_rows`` / ``misti_basinhopping_split``: shapes the inputs, draws the uniforms, calls ``symbol`` and returns
         the results with the work counters.  ``split_times`` is None for the split form, whose starts carry the split as one coordinate
-        more.  Band bounds and pulse times that are ``None``, or that the model has no band / pulse for, go as NULL."""
+        more.  Band bounds and pulse times that are ``None``, or that the model has no band / pulse for, go as NULL.
+        ``misti_basinhopping_box`` (``box`` given) takes the same search in its own order: the split times (or NULL), the rows, the table,
+        bounds and times, then the box."""
         N = self.n_param + (1 if split_times is None else 0)
         st = _f64(starts, (-1, N))
         S = st.shape[0]
@@ -439,7 +466,11 @@ class Engine:
         x = np.empty((S, N))
         llh = np.empty(S)
         nfev, failures, accepted = (np.empty(S, dtype=np.int32) for _ in range(3))
-        _lib.check(getattr(self._lib, symbol)(self._ctx, S, ptr(st), *per_start, ptr(r_of), ptr(bb), ptr(pt), tab.shape[0], ptr(tab),
+        if box is None:
+            search = [*per_start, ptr(r_of), ptr(bb), ptr(pt), tab.shape[0], ptr(tab)]
+        else:
+            search = [per_start[0] if per_start else None, ptr(r_of), tab.shape[0], ptr(tab), ptr(bb), ptr(pt), *_box_args(box, N)]
+        _lib.check(getattr(self._lib, symbol)(self._ctx, S, ptr(st), *search,
                                               int(niter), float(T), float(stepsize), int(interval), float(target_accept_rate),
                                               float(stepwise_factor), float(xatol), float(fatol),
                                               int(nm_maxiter if nm_maxiter is not None else 200 * N),
@@ -472,6 +503,19 @@ class Engine:
         r = self._bh_search("misti_basinhopping_split", starts, rows, table, rngs, None, band_bounds, pulse_times, niter, T, stepsize, interval,
                             target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev)
         r["split"] = r["x"][:, -1].copy()
+        return r
+
+    def basinhopping_box(self, starts, rows, table, rngs, box, split_times=None, band_bounds=None, pulse_times=None, niter=100, T=0.5,
+                         stepsize=0.5, interval=50, target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None,
+                         nm_maxfev=None):
+        """``misti_basinhopping_box``: basin hopping around the boxed search - start s is ``scipy.optimize.basinhopping(...,
+        minimizer_kwargs=dict(method='Nelder-Mead', bounds=Bounds(lo, hi)))``.  ``box`` and ``split_times`` as in ``nm_solve_box``; the
+        displacement is not clipped (SciPy's is not), the minimisation from the trial point clips it.  The other arguments as
+        ``basinhopping_split`` / ``basinhopping_rows``.  Returns what ``basinhopping_split`` returns."""
+        sp = None if split_times is None else np.asarray(split_times, dtype=np.float64)
+        r = self._bh_search("misti_basinhopping_box", starts, rows, table, rngs, sp, band_bounds, pulse_times, niter, T, stepsize, interval,
+                            target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev, box=box)
+        r["split"] = r["x"][:, -1].copy() if sp is None else sp.reshape(-1).copy()
         return r
 
     def enable_solver_trace(self, on=True):

@@ -40,6 +40,30 @@ def initial_simplex(x0):
     return sim
 
 
+def box_clip(x, lo, hi):
+    """A point, or an array of points, clipped to the box as SciPy's bounded Nelder-Mead clips every point it evaluates
+    (``np.clip(x, lower_bound, upper_bound)``): NaN passes through, an infinite bound never binds, ``lo == hi`` pins the coordinate.
+    What ``misti_nm_solve_box`` applies per coordinate on the device (``box_clip`` in ``misti_nm.hip``)."""
+    return np.clip(np.asarray(x, dtype=float), np.asarray(lo, dtype=float), np.asarray(hi, dtype=float))
+
+
+def box_initial_simplex(x0, lo, hi):
+    """[S, N] starts (or one ``[N]`` start) -> [S, N+1, N] (``[N+1, N]``) initial simplices as SciPy builds them under
+    ``bounds=Bounds(lo, hi)`` (``_minimize_neldermead``, SciPy 1.15.3): the start is clipped, the 5 % / 0.00025 simplex is built from the
+    clipped start, a vertex beyond its upper bound is reflected into the interior (``2 * hi - x``), and the simplex is clipped.
+    ``lo`` / ``hi``: ``[N]``, or ``[S, N]`` for a box per start.  The rule of ``nm_init_kernel`` under a box."""
+    x0 = np.asarray(x0, dtype=float)
+    one = x0.ndim == 1
+    x0 = np.atleast_2d(x0)
+    lo = np.broadcast_to(np.asarray(lo, dtype=float), x0.shape)[:, None, :]
+    hi = np.broadcast_to(np.asarray(hi, dtype=float), x0.shape)[:, None, :]
+    sim = initial_simplex(np.clip(x0, lo[:, 0], hi[:, 0]))
+    with np.errstate(invalid="ignore"):                   # 2 * inf - x where the mask is False anyway
+        sim = np.where(sim > hi, 2 * hi - sim, sim)
+    sim = np.clip(sim, lo, hi)
+    return sim[0] if one else sim
+
+
 def _sort(sim, fsim):
     order = np.argsort(fsim, axis=1)          # as SciPy: default argsort (insertion sort at these sizes)
     return np.take_along_axis(sim, order[:, :, None], axis=1), np.take_along_axis(fsim, order, axis=1)
@@ -335,12 +359,14 @@ def scan_best(engine, split, params, jsfs_rows, k=1, band_bounds=None, pulse_tim
     return best.cpu().numpy().astype(np.int64), best_llk.cpu().numpy(), status.cpu().numpy()
 
 
-def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
+def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000, box=None):
     """Scan, keep the ``k`` best candidates per replicate, polish those: ``scan_best``, then ONE batched search whose starts are the
     listed candidates - row r's j-th place is a start with that candidate's parameters, split, band bounds and pulse times against
     row r (row outermost, place innermost; a -1 place gives no start) - through ``misti_nm_solve_pulses`` / ``_bounds`` / ``_rows``,
     whichever the given arrays need.  Per row the best polished search is kept (``_best_start_profile``'s rule: the first maximum,
     NaN never wins).  Where ``--grid-solve`` searches from every (row, split, start) triple, this searches from ``k`` per row.
+    ``box``: ``(lo, hi)``, each ``[n_param]`` - the polish runs inside it (``misti_nm_solve_box``: SciPy's ``bounds=``); the scan is not
+    touched.
     Returns dict(best[R][k], best_llk[R][k], scan_status[n] (the scan's), x[R][n_param], split[R], llh[R], nit / nfev / status[R],
     place[R] (which place of the row's list was kept; a row without a start: -1, with x nan, llh -inf, status -1), searches (every
     search: row, place, cand, x, llh, nit, nfev, status), and the search's work counters)."""
@@ -360,6 +386,9 @@ def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_tim
     if cand.size == 0:
         res = dict(x=np.empty((0, N)), llh=np.empty(0), nit=np.empty(0, dtype=np.int32), nfev=np.empty(0, dtype=np.int32),
                    status=np.empty(0, dtype=np.int32), iterations_issued=0, slots=0, speculative_iterations=0)
+    elif box is not None:
+        res = engine.nm_solve_box(params[cand], r_of.astype(np.int32), rows, box, split_times=split[cand], band_bounds=bb, pulse_times=pt,
+                                  tol=tol, maxiter=maxiter)
     elif pt is not None:
         res = engine.nm_solve_pulses(params[cand], split[cand], r_of.astype(np.int32), rows, bb, pt, tol=tol, maxiter=maxiter)
     elif bb is not None:
@@ -497,14 +526,18 @@ def profile_interval(prof_llk, values, drop):
     return out
 
 
-def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter=1000):
+def bootstrap_profile(engine, split_values, jsfs_rows, starts, tol=1e-4, maxiter=1000, box=None):
     """The bootstrap profiles of the reference's ``test.bs`` scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
     -mi ...``: one ``MigrationInference.Solve`` per (replicate, split) pair, MigrationInference.py:718-733 of the reference) in ONE
     ``misti_nm_solve_rows`` call: every (row, split, start) triple is a start of the batched search.  ``jsfs_rows`` is ``[R][8]``,
     ``split_values`` ``[P]``, ``starts`` ``[Q][N]``.  Per (row, split) the best start is kept (ties: the lowest start index).
+    ``box``: ``(lo, hi)``, each ``[N]`` - every search runs inside it (``misti_nm_solve_box``: SciPy's ``bounds=``).
     Returns dict(x[R][P][N], llh[R][P], nit / nfev / status / start[R][P], and the search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_values, dtype=float).reshape(-1)
+    if box is not None:
+        return _best_start_profile(lambda r_of, p_of, st: engine.nm_solve_box(st, r_of, rows, box, split_times=splits[p_of], tol=tol, maxiter=maxiter),
+                                   rows.shape[0], splits.size, starts)
     return _best_start_profile(lambda r_of, p_of, st: engine.nm_solve_rows(st, splits[p_of], r_of, rows, tol=tol, maxiter=maxiter),
                                rows.shape[0], splits.size, starts)
 
@@ -537,14 +570,14 @@ def _hop_generators(seed, R, n):
     return [np.random.default_rng([int(seed), j]) for _ in range(R) for j in range(n)]
 
 
-def bootstrap_profile_global(engine, split_values, jsfs_rows, starts, seed=0, niter=100, T=0.5, stepsize=0.5, **hop_options):
+def bootstrap_profile_global(engine, split_values, jsfs_rows, starts, seed=0, niter=100, T=0.5, stepsize=0.5, box=None, **hop_options):
     """``bootstrap_profile`` with hops: per (row, split, start) triple the reference's global search - ``Solve(globalOpt=True)``,
     ``scipy.optimize.basinhopping(T=0.5, Nelder-Mead)``, MigrationInference.py:723-725 of the reference - instead of its local one, all
     triples in ONE ``misti_basinhopping_rows`` call.  Same triple layout (row outermost, start innermost) and the same best-start rule.
     The generator of search j is ``numpy.random.default_rng([seed, j])``, j = the search's index in the flattened (row, point, start)
     order taken WITHIN its row (``_hop_generators``), so a row's result does not depend on which other rows are in the call.
     ``hop_options``: ``interval``, ``target_accept_rate``, ``stepwise_factor``, ``xatol``, ``fatol``, ``nm_maxiter``, ``nm_maxfev`` of
-    ``Engine.basinhopping_rows`` (SciPy's defaults).
+    ``Engine.basinhopping_rows`` (SciPy's defaults).  ``box`` as in ``bootstrap_profile`` (``misti_basinhopping_box``).
     Returns dict(x[R][P][N], llh[R][P], nfev / failures / accepted / start[R][P], and the search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_values, dtype=float).reshape(-1)
@@ -552,6 +585,8 @@ def bootstrap_profile_global(engine, split_values, jsfs_rows, starts, seed=0, ni
 
     def search(r_of, p_of, st):
         gens = _hop_generators(seed, R, r_of.size // R)
+        if box is not None:
+            return engine.basinhopping_box(st, r_of, rows, gens, box, split_times=splits[p_of], niter=niter, T=T, stepsize=stepsize, **hop_options)
         return engine.basinhopping_rows(st, splits[p_of], r_of, rows, gens, niter=niter, T=T, stepsize=stepsize, **hop_options)
     return _best_start_profile(search, R, splits.size, starts, _HOP_RESULTS)
 
@@ -587,13 +622,14 @@ def bootstrap_profile_interval(llh, split_values, x=None):
     return out
 
 
-def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
+def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000, box=None):
     """The split time FITTED per row instead of scanned (the ``for st in A..Z`` loops of the reference's ``test.bs`` scripts and the
     arg-max over them): for every row of ``jsfs_rows`` (``[R][8]``) one search from every (start, initial split) pair - ``starts``
     ``[Q][n_param]`` (ignored for a model without an optimised parameter), ``split_starts`` ``[P]`` - with the split as the last
     coordinate of the simplex, all R x Q x P searches in ONE ``misti_nm_solve_split`` call (row outermost, initial split innermost).
     Per row the best search is kept (``_best_start_profile``'s rule: the first maximum, NaN never wins).  ``band_bounds``
     (``[n_band][2]``, end -1: the point's own split index) and ``pulse_times`` (``[n_pulse]``) apply to every search.
+    ``box``: ``(lo, hi)``, each ``[n_param + 1]``, the split last - every search runs inside it (``misti_nm_solve_box``).
     Returns dict(x[R][n_param + 1], split[R], llh[R], nit / nfev / status / start[R] (index into the (start, split) pairs), and the
     search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
@@ -605,8 +641,9 @@ def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_t
 
     def search(r_of, p_of, x0):
         bb, pt = tile(band_bounds, (1, -1, 2)), tile(pulse_times, (1, -1))
-        return engine.nm_solve_split(x0, r_of, rows, band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
-                                     pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0), tol=tol, maxiter=maxiter)
+        per = dict(band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
+                   pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0), tol=tol, maxiter=maxiter)
+        return engine.nm_solve_split(x0, r_of, rows, **per) if box is None else engine.nm_solve_box(x0, r_of, rows, box, **per)
     out = _best_start_profile(search, rows.shape[0], 1, pairs)
     out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
     out["split"] = out["x"][:, -1].copy()
@@ -614,14 +651,15 @@ def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_t
 
 
 def split_fit_global(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_times=None, seed=0, niter=100, T=0.5, stepsize=0.5,
-                     **hop_options):
+                     box=None, **hop_options):
     """``split_fit`` with hops: per row one basin-hopping search over (optimised parameters, split) from every (start, initial split)
     pair - the answer to an objective that is piecewise in the split, where a local simplex search stops at the first kink it meets -
     all R x Q x P searches in ONE ``misti_basinhopping_split`` call.  Same layout of the triples (row outermost, initial split
     innermost), same best-search rule (``_best_start_profile``).  The generator of search j is
     ``numpy.random.default_rng([seed, j])``, j = the search's index in the flattened (row, point, start) order taken WITHIN its row
     (``_hop_generators``), so a row's result does not depend on which other rows are in the call.  ``hop_options`` as
-    ``bootstrap_profile_global`` (``nm_maxiter`` / ``nm_maxfev`` default to ``200 x (n_param + 1)``).
+    ``bootstrap_profile_global`` (``nm_maxiter`` / ``nm_maxfev`` default to ``200 x (n_param + 1)``).  ``box`` as in ``split_fit``
+    (``misti_basinhopping_box``): a hop may leave the box, the minimisation from it is clipped back.
     Returns dict(x[R][n_param + 1], split[R], llh[R], nfev / failures / accepted / start[R], and the search's work counters);
     ``split_fit_interval`` takes ``split`` and ``llh`` unchanged."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
@@ -635,9 +673,10 @@ def split_fit_global(engine, jsfs_rows, starts, split_starts, band_bounds=None, 
     def search(r_of, p_of, x0):
         bb, pt = tile(band_bounds, (1, -1, 2)), tile(pulse_times, (1, -1))
         gens = _hop_generators(seed, R, r_of.size // R)
-        return engine.basinhopping_split(x0, r_of, rows, gens, band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
-                                         pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0),
-                                         niter=niter, T=T, stepsize=stepsize, **hop_options)
+        per = dict(band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
+                   pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0),
+                   niter=niter, T=T, stepsize=stepsize, **hop_options)
+        return engine.basinhopping_split(x0, r_of, rows, gens, **per) if box is None else engine.basinhopping_box(x0, r_of, rows, gens, box, **per)
     out = _best_start_profile(search, R, 1, pairs, _HOP_RESULTS)
     out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
     out["split"] = out["x"][:, -1].copy()
