@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CPFIT, SMOOTH, TRUE_EPS, UNFOLDED, MistiError, STATUS_TEXT
+from .optimize import fold_classes
 
 __all__ = ["Engine", "MigrationInference", "ModelError", "BatchResult", "CurvatureResult"]
 
@@ -799,7 +800,7 @@ def draw_uniforms(rngs, S, niter, N):
 
 def _classes(v, unfolded):
     """The spectrum classes the likelihood distinguishes: all 7, or folded pairs 0+6, 1+5, 2+4 and 3 (:217-227, :600-609)."""
-    return list(v) if unfolded else [v[0] + v[6], v[1] + v[5], v[2] + v[4], v[3]]
+    return fold_classes(v, unfolded)
 
 
 def _multinomial_const(counts, unfolded):

@@ -801,12 +801,19 @@ def curvature_stencil(x, rel_step=CURV_REL_STEP, abs_step=0.0):
     return pts, h, boundary
 
 
-def _class_values(jafs, unfolded):
-    """The class values the likelihood takes the logs of: all 7, or folded 0+6, 1+5, 2+4 and 3 (``engine._classes``)."""
-    j = np.asarray(jafs, dtype=np.float64)
+def fold_classes(v, unfolded, pad=False):
+    """The classes the likelihood distinguishes, as a list: all 7 of ``v``, or folded the sums 0+6, 1+5, 2+4 and 3 (``pad``: then three
+    zeros).  ``v`` is a sequence of seven values, or an array with the seven along its last axis - the one fold of the Python side, as
+    ``row_counts`` / ``class_value`` (misti_score.h) are of the device's."""
+    at = (lambda i: v[..., i]) if isinstance(v, np.ndarray) and v.ndim > 1 else (lambda i: v[i])
     if unfolded:
-        return j
-    return np.stack([j[..., 0] + j[..., 6], j[..., 1] + j[..., 5], j[..., 2] + j[..., 4], j[..., 3]], axis=-1)
+        return [at(i) for i in range(7)]
+    return [at(0) + at(6), at(1) + at(5), at(2) + at(4), at(3)] + ([np.zeros_like(at(3))] * 3 if pad else [])
+
+
+def _class_values(jafs, unfolded):
+    """The class values the likelihood takes the logs of: all 7, or folded 0+6, 1+5, 2+4 and 3."""
+    return np.stack(fold_classes(np.asarray(jafs, dtype=np.float64), unfolded), axis=-1)
 
 
 def curvature_from_spectra(jafs, status, h, unfolded):
@@ -859,11 +866,7 @@ def class_counts(table, unfolded):
     """``[R][7]`` class counts of the rows of a replicate table ``[R][8]`` as the replicate epilogue forms them (folded: d0+d6,
     d1+d5, d2+d4, d3, then zeros)."""
     d = np.asarray(table, dtype=np.float64).reshape(-1, 8)[:, 1:]
-    if unfolded:
-        return d.copy()
-    f = np.zeros_like(d)
-    f[:, 0], f[:, 1], f[:, 2], f[:, 3] = d[:, 0] + d[:, 6], d[:, 1] + d[:, 5], d[:, 2] + d[:, 4], d[:, 3]
-    return f
+    return np.stack(fold_classes(d, unfolded, pad=True), axis=-1)
 
 
 def curvature_contract(dlog, d2log, table, rows, unfolded):
