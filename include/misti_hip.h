@@ -270,6 +270,43 @@ int misti_scan_profile_dev(misti_ctx* ctx, int64_t n_cand, const double* d_jafs,
  * Copies n_cand doubles to HOST memory and synchronises the stream. */
 int misti_last_diag(misti_ctx* ctx, int64_t n_cand, double* max_rate_x_len);
 
+/* ---- block bootstrap: the replicate rows themselves --------------------------------- */
+/* Makes the rows every entry point above scores: n_rep block-bootstrap replicates of a chunked JSFS, one replicate per lane.  The
+ * reference makes them with migrationIO.BootstrapJAFS (migrationIO.py:506-524) once per replicate, under Python's Mersenne Twister:
+ * a SEQUENTIAL stream, where a row depends on how many were drawn before it.  The stream here is THE PROJECT'S OWN and is not the
+ * reference's: counter-based, so that replicate r is a function of (seed, r) alone - the same row whatever n_rep, first_rep, device
+ * or launch geometry.  The rule (optimize.block_bootstrap states it in NumPy; the device result is that, bit for bit):
+ *   - chunks[n_chunk][8], HOST memory: column 0 the chunk's length, columns 1..7 its class counts;
+ *   - genome = the lengths added in chunk order; seg = the running sum over the chunks of ((c1 + c2) + ... + c7);
+ *   - the stream of replicate r is numpy.random.Philox(key=[seed, r]): Philox4x64-10, counter 0 as NumPy starts it (NumPy advances
+ *     the counter before its first block: block b is the counter b + 1); draw j is element j of its random_raw stream;
+ *   - the chunk of a draw is the high 64 bits of the 128-bit product raw x n_chunk.  No rejection step, one raw value per draw: a
+ *     chunk's probability is within n_chunk / 2^64 of 1 / n_chunk (below 4e-15 relative at MISTI_BOOT_MAX_CHUNKS) - documented,
+ *     not corrected;
+ *   - a replicate starts at 0 and, while its column 0 is below genome, draws a chunk and adds the chunk's 8 columns to its own, each
+ *     column in draw order, one float64 addition per draw;
+ *   - with MISTI_BOOT_NORMALIZE (the reference's normalize=True) every one of the 8 entries is then multiplied by seg / seg_bs,
+ *     seg_bs = ((s1 + s2) + ... + s7) of the replicate: the division first, then 8 products.
+ * Writes replicates first_rep ... first_rep + n_rep - 1 to d_rows[0 ... n_rep) (a table made in two calls equals the table made in
+ * one) and, with d_draws, the number of chunks each drew.  d_rows is an ordinary row buffer: misti_eval_batch_dev, misti_llk_dev,
+ * misti_scan_best_dev and misti_scan_profile_dev take it as d_jsfs.  Row 0 of a bootstrap table (the column sums of all chunks) is
+ * the caller's: Engine.bootstrap_table puts it in front.
+ * Checked on the host before anything touches the device (and before ctx is looked at): MISTI_E_ARG for n_chunk < 1, a negative
+ * n_rep or first_rep, unknown flag bits, a NULL chunks / d_rows with work to do, a non-finite entry, a negative count, or a chunk
+ * length that is not > 0 (which is what bounds the loop); MISTI_E_LIMIT for n_chunk > MISTI_BOOT_MAX_CHUNKS, n_rep > INT32_MAX, or
+ * ceil(genome / smallest length) > MISTI_BOOT_MAX_DRAWS - the most draws a replicate can need; the kernel's loop carries the same
+ * bound.  n_rep == 0 writes nothing.  Asynchronous on the context's stream (the chunk table is copied before the call returns). */
+#define MISTI_BOOT_NORMALIZE   1u
+#define MISTI_BOOT_MAX_CHUNKS  65535
+#define MISTI_BOOT_MAX_DRAWS   (1 << 24)
+int misti_bootstrap_rows_dev(misti_ctx* ctx, int64_t n_chunk, const double* chunks /* HOST [n_chunk][8] */,
+                             uint64_t seed, int64_t first_rep, int64_t n_rep, uint32_t flags,
+                             double* d_rows /* DEVICE [n_rep][8] */, int32_t* d_draws /* DEVICE [n_rep] or NULL */);
+/* The first n chunk indices replicate `rep` draws from a table of n_chunk chunks, to HOST memory: pure host code - no context, no
+ * device - through the very generator functions the kernel calls (misti_boot.h).  MISTI_E_ARG for a negative rep or n, n_chunk < 1
+ * or a NULL idx with n > 0; MISTI_E_LIMIT for n_chunk > MISTI_BOOT_MAX_CHUNKS or n > MISTI_BOOT_MAX_DRAWS. */
+int misti_bootstrap_draws(uint64_t seed, int64_t rep, int64_t n_chunk, int64_t n, int64_t* idx /* HOST [n] */);
+
 /* ---- batched optimiser ------------------------------------------------------------ */
 /* Replaces MigrationInference.Solve (MigrationInference.py:718-733: SciPy Nelder-Mead on -JAFSLikelihood, xatol =
  * fatol = tol, maxiter = 1000, started from the -mi / -pu initial values) for n_start starts at once - BASELINE

@@ -29,6 +29,7 @@ ABI_VERSION = 6
 TRACE_MAX_CAND, TRACE_MAX_ITER = 64, 200
 SCAN_MAX_BEST = 8
 SCAN_MAX_GROUPS = 65535
+BOOT_NORMALIZE, BOOT_MAX_CHUNKS, BOOT_MAX_DRAWS = 1, 65535, 1 << 24
 
 
 class Band(C.Structure):
@@ -109,6 +110,8 @@ SYMBOLS = {
     "misti_argmax_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_scan_best_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "misti_scan_profile_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_bootstrap_rows_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "misti_bootstrap_draws": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "misti_curvature_assemble_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_curvature": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,

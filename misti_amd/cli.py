@@ -17,6 +17,12 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               given split time follow each candidate's split
     --grid-mi K LO HI N       N log-spaced values for the K-th optimised parameter
     --all-bs                  evaluate every row of the JSFS file as a replicate
+    --bootstrap N             the rows of the JSFS file are CHUNKS (column 0 a chunk's length): N block-bootstrap replicates of them are drawn on
+                              the device (misti_bootstrap_rows_dev) and the 1 + N-row table - row 0 the sum of all chunks - replaces the rows
+                              before any mode sees them; implies --all-bs.  The stream is this project's own (Philox4x64-10 keyed by
+                              (--bs-seed K, replicate): replicate r is the same row whatever N, rank or device), NOT the reference's
+                              generateJSFS_bs.py, which draws from Python's Mersenne Twister.  --bs-normalize: the reference's normalize=True;
+                              --bootstrap-out FILE keeps the table as a #MiSTI_JSFS file (--all-bs on it repeats the run).  Not offered with -bs K
     --grid-solve              with --grid-st and/or --all-bs: for every (row, split) pair the reference's Solve from the
                               -mi/-pu initial values (the --grid-mi mesh points as starts: the best per pair), all pairs
                               in ONE batched search on the device; per pair the line MiSTI.py:240 prints (the test.bs
@@ -138,6 +144,12 @@ def build_parser():
     p.add_argument("--grid-mi", nargs=4, action="append", default=[], metavar=("K", "LO", "HI", "N"),
                    help="log-spaced values for optimised parameter K")
     p.add_argument("--all-bs", action="store_true", help="evaluate every JSFS row as a bootstrap replicate")
+    p.add_argument("--bootstrap", type=int, default=None, metavar="N",
+                   help="the JSFS rows are chunks: draw N block-bootstrap replicates of them on the device (the project's own counter-based stream, "
+                        "not the reference's Mersenne Twister) and evaluate the 1 + N-row table; implies --all-bs")
+    p.add_argument("--bs-seed", type=int, default=None, metavar="K", help="with --bootstrap: the seed of the replicates' streams, a uint64 (default 0)")
+    p.add_argument("--bs-normalize", action="store_true", help="with --bootstrap: scale every replicate to the data's number of segregating sites")
+    p.add_argument("--bootstrap-out", type=str, default=None, metavar="FILE", help="with --bootstrap: write the table that was drawn as a #MiSTI_JSFS file")
     p.add_argument("--gpus", type=int, default=1, help="grid mode: start this many ranks, one per GPU (replaces `parallel -j N ./MiSTI.py ...`)")
     p.add_argument("--devices", type=str, default="", help="grid mode: comma-separated device list evaluated from this one process (misti_create_multi)")
     p.add_argument("--grid-solve", action="store_true",
@@ -172,6 +184,37 @@ def build_parser():
     p.add_argument("--sweep-pu", nargs="+", action="append", default=[], metavar=("NAME", "V"),
                    help="a sweep variable of the pulses: {NAME} in the time field or in the fraction field of -pu")
     return p
+
+
+def bootstrap_error(a):
+    """Why ``--bootstrap`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.bootstrap is None:
+        if a.bs_seed is not None or a.bs_normalize or a.bootstrap_out is not None:
+            return "--bs-seed / --bs-normalize / --bootstrap-out belong to --bootstrap N: give --bootstrap N"
+        return None
+    if a.bootstrap < 1:
+        return "--bootstrap N: the number of replicates must be at least 1 (got %d)" % a.bootstrap
+    if a.bsMode != -1:
+        return "--bootstrap replaces the rows of the file by the table it draws and evaluates every row: -bs K is not offered with it"
+    if a.bs_seed is not None and not 0 <= a.bs_seed < 1 << 64:
+        return "--bs-seed is a uint64: 0 ... 2^64 - 1 (got %d)" % a.bs_seed
+    return None
+
+
+def bootstrap_rows(a, inp, rows, pop1=None, pop2=None):
+    """The table of ``--bootstrap N``: the file's rows are the chunks, the device draws the replicates (Engine.bootstrap_table on this
+    process's device - a rank of --gpus N regenerates the same table from (seed, r)); with --bootstrap-out the table is written through
+    the JSFS writer (by rank 0)."""
+    from .dist import env_rank
+    rank, local, world = env_rank()
+    device = local if world > 1 else (int(a.devices.split(",")[0]) if a.devices else a.device)
+    with Engine(inp.times, inp.lambdas, device=device) as e:
+        table = e.bootstrap_table(rows, a.bootstrap, seed=a.bs_seed or 0, normalize=a.bs_normalize)
+    table = table.tolist()
+    if a.bootstrap_out is not None and rank == 0:
+        with open(os.path.join(a.wd, a.bootstrap_out), "w") as fw:
+            fw.write(mio.format_jsfs(table, pop1, pop2))
+    return table
 
 
 def se_error(a):
@@ -851,10 +894,12 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
+    why = bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
+    if a.bootstrap is not None:
+        a.all_bs = True                                     # every mode below sees a bootstrap table
     # the two ways of using several GPUs exclude each other: N ranks that each opened the whole device list would run N x D contexts
     if a.gpus > 1 and a.devices:
         print("--gpus (one rank per GPU) and --devices (a device list in one process) exclude each other", file=sys.stderr)
@@ -888,6 +933,13 @@ def main(argv=None):
     print("pop2\t", f2)
     print("jafs\t", fj)
     rows, pop1, pop2 = mio.read_jsfs(fj)
+    if a.bootstrap is not None:
+        from .optimize import check_chunks
+        try:
+            check_chunks(rows)                              # what the ABI would refuse, said before the GPU is touched
+        except ValueError as e:
+            print("--bootstrap: %s: %s" % (fj, e), file=sys.stderr)
+            return 2
     if a.bsMode == -1:
         inputSFS = [sum(r[i] for r in rows) for i in range(8)]
     else:
@@ -896,6 +948,11 @@ def main(argv=None):
           "order as populations appear in the joint allele frequency spectrum.")
     fout = os.path.join(a.wd, a.fout) if a.fout else ""
     inp = mio.read_psmc(f1, f2, a.sdate, a.rd, units)
+    if a.bootstrap is not None:
+        n_chunk = len(rows)
+        rows = bootstrap_rows(a, inp, rows, pop1, pop2)
+        print("Bootstrap: %d replicates of %d chunks drawn on the device (seed %d%s): the project's own stream, not the reference's"
+              % (a.bootstrap, n_chunk, a.bs_seed or 0, ", normalized" if a.bs_normalize else ""))
     if a.sweep or a.sweep_pu:
         return sweep_solve(a, inp, rows) if a.grid_solve else sweep_eval(a, inp, rows)
     inp.divergenceTime = a.st

@@ -106,6 +106,31 @@ def _model_struct(times, lh, bands, pulses, n_param, cpfit, true_eps, smooth, un
     return m, (times, lh, b_arr, p_arr)
 
 
+def _bootstrap_rows(lib, ctx, device, chunks, n, seed, first, normalize, draws):
+    """``misti_bootstrap_rows_dev`` on context ``ctx`` of ``device`` into fresh torch tensors: ``rows[n][8]`` float64 and, with ``draws``,
+    the draw counts ``[n]`` int32 (else None).  Waits for the context's stream: the tensors are ready for any stream."""
+    import torch
+    c = _f64(chunks, (-1, 8))
+    n = int(n)
+    if n < 0:
+        raise ValueError("bootstrap: the number of replicates must not be negative (got %d)" % n)
+    dev = torch.device("cuda", int(device))
+    rows = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev) if draws else None
+    v = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    torch.cuda.current_stream(dev).synchronize()      # the engine's stream is non-blocking: whatever last used this memory must have finished
+    _lib.check(lib.misti_bootstrap_rows_dev(ctx, c.shape[0], c.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed)), int(first), n,
+                                            _lib.BOOT_NORMALIZE if normalize else 0, v(rows), v(count)))
+    _lib.check(lib.misti_sync(ctx))
+    return rows, count
+
+
+def _bootstrap_table(rows_dev, chunks):
+    """Row 0 - the column sums of all chunks, added in chunk order - in front of the replicates a device made: ``io.bootstrap_table``'s layout."""
+    from .optimize import _in_order_sum
+    return np.vstack([_in_order_sum(_f64(chunks, (-1, 8)))[None, :], rows_dev.cpu().numpy()])
+
+
 class Engine:
     """One model on one GPU (``misti_create`` ... ``misti_destroy``).
 
@@ -186,6 +211,8 @@ class Engine:
         par = None
         if P:
             par = _f64(params, (n, P))
+        if hasattr(jsfs, "data_ptr"):              # a device tensor (bootstrap_rows_dev): this is the host-buffer form
+            jsfs = jsfs.cpu().numpy()
         rows = _f64(jsfs, (-1, 8)) if jsfs is not None and len(jsfs) else np.zeros((0, 8))
         R = rows.shape[0]
         llk = np.empty((n, R))
@@ -282,6 +309,21 @@ class Engine:
         v = lambda p: C.c_void_p(int(p)) if p else None
         _lib.check(self._lib.misti_scan_profile_dev(self._ctx, int(n_cand), v(d_jafs), v(d_status), v(d_group), int(n_group), int(n_rep), v(d_jsfs),
                                                     v(d_prof_llk), v(d_prof_best)))
+
+    def bootstrap_rows_dev(self, chunks, n, seed=0, first=0, normalize=False, draws=False):
+        """``misti_bootstrap_rows_dev``: block-bootstrap replicates ``first ... first + n - 1`` of the chunk table ``chunks[n_chunk][8]``
+        (host; column 0 the chunk's length, columns 1..7 its class counts) made on this device - a torch tensor ``[n][8]`` float64 and,
+        with ``draws``, the number of chunks each replicate drew (``[n]`` int32).  The rule is ``optimize.block_bootstrap``, bit for bit:
+        the project's own counter-based stream (replicate r depends on ``(seed, r)`` alone), not the reference's Mersenne Twister.
+        ``normalize``: the reference's ``normalize=True``.  The tensor is an ordinary row buffer: ``evaluate`` takes it as it is, and
+        ``evaluate_dev``, ``llk_dev``, ``scan_best_dev`` and ``scan_profile_dev`` its ``data_ptr()``.  Returns when the rows are there."""
+        rows, count = _bootstrap_rows(self._lib, self._ctx, self.device, chunks, n, seed, first, normalize, draws)
+        return (rows, count) if draws else rows
+
+    def bootstrap_table(self, chunks, n, seed=0, normalize=False):
+        """The table ``io.bootstrap_table`` lays out, its replicates made by ``bootstrap_rows_dev``: a host ``ndarray [1 + n][8]``, row 0 the
+        column sums of all chunks (added in chunk order), row 1 + r replicate r - ``optimize.block_bootstrap_table``, bit for bit."""
+        return _bootstrap_table(self.bootstrap_rows_dev(chunks, n, seed=seed, normalize=normalize), chunks)
 
     def curvature(self, x, split_times, rows, table, band_bounds=None, pulse_times=None, rel_step=1e-2, abs_step=0.0, batch_limit=0):
         """``misti_curvature``: gradient and Hessian of the log-likelihood at every point ``x[P][n_param]`` (split ``split_times[p]``
@@ -723,6 +765,14 @@ class MultiEngine:
         _lib.check(self._lib.misti_multi_eval_batch(self._m, n, ptr(split), ptr(par), ptr(bb), R, ptr(rows), ptr(llk), ptr(jafs),
                                                     ptr(lc), ptr(pr), ptr(status)))
         return BatchResult(llk, jafs, status, lc, pr, None)
+
+    def bootstrap_table(self, chunks, n, seed=0, normalize=False):
+        """``Engine.bootstrap_table``, made on the first context of the list: a replicate depends on ``(seed, r)`` alone, so one device
+        makes the host rows and every context is handed the same ones."""
+        ctx, dev = C.c_void_p(), C.c_int(0)
+        _lib.check(self._lib.misti_multi_context(self._m, 0, C.byref(ctx), C.byref(dev)))
+        rows, _ = _bootstrap_rows(self._lib, ctx, dev.value, chunks, n, seed, 0, normalize, False)
+        return _bootstrap_table(rows, chunks)
 
     def last_shards(self):
         """(candidates per context, chains per context) of the last ``evaluate``."""

@@ -959,3 +959,102 @@ def correlation(cov):
     se = standard_errors(c)
     with np.errstate(invalid="ignore", divide="ignore"):
         return c / (se[..., :, None] * se[..., None, :])
+
+
+# ------------------------------------------------------------------------------------------------ block bootstrap ----
+# The rule of misti_bootstrap_rows_dev stated on the host (include/misti_hip.h, "block bootstrap"): the device result is this, bit for
+# bit.  The stream is the project's own - counter-based, replicate r a function of (seed, r) alone - and NOT the reference's:
+# migrationIO.BootstrapJAFS draws from Python's Mersenne Twister, a sequential stream (io.bootstrap_jsfs / io.bootstrap_table keep that one).
+BOOT_MAX_CHUNKS, BOOT_MAX_DRAWS = 65535, 1 << 24
+
+
+def philox_draws(seed, rep, n_chunk, n):
+    """The first ``n`` chunk indices of replicate ``rep`` (``misti_bootstrap_draws``): draw j is element j of
+    ``numpy.random.Philox(key=[seed, rep]).random_raw`` - Philox4x64-10 from counter 0, which NumPy advances before its first block -
+    and its chunk the high 64 bits of the 128-bit product ``raw * n_chunk``.  No rejection step: a chunk's probability is within
+    ``n_chunk / 2**64`` of ``1 / n_chunk``.  ``seed`` is a uint64, ``1 <= n_chunk < 2**32``.  Returns int64 ``[n]``."""
+    n_chunk = int(n_chunk)
+    if not 1 <= n_chunk < 1 << 32 or int(rep) < 0 or int(n) < 0:
+        raise ValueError("philox_draws: n_chunk must be 1 ... 2**32 - 1, rep and n not negative")
+    raw = np.random.Philox(key=np.array([int(seed), int(rep)], dtype=np.uint64)).random_raw(int(n))
+    raw = np.atleast_1d(np.asarray(raw, dtype=np.uint64))
+    m, s32 = np.uint64(n_chunk), np.uint64(32)
+    hi, lo = raw >> s32, raw & np.uint64(0xFFFFFFFF)                  # raw m = hi m 2^32 + lo m, every term below 2^64
+    return ((hi * m + ((lo * m) >> s32)) >> s32).astype(np.int64)
+
+
+def _in_order_sum(a):
+    """The sum along axis 0 by plain additions in index order, from 0.0 (``np.sum`` adds pairwise)."""
+    a = np.asarray(a, dtype=np.float64)
+    return np.cumsum(np.concatenate([np.zeros((1,) + a.shape[1:]), a]), axis=0)[-1]
+
+
+def _seg_of(rows):
+    """``((c1 + c2) + ... + c7)`` of every row of ``rows[...][8]``."""
+    t = rows[..., 1] + rows[..., 2]
+    for k in range(3, 8):
+        t = t + rows[..., k]
+    return t
+
+
+def check_chunks(chunks):
+    """The chunk table as ``misti_bootstrap_rows_dev`` takes it - float64 ``[n_chunk][8]``, column 0 the chunk's length, columns 1..7
+    its class counts - with the checks the ABI makes before it touches the device, as a ``ValueError`` of one line: at least one
+    chunk and at most ``BOOT_MAX_CHUNKS``, every entry finite, every length > 0 (which bounds the loop), no negative count, and
+    ``ceil(genome / smallest length) <= BOOT_MAX_DRAWS``.  Returns ``(chunks, genome, seg)``: the lengths added in chunk order, and the
+    running sum over the chunks of ``((c1 + c2) + ... + c7)``."""
+    c = np.ascontiguousarray(chunks, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 8 or c.shape[0] < 1:
+        raise ValueError("the chunk table must be [n_chunk][8] with at least one chunk (got shape %s)" % (c.shape,))
+    if c.shape[0] > BOOT_MAX_CHUNKS:
+        raise ValueError("%d chunks, beyond the limit of %d" % (c.shape[0], BOOT_MAX_CHUNKS))
+    if not np.isfinite(c).all():
+        raise ValueError("chunk %d has an entry that is not finite" % int(np.argmax(~np.isfinite(c).all(axis=1))))
+    if not (c[:, 0] > 0).all():
+        raise ValueError("chunk %d has length %g: a chunk's length must be > 0" % (int(np.argmax(~(c[:, 0] > 0))), c[np.argmax(~(c[:, 0] > 0)), 0]))
+    if (c[:, 1:] < 0).any():
+        raise ValueError("chunk %d has a negative count" % int(np.argmax((c[:, 1:] < 0).any(axis=1))))
+    genome, seg = float(_in_order_sum(c[:, 0])), float(_in_order_sum(_seg_of(c)))
+    if not (np.isfinite(genome) and np.isfinite(seg)):
+        raise ValueError("the chunk lengths or counts do not sum to a finite number")
+    if not np.ceil(genome / c[:, 0].min()) <= BOOT_MAX_DRAWS:
+        raise ValueError("a replicate may need ceil(%g / %g) draws, beyond the limit of %d" % (genome, c[:, 0].min(), BOOT_MAX_DRAWS))
+    return c, genome, seg
+
+
+def block_bootstrap(chunks, n, seed=0, first=0, normalize=False, draws=False):
+    """The rule of ``misti_bootstrap_rows_dev`` on the host: replicates ``first ... first + n - 1`` of the chunk table (``check_chunks``),
+    float64 ``[n][8]`` - with ``draws`` also the number of chunks each drew (int32 ``[n]``).  Replicate r, as ``BootstrapJAFS`` builds
+    one: ``sfs = 0``; while ``sfs[0] < genome`` the next index of ``philox_draws(seed, r, n_chunk, ...)`` names a chunk and its 8
+    columns are added to ``sfs``, each column in draw order, one float64 addition per draw - nothing is summed in any other order (and,
+    as in the kernel, never more than ``BOOT_MAX_DRAWS`` draws: a table that passes the checks stays below).  ``normalize``: the
+    reference's ``normalize=True`` - all 8 entries times ``seg / seg_bs``, ``seg_bs = ((s1 + s2) + ... + s7)`` of the replicate, the
+    division first and then 8 products.  Replicate r depends on ``(seed, r)`` and the table alone, not on ``n`` or ``first``."""
+    c, genome, seg = check_chunks(chunks)
+    n, first, n_chunk = int(n), int(first), c.shape[0]
+    if n < 0 or first < 0:
+        raise ValueError("block_bootstrap: n and first must not be negative")
+    rows, count = np.empty((n, 8)), np.empty(n, dtype=np.int32)
+    guess = int(min(BOOT_MAX_DRAWS, np.ceil(genome / c[:, 0].mean()) + 8 * np.sqrt(n_chunk) + 16))
+    for i in range(n):
+        m = guess
+        while True:
+            idx = philox_draws(seed, first + i, n_chunk, m)
+            run = np.cumsum(np.concatenate([np.zeros((1, 8)), c[idx]]), axis=0)      # run[j]: the row after j draws, added in draw order
+            reached = run[1:, 0] >= genome
+            if reached.any() or m >= BOOT_MAX_DRAWS:
+                break
+            m = min(2 * m, BOOT_MAX_DRAWS)
+        count[i] = int(np.argmax(reached)) + 1 if reached.any() else m
+        rows[i] = run[count[i]]
+    if normalize:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rows = rows * (seg / _seg_of(rows))[:, None]
+    return (rows, count) if draws else rows
+
+
+def block_bootstrap_table(chunks, n, seed=0, normalize=False):
+    """The table ``io.bootstrap_table`` lays out, under this rule: row 0 the column sums of all chunks, added in chunk order (never
+    normalised: it is the data), row 1 + r replicate r of ``block_bootstrap``.  Float64 ``[1 + n][8]``."""
+    c, _, _ = check_chunks(chunks)
+    return np.vstack([_in_order_sum(c)[None, :], block_bootstrap(c, n, seed=seed, normalize=normalize)])
