@@ -781,6 +781,24 @@ int misti_kernel_times(misti_ctx* ctx, double ms[3], int64_t launches[3], int re
  * Either pointer may be NULL. */
 int misti_tables(int32_t* gen, int32_t* jaf);
 
+/* The residual of the lambda correction's 3-state pair chain, as the chain kernels evaluate it (pair_eval), one problem per GPU
+ * lane - no model, no solver.  A problem is ten doubles, everything already stretched to the unit interval:
+ *   mu0, mu1   migration rates (finite, >= 0)
+ *   P[3]       pair-state vector at the start of the interval (both in 0, both in 1, one in each)
+ *   tgt        the target: cpfit e^-lh * sum(P); default fit the one-population expected coalescence time
+ *   x0, x1     the point - the two rates being solved for; may be non-finite or overflowing (everything comes back NaN)
+ *   role       0..5 = 2 e + k: e = 0 evaluates the point, 1 / 2 the forward-difference point of x0 / x1
+ *              (x + sqrt(eps) * sign(x) * max(1, |x|)); k is the genome P belongs to and changes nothing here
+ *   red        0, or the structural reduction 1 / 2 (state 0 / 1 empty and unfed): cpfit only, and only with mu1 (mu0) == 0 and
+ *              P[0] (P[1]) == 0 exactly
+ * out[i] = { res, w[3] }: w = e^M P, and res = sum(w) - tgt with cpfit, (l . int_0^1 u e^{uM} pn du) / (1 - sum(e^M pn)) - tgt with
+ * the default fit (pn = P / sum(P)).  Host buffers; runs on the context's device and stream and returns when out is written.
+ * Arguments are checked before the context is looked at: MISTI_E_ARG for cpfit outside {0, 1}, n < 0, a NULL buffer with n > 0, a
+ * non-finite or negative rate, a non-finite P or tgt, role or red outside their ranges, or red != 0 where it does not apply;
+ * MISTI_E_LIMIT for n > MISTI_PAIR_MAX_PROBLEMS. */
+#define MISTI_PAIR_MAX_PROBLEMS (1 << 20)
+int misti_pair_residuals(misti_ctx* ctx, int cpfit, int64_t n, const double* problems /* HOST [n][10] */, double* out /* HOST [n][4] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1033,6 +1033,41 @@ int misti_forward_rates(misti_ctx* c, int64_t n_cand, const double* split, const
     return 0;
 }
 
+int misti_pair_residuals(misti_ctx* c, int cpfit, int64_t n, const double* problems, double* out) {
+    // everything that can be said about the arguments is said before the context is looked at
+    if (cpfit != 0 && cpfit != 1) return fail(MISTI_E_ARG, "cpfit must be 0 or 1 (got %d)", cpfit);
+    if (n < 0) return fail(MISTI_E_ARG, "negative number of problems");
+    if (n > MISTI_PAIR_MAX_PROBLEMS) return fail(MISTI_E_LIMIT, "n beyond MISTI_PAIR_MAX_PROBLEMS = %d (got %lld)", (int)MISTI_PAIR_MAX_PROBLEMS, (long long)n);
+    if (n > 0 && (!problems || !out)) return fail(MISTI_E_ARG, "problems / out is NULL");
+    for (int64_t i = 0; i < n; ++i) {
+        const double* p = problems + i * 10;
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(p[k])) return fail(MISTI_E_ARG, "problems[%lld][%d] is not finite (only the point may be)", (long long)i, k);
+        if (p[0] < 0.0 || p[1] < 0.0) return fail(MISTI_E_ARG, "problems[%lld]: a migration rate must not be negative", (long long)i);
+        const double role = p[8], red = p[9];
+        if (!(role == 0.0 || role == 1.0 || role == 2.0 || role == 3.0 || role == 4.0 || role == 5.0))
+            return fail(MISTI_E_ARG, "problems[%lld]: role %g is not one of 0..5", (long long)i, role);
+        if (!(red == 0.0 || red == 1.0 || red == 2.0)) return fail(MISTI_E_ARG, "problems[%lld]: red %g is not one of 0..2", (long long)i, red);
+        if (red != 0.0) {
+            if (!cpfit) return fail(MISTI_E_ARG, "problems[%lld]: red = %g without cpfit (the default fit has no reduced form)", (long long)i, red);
+            const int k = red == 1.0 ? 0 : 1;            // the state that is empty and unfed: mu of the OTHER population is zero
+            if (p[1 - k] != 0.0 || p[2 + k] != 0.0)
+                return fail(MISTI_E_ARG, "problems[%lld]: red = %g needs mu%d == 0 and P[%d] == 0 exactly", (long long)i, red, 1 - k, k);
+        }
+    }
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nn = (size_t)n;
+    HIP_TRY(c->st_params.reserve(nn * 10 * sizeof(double)));
+    HIP_TRY(c->st_lc.reserve(nn * 4 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->st_params.p, problems, nn * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(misti::launch_pair_residuals(cpfit != 0, n, c->st_params.as<double>(), c->st_lc.as<double>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->st_lc.p, nn * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {

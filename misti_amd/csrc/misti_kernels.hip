@@ -1091,8 +1091,9 @@ struct PairProblem {
 // its successors, see correct_body).  A pure function of (pb, point, role): what else sits in the wave changes no bit.
 // PROBE (default fit only): *probe receives, for this lane's evaluation, the difference between the REFERENCE's form of the
 // expected coalescence time (ect_reference_form) and the integral series used for the value: one draw of the rounding noise the
-// reference's residual carries at this point (the series is accurate to ~4e-15; the formula loses ~1/|M|^2 digits).  See
-// ect_noise_continues.
+// reference's residual carries at this point (the series' integral is accurate to a few ulps, and the quotient by 1 - pnc carries the
+// rounding of pnc beside one: 16 eps (1 + 1 / (1 - pnc)) of ect bounds it - measured 1e-15 ... 8e-15 relative at |M| 0.12 ... 2, 5e-14 at 0.01 and 4e-11 at
+// |M| = 1e-5, tests/test_gpu_pair_residuals.py; the formula loses ~1/|M|^2 digits).  See ect_noise_continues.
 template <bool CPFIT, bool PROBE = false>
 __device__ __forceinline__ void pair_eval(const PairProblem& pb, double x0, double x1, int role, Diag& dg, double& res, double w[3], bool& guard,
                                           double* probe = nullptr) {
@@ -1449,6 +1450,31 @@ void forward_kernel(DevModel m, int64_t n_cand, const double* __restrict__ split
         }
         lh_o[2 * t] = l0; lh_o[2 * t + 1] = l1;
     }
+}
+
+// ------------------------------------------------------------ residual probe ----
+// misti_pair_residuals (include/misti_hip.h, "introspection (tests)"): pair_eval as the chain kernels call it, one problem per lane, so
+// that the suite reaches every branch of the residual directly - pair_reduced and the default fit's two forms of the expected
+// coalescence time are otherwise met only inside the solver.  A problem is [mu0, mu1, P[3], tgt, x0, x1, role, red], everything already
+// stretched to the unit interval; sk is the sum of P in the order the chain kernel adds it (correct_body).  No solver, no model.
+template <bool CPFIT>
+__global__ __launch_bounds__(64)
+void pair_residuals_kernel(int64_t n, const double* __restrict__ problems, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* p = problems + i * 10;
+    PairProblem pb;
+    pb.mu0 = p[0]; pb.mu1 = p[1];
+    pb.Pk[0] = p[2]; pb.Pk[1] = p[3]; pb.Pk[2] = p[4];
+    pb.sk = (pb.Pk[0] + pb.Pk[1]) + pb.Pk[2];
+    pb.tgtk = p[5];
+    pb.red = (int)p[9];
+    Diag dg;
+    double res, w[3];
+    bool guard = false;
+    pair_eval<CPFIT>(pb, p[6], p[7], (int)p[8], dg, res, w, guard);
+    double* o = out + i * 4;
+    o[0] = res; o[1] = w[0]; o[2] = w[1]; o[3] = w[2];
 }
 
 // Kernel 1: lambda correction of the two-population intervals (CorrectLambdas loop t < splitT,
@@ -3243,6 +3269,14 @@ hipError_t launch_forward(const DevModel& m, int64_t n_cand, const double* split
                           int32_t* status, hipStream_t stream) {
     if (n_cand <= 0) return hipSuccess;
     hipLaunchKernelGGL(forward_kernel, dim3((unsigned)((n_cand + 63) / 64)), dim3(64), 0, stream, m, n_cand, split, params, hold_mu, lh_out, pr_out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_residuals(bool cpfit, int64_t n, const double* problems, double* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    if (cpfit) hipLaunchKernelGGL(pair_residuals_kernel<true>, grid, block, 0, stream, n, problems, out);
+    else hipLaunchKernelGGL(pair_residuals_kernel<false>, grid, block, 0, stream, n, problems, out);
     return hipGetLastError();
 }
 

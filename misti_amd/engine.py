@@ -249,6 +249,15 @@ class Engine:
         _lib.check(self._lib.misti_forward_rates(self._ctx, n, ptr(split), ptr(par), 1 if hold_mu else 0, ptr(lh), ptr(pr), ptr(status)))
         return lh, pr, status
 
+    def pair_residuals(self, problems, cpfit=True):
+        """``misti_pair_residuals`` (introspection, for the suite): the pair-chain residual as the chain kernels evaluate it, one problem
+        ``[mu0, mu1, P[3], tgt, x0, x1, role, red]`` per lane.  Returns ``out[n][4]``: the residual and ``w = e^M P``."""
+        p = _f64(problems, (-1, 10))
+        out = np.empty((p.shape[0], 4))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        _lib.check(self._lib.misti_pair_residuals(self._ctx, 1 if cpfit else 0, p.shape[0], ptr(p), ptr(out)))
+        return out
+
     def last_diag(self, n_cand):
         """Largest corrected rate x interval length per candidate of the last batch (misti_last_diag)."""
         out = np.empty(int(n_cand))
