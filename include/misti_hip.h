@@ -799,6 +799,36 @@ int misti_tables(int32_t* gen, int32_t* jaf);
 #define MISTI_PAIR_MAX_PROBLEMS (1 << 20)
 int misti_pair_residuals(misti_ctx* ctx, int cpfit, int64_t n, const double* problems /* HOST [n][10] */, double* out /* HOST [n][4] */);
 
+/* The linear algebra of the lambda correction's least-squares solver, as the chain kernels run it, one problem per GPU lane through
+ * the device functions themselves - no model, no residual, no solver loop.  A problem is MISTI_LSQ_IN doubles, a result
+ * MISTI_LSQ_OUT; entries a kind does not use are ignored on the way in and 0 on the way out.  Integers travel as doubles.
+ *   kind     calls                                  in                                                    out
+ *   SCALAR   rcp64(x), sqrt64(x)                    [0] x                                                 [0] 1/x  [1] sqrt(x)
+ *   SVD2     svd_mx2<2>(J, f)                       [0..3] J row-major  [4..5] f                           [0..1] s  [2..5] V row-major
+ *                                                                                                         (V[r][i]: component r of right vector i)  [6..7] U^T f
+ *   SVD4     svd_aug(A, f), N = 2: A[4][2], f[4]    [0..7] A row-major  [8..11] f  [12] N                  as SVD2
+ *                           N = 1: A[2][1], f[2]    [0], [2] A  [8..9] f  [12] N                           [0] s  [2] V  [6] U^T f
+ *   STEP     next_step(J, f, g = J^T f, ...)        [0..3] J  [4..5] f  [6] Delta  [7] alpha               [0..1] p  [2] alpha  [3] predicted
+ *                                                                                                         [4] increment of the regularised-step count  [5] axis
+ *   STEPN    svd_aug + solve_tr_n<N>(m = N)         A, f, N as SVD4  [13] Delta  [14] alpha                [0..N-1] p_h  [2] alpha
+ *   SELECT   select_step<N>                         [0..1] x  [2..5] J_h  [6..7] diag  [8..9] g_h          [0..1] step  [2..3] step_h  [4] predicted
+ *                                                   [10..11] p  [12..13] p_h  [14..15] d  [16] Delta
+ *                                                   [17] lb  [18] theta  [19] N   (N = 1: the first entry of each)
+ *   UPDATE   tr_update                              [0] finite  [1..2] p  [3..4] x  [5] cost               [0] Delta  [1] 0.25 |p|  [2] term  [3] accept
+ *                                                   [6] cost_new  [7] predicted  [8] Delta
+ *   SOLVE3   solve3, solve3_ge, mat3_solve(M, I)    [0..8] M row-major  [9..11] b                          [0..2] x (cofactors)  [3..5] x (elimination)
+ *                                                                                                         [6..14] M^-1 row-major
+ * The values of a problem may be anything (the functions are probed at their edges: zeros, infinities, NaN).  Host buffers; runs on
+ * the context's device and stream and returns when out is written.  Arguments are checked before the context is looked at:
+ * MISTI_E_ARG for an unknown kind, n < 0, a NULL buffer with n > 0, N other than 1 or 2, a finite flag other than 0 or 1;
+ * MISTI_E_LIMIT for n > MISTI_LSQ_MAX_PROBLEMS. */
+#define MISTI_LSQ_IN 20
+#define MISTI_LSQ_OUT 16
+#define MISTI_LSQ_MAX_PROBLEMS (1 << 20)
+enum { MISTI_LSQ_SCALAR = 0, MISTI_LSQ_SVD2 = 1, MISTI_LSQ_SVD4 = 2, MISTI_LSQ_STEP = 3, MISTI_LSQ_STEPN = 4, MISTI_LSQ_SELECT = 5,
+       MISTI_LSQ_UPDATE = 6, MISTI_LSQ_SOLVE3 = 7, MISTI_LSQ_KINDS = 8 };
+int misti_lsq_probe(misti_ctx* ctx, int kind, int64_t n, const double* problems /* HOST [n][MISTI_LSQ_IN] */, double* out /* HOST [n][MISTI_LSQ_OUT] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,7 @@ SYMBOLS = {
     "misti_kernel_times": (C.c_int, [C.c_void_p, _PD, C.POINTER(C.c_int64), C.c_int]),
     "misti_tables": (C.c_int, [_PI, _PI]),
     "misti_pair_residuals": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "misti_lsq_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "misti_create_lanes": (C.c_int, [C.POINTER(Model), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "misti_destroy_lanes": (C.c_int, [C.c_void_p]),
     "misti_lanes_size": (C.c_int, [C.c_void_p]),

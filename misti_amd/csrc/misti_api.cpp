@@ -1068,6 +1068,33 @@ int misti_pair_residuals(misti_ctx* c, int cpfit, int64_t n, const double* probl
     return 0;
 }
 
+int misti_lsq_probe(misti_ctx* c, int kind, int64_t n, const double* problems, double* out) {
+    // everything that can be said about the arguments is said before the context is looked at
+    if (kind < 0 || kind >= MISTI_LSQ_KINDS) return fail(MISTI_E_ARG, "kind must be one of 0..%d (got %d)", (int)MISTI_LSQ_KINDS - 1, kind);
+    if (n < 0) return fail(MISTI_E_ARG, "negative number of problems");
+    if (n > MISTI_LSQ_MAX_PROBLEMS) return fail(MISTI_E_LIMIT, "n beyond MISTI_LSQ_MAX_PROBLEMS = %d (got %lld)", (int)MISTI_LSQ_MAX_PROBLEMS, (long long)n);
+    if (n > 0 && (!problems || !out)) return fail(MISTI_E_ARG, "problems / out is NULL");
+    const int n_at = kind == MISTI_LSQ_SVD4 || kind == MISTI_LSQ_STEPN ? 12 : kind == MISTI_LSQ_SELECT ? 19 : -1;
+    for (int64_t i = 0; i < n; ++i) {
+        const double* p = problems + i * MISTI_LSQ_IN;
+        if (n_at >= 0 && !(p[n_at] == 1.0 || p[n_at] == 2.0))
+            return fail(MISTI_E_ARG, "problems[%lld]: N %g is not 1 or 2", (long long)i, p[n_at]);
+        if (kind == MISTI_LSQ_UPDATE && !(p[0] == 0.0 || p[0] == 1.0))
+            return fail(MISTI_E_ARG, "problems[%lld]: finite %g is not 0 or 1", (long long)i, p[0]);
+    }
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nn = (size_t)n;
+    HIP_TRY(c->st_params.reserve(nn * MISTI_LSQ_IN * sizeof(double)));
+    HIP_TRY(c->st_lc.reserve(nn * MISTI_LSQ_OUT * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->st_params.p, problems, nn * MISTI_LSQ_IN * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(misti::launch_lsq_probe(kind, n, c->st_params.as<double>(), c->st_lc.as<double>(), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->st_lc.p, nn * MISTI_LSQ_OUT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {

@@ -242,6 +242,8 @@ hipError_t launch_forward(const DevModel& m, int64_t n_cand, const double* split
                           int32_t* status, hipStream_t stream);
 // misti_pair_residuals: problems[n][10] -> out[n][4], one problem per lane through pair_eval<cpfit>
 hipError_t launch_pair_residuals(bool cpfit, int64_t n, const double* problems, double* out, hipStream_t stream);
+// misti_lsq_probe: problems[n][MISTI_LSQ_IN] -> out[n][MISTI_LSQ_OUT], one problem per lane through the solver's linear algebra
+hipError_t launch_lsq_probe(int kind, int64_t n, const double* problems, double* out, hipStream_t stream);
 hipError_t launch_argmax(int64_t n_cand, int64_t n_rep, const double* llk, int32_t* best, double* best_llk, hipStream_t stream);
 // The k best candidates per replicate without the table (misti_scan_best_dev): llk_kernel's values reduced where they are computed.
 // `slices` = scan_best_slices(...) lists of width scan_best_width(k) go through part_v / part_i ([slices][width][n_rep] each), then one

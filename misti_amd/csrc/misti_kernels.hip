@@ -755,7 +755,9 @@ __device__ __forceinline__ Svd2 svd_mx2(const double A[MROWS][2], const double f
     double c = 1.0, sn = 0.0;
     if (ga != 0.0) {
         double zeta = (be - al) * rcp64(2.0 * ga);
-        double t = copysign(1.0, zeta) * rcp64(fabs(zeta) + sqrt64(1.0 + zeta * zeta));
+        const double den = fabs(zeta) + sqrt64(1.0 + zeta * zeta);
+        double t = copysign(1.0, zeta) * rcp64(den);
+        t = den < INFINITY ? t : copysign(0.0, zeta);      // zeta^2 overflowed (|zeta| > 1.3e154): rcp64(inf) is NaN, the tangent is 0
         c = rcp64(sqrt64(1.0 + t * t));
         sn = c * t;
     }
@@ -1475,6 +1477,95 @@ void pair_residuals_kernel(int64_t n, const double* __restrict__ problems, doubl
     pair_eval<CPFIT>(pb, p[6], p[7], (int)p[8], dg, res, w, guard);
     double* o = out + i * 4;
     o[0] = res; o[1] = w[0]; o[2] = w[1]; o[3] = w[2];
+}
+
+// ------------------------------------------------------------ least-squares probe ----
+// misti_lsq_probe (include/misti_hip.h, "introspection (tests)"): the solver's linear algebra - rcp64 / sqrt64, the Jacobi SVD, the
+// trust-region steps, select_step, tr_update and the 3 x 3 solves - one problem per lane through the device functions the chain
+// kernels call (no copies: the chain kernels' own next_step, svd_aug, ... are instantiated here), so that the suite reaches each of
+// them directly and not only through whole solves.  A problem is MISTI_LSQ_IN doubles, a result MISTI_LSQ_OUT, unused entries 0; the
+// layouts of the kinds are in the header.  Integers travel as doubles.
+// next_step is instantiated with GROUP = 8: with GROUP == 64 uni<> takes the first lane's branch for the whole wave (a chain owns
+// its wave there) and the probe would test one problem per wave; for every other GROUP uni<> is the identity and each lane takes
+// its own branch.  kind is the same in every lane of a launch.
+__global__ __launch_bounds__(64)
+void lsq_probe_kernel(int kind, int64_t n, const double* __restrict__ problems, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* q = problems + i * MISTI_LSQ_IN;
+    double* o = out + i * MISTI_LSQ_OUT;
+    double r[MISTI_LSQ_OUT];
+    for (int k = 0; k < MISTI_LSQ_OUT; ++k) r[k] = 0.0;
+    if (kind == MISTI_LSQ_SCALAR) {
+        r[0] = rcp64(q[0]); r[1] = sqrt64(q[0]);
+    } else if (kind == MISTI_LSQ_SVD2) {
+        const double J[2][2] = {{q[0], q[1]}, {q[2], q[3]}}, f[2] = {q[4], q[5]};
+        const Svd2 d = svd_mx2<2>(J, f);
+        r[0] = d.s[0]; r[1] = d.s[1]; r[2] = d.V[0][0]; r[3] = d.V[0][1]; r[4] = d.V[1][0]; r[5] = d.V[1][1]; r[6] = d.uf[0]; r[7] = d.uf[1];
+    } else if (kind == MISTI_LSQ_SVD4) {
+        if ((int)q[12] == 1) {
+            const double A[2][1] = {{q[0]}, {q[2]}}, f[2] = {q[8], q[9]};
+            const SvdN<1> d = svd_aug(A, f);
+            r[0] = d.s[0]; r[2] = d.V[0][0]; r[6] = d.uf[0];
+        } else {
+            const double A[4][2] = {{q[0], q[1]}, {q[2], q[3]}, {q[4], q[5]}, {q[6], q[7]}}, f[4] = {q[8], q[9], q[10], q[11]};
+            const SvdN<2> d = svd_aug(A, f);
+            r[0] = d.s[0]; r[1] = d.s[1]; r[2] = d.V[0][0]; r[3] = d.V[0][1]; r[4] = d.V[1][0]; r[5] = d.V[1][1]; r[6] = d.uf[0]; r[7] = d.uf[1];
+        }
+    } else if (kind == MISTI_LSQ_STEP) {
+        const double J[2][2] = {{q[0], q[1]}, {q[2], q[3]}}, f[2] = {q[4], q[5]};
+        double g[2];
+        g[0] = J[0][0] * f[0] + J[1][0] * f[1];                     // as correct_body forms the gradient
+        g[1] = J[0][1] * f[0] + J[1][1] * f[1];
+        double alpha = q[7], p[2];
+        int lm = 0, axis = -1;
+        const double predicted = next_step<8>(J, f, g, q[6], alpha, p, lm, axis);
+        r[0] = p[0]; r[1] = p[1]; r[2] = alpha; r[3] = predicted; r[4] = (double)lm; r[5] = (double)axis;
+    } else if (kind == MISTI_LSQ_STEPN) {
+        double alpha = q[14];
+        if ((int)q[12] == 1) {
+            const double A[2][1] = {{q[0]}, {q[2]}}, f[2] = {q[8], q[9]};
+            const SvdN<1> d = svd_aug(A, f);
+            double ph[1];
+            solve_tr_n<1>(d, 1, q[13], alpha, ph);
+            r[0] = ph[0];
+        } else {
+            const double A[4][2] = {{q[0], q[1]}, {q[2], q[3]}, {q[4], q[5]}, {q[6], q[7]}}, f[4] = {q[8], q[9], q[10], q[11]};
+            const SvdN<2> d = svd_aug(A, f);
+            double ph[2];
+            solve_tr_n<2>(d, 2, q[13], alpha, ph);
+            r[0] = ph[0]; r[1] = ph[1];
+        }
+        r[2] = alpha;
+    } else if (kind == MISTI_LSQ_SELECT) {
+        if ((int)q[19] == 1) {
+            const double x[1] = {q[0]}, Jh[1][1] = {{q[2]}}, diag[1] = {q[6]}, gh[1] = {q[8]}, d[1] = {q[14]};
+            double p[1] = {q[10]}, ph[1] = {q[12]}, step[1], steph[1];
+            r[4] = select_step<1>(x, Jh, diag, gh, p, ph, d, q[16], q[17], q[18], step, steph);
+            r[0] = step[0]; r[2] = steph[0];
+        } else {
+            const double x[2] = {q[0], q[1]}, Jh[2][2] = {{q[2], q[3]}, {q[4], q[5]}}, diag[2] = {q[6], q[7]}, gh[2] = {q[8], q[9]}, d[2] = {q[14], q[15]};
+            double p[2] = {q[10], q[11]}, ph[2] = {q[12], q[13]}, step[2], steph[2];
+            r[4] = select_step<2>(x, Jh, diag, gh, p, ph, d, q[16], q[17], q[18], step, steph);
+            r[0] = step[0]; r[1] = step[1]; r[2] = steph[0]; r[3] = steph[1];
+        }
+    } else if (kind == MISTI_LSQ_UPDATE) {
+        const double p[2] = {q[1], q[2]}, x[2] = {q[3], q[4]};
+        double Delta = q[8], dq;
+        int term;
+        bool accept;
+        tr_update(q[0] != 0.0, p, x, q[5], q[6], q[7], Delta, dq, term, accept);
+        r[0] = Delta; r[1] = dq; r[2] = (double)term; r[3] = accept ? 1.0 : 0.0;
+    } else if (kind == MISTI_LSQ_SOLVE3) {
+        const double M[3][3] = {{q[0], q[1], q[2]}, {q[3], q[4], q[5]}, {q[6], q[7], q[8]}}, b[3] = {q[9], q[10], q[11]};
+        const double I3[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+        double x[3], y[3], X[3][3];
+        solve3(M, b, x);
+        solve3_ge(M, b, y);
+        mat3_solve(M, I3, X);
+        for (int k = 0; k < 3; ++k) { r[k] = x[k]; r[3 + k] = y[k]; for (int j = 0; j < 3; ++j) r[6 + 3 * k + j] = X[k][j]; }
+    }
+    for (int k = 0; k < MISTI_LSQ_OUT; ++k) o[k] = r[k];
 }
 
 // Kernel 1: lambda correction of the two-population intervals (CorrectLambdas loop t < splitT,
@@ -3277,6 +3368,12 @@ hipError_t launch_pair_residuals(bool cpfit, int64_t n, const double* problems, 
     const dim3 grid((unsigned)((n + 63) / 64)), block(64);
     if (cpfit) hipLaunchKernelGGL(pair_residuals_kernel<true>, grid, block, 0, stream, n, problems, out);
     else hipLaunchKernelGGL(pair_residuals_kernel<false>, grid, block, 0, stream, n, problems, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_lsq_probe(int kind, int64_t n, const double* problems, double* out, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lsq_probe_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, kind, n, problems, out);
     return hipGetLastError();
 }
 

@@ -258,6 +258,23 @@ class Engine:
         _lib.check(self._lib.misti_pair_residuals(self._ctx, 1 if cpfit else 0, p.shape[0], ptr(p), ptr(out)))
         return out
 
+    LSQ_KINDS = {"SCALAR": 0, "SVD2": 1, "SVD4": 2, "STEP": 3, "STEPN": 4, "SELECT": 5, "UPDATE": 6, "SOLVE3": 7}
+    LSQ_IN, LSQ_OUT = 20, 16
+
+    def lsq_probe(self, kind, problems):
+        """``misti_lsq_probe`` (introspection, for the suite): the solver's linear algebra as the chain kernels run it, one problem per
+        lane.  ``kind`` is a name of ``LSQ_KINDS`` or its number; a row of ``problems`` may be shorter than ``LSQ_IN`` (the rest is 0).
+        Returns ``out[n][LSQ_OUT]``; the layouts are in include/misti_hip.h."""
+        k = self.LSQ_KINDS[kind] if isinstance(kind, str) else int(kind)
+        a = np.asarray(problems, dtype=np.float64)
+        a = a.reshape(-1, a.shape[-1]) if a.size else a.reshape(0, self.LSQ_IN)
+        p = np.zeros((a.shape[0], self.LSQ_IN))
+        p[:, :a.shape[1]] = a
+        out = np.empty((p.shape[0], self.LSQ_OUT))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        _lib.check(self._lib.misti_lsq_probe(self._ctx, k, p.shape[0], ptr(p), ptr(out)))
+        return out
+
     def last_diag(self, n_cand):
         """Largest corrected rate x interval length per candidate of the last batch (misti_last_diag)."""
         out = np.empty(int(n_cand))
