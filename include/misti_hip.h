@@ -307,6 +307,58 @@ int misti_bootstrap_rows_dev(misti_ctx* ctx, int64_t n_chunk, const double* chun
  * or a NULL idx with n > 0; MISTI_E_LIMIT for n_chunk > MISTI_BOOT_MAX_CHUNKS or n > MISTI_BOOT_MAX_DRAWS. */
 int misti_bootstrap_draws(uint64_t seed, int64_t rep, int64_t n_chunk, int64_t n, int64_t* idx /* HOST [n] */);
 
+/* ---- parametric bootstrap: replicate rows drawn from a spectrum -------------------- */
+/* Makes replicate rows where there are no chunks to resample (a one-row JSFS: the reference's README example, a realSFS 2-D spectrum,
+ * MS2JSFS.py's sim.jafs): n_rep tables of n_sites sites, every site drawn independently from the seven classes of a spectrum - the
+ * multinomial the data are scored as (MigrationInference.py:600-609), from the normalised expected spectrum an evaluation leaves on
+ * the device (d_jafs of misti_eval_batch_dev).  The reference has no counterpart (its route is one ms / scrm simulation and one
+ * conversion per replicate, run_sim.sh).  The rule is the project's own (optimize.parametric_thresholds / optimize.parametric_rows
+ * state it in NumPy; the device result is that, bit for bit):
+ *   - replicate r of the call is the global replicate rep = first_rep + r and draws from spectrum d_spec_of[r] (spectrum 0 without
+ *     d_spec_of), seven float64 p[0..6] that need not be normalised;
+ *   - a spectrum is usable if all seven entries are finite and >= 0, the running sum c6 = (((((p0 + p1) + p2) + p3) + p4) + p5) + p6
+ *     is finite and > 0 and, where d_status is given, its status is one the scorer gives a value (MISTI_OK: the predicate of
+ *     misti_score.h, the one misti_llk_dev and the scans apply);
+ *   - thresholds: c_k the running sum in class order, q_k = c_k / c6 (one float64 division each, k = 0 ... 5), T_k = ceil(q_k 2^53)
+ *     as a uint64 in [0, 2^53] - exact or correctly rounded float64 throughout, so host, device and NumPy agree;
+ *   - draw j (0 <= j < n_sites) is element j of numpy.random.Philox(key=[seed, rep]).random_raw - the stream and the counter
+ *     convention of the block bootstrap above - u = raw >> 11, and its class is the number of k in 0 ... 5 with u >= T_k.  That is
+ *     numpy.searchsorted(q, numpy.random.Generator(Philox(key=[seed, rep])).random(n_sites), side='right');
+ *   - no rejection step: a class's probability is quantised to 2^-53 (a class with p_k = 0 is never drawn; one below 2^-53 of the
+ *     total may never be) - documented, not corrected;
+ *   - the row is [genome, n0 ... n6] as float64: with g_k = #{j : u_j >= T_k}, n0 = n_sites - g0, n_k = g_(k-1) - g_k, n6 = g5.
+ *     The counts are integers (exact in float64: n_sites <= 2^36) and sum to n_sites exactly; genome only fills column 0;
+ *   - a replicate whose spectrum is unusable, or whose index is outside 0 ... n_spec - 1, gets [genome, 0 x 7] and row status 1; a
+ *     usable one row status 0.  n_sites == 0 gives rows of zeros (and the same statuses).
+ * A replicate is a function of (seed, rep, p, n_sites) alone, whatever n_rep, first_rep, the device or the launch geometry: the
+ * counts are integer sums.  Folded models need no case of their own: the scorer folds the seven counts, and the sum of a class pair
+ * is multinomial with the summed probability.
+ * WHAT THE REPLICATES DO NOT DO: the sites are drawn INDEPENDENTLY.  The real sites of the composite likelihood are linked, so
+ * intervals from these replicates are narrower than the block bootstrap's on the same genome; where chunks exist the block
+ * bootstrap remains the confidence statement.  A caller may pass an effective n_sites (fewer than the data's) to allow for it.
+ * Launch: grid (blocks_per_rep, n_rep) in slices of 65 535 replicates, 256 lanes; blocks_per_rep = max(1, min(ceil(8192 / n_rep),
+ * ceil(ceil(n_sites / 4) / 4096))) - 1 once there are 8 192 replicates, more for few replicates of many sites, never leaving a lane
+ * fewer than 16 Philox blocks; misti_parametric_geometry returns it (host only, no context).
+ * d_rows is an ordinary row buffer: misti_eval_batch_dev, misti_llk_dev, misti_scan_best_dev and misti_scan_profile_dev take it as
+ * d_jsfs.  Checked before the context is looked at: MISTI_E_ARG for a negative count or first_rep, n_spec < 1, a NULL d_spectra /
+ * d_rows with n_rep > 0, or a genome that is not finite; MISTI_E_LIMIT for n_sites > MISTI_PARAM_MAX_SITES, n_rep > INT32_MAX or
+ * first_rep + n_rep overflowing.  n_rep == 0 writes nothing.  Asynchronous on the context's stream. */
+#define MISTI_PARAM_MAX_SITES (1ll << 36)
+int misti_parametric_rows_dev(misti_ctx* ctx, int64_t n_spec, const double* d_spectra /* DEVICE [n_spec][7] */,
+                              const int32_t* d_status /* DEVICE [n_spec] or NULL */, const int32_t* d_spec_of /* DEVICE [n_rep] or NULL: spectrum 0 */,
+                              double genome, int64_t n_sites, uint64_t seed, int64_t first_rep, int64_t n_rep,
+                              double* d_rows /* DEVICE [n_rep][8] */, int32_t* d_row_status /* DEVICE [n_rep] or NULL */);
+/* The thresholds of one spectrum, on the host through the very function the kernel calls (misti_parametric.h): 0, or 1 for an
+ * unusable spectrum (T is then all zero).  MISTI_E_ARG for a NULL pointer. */
+int misti_parametric_thresholds(const double p[7], uint64_t T[6]);
+/* The seven class counts of replicate `rep` drawn from p, on the host without a context or a device: 0, or 1 for an unusable
+ * spectrum (counts all zero).  MISTI_E_ARG for a negative n_sites or rep or a NULL pointer, MISTI_E_LIMIT for n_sites >
+ * MISTI_PARAM_MAX_SITES. */
+int misti_parametric_counts(const double p[7], int64_t n_sites, uint64_t seed, int64_t rep, int64_t counts[7]);
+/* blocks_per_rep of the launch misti_parametric_rows_dev would make for this shape (the rule above).  MISTI_E_ARG for a negative
+ * count or a NULL pointer, MISTI_E_LIMIT as for misti_parametric_rows_dev. */
+int misti_parametric_geometry(int64_t n_sites, int64_t n_rep, int32_t* blocks_per_rep);
+
 /* ---- batched optimiser ------------------------------------------------------------ */
 /* Replaces MigrationInference.Solve (MigrationInference.py:718-733: SciPy Nelder-Mead on -JAFSLikelihood, xatol =
  * fatol = tol, maxiter = 1000, started from the -mi / -pu initial values) for n_start starts at once - BASELINE

@@ -30,6 +30,7 @@ TRACE_MAX_CAND, TRACE_MAX_ITER = 64, 200
 SCAN_MAX_BEST = 8
 SCAN_MAX_GROUPS = 65535
 BOOT_NORMALIZE, BOOT_MAX_CHUNKS, BOOT_MAX_DRAWS = 1, 65535, 1 << 24
+PARAM_MAX_SITES = 1 << 36
 
 
 class Band(C.Structure):
@@ -112,6 +113,11 @@ SYMBOLS = {
     "misti_scan_profile_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_bootstrap_rows_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "misti_bootstrap_draws": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "misti_parametric_rows_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_uint64, C.c_int64,
+                                            C.c_int64, C.c_void_p, C.c_void_p]),
+    "misti_parametric_thresholds": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "misti_parametric_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p]),
+    "misti_parametric_geometry": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p]),
     "misti_curvature_assemble_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_curvature": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,

@@ -23,6 +23,15 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               (--bs-seed K, replicate): replicate r is the same row whatever N, rank or device), NOT the reference's
                               generateJSFS_bs.py, which draws from Python's Mersenne Twister.  --bs-normalize: the reference's normalize=True;
                               --bootstrap-out FILE keeps the table as a #MiSTI_JSFS file (--all-bs on it repeats the run).  Not offered with -bs K
+    --parametric N            for a JSFS file WITHOUT chunks (one row): stage 1 is the ordinary fit of the data row at the given split and
+                              -mi/-pu initial values (what this line prints without grid options); stage 2 draws N replicates of the data's
+                              number of sites (--sites M: of M sites) from the spectrum at that fit on the device
+                              (misti_parametric_rows_dev; --bs-seed K) and the table [data; replicates] replaces the rows before any
+                              mode sees them; implies --all-bs.  CAVEAT: the sites are drawn INDEPENDENTLY, real sites are linked - intervals
+                              from these replicates are narrower than a block bootstrap's on the same genome; where the file has chunks
+                              --bootstrap remains the confidence statement (--sites M may pass an effective number of sites).
+                              --bootstrap-out FILE keeps the table (--all-bs on it repeats stage 2).  Not offered with --bootstrap,
+                              --bs-normalize (there is nothing to normalise) or -bs K
     --grid-solve              with --grid-st and/or --all-bs: for every (row, split) pair the reference's Solve from the
                               -mi/-pu initial values (the --grid-mi mesh points as starts: the best per pair), all pairs
                               in ONE batched search on the device; per pair the line MiSTI.py:240 prints (the test.bs
@@ -150,6 +159,12 @@ def build_parser():
     p.add_argument("--bs-seed", type=int, default=None, metavar="K", help="with --bootstrap: the seed of the replicates' streams, a uint64 (default 0)")
     p.add_argument("--bs-normalize", action="store_true", help="with --bootstrap: scale every replicate to the data's number of segregating sites")
     p.add_argument("--bootstrap-out", type=str, default=None, metavar="FILE", help="with --bootstrap: write the table that was drawn as a #MiSTI_JSFS file")
+    p.add_argument("--parametric", type=int, default=None, metavar="N",
+                   help="a JSFS without chunks: fit the data row, then draw N parametric-bootstrap replicates from the fitted spectrum on the device and "
+                        "evaluate the 1 + N-row table; implies --all-bs; --bs-seed and --bootstrap-out apply.  The sites are drawn independently, real "
+                        "sites are linked: intervals from these replicates are narrower than a block bootstrap's (--bootstrap, where the file has chunks)")
+    p.add_argument("--sites", type=int, default=None, metavar="M",
+                   help="with --parametric: sites per replicate (default: the data row's number of sites; fewer = an effective number of independent sites)")
     p.add_argument("--gpus", type=int, default=1, help="grid mode: start this many ranks, one per GPU (replaces `parallel -j N ./MiSTI.py ...`)")
     p.add_argument("--devices", type=str, default="", help="grid mode: comma-separated device list evaluated from this one process (misti_create_multi)")
     p.add_argument("--grid-solve", action="store_true",
@@ -189,6 +204,8 @@ def build_parser():
 def bootstrap_error(a):
     """Why ``--bootstrap`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
     if a.bootstrap is None:
+        if getattr(a, "parametric", None) is not None:
+            return None                                     # --bs-seed / --bootstrap-out belong to --parametric too: parametric_error
         if a.bs_seed is not None or a.bs_normalize or a.bootstrap_out is not None:
             return "--bs-seed / --bs-normalize / --bootstrap-out belong to --bootstrap N: give --bootstrap N"
         return None
@@ -210,6 +227,61 @@ def bootstrap_rows(a, inp, rows, pop1=None, pop2=None):
     device = local if world > 1 else (int(a.devices.split(",")[0]) if a.devices else a.device)
     with Engine(inp.times, inp.lambdas, device=device) as e:
         table = e.bootstrap_table(rows, a.bootstrap, seed=a.bs_seed or 0, normalize=a.bs_normalize)
+    table = table.tolist()
+    if a.bootstrap_out is not None and rank == 0:
+        with open(os.path.join(a.wd, a.bootstrap_out), "w") as fw:
+            fw.write(mio.format_jsfs(table, pop1, pop2))
+    return table
+
+
+def parametric_error(a):
+    """Why ``--parametric`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.parametric is None:
+        return "--sites belongs to --parametric N: give --parametric N" if a.sites is not None else None
+    if a.parametric < 1:
+        return "--parametric N: the number of replicates must be at least 1 (got %d)" % a.parametric
+    if a.bootstrap is not None:
+        return "--parametric draws its replicates from a fitted spectrum, --bootstrap resamples the chunks of the file: give one of them"
+    if a.bs_normalize:
+        return "--bs-normalize is not offered with --parametric: every replicate has exactly the number of sites asked for, there is nothing to normalise"
+    if a.bsMode != -1:
+        return "--parametric replaces the rows of the file by the table it draws and evaluates every row: -bs K is not offered with it"
+    if a.bs_seed is not None and not 0 <= a.bs_seed < 1 << 64:
+        return "--bs-seed is a uint64: 0 ... 2^64 - 1 (got %d)" % a.bs_seed
+    if a.sites is not None and not 1 <= a.sites <= 1 << 36:
+        return "--sites M: 1 ... 2^36 sites per replicate (got %d)" % a.sites
+    if a.sweep or a.sweep_pu:
+        return "--parametric fits the model of this command line at its split time: a {NAME} of a --sweep has no single fit to draw from"
+    return None
+
+
+def parametric_rows(a, inp, data_row, pop1=None, pop2=None):
+    """The table of ``--parametric N``.  Stage 1: the ordinary fit of ``data_row`` at the command line's split and initial values (the
+    single-model path of main: MigrationInference.Solve), printed as that path prints it.  Stage 2: N replicates drawn on this
+    process's device from the spectrum at the fit (Engine.parametric_table - a rank of --gpus N fits and regenerates the same table
+    from (seed, r) rather than receiving it); with --bootstrap-out the table is written through the JSFS writer (by rank 0).  Returns
+    the table as lists, or None where the fit has no value."""
+    from .dist import env_rank
+    rank, local, world = env_rank()
+    device = local if world > 1 else (int(a.devices.split(",")[0]) if a.devices else a.device)
+    times = list(inp.times)                                 # MigrationInference extends its grid in place for a fractional split
+    mig = MigrationInference(times, [list(l) for l in inp.lambdas], data_row, a.st, a.mi, a.pu, thrh=[inp.theta, inp.rho], Tpsmc=inp.Tpsmc,
+                             enableOutput=False, smooth=not a.nosmooth, unfolded=a.uf, trueEPS=a.trueEPS, sampleDate=inp.sampleDateDiscr,
+                             mixtureTH=a.mth, cpfit=a.cpfit, device=device)
+    try:
+        sol = mig.Solve(a.tol)
+        print(sol)
+        print("\nParameter estimates:")
+        print(result_line(a.bsMode, a.st, times, inp.scaleTime, a.mi, sol[0], sol[1]))
+        if sol[1] == -10 ** 9 or not np.isfinite(sol[1]):
+            return None
+        n_sites = a.sites if a.sites is not None else int(np.rint(np.asarray(data_row[1:], dtype=float).sum()))
+        table = mig._engine.parametric_table(a.st, [float(v) for v in sol[0]], data_row, a.parametric, n_sites=n_sites, seed=a.bs_seed or 0)
+    finally:
+        mig._engine.close()
+    print("Parametric bootstrap: %d replicates of %d sites drawn on the device from the spectrum at splitT = %s, optim = [%s] (llh = %s), seed %d: "
+          "independent sites - intervals from them are narrower than a block bootstrap's"
+          % (a.parametric, n_sites, a.st, ", ".join(str(v) for v in sol[0]), sol[1], a.bs_seed or 0))
     table = table.tolist()
     if a.bootstrap_out is not None and rank == 0:
         with open(os.path.join(a.wd, a.bootstrap_out), "w") as fw:
@@ -894,11 +966,11 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
+    why = parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
-    if a.bootstrap is not None:
+    if a.bootstrap is not None or a.parametric is not None:
         a.all_bs = True                                     # every mode below sees a bootstrap table
     # the two ways of using several GPUs exclude each other: N ranks that each opened the whole device list would run N x D contexts
     if a.gpus > 1 and a.devices:
@@ -953,6 +1025,11 @@ def main(argv=None):
         rows = bootstrap_rows(a, inp, rows, pop1, pop2)
         print("Bootstrap: %d replicates of %d chunks drawn on the device (seed %d%s): the project's own stream, not the reference's"
               % (a.bootstrap, n_chunk, a.bs_seed or 0, ", normalized" if a.bs_normalize else ""))
+    if a.parametric is not None:
+        rows = parametric_rows(a, inp, inputSFS, pop1, pop2)
+        if rows is None:
+            print("Failed to fit such a model: --parametric has no spectrum to draw from.")
+            return 1
     if a.sweep or a.sweep_pu:
         return sweep_solve(a, inp, rows) if a.grid_solve else sweep_eval(a, inp, rows)
     inp.divergenceTime = a.st

@@ -118,6 +118,7 @@ struct misti_ctx {
     DevBuf nm_f64, nm_i32;              // batched Nelder-Mead: simplices, points, counters (misti_nm_solve)
     DevBuf curv_f64, curv_i32;          // misti_curvature: points, stencil candidates, their spectra, derivatives | rows, slots, statuses
     DevBuf boot_chunks;                 // misti_bootstrap_rows_dev: the chunk table [n_chunk][8]
+    DevBuf param_totals;                // misti_parametric_rows_dev: the draw counts of one slice of replicates, [n][6] uint64
     int32_t* nm_live_host = nullptr;    // pinned: live starts after the last two finished iterations
     int64_t nm_iterations = 0;          // iterations issued by the last misti_nm_solve
     int64_t nm_slots = 0;               // and the batch slots they had in total (live starts + the stale-count slack)
@@ -523,6 +524,17 @@ int misti_boot_ctx_(misti_ctx* c, size_t bytes, void** stream, void** d_chunks) 
     return 0;
 }
 
+// internal (misti_parametric.hip): make the context's device current; its stream, and its buffer for the draw counts grown to `bytes`.
+// A buffer that grows frees the old one, which waits for the device: no kernel of an earlier call still adds to it.
+int misti_param_ctx_(misti_ctx* c, size_t bytes, void** stream, void** d_totals) {
+    if (!c || !stream || !d_totals) return fail(MISTI_E_ARG, "ctx is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->param_totals.reserve(bytes));
+    *stream = static_cast<void*>(c->stream);
+    *d_totals = c->param_totals.p;
+    return 0;
+}
+
 int misti_device_count(void) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -698,7 +710,7 @@ int misti_destroy(misti_ctx* c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     (void)hipGetLastError();
     for (auto* b : {&c->model_f64, &c->model_i32, &c->consts, &c->ws_jafs, &c->ws_status, &c->ws_chain_f64, &c->ws_chain_i32, &c->ws_order, &c->ws_diag, &c->ws_trunk, &c->ws_solver, &c->ws_iters, &c->ws_post,
-                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx, &c->curv_f64, &c->curv_i32, &c->boot_chunks})
+                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx, &c->curv_f64, &c->curv_i32, &c->boot_chunks, &c->param_totals})
         b->release();
     c->pin_in.release();
     c->pin_out.release();

@@ -57,6 +57,9 @@ __device__ __forceinline__ double llk_of(const double* __restrict__ row, double 
     return a;
 }
 
+// Whether a candidate of this status has a value: the one predicate of every path that scores a spectrum or draws from one.
+__host__ __device__ __forceinline__ bool status_has_value(int32_t st) { return st == MISTI_OK; }
+
 // A chunk of at most SCORE_CHUNK candidates staged in LDS for the kernels that walk candidates per row: lj[c][0..6] = the class logs of
 // the chunk's c-th candidate, lj[c][7] = 1.0 where it has no value (status != OK), else 0.0.  The block fills lj[0 .. nc): cand_of(c) is
 // the candidate's index in jafs / status, also left in lc[c] where lc is given.
@@ -68,7 +71,7 @@ void stage_class_logs(double (*lj)[8], int nc, const double* __restrict__ jafs, 
         const int64_t cand = cand_of(c);
         double v;
         if (k < 7) v = log_class(jafs + cand * 7, k, UNFOLDED ? 1 : 0);
-        else { v = (status && status[cand] != MISTI_OK) ? 1.0 : 0.0; if (lc) lc[c] = (int32_t)cand; }
+        else { v = (status && !status_has_value(status[cand])) ? 1.0 : 0.0; if (lc) lc[c] = (int32_t)cand; }
         lj[c][k] = v;
     }
 }

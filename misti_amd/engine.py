@@ -131,6 +131,59 @@ def _bootstrap_table(rows_dev, chunks):
     return np.vstack([_in_order_sum(_f64(chunks, (-1, 8)))[None, :], rows_dev.cpu().numpy()])
 
 
+def _parametric_rows(lib, ctx, device, spectra, n, n_sites, genome, seed, first, spec_of, status, row_status):
+    """``misti_parametric_rows_dev`` on context ``ctx`` of ``device`` into fresh torch tensors: ``rows[n][8]`` float64 and the row
+    statuses ``[n]`` int32.  ``spectra`` (``[n_spec][7]`` float64), ``spec_of`` and ``status`` (int32) are ndarrays - uploaded - or
+    tensors of this device, read where they are.  Waits for the context's stream.  Raises if a row status is set, unless
+    ``row_status`` asks for the array: returns ``rows`` or ``(rows, statuses)``."""
+    import torch
+    n, n_sites = int(n), int(n_sites)
+    if n < 0:
+        raise ValueError("parametric bootstrap: the number of replicates must not be negative (got %d)" % n)
+    dev = torch.device("cuda", int(device))
+
+    def on_device(a, dtype, shape):
+        if a is None:
+            return None
+        if hasattr(a, "data_ptr"):
+            if a.device != dev or a.dtype != dtype or not a.is_contiguous():
+                raise ValueError("parametric bootstrap: a tensor argument must be contiguous %s on %s" % (dtype, dev))
+            return a.reshape(shape)
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64 if dtype == torch.float64 else np.int32).reshape(shape), device=dev)
+
+    sp = on_device(spectra, torch.float64, (-1, 7))
+    of = on_device(spec_of, torch.int32, (n,))
+    st = on_device(status, torch.int32, (sp.shape[0],))
+    rows = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    flags = torch.empty(n, dtype=torch.int32, device=dev)
+    v = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    torch.cuda.current_stream(dev).synchronize()      # the engine's stream is non-blocking: the uploads and whatever last used this memory must have finished
+    _lib.check(lib.misti_parametric_rows_dev(ctx, sp.shape[0], v(sp), v(st), v(of), float(genome), n_sites, C.c_uint64(int(seed)), int(first), n,
+                                             v(rows), v(flags)))
+    _lib.check(lib.misti_sync(ctx))
+    if row_status:
+        return rows, flags
+    bad = int(flags.count_nonzero())
+    if bad:
+        raise ValueError("parametric bootstrap: %d of %d replicates have no usable spectrum (an entry negative or not finite, a sum that is "
+                         "not > 0, a status without a value or an index out of range); row_status=True returns the flags" % (bad, n))
+    return rows
+
+
+def _parametric_table(engine, ctx, device, split, params, data_row, n, n_sites, seed, band_bounds=None, pulse_times=None):
+    """``Engine.parametric_table`` with the point evaluated by ``engine`` (an Engine or a MultiEngine) and the rows drawn on ``ctx``."""
+    from .optimize import parametric_table
+    row = _f64(data_row, (8,))
+    kw = {} if pulse_times is None else {"pulse_times": pulse_times}
+    res = engine.evaluate([float(split)], [list(params)] if params is not None and len(params) else None, band_bounds=band_bounds, **kw)
+    if int(res.status[0]) != 0:
+        raise MistiError(int(res.status[0]), "parametric bootstrap: the generating point has no value: " + STATUS_TEXT.get(int(res.status[0]), "?"))
+    if n_sites is None:
+        n_sites = int(np.rint(row[1:].sum()))
+    rows = _parametric_rows(engine._lib, ctx, device, res.jafs[:1], n, n_sites, row[0], seed, 0, None, None, False)
+    return parametric_table(row, rows.cpu().numpy())
+
+
 class Engine:
     """One model on one GPU (``misti_create`` ... ``misti_destroy``).
 
@@ -350,6 +403,25 @@ class Engine:
         """The table ``io.bootstrap_table`` lays out, its replicates made by ``bootstrap_rows_dev``: a host ``ndarray [1 + n][8]``, row 0 the
         column sums of all chunks (added in chunk order), row 1 + r replicate r - ``optimize.block_bootstrap_table``, bit for bit."""
         return _bootstrap_table(self.bootstrap_rows_dev(chunks, n, seed=seed, normalize=normalize), chunks)
+
+    def parametric_rows_dev(self, spectra, n, n_sites, genome, seed=0, first=0, spec_of=None, status=None, row_status=False):
+        """``misti_parametric_rows_dev``: parametric-bootstrap replicates ``first ... first + n - 1`` made on this device - ``n_sites``
+        sites each, drawn independently from the seven classes of ``spectra[spec_of[r]]`` (spectrum 0 without ``spec_of``); a torch tensor
+        ``[n][8]`` float64, column 0 ``genome``.  ``spectra`` is an ndarray or a tensor of this device (the ``d_jafs`` an ``evaluate_dev``
+        wrote, read where it is), ``status`` likewise (the evaluation's statuses: a spectrum without a value is unusable).  The rule is
+        ``optimize.parametric_rows``, bit for bit; replicate r depends on ``(seed, r, spectrum, n_sites)`` alone.  A replicate without a
+        usable spectrum is a row of zeros with status 1: that raises, unless ``row_status=True`` asks for ``(rows, statuses)``.  The
+        tensor is an ordinary row buffer, usable wherever ``bootstrap_rows_dev``'s is.  NOTE: independent sites - real sites are
+        linked, so intervals from these rows are narrower than the block bootstrap's; where chunks exist that one is the confidence
+        statement.  Returns when the rows are there."""
+        return _parametric_rows(self._lib, self._ctx, self.device, spectra, n, n_sites, genome, seed, first, spec_of, status, row_status)
+
+    def parametric_table(self, split, params, data_row, n, n_sites=None, seed=0, band_bounds=None, pulse_times=None):
+        """The table ``[data_row; n replicates]`` (host ``ndarray [1 + n][8]``) of a parametric bootstrap from the point ``(split,
+        params)``: the point is evaluated, and the replicates are drawn from its spectrum with ``genome = data_row[0]`` and ``n_sites``
+        sites - by default ``rint`` of the sum of the data row's seven classes.  ``optimize.parametric_table(data_row,
+        optimize.parametric_rows(evaluate(...).jafs, ...))``, bit for bit.  Raises if the point has no value."""
+        return _parametric_table(self, self._ctx, self.device, split, params, data_row, n, n_sites, seed, band_bounds, pulse_times)
 
     def curvature(self, x, split_times, rows, table, band_bounds=None, pulse_times=None, rel_step=1e-2, abs_step=0.0, batch_limit=0):
         """``misti_curvature``: gradient and Hessian of the log-likelihood at every point ``x[P][n_param]`` (split ``split_times[p]``
@@ -799,6 +871,13 @@ class MultiEngine:
         _lib.check(self._lib.misti_multi_context(self._m, 0, C.byref(ctx), C.byref(dev)))
         rows, _ = _bootstrap_rows(self._lib, ctx, dev.value, chunks, n, seed, 0, normalize, False)
         return _bootstrap_table(rows, chunks)
+
+    def parametric_table(self, split, params, data_row, n, n_sites=None, seed=0, band_bounds=None):
+        """``Engine.parametric_table``, its replicates drawn on the first context of the list: a replicate depends on ``(seed, r)`` and the
+        spectrum alone, so one device makes the host rows and every context is handed the same ones."""
+        ctx, dev = C.c_void_p(), C.c_int(0)
+        _lib.check(self._lib.misti_multi_context(self._m, 0, C.byref(ctx), C.byref(dev)))
+        return _parametric_table(self, ctx, dev.value, split, params, data_row, n, n_sites, seed, band_bounds)
 
     def last_shards(self):
         """(candidates per context, chains per context) of the last ``evaluate``."""

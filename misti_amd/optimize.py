@@ -1058,3 +1058,75 @@ def block_bootstrap_table(chunks, n, seed=0, normalize=False):
     normalised: it is the data), row 1 + r replicate r of ``block_bootstrap``.  Float64 ``[1 + n][8]``."""
     c, _, _ = check_chunks(chunks)
     return np.vstack([_in_order_sum(c)[None, :], block_bootstrap(c, n, seed=seed, normalize=normalize)])
+
+
+# ------------------------------------------------------------------------------------------- parametric bootstrap ----
+# The rule of misti_parametric_rows_dev stated on the host (include/misti_hip.h, "parametric bootstrap"): the device result is this, bit
+# for bit.  Replicates for inputs that have no chunks to resample: every site is drawn INDEPENDENTLY from the seven classes of a
+# spectrum - the multinomial the data are scored as.  Real sites are linked: intervals from these replicates are narrower than the block
+# bootstrap's on the same genome, which remains the confidence statement where chunks exist (pass an effective n_sites to allow for it).
+PARAM_MAX_SITES = 1 << 36
+
+
+def parametric_thresholds(p):
+    """The six thresholds of a spectrum ``p[7]`` (``misti_parametric_thresholds``), or None where it is unusable.  ``c_k`` is the running
+    sum in class order (one float64 addition per class), ``q_k = c_k / c_6`` one float64 division each, ``T_k = ceil(q_k * 2**53)`` a
+    uint64 in ``[0, 2**53]`` - every step exact or correctly rounded, so host, device and NumPy agree.  Unusable: an entry that is
+    negative or not finite, or a running sum ``c_6`` that is not finite or not > 0.  ``p`` need not be normalised.  A class's
+    probability is quantised to ``2**-53``: no rejection step corrects that."""
+    p = np.asarray(p, dtype=np.float64)
+    if p.shape != (7,):
+        raise ValueError("parametric_thresholds: a spectrum is 7 numbers (got shape %s)" % (p.shape,))
+    with np.errstate(over="ignore", invalid="ignore"):
+        c = np.cumsum(p)                                              # sequential: ((p0 + p1) + p2) + ...
+    if not (np.isfinite(p).all() and (p >= 0).all() and np.isfinite(c[6]) and c[6] > 0):
+        return None
+    return np.ceil((c[:6] / c[6]) * 2.0 ** 53).astype(np.uint64)
+
+
+def parametric_counts(T, n_sites, seed, rep):
+    """The seven class counts of replicate ``rep`` under thresholds ``T`` (``misti_parametric_counts``): draw j is element j of
+    ``numpy.random.Philox(key=[seed, rep]).random_raw`` - the block bootstrap's stream and counter convention (``philox_draws``) -
+    ``u = raw >> 11``, and its class the number of k with ``u >= T[k]``: ``numpy.searchsorted(q, Generator(Philox(...)).random(n_sites),
+    side='right')``.  With ``g_k = #{j : u_j >= T_k}``: ``n_0 = n_sites - g_0``, ``n_k = g_(k-1) - g_k``, ``n_6 = g_5``.  int64 ``[7]``."""
+    n_sites = int(n_sites)
+    g = np.zeros(6, dtype=np.int64)
+    gen = np.random.Philox(key=np.array([int(seed), int(rep)], dtype=np.uint64))
+    left = n_sites
+    while left > 0:                                                   # in pieces of whole Philox blocks: the stream simply goes on
+        m = min(left, 1 << 22)
+        u = np.atleast_1d(np.asarray(gen.random_raw(m), dtype=np.uint64)) >> np.uint64(11)
+        u.sort()
+        g += m - np.searchsorted(u, T, side="left")                   # #{u >= T_k}
+        left -= m
+    return np.concatenate([[n_sites - g[0]], g[:-1] - g[1:], [g[5]]]).astype(np.int64)
+
+
+def parametric_rows(spectra, n, n_sites, genome, seed=0, first=0, spec_of=None, status=None):
+    """The rule of ``misti_parametric_rows_dev`` on the host: ``(rows, row_status)`` - replicates ``first ... first + n - 1`` as float64
+    ``[n][8]`` and int32 ``[n]``.  Replicate i (global index ``rep = first + i``) draws ``n_sites`` sites from spectrum ``spec_of[i]`` of
+    ``spectra[n_spec][7]`` (spectrum 0 without ``spec_of``) and is the row ``[genome, n_0, ..., n_6]`` of ``parametric_counts``: integers
+    that sum to ``n_sites`` exactly.  A replicate whose spectrum is unusable (``parametric_thresholds``), whose ``status`` entry is not 0
+    (the scorer's rule: only status 0 has a value) or whose index is outside ``0 ... n_spec - 1`` is ``[genome, 0 x 7]`` with row status 1.
+    A replicate depends on ``(seed, rep, p, n_sites)`` alone.  The sites are independent - see the note above."""
+    sp = np.ascontiguousarray(spectra, dtype=np.float64).reshape(-1, 7)
+    n, n_sites, first = int(n), int(n_sites), int(first)
+    if n < 0 or first < 0 or not 0 <= n_sites <= PARAM_MAX_SITES or sp.shape[0] < 1 or not np.isfinite(genome):
+        raise ValueError("parametric_rows: n and first not negative, 0 <= n_sites <= 2**36, at least one spectrum, a finite genome")
+    of = np.zeros(n, dtype=np.int64) if spec_of is None else np.asarray(spec_of, dtype=np.int64).reshape(n)
+    st = None if status is None else np.asarray(status, dtype=np.int64).reshape(sp.shape[0])
+    T = [parametric_thresholds(p) if st is None or st[s] == 0 else None for s, p in enumerate(sp)]
+    rows, row_status = np.zeros((n, 8)), np.zeros(n, dtype=np.int32)
+    rows[:, 0] = float(genome)
+    for i in range(n):
+        t = T[of[i]] if 0 <= of[i] < sp.shape[0] else None
+        if t is None:
+            row_status[i] = 1
+        else:
+            rows[i, 1:] = parametric_counts(t, n_sites, seed, first + i)
+    return rows, row_status
+
+
+def parametric_table(data_row, rows):
+    """The data row in front of the replicates, as ``block_bootstrap_table`` lays a table out: float64 ``[1 + n][8]``."""
+    return np.vstack([np.asarray(data_row, dtype=np.float64).reshape(1, 8), np.asarray(rows, dtype=np.float64).reshape(-1, 8)])
