@@ -592,8 +592,11 @@ int misti_nm_last_spec_iterations(misti_ctx* ctx, int64_t* n);
  * floating-point operations the kernels follow):
  *   - a point is D = n_param >= 1 parameters x, a FIXED split time and optionally its own band bounds and pulse times; the split is
  *     not a differentiated coordinate (the objective is piecewise in it);
- *   - steps h_i = max(rel_step |x_i|, abs_step), both step arguments finite and not negative, at least one positive;
- *   - a point with x_i - h_i < 0 for some i (or h_i == 0: a rate of 0 under abs_step == 0) has no two-sided stencil: status
+ *   - steps h_i = (x_i + max(rel_step |x_i|, abs_step)) - x_i in float64: the nominal step moved by at most half an ulp of x_i to
+ *     the one the doubles realise, so that x_i + h_i and x_i - h_i are exact and the quotients divide by the step taken (a
+ *     rounded abscissa would cost a second difference ulp(x) |dL| / h^2); both step arguments finite and not negative, at least
+ *     one positive;
+ *   - a point with x_i - h_i < 0 for some i (or h_i == 0: a rate of 0 under abs_step == 0, or a nominal step below half an ulp of x_i) has no two-sided stencil: status
  *     MISTI_CURV_BOUNDARY, none of its stencil points is evaluated (one-sided stencils are out of scope);
  *   - M = 1 + 2 D^2 candidates: 0 the centre; 1 + 2i is +h_i, 2 + 2i is -h_i; for the pairs i < j in lexicographic order, of rank
  *     q, 1 + 2D + 4q + {0, 1, 2, 3} are (+h_i, +h_j), (+h_i, -h_j), (-h_i, +h_j), (-h_i, -h_j);

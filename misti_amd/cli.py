@@ -85,8 +85,9 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               resamples) also the sandwich standard error H^-1 (A C A^T) H^-1 of a composite likelihood, C the
                               covariance of the class counts over those rows.  Not offered with --gpus N > 1, --devices, --fit-st,
                               --hops, --sweep or --sweep-pu; grid mode needs --grid-solve for it.  Every other line stays as it is
-    --se-step REL             with --se (refused without): the relative step of the stencil, h_i = REL x |rate_i| (default 1e-2: an
-                              unmeasured choice)
+    --se-step REL             with --se (refused without): the relative step of the stencil, h_i = REL x |rate_i|, adjusted by at most
+                              half an ulp of the rate so that rate +- h_i are exact (default 1e-2:
+                              DESIGN.md section 4 measures it; a rate near zero needs an absolute step)
     --gpus N                  the sweep on N GPUs of the node: this process starts N ranks (one per GPU, torch.distributed over
                               RCCL), whole lambda-correction chains are dealt to the ranks, one all_gather, rank 0 prints
     --devices 0,1,...         the sweep on a LIST of devices from this one process (misti_create_multi: one context and one host
@@ -313,7 +314,7 @@ def se_error(a):
 
 
 def _se_step(a):
-    """--se-step, or its default: optimize.CURV_REL_STEP (1e-2, an unmeasured choice)."""
+    """--se-step, or its default: optimize.CURV_REL_STEP (1e-2; measured in DESIGN.md section 4)."""
     from .optimize import CURV_REL_STEP
     return CURV_REL_STEP if a.se_step is None else a.se_step
 

@@ -1698,7 +1698,7 @@ int curvature_impl(misti_ctx* c, int64_t n_point, const double* x, const double*
         for (int i = 0; i < D; ++i) {
             const double xi = x[p * D + i];
             if (!std::isfinite(xi)) return fail(MISTI_E_ARG, "x[%lld][%d] is not finite", (long long)p, i);
-            const double hi = std::fmax(rel_step * std::fabs(xi), abs_step);
+            const double hi = (xi + std::fmax(rel_step * std::fabs(xi), abs_step)) - xi;
             boundary = boundary || xi - hi < 0.0 || hi == 0.0;
         }
         n_live += boundary ? 0 : 1;

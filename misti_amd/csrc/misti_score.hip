@@ -421,7 +421,7 @@ hipError_t launch_llk(int64_t n_cand, const double* jafs, const int32_t* status,
 // q-th pair i < j (lexicographic) 1 + 2D + 4q + {0, 1, 2, 3} the steps (+,+), (+,-), (-,+), (-,-).
 __host__ __device__ __forceinline__ int curv_pair_rank(int i, int j, int D) { return i * D - i * (i + 1) / 2 + (j - i - 1); }
 
-// thread = point: h[p][i] = max(rel |x_i|, abs); a point with a step that leaves the positive half-line (x_i - h_i < 0), or with no
+// thread = point: h[p][i] = (x_i + max(rel |x_i|, abs)) - x_i, the step the doubles realise; a point with a step that leaves the positive half-line (x_i - h_i < 0), or with no
 // step at all (h_i == 0: a rate of 0 under a purely relative step), has no two-sided stencil: MISTI_CURV_BOUNDARY.
 __global__ __launch_bounds__(256)
 void curv_steps_kernel(int64_t n_point, int D, const double* __restrict__ x, double rel_step, double abs_step,
@@ -431,7 +431,7 @@ void curv_steps_kernel(int64_t n_point, int D, const double* __restrict__ x, dou
     bool boundary = false;
     for (int i = 0; i < D; ++i) {
         const double xi = x[p * D + i];
-        const double hi = fmax(rel_step * fabs(xi), abs_step);
+        const double hi = (xi + fmax(rel_step * fabs(xi), abs_step)) - xi;    // the realised step: xi + hi and (for hi <= xi; else boundary) xi - hi are exact
         h[p * D + i] = hi;
         boundary = boundary || xi - hi < 0.0 || hi == 0.0;
     }

@@ -429,7 +429,8 @@ class Engine:
         ``pulse_times[P][n_pulse]``) by central differences of the class logs over ``optimize.curvature_stencil``'s
         ``1 + 2 n_param^2`` candidates per point - laid out on the device, evaluated through the batch path in batches of at most
         ``batch_limit`` candidates (0: the library's choice; whole points only), assembled and contracted there.  ``rel_step`` /
-        ``abs_step``: ``h_i = max(rel_step |x_i|, abs_step)``; the default 1e-2 is an unmeasured choice.  A point with
+        ``abs_step``: ``h_i = (x_i + max(rel_step |x_i|, abs_step)) - x_i`` (the realised step: ``x_i +- h_i`` are exact doubles); what the default 1e-2 costs in truncation is measured in DESIGN.md
+        section 4 ("Curvature at a fitted point", paragraph "Measured"), with the advice for a rate near zero.  A point with
         ``x_i - h_i < 0`` gets status 7 and is not evaluated.  Returns a ``CurvatureResult``; ``optimize.observed_covariance`` /
         ``sandwich_covariance`` / ``standard_errors`` take it from there."""
         D = self.n_param
@@ -446,7 +447,7 @@ class Engine:
         status = np.empty(P, dtype=np.int32)
         _lib.check(self._lib.misti_curvature(self._ctx, P, ptr(xs), ptr(st), ptr(r_of), ptr(bb), ptr(pt), tab.shape[0], ptr(tab),
                                              float(rel_step), float(abs_step), int(batch_limit), ptr(llh0), ptr(grad), ptr(hess), ptr(dlog), ptr(status)))
-        h = np.maximum(float(rel_step) * np.abs(xs), float(abs_step))             # curv_steps_kernel's two operations
+        h = (xs + np.maximum(float(rel_step) * np.abs(xs), float(abs_step))) - xs  # curv_steps_kernel's four operations
         return CurvatureResult(llh0, grad, hess, dlog, h, status)
 
     def curvature_assemble_dev(self, n_point, d_jafs, d_status, d_h, d_rows, n_rep, d_jsfs, d_dlog=0, d_d2log=0, d_grad=0, d_hess=0, d_point_status=0):

@@ -759,7 +759,7 @@ def sweep_interval(llh, values, x=None):
 # the same floating-point operations in the same order.
 CURV_BOUNDARY = 7         # MISTI_CURV_BOUNDARY
 CURV_NUMERIC = 5          # MISTI_NUMERIC
-CURV_REL_STEP = 1e-2      # default relative step: an UNMEASURED choice (no study of truncation against the engine's noise yet)
+CURV_REL_STEP = 1e-2      # default relative step: its truncation is measured in DESIGN.md section 4 ("Measured"; tests/test_curvature_exact_cpu.py)
 
 
 def curvature_size(D):
@@ -768,7 +768,10 @@ def curvature_size(D):
 
 
 def curvature_stencil(x, rel_step=CURV_REL_STEP, abs_step=0.0):
-    """The stencil of ``misti_curvature``.  ``x`` is ``[P][D]`` (or ``[D]``: one point).  Steps ``h_i = max(rel_step |x_i|, abs_step)``;
+    """The stencil of ``misti_curvature``.  ``x`` is ``[P][D]`` (or ``[D]``: one point).  Steps ``h_i = (x_i + max(rel_step |x_i|,
+    abs_step)) - x_i`` in float64 - the nominal step moved by at most half an ulp of ``x_i`` to the one for which ``x_i + h_i`` and
+    ``x_i - h_i`` are both exact (for ``h_i <= x_i``; a larger step makes a boundary point anyway), so that the quotients divide by the step the candidates really take (a rounded abscissa costs a second
+    difference ``ulp(x) |dL| / h^2``, which does not fall with ``h``; a nominal step below half an ulp of ``x_i`` gives ``h_i == 0``);
     ``M = 1 + 2 D^2`` points per stencil: 0 the centre; ``1 + 2i`` is ``+h_i``, ``2 + 2i`` is ``-h_i``; for the pairs ``i < j`` in
     lexicographic order, of rank q, ``1 + 2D + 4q + (0, 1, 2, 3)`` are ``(+h_i, +h_j)``, ``(+h_i, -h_j)``, ``(-h_i, +h_j)``,
     ``(-h_i, -h_j)``.  A point with some ``x_i - h_i < 0`` (or ``h_i == 0``: a rate of 0 under a purely relative step) is a BOUNDARY
@@ -783,7 +786,7 @@ def curvature_stencil(x, rel_step=CURV_REL_STEP, abs_step=0.0):
     P, D = x.shape
     if D < 1:
         raise ValueError("a point needs at least one parameter")
-    h = np.maximum(rel_step * np.abs(x), abs_step)
+    h = (x + np.maximum(rel_step * np.abs(x), abs_step)) - x          # the step the doubles realise: x + h and x - h are exact
     boundary = ((x - h < 0) | (h == 0)).any(axis=1)
     pts = np.repeat(x[:, None, :], curvature_size(D), axis=1)
     up, down = x + h, x - h

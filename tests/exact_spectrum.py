@@ -12,7 +12,8 @@ infinite interval is -M^-1 x (with two populations and mu0 + mu1 = 0 there is no
 
 Input: an ``oracle.misti_oracle.OracleModel`` built with ``trueEPS=True`` on which ``map_parameters`` and ``correct_lambdas``
 have run, so that ``lc`` holds the rates the spectrum is taken with.  Its ``numT``, ``splitT`` (a fractional split's interval
-already inserted), ``sampleDate``, ``mi``, ``pu``, ``lc`` and ``times`` are read; doubles are taken at their exact values.
+already inserted), ``sampleDate``, ``mi``, ``pu``, ``lc`` and ``times`` are read; doubles are taken at their exact values, and an
+mpf in their place as it is (tests/golden/make_curvature_exact.py differentiates the spectrum with steps no double can hold).
 """
 import mpmath as mp
 
@@ -82,10 +83,11 @@ def interval(M, x, T):
     return P1, integ
 
 
-def raw_spectrum(om, dps=DPS):
-    """The seven unnormalised classes of the expected spectrum (mpf), JAFSpectrum :467-506."""
+def raw_spectrum(om, dps=DPS, interval=interval):
+    """The seven unnormalised classes of the expected spectrum (mpf), JAFSpectrum :467-506.  `interval`: a stand-in for the
+    function of that name (a generator that meets the same interval many times passes a memoising one)."""
     with mp.workdps(dps):
-        f = lambda v: mp.mpf(float(v))
+        f = lambda v: v if isinstance(v, mp.mpf) else mp.mpf(float(v))    # an mpf passes as it is (make_curvature_exact.py)
         N = TWO_POP.N
         split, numT, sd = om.splitT, om.numT, om.sampleDate
         x = mp.matrix(N, 1)
@@ -120,10 +122,10 @@ def raw_spectrum(om, dps=DPS):
         return jafs
 
 
-def spectrum(om, dps=DPS):
+def spectrum(om, dps=DPS, interval=interval):
     """The normalised spectrum (7 mpf), as JAFSLikelihood normalises it (:583-584)."""
     with mp.workdps(dps):
-        raw = raw_spectrum(om, dps)
+        raw = raw_spectrum(om, dps, interval)
         tot = mp.fsum(raw)
         return [v / tot for v in raw]
 

@@ -22,7 +22,8 @@ def test_stencil_order_and_count(D):
     pts, h, boundary = curvature_stencil(x, 1e-2, 0.0)
     M = 1 + 2 * D * D
     assert curvature_size(D) == M and pts.shape == (2, M, D) and h.shape == (2, D) and not boundary.any()
-    assert same_bits(h, 1e-2 * np.abs(x))
+    assert same_bits(h, (x + 1e-2 * np.abs(x)) - x) and (np.abs(h - 1e-2 * x) <= np.spacing(x) / 2).all()
+    assert same_bits(pts[:, 1, 0] - x[:, 0], h[:, 0]) and same_bits(x[:, 0] - pts[:, 2, 0], h[:, 0])     # the realised step, exactly
     for p in range(2):
         want = [list(x[p])]
         for i in range(D):
@@ -40,7 +41,7 @@ def test_stencil_order_and_count(D):
         assert len(want) == M and same_bits(pts[p], np.array(want))
     # the absolute step wins where it is the larger one; a single point may come as a vector
     pts1, h1, b1 = curvature_stencil(x[0], 1e-2, 0.01)
-    assert pts1.shape == (1, M, D) and same_bits(h1[0], np.maximum(1e-2 * x[0], 0.01)) and not b1[0]
+    assert pts1.shape == (1, M, D) and same_bits(h1[0], (x[0] + np.maximum(1e-2 * x[0], 0.01)) - x[0]) and not b1[0]
 
 
 def test_stencil_boundary_rule():
@@ -51,7 +52,7 @@ def test_stencil_boundary_rule():
                   [h0, 1.0],            # x - h == 0: a two-sided stencil that touches 0
                   [1.0, 1.0]])
     pts, h, boundary = curvature_stencil(x, 0.0, h0)
-    assert list(boundary) == [True, True, False, False] and (h == h0).all()
+    assert list(boundary) == [True, True, False, False] and (h[:3, 0] == h0).all() and (np.abs(h - h0) <= np.spacing(x) / 2).all()
     assert pts[2, 2, 0] == 0.0
     # under a purely relative step a rate of 0 has no step at all: a boundary point as well; any other positive rate has a stencil
     _, h, boundary = curvature_stencil(x, 1e-2, 0.0)
