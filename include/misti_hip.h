@@ -307,6 +307,35 @@ int misti_bootstrap_rows_dev(misti_ctx* ctx, int64_t n_chunk, const double* chun
  * or a NULL idx with n > 0; MISTI_E_LIMIT for n_chunk > MISTI_BOOT_MAX_CHUNKS or n > MISTI_BOOT_MAX_DRAWS. */
 int misti_bootstrap_draws(uint64_t seed, int64_t rep, int64_t n_chunk, int64_t n, int64_t* idx /* HOST [n] */);
 
+/* ---- block jackknife: the delete-m leave-out rows ----------------------------------- */
+/* The other resampling scheme of a chunked JSFS: the delete-m block jackknife, the standard one for statistics of linked sites along
+ * a genome.  Deterministic - nothing is drawn, there is no stream and no seed - and G fits instead of a thousand.  The reference has
+ * no counterpart.  The rule (optimize.jackknife_rows states it in NumPy; the device result is that, bit for bit):
+ *   - chunks[n_chunk][8], HOST memory, as for the block bootstrap: column 0 the chunk's length, columns 1..7 its class counts;
+ *   - group g covers chunks g m ... min((g + 1) m, n_chunk) - 1; there are G = ceil(n_chunk / m) groups, the last one may be short;
+ *   - row g starts at eight zeros and walks the chunks in chunk order: for every chunk OUTSIDE group g it adds the chunk's 8 columns
+ *     to its own, one float64 addition per column per chunk.  A chunk inside the group is skipped - it is not added as zero, and the
+ *     row is not "the total minus the group": that fixed order is what makes the result a matter of bits for counts that are no
+ *     integers;
+ *   - no normalisation: scaling a row does not move the arg-max of the multinomial log-likelihood.
+ * Column 0 of row g is the length left in: with row 0 of a table (the column sums of all chunks, the caller's:
+ * Engine.jackknife_table puts it in front) it gives the weights of the delete-m estimator (optimize.jackknife_estimate).
+ * Writes groups first_group ... first_group + n_group - 1 to d_rows[0 ... n_group) (a table made in two calls equals the table made
+ * in one).  d_rows is an ordinary row buffer: misti_eval_batch_dev, misti_llk_dev, the scans and the searches take it as d_jsfs.
+ * Launch: one lane per group in workgroups of 256; every lane walks all chunks, staged through LDS in tiles of 1 024 rows (64 KiB)
+ * in chunk order, so that at every step all lanes read the same row: a broadcast.
+ * Checked on the host before anything touches the device (and before ctx is looked at): MISTI_E_ARG for n_chunk < 2, m < 1,
+ * m >= n_chunk (a single group would leave nothing behind), a negative first_group or n_group, first_group + n_group > G, non-zero
+ * flags, a NULL chunks / d_rows with work to do, a non-finite entry, a negative count, or a chunk length that is not > 0;
+ * MISTI_E_LIMIT for n_chunk > MISTI_BOOT_MAX_CHUNKS.  The bootstrap's draw limit does not apply: the loop is bounded by n_chunk.
+ * n_group == 0 writes nothing.  Asynchronous on the context's stream (the chunk table is copied before the call returns). */
+int misti_jackknife_rows_dev(misti_ctx* ctx, int64_t n_chunk, const double* chunks /* HOST [n_chunk][8] */,
+                             int64_t m, int64_t first_group, int64_t n_group, uint32_t flags /* must be 0 */,
+                             double* d_rows /* DEVICE [n_group][8] */);
+/* G = ceil(n_chunk / m), on the host without a context: MISTI_E_ARG for n_chunk < 2, m < 1, m >= n_chunk or a NULL n_group,
+ * MISTI_E_LIMIT for n_chunk > MISTI_BOOT_MAX_CHUNKS. */
+int misti_jackknife_geometry(int64_t n_chunk, int64_t m, int64_t* n_group);
+
 /* ---- parametric bootstrap: replicate rows drawn from a spectrum -------------------- */
 /* Makes replicate rows where there are no chunks to resample (a one-row JSFS: the reference's README example, a realSFS 2-D spectrum,
  * MS2JSFS.py's sim.jafs): n_rep tables of n_sites sites, every site drawn independently from the seven classes of a spectrum - the

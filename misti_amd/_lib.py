@@ -113,6 +113,8 @@ SYMBOLS = {
     "misti_scan_profile_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_bootstrap_rows_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "misti_bootstrap_draws": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "misti_jackknife_rows_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p]),
+    "misti_jackknife_geometry": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p]),
     "misti_parametric_rows_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_uint64, C.c_int64,
                                             C.c_int64, C.c_void_p, C.c_void_p]),
     "misti_parametric_thresholds": (C.c_int, [C.c_void_p, C.c_void_p]),

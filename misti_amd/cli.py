@@ -32,6 +32,17 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               --bootstrap remains the confidence statement (--sites M may pass an effective number of sites).
                               --bootstrap-out FILE keeps the table (--all-bs on it repeats stage 2).  Not offered with --bootstrap,
                               --bs-normalize (there is nothing to normalise) or -bs K
+    --jackknife M             with --fit-st or --grid-solve (M >= 1): the rows of the JSFS file are CHUNKS, as for --bootstrap; the delete-M block
+                              jackknife's table - row 0 the sum of all chunks, then G = ceil(chunks / M) leave-out rows, row g the chunks
+                              outside group g added in chunk order - is made on the device (misti_jackknife_rows_dev) and replaces the
+                              rows; implies --all-bs.  Deterministic: no seed.  Behind the lines of row 0 the mode prints `jackknife:`
+                              lines in place of the bootstrap t-interval: for the fitted split (--fit-st) and every rate the estimate,
+                              the bias-corrected jackknife estimate, the bias, the standard error, the t-interval and the groups used
+                              (optimize.jackknife_estimate: the weighted delete-m jackknife, weights from column 0 of the table).
+                              --jackknife 0: the file already IS such a table (row 0 the data, rows 1.. the leave-out rows), nothing is
+                              made; --jackknife-out FILE keeps the table of --jackknife M (--jackknife 0 --all-bs on it repeats the run).
+                              Not offered with --bootstrap, --parametric, -bs K, --se, --sweep / --sweep-pu, or a mode that scans (plain
+                              grid mode, --top, --polish, --profile: the arg-max over a grid does not move when one block is left out)
     --grid-solve              with --grid-st and/or --all-bs: for every (row, split) pair the reference's Solve from the
                               -mi/-pu initial values (the --grid-mi mesh points as starts: the best per pair), all pairs
                               in ONE batched search on the device; per pair the line MiSTI.py:240 prints (the test.bs
@@ -166,6 +177,12 @@ def build_parser():
                         "sites are linked: intervals from these replicates are narrower than a block bootstrap's (--bootstrap, where the file has chunks)")
     p.add_argument("--sites", type=int, default=None, metavar="M",
                    help="with --parametric: sites per replicate (default: the data row's number of sites; fewer = an effective number of independent sites)")
+    p.add_argument("--jackknife", type=int, default=None, metavar="M",
+                   help="with --fit-st / --grid-solve: the JSFS rows are chunks: make the delete-M block jackknife's 1 + G-row table on the device (row 0 the "
+                        "sum of all chunks, then the leave-out rows of groups of M chunks) and print jackknife: lines - estimate, bias-corrected estimate, "
+                        "bias, standard error, t-interval - for the fitted split and every rate; implies --all-bs; M = 0: the file already is such a table")
+    p.add_argument("--jackknife-out", type=str, default=None, metavar="FILE",
+                   help="with --jackknife M >= 1: write the table that was made as a #MiSTI_JSFS file (--jackknife 0 --all-bs on it repeats the run)")
     p.add_argument("--gpus", type=int, default=1, help="grid mode: start this many ranks, one per GPU (replaces `parallel -j N ./MiSTI.py ...`)")
     p.add_argument("--devices", type=str, default="", help="grid mode: comma-separated device list evaluated from this one process (misti_create_multi)")
     p.add_argument("--grid-solve", action="store_true",
@@ -288,6 +305,65 @@ def parametric_rows(a, inp, data_row, pop1=None, pop2=None):
         with open(os.path.join(a.wd, a.bootstrap_out), "w") as fw:
             fw.write(mio.format_jsfs(table, pop1, pop2))
     return table
+
+
+JACKKNIFE_NEEDS_A_FIT = "the arg-max over a grid does not move when one block is left out; fit with --fit-st or --grid-solve"
+
+
+def jackknife_error(a):
+    """Why ``--jackknife`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.jackknife is None:
+        return "--jackknife-out keeps the table of --jackknife M: give --jackknife M with M >= 1" if a.jackknife_out is not None else None
+    if a.jackknife < 0:
+        return "--jackknife M: the group size must not be negative (got %d; 0: the file already is a jackknife table)" % a.jackknife
+    if a.jackknife_out is not None and a.jackknife < 1:
+        return "--jackknife-out keeps the table --jackknife M makes: with --jackknife 0 nothing is made - give M >= 1"
+    if a.bootstrap is not None or a.parametric is not None:
+        return "--jackknife leaves blocks out, --bootstrap / --parametric draw replicates: give one of them"
+    if a.bsMode != -1:
+        return "--jackknife replaces the rows of the file by its table and fits every row: -bs K is not offered with it"
+    if a.se:
+        return "--jackknife states its own standard error from the leave-out fits: --se is not offered with it"
+    if a.top is not None or a.polish or a.profile is not None or a.sweep or a.sweep_pu or not (a.fit_st or a.grid_solve):
+        return "--jackknife: " + JACKKNIFE_NEEDS_A_FIT
+    return None
+
+
+def jackknife_rows(a, inp, rows, pop1=None, pop2=None):
+    """The table of ``--jackknife M``: the file's rows are the chunks, the device makes the leave-out rows (Engine.jackknife_table on this
+    process's device - a rank of --gpus N makes the same table itself: it depends on the chunks and M alone); with --jackknife-out the
+    table is written through the JSFS writer (by rank 0)."""
+    from .dist import env_rank
+    rank, local, world = env_rank()
+    device = local if world > 1 else (int(a.devices.split(",")[0]) if a.devices else a.device)
+    with Engine(inp.times, inp.lambdas, device=device) as e:
+        table = e.jackknife_table(rows, a.jackknife)
+    table = table.tolist()
+    if a.jackknife_out is not None and rank == 0:
+        with open(os.path.join(a.wd, a.jackknife_out), "w") as fw:
+            fw.write(mio.format_jsfs(table, pop1, pop2))
+    return table
+
+
+def print_jackknife(names, theta, lengths):
+    """The ``jackknife:`` lines: per named quantity (``theta[1 + G][K]``: row 0's estimate, then the leave-out rows'; NaN where a row
+    has no fit) the weighted delete-m jackknife of optimize.jackknife_estimate, weighted by ``lengths`` - column 0 of the table.
+    Numbers are printed with repr: they read back exactly."""
+    from .optimize import jackknife_estimate
+    try:
+        est = jackknife_estimate(np.asarray(theta, dtype=float).reshape(len(lengths), len(names)), lengths)
+    except ValueError as e:
+        print("jackknife: no interval:", e)
+        return
+    for k, name in enumerate(names):
+        if not np.isfinite(est["estimate"][k]):
+            print("jackknife:", name, "\tbs_id = 0 has no fit: no estimate")
+        elif est["n_group"][k] < 2:
+            print("jackknife:", name, "\tno interval (%d leave-out rows with a fit; at least 2 needed)" % est["n_group"][k])
+        else:
+            print("jackknife:", name, "\testimate = %r \tjackknife = %r \tbias = %r \tse = %r \tinterval = [%r, %r] \tgroups = %d"
+                  % (float(est["estimate"][k]), float(est["jackknife"][k]), float(est["bias"][k]), float(est["se"][k]),
+                     float(est["interval"][k, 0]), float(est["interval"][k, 1]), int(est["n_group"][k])))
 
 
 def se_error(a):
@@ -783,7 +859,13 @@ def grid_solve(a, inp, rows):
     else:
         print("grid-solve: bs_id =", ids[0], "best splitT =", iv["data_split"], "optim = [" + ", ".join(str(v) for v in iv["data_x"]) + "]",
               "llh =", iv["data_llh"])
-    if iv["interval"] is None:
+    if a.jackknife is not None:
+        # every rate at the row's own best split (NaN for a row without a finite llh at any split)
+        has = np.isfinite(prof["llh"]).any(axis=1)
+        at = np.argmax(np.where(np.isfinite(prof["llh"]), prof["llh"], -np.inf), axis=1)
+        theta = np.where(has[:, None], prof["x"][np.arange(data.shape[0]), at], np.nan)
+        print_jackknife(["optim[%d]" % i for i in range(k)], theta, data[:, 0])
+    elif iv["interval"] is None:
         print("grid-solve: no bootstrap interval (%d bootstrap rows with a best split; at least 2 needed)" % iv["n_boot"])
     else:
         print("grid-solve: bootstrap best splitT mean =", iv["mean"], "97.5%% t-interval = [%r, %r]" % tuple(float(v) for v in iv["interval"]),
@@ -825,7 +907,11 @@ def fit_st(a, inp, rows):
         print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, fit["x"][r, :k], fit["llh"][r])
               + (_hops_text(fit, r) if a.hops else ""))
     print()
-    if a.all_bs:
+    if a.jackknife is not None:
+        has = np.isfinite(fit["llh"]) & np.isfinite(fit["split"])
+        theta = np.where(has[:, None], np.hstack([fit["split"][:, None], fit["x"][:, :k]]), np.nan)
+        print_jackknife(["splitT"] + ["optim[%d]" % i for i in range(k)], theta, data[:, 0])
+    elif a.all_bs:
         iv = split_fit_interval(fit["split"], fit["llh"])
         if iv["interval"] is None:
             print("fit-st: no bootstrap interval (%d bootstrap rows with a fitted split; at least 2 needed)" % iv["n_boot"])
@@ -967,12 +1053,12 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
+    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2
-    if a.bootstrap is not None or a.parametric is not None:
-        a.all_bs = True                                     # every mode below sees a bootstrap table
+    if a.bootstrap is not None or a.parametric is not None or a.jackknife is not None:
+        a.all_bs = True                                     # every mode below sees a bootstrap (or jackknife) table
     # the two ways of using several GPUs exclude each other: N ranks that each opened the whole device list would run N x D contexts
     if a.gpus > 1 and a.devices:
         print("--gpus (one rank per GPU) and --devices (a device list in one process) exclude each other", file=sys.stderr)
@@ -1013,6 +1099,16 @@ def main(argv=None):
         except ValueError as e:
             print("--bootstrap: %s: %s" % (fj, e), file=sys.stderr)
             return 2
+    if a.jackknife is not None:
+        from .optimize import check_jackknife, jackknife_weights
+        try:
+            if a.jackknife >= 1:
+                check_jackknife(rows, a.jackknife)          # what the ABI would refuse, said before the GPU is touched
+            else:
+                jackknife_weights([r[0] for r in rows])     # the file is the table: its column 0 must be one's
+        except ValueError as e:
+            print("--jackknife: %s: %s" % (fj, e), file=sys.stderr)
+            return 2
     if a.bsMode == -1:
         inputSFS = [sum(r[i] for r in rows) for i in range(8)]
     else:
@@ -1026,6 +1122,10 @@ def main(argv=None):
         rows = bootstrap_rows(a, inp, rows, pop1, pop2)
         print("Bootstrap: %d replicates of %d chunks drawn on the device (seed %d%s): the project's own stream, not the reference's"
               % (a.bootstrap, n_chunk, a.bs_seed or 0, ", normalized" if a.bs_normalize else ""))
+    if a.jackknife:
+        n_chunk = len(rows)
+        rows = jackknife_rows(a, inp, rows, pop1, pop2)
+        print("Jackknife: %d leave-out rows of %d chunks in groups of %d made on the device" % (len(rows) - 1, n_chunk, a.jackknife))
     if a.parametric is not None:
         rows = parametric_rows(a, inp, inputSFS, pop1, pop2)
         if rows is None:

@@ -78,9 +78,11 @@ int failb(int code, const char* fmt, ...) {
     return misti_set_error_(code, buf);
 }
 
-// What a chunk table must be for the loop to end, and the two sums of the rule: genome = the lengths added in chunk order, seg = the
-// running sum over the chunks of ((c1 + c2) + ... + c7).
-int check_chunks(int64_t n_chunk, const double* chunks, double* genome, double* seg) {
+}  // namespace
+
+// internal (misti_jack.hip shares it): what every entry of a chunk table must be, whoever resamples it - finite, a length > 0, no negative
+// count, sums that stay finite - and the sums themselves with the shortest length.  The bootstrap's draw limit is not part of it.
+extern "C" int misti_chunk_entries_(int64_t n_chunk, const double* chunks, double* genome, double* seg, double* shortest_out) {
     double g = 0.0, sg = 0.0, shortest = INFINITY;
     for (int64_t i = 0; i < n_chunk; ++i) {
         const double* c = chunks + i * 8;
@@ -94,11 +96,23 @@ int check_chunks(int64_t n_chunk, const double* chunks, double* genome, double* 
         shortest = c[0] < shortest ? c[0] : shortest;
     }
     if (!std::isfinite(g) || !std::isfinite(sg)) return failb(MISTI_E_ARG, "the chunk lengths or counts do not sum to a finite number");
+    *genome = g;
+    *seg = sg;
+    *shortest_out = shortest;
+    return 0;
+}
+
+namespace {
+
+// What a chunk table must be for the loop to end, and the two sums of the rule: genome = the lengths added in chunk order, seg = the
+// running sum over the chunks of ((c1 + c2) + ... + c7).
+int check_chunks(int64_t n_chunk, const double* chunks, double* genome, double* seg) {
+    double shortest = INFINITY;
+    if (int r = misti_chunk_entries_(n_chunk, chunks, genome, seg, &shortest)) return r;
+    const double g = *genome;
     // the most draws a replicate can need; the comparison is made in floating point, where an infinite quotient is simply too large
     if (!(std::ceil(g / shortest) <= (double)MISTI_BOOT_MAX_DRAWS))
         return failb(MISTI_E_LIMIT, "a replicate may need ceil(%g / %g) draws, beyond MISTI_BOOT_MAX_DRAWS = %d", g, shortest, (int)MISTI_BOOT_MAX_DRAWS);
-    *genome = g;
-    *seg = sg;
     return 0;
 }
 

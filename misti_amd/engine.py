@@ -131,6 +131,29 @@ def _bootstrap_table(rows_dev, chunks):
     return np.vstack([_in_order_sum(_f64(chunks, (-1, 8)))[None, :], rows_dev.cpu().numpy()])
 
 
+def _jackknife_rows(lib, ctx, device, chunks, m, first, n):
+    """``misti_jackknife_rows_dev`` on context ``ctx`` of ``device`` into a fresh torch tensor ``rows[n][8]`` float64: leave-out rows
+    ``first ... first + n - 1`` (``n`` None: all from ``first``; ``misti_jackknife_geometry`` says how many there are).  Waits for the
+    context's stream: the tensor is ready for any stream."""
+    import torch
+    c = _f64(chunks, (-1, 8))
+    m, first = int(m), int(first)
+    if n is None:
+        G = C.c_int64(0)
+        _lib.check(lib.misti_jackknife_geometry(c.shape[0], m, C.byref(G)))
+        n = G.value - first
+    n = int(n)
+    if n < 0 or first < 0:
+        raise ValueError("jackknife: first and the number of rows must not be negative (got %d, %d)" % (first, n))
+    dev = torch.device("cuda", int(device))
+    rows = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()      # the engine's stream is non-blocking: whatever last used this memory must have finished
+    _lib.check(lib.misti_jackknife_rows_dev(ctx, c.shape[0], c.ctypes.data_as(C.c_void_p), m, first, n, 0,
+                                            C.c_void_p(rows.data_ptr()) if n else None))
+    _lib.check(lib.misti_sync(ctx))
+    return rows
+
+
 def _parametric_rows(lib, ctx, device, spectra, n, n_sites, genome, seed, first, spec_of, status, row_status):
     """``misti_parametric_rows_dev`` on context ``ctx`` of ``device`` into fresh torch tensors: ``rows[n][8]`` float64 and the row
     statuses ``[n]`` int32.  ``spectra`` (``[n_spec][7]`` float64), ``spec_of`` and ``status`` (int32) are ndarrays - uploaded - or
@@ -403,6 +426,18 @@ class Engine:
         """The table ``io.bootstrap_table`` lays out, its replicates made by ``bootstrap_rows_dev``: a host ``ndarray [1 + n][8]``, row 0 the
         column sums of all chunks (added in chunk order), row 1 + r replicate r - ``optimize.block_bootstrap_table``, bit for bit."""
         return _bootstrap_table(self.bootstrap_rows_dev(chunks, n, seed=seed, normalize=normalize), chunks)
+
+    def jackknife_rows_dev(self, chunks, m=1, first=0, n=None):
+        """``misti_jackknife_rows_dev``: delete-m leave-out rows ``first ... first + n - 1`` (``n`` None: all from ``first``) of the chunk
+        table ``chunks[n_chunk][8]``, made on this device - a torch tensor ``[n][8]`` float64.  Row g is the chunks outside group
+        ``g m ... min((g + 1) m, n_chunk) - 1`` added in chunk order: ``optimize.jackknife_rows``, bit for bit.  The tensor is an
+        ordinary row buffer, usable wherever ``bootstrap_rows_dev``'s is."""
+        return _jackknife_rows(self._lib, self._ctx, self.device, chunks, m, first, n)
+
+    def jackknife_table(self, chunks, m=1):
+        """A host ``ndarray [1 + G][8]``: row 0 the column sums of all chunks (added in chunk order), row 1 + g leave-out row g of
+        ``jackknife_rows_dev`` - ``optimize.jackknife_table``, bit for bit.  Its column 0 is what ``optimize.jackknife_estimate`` weighs by."""
+        return _bootstrap_table(self.jackknife_rows_dev(chunks, m), chunks)
 
     def parametric_rows_dev(self, spectra, n, n_sites, genome, seed=0, first=0, spec_of=None, status=None, row_status=False):
         """``misti_parametric_rows_dev``: parametric-bootstrap replicates ``first ... first + n - 1`` made on this device - ``n_sites``
@@ -872,6 +907,13 @@ class MultiEngine:
         _lib.check(self._lib.misti_multi_context(self._m, 0, C.byref(ctx), C.byref(dev)))
         rows, _ = _bootstrap_rows(self._lib, ctx, dev.value, chunks, n, seed, 0, normalize, False)
         return _bootstrap_table(rows, chunks)
+
+    def jackknife_table(self, chunks, m=1):
+        """``Engine.jackknife_table``, made on the first context of the list: the rows depend on the table and ``m`` alone, so one device
+        makes the host rows and every context is handed the same ones."""
+        ctx, dev = C.c_void_p(), C.c_int(0)
+        _lib.check(self._lib.misti_multi_context(self._m, 0, C.byref(ctx), C.byref(dev)))
+        return _bootstrap_table(_jackknife_rows(self._lib, ctx, dev.value, chunks, m, 0, None), chunks)
 
     def parametric_table(self, split, params, data_row, n, n_sites=None, seed=0, band_bounds=None):
         """``Engine.parametric_table``, its replicates drawn on the first context of the list: a replicate depends on ``(seed, r)`` and the

@@ -1063,6 +1063,127 @@ def block_bootstrap_table(chunks, n, seed=0, normalize=False):
     return np.vstack([_in_order_sum(c)[None, :], block_bootstrap(c, n, seed=seed, normalize=normalize)])
 
 
+# ------------------------------------------------------------------------------------------------ block jackknife ----
+# The rule of misti_jackknife_rows_dev stated on the host (include/misti_hip.h, "block jackknife"): the device result is this, bit for
+# bit.  The delete-m block jackknife: deterministic - no stream, no seed - G fits instead of a thousand, and a bias-corrected estimate
+# besides the standard error (jackknife_estimate).  The reference has no counterpart.
+def check_jackknife(chunks, m=1):
+    """The chunk table as ``misti_jackknife_rows_dev`` takes it, with the checks the ABI makes before it touches the device, as a
+    ``ValueError`` of one line: everything ``check_chunks`` refuses except its draw limit (nothing is drawn here), fewer than 2 chunks,
+    ``m < 1``, and ``m >= n_chunk`` - a single group would leave nothing behind.  Returns ``(chunks, G)``, ``G = ceil(n_chunk / m)``."""
+    c = np.ascontiguousarray(chunks, dtype=np.float64)
+    m = int(m)
+    if c.ndim != 2 or c.shape[1] != 8 or c.shape[0] < 2:
+        raise ValueError("the chunk table of a jackknife must be [n_chunk][8] with at least 2 chunks (got shape %s)" % (c.shape,))
+    if c.shape[0] > BOOT_MAX_CHUNKS:
+        raise ValueError("%d chunks, beyond the limit of %d" % (c.shape[0], BOOT_MAX_CHUNKS))
+    if m < 1:
+        raise ValueError("m must be at least 1 (got %d)" % m)
+    if m >= c.shape[0]:
+        raise ValueError("groups of m = %d chunks out of %d: a single group would leave nothing behind" % (m, c.shape[0]))
+    if not np.isfinite(c).all():
+        raise ValueError("chunk %d has an entry that is not finite" % int(np.argmax(~np.isfinite(c).all(axis=1))))
+    if not (c[:, 0] > 0).all():
+        raise ValueError("chunk %d has length %g: a chunk's length must be > 0" % (int(np.argmax(~(c[:, 0] > 0))), c[np.argmax(~(c[:, 0] > 0)), 0]))
+    if (c[:, 1:] < 0).any():
+        raise ValueError("chunk %d has a negative count" % int(np.argmax((c[:, 1:] < 0).any(axis=1))))
+    with np.errstate(over="ignore"):
+        if not (np.isfinite(_in_order_sum(c[:, 0])) and np.isfinite(_in_order_sum(_seg_of(c)))):
+            raise ValueError("the chunk lengths or counts do not sum to a finite number")
+    return c, -(-c.shape[0] // m)
+
+
+def jackknife_rows(chunks, m=1, first=0, n=None):
+    """The rule of ``misti_jackknife_rows_dev`` on the host: leave-out rows ``first ... first + n - 1`` (``n`` None: all from ``first``) of
+    the chunk table (``check_jackknife``), float64 ``[n][8]``.  Group g covers chunks ``g m ... min((g + 1) m, n_chunk) - 1`` - there are
+    ``G = ceil(n_chunk / m)``, the last may be short.  Row g starts at eight zeros and walks the chunks in chunk order; for every chunk
+    OUTSIDE group g it adds the chunk's 8 columns to its own, one float64 addition per column per chunk.  A chunk inside the group is
+    skipped: it is not added as zero, and nothing is subtracted from a total - the fixed order is what makes the result a matter of
+    bits for counts that are no integers.  No stream, no normalisation (scaling a row does not move the arg-max of the multinomial
+    log-likelihood).  Column 0 of a row is the length left in."""
+    c, G = check_jackknife(chunks, m)
+    m, first, n_chunk = int(m), int(first), c.shape[0]
+    n = G - first if n is None else int(n)
+    if first < 0 or n < 0 or first + n > G:
+        raise ValueError("jackknife_rows: groups %d ... %d of G = %d" % (first, first + n - 1, G))
+    before = np.cumsum(np.concatenate([np.zeros((1, 8)), c]), axis=0)     # before[i]: the row after chunks 0 ... i - 1, added in chunk order
+    rows = np.empty((n, 8))
+    for i in range(n):
+        lo, hi = (first + i) * m, min((first + i + 1) * m, n_chunk)
+        # the additions behind the group simply go on from where the ones in front of it stopped
+        rows[i] = np.cumsum(np.concatenate([before[lo][None, :], c[hi:]]), axis=0)[-1]
+    return rows
+
+
+def jackknife_table(chunks, m=1):
+    """Row 0 - the column sums of all chunks, added in chunk order: exactly row 0 of ``block_bootstrap_table`` - in front of the ``G``
+    leave-out rows of ``jackknife_rows``.  Float64 ``[1 + G][8]``; its column 0 carries everything ``jackknife_estimate`` needs."""
+    c, _ = check_jackknife(chunks, m)
+    return np.vstack([_in_order_sum(c)[None, :], jackknife_rows(c, m)])
+
+
+def jackknife_weights(lengths):
+    """``(n, m_g[G], h_g[G])`` from column 0 of a jackknife table (``lengths[1 + G]``: the whole, then what every leave-out row keeps):
+    ``m_g = n - lengths[g]`` the length of group g, ``h_g = n / m_g``.  ``ValueError`` where the column is not such a table's: fewer
+    than two leave-out rows, or a row that keeps nothing or everything."""
+    l = np.asarray(lengths, dtype=np.float64).reshape(-1)
+    if l.size < 3:
+        raise ValueError("a jackknife table has row 0 and at least 2 leave-out rows (got %d rows)" % l.size)
+    n = l[0]
+    if not (np.isfinite(l).all() and n > 0 and (l[1:] > 0).all() and (l[1:] < n).all()):
+        raise ValueError("column 0 is not a jackknife table's: every leave-out row keeps a length > 0 and below row 0's")
+    m_g = n - l[1:]
+    return n, m_g, n / m_g
+
+
+def _jackknife_one(theta, n, m_g, h_g, level):
+    from scipy import stats
+    if not np.isfinite(theta[0]):
+        return None
+    est = float(theta[0])
+    has = np.isfinite(theta[1:])
+    t, mg, hg = theta[1:][has], m_g[has], h_g[has]
+    G = int(t.size)
+    out = dict(estimate=est, jackknife=None, bias=None, se=None, interval=None, n_group=G)
+    if G < 1:
+        return out
+    jack = G * est - float(np.sum((1.0 - mg / n) * t))
+    out["jackknife"], out["bias"] = jack, est - jack
+    if G < 2:
+        return out
+    tau = hg * est - (hg - 1.0) * t
+    se = float(np.sqrt(np.sum((tau - jack) ** 2 / (hg - 1.0)) / G))
+    half = float(stats.t.ppf(0.5 + level / 2, G - 1)) * se
+    out["se"], out["interval"] = se, (jack - half, jack + half)
+    return out
+
+
+def jackknife_estimate(theta, lengths, level=0.95):
+    """The weighted delete-m jackknife of Busing, Meijer and van der Leeden (1999, Statistics and Computing 9: 3-8) from the rows'
+    estimates and COLUMN 0 of the table alone (``jackknife_weights``) - a table read back from a file carries everything it needs.
+    ``theta[1 + G]`` holds row 0's estimate first, then the leave-out estimates; ``lengths[1 + G]`` is the table's column 0.  With
+    ``n = lengths[0]``, ``m_g = n - lengths[g]`` and ``h_g = n / m_g``:
+    ``jackknife = G estimate - sum_g (1 - m_g / n) theta_(g)``; pseudo-values ``tau_g = h_g estimate - (h_g - 1) theta_(g)``;
+    ``se^2 = (1 / G) sum_g (tau_g - jackknife)^2 / (h_g - 1)``.
+    Returns dict(estimate, jackknife, bias (= estimate - jackknife), se, interval (jackknife -+ t.ppf(0.975, G - 1) se), n_group).
+    Leave-out rows without a finite estimate are dropped and ``n_group`` counts the rest (G above is that count); fewer than 2 give no
+    ``se`` and no ``interval`` (None), none gives no ``jackknife`` either.  A row-0 estimate that is not finite gives no result: None.
+    ``theta[1 + G][K]`` is handled per column: every entry an array over the K columns (``interval[K][2]``), NaN where a column has
+    none, ``n_group`` 0 for a column without a row-0 estimate."""
+    th = np.asarray(theta, dtype=np.float64)
+    n, m_g, h_g = jackknife_weights(lengths)
+    if th.shape[0] != 1 + m_g.size or th.ndim not in (1, 2):
+        raise ValueError("jackknife_estimate: theta must be [1 + G] or [1 + G][K] for the table's G = %d (got shape %s)" % (m_g.size, th.shape))
+    if th.ndim == 1:
+        return _jackknife_one(th, n, m_g, h_g, level)
+    cols = [_jackknife_one(th[:, k], n, m_g, h_g, level) for k in range(th.shape[1])]
+    num = lambda v: np.nan if v is None else v
+    out = {key: np.array([num(c[key]) if c else np.nan for c in cols], dtype=np.float64) for key in ("estimate", "jackknife", "bias", "se")}
+    out["interval"] = np.array([c["interval"] if c and c["interval"] else (np.nan, np.nan) for c in cols], dtype=np.float64).reshape(-1, 2)
+    out["n_group"] = np.array([c["n_group"] if c else 0 for c in cols], dtype=np.int64)
+    return out
+
+
 # ------------------------------------------------------------------------------------------- parametric bootstrap ----
 # The rule of misti_parametric_rows_dev stated on the host (include/misti_hip.h, "parametric bootstrap"): the device result is this, bit
 # for bit.  Replicates for inputs that have no chunks to resample: every site is drawn INDEPENDENTLY from the seven classes of a
