@@ -8,6 +8,12 @@ constexpr int MAXPULSE = 12;          // entries per row of the pulse operator
 #ifndef MISTI_WAVES_PER_BLOCK
 #define MISTI_WAVES_PER_BLOCK 4
 #endif
+// Issue priority (s_setprio) in a one-chain-per-wave launch of at most 256 chains (correct_follow_kernel; the ladder of larger launches
+// is not touched): 0 none; 1 the chain wave runs at priority 3 and returns to 0 before it pulls the next chain; 2 as 1, and the trunk
+// wave sets priority 0 explicitly.  Shipped: 1 (measured against 0 and 2: DESIGN.md section 6).
+#ifndef MISTI_SMALL_LAUNCH_PRIO
+#define MISTI_SMALL_LAUNCH_PRIO 1
+#endif
 constexpr int WAVES_PER_BLOCK = MISTI_WAVES_PER_BLOCK;    // candidates per workgroup of kernel 2 (one wavefront each)
 constexpr int TALBOT_N = 28;           // nodes of the Talbot contour (conjugate pairs folded: TALBOT_HALF solves)
 constexpr int TALBOT_HALF = TALBOT_N / 2;

@@ -2603,17 +2603,28 @@ void correct_follow_kernel(DevModel m, int64_t n_items, ChainBufs cb, const doub
         const int64_t ch = cb.chain_order[pos];
         if (chain_role) {
             // a launch that fills the chip: the longest chains - the ones the launch waits for - get the issue priority on the SIMD
-            // they share with another wave (s_setprio; measured on 1 024 chains: 2.04 -> 1.92 ms per call; on the headline grid's 64
-            // chains it changes nothing alone and costs 1 % with 20 batches in flight, so not there)
+            // they share with another wave (s_setprio; measured on 1 024 chains: 2.04 -> 1.92 ms per call).
+            // A launch of at most 256 chains (the headline grid's 64): MISTI_SMALL_LAUNCH_PRIO (misti_consts.h), priority 3 for the chain wave.
+            // Measured 2026-10-20 with the 4 queues a process inherits (11 batches in flight): +2 % at 512 steps, +5 % at 20; at
+            // GPU_MAX_HW_QUEUES=22, where it once cost 1 %, now inside the run-to-run range.
             if (n_live > 256) {
                 if (4 * pos < n_live) __builtin_amdgcn_s_setprio(3);
                 else if (2 * pos < n_live) __builtin_amdgcn_s_setprio(2);
                 else __builtin_amdgcn_s_setprio(1);
             }
+#if MISTI_SMALL_LAUNCH_PRIO >= 1
+            else __builtin_amdgcn_s_setprio(3);
+#endif
             correct_body<CPFIT, 64, false, true>(m, n_items, cb, split_time, params, ch, lds, lc_sh, flags, pre);
             lds_order();
             if (lane_id() == 0) lds_put(flags + 1, 1);                       // whatever way the chain ended
+#if MISTI_SMALL_LAUNCH_PRIO >= 1
+            if (n_live <= 256) __builtin_amdgcn_s_setprio(0);                // back in the pull loop the wave is nobody's critical path
+#endif
         } else {
+#if MISTI_SMALL_LAUNCH_PRIO >= 2
+            if (n_live <= 256) __builtin_amdgcn_s_setprio(0);
+#endif
             trunk_follow(m, n_items, params, cb, ch, tk, lc_sh, flags);
         }
         __syncthreads();                                                     // both waves are done with the hand-over area
