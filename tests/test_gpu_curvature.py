@@ -212,19 +212,16 @@ def through_evaluate(e, x, splits, rows, table, unfolded, pulse_times=None, band
 
 
 # ---- 2. the driver against the assembly, 3. against differences of the llk values -----------------------------------------------------
-@pytest.mark.parametrize("name", sorted(MODELS))
-def test_driver_equals_the_stencil_through_evaluate_and_llk_differences(name, table):
-    e, D, split, x0, unfolded = model_engine(name)
+def driver_comparison(name, e, D, unfolded, x, splits, rows, pt, table, may_fail=False):
+    """The driver against the stencil pushed through Engine.evaluate and the rule (2.), and against central differences of the llk
+    values themselves (3.); `e` is closed here.  Every point must come back with status 0 unless `may_fail`."""
     with e:
-        x, splits, rows, pt = points_of(name, 4, np.random.default_rng(7))
         got = e.curvature(x, splits, rows, table, pulse_times=pt)
         want, jafs, llk, h, boundary = through_evaluate(e, x, splits, rows, table, unfolded, pulse_times=pt)
-    # (under the default fit the lambda-correction fails at three of these four points - status 2, from evaluate and from the driver
-    #  alike; the points with a value are held to the rule, the others must be NaN throughout)
     print(name, "status", got.status, "through evaluate", want["status"])
     assert not boundary.any() and np.array_equal(got.status, want["status"])
     ok = got.status == 0
-    assert ok.any() and (ok.all() or name == "two_way_default")
+    assert ok.any() and (ok.all() or may_fail)
     assert same_bits(got.h, h)
     assert same_bits(got.llh0[ok], llk[ok, 0]), "llh0 is the centre's evaluate value, bit for bit"
     assert np.isnan(got.llh0[~ok]).all()
@@ -233,7 +230,7 @@ def test_driver_equals_the_stencil_through_evaluate_and_llk_differences(name, ta
     assert_floor(got.hess, want["hess"], want["tol_hess"], ok, (name, "hess"))
     assert same_bits(got.hess, np.swapaxes(got.hess, 1, 2))
     if pt is not None:
-        assert len({float(v) for v in got.llh0}) == 4                  # the per-point pulse times reach the values
+        assert len({float(v) for v in got.llh0}) == x.shape[0]         # the per-point pulse times reach the values
     # 3. the independent path: central differences of the llk values themselves.  eps is the clause-1 floor (tests/parity.py) of the
     # point's centre; a difference of 2 (4) such values over 2 h (h_i h_j) is allowed 2 eps / h_i (4 eps / (h_i h_j)).
     P = x.shape[0]
@@ -252,6 +249,15 @@ def test_driver_equals_the_stencil_through_evaluate_and_llk_differences(name, ta
     assert_floor(got.grad, g_fd, 2 * eps[:, None] / h, ok, (name, "grad against llk differences"))
     assert_floor(got.hess, h_fd, 4 * eps[:, None, None] / (h[:, :, None] * h[:, None, :]), ok, (name, "hess against llk differences"))
     assert (np.abs(got.grad[ok]) > 0).all() and (np.abs(got.hess[ok]) > 0).all()
+
+
+@pytest.mark.parametrize("name", sorted(MODELS))
+def test_driver_equals_the_stencil_through_evaluate_and_llk_differences(name, table):
+    e, D, split, x0, unfolded = model_engine(name)
+    x, splits, rows, pt = points_of(name, 4, np.random.default_rng(7))
+    # (under the default fit the lambda-correction fails at three of these four points - status 2, from evaluate and from the driver
+    #  alike; the points with a value are held to the rule, the others must be NaN throughout)
+    driver_comparison(name, e, D, unfolded, x, splits, rows, pt, table, may_fail=name == "two_way_default")
 
 
 # ---- 4. the batch cut ------------------------------------------------------------------------------------------------------------------
