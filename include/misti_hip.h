@@ -389,212 +389,198 @@ int misti_parametric_counts(const double p[7], int64_t n_sites, uint64_t seed, i
 int misti_parametric_geometry(int64_t n_sites, int64_t n_rep, int32_t* blocks_per_rep);
 
 /* ---- batched optimiser ------------------------------------------------------------ */
-/* Replaces MigrationInference.Solve (MigrationInference.py:718-733: SciPy Nelder-Mead on -JAFSLikelihood, xatol =
- * fatol = tol, maxiter = 1000, started from the -mi / -pu initial values) for n_start starts at once - BASELINE
- * config 3 runs it from 16 384 random starts.  Every start follows scipy.optimize.minimize(method='Nelder-Mead')
- * decision for decision (same simplex, same evaluation count), so its result equals SciPy's on the same objective.
- * Simplices, function values and decisions stay in HBM; per iteration the reflection points of all starts are one
- * engine batch, their expansion / contraction points a second, shrunk vertices a third; finished starts cost nothing;
- * once few starts are left, iterations become speculative (misti_nm_last_spec_iterations).
- * Host buffers; synchronous.
- *   starts      [n_start][n_param]   (n_param >= 1)
- *   split_time  the split time of every evaluation (fractional allowed)
- *   jsfs_row    [8]                  the data JSFS (one replicate)
- *   maxiter     SciPy's maxiter (the reference passes 1000); the evaluation budget is unlimited, as there
- *   x           [n_start][n_param]   best vertex per start
- *   llh         [n_start]            its log-likelihood (-inf if no vertex has a value)
- *   nit, nfev   [n_start] or NULL    SciPy's OptimizeResult.nit / .nfev
- *   status      [n_start] or NULL    0 converged (both tolerances), 2 iteration budget (1: evaluation budget - only inside
- *                                    misti_basinhopping, whose minimisations run with SciPy's default maxfev = 200 x n_param; the
- *                                    budget is cut per evaluation as SciPy does: nfev never exceeds it) */
+/* ONE search, described by ONE record.  misti_search is the entry for new callers; the ten older entry points below it are fixed
+ * wrappers, each a descriptor with some fields set and the others NULL.
+ *
+ * What a search is.  Replaces MigrationInference.Solve (MigrationInference.py:718-733: SciPy Nelder-Mead on -JAFSLikelihood, xatol =
+ * fatol = tol, maxiter = 1000, started from the -mi / -pu initial values) for n_start starts at once - BASELINE config 3 runs it
+ * from 16 384 random starts.  Every start follows scipy.optimize.minimize(method='Nelder-Mead') decision for decision (same simplex,
+ * same evaluation count), so its result equals SciPy's on the same objective.  Simplices, function values and decisions stay in
+ * HBM; per iteration the reflection points of all starts are one engine batch, their expansion / contraction points a second,
+ * shrunk vertices a third; finished starts cost nothing; once few starts are left, iterations become speculative
+ * (misti_nm_last_spec_iterations).  Host buffers; synchronous; misti_nm_last_stats / misti_nm_last_spec_iterations report on the
+ * call (with hops: all its minimisations together).
+ *
+ * The split mode says where a point's split time comes from, and with it which of the fields apply: */
+#define MISTI_SPLIT_ONE       0   /* split_time for every start; jsfs is the one data row [8] (n_rep = 1); rows, band_bounds, pulse_times
+                                   * are not read - the search the engine evaluates with its replicate epilogue inline */
+#define MISTI_SPLIT_PER_START 1   /* split_times[s]; start s against row rows[s] of the table jsfs[n_rep][8]: the rows path */
+#define MISTI_SPLIT_FITTED    2   /* the split is the LAST of N = n_param + 1 coordinates of every simplex; otherwise the rows path */
+/* N, the number of coordinates, is n_param (n_param >= 1), or n_param + 1 with MISTI_SPLIT_FITTED (n_param == 0 is allowed there, and
+ * only there, as a one-coordinate search; MISTI_E_LIMIT for n_param + 1 > MISTI_MAX_PARAMS).
+ *
+ * The rows path (MISTI_SPLIT_PER_START).  Replaces the bootstrap profiles of the reference's test.bs scripts
+ * (test.bs/san_din.bs.sh:27-36 and its siblings: `for bs in 0..100; for st in 15..25: MiSTI.py ... ${st} -bs ${bs} -mi ... --cpfit`,
+ * one MigrationInference.Solve per (replicate, split) pair and process) with ONE batched search over all pairs (and starts): every
+ * evaluation batch of the search carries points of many splits and rows, then one small kernel scores each point against its own
+ * row - the same bits as the inline replicate epilogue, so start s returns exactly what misti_nm_solve(starts[s], split_times[s],
+ * jsfs + 8 rows[s]) returns, on a context whose model carries band_bounds[s] and pulse_times[s] where those are given.  Starts that
+ * share initial values also share the chains of their initial simplices (computed once, up to the largest split); starts with equal
+ * bounds and equal initial values share them too, starts with different bounds never share a chain (the chain key holds the bounds).
+ * band_bounds replaces the boundary profiles "when did migration start or stop" - the test.bs scripts' `-mi 1 4 ${st} ${j} 1` loops
+ * with a loop over the boundary added, one Engine per bound set and one Solve per model there; pulse_times the pulse-date profile
+ * with an optimised fraction - `-pu 2 {t} f 1` under a loop over t.  A field left NULL is exactly the search without it: NULL
+ * pulse_times is misti_nm_solve_bounds, NULL band_bounds as well is misti_nm_solve_rows, bit for bit.
+ *
+ * The split as a coordinate (MISTI_SPLIT_FITTED).  Start s is SciPy's Nelder-Mead from starts[s] against row rows[s] on
+ *     f(mu, st) = -JAFSLikelihood(mu) of a model at split time st
+ * as misti_eval_batch evaluates it for a fractional st (MigrationInference.__init__ :89-99: the interval the split falls in is cut in
+ * two); mu in the reference's order, the split last.  Replaces the scans of the test.bs scripts - `for st in A..Z` around `MiSTI.py
+ * ... ${st} -bs ${bs}`, the arg-max taken per bootstrap row afterwards, an answer on the PSMC grid - with ONE batched search per
+ * call, one start per (row, initial values, initial split); and it is the only search a model without an optimised parameter has
+ * (the `*no.mig.sh` scripts).  What it is not: the reference has no such search, so there is no reference run to agree with.  The
+ * parity target is SciPy's Nelder-Mead on this engine's own objective (same initial simplex - 5 % or 0.00025 per coordinate, the
+ * split included -, same decisions, xatol over all coordinates alike, the split in grid-index units), and the engine's parity
+ * contract is the objective's.  The objective is piecewise in the split (band ends and smoothing runs follow its index);
+ * Nelder-Mead is defined on such a function.  A band end of -1 is the POINT's own split index.  Out of scope: the lanes, the
+ * device-list (misti_multi_*) forms and the forward map keep a fixed split per start.
+ *
+ * Points the engine refuses.  A split time that is invalid, negative or beyond the grid, no finite coalescent time, a negative rate,
+ * band bounds that break SetModel's checks (MigrationInference.py:237-255: start >= sample date, start < end, end inside the grid,
+ * no overlap within a population), pulse times that break them: such a point has no value and scores +inf for the optimiser,
+ * exactly as -inf from misti_eval_batch would.  It is never an argument error and the other starts are unaffected; a start none of
+ * whose points ever has a value returns llh = -inf (a simplex just beyond the grid may reflect back into it, as SciPy's would).
+ *
+ * The box (n_box != 0): SciPy's bounds= on the search.  Start s is
+ *     scipy.optimize.minimize(f, starts[s], method='Nelder-Mead', bounds=Bounds(box_lo, box_hi), options=dict(xatol, fatol, maxiter))
+ * on this engine's objective, bit for bit (SciPy 1.15.3, _minimize_neldermead): the start is clipped to the box; the 5 % / 0.00025
+ * simplex is built from the clipped start, a vertex beyond an upper bound is reflected into the interior (2 hi - x) and the simplex
+ * clipped; every reflection, expansion, contraction and shrunk vertex is clipped - numpy.clip per coordinate - before the objective
+ * sees it.  Without a box the only limit of a search is the engine's refusal of a point; with one, rates can be capped, a fitted
+ * split kept inside a range, and a coordinate held fixed (lo == hi).  The word "bounds" is taken (band bounds per start), hence
+ * "box".  A box of (-inf, +inf) throughout returns the bytes of the search without a box.  Not with MISTI_SPLIT_ONE.
+ *
+ * Errors.  MISTI_E_ARG, before anything touches the device, in this order: a NULL descriptor or a size that is not this library's; a
+ * negative n_start; a NULL pointer among those the mode needs; n_rep < 1; maxiter < 1 (with hops: niter < 0, NULL uniforms with
+ * niter > 0, maxiter, nm_maxfev or interval below 1); a row out of range; a non-finite split time; a NULL context; a model without
+ * an optimised parameter; then MISTI_E_LIMIT for n_param + 1 > MISTI_MAX_PARAMS, too many starts or too many rows; then a non-finite
+ * start coordinate (MISTI_SPLIT_FITTED); then the box: n_box neither 1 nor n_start, a NULL box pointer, a NaN bound, or a lower bound
+ * greater than its upper bound (the message names the box and the coordinate; SciPy raises ValueError there).  n_start == 0 returns
+ * 0 once the arguments are accepted, and writes nothing. */
+typedef struct misti_hops_t misti_hops_t;
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_search_t): a descriptor of another layout is refused, not misread */
+    int32_t split;                   /* MISTI_SPLIT_* */
+    double split_time;               /* MISTI_SPLIT_ONE: the split time of every evaluation (fractional allowed) */
+    const double* split_times;       /* MISTI_SPLIT_PER_START: [n_start], finite, fractional allowed */
+    int64_t n_start;
+    const double* starts;            /* [n_start][N]; MISTI_SPLIT_FITTED: initial parameters, then the initial split time (all finite).  A
+                                      * start outside its box is no error: it is clipped (SciPy only warns) */
+    const int32_t* rows;             /* [n_start], 0 <= rows[s] < n_rep: each start's row of the table */
+    int64_t n_rep;
+    const double* jsfs;              /* [n_rep][8] the replicate table (row 0 of a -bs file: the data) */
+    const int32_t* band_bounds;      /* [n_start][n_band][2] or NULL, as misti_eval_batch's (end == -1: the start's split index).  Ignored
+                                      * when the model has no band */
+    const int32_t* pulse_times;      /* [n_start][n_pulse] or NULL, as misti_eval_batch_pulses'.  Ignored when the model has no pulse */
+    int64_t n_box;                   /* 0: no box.  1: one box for every start.  n_start: a box per start */
+    const double* box_lo;            /* [n_box][N]  -inf: no bound on that side; lo == hi: the coordinate is held fixed */
+    const double* box_hi;            /* [n_box][N]  +inf: no bound on that side */
+    double xatol;
+    double fatol;
+    int32_t maxiter;                 /* SciPy's maxiter (the reference passes 1000); without hops the evaluation budget is unlimited, as there */
+    double* x;                       /* [n_start][N] best vertex per start (MISTI_SPLIT_FITTED: the fitted split last); inside the box.  With
+                                      * hops: the lowest successful minimum found (res.x) */
+    double* llh;                     /* [n_start] its log-likelihood (-inf if no vertex has a value); with hops -res.fun */
+    int32_t* nit;                    /* [n_start] or NULL: SciPy's OptimizeResult.nit.  NULL with hops (an argument error otherwise) */
+    int32_t* nfev;                   /* [n_start] or NULL: SciPy's OptimizeResult.nfev.  NULL with hops */
+    int32_t* status;                 /* [n_start] or NULL: 0 converged (both tolerances), 2 iteration budget (1: evaluation budget - only under
+                                      * hops, whose budget is cut per evaluation as SciPy does: nfev never exceeds it).  NULL with hops */
+    const misti_hops_t* hops;        /* basin hopping around the search; NULL: the search alone */
+} misti_search_t;
+
+/* Basin hopping around a search: scipy.optimize.basinhopping(func, x0, niter, T, stepsize, minimizer_kwargs=dict(method='Nelder-Mead'),
+ * interval, target_accept_rate, stepwise_factor, rng=...) for n_start starts at once - the reference's global search,
+ * MigrationInference.Solve(globalOpt=True) (MigrationInference.py:723-725: T = 0.5, Nelder-Mead with SciPy's defaults, i.e.
+ * xatol = fatol = 1e-4, maxiter = maxfev = 200 x N), which BASELINE config 3 runs from 16 384 random starts and the test.bs workflow
+ * once per (row, split) pair and process.  Every start follows SciPy's runner step for step (_basinhopping.py: initial minimisation,
+ * then per hop AdaptiveStepsize.take_step, RandomDisplacement, the local minimisation - the search above, all starts in one set of
+ * engine batches - Metropolis.accept_reject, Storage.update); the hops of all starts go in step.  Incumbents, step sizes and
+ * decisions stay in HBM.  With the split as a coordinate the random displacement moves it like any other (SciPy's
+ * RandomDisplacement: one stepsize for all, the split in grid-index units); with a box the displacement itself is not clipped, as in
+ * SciPy - a trial point may leave the box - and the minimisation that starts from it clips it.  A start none of whose points has a
+ * value returns llh = -inf and counts every minimisation as failed, as SciPy does on an objective that returns inf: the Metropolis
+ * test treats inf - inf as Python's min(0, nan) does.  Start s of the rows path returns, bit for bit, what misti_basinhopping(starts[s],
+ * split_times[s], jsfs + 8 rows[s], the same uniforms) returns on a context whose model carries band_bounds[s] and pulse_times[s]:
+ * x, llh, nfev, failures and accepted.  Out of scope: hops out of step (a start taking its next hop while others still minimise).
+ * The random numbers are the CALLER's: SciPy draws, per hop, N uniforms for the displacement and then one for the acceptance test
+ * from one generator; their number does not depend on the data, so the caller draws them up front, and start s then reproduces
+ * scipy.optimize.basinhopping(rng = that generator) on the same objective (x, fun, nfev, minimization_failures). */
+struct misti_hops_t {
+    int32_t niter;
+    double T;
+    double stepsize;
+    int32_t interval;
+    double target_accept_rate;
+    double stepwise_factor;
+    int64_t nm_maxfev;               /* the minimiser's evaluation budget (SciPy's default 200 x N); its iteration budget is the search's maxiter */
+    const double* uniforms;          /* [n_start][niter][N + 1] numpy.random.Generator.random() values (in [0, 1)) in exactly SciPy's order,
+                                      * start s from the generator SciPy would be given for start s */
+    int32_t* nfev;                   /* [n_start] or NULL: res.nfev */
+    int32_t* failures;               /* [n_start] or NULL: res.minimization_failures */
+    int32_t* accepted;               /* [n_start] or NULL: hops accepted */
+};
+
+int misti_search(misti_ctx* ctx, const misti_search_t* search);
+
+/* The older entry points, prototypes fixed: each is misti_search on the descriptor named, the arguments the fields of the same name
+ * (jsfs_row: jsfs; nm_maxiter: maxiter; niter .. accepted: the hops), every other field NULL or 0.  They keep their argument orders. */
+/* MISTI_SPLIT_ONE. */
 int misti_nm_solve(misti_ctx* ctx, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
                    double xatol, double fatol, int32_t maxiter,
                    double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
-/* misti_nm_solve with a split time and a data row PER START: start s is SciPy's Nelder-Mead on -JAFSLikelihood at split_times[s]
- * against row rows[s] of the replicate table.  Replaces the bootstrap profiles of the reference's test.bs scripts
- * (test.bs/san_din.bs.sh:27-36 and its siblings: `for bs in 0..100; for st in 15..25: MiSTI.py ... ${st} -bs ${bs} -mi ... --cpfit`,
- * one MigrationInference.Solve - MigrationInference.py:718-733 - per (replicate, split) pair and process) with ONE batched
- * search over all pairs (and starts): every evaluation batch of the search carries points of many splits and rows, then one
- * small kernel scores each point against its own row - the same bits as the inline replicate epilogue, so start s returns
- * exactly what misti_nm_solve(starts[s], split_times[s], jsfs + 8 rows[s]) returns.  Starts that share initial values also
- * share the chains of their initial simplices (computed once, up to the largest split).  Host buffers; synchronous;
- * misti_nm_last_stats / misti_nm_last_spec_iterations report on it.
- *   starts       [n_start][n_param]   (n_param >= 1)
- *   split_times  [n_start]            finite, fractional allowed (an invalid one gives its start llh = -inf)
- *   rows         [n_start]            0 <= rows[s] < n_rep
- *   jsfs         [n_rep][8]           the replicate table (row 0 of a -bs file: the data)
- *   xatol .. status                   as misti_nm_solve
- * MISTI_E_ARG, before anything touches the device, for a NULL pointer, n_rep < 1, a row out of range, a non-finite split time
- * or maxiter < 1. */
+/* MISTI_SPLIT_PER_START with NULL bounds, times and box. */
 int misti_nm_solve_rows(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                         int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                         double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
-/* misti_nm_solve_rows with band bounds PER START as well: start s is SciPy's Nelder-Mead at split_times[s] against row rows[s], with the
- * model's -mi bands starting and ending where band_bounds[s] says (as misti_eval_batch's band_bounds: end == -1 = the start's split
- * index).  Replaces the boundary profiles "when did migration start or stop" - the test.bs scripts' `-mi 1 4 ${st} ${j} 1` loops with
- * a loop over the boundary added, one Engine per bound set and one Solve per model there - with ONE batched search: every batch of
- * the search carries each point's own bounds.  Starts with equal bounds and equal initial values share the chains of their initial
- * simplices; starts with different bounds never share a chain (the chain key holds the bounds).  Start s returns exactly what
- * misti_nm_solve(starts[s], split_times[s], jsfs + 8 rows[s]) returns on a context whose model carries band_bounds[s].
- *   band_bounds  [n_start][n_band][2] or NULL   NULL: exactly misti_nm_solve_rows.  Ignored when the model has no band.
- *                Bounds that break SetModel's checks (MigrationInference.py:237-255: start >= sample date, start < end, end inside
- *                the grid, no overlap within a population) are no argument error: that start gets llh = -inf, its neighbours are
- *                unaffected (as for an invalid split time).
- *   other arguments, errors, synchronisation and statistics as misti_nm_solve_rows. */
+/* MISTI_SPLIT_PER_START with NULL times and box. */
 int misti_nm_solve_bounds(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                           double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
-/* misti_nm_solve_bounds with pulse times PER START as well (as misti_eval_batch_pulses' pulse_times).  Replaces the pulse-date
- * profile with an optimised fraction - `-pu 2 {t} f 1` under a loop over t, one Engine and one Solve per time there - with ONE
- * batched search.  Start s returns exactly what misti_nm_solve(starts[s], split_times[s], jsfs + 8 rows[s]) returns on a context
- * whose model carries band_bounds[s] and pulse_times[s].
- *   pulse_times  [n_start][n_pulse] or NULL   NULL: exactly misti_nm_solve_bounds.  Ignored when the model has no pulse.  Times
- *                that break the checks are no argument error: that start gets llh = -inf, its neighbours are unaffected.
- *   other arguments, errors (MISTI_E_ARG before anything touches the device), synchronisation and statistics as misti_nm_solve_rows. */
+/* MISTI_SPLIT_PER_START with a NULL box. */
 int misti_nm_solve_pulses(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
                           double xatol, double fatol, int32_t maxiter,
                           double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
-/* The split time as a COORDINATE of the search: every simplex has n_param + 1 coordinates, the model's optimised parameters in the
- * reference's mu order and, last, the split time; start s is SciPy's Nelder-Mead from starts[s] against row rows[s] on
- *     f(mu, st) = -JAFSLikelihood(mu) of a model at split time st
- * as misti_eval_batch evaluates it for a fractional st (MigrationInference.__init__ :89-99: the interval the split falls in is cut in
- * two).  Replaces the scans of the test.bs scripts - `for st in A..Z` around `MiSTI.py ... ${st} -bs ${bs}`, the arg-max taken per
- * bootstrap row afterwards, an answer on the PSMC grid - with ONE batched search per call, one start per (row, initial values,
- * initial split); and it is the only search a model without an optimised parameter has (the `*no.mig.sh` scripts): n_param == 0 is
- * allowed here, and only here, as a one-coordinate search.
- * What it is not: the reference has no such search, so there is no reference run to agree with.  The parity target is SciPy's
- * Nelder-Mead on this engine's own objective (same initial simplex - 5 % or 0.00025 per coordinate, the split included -, same
- * decisions, xatol over all coordinates alike, the split in grid-index units), and the engine's parity contract is the objective's.
- * The objective is piecewise in the split (band ends and smoothing runs follow its index); Nelder-Mead is defined on such a function.
- *   starts       [n_start][n_param + 1]  initial parameters, then the initial split time
- *   rows         [n_start]               replicate row per start, as misti_nm_solve_rows
- *   band_bounds  [n_start][n_band][2] or NULL   per start, as misti_nm_solve_bounds (end == -1: the POINT's own split index)
- *   pulse_times  [n_start][n_pulse] or NULL     per start, as misti_nm_solve_pulses
- *   n_rep, jsfs, xatol, fatol, maxiter          as misti_nm_solve_rows
- *   x            [n_start][n_param + 1]  best vertex, the fitted split time last
- *   llh .. status                        as misti_nm_solve
- * A point whose split the engine refuses - negative, beyond the grid, no finite coalescent time, bands or pulses broken at that
- * split - has no value and scores +inf for the optimiser, exactly as -inf from misti_eval_batch would; it is never an argument
- * error, and other starts are unaffected (a start none of whose points ever has a value returns llh = -inf; a simplex
- * just beyond the grid may reflect back into it, as SciPy's would).
- * MISTI_E_LIMIT for a model with n_param + 1 > MISTI_MAX_PARAMS, MISTI_E_ARG for a NULL pointer, n_rep < 1, a row out of range, a
- * non-finite start coordinate or maxiter < 1 - all before anything touches the device.  Synchronisation and statistics
- * (misti_nm_last_stats, misti_nm_last_spec_iterations) as misti_nm_solve_rows.
- * Basin hopping over the same coordinates: misti_basinhopping_split.  Out of scope: the lanes, the device-list (misti_multi_*) forms
- * and the forward map keep a fixed split per start. */
+/* MISTI_SPLIT_FITTED with a NULL box. */
 int misti_nm_solve_split(misti_ctx* ctx, int64_t n_start, const double* starts, const int32_t* rows,
                          const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
                          double xatol, double fatol, int32_t maxiter,
                          double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
-/* Batched basin hopping: scipy.optimize.basinhopping(func, x0, niter, T, stepsize, minimizer_kwargs=dict(method='Nelder-Mead'),
- * interval, target_accept_rate, stepwise_factor, rng=...) for n_start starts at once - the reference's global search,
- * MigrationInference.Solve(globalOpt=True) (MigrationInference.py:723-725: T = 0.5, Nelder-Mead with SciPy's defaults, i.e.
- * xatol = fatol = 1e-4, maxiter = maxfev = 200 x n_param), which BASELINE config 3 runs from 16 384 random starts.
- * Every start follows SciPy's runner step for step (_basinhopping.py: initial minimisation, then per hop
- * AdaptiveStepsize.take_step, RandomDisplacement, the local minimisation - misti_nm_solve's machinery, all starts in one set of
- * engine batches - Metropolis.accept_reject, Storage.update).  Incumbents, step sizes and decisions stay in HBM.
- * The random numbers are the CALLER's: SciPy draws, per hop, n_param uniforms for the displacement and then one for the
- * acceptance test from one generator; their number does not depend on the data, so the caller draws them up front -
- *   uniforms   [n_start][niter][n_param + 1]   numpy.random.Generator.random() values (in [0, 1)) in exactly that order,
- *                                              start s from the generator SciPy would be given for start s -
- * and start s then reproduces scipy.optimize.basinhopping(rng = that generator) on the same objective (x, fun, nfev,
- * minimization_failures).  Host buffers; synchronous.
- *   x, llh     [n_start][n_param], [n_start]   lowest successful minimum found (res.x, -res.fun)
- *   nfev, failures, accepted [n_start] or NULL  res.nfev, res.minimization_failures, hops accepted */
+/* MISTI_SPLIT_ONE with hops.  Its own, older order of checks: the context first, then negative counts, n_start == 0 (returns 0), the
+ * model, the pointers, the budgets, the limit. */
 int misti_basinhopping(misti_ctx* ctx, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
                        int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                        double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                        double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
 
-/* misti_basinhopping with a split time and a replicate row PER START, and band bounds and pulse times per start as well: start s is
- * SciPy's basinhopping around Nelder-Mead at split_times[s] against row rows[s], with the model's bands at band_bounds[s] and its
- * pulses at pulse_times[s].  Replaces the reference's global search run as its bootstrap workflow runs everything - test.bs: one
- * process, one MigrationInference and one Solve(globalOpt=True) per (row, split) pair - with ONE call: the hops of all starts go in
- * step, every minimisation of a hop is one batched search (misti_nm_solve_pulses' machinery and its one host path).  Start s returns,
- * bit for bit, what misti_basinhopping(starts[s], split_times[s], jsfs + 8 rows[s], the same uniforms) returns on a context whose
- * model carries band_bounds[s] and pulse_times[s]: x, llh, nfev, failures and accepted.
- *   starts       [n_start][n_param]   (n_param >= 1)
- *   split_times  [n_start]            finite, fractional allowed
- *   rows         [n_start]            0 <= rows[s] < n_rep
- *   band_bounds  [n_start][n_band][2] or NULL   NULL: the model's own, exactly as in misti_nm_solve_pulses
- *   pulse_times  [n_start][n_pulse] or NULL     NULL: the model's own
- *   n_rep, jsfs                       the replicate table [n_rep][8]
- *   niter .. nm_maxfev, x .. accepted as misti_basinhopping
- *   uniforms     [n_start][niter][n_param + 1]
- * A point, or a whole hop, that the engine refuses - a negative rate, a split off the grid, bounds or times broken at that split -
- * has no value and scores +inf; it is never an argument error and the other starts are unaffected (a start none of whose points has
- * a value returns llh = -inf and counts every minimisation as failed, as SciPy does on an objective that returns inf: the Metropolis
- * test treats inf - inf as Python's min(0, nan) does).
- * MISTI_E_ARG, before anything touches the device, for a NULL pointer, n_rep < 1, a row out of range, a non-finite split time,
- * niter < 0, or nm_maxiter, nm_maxfev or interval below 1; MISTI_E_LIMIT for too many starts.  n_start == 0 returns 0.  Host
- * buffers; synchronous; misti_nm_last_stats / misti_nm_last_spec_iterations report on the call (all its minimisations together). */
+/* MISTI_SPLIT_PER_START with hops and a NULL box. */
 int misti_basinhopping_rows(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                             const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
                             int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                             double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                             double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
 
-/* Basin hopping with the split time as a COORDINATE: every simplex has n_param + 1 coordinates, the split last, as in
- * misti_nm_solve_split, and the random displacement moves the split like any other coordinate (SciPy's RandomDisplacement: one
- * stepsize for all, the split in grid-index units).  Replaces the handful of initial splits a local fit of the split needs on its
- * piecewise objective (`--fit-st --grid-st 15 25 5`, the best kept) - and, per bootstrap row, the `for st in A..Z` scans of the
- * test.bs scripts around Solve(globalOpt=True) - with ONE global search per (row, start); n_param == 0 is allowed here: the global
- * search of the `*no.mig.sh` models.
- * What it is not: the reference has no such search, so there is no reference run to agree with.  The parity target is
- * scipy.optimize.basinhopping(T, stepsize, interval, minimizer_kwargs = Nelder-Mead) on this engine's own objective over (parameters,
- * split), no value scoring +inf; SciPy's defaults for the minimiser are maxiter = maxfev = 200 x (n_param + 1).
- *   starts       [n_start][n_param + 1]  initial parameters, then the initial split time (all finite)
- *   rows, band_bounds, pulse_times, n_rep, jsfs   as misti_nm_solve_split
- *   uniforms     [n_start][niter][n_param + 2]   per hop n_param + 1 for the displacement, then one for the Metropolis test
- *   x            [n_start][n_param + 1]  lowest successful minimum, the fitted split last
- *   other arguments, refused points, synchronisation and statistics as misti_basinhopping_rows.
- * MISTI_E_LIMIT for n_param + 1 > MISTI_MAX_PARAMS or too many starts; MISTI_E_ARG as misti_basinhopping_rows, a non-finite start
- * coordinate in the place of the split time - all before anything touches the device.
- * Out of scope: hops out of step (a start taking its next hop while others still minimise), the lanes and the device-list forms. */
+/* MISTI_SPLIT_FITTED with hops and a NULL box (uniforms [n_start][niter][n_param + 2]). */
 int misti_basinhopping_split(misti_ctx* ctx, int64_t n_start, const double* starts, const int32_t* rows,
                              const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs,
                              int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                              double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                              double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted);
 
-/* ---- the box: SciPy's bounds= on the batched searches -------------------------------------------- */
-/* The general form of the search, with box constraints: start s is
- *     scipy.optimize.minimize(f, starts[s], method='Nelder-Mead', bounds=Bounds(box_lo, box_hi), options=dict(xatol, fatol, maxiter))
- * on this engine's objective, bit for bit (SciPy 1.15.3, _minimize_neldermead): the start is clipped to the box; the 5 % / 0.00025
- * simplex is built from the clipped start, a vertex beyond an upper bound is reflected into the interior (2 hi - x) and the simplex
- * clipped; every reflection, expansion, contraction and shrunk vertex is clipped - numpy.clip per coordinate - before the objective
- * sees it.  Without a box the only limit of a search is the engine's refusal of a point (a negative rate, a split off the grid: +inf);
- * with one, rates can be capped, a fitted split kept inside a range, and a coordinate held fixed (lo == hi).  The word "bounds" is
- * taken (band bounds per start), hence "box".
- *   split_times  [n_start], or NULL             set: a split per start and N = n_param coordinates (misti_nm_solve_pulses' search);
- *                                               NULL: the split is the LAST of N = n_param + 1 coordinates (misti_nm_solve_split's
- *                                               search) and is clipped like any other
- *   starts       [n_start][N]                   a start outside its box is no error: it is clipped (SciPy only warns)
- *   rows, n_rep, jsfs, band_bounds, pulse_times as misti_nm_solve_pulses / misti_nm_solve_split
- *   n_box        1 or n_start                   one box for every start, or a box per start
- *   box_lo, box_hi  [n_box][N]                  -inf / +inf: no bound on that side; lo == hi: the coordinate is held fixed
- *   xatol .. status                             as misti_nm_solve; x lies inside the box
- * A box of (-inf, +inf) throughout returns the bytes of misti_nm_solve_pulses / misti_nm_solve_split.
- * MISTI_E_ARG, before anything touches the device: what the search without a box refuses, n_box neither 1 nor n_start, a NULL box
- * pointer, a NaN bound, or a lower bound greater than its upper bound (the message names the box and the coordinate; SciPy raises
- * ValueError there).  Synchronisation and statistics as misti_nm_solve_rows. */
+/* The whole descriptor but the hops: MISTI_SPLIT_PER_START with split_times set, MISTI_SPLIT_FITTED with NULL.  This entry point always
+ * takes a box: n_box == 0 is refused here. */
 int misti_nm_solve_box(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                        int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
                        int64_t n_box, const double* box_lo, const double* box_hi,
                        double xatol, double fatol, int32_t maxiter,
                        double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status);
 
-/* Basin hopping around the boxed search: scipy.optimize.basinhopping(..., minimizer_kwargs=dict(method='Nelder-Mead',
- * bounds=Bounds(box_lo, box_hi))) per start.  As in SciPy the random displacement itself is not clipped - a trial point may leave the
- * box - and the minimisation that starts from it clips it.  The search's arguments as misti_nm_solve_box, the hops' as
- * misti_basinhopping_rows (uniforms [n_start][niter][N + 1]); results, errors and statistics as misti_basinhopping_rows /
- * misti_basinhopping_split plus the box's own argument errors. */
+/* misti_nm_solve_box's descriptor with hops. */
 int misti_basinhopping_box(misti_ctx* ctx, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                            int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
                            int64_t n_box, const double* box_lo, const double* box_hi,

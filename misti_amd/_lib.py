@@ -48,6 +48,26 @@ class Model(C.Structure):
                 ("bands", C.POINTER(Band)), ("pulses", C.POINTER(Pulse))]
 
 
+class Hops(C.Structure):
+    """``misti_hops_t``: basin hopping around a search."""
+    _fields_ = [("niter", C.c_int32), ("T", C.c_double), ("stepsize", C.c_double), ("interval", C.c_int32),
+                ("target_accept_rate", C.c_double), ("stepwise_factor", C.c_double), ("nm_maxfev", C.c_int64),
+                ("uniforms", C.c_void_p), ("nfev", C.c_void_p), ("failures", C.c_void_p), ("accepted", C.c_void_p)]
+
+
+SPLIT_ONE, SPLIT_PER_START, SPLIT_FITTED = 0, 1, 2
+
+
+class Search(C.Structure):
+    """``misti_search_t``: one batched search; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("split", C.c_int32), ("split_time", C.c_double), ("split_times", C.c_void_p),
+                ("n_start", C.c_int64), ("starts", C.c_void_p), ("rows", C.c_void_p), ("n_rep", C.c_int64), ("jsfs", C.c_void_p),
+                ("band_bounds", C.c_void_p), ("pulse_times", C.c_void_p), ("n_box", C.c_int64), ("box_lo", C.c_void_p),
+                ("box_hi", C.c_void_p), ("xatol", C.c_double), ("fatol", C.c_double), ("maxiter", C.c_int32),
+                ("x", C.c_void_p), ("llh", C.c_void_p), ("nit", C.c_void_p), ("nfev", C.c_void_p), ("status", C.c_void_p),
+                ("hops", C.POINTER(Hops))]
+
+
 class MistiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmisti_hip error %d: %s" % (code, msg))
@@ -75,6 +95,7 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_eval_batch_pulses_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_search": (C.c_int, [C.c_void_p, C.POINTER(Search)]),
     "misti_nm_solve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_nm_solve_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,

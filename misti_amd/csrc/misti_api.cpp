@@ -1323,50 +1323,15 @@ int nm_copy_back(misti_ctx* c, const NmWork& w, double* x, double* llh, int32_t*
     return 0;
 }
 
-// The hops of a basin-hopping call around a search (misti_basinhopping*): SciPy's basinhopping arguments, the caller's uniforms and
-// the runner's own counters.  The minimiser's iteration budget is the search's maxiter.
-struct NmHops {
-    int32_t niter;
-    double T, stepsize;
-    int32_t interval;
-    double target_accept_rate, stepwise_factor;
-    int64_t nm_maxfev;
-    const double* uniforms;          // [n_start][niter][N + 1]
-    int32_t *nfev, *failures, *accepted;
-};
-
-// One batched search, as its entry point describes it.
-struct NmSearch {
-    int64_t n_start;
-    const double* starts;            // [n_start][N]
-    enum { ONE_SPLIT, SPLIT_PER_START, SPLIT_FITTED } split;
-    double split_time;               // ONE_SPLIT (misti_nm_solve): the split of every start, `jsfs` is the one data row [8], and nothing below
-                                     // `jsfs` applies - the search the engine evaluates with its replicate epilogue inline
-    const double* split_times;       // SPLIT_PER_START: [n_start].  SPLIT_FITTED: the split is the last of the N = n_param + 1 coordinates
-    const int32_t* rows;             // [n_start] each start's row of ...
-    int64_t n_rep;
-    const double* jsfs;              // ... the table [n_rep][8]: the rows path, llk_rows_kernel behind every batch
-    const int32_t* band_bounds;      // [n_start][n_band][2] or NULL; ignored when the model has no band (as misti_eval_batch)
-    const int32_t* pulse_times;      // [n_start][n_pulse] or NULL; ignored when the model has no pulse (as misti_eval_batch_pulses)
-    double xatol, fatol;
-    int32_t maxiter;
-    double *x, *llh;
-    int32_t *nit, *nfev, *status;
-    const NmHops* hops = nullptr;    // basin hopping around the search; NULL: the search alone
-    bool box = false;                // misti_nm_solve_box / misti_basinhopping_box: SciPy's bounds=Bounds(box_lo, box_hi) on every minimisation
-    int64_t n_box = 0;               // 1: one box for every start; n_start: a box per start
-    const double *box_lo = nullptr, *box_hi = nullptr;      // [n_box][N]
-};
-
 // The arguments of every search, and of basin hopping around one, checked before the first HIP call, in one order: what does not
 // depend on the context, the context, what needs the model.  Bounds or times that break SetModel's checks, and a fitted split the
 // engine refuses, are no argument errors: the engine gives such a point status MISTI_BAD_STRUCTURE and no value, the optimiser
 // +inf - as SciPy sees -JAFSLikelihood.  Leaves the number of coordinates in N and, in `whole`, whether every split time of the
 // rows path is an integer.
-int nm_check(const misti_ctx* c, const NmSearch& q, int& N, bool& whole) {
-    const bool rows_path = q.split != NmSearch::ONE_SPLIT, fit_split = q.split == NmSearch::SPLIT_FITTED;
-    const bool per_start = q.split == NmSearch::SPLIT_PER_START;
-    const NmHops* h = q.hops;
+int nm_check(const misti_ctx* c, const misti_search_t& q, int& N, bool& whole) {
+    const bool rows_path = q.split != MISTI_SPLIT_ONE, fit_split = q.split == MISTI_SPLIT_FITTED;
+    const bool per_start = q.split == MISTI_SPLIT_PER_START;
+    const misti_hops_t* h = q.hops;
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
     if (!q.starts || !q.jsfs || !q.x || !q.llh || (rows_path && !q.rows) || (per_start && !q.split_times))
         return fail(MISTI_E_ARG, "starts / %s / x / llh is NULL", !rows_path ? "jsfs_row" : (per_start ? "split_times / rows / jsfs" : "rows / jsfs"));
@@ -1395,7 +1360,7 @@ int nm_check(const misti_ctx* c, const NmSearch& q, int& N, bool& whole) {
         for (int k = 0; k < N; ++k)
             if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
     // the box: lo == hi holds a coordinate fixed, +-inf leaves a side open, and a start outside its box is clipped (SciPy only warns)
-    if (q.box) {
+    if (q.n_box) {
         if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld starts)", (long long)q.n_box, (long long)q.n_start);
         if (!q.box_lo || !q.box_hi) return fail(MISTI_E_ARG, "box_lo / box_hi is NULL");
         for (int64_t b = 0; b < q.n_box; ++b)
@@ -1414,9 +1379,9 @@ int nm_check(const misti_ctx* c, const NmSearch& q, int& N, bool& whole) {
 // the table and clears the context's work counters.  A path that is not taken allocates and writes nothing: without bounds nothing
 // of the bounds path, and so on.
 template <class Extra>
-int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extra&& extra) {
-    const bool rows_path = q.split != NmSearch::ONE_SPLIT, fit_split = q.split == NmSearch::SPLIT_FITTED;
-    const bool per_start = q.split == NmSearch::SPLIT_PER_START;
+int nm_setup(misti_ctx* c, const misti_search_t& q, int N, bool whole, NmWork& w, Extra&& extra) {
+    const bool rows_path = q.split != MISTI_SPLIT_ONE, fit_split = q.split == MISTI_SPLIT_FITTED;
+    const bool per_start = q.split == MISTI_SPLIT_PER_START;
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = (size_t)q.n_start, V = (size_t)N + 1, R = (size_t)q.n_rep;
     const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
@@ -1429,7 +1394,7 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
     misti::NmState& st = w.st;
     double *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
     int32_t *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
-    const size_t NX = q.box ? (size_t)q.n_box * (size_t)N : 0;                  // doubles per box array
+    const size_t NX = (size_t)q.n_box * (size_t)N;                  // doubles per box array
     double *d_lo = nullptr, *d_hi = nullptr;
     // rows path: what each start hands its points, then one of it per slot of every batch
     auto rows_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
@@ -1451,7 +1416,7 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
     st.split_of = d_split; st.row_of = d_rowof;
     st.bounds_of = d_bounds; st.nb2 = (int)NB2;
     st.pulses_of = d_pulses; st.np = (int)NP;
-    st.box_lo = d_lo; st.box_hi = d_hi; st.box_per_start = q.box && q.n_box != 1 ? 1 : 0;
+    st.box_lo = d_lo; st.box_hi = d_hi; st.box_per_start = q.n_box > 1 ? 1 : 0;
     w.table = d_table; w.consts = d_consts; w.whole = whole;
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(w.d_starts, q.starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
@@ -1472,26 +1437,12 @@ int nm_setup(misti_ctx* c, const NmSearch& q, int N, bool whole, NmWork& w, Extr
     return 0;
 }
 
-// All five searches.
-int nm_solve_impl(misti_ctx* c, const NmSearch& q) {
-    int N = 0;
-    bool whole = false;
-    if (int r = nm_check(c, q, N, whole)) return r;
-    if (q.n_start == 0) return 0;
-    NmWork w;
-    if (int r = nm_setup(c, q, N, whole, w, [](Carver<double>&, Carver<int32_t>&) {})) return r;
-    if (int r = nm_run(c, w, q.split == NmSearch::ONE_SPLIT ? q.split_time : 0.0, q.xatol, q.fatol, q.maxiter, INT64_MAX)) return r;
-    if (int r = nm_copy_back(c, w, q.x, q.llh, q.nit, q.nfev, q.status)) return r;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// Basin hopping around a checked search with n_start >= 1 (all three misti_basinhopping*): SciPy's runner per start, all starts in
+// Basin hopping around a checked search with n_start >= 1 (a descriptor with hops): SciPy's runner per start, all starts in
 // step - the initial minimisation, then per hop the displacement (bh_step), the minimisation of every trial point and the Metropolis
 // test (bh_update).  The hop state lies behind the search's own in the same two allocations; with the split as a coordinate it is
 // displaced like any other (bh.N counts it).
-int bh_run(misti_ctx* c, const NmSearch& q, int N, bool whole) {
-    const NmHops& h = *q.hops;
+int bh_run(misti_ctx* c, const misti_search_t& q, int N, bool whole) {
+    const misti_hops_t& h = *q.hops;
     const int niter = h.niter;
     const size_t S = (size_t)q.n_start, U = S * (size_t)niter * (size_t)(N + 1);
     NmWork w;
@@ -1515,7 +1466,7 @@ int bh_run(misti_ctx* c, const NmSearch& q, int N, bool whole) {
         HIP_TRY(hipMemcpyAsync(bh.stepsize, st0.data(), S * sizeof(double), hipMemcpyHostToDevice, sm));
         HIP_TRY(hipStreamSynchronize(sm));                  // st0 is a local
     }
-    const double split_time = q.split == NmSearch::ONE_SPLIT ? q.split_time : 0.0;
+    const double split_time = q.split == MISTI_SPLIT_ONE ? q.split_time : 0.0;
     // BasinHoppingRunner.__init__: the initial minimisation from the start itself
     if (int r = nm_run(c, w, split_time, q.xatol, q.fatol, q.maxiter, h.nm_maxfev)) return r;
     HIP_TRY(misti::launch_bh_update(bh, w.st, w.d_starts, w.d_llh, w.st.shrunk, -1, niter, d_uni, sm));
@@ -1534,71 +1485,90 @@ int bh_run(misti_ctx* c, const NmSearch& q, int N, bool whole) {
     return 0;
 }
 
-// misti_basinhopping_rows / misti_basinhopping_split: the search's arguments and the hops' in nm_check's order, then the hops.
-int bh_impl(misti_ctx* c, NmSearch q, const NmHops& h) {
-    q.hops = &h;
+// Every search and every basin hopping, as its descriptor says: the shared path behind misti_search and the ten older entry points.
+int search_impl(misti_ctx* c, const misti_search_t& q) {
     int N = 0;
     bool whole = false;
     if (int r = nm_check(c, q, N, whole)) return r;
     if (q.n_start == 0) return 0;
-    return bh_run(c, q, N, whole);
+    if (q.hops) return bh_run(c, q, N, whole);
+    NmWork w;
+    if (int r = nm_setup(c, q, N, whole, w, [](Carver<double>&, Carver<int32_t>&) {})) return r;
+    if (int r = nm_run(c, w, q.split == MISTI_SPLIT_ONE ? q.split_time : 0.0, q.xatol, q.fatol, q.maxiter, INT64_MAX)) return r;
+    if (int r = nm_copy_back(c, w, q.x, q.llh, q.nit, q.nfev, q.status)) return r;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
-// The general form of the search: a split per start (split_times set) or the split as the last coordinate (NULL), rows, bounds and
-// pulse times per start, and a box.
-NmSearch box_search(int64_t n_start, const double* starts, const double* split_times, const int32_t* rows, int64_t n_rep, const double* jsfs,
-                    const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_box, const double* box_lo, const double* box_hi,
-                    double xatol, double fatol, int32_t maxiter, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    NmSearch q{n_start, starts, split_times ? NmSearch::SPLIT_PER_START : NmSearch::SPLIT_FITTED, 0.0, split_times, rows, n_rep, jsfs,
-               band_bounds, pulse_times, xatol, fatol, maxiter, x, llh, nit, nfev, status};
-    q.box = true; q.n_box = n_box; q.box_lo = box_lo; q.box_hi = box_hi;
-    return q;
+// misti_nm_solve_box / misti_basinhopping_box took a box always: n_box == 0, "no box" in a descriptor, is theirs to refuse.
+int no_box(int64_t n_box, int64_t n_start) {
+    if (n_box == 0 && n_start != 0) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got 0 for %lld starts)", (long long)n_start);
+    return 0;
 }
 
 }  // namespace
 
 extern "C" {
 
+int misti_search(misti_ctx* c, const misti_search_t* q) {
+    if (!q) return fail(MISTI_E_ARG, "the search descriptor is NULL");
+    if (q->size != sizeof(misti_search_t))
+        return fail(MISTI_E_ARG, "the search descriptor's size is %u, this library's misti_search_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_search_t));
+    if (q->split != MISTI_SPLIT_ONE && q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
+        return fail(MISTI_E_ARG, "the search descriptor's split mode %d is none of MISTI_SPLIT_*", (int)q->split);
+    if (q->hops && (q->nit || q->nfev || q->status)) return fail(MISTI_E_ARG, "with hops, nit / nfev / status of the search must be NULL (the hops report their own)");
+    return search_impl(c, *q);
+}
+
+// The ten older entry points: each fills the descriptor it is (in the descriptor's field order) and joins the shared path.
 int misti_nm_solve(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
                    double xatol, double fatol, int32_t maxiter,
                    double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_impl(c, {n_start, starts, NmSearch::ONE_SPLIT, split_time, nullptr, nullptr, 1, jsfs_row, nullptr, nullptr,
-                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
+    return search_impl(c, {sizeof(misti_search_t), MISTI_SPLIT_ONE, split_time, nullptr, n_start, starts, nullptr, 1, jsfs_row, nullptr, nullptr,
+                           0, nullptr, nullptr, xatol, fatol, maxiter, x, llh, nit, nfev, status, nullptr});
 }
 
 int misti_nm_solve_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                         int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                         double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, nullptr, nullptr,
-                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
+    return misti_nm_solve_pulses(c, n_start, starts, split_times, rows, nullptr, nullptr, n_rep, jsfs, xatol, fatol, maxiter, x, llh, nit, nfev, status);
 }
 
 int misti_nm_solve_bounds(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                           double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, band_bounds, nullptr,
-                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
+    return misti_nm_solve_pulses(c, n_start, starts, split_times, rows, band_bounds, nullptr, n_rep, jsfs, xatol, fatol, maxiter, x, llh, nit, nfev, status);
 }
 
 int misti_nm_solve_pulses(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
                           const int32_t* band_bounds, const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double xatol, double fatol,
                           int32_t maxiter, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, band_bounds, pulse_times,
-                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
+    return search_impl(c, {sizeof(misti_search_t), MISTI_SPLIT_PER_START, 0.0, split_times, n_start, starts, rows, n_rep, jsfs, band_bounds, pulse_times,
+                           0, nullptr, nullptr, xatol, fatol, maxiter, x, llh, nit, nfev, status, nullptr});
 }
 
 int misti_nm_solve_split(misti_ctx* c, int64_t n_start, const double* starts, const int32_t* rows, const int32_t* band_bounds,
                          const int32_t* pulse_times, int64_t n_rep, const double* jsfs, double xatol, double fatol, int32_t maxiter,
                          double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_impl(c, {n_start, starts, NmSearch::SPLIT_FITTED, 0.0, nullptr, rows, n_rep, jsfs, band_bounds, pulse_times,
-                             xatol, fatol, maxiter, x, llh, nit, nfev, status});
+    return search_impl(c, {sizeof(misti_search_t), MISTI_SPLIT_FITTED, 0.0, nullptr, n_start, starts, rows, n_rep, jsfs, band_bounds, pulse_times,
+                           0, nullptr, nullptr, xatol, fatol, maxiter, x, llh, nit, nfev, status, nullptr});
+}
+
+int misti_nm_solve_box(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
+                       int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
+                       int64_t n_box, const double* box_lo, const double* box_hi, double xatol, double fatol, int32_t maxiter,
+                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
+    if (int r = no_box(n_box, n_start)) return r;
+    return search_impl(c, {sizeof(misti_search_t), split_times ? MISTI_SPLIT_PER_START : MISTI_SPLIT_FITTED, 0.0, split_times, n_start, starts, rows, n_rep, jsfs,
+                           band_bounds, pulse_times, n_box, box_lo, box_hi, xatol, fatol, maxiter, x, llh, nit, nfev, status, nullptr});
 }
 
 int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
                        int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                        double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                        double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
-    // (this entry point's own order of checks, older than nm_check's: the context first, no starts before the pointers)
+    // (this entry point's own order of checks, older than nm_check's: the context first, no starts before the pointers; what passes
+    //  them passes nm_check)
     if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_start < 0 || niter < 0) return fail(MISTI_E_ARG, "negative number of starts / hops");
     if (n_start == 0) return 0;
@@ -1607,9 +1577,9 @@ int misti_basinhopping(misti_ctx* c, int64_t n_start, const double* starts, doub
     if (!starts || !jsfs_row || !x || !llh || (niter > 0 && !uniforms)) return fail(MISTI_E_ARG, "starts / jsfs_row / uniforms / x / llh is NULL");
     if (nm_maxiter < 1 || nm_maxfev < 1 || interval < 1) return fail(MISTI_E_ARG, "nm_maxiter, nm_maxfev and interval must be >= 1");
     if (n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
-    const NmHops h{niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted};
-    return bh_run(c, {n_start, starts, NmSearch::ONE_SPLIT, split_time, nullptr, nullptr, 1, jsfs_row, nullptr, nullptr,
-                      xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr, &h}, N, false);
+    const misti_hops_t h{niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted};
+    return search_impl(c, {sizeof(misti_search_t), MISTI_SPLIT_ONE, split_time, nullptr, n_start, starts, nullptr, 1, jsfs_row, nullptr, nullptr,
+                           0, nullptr, nullptr, xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr, &h});
 }
 
 int misti_basinhopping_rows(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
@@ -1617,9 +1587,9 @@ int misti_basinhopping_rows(misti_ctx* c, int64_t n_start, const double* starts,
                             int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                             double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                             double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
-    return bh_impl(c, {n_start, starts, NmSearch::SPLIT_PER_START, 0.0, split_times, rows, n_rep, jsfs, band_bounds, pulse_times,
-                       xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr},
-                   {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
+    const misti_hops_t h{niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted};
+    return search_impl(c, {sizeof(misti_search_t), MISTI_SPLIT_PER_START, 0.0, split_times, n_start, starts, rows, n_rep, jsfs, band_bounds, pulse_times,
+                           0, nullptr, nullptr, xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr, &h});
 }
 
 int misti_basinhopping_split(misti_ctx* c, int64_t n_start, const double* starts, const int32_t* rows,
@@ -1627,17 +1597,9 @@ int misti_basinhopping_split(misti_ctx* c, int64_t n_start, const double* starts
                              int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                              double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                              double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
-    return bh_impl(c, {n_start, starts, NmSearch::SPLIT_FITTED, 0.0, nullptr, rows, n_rep, jsfs, band_bounds, pulse_times,
-                       xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr},
-                   {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
-}
-
-int misti_nm_solve_box(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
-                       int64_t n_rep, const double* jsfs, const int32_t* band_bounds, const int32_t* pulse_times,
-                       int64_t n_box, const double* box_lo, const double* box_hi, double xatol, double fatol, int32_t maxiter,
-                       double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    return nm_solve_impl(c, box_search(n_start, starts, split_times, rows, n_rep, jsfs, band_bounds, pulse_times, n_box, box_lo, box_hi,
-                                       xatol, fatol, maxiter, x, llh, nit, nfev, status));
+    const misti_hops_t h{niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted};
+    return search_impl(c, {sizeof(misti_search_t), MISTI_SPLIT_FITTED, 0.0, nullptr, n_start, starts, rows, n_rep, jsfs, band_bounds, pulse_times,
+                           0, nullptr, nullptr, xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr, &h});
 }
 
 int misti_basinhopping_box(misti_ctx* c, int64_t n_start, const double* starts, const double* split_times, const int32_t* rows,
@@ -1646,9 +1608,10 @@ int misti_basinhopping_box(misti_ctx* c, int64_t n_start, const double* starts, 
                            int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                            double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                            double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
-    return bh_impl(c, box_search(n_start, starts, split_times, rows, n_rep, jsfs, band_bounds, pulse_times, n_box, box_lo, box_hi,
-                                 xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr),
-                   {niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted});
+    if (int r = no_box(n_box, n_start)) return r;
+    const misti_hops_t h{niter, T, stepsize, interval, target_accept_rate, stepwise_factor, nm_maxfev, uniforms, nfev, failures, accepted};
+    return search_impl(c, {sizeof(misti_search_t), split_times ? MISTI_SPLIT_PER_START : MISTI_SPLIT_FITTED, 0.0, split_times, n_start, starts, rows, n_rep, jsfs,
+                           band_bounds, pulse_times, n_box, box_lo, box_hi, xatol, fatol, nm_maxiter, x, llh, nullptr, nullptr, nullptr, &h});
 }
 
 }  // extern "C"

@@ -77,13 +77,12 @@ def _f64(a, shape=None):
     return a
 
 
-def _box_args(box, N):
-    """``(lo, hi)``, each ``[N]`` or ``[S][N]``, as the ``n_box, box_lo, box_hi`` arguments of ``misti_nm_solve_box``."""
+def _box_arrays(box, N):
+    """``(lo, hi)``, each ``[N]`` or ``[S][N]``, as the ``box_lo`` / ``box_hi`` arrays ``[n_box][N]`` of a search."""
     lo, hi = (_f64(a) for a in box)
     if lo.shape != hi.shape or lo.ndim not in (1, 2) or lo.shape[-1] != N:
         raise ValueError("box: lo and hi must both be [%d] or [S][%d] (got %s and %s)" % (N, N, lo.shape, hi.shape))
-    lo, hi = lo.reshape(-1, N), hi.reshape(-1, N)
-    return [lo.shape[0], lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)]
+    return lo.reshape(-1, N), hi.reshape(-1, N)
 
 
 def _model_struct(times, lh, bands, pulses, n_param, cpfit, true_eps, smooth, unfolded, sample_date, mixture_th):
@@ -505,52 +504,63 @@ class Engine:
         _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
         return dict(iterations_issued=int(stats[0]), slots=int(stats[1]), speculative_iterations=int(spec.value))
 
-    # what each search takes between `starts` and the tolerances, in its prototype's order (include/misti_hip.h)
-    _NM_TAKES = {"misti_nm_solve": ("split_time", "jsfs_row"),
-                 "misti_nm_solve_rows": ("split_times", "rows", "table"),
-                 "misti_nm_solve_bounds": ("split_times", "rows", "band_bounds", "table"),
-                 "misti_nm_solve_pulses": ("split_times", "rows", "band_bounds", "pulse_times", "table"),
-                 "misti_nm_solve_split": ("rows", "band_bounds", "pulse_times", "table"),
-                 "misti_nm_solve_box": ("split_times", "rows", "table", "band_bounds", "pulse_times", "box")}
-
-    def _nm_search(self, symbol, starts, tol, maxiter, **given):
-        """Every ``misti_nm_solve*``: shapes the inputs ``_NM_TAKES[symbol]`` names, allocates the results, calls ``symbol`` and returns
-        the results with the work counters.  ``misti_nm_solve_split``'s starts carry the split as one coordinate more.  Band bounds and
-        pulse times that are ``None``, or that the model has no band / pulse for, go as NULL."""
-        fitted = symbol == "misti_nm_solve_split" or (symbol == "misti_nm_solve_box" and given["split_times"] is None)
-        N = self.n_param + (1 if fitted else 0)
+    def search(self, starts, table, *, split_time=None, split_times=None, rows=None, band_bounds=None, pulse_times=None, box=None,
+               hops=None, rngs=None, xatol=1e-4, fatol=1e-4, maxiter=None):
+        """``misti_search``: every batched search and every basin hopping is this call (``misti_search_t`` in include/misti_hip.h
+        documents the fields).  ``split_time`` given: one split for all starts and ``table`` the one data row ``[8]``; ``split_times``
+        given: a split per start; neither: the split is the last of ``n_param + 1`` coordinates of ``starts``.  ``rows`` ``[S]`` into
+        ``table[n_rep][8]``; ``band_bounds`` / ``pulse_times`` per start (``None``, or a model without band / pulse: NULL); ``box``
+        ``(lo, hi)``, each ``[N]`` or ``[S][N]``.  ``hops``: a dict of ``niter``, ``T``, ``stepsize``, ``interval``,
+        ``target_accept_rate``, ``stepwise_factor``, ``nm_maxfev`` (SciPy's defaults where absent or None) with ``rngs`` one
+        generator or seed per start - basin hopping around the search.  ``maxiter`` defaults to 1000, under hops to ``200 x N``.
+        Returns dict(x[S][N], llh[S], nit / nfev / status[S] - with hops nfev / failures / accepted[S] -, and the work counters)."""
+        one = split_time is not None
+        N = self.n_param + (0 if one or split_times is not None else 1)
         st = _f64(starts, (-1, N))
         S = st.shape[0]
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
         i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
-        shaped = {"split_time": lambda v: [float(v)],
-                  "jsfs_row": lambda v: [ptr(_f64(v, (8,)))],
-                  "split_times": lambda v: [ptr(_f64(v, (S,)) if v is not None else None)],       # None: misti_nm_solve_box with a fitted split
-                  "box": lambda v: _box_args(v, N),
-                  "rows": lambda v: [ptr(i32(v, (S,)))],
-                  "band_bounds": lambda v: [ptr(i32(v, (S, self.n_band, 2)) if v is not None and self.n_band else None)],
-                  "pulse_times": lambda v: [ptr(i32(v, (S, self.n_pulse)) if v is not None and self.n_pulse else None)],
-                  "table": lambda v: [_f64(v, (-1, 8)).shape[0], ptr(_f64(v, (-1, 8)))]}
-        args = [a for name in self._NM_TAKES[symbol] for a in shaped[name](given[name])]
-        x = np.empty((S, N))
-        llh = np.empty(S)
-        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
-        _lib.check(getattr(self._lib, symbol)(self._ctx, S, ptr(st), *args, float(tol), float(tol), int(maxiter),
-                                              ptr(x), ptr(llh), ptr(nit), ptr(nfev), ptr(status)))
-        return dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, **self._nm_stats())
+        tab = _f64(table, (8,) if one else (-1, 8))
+        sp = _f64(split_times, (S,)) if split_times is not None else None
+        r_of = i32(rows, (S,)) if rows is not None else None
+        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
+        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
+        lo, hi = _box_arrays(box, N) if box is not None else (None, None)
+        x, llh = np.empty((S, N)), np.empty(S)
+        counters = dict(zip(("nit", "nfev", "status") if hops is None else ("nfev", "failures", "accepted"),
+                            (np.empty(S, dtype=np.int32) for _ in range(3))))
+        q = _lib.Search(size=C.sizeof(_lib.Search), split=_lib.SPLIT_ONE if one else _lib.SPLIT_PER_START if sp is not None else _lib.SPLIT_FITTED,
+                        split_time=float(split_time) if one else 0.0, split_times=ptr(sp), n_start=S, starts=ptr(st), rows=ptr(r_of),
+                        n_rep=1 if one else tab.shape[0], jsfs=ptr(tab), band_bounds=ptr(bb), pulse_times=ptr(pt),
+                        n_box=0 if lo is None else lo.shape[0], box_lo=ptr(lo), box_hi=ptr(hi), xatol=float(xatol), fatol=float(fatol),
+                        x=ptr(x), llh=ptr(llh))
+        if hops is None:
+            q.maxiter = int(maxiter if maxiter is not None else 1000)
+            q.nit, q.nfev, q.status = (ptr(a) for a in counters.values())
+        else:
+            h = {k: v for k, v in hops.items() if v is not None}
+            uni = draw_uniforms(rngs, S, max(int(h.get("niter", 100)), 0), N)          # (a negative niter is the library's to refuse)
+            q.maxiter = int(maxiter if maxiter is not None else 200 * N)
+            hop = _lib.Hops(niter=int(h.get("niter", 100)), T=float(h.get("T", 0.5)), stepsize=float(h.get("stepsize", 0.5)),
+                            interval=int(h.get("interval", 50)), target_accept_rate=float(h.get("target_accept_rate", 0.5)),
+                            stepwise_factor=float(h.get("stepwise_factor", 0.9)), nm_maxfev=int(h.get("nm_maxfev", 200 * N)), uniforms=ptr(uni))
+            hop.nfev, hop.failures, hop.accepted = (ptr(a) for a in counters.values())
+            q.hops = C.pointer(hop)
+        _lib.check(self._lib.misti_search(self._ctx, C.byref(q)))
+        return dict(x=x, llh=llh, **counters, **self._nm_stats())
 
     def nm_solve(self, starts, split_time, jsfs_row, tol=1e-4, maxiter=1000):
         """``misti_nm_solve``: SciPy-exact Nelder-Mead from every row of ``starts`` with the simplices resident in
         HBM (``MigrationInference.Solve`` for many starts; reference semantics :718-733).
         Returns dict(x[S][P], llh[S], nit[S], nfev[S], status[S]) - status 0 converged, 2 iteration budget."""
-        return self._nm_search("misti_nm_solve", starts, tol, maxiter, split_time=split_time, jsfs_row=jsfs_row)
+        return self.search(starts, jsfs_row, split_time=split_time, xatol=tol, fatol=tol, maxiter=maxiter)
 
     def nm_solve_rows(self, starts, split_times, rows, jsfs, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_rows``: ``nm_solve`` with a split time and a replicate row PER START - start s is SciPy's
         Nelder-Mead at ``split_times[s]`` against ``jsfs[rows[s]]``, all starts in one batched search (the bootstrap profiles of
         the reference's ``test.bs`` scripts, one ``Solve`` per (replicate, split) pair there).  ``jsfs`` is ``[n_rep][8]``.
         Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` bit for bit."""
-        return self._nm_search("misti_nm_solve_rows", starts, tol, maxiter, split_times=split_times, rows=rows, table=jsfs)
+        return self.search(starts, jsfs, split_times=split_times, rows=rows, xatol=tol, fatol=tol, maxiter=maxiter)
 
     def nm_solve_bounds(self, starts, split_times, rows, jsfs, band_bounds, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_bounds``: ``nm_solve_rows`` with the band bounds PER START as well - start s is SciPy's Nelder-Mead at
@@ -560,8 +570,7 @@ class Engine:
         that break SetModel's checks give that start ``llh = -inf``.  ``band_bounds=None`` is ``nm_solve_rows``.
         Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` on an engine whose
         bands carry ``band_bounds[s]``, bit for bit."""
-        return self._nm_search("misti_nm_solve_bounds", starts, tol, maxiter, split_times=split_times, rows=rows, band_bounds=band_bounds,
-                               table=jsfs)
+        return self.search(starts, jsfs, split_times=split_times, rows=rows, band_bounds=band_bounds, xatol=tol, fatol=tol, maxiter=maxiter)
 
     def nm_solve_pulses(self, starts, split_times, rows, jsfs, band_bounds, pulse_times, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_pulses``: ``nm_solve_bounds`` with the pulse times PER START as well (``[n_start][n_pulse]`` ints, on
@@ -570,8 +579,8 @@ class Engine:
         ``nm_solve_bounds``.
         Returns what ``nm_solve`` returns; start s equals ``nm_solve(starts[s], split_times[s], jsfs[rows[s]])`` on an engine whose
         model carries ``band_bounds[s]`` and ``pulse_times[s]``, bit for bit."""
-        return self._nm_search("misti_nm_solve_pulses", starts, tol, maxiter, split_times=split_times, rows=rows, table=jsfs,
-                               band_bounds=band_bounds, pulse_times=pulse_times)
+        return self.search(starts, jsfs, split_times=split_times, rows=rows, band_bounds=band_bounds, pulse_times=pulse_times,
+                           xatol=tol, fatol=tol, maxiter=maxiter)
 
     def nm_solve_split(self, starts, rows, table, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_split``: the split time as the LAST coordinate of every simplex - ``starts`` is ``[S][n_param + 1]``
@@ -581,10 +590,7 @@ class Engine:
         (``n_param == 0``) its only search.  ``band_bounds`` / ``pulse_times`` per start as in ``nm_solve_pulses`` (band end -1: the
         point's own split index).  A point whose split the engine refuses scores +inf; a start without any value has ``llh = -inf``.
         Returns what ``nm_solve`` returns with ``x[S][n_param + 1]``, plus ``split`` (= ``x[:, -1]``)."""
-        r = self._nm_search("misti_nm_solve_split", starts, tol, maxiter, rows=rows, table=table, band_bounds=band_bounds,
-                            pulse_times=pulse_times)
-        r["split"] = r["x"][:, -1].copy()
-        return r
+        return self.nm_solve_box(starts, rows, table, None, None, band_bounds, pulse_times, tol, maxiter)
 
     def nm_solve_box(self, starts, rows, table, box, split_times=None, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000):
         """``misti_nm_solve_box``: the batched search with box constraints - start s is ``scipy.optimize.minimize(f, starts[s],
@@ -594,8 +600,8 @@ class Engine:
         (``nm_solve_split``'s search, the split clipped like any other coordinate); ``split_times`` given: a split per start,
         ``starts`` is ``[S][n_param]`` (``nm_solve_pulses``' search).  ``optimize.box_initial_simplex`` / ``box_clip`` state the rule.
         Returns what ``nm_solve_split`` returns (``split``: the fitted splits, or ``split_times`` themselves)."""
-        r = self._nm_search("misti_nm_solve_box", starts, tol, maxiter, split_times=split_times, rows=rows, table=table,
-                            band_bounds=band_bounds, pulse_times=pulse_times, box=box)
+        r = self.search(starts, table, split_times=split_times, rows=rows, band_bounds=band_bounds, pulse_times=pulse_times, box=box,
+                        xatol=tol, fatol=tol, maxiter=maxiter)
         r["split"] = r["x"][:, -1].copy() if split_times is None else np.array(split_times, dtype=np.float64).reshape(-1)
         return r
 
@@ -607,53 +613,11 @@ class Engine:
         ``rngs``: one ``numpy.random.Generator`` per start (or one seed per start): the uniforms SciPy would draw from it
         (per hop ``n_param`` for the displacement, one for the Metropolis test) are drawn here, up front.
         Returns dict(x[S][P], llh[S], nfev[S], failures[S], accepted[S])."""
-        st = _f64(starts, (-1, self.n_param))
-        S, N = st.shape
-        row = _f64(jsfs_row, (8,))
-        uni = draw_uniforms(rngs, S, int(niter), N)
-        x = np.empty((S, N))
-        llh = np.empty(S)
-        nfev, failures, accepted = (np.empty(S, dtype=np.int32) for _ in range(3))
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(self._lib.misti_basinhopping(self._ctx, S, ptr(st), float(split_time), ptr(row), int(niter), float(T), float(stepsize), int(interval),
-                                                float(target_accept_rate), float(stepwise_factor), float(xatol), float(fatol),
-                                                int(nm_maxiter if nm_maxiter is not None else 200 * N), int(nm_maxfev if nm_maxfev is not None else 200 * N),
-                                                ptr(uni), ptr(x), ptr(llh), ptr(nfev), ptr(failures), ptr(accepted)))
-        stats = self._nm_stats()
-        return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, iterations_issued=stats["iterations_issued"], slots=stats["slots"])
-
-    def _bh_search(self, symbol, starts, rows, table, rngs, split_times, band_bounds, pulse_times, niter, T, stepsize, interval,
-                   target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev, box=None):
-        """``misti_basinhopping_rows`` / ``misti_basinhopping_split``: shapes the inputs, draws the uniforms, calls ``symbol`` and returns
-        the results with the work counters.  ``split_times`` is None for the split form, whose starts carry the split as one coordinate
-        more.  Band bounds and pulse times that are ``None``, or that the model has no band / pulse for, go as NULL.
-        ``misti_basinhopping_box`` (``box`` given) takes the same search in its own order: the split times (or NULL), the rows, the table,
-        bounds and times, then the box."""
-        N = self.n_param + (1 if split_times is None else 0)
-        st = _f64(starts, (-1, N))
-        S = st.shape[0]
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
-        tab = _f64(table, (-1, 8))
-        per_start = [] if split_times is None else [ptr(_f64(split_times, (S,)))]
-        r_of = i32(rows, (S,))
-        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
-        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
-        uni = draw_uniforms(rngs, S, max(int(niter), 0), N)          # (a negative niter is the library's to refuse)
-        x = np.empty((S, N))
-        llh = np.empty(S)
-        nfev, failures, accepted = (np.empty(S, dtype=np.int32) for _ in range(3))
-        if box is None:
-            search = [*per_start, ptr(r_of), ptr(bb), ptr(pt), tab.shape[0], ptr(tab)]
-        else:
-            search = [per_start[0] if per_start else None, ptr(r_of), tab.shape[0], ptr(tab), ptr(bb), ptr(pt), *_box_args(box, N)]
-        _lib.check(getattr(self._lib, symbol)(self._ctx, S, ptr(st), *search,
-                                              int(niter), float(T), float(stepsize), int(interval), float(target_accept_rate),
-                                              float(stepwise_factor), float(xatol), float(fatol),
-                                              int(nm_maxiter if nm_maxiter is not None else 200 * N),
-                                              int(nm_maxfev if nm_maxfev is not None else 200 * N),
-                                              ptr(uni), ptr(x), ptr(llh), ptr(nfev), ptr(failures), ptr(accepted)))
-        return dict(x=x, llh=llh, nfev=nfev, failures=failures, accepted=accepted, **self._nm_stats())
+        r = self.search(starts, jsfs_row, split_time=split_time, rngs=rngs, xatol=xatol, fatol=fatol, maxiter=nm_maxiter,
+                        hops=dict(niter=niter, T=T, stepsize=stepsize, interval=interval, target_accept_rate=target_accept_rate,
+                                  stepwise_factor=stepwise_factor, nm_maxfev=nm_maxfev))
+        del r["speculative_iterations"]
+        return r
 
     def basinhopping_rows(self, starts, split_times, rows, table, rngs, band_bounds=None, pulse_times=None, niter=100, T=0.5, stepsize=0.5,
                           interval=50, target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
@@ -665,8 +629,10 @@ class Engine:
         Returns what ``basinhopping`` returns plus ``speculative_iterations``; start s equals
         ``basinhopping(starts[s:s+1], split_times[s], table[rows[s]], [rngs[s]])`` on an engine whose model carries ``band_bounds[s]`` and
         ``pulse_times[s]``, bit for bit."""
-        return self._bh_search("misti_basinhopping_rows", starts, rows, table, rngs, np.asarray(split_times, dtype=np.float64), band_bounds,
-                               pulse_times, niter, T, stepsize, interval, target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev)
+        return self.search(starts, table, split_times=split_times, rows=rows, band_bounds=band_bounds, pulse_times=pulse_times, rngs=rngs,
+                           xatol=xatol, fatol=fatol, maxiter=nm_maxiter,
+                           hops=dict(niter=niter, T=T, stepsize=stepsize, interval=interval, target_accept_rate=target_accept_rate,
+                                     stepwise_factor=stepwise_factor, nm_maxfev=nm_maxfev))
 
     def basinhopping_split(self, starts, rows, table, rngs, band_bounds=None, pulse_times=None, niter=100, T=0.5, stepsize=0.5, interval=50,
                            target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None, nm_maxfev=None):
@@ -677,10 +643,8 @@ class Engine:
         counterpart of ``nm_solve_split`` on its piecewise objective, and the global search of a model without an optimised
         parameter.  ``band_bounds`` / ``pulse_times`` per start as in ``nm_solve_split``.
         Returns what ``basinhopping_rows`` returns with ``x[S][n_param + 1]``, plus ``split`` (= ``x[:, -1]``)."""
-        r = self._bh_search("misti_basinhopping_split", starts, rows, table, rngs, None, band_bounds, pulse_times, niter, T, stepsize, interval,
-                            target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev)
-        r["split"] = r["x"][:, -1].copy()
-        return r
+        return self.basinhopping_box(starts, rows, table, rngs, None, None, band_bounds, pulse_times, niter, T, stepsize, interval,
+                                     target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev)
 
     def basinhopping_box(self, starts, rows, table, rngs, box, split_times=None, band_bounds=None, pulse_times=None, niter=100, T=0.5,
                          stepsize=0.5, interval=50, target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, nm_maxiter=None,
@@ -689,10 +653,11 @@ class Engine:
         minimizer_kwargs=dict(method='Nelder-Mead', bounds=Bounds(lo, hi)))``.  ``box`` and ``split_times`` as in ``nm_solve_box``; the
         displacement is not clipped (SciPy's is not), the minimisation from the trial point clips it.  The other arguments as
         ``basinhopping_split`` / ``basinhopping_rows``.  Returns what ``basinhopping_split`` returns."""
-        sp = None if split_times is None else np.asarray(split_times, dtype=np.float64)
-        r = self._bh_search("misti_basinhopping_box", starts, rows, table, rngs, sp, band_bounds, pulse_times, niter, T, stepsize, interval,
-                            target_accept_rate, stepwise_factor, xatol, fatol, nm_maxiter, nm_maxfev, box=box)
-        r["split"] = r["x"][:, -1].copy() if sp is None else sp.reshape(-1).copy()
+        r = self.search(starts, table, split_times=split_times, rows=rows, band_bounds=band_bounds, pulse_times=pulse_times, box=box,
+                        rngs=rngs, xatol=xatol, fatol=fatol, maxiter=nm_maxiter,
+                        hops=dict(niter=niter, T=T, stepsize=stepsize, interval=interval, target_accept_rate=target_accept_rate,
+                                  stepwise_factor=stepwise_factor, nm_maxfev=nm_maxfev))
+        r["split"] = r["x"][:, -1].copy() if split_times is None else np.array(split_times, dtype=np.float64).reshape(-1)
         return r
 
     def enable_solver_trace(self, on=True):

@@ -362,9 +362,8 @@ def scan_best(engine, split, params, jsfs_rows, k=1, band_bounds=None, pulse_tim
 def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000, box=None):
     """Scan, keep the ``k`` best candidates per replicate, polish those: ``scan_best``, then ONE batched search whose starts are the
     listed candidates - row r's j-th place is a start with that candidate's parameters, split, band bounds and pulse times against
-    row r (row outermost, place innermost; a -1 place gives no start) - through ``misti_nm_solve_pulses`` / ``_bounds`` / ``_rows``,
-    whichever the given arrays need.  Per row the best polished search is kept (``_best_start_profile``'s rule: the first maximum,
-    NaN never wins).  Where ``--grid-solve`` searches from every (row, split, start) triple, this searches from ``k`` per row.
+    row r (row outermost, place innermost; a -1 place gives no start) - ``misti_search`` with whichever of the arrays are given.
+    Per row the best polished search is kept (``_best_start_profile``'s rule: the first maximum, NaN never wins).  Where ``--grid-solve`` searches from every (row, split, start) triple, this searches from ``k`` per row.
     ``box``: ``(lo, hi)``, each ``[n_param]`` - the polish runs inside it (``misti_nm_solve_box``: SciPy's ``bounds=``); the scan is not
     touched.
     Returns dict(best[R][k], best_llk[R][k], scan_status[n] (the scan's), x[R][n_param], split[R], llh[R], nit / nfev / status[R],
@@ -386,15 +385,9 @@ def scan_polish(engine, split, params, jsfs_rows, k, band_bounds=None, pulse_tim
     if cand.size == 0:
         res = dict(x=np.empty((0, N)), llh=np.empty(0), nit=np.empty(0, dtype=np.int32), nfev=np.empty(0, dtype=np.int32),
                    status=np.empty(0, dtype=np.int32), iterations_issued=0, slots=0, speculative_iterations=0)
-    elif box is not None:
-        res = engine.nm_solve_box(params[cand], r_of.astype(np.int32), rows, box, split_times=split[cand], band_bounds=bb, pulse_times=pt,
-                                  tol=tol, maxiter=maxiter)
-    elif pt is not None:
-        res = engine.nm_solve_pulses(params[cand], split[cand], r_of.astype(np.int32), rows, bb, pt, tol=tol, maxiter=maxiter)
-    elif bb is not None:
-        res = engine.nm_solve_bounds(params[cand], split[cand], r_of.astype(np.int32), rows, bb, tol=tol, maxiter=maxiter)
     else:
-        res = engine.nm_solve_rows(params[cand], split[cand], r_of.astype(np.int32), rows, tol=tol, maxiter=maxiter)
+        res = engine.search(params[cand], rows, split_times=split[cand], rows=r_of.astype(np.int32), band_bounds=bb, pulse_times=pt, box=box,
+                            xatol=tol, fatol=tol, maxiter=maxiter)
     llh = np.full(best.shape, -np.inf)
     llh[r_of, j_of] = np.where(np.isnan(res["llh"]), -np.inf, res["llh"])
     place = np.where((best >= 0).any(axis=1), np.argmax(llh, axis=1), -1)           # first maximum: the lowest place
@@ -622,6 +615,16 @@ def bootstrap_profile_interval(llh, split_values, x=None):
     return out
 
 
+def _split_pairs(engine, starts, splits, band_bounds, pulse_times):
+    """What split_fit and split_fit_global share: the (start, initial split) pairs ``[Q x P][n_param + 1]`` (start outermost, initial
+    split innermost; a model without an optimised parameter has the splits alone), and ``per_search(S)``: the one set of band bounds
+    and pulse times repeated for S searches (``None`` stays ``None``)."""
+    st = np.asarray(starts, dtype=float).reshape(-1, engine.n_param) if engine.n_param else np.empty((1, 0))
+    pairs = np.hstack([np.repeat(st, splits.size, axis=0), np.tile(splits, st.shape[0])[:, None]])
+    tile = lambda a, shape, S: None if a is None else np.repeat(np.asarray(a, dtype=np.int32).reshape(shape), S, axis=0)
+    return pairs, lambda S: dict(band_bounds=tile(band_bounds, (1, -1, 2), S), pulse_times=tile(pulse_times, (1, -1), S))
+
+
 def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_times=None, tol=1e-4, maxiter=1000, box=None):
     """The split time FITTED per row instead of scanned (the ``for st in A..Z`` loops of the reference's ``test.bs`` scripts and the
     arg-max over them): for every row of ``jsfs_rows`` (``[R][8]``) one search from every (start, initial split) pair - ``starts``
@@ -634,15 +637,10 @@ def split_fit(engine, jsfs_rows, starts, split_starts, band_bounds=None, pulse_t
     search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_starts, dtype=float).reshape(-1)
-    P = engine.n_param
-    st = np.asarray(starts, dtype=float).reshape(-1, P) if P else np.empty((1, 0))
-    pairs = np.hstack([np.repeat(st, splits.size, axis=0), np.tile(splits, st.shape[0])[:, None]])       # [Q x P][n_param + 1]
-    tile = lambda a, shape: None if a is None else np.asarray(a, dtype=np.int32).reshape(shape)
+    pairs, per_search = _split_pairs(engine, starts, splits, band_bounds, pulse_times)
 
     def search(r_of, p_of, x0):
-        bb, pt = tile(band_bounds, (1, -1, 2)), tile(pulse_times, (1, -1))
-        per = dict(band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
-                   pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0), tol=tol, maxiter=maxiter)
+        per = dict(per_search(r_of.size), tol=tol, maxiter=maxiter)
         return engine.nm_solve_split(x0, r_of, rows, **per) if box is None else engine.nm_solve_box(x0, r_of, rows, box, **per)
     out = _best_start_profile(search, rows.shape[0], 1, pairs)
     out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
@@ -664,18 +662,12 @@ def split_fit_global(engine, jsfs_rows, starts, split_starts, band_bounds=None, 
     ``split_fit_interval`` takes ``split`` and ``llh`` unchanged."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_starts, dtype=float).reshape(-1)
-    P = engine.n_param
-    st = np.asarray(starts, dtype=float).reshape(-1, P) if P else np.empty((1, 0))
-    pairs = np.hstack([np.repeat(st, splits.size, axis=0), np.tile(splits, st.shape[0])[:, None]])       # [Q x P][n_param + 1]
-    tile = lambda a, shape: None if a is None else np.asarray(a, dtype=np.int32).reshape(shape)
+    pairs, per_search = _split_pairs(engine, starts, splits, band_bounds, pulse_times)
     R = rows.shape[0]
 
     def search(r_of, p_of, x0):
-        bb, pt = tile(band_bounds, (1, -1, 2)), tile(pulse_times, (1, -1))
         gens = _hop_generators(seed, R, r_of.size // R)
-        per = dict(band_bounds=None if bb is None else np.repeat(bb, r_of.size, axis=0),
-                   pulse_times=None if pt is None else np.repeat(pt, r_of.size, axis=0),
-                   niter=niter, T=T, stepsize=stepsize, **hop_options)
+        per = dict(per_search(r_of.size), niter=niter, T=T, stepsize=stepsize, **hop_options)
         return engine.basinhopping_split(x0, r_of, rows, gens, **per) if box is None else engine.basinhopping_box(x0, r_of, rows, gens, box, **per)
     out = _best_start_profile(search, R, 1, pairs, _HOP_RESULTS)
     out = {k: (v[:, 0] if isinstance(v, np.ndarray) else v) for k, v in out.items()}
@@ -708,22 +700,21 @@ def split_fit_interval(split, llh, level=0.95):
 def sweep_profile(engine, models, jsfs_rows, starts, tol=1e-4, maxiter=1000):
     """``bootstrap_profile`` with a MODEL axis instead of a split axis: ``models`` is a list of ``(split, band_bounds[n_band][2])``
     (end -1: the model's split index) - the boundary profiles "when did migration start or stop" (the test.bs scripts' Solve per
-    (replicate, split) pair with a loop over a band boundary added, one Engine per boundary there) in ONE ``misti_nm_solve_bounds``
+    (replicate, split) pair with a loop over a band boundary added, one Engine per boundary there) in ONE ``misti_search``
     call: every (row, model, start) triple is a start of the batched search.  ``jsfs_rows`` is ``[R][8]``, ``starts`` ``[Q][N]``.
     Per (row, model) the best start is kept (ties: the lowest start index).  A model may carry its own pulse times as a third
-    element, ``(split, band_bounds, pulse_times[n_pulse])`` - the pulse-date profile "when did the pulse happen"; with any third
-    element the call is ``misti_nm_solve_pulses``.
+    element, ``(split, band_bounds, pulse_times[n_pulse])`` - the pulse-date profile "when did the pulse happen".
     Returns dict(x[R][M][N], llh[R][M], nit / nfev / status / start[R][M], and the search's work counters)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.array([float(m[0]) for m in models], dtype=float)
     bounds = np.array([np.asarray(m[1], dtype=np.int32).reshape(-1, 2) for m in models], dtype=np.int32).reshape(len(models), -1, 2)
+    times = None
     if any(len(m) > 2 for m in models):
         if not all(len(m) > 2 for m in models):
             raise ValueError("sweep_profile: either every model carries pulse times or none does")
         times = np.array([np.asarray(m[2], dtype=np.int32).reshape(-1) for m in models], dtype=np.int32).reshape(len(models), -1)
-        search = lambda r_of, m_of, st: engine.nm_solve_pulses(st, splits[m_of], r_of, rows, bounds[m_of], times[m_of], tol=tol, maxiter=maxiter)
-    else:
-        search = lambda r_of, m_of, st: engine.nm_solve_bounds(st, splits[m_of], r_of, rows, bounds[m_of], tol=tol, maxiter=maxiter)
+    search = lambda r_of, m_of, st: engine.search(st, rows, split_times=splits[m_of], rows=r_of, band_bounds=bounds[m_of],
+                                                  pulse_times=None if times is None else times[m_of], xatol=tol, fatol=tol, maxiter=maxiter)
     return _best_start_profile(search, rows.shape[0], splits.size, starts)
 
 
