@@ -112,6 +112,7 @@ struct misti_ctx {
     hipEvent_t order_ev = nullptr;      // orders a replaced stream before its successor (misti_set_stream)
     hipEvent_t last_ev = nullptr;       // recorded behind every batch: lets OTHER contexts see whether this one has work in flight
     bool last_ev_set = false;
+    int64_t batches_begun = 0, batches_recorded = 0;   // batches that reached their first stream operation / that recorded last_ev behind them (misti_batch_event_)
     unsigned hints = 0;                 // misti_set_hints: what the caller knows about its batches (MISTI_HINT_INTEGER_SPLITS)
     hipStream_t side_stream = nullptr;  // phase 1 of a two-phase batch (run_dev): what follows the chains a packed launch completed, beside its resume launch
     hipEvent_t packed_ev = nullptr, side_ev = nullptr;
@@ -306,6 +307,7 @@ int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const doub
     HIP_TRY(c->ws_order.reserve(nc * sizeof(int32_t)));
     if (ntr) HIP_TRY(c->ws_trunk.reserve(ntr * numT * misti::TRUNK_REC * sizeof(double)));
     if (n_rep > 0) HIP_TRY(c->consts.reserve((size_t)n_rep * sizeof(double)));
+    c->batches_begun += 1;                          // from here on the batch puts work into the stream
     misti::ChainBufs cb;
     {
         double* d = c->ws_chain_f64.as<double>();
@@ -403,7 +405,8 @@ int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const doub
         follow = misti::trunk_follows(cpw, (int64_t)ntr, c->tune);
     };
     // a batch is four launches (+1 for the default fit, +1 with more than LLK_INLINE_MAX replicates): setup | chains |
-    // trunks + tails | candidates (+ replicate epilogue).  Few launches matter when many batches are in flight.
+    // trunks + tails | candidates (+ replicate epilogue) - three where the trunk follows its chain inside the chain launch
+    // (the headline grid: setup | chains with their trunks and tails | candidates).  Few launches matter when many batches are in flight.
     int32_t* d_order = c->ws_order.as<int32_t>();
     double* d_consts = n_rep > 0 ? c->consts.as<double>() : nullptr;
     const bool llk_inline = n_rep > 0 && n_rep <= misti::LLK_INLINE_MAX;
@@ -474,10 +477,11 @@ int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const doub
         if (int r = record_end(c, 2, a, b)) return r;
         if (c->timing) c->launches[2] += 1;
     }
-    if (c->last_ev) {                              // behind the batch: other contexts read it (other_contexts_busy)
+    if (c->last_ev) {                              // behind the batch: other contexts read it (other_contexts_busy), and so does the context's lane (misti_lanes.cpp)
         std::lock_guard<std::mutex> lock(g_ctx_mu);
         HIP_TRY(hipEventRecord(c->last_ev, c->stream));
         c->last_ev_set = true;
+        c->batches_recorded += 1;
     }
     return 0;
 }
@@ -693,6 +697,16 @@ int misti_create_prio_(const misti_model_t* model, int device, int priority, mis
 }
 
 int misti_create(const misti_model_t* model, int device, misti_ctx** out) { return misti_create_prio_(model, device, 0, out); }
+
+// internal (misti_lanes.cpp): the event the context records behind every batch (NULL: it has none), how many batches have recorded it and
+// how many have put work into the stream.  A lane reads the counters around a batch: the first moved - the context's record, on the
+// lane's stream, stands behind that batch and the lane needs none of its own; only the second moved - the batch failed with work in flight.
+void* misti_batch_event_(misti_ctx* c, int64_t* recorded, int64_t* begun) {
+    if (!c) return nullptr;
+    if (recorded) *recorded = c->batches_recorded;
+    if (begun) *begun = c->batches_begun;
+    return static_cast<void*>(c->last_ev);
+}
 
 int misti_destroy(misti_ctx* c) {
     if (!c) return 0;

@@ -21,6 +21,9 @@ extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp
 // this file against stand-ins (tests/multi_host) has not, and is then a pool on one level made by misti_create, as before the plan.
 extern "C" int misti_create_prio_(const misti_model_t* model, int device, int priority, misti_ctx** out) __attribute__((weak));
 extern "C" hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) __attribute__((weak));
+// misti_api.cpp: the event a context records behind every batch of its own, with its counters (weak for the same reason: without it a
+// lane records its own event behind every batch, as before)
+extern "C" void* misti_batch_event_(misti_ctx* c, int64_t* recorded, int64_t* begun) __attribute__((weak));
 
 namespace {
 
@@ -113,8 +116,9 @@ struct misti_lanes {
     std::vector<misti_ctx*> ctx;
     std::vector<int> level;               // each lane's priority level (lane_plan)
     std::vector<hipStream_t> stream;      // each context's own stream (misti_get_stream at creation)
-    std::vector<hipEvent_t> done;         // recorded behind every batch of the lane: "nothing in flight" is a query of it
-    std::vector<char> used;               // the lane has had a batch (its event has been recorded)
+    std::vector<hipEvent_t> done;         // the lane's own event: recorded behind a batch only where the context recorded none behind it
+    std::vector<hipEvent_t> last;         // the event behind the lane's last batch - the context's or done[i]; NULL: no batch yet.
+                                          // "Nothing in flight" is a query of it
     int next = 0;                         // round-robin position of MISTI_LANE_ANY
 };
 
@@ -135,8 +139,8 @@ int guarded(const char* where, F&& fn) noexcept {
 
 // 1 busy, 0 idle, < 0 error
 int lane_busy(misti_lanes* L, int i) {
-    if (!L->used[(size_t)i]) return 0;
-    const hipError_t e = hipEventQuery(L->done[(size_t)i]);
+    if (!L->last[(size_t)i]) return 0;
+    const hipError_t e = hipEventQuery(L->last[(size_t)i]);
     if (e == hipSuccess) return 0;
     (void)hipGetLastError();
     if (e == hipErrorNotReady) return 1;
@@ -183,7 +187,7 @@ int misti_create_lanes(const misti_model_t* model, int device, int n_lanes, mist
             const hipError_t he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
             if (he != hipSuccess) return faill(MISTI_E_HIP, "hipEventCreateWithFlags: %s", hipGetErrorString(he));
             L->done.push_back(e);
-            L->used.push_back(0);
+            L->last.push_back(nullptr);
         }
         return 0;
     });
@@ -255,10 +259,25 @@ int misti_lanes_eval_batch_dev(misti_lanes* L, int lane, int64_t n_cand, const d
         }
         L->next = (lane + 1) % n;
     }
-    if (int r = misti_eval_batch_dev(L->ctx[(size_t)lane], n_cand, d_split, d_params, d_bounds, n_rep, d_jsfs, d_llk, d_jafs, d_lc, d_pr, d_status)) return r;
-    const hipError_t e = hipEventRecord(L->done[(size_t)lane], L->stream[(size_t)lane]);
-    if (e != hipSuccess) return faill(MISTI_E_HIP, "hipEventRecord on lane %d: %s", lane, hipGetErrorString(e));
-    L->used[(size_t)lane] = 1;
+    // One event per batch: the context records its own behind every batch, on this lane's stream (misti_api.cpp: last_ev).  A second
+    // record straight behind it would be one more packet for the queue to hand over, and streams that share a hardware queue are
+    // served packet by packet.  So the lane records its own event only where the context's does not stand behind the batch: a context
+    // without one, a batch that put nothing into the stream (n_cand == 0), and a batch that failed with work already in flight - which
+    // stays waitable.  A batch that failed before its first stream operation leaves the lane as it was.
+    misti_ctx* const c = L->ctx[(size_t)lane];
+    int64_t rec0 = 0, rec1 = 0, beg0 = 0, beg1 = 0;
+    void* const ctx_ev = misti_batch_event_ ? misti_batch_event_(c, &rec0, &beg0) : nullptr;
+    const int r = misti_eval_batch_dev(c, n_cand, d_split, d_params, d_bounds, n_rep, d_jsfs, d_llk, d_jafs, d_lc, d_pr, d_status);
+    if (ctx_ev) (void)misti_batch_event_(c, &rec1, &beg1);
+    if (ctx_ev && rec1 != rec0) {
+        L->last[(size_t)lane] = static_cast<hipEvent_t>(ctx_ev);
+    } else if (r == 0 || beg1 != beg0) {
+        const hipError_t e = hipEventRecord(L->done[(size_t)lane], L->stream[(size_t)lane]);
+        if (e == hipSuccess) L->last[(size_t)lane] = L->done[(size_t)lane];
+        else if (r == 0) return faill(MISTI_E_HIP, "hipEventRecord on lane %d: %s", lane, hipGetErrorString(e));
+        else (void)hipGetLastError();                    // the batch's own error is the one to report
+    }
+    if (r != 0) return r;
     if (lane_used) *lane_used = lane;
     return 0;
 }
@@ -274,8 +293,8 @@ int misti_lanes_eval_batch_dev(misti_lanes* L, int lane, int64_t n_cand, const d
 // that price: the bench gains nothing from waiting here first (2.73 against 2.76 - 2.81 ms, run-to-run spread), a caller that
 // waits lane by lane does.
 static int wait_done(misti_lanes* L, size_t i) {
-    if (!L->used[i]) return 0;
-    const hipError_t e = hipEventSynchronize(L->done[i]);
+    if (!L->last[i]) return 0;
+    const hipError_t e = hipEventSynchronize(L->last[i]);
     if (e != hipSuccess) return faill(MISTI_E_HIP, "hipEventSynchronize on lane %d: %s", (int)i, hipGetErrorString(e));
     return 0;
 }

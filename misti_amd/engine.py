@@ -763,7 +763,7 @@ class Lanes:
     def bind_dev(self, lane, n_cand, d_split, d_params, n_rep, d_jsfs, d_llk, d_jafs=0, d_lc=0, d_pr=0, d_status=0, d_bounds=0):
         """``evaluate_dev`` with its arguments converted ONCE: returns a function of no arguments that issues this batch on lane ``lane``
         (an explicit lane).  A sweep that re-issues a batch on fixed device buffers - the bench's steps - saves the ~2 us of ctypes argument
-        conversion per call (12.6 -> 10.8 us per step on the headline grid; the rest is the library's three launches and two event records)."""
+        conversion per call (12.6 -> 10.8 us per step on the headline grid; the rest is the library's three launches and its event record)."""
         v = lambda p: C.c_void_p(int(p)) if p else None
         fn, check = self._lib.misti_lanes_eval_batch_dev, _lib.check
         args = (self._h, C.c_int(int(lane)), C.c_int64(int(n_cand)), v(d_split), v(d_params), v(d_bounds), C.c_int64(int(n_rep)), v(d_jsfs),
