@@ -597,6 +597,91 @@ int misti_nm_last_stats(misti_ctx* ctx, int64_t stats[2]);
  * from the values it would have asked for - one chain latency per iteration instead of three; nfev stays SciPy's count. */
 int misti_nm_last_spec_iterations(misti_ctx* ctx, int64_t* n);
 
+/* ---- differential evolution per search ------------------------------------------------------ */
+/* A population search: n_start searches at once, every generation of every live search ONE engine batch of pop points per search.
+ * No inner minimisations and no tails: where basin hopping's hops wait for the slowest Nelder-Mead run of every hop, a generation
+ * here is one dense rows-path batch (each point against its own row, split, band bounds and pulse times).  The reference has no
+ * counterpart, and there is no SciPy bit-parity target either: scipy.optimize.differential_evolution redraws a coordinate that
+ * leaves the bounds, so the number of its draws depends on the data.  The rule is THE PROJECT'S OWN, NOT SCIPY'S - modelled on
+ * SciPy's best1bin with updating='deferred' - stated once in NumPy (optimize.differential_evolution_rule); the device result is
+ * that, bit for bit, on the engine's own objective.
+ *
+ * Search s has N coordinates - n_param, or n_param + 1 with MISTI_SPLIT_FITTED (the split last, in grid-index units; n_param == 0
+ * allowed there) -, a row rows[s], optional band bounds and pulse times, a FINITE box [lo, hi] per coordinate (lo == hi holds the
+ * coordinate fixed), pop = P members and a stream id ids[s] (NULL: s).  The rule:
+ *   - everything random is numpy.random.Philox(key=[seed, ids[s]]), the block bootstrap's counter convention.  Member i of
+ *     generation g (g = 0: the initial population) owns the MISTI_DE_BLOCKS blocks from block (g P + i) MISTI_DE_BLOCKS on, i.e.
+ *     4 MISTI_DE_BLOCKS words w[0 ...]: w[0] gives r1, w[1] r2, w[2] jrand, w[3] F's uniform, w[4 + k] the uniform of coordinate
+ *     k.  A uniform is (raw >> 11) 2^-53; an index out of n is the high 64 bits of raw x n - no rejection;
+ *   - generation 0: member 0 is starts[s] clipped to the box; member i > 0 has clip(lo + u_k (hi - lo)) per coordinate, every
+ *     operation rounded on its own.  All P points are evaluated;
+ *   - generation g >= 1, member i: best = the member with the lowest objective after generation g - 1 (ties: the lowest index);
+ *     r1 is the w[0]-th of the P - 1 members other than i, r2 the w[1]-th of the P - 2 members other than i and r1 (in member
+ *     order), jrand one of the N coordinates, F = F_lo + u (F_hi - F_lo) (dither; F_lo == F_hi: a constant);
+ *   - the mutant v = best + F (x_r1 - x_r2), three separately rounded operations per coordinate, no fused multiply-add.  The trial
+ *     coordinate t_k is v_k where k == jrand or u_k < CR, x_i,k otherwise; a v_k outside the box becomes the midpoint between
+ *     x_i,k and the bound it crossed, x_i,k + 0.5 (bound - x_i,k), without another draw; a fixed coordinate stays at lo;
+ *   - selection is deferred: all trials of a generation are evaluated as one batch against the population of generation g - 1,
+ *     then member i is replaced iff f(t) <= f(x_i), f = -llk and +inf where the engine has no value (so inf <= inf replaces);
+ *   - after every generation, the initial one included, a search stops with status 0 when every member has a value and
+ *     q / P <= (atol + tol |m|)^2 with m = (f_0 + f_1 + ...) / P and q = (f_0 - m)^2 + (f_1 - m)^2 + ... - sums in member order,
+ *     every operation rounded on its own: std(f) <= atol + tol |mean(f)| without a square root; with status 2 after maxiter
+ *     generations.  A stopped search submits no further points; nit counts its generations after the initial one, nfev is
+ *     P (nit + 1).  A search none of whose points ever has a value returns llh = -inf (and status 2).
+ * A search's result is a function of its own arguments alone: not of the other searches in the call, their number or order, the
+ * device or the launch geometry.  Polishing is not part of the rule: a caller follows with misti_nm_solve_box from x.
+ * Populations, values, decisions and counters stay in HBM; the host runs at most two generations ahead of the device and reads
+ * only the count of live searches.  Host buffers; synchronous.
+ *
+ * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this
+ * library's; a split mode that is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED; a negative n_start; a NULL pointer among
+ * starts / rows / jsfs / box_lo / box_hi / x / llh (and split_times with MISTI_SPLIT_PER_START); n_rep < 1; pop < 4 (MISTI_E_LIMIT
+ * for pop > MISTI_DE_MAX_POP); maxiter < 1; tol or atol negative or not finite; F_lo or F_hi not finite or negative, or F_lo >
+ * F_hi; CR outside [0, 1]; n_box neither 1 nor n_start; a row out of range; a non-finite split time; then a NULL context; a model
+ * without a coordinate to search; MISTI_E_LIMIT for N > MISTI_MAX_PARAMS, n_start x pop > INT32_MAX / 8 / (N + 1) or n_rep >
+ * INT32_MAX; a non-finite start coordinate; the box: a bound that is infinite or NaN, lo > hi, or hi - lo not finite (the message
+ * names the box and the coordinate).  n_start == 0 returns 0 once the arguments are accepted, and writes nothing.  Points the
+ * engine refuses are no errors: they score +inf, as in the searches above. */
+#define MISTI_DE_MAX_POP 256
+#define MISTI_DE_BLOCKS  5    /* Philox blocks per member and generation: 4 + MISTI_MAX_PARAMS words fit */
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_de_t) */
+    int32_t split;                   /* MISTI_SPLIT_PER_START or MISTI_SPLIT_FITTED */
+    const double* split_times;       /* MISTI_SPLIT_PER_START: [n_start], finite */
+    int64_t n_start;
+    const double* starts;            /* [n_start][N]: member 0 of every search (clipped to its box); all finite */
+    const int32_t* rows;             /* [n_start], 0 <= rows[s] < n_rep */
+    int64_t n_rep;
+    const double* jsfs;              /* [n_rep][8] */
+    const int32_t* band_bounds;      /* [n_start][n_band][2] or NULL; ignored when the model has no band */
+    const int32_t* pulse_times;      /* [n_start][n_pulse] or NULL; ignored when the model has no pulse */
+    int64_t n_box;                   /* 1: one box for every search; n_start: a box per search */
+    const double* box_lo;            /* [n_box][N] finite */
+    const double* box_hi;            /* [n_box][N] finite, >= box_lo */
+    int32_t pop;                     /* members per search, 4 ... MISTI_DE_MAX_POP */
+    int32_t maxiter;                 /* generations after the initial population */
+    double tol, atol;
+    double F_lo, F_hi;               /* dither range of the differential weight */
+    double CR;                       /* crossover probability */
+    uint64_t seed;
+    const uint64_t* ids;             /* [n_start] stream ids, or NULL: 0, 1, ... */
+    double* x;                       /* [n_start][N] the best member; inside the box; a fitted split last */
+    double* llh;                     /* [n_start] its log-likelihood; -inf: no point of the search ever had a value */
+    int32_t* nit;                    /* [n_start] or NULL: generations */
+    int32_t* nfev;                   /* [n_start] or NULL: points evaluated */
+    int32_t* status;                 /* [n_start] or NULL: 0 converged, 2 generation budget */
+    double* population;              /* [n_start][pop][N] or NULL: the final population */
+    double* population_llh;          /* [n_start][pop] or NULL: its log-likelihoods (-inf: no value) */
+    int64_t* n_points;               /* [1] or NULL: points of searches the call handed the engine, empty batch slots not counted */
+} misti_de_t;
+int misti_de_search(misti_ctx* ctx, const misti_de_t* search);
+/* What member `member` of generation `generation` of the stream (seed, id) draws in a search of pop members and n coordinates, on
+ * the host through the very functions the kernels call: r1, r2, jrand, F's uniform and the n per-coordinate uniforms (generation 0
+ * uses only the latter).  No context, no device.  MISTI_E_ARG for a negative generation, pop < 4, a member outside 0 ... pop - 1,
+ * n < 1 or a NULL pointer; MISTI_E_LIMIT for pop > MISTI_DE_MAX_POP or n > MISTI_MAX_PARAMS. */
+int misti_de_draws(uint64_t seed, uint64_t id, int64_t generation, int32_t member, int32_t pop, int32_t n,
+                   int32_t* r1, int32_t* r2, int32_t* jrand, double* u_F, double* u /* HOST [n] */);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

@@ -68,6 +68,20 @@ class Search(C.Structure):
                 ("hops", C.POINTER(Hops))]
 
 
+DE_MAX_POP, DE_BLOCKS = 256, 5
+
+
+class DeSearch(C.Structure):
+    """``misti_de_t``: differential evolution per search; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("split", C.c_int32), ("split_times", C.c_void_p), ("n_start", C.c_int64), ("starts", C.c_void_p),
+                ("rows", C.c_void_p), ("n_rep", C.c_int64), ("jsfs", C.c_void_p), ("band_bounds", C.c_void_p), ("pulse_times", C.c_void_p),
+                ("n_box", C.c_int64), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p), ("pop", C.c_int32), ("maxiter", C.c_int32),
+                ("tol", C.c_double), ("atol", C.c_double), ("F_lo", C.c_double), ("F_hi", C.c_double), ("CR", C.c_double),
+                ("seed", C.c_uint64), ("ids", C.c_void_p), ("x", C.c_void_p), ("llh", C.c_void_p), ("nit", C.c_void_p),
+                ("nfev", C.c_void_p), ("status", C.c_void_p), ("population", C.c_void_p), ("population_llh", C.c_void_p),
+                ("n_points", C.c_void_p)]
+
+
 class MistiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmisti_hip error %d: %s" % (code, msg))
@@ -96,6 +110,9 @@ SYMBOLS = {
     "misti_eval_batch_pulses_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_search": (C.c_int, [C.c_void_p, C.POINTER(Search)]),
+    "misti_de_search": (C.c_int, [C.c_void_p, C.POINTER(DeSearch)]),
+    "misti_de_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_nm_solve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_nm_solve_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,

@@ -64,6 +64,19 @@ and the GNU-parallel recipe of ``README.md:110-115``):
     --hop-step S              with --hops (refused without): the initial step size of the random displacement (default 0.5; the split
                               in grid-index units)
     --hop-seed K              with --hops (refused without): search j of a row draws from numpy.random.default_rng([K, j]) (default 0)
+    --de POP GENS             with --fit-st or --grid-solve (where --hops is): every search becomes a DIFFERENTIAL EVOLUTION of POP members
+                              (4 ... 256) over at most GENS generations inside the box - one misti_de_search call over all rows, every
+                              generation ONE dense engine batch, no inner minimisations.  The rule is this project's own, not SciPy's
+                              (best1bin, dither, deferred selection; include/misti_hip.h states it).  Needs a finite --box for EVERY
+                              searched coordinate (the split included under --fit-st) and refuses otherwise; member 0 of every
+                              population is the -mi/-pu initial values (--grid-mi is not offered; under --fit-st the first split of
+                              --grid-st).  The lines are those of the mode without it, and one line states members, generations, F,
+                              CR and seed.  Not offered with --hops, --se, --sweep, --sweep-pu, --gpus N > 1 or --devices
+    --de-seed K               with --de (refused without): every random number is numpy.random.Philox(key=[K, j]), j the search's index
+                              within its row (default 0)
+    --de-F LO HI              with --de: the dither range of the differential weight (default 0.5 1)
+    --de-CR C                 with --de: the crossover probability (default 0.7)
+    --de-polish               with --de: one boxed Nelder-Mead call (misti_nm_solve_box, -tol) from the DE results; a search keeps the better
     --box K LO HI             with --grid-solve, --fit-st or --polish, with or without --hops; repeatable: every search runs inside a box -
                               SciPy's Nelder-Mead with bounds= (misti_nm_solve_box / misti_basinhopping_box): LO <= parameter K <= HI, K the
                               index of an optimised parameter as --grid-mi K names it, or `st` for the fitted split of --fit-st.  inf and
@@ -193,6 +206,13 @@ def build_parser():
                    help="with --fit-st / --grid-solve: basin hopping with N hops (T = 0.5, SciPy's minimiser defaults; -tol does not apply) in place of the local search")
     p.add_argument("--hop-step", type=float, default=None, metavar="S", help="with --hops: initial step size of the random displacement (default 0.5)")
     p.add_argument("--hop-seed", type=int, default=None, metavar="K", help="with --hops: seed of the searches' generators (default 0)")
+    p.add_argument("--de", nargs=2, type=int, default=None, metavar=("POP", "GENS"),
+                   help="with --fit-st / --grid-solve: differential evolution of POP members over at most GENS generations inside the --box of "
+                        "every searched coordinate, in place of the local search (the project's own rule, not SciPy's)")
+    p.add_argument("--de-seed", type=int, default=None, metavar="K", help="with --de: seed of the searches' Philox streams (default 0)")
+    p.add_argument("--de-F", nargs=2, type=float, default=None, metavar=("LO", "HI"), dest="de_F", help="with --de: dither range of the differential weight (default 0.5 1)")
+    p.add_argument("--de-CR", type=float, default=None, metavar="C", dest="de_CR", help="with --de: crossover probability (default 0.7)")
+    p.add_argument("--de-polish", action="store_true", help="with --de: one boxed Nelder-Mead call from the DE results; a search keeps the better result")
     p.add_argument("--box", nargs=3, action="append", default=[], metavar=("K", "LO", "HI"),
                    help="with --grid-solve / --fit-st / --polish: keep optimised parameter K (or `st`: the fitted split of --fit-st) within [LO, HI] "
                         "in every search (SciPy's bounds=; inf / -inf accepted); repeatable")
@@ -464,6 +484,61 @@ def hops_error(a):
     if a.hop_seed is not None and a.hop_seed < 0:
         return "--hop-seed must not be negative (got %d)" % a.hop_seed
     return None
+
+
+def de_error(a):
+    """Why ``--de`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.de is None:
+        if a.de_seed is not None or a.de_F is not None or a.de_CR is not None or a.de_polish:
+            return "--de-seed / --de-F / --de-CR / --de-polish set the search of --de POP GENS: give --de POP GENS"
+        return None
+    pop, gens = a.de
+    if not 4 <= pop <= 256:
+        return "--de POP GENS: POP must be 4 ... 256 (got %d)" % pop
+    if gens < 1:
+        return "--de POP GENS: GENS must be at least 1 (got %d)" % gens
+    if a.hops is not None:
+        return "--de and --hops are two global searches: give one of them"
+    if a.se:
+        return "--se follows the local search of --grid-solve or of the single model: --de is not offered with it"
+    if a.sweep or a.sweep_pu:
+        return "--de searches ONE model globally: --sweep / --sweep-pu are not offered with it"
+    if not (a.fit_st or a.grid_solve):
+        return "--de makes the searches of --fit-st or --grid-solve global: give one of them"
+    if a.gpus > 1 or a.devices:
+        return "--de runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    if a.grid_mi:
+        return "--de draws its population inside the box: --grid-mi starts are not offered with it (member 0 is the -mi/-pu initial values)"
+    if a.de_seed is not None and not 0 <= a.de_seed < 2 ** 64:
+        return "--de-seed must be a uint64 (got %d)" % a.de_seed
+    if a.de_F is not None and not (0 <= a.de_F[0] <= a.de_F[1] and np.isfinite(a.de_F[1])):
+        return "--de-F LO HI: a finite range 0 <= LO <= HI (got %g %g)" % tuple(a.de_F)
+    if a.de_CR is not None and not 0 <= a.de_CR <= 1:
+        return "--de-CR must lie in [0, 1] (got %g)" % a.de_CR
+    k = sum(1 for el in a.mi if int(el[4])) + sum(1 for el in a.pu if int(el[3]))
+    boxed = {}
+    for name, lo, hi in a.box:
+        try:
+            boxed[name] = (float(lo), float(hi))
+        except ValueError:
+            return None                                   # box_error names it
+    for name in [str(i) for i in range(k)] + (["st"] if a.fit_st else []):
+        if name not in boxed:
+            return "--de searches inside a box: coordinate %s has no --box %s LO HI" % (name, name)
+        if not all(np.isfinite(v) for v in boxed[name]):
+            return "--de needs a finite box: --box %s has an infinite bound" % name
+    return None
+
+
+def _de_options(a):
+    """The options of --de, or their defaults: F in [0.5, 1], CR 0.7, seed 0."""
+    return dict(pop=a.de[0], maxiter=a.de[1], F=tuple(a.de_F) if a.de_F is not None else (0.5, 1.0), CR=0.7 if a.de_CR is None else a.de_CR,
+                seed=0 if a.de_seed is None else a.de_seed, polish=a.de_polish)
+
+
+def _de_text(o):
+    return "differential evolution with %d members, at most %d generations, F in [%g, %g], CR %g, seed %d%s" % (
+        o["pop"], o["maxiter"], o["F"][0], o["F"][1], o["CR"], o["seed"], ", polished" if o["polish"] else "")
 
 
 def _hop_step_seed(a):
@@ -825,7 +900,7 @@ def grid_profile(a, inp, rows):
 def grid_solve(a, inp, rows):
     """The bootstrap profiles of the reference's test.bs scripts (``for bs in 0..B; for st in A..Z: MiSTI.py ... ${st} -bs ${bs}
     -mi ...``, one Solve per pair) as ONE batched search: every (row, split, start) triple is a start of misti_nm_solve_rows."""
-    from .optimize import bootstrap_profile, bootstrap_profile_global, bootstrap_profile_interval
+    from .optimize import bootstrap_profile, bootstrap_profile_de, bootstrap_profile_global, bootstrap_profile_interval
     splits, bands, pulses, k, axes = grid_model(a)
     starts = np.stack([m.ravel() for m in np.meshgrid(*axes, indexing="ij")], axis=1)
     data = np.array(rows if a.all_bs else [rows[a.bsMode] if a.bsMode >= 0 else np.sum(rows, axis=0)], dtype=float)
@@ -834,7 +909,9 @@ def grid_solve(a, inp, rows):
     hop_step, hop_seed = _hop_step_seed(a)
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
-        if a.hops:
+        if a.de:
+            prof = bootstrap_profile_de(e, splits, data, starts[0], _box(a, k), polish_tol=a.tol, **_de_options(a))
+        elif a.hops:
             prof = bootstrap_profile_global(e, splits, data, starts, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
             prof = bootstrap_profile(e, splits, data, starts, tol=a.tol, maxiter=1000, box=_box(a, k))
@@ -873,6 +950,11 @@ def grid_solve(a, inp, rows):
     n = prof["llh"].size
     if a.box:
         print("grid-solve:", _box_text(a))
+    if a.de:
+        print("grid-solve:", _de_text(_de_options(a)))
+        print("grid-solve: %d pairs in one population search, %.3f s, %d points; %d pairs ended on the generation cap, %d without a value"
+              % (n, dt, prof["n_points"], int((prof["status"] == 2).sum()), int((~np.isfinite(prof["llh"])).sum())))
+        return 0
     if a.hops:
         print("grid-solve: basin hopping with %d hops, step %g, seed %d" % (a.hops, hop_step, hop_seed))
         print("grid-solve: %d pairs x %d starts in one global search, %.3f s; %d pairs with a failed minimisation, %d without a value"
@@ -886,7 +968,7 @@ def grid_solve(a, inp, rows):
 def fit_st(a, inp, rows):
     """--fit-st: the split time as a coordinate - per JSFS row one search over (optimised parameters, split) from every (start,
     initial split) pair, all in ONE misti_nm_solve_split call; the best search per row is printed."""
-    from .optimize import split_fit, split_fit_global, split_fit_interval
+    from .optimize import split_fit, split_fit_de, split_fit_global, split_fit_interval
     splits, bands, pulses, k, axes = grid_model(a)
     starts = np.stack([m.ravel() for m in np.meshgrid(*axes, indexing="ij")], axis=1) if k else np.empty((1, 0))
     data, ids = _data_rows(a, rows)
@@ -894,7 +976,9 @@ def fit_st(a, inp, rows):
     hop_step, hop_seed = _hop_step_seed(a)
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
-        if a.hops:
+        if a.de:
+            fit = split_fit_de(e, data, np.append(starts[0], splits[0]), _box(a, k), polish_tol=a.tol, **_de_options(a))
+        elif a.hops:
             fit = split_fit_global(e, data, starts, splits, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
             fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000, box=_box(a, k))
@@ -920,6 +1004,11 @@ def fit_st(a, inp, rows):
                   "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
     if a.box:
         print("fit-st:", _box_text(a))
+    if a.de:
+        print("fit-st:", _de_text(_de_options(a)))
+        print("fit-st: %d rows in one population search, %.3f s, %d points; %d rows ended on the generation cap, %d without a value"
+              % (data.shape[0], dt, fit["n_points"], int((fit["status"] == 2).sum()), int((~np.isfinite(fit["llh"])).sum())))
+        return 0
     if a.hops:
         print("fit-st: basin hopping with %d hops, step %g, seed %d" % (a.hops, hop_step, hop_seed))
         print("fit-st: %d rows x %d (start, initial split) pairs in one global search, %.3f s; %d rows with a failed minimisation, %d without a value"
@@ -1053,7 +1142,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
+    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or de_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2

@@ -1215,6 +1215,16 @@ int nm_prepare(misti_ctx* c, int64_t n_start, int N, NmWork& w, Extra&& extra) {
     return 0;
 }
 
+// One batch of the rows path through the engine (batched Nelder-Mead, differential evolution): the first n slots of `b` evaluated
+// without replicates into rjafs / rstatus, with each slot's own band bounds and pulse times where the batch carries them, then every
+// point scored against its own row of the table.
+int eval_rows(misti_ctx* c, const NmBatch& b, int64_t n, const double* params, unsigned hints, double* rjafs, int32_t* rstatus,
+              const double* table, const double* consts, double* llk) {
+    if (int r = run_dev(c, n, b.split, params, b.bnd, 0, nullptr, nullptr, rjafs, nullptr, nullptr, rstatus, hints, b.put)) return r;
+    HIP_TRY(misti::launch_llk_rows(n, rjafs, rstatus, b.row, table, consts, llk, c->unfolded, c->stream));
+    return 0;
+}
+
 // One minimisation of every start from w.d_starts (device); leaves best vertices in w.d_starts, their log-likelihood in w.d_llh,
 // SciPy's counters in st.nit / st.nfev and the termination status in st.shrunk (0 converged, 1 evaluation budget, 2 iteration
 // budget).  Asynchronous except for the 4-byte live counts; results are complete when the stream is.
@@ -1246,9 +1256,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
         const NmBatch& b = st.b[which];
         const double* params = st.fit_split ? b.par : b.pts;
         if (!rows) return run_dev(c, n, b.split, params, nullptr, 1, w.d_row, w.llk[which], nullptr, nullptr, nullptr, nullptr, nm_hints);
-        if (int r = run_dev(c, n, b.split, params, b.bnd, 0, nullptr, nullptr, w.rjafs, nullptr, nullptr, w.rstatus, nm_hints, b.put)) return r;
-        HIP_TRY(launch_llk_rows(n, w.rjafs, w.rstatus, b.row, w.table, w.consts, w.llk[which], c->unfolded, sm));
-        return 0;
+        return eval_rows(c, b, n, params, nm_hints, w.rjafs, w.rstatus, w.table, w.consts, w.llk[which]);
     };
     int32_t* cnt = w.cnt;
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
@@ -1520,9 +1528,188 @@ int no_box(int64_t n_box, int64_t n_start) {
     return 0;
 }
 
+// ---- differential evolution per search (misti_de.hip) ----------------------------------------------------------------------------
+// The arguments of misti_de_search, before the first HIP call, in the header's order: what does not depend on the context, the
+// context, what needs the model.  Leaves the number of coordinates in N and whether every split time is an integer in `whole`.
+int de_check(const misti_ctx* c, const misti_de_t& q, int& N, bool& whole) {
+    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
+    if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
+    if (!q.starts || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.x || !q.llh || (per_start && !q.split_times))
+        return fail(MISTI_E_ARG, "starts / rows / jsfs / box_lo / box_hi / x / llh%s is NULL", per_start ? " / split_times" : "");
+    if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
+    if (q.pop < 4) return fail(MISTI_E_ARG, "pop must be >= 4 (got %d)", (int)q.pop);
+    if (q.pop > MISTI_DE_MAX_POP) return fail(MISTI_E_LIMIT, "pop = %d exceeds MISTI_DE_MAX_POP = %d", (int)q.pop, MISTI_DE_MAX_POP);
+    if (q.maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
+    if (!(q.tol >= 0.0) || !(q.atol >= 0.0) || !std::isfinite(q.tol) || !std::isfinite(q.atol)) return fail(MISTI_E_ARG, "tol and atol must be finite and not negative");
+    if (!std::isfinite(q.F_lo) || !std::isfinite(q.F_hi) || q.F_lo < 0.0 || q.F_lo > q.F_hi)
+        return fail(MISTI_E_ARG, "F must be a finite range 0 <= F_lo <= F_hi (got %g, %g)", q.F_lo, q.F_hi);
+    if (!(q.CR >= 0.0 && q.CR <= 1.0)) return fail(MISTI_E_ARG, "CR must lie in [0, 1] (got %g)", q.CR);
+    if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld searches)", (long long)q.n_box, (long long)q.n_start);
+    whole = per_start;
+    for (int64_t s = 0; s < q.n_start; ++s) {
+        if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
+        if (!per_start) continue;
+        if (!std::isfinite(q.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+        if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
+    }
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    N = c->dm.n_param + (fit_split ? 1 : 0);
+    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
+    if (q.n_start > INT32_MAX / 8 / (N + 1) / q.pop) return fail(MISTI_E_LIMIT, "too many searches x members for one call");
+    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
+    for (int64_t s = 0; s < q.n_start; ++s)
+        for (int k = 0; k < N; ++k)
+            if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
+    for (int64_t b = 0; b < q.n_box; ++b)
+        for (int k = 0; k < N; ++k) {
+            const double lo = q.box_lo[b * N + k], hi = q.box_hi[b * N + k];
+            if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is not finite (a population search needs a finite box)", (long long)b, k);
+            if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
+            if (!std::isfinite(hi - lo)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: hi - lo is not finite", (long long)b, k);
+        }
+    return 0;
+}
+
+// A checked call with n_start >= 1.  One batch record of n_start x pop slots serves the initial population and every generation;
+// the state lies in the search buffers of the context (the batched Nelder-Mead's two allocations).
+int de_run(misti_ctx* c, const misti_de_t& q, int N, bool whole) {
+    using namespace misti;
+    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = (size_t)q.n_start, P = (size_t)q.pop, M = S * P, R = (size_t)q.n_rep;
+    const size_t NB2 = q.band_bounds ? 2 * (size_t)c->dm.n_band : 0, NP = q.pulse_times ? (size_t)c->dm.n_pulse : 0;
+    const size_t NQ = fit_split ? (size_t)N - 1 : 0, NX = (size_t)q.n_box * (size_t)N;
+    DeState st{};
+    st.S = q.n_start; st.N = N; st.P = q.pop; st.maxiter = q.maxiter;
+    st.tol = q.tol; st.atol = q.atol; st.F_lo = q.F_lo; st.F_hi = q.F_hi; st.CR = q.CR; st.seed = q.seed;
+    st.fit_split = fit_split ? 1 : 0; st.nb2 = (int)NB2; st.np = (int)NP; st.box_per_start = q.n_box > 1 ? 1 : 0;
+    double *llk = nullptr, *d_starts = nullptr, *d_llh = nullptr, *d_popllh = nullptr, *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
+    double *rjafs = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_ids = nullptr, *d_points = nullptr;
+    int32_t *rstatus = nullptr, *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr, *d_nfev = nullptr, *d_status = nullptr;
+    int32_t *idx[2] = {nullptr, nullptr}, *cnt = nullptr;
+    auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        st.b.pts = f.take(M * N); st.pop = f.take(M * N); st.f = f.take(M); st.b.split = f.take(M); llk = f.take(M);
+        if (NQ) st.b.par = f.take(M * NQ);
+        d_starts = f.take(S * N); d_llh = f.take(S); d_popllh = f.take(M);
+        if (per_start) d_split = f.take(S);
+        d_table = f.take(R * 8); d_consts = f.take(R); rjafs = f.take(M * 7);
+        d_lo = f.take(NX); d_hi = f.take(NX);
+        if (q.ids) d_ids = f.take(S);                      // uint64 ids and the point counter: 8-byte words of the double buffer
+        d_points = f.take(1);
+        st.b.row = i.take(M); rstatus = i.take(M); d_rowof = i.take(S);
+        if (NB2) { d_bounds = i.take(S * NB2); st.b.bnd = i.take(M * NB2); }
+        if (NP) { d_pulses = i.take(S * NP); st.b.put = i.take(M * NP); }
+        st.best = i.take(S); st.nit = i.take(S); st.done = i.take(S); d_nfev = i.take(S); d_status = i.take(S);
+        idx[0] = i.take(S); idx[1] = i.take(S); cnt = i.take(4);
+    };
+    Carver<double> f;
+    Carver<int32_t> i;
+    layout(f, i);
+    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
+    HIP_TRY(c->nm_i32.reserve(i.n * sizeof(int32_t)));
+    if (!c->nm_live_host) {
+        if (hipHostMalloc((void**)&c->nm_live_host, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            c->nm_live_host = nullptr;
+            return fail(MISTI_E_HIP, "pinned allocation for the live-search count failed");
+        }
+    }
+    f = Carver<double>{c->nm_f64.as<double>()};
+    i = Carver<int32_t>{c->nm_i32.as<int32_t>()};
+    layout(f, i);
+    st.split_of = d_split; st.row_of = d_rowof; st.bounds_of = d_bounds; st.pulses_of = d_pulses;
+    st.box_lo = d_lo; st.box_hi = d_hi;
+    st.ids = reinterpret_cast<const uint64_t*>(d_ids);
+    st.points = reinterpret_cast<unsigned long long*>(d_points);
+    hipStream_t sm = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_starts, q.starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (per_start) HIP_TRY(hipMemcpyAsync(d_split, q.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_lo, q.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_hi, q.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (q.ids) HIP_TRY(hipMemcpyAsync(d_ids, q.ids, S * sizeof(uint64_t), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));
+    HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
+    HIP_TRY(hipMemsetAsync(d_points, 0, sizeof(double), sm));
+    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
+    // the rows path's hints (nm_run): integer splits where the caller's are; a fitted split is never known to be whole
+    const unsigned hints = whole ? RUN_INTEGER_SPLITS : 0u;
+    auto eval = [&](int64_t n) { return eval_rows(c, st.b, n, fit_split ? st.b.par : st.b.pts, hints, rjafs, rstatus, d_table, d_consts, llk); };
+    // generation 0: every search in its own slot
+    HIP_TRY(launch_de_init(st, d_starts, sm));
+    if (int r = eval((int64_t)M)) return r;
+    int cur = 0;
+    st.idx_cur = idx[cur ^ 1]; st.count_cur = cnt + (cur ^ 1);
+    st.idx_next = idx[cur]; st.count_next = cnt + cur;
+    HIP_TRY(launch_de_select(st, q.n_start, 0, llk, sm));
+    // The host runs at most two generations ahead of the device, as nm_run does: before issuing generation g it waits for the event of
+    // generation g - 2 and reads the count of live searches that generation left in pinned memory - an upper bound, the number only
+    // falls - which sizes the batch; zero: stop issuing.
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ev};
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    volatile int32_t* live_host = c->nm_live_host;
+    live_host[0] = live_host[1] = -1;
+    HIP_TRY(hipMemcpyAsync((void*)&live_host[0], cnt + cur, sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipEventRecord(ev[0], sm));
+    HIP_TRY(hipEventSynchronize(ev[0]));
+    int64_t bound = live_host[0];
+    int64_t issued = 0, slots = 0;
+    for (int it = 0; bound > 0 && it < q.maxiter; ++it) {
+        const int slot = it & 1;
+        if (it >= 2) {
+            HIP_TRY(hipEventSynchronize(ev[slot]));
+            if (live_host[slot] < bound) bound = live_host[slot];
+            if (bound <= 0) break;
+        }
+        st.idx_cur = idx[cur]; st.count_cur = cnt + cur;
+        st.idx_next = idx[cur ^ 1]; st.count_next = cnt + (cur ^ 1);
+        HIP_TRY(launch_de_trial(st, bound, it + 1, sm));
+        if (int r = eval(bound * (int64_t)P)) return r;
+        HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
+        HIP_TRY(launch_de_select(st, bound, it + 1, llk, sm));
+        HIP_TRY(hipMemcpyAsync((void*)&live_host[slot], cnt + (cur ^ 1), sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+        HIP_TRY(hipEventRecord(ev[slot], sm));
+        cur ^= 1;
+        ++issued;
+        slots += bound;
+    }
+    c->nm_iterations = issued;
+    c->nm_slots = slots;
+    HIP_TRY(launch_de_result(st, d_starts, d_llh, d_nfev, d_status, q.population_llh ? d_popllh : nullptr, sm));
+    HIP_TRY(hipMemcpyAsync(q.x, d_starts, S * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(q.llh, d_llh, S * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.nit) HIP_TRY(hipMemcpyAsync(q.nit, st.nit, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.nfev) HIP_TRY(hipMemcpyAsync(q.nfev, d_nfev, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.status) HIP_TRY(hipMemcpyAsync(q.status, d_status, S * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.population) HIP_TRY(hipMemcpyAsync(q.population, st.pop, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.population_llh) HIP_TRY(hipMemcpyAsync(q.population_llh, d_popllh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.n_points) HIP_TRY(hipMemcpyAsync(q.n_points, d_points, sizeof(int64_t), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipStreamSynchronize(sm));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int misti_de_search(misti_ctx* c, const misti_de_t* q) {
+    if (!q) return fail(MISTI_E_ARG, "the search descriptor is NULL");
+    if (q->size != sizeof(misti_de_t))
+        return fail(MISTI_E_ARG, "the search descriptor's size is %u, this library's misti_de_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_de_t));
+    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
+        return fail(MISTI_E_ARG, "the search descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
+    int N = 0;
+    bool whole = false;
+    if (int r = de_check(c, *q, N, whole)) return r;
+    if (q->n_start == 0) return 0;
+    return de_run(c, *q, N, whole);
+}
 
 int misti_search(misti_ctx* c, const misti_search_t* q) {
     if (!q) return fail(MISTI_E_ARG, "the search descriptor is NULL");

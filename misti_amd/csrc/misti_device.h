@@ -104,6 +104,19 @@ __host__ __device__ __forceinline__ int32_t solver_word(int nfev, int status, in
 __device__ __forceinline__ int64_t chain_of(const ChainBufs& cb, int64_t cand) { return cb.of[cand]; }
 __device__ __forceinline__ int chain_len(const ChainBufs& cb, int64_t ch) { return cb.slot_len[cb.chain_slot[ch]]; }
 
+// What the searches (misti_nm.hip, misti_de.hip) share on the device.
+// -JAFSLikelihood as an optimiser sees it; no value = +inf
+__device__ __forceinline__ double objective(double llk) { return (llk == llk && llk > -INFINITY) ? -llk : INFINITY; }
+// the value as rounded so far: opaque to the optimiser, so a product passed through it is never contracted into an fma
+__device__ __forceinline__ double rn(double v) { __asm__ volatile("" : "+v"(v)); return v; }
+// numpy.clip(x, lo, hi) = minimum(maximum(x, lo), hi) on one coordinate: a NaN passes through (fmin / fmax would drop it), an x equal to
+// a bound comes back as the bound itself (a zero takes the bound's sign, as NumPy's does), +-inf bounds never bind.  lo <= hi, neither NaN.
+__device__ __forceinline__ double box_clip(double x, double lo, double hi) {
+    double t = x > lo ? x : lo;
+    t = t < hi ? t : hi;
+    return x != x ? x : t;
+}
+
 // Batched Nelder-Mead (misti_nm.hip): everything a start owns, in HBM.  V = N + 1 vertices.
 enum { NM_NONE = 0, NM_REFLECT = 1, NM_EXPAND = 2, NM_CONTRACT = 3, NM_INSIDE = 4,
        NM_CUT = 5 };        // the evaluation budget (maxfev) ran out before the iteration's second point: SciPy abandons the iteration there
@@ -202,6 +215,49 @@ hipError_t launch_bh_update(const BhState& bh, const NmState& nm, const double* 
 // next trial points: AdaptiveStepsize.take_step + RandomDisplacement with the pre-drawn uniforms of hop `hop`
 hipError_t launch_bh_step(const BhState& bh, int hop, int niter, const double* uniforms, double* trial, hipStream_t stream);
 hipError_t launch_bh_result(const BhState& bh, double* x, double* llh, hipStream_t stream);
+
+// Differential evolution per search (misti_de.hip; the rule is optimize.differential_evolution_rule, operation for operation):
+// everything a search owns, in HBM.  A generation of every live search is ONE engine batch of P points per search; batch slot
+// j * P + i carries member i of the search in live slot j.  What a search hands its points (split, row, bounds, pulse times, the box)
+// are NmState's fields of the same names, and the batch is an NmBatch: the engine sees what a Nelder-Mead batch hands it.
+struct DeState {
+    int64_t S;              // searches
+    int N, P;               // coordinates, members
+    int maxiter;            // generations
+    double tol, atol;       // stop: var(f) <= (atol + tol |mean(f)|)^2 over members that all have a value
+    double F_lo, F_hi, CR;
+    uint64_t seed;
+    const uint64_t* ids;    // [S] or NULL: the stream of search s is Philox(key=[seed, ids[s]]); NULL: ids[s] = s
+    const double* split_of; // [S] or NULL (fit_split)
+    const int32_t* row_of;  // [S]
+    const int32_t* bounds_of;   // [S][nb2] or NULL
+    int nb2;
+    const int32_t* pulses_of;   // [S][np] or NULL
+    int np;
+    int fit_split;          // 1: the last coordinate is the point's split time, the N - 1 before it go to the batch's compact `par`
+    const double* box_lo;   // [N], or [S][N] with box_per_start: finite, lo <= hi
+    const double* box_hi;
+    int box_per_start;
+    double* pop;            // [S][P][N] the population
+    double* f;              // [S][P]    its objective (-llk, +inf where the engine has no value)
+    int32_t* best;          // [S] the member with the lowest objective (ties: the lowest index)
+    int32_t* nit;           // [S] generations completed
+    int32_t* done;          // [S] -1 while running; 0 converged, 2 generation budget
+    NmBatch b;              // [S * P] slots: the initial population, then every generation's trial points (live searches compacted)
+    int32_t* idx_cur;       // [S] live slot -> search of the generation in progress
+    int32_t* count_cur;     // [1]
+    int32_t* idx_next;      // [S] filled by the selection that ends the generation
+    int32_t* count_next;    // [1]
+    unsigned long long* points;   // [1] points handed to the engine that carry a search's point (empty slots not counted)
+};
+hipError_t launch_de_init(const DeState& st, const double* starts, hipStream_t stream);
+// trial points of generation `gen` (>= 1) for the first `bound` live slots (slots beyond the live searches carry no point)
+hipError_t launch_de_trial(const DeState& st, int64_t bound, int gen, hipStream_t stream);
+// values of generation `gen` are in (gen 0: the initial population, every search live in its own slot): selection, best, stop test,
+// and the searches that go on compacted into idx_next / count_next
+hipError_t launch_de_select(const DeState& st, int64_t bound, int gen, const double* llk, hipStream_t stream);
+// x[S][N], llh[S], nit / nfev / status[S]; pop_llh[S][P] (or NULL): -f
+hipError_t launch_de_result(const DeState& st, double* x, double* llh, int32_t* nfev, int32_t* status, double* pop_llh, hipStream_t stream);
 
 // Replicate epilogue fused into the spectrum kernel up to this many replicates (one launch less per batch).
 constexpr int LLK_INLINE_MAX = 8;

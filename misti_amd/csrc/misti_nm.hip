@@ -44,18 +44,7 @@ namespace {
 constexpr double NM_RHO = 1.0, NM_CHI = 2.0, NM_PSI = 0.5, NM_SIGMA = 0.5;
 constexpr double NM_NONZDELT = 0.05, NM_ZDELT = 0.00025;
 
-__device__ __forceinline__ double objective(double llk) { return (llk == llk && llk > -INFINITY) ? -llk : INFINITY; }   // -JAFSLikelihood; no value = +inf
-
-// the value as rounded so far: opaque to the optimiser, so a product passed through it is never contracted into an fma
-__device__ __forceinline__ double rn(double v) { __asm__ volatile("" : "+v"(v)); return v; }
-
-// numpy.clip(x, lo, hi) = minimum(maximum(x, lo), hi) on one coordinate: a NaN passes through (fmin / fmax would drop it), an x equal to
-// a bound comes back as the bound itself (a zero takes the bound's sign, as NumPy's does), +-inf bounds never bind.  lo <= hi, neither NaN.
-__device__ __forceinline__ double box_clip(double x, double lo, double hi) {
-    double t = x > lo ? x : lo;
-    t = t < hi ? t : hi;
-    return x != x ? x : t;
-}
+// objective(), rn() and box_clip() are misti_device.h's: the population search (misti_de.hip) rounds, clips and scores by the same three.
 // Where start s's box begins in box_lo / box_hi, and coordinate k of one of its points clipped to it (SciPy: np.clip(x, lower_bound,
 // upper_bound) on every point before func sees it); without a box the value as it is.
 __device__ __forceinline__ int64_t box_of(const NmState& st, int64_t s) { return st.box_per_start ? s * st.N : 0; }

@@ -660,6 +660,51 @@ class Engine:
         r["split"] = r["x"][:, -1].copy() if split_times is None else np.array(split_times, dtype=np.float64).reshape(-1)
         return r
 
+    def differential_evolution(self, starts, rows, jsfs, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, pop=16,
+                               maxiter=50, tol=0.01, atol=0.0, F=(0.5, 1.0), CR=0.7, seed=0, ids=None, return_population=False):
+        """``misti_de_search``: differential evolution per search - search s is a population of ``pop`` members inside its finite ``box``
+        (``(lo, hi)``, each ``[N]`` or ``[S][N]``; ``lo == hi`` holds a coordinate fixed) against ``jsfs[rows[s]]`` (``[n_rep][8]``), member
+        0 its row of ``starts``; every generation of all searches is ONE engine batch.  The rule is the project's own, not SciPy's
+        (``optimize.differential_evolution_rule`` states it; the result equals it bit for bit): best1bin, dither ``F = (lo, hi)``,
+        crossover ``CR``, deferred selection, stop at ``std(f) <= atol + tol |mean(f)|`` or after ``maxiter`` generations.  Exactly one of
+        ``split_times`` (``[S]``, ``starts`` is ``[S][n_param]``) and ``fit_split=True`` (the split is the LAST coordinate, ``starts`` is
+        ``[S][n_param + 1]``).  Everything random is ``numpy.random.Philox(key=[seed, ids[s]])`` (``ids`` default ``0 ... S - 1``): a
+        search's result depends on its own arguments alone.  ``band_bounds`` / ``pulse_times`` per search as in ``nm_solve_pulses``.
+        Returns dict(x[S][N], llh[S], nit / nfev / status[S] (0 converged, 2 generation budget), split[S], n_points (points the call handed
+        the engine), the work counters ``iterations_issued`` / ``slots`` and, with ``return_population``, population[S][pop][N] and
+        population_llh[S][pop])."""
+        if (split_times is None) != bool(fit_split):
+            raise ValueError("differential_evolution: give exactly one of split_times and fit_split=True")
+        N = self.n_param + (1 if fit_split else 0)
+        st = _f64(starts, (-1, N))
+        S, P = st.shape[0], int(pop)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
+        tab = _f64(jsfs, (-1, 8))
+        sp = _f64(split_times, (S,)) if split_times is not None else None
+        r_of = i32(rows, (S,))
+        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
+        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
+        lo, hi = _box_arrays(box, N)
+        id_ = np.ascontiguousarray(np.asarray(ids).reshape(S), dtype=np.uint64) if ids is not None else None
+        x, llh = np.empty((S, N)), np.empty(S)
+        nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
+        keep = return_population and 4 <= P <= _lib.DE_MAX_POP
+        popx, popl = (np.empty((S, P, N)), np.empty((S, P))) if keep else (None, None)
+        n_points = np.zeros(1, dtype=np.int64)
+        q = _lib.DeSearch(size=C.sizeof(_lib.DeSearch), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, split_times=ptr(sp),
+                          n_start=S, starts=ptr(st), rows=ptr(r_of), n_rep=tab.shape[0], jsfs=ptr(tab), band_bounds=ptr(bb), pulse_times=ptr(pt),
+                          n_box=lo.shape[0], box_lo=ptr(lo), box_hi=ptr(hi), pop=P, maxiter=int(maxiter), tol=float(tol), atol=float(atol),
+                          F_lo=float(F[0]), F_hi=float(F[1]), CR=float(CR), seed=int(seed), ids=ptr(id_), x=ptr(x), llh=ptr(llh), nit=ptr(nit),
+                          nfev=ptr(nfev), status=ptr(status), population=ptr(popx), population_llh=ptr(popl), n_points=ptr(n_points))
+        _lib.check(self._lib.misti_de_search(self._ctx, C.byref(q)))
+        stats = self._nm_stats()
+        out = dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, n_points=int(n_points[0]),
+                   split=x[:, -1].copy() if fit_split else sp.copy(), iterations_issued=stats["iterations_issued"], slots=stats["slots"])
+        if return_population:
+            out.update(population=popx, population_llh=popl)
+        return out
+
     def enable_solver_trace(self, on=True):
         """Record, for the following batches, SciPy-comparable solver statistics per candidate and interval
         (``misti_enable_solver_trace``; see ``solver_trace``)."""

@@ -1245,3 +1245,212 @@ def parametric_rows(spectra, n, n_sites, genome, seed=0, first=0, spec_of=None, 
 def parametric_table(data_row, rows):
     """The data row in front of the replicates, as ``block_bootstrap_table`` lays a table out: float64 ``[1 + n][8]``."""
     return np.vstack([np.asarray(data_row, dtype=np.float64).reshape(1, 8), np.asarray(rows, dtype=np.float64).reshape(-1, 8)])
+
+
+# ----------------------------------------------------------------------------------------- differential evolution ----
+# The rule of misti_de_search stated on the host (include/misti_hip.h, "differential evolution per search"): the device result is this,
+# bit for bit, on the engine's own objective.  The rule is the project's own, not SciPy's: scipy.optimize.differential_evolution redraws
+# a coordinate that leaves the bounds, so the number of its draws depends on the data; here every member of every generation owns a
+# fixed piece of a counter-based stream and a crossed bound is repaired without a draw.  Modelled on SciPy's best1bin, updating='deferred'.
+DE_BLOCKS, DE_MAX_POP, DE_MAX_N = 5, 256, 16
+
+
+def _mulhi_index(raw, n):
+    """The high 64 bits of ``raw x n`` per element (``boot_index`` of misti_boot.h), ``1 <= n < 2**32``: int64."""
+    raw = np.asarray(raw, dtype=np.uint64)
+    m, s32 = np.uint64(n), np.uint64(32)
+    hi, lo = raw >> s32, raw & np.uint64(0xFFFFFFFF)
+    return ((hi * m + ((lo * m) >> s32)) >> s32).astype(np.int64)
+
+
+def _de_generation(seed, id_, generation, pop, n):
+    """What the ``pop`` members of generation ``generation`` of the stream ``Philox(key=[seed, id_])`` draw: member i owns the
+    ``DE_BLOCKS`` blocks from block ``(generation * pop + i) * DE_BLOCKS`` on (NumPy advances the counter before every block, so the
+    stream's block b is the counter b + 1: a generator set to counter b starts with it), 4 ``DE_BLOCKS`` words ``w``: ``w[0]`` r1,
+    ``w[1]`` r2, ``w[2]`` jrand, ``w[3]`` F's uniform, ``w[4 + k]`` the uniform of coordinate k.
+    Returns r1[pop], r2[pop], jrand[pop] (int64), u_F[pop], u[pop][n] (float64)."""
+    pop, n = int(pop), int(n)
+    if not 4 <= pop <= DE_MAX_POP or not 1 <= n <= DE_MAX_N or int(generation) < 0:
+        raise ValueError("de_draws: pop must be 4 ... %d, n 1 ... %d, the generation not negative" % (DE_MAX_POP, DE_MAX_N))
+    counter = np.array([int(generation) * pop * DE_BLOCKS, 0, 0, 0], dtype=np.uint64)
+    gen = np.random.Philox(key=np.array([int(seed), int(id_)], dtype=np.uint64), counter=counter)
+    w = np.asarray(gen.random_raw(pop * 4 * DE_BLOCKS), dtype=np.uint64).reshape(pop, 4 * DE_BLOCKS)
+    i = np.arange(pop)
+    r1 = _mulhi_index(w[:, 0], pop - 1)
+    r1 = r1 + (r1 >= i)                                               # the P - 1 members other than i, in member order
+    a, b = np.minimum(i, r1), np.maximum(i, r1)
+    r2 = _mulhi_index(w[:, 1], pop - 2)
+    r2 = r2 + (r2 >= a)                                               # the P - 2 members other than i and r1
+    r2 = r2 + (r2 >= b)
+    jrand = _mulhi_index(w[:, 2], n)
+    uniform = lambda raw: (raw >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    return r1, r2, jrand, uniform(w[:, 3]), uniform(w[:, 4:4 + n])
+
+
+def de_draws(seed, id_, generation, member, pop, n):
+    """``misti_de_draws``: what member ``member`` of generation ``generation`` of the stream ``numpy.random.Philox(key=[seed, id_])``
+    draws in a search of ``pop`` members and ``n`` coordinates.  Returns dict(r1, r2, jrand, u_F, u[n]); generation 0 uses ``u`` alone."""
+    if not 0 <= int(member) < int(pop):
+        raise ValueError("de_draws: member must be 0 ... pop - 1")
+    r1, r2, jrand, u_F, u = _de_generation(seed, id_, generation, pop, n)
+    m = int(member)
+    return dict(r1=int(r1[m]), r2=int(r2[m]), jrand=int(jrand[m]), u_F=float(u_F[m]), u=u[m].copy())
+
+
+def differential_evolution_rule(fun_batch, starts, lo, hi, pop=16, maxiter=100, tol=0.01, atol=0.0, F=(0.5, 1.0), CR=0.7, seed=0, ids=None):
+    """The rule of ``misti_de_search``, operation for operation.  ``fun_batch(X[M][N], s[M]) -> f[M]`` evaluates M points at once, point
+    m belonging to search ``s[m]`` (``+inf``: no value; a NaN counts as ``+inf``).  ``starts`` ``[S][N]``: member 0 of every search;
+    ``lo`` / ``hi``: the finite box, ``[N]`` or ``[S][N]``, ``lo == hi`` holds a coordinate fixed; ``ids[s]`` (default s): the stream of
+    search s is ``numpy.random.Philox(key=[seed, ids[s]])``.
+
+    Generation 0: member 0 is the start clipped to the box, member i > 0 ``clip(lo + u * (hi - lo))``.  Generation g >= 1, member i:
+    ``best`` the member with the lowest f (ties: the lowest index), ``v = best + F * (x[r1] - x[r2])`` with ``F = F_lo + u_F * (F_hi -
+    F_lo)``; the trial takes ``v[k]`` where ``k == jrand`` or ``u[k] < CR`` and ``x[i][k]`` elsewhere; a ``v[k]`` beyond a bound becomes
+    ``x[i][k] + 0.5 * (bound - x[i][k])``; a fixed coordinate stays at ``lo``.  All trials of a generation are evaluated as one batch
+    against the population of the generation before; member i is replaced iff ``f(trial) <= f(x[i])``.  After every generation, the
+    initial one included, a search stops with status 0 when every member has a value and ``q / P <= (atol + tol * abs(m)) ** 2`` with
+    ``m = (f[0] + f[1] + ...) / P`` and ``q = (f[0] - m) ** 2 + (f[1] - m) ** 2 + ...`` (sums in member order, from f[0] and from 0.0);
+    with status 2 after ``maxiter`` generations.  A stopped search submits no further points.
+    Returns dict(x[S][N], llh[S] (= -f of the best member; -inf: no point ever had a value), nit[S], nfev[S], status[S],
+    population[S][P][N], population_llh[S][P], n_points: the points handed to ``fun_batch`` in all)."""
+    x0 = np.atleast_2d(np.asarray(starts, dtype=float))
+    S, N = x0.shape
+    P = int(pop)
+    F_lo, F_hi = (float(v) for v in F)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=float), (S, N)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=float), (S, N)))
+    with np.errstate(over="ignore", invalid="ignore"):
+        usable = np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(hi - lo).all() and np.isfinite(x0).all()
+    if not usable:
+        raise ValueError("differential_evolution_rule: the box must be finite with lo <= hi, the starts finite")
+    if not 4 <= P <= DE_MAX_POP or int(maxiter) < 1:
+        raise ValueError("differential_evolution_rule: pop must be 4 ... %d, maxiter >= 1" % DE_MAX_POP)
+    ids = np.arange(S) if ids is None else np.asarray(ids).reshape(S)
+    fixed = lo == hi
+
+    def values(X, s_of):
+        f = np.asarray(fun_batch(X.reshape(-1, N), np.repeat(s_of, P)), dtype=float).reshape(-1, P)
+        return np.where(np.isnan(f), np.inf, f)
+
+    x = np.empty((S, P, N))
+    for s in range(S):
+        u = _de_generation(seed, ids[s], 0, P, N)[4]
+        x[s] = lo[s] + u * (hi[s] - lo[s])
+        x[s, 0] = x0[s]
+        x[s] = np.clip(x[s], lo[s], hi[s])
+    f = values(x, np.arange(S))
+    n_points = S * P
+    nit = np.zeros(S, dtype=np.int32)
+    status = np.full(S, 2, dtype=np.int32)
+    best = np.zeros(S, dtype=np.int64)
+    live = np.arange(S)
+    for g in range(0, int(maxiter) + 1):
+        if g >= 1:
+            t = np.empty((live.size, P, N))
+            for j, s in enumerate(live):
+                r1, r2, jrand, u_F, u = _de_generation(seed, ids[s], g, P, N)
+                Fd = (F_lo + u_F * (F_hi - F_lo))[:, None]
+                v = x[s, best[s]][None, :] + Fd * (x[s, r1] - x[s, r2])
+                up = x[s] + 0.5 * (hi[s] - x[s])
+                dn = x[s] + 0.5 * (lo[s] - x[s])
+                v = np.clip(np.where(v > hi[s], up, np.where(v < lo[s], dn, v)), lo[s], hi[s])
+                cross = (np.arange(N)[None, :] == jrand[:, None]) | (u < CR)
+                t[j] = np.where(fixed[s], lo[s], np.where(cross, v, x[s]))
+            ft = values(t, live)
+            n_points += live.size * P
+            take = ft <= f[live]
+            x[live] = np.where(take[:, :, None], t, x[live])
+            f[live] = np.where(take, ft, f[live])
+            nit[live] = g
+        go = []
+        for s in live:
+            fs = f[s]
+            best[s] = int(np.argmin(fs))                      # the first minimum: the lowest index on ties
+            stop = False
+            if (fs < np.inf).all():
+                total = fs[0]
+                for m in range(1, P):
+                    total = total + fs[m]
+                mean = total / P
+                q = 0.0
+                with np.errstate(invalid="ignore", over="ignore"):
+                    for m in range(P):
+                        d = fs[m] - mean
+                        q = q + d * d
+                    thr = atol + tol * abs(mean)
+                    stop = bool(q / P <= thr * thr)
+            if stop:
+                status[s] = 0
+            elif g < int(maxiter):
+                go.append(s)
+        live = np.asarray(go, dtype=np.int64)
+        if live.size == 0:
+            break
+    bi = best[:, None]
+    return dict(x=np.take_along_axis(x, bi[:, :, None], axis=1)[:, 0], llh=-np.take_along_axis(f, bi, axis=1)[:, 0], nit=nit,
+                nfev=(P * (nit + 1)).astype(np.int32), status=status, population=x, population_llh=-f, n_points=int(n_points))
+
+
+def _de_profile(R, n_per_row, search, polish):
+    """What bootstrap_profile_de and split_fit_de share: ``search(r_of, j_of, ids)`` is ONE differential-evolution call over every
+    (row, search-within-row) pair, row outermost; the stream id of a search is its index WITHIN its row, so a row's result does not depend
+    on which other rows the call holds.  With ``polish`` one boxed Nelder-Mead call (``search`` with the DE's ``x`` as its last argument)
+    starts from the DE results and a search keeps the better of the two (the polished one on ties)."""
+    r_of, j_of = (a.ravel() for a in np.meshgrid(np.arange(R), np.arange(n_per_row), indexing="ij"))
+    de = search(r_of.astype(np.int32), j_of, j_of.astype(np.uint64), None)
+    out = dict(de, de_llh=de["llh"].copy(), polished=np.zeros(r_of.size, dtype=bool))
+    if polish:
+        nm = search(r_of.astype(np.int32), j_of, None, de["x"])
+        better = nm["llh"] >= de["llh"]                       # NaN never wins
+        out["x"] = np.where(better[:, None], nm["x"], de["x"])
+        out["llh"] = np.where(better, nm["llh"], de["llh"])
+        out["polished"] = better
+        out["polish_nfev"] = nm["nfev"]
+    return out
+
+
+def bootstrap_profile_de(engine, split_values, jsfs_rows, start, box, pop=16, maxiter=50, tol=0.01, atol=0.0, F=(0.5, 1.0), CR=0.7, seed=0,
+                         polish=False, polish_tol=1e-4, polish_maxiter=1000):
+    """``bootstrap_profile_global`` with differential evolution in place of basin hopping: per (row, split) pair ONE population search
+    inside ``box`` (``(lo, hi)``, each ``[n_param]``, finite), all R x P searches in ONE ``misti_de_search`` call - every generation one
+    dense engine batch, no inner minimisations.  ``start`` ``[n_param]`` is member 0 of every search.  The stream id of a search is its
+    split's index, so a row's result does not depend on the other rows.  ``polish``: one ``nm_solve_box`` call from the DE results
+    under the same box (the ``scan_polish`` pattern); a search keeps the better result.
+    Returns dict(x[R][P][N], llh[R][P], de_llh[R][P], nit / nfev / status[R][P] (the DE's), polished[R][P], n_points)."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.asarray(split_values, dtype=float).reshape(-1)
+    R, Q = rows.shape[0], splits.size
+    x0 = np.asarray(start, dtype=float).reshape(1, engine.n_param)
+
+    def search(r_of, j_of, ids, polish_from):
+        if polish_from is not None:
+            return engine.nm_solve_box(polish_from, r_of, rows, box, split_times=splits[j_of], tol=polish_tol, maxiter=polish_maxiter)
+        return engine.differential_evolution(np.repeat(x0, r_of.size, axis=0), r_of, rows, box, split_times=splits[j_of], pop=pop,
+                                             maxiter=maxiter, tol=tol, atol=atol, F=F, CR=CR, seed=seed, ids=ids)
+    out = _de_profile(R, Q, search, polish)
+    return {k: (v.reshape(R, Q, *v.shape[1:]) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+
+
+def split_fit_de(engine, jsfs_rows, start, box, band_bounds=None, pulse_times=None, pop=16, maxiter=50, tol=0.01, atol=0.0, F=(0.5, 1.0), CR=0.7,
+                 seed=0, polish=False, polish_tol=1e-4, polish_maxiter=1000):
+    """``split_fit_global`` with differential evolution in place of basin hopping: per row ONE population search over (optimised
+    parameters, split) inside ``box`` (``(lo, hi)``, each ``[n_param + 1]``, finite, the split last), all R searches in ONE
+    ``misti_de_search`` call.  ``start`` ``[n_param + 1]`` is member 0 of every search; every row draws from stream 0 (the rows of a
+    bootstrap share their random numbers - only the data differ).  ``band_bounds`` / ``pulse_times`` apply to every search.
+    ``polish``: one ``nm_solve_box`` call from the DE results under the same box; a row keeps the better result.
+    Returns dict(x[R][n_param + 1], split[R], llh[R], de_llh[R], nit / nfev / status[R] (the DE's), polished[R], n_points);
+    ``split_fit_interval`` takes ``split`` and ``llh`` unchanged."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    R = rows.shape[0]
+    x0 = np.asarray(start, dtype=float).reshape(1, engine.n_param + 1)
+    tile = lambda a, shape, S: None if a is None else np.repeat(np.asarray(a, dtype=np.int32).reshape(shape), S, axis=0)
+
+    def search(r_of, j_of, ids, polish_from):
+        per = dict(band_bounds=tile(band_bounds, (1, -1, 2), r_of.size), pulse_times=tile(pulse_times, (1, -1), r_of.size))
+        if polish_from is not None:
+            return engine.nm_solve_box(polish_from, r_of, rows, box, tol=polish_tol, maxiter=polish_maxiter, **per)
+        return engine.differential_evolution(np.repeat(x0, r_of.size, axis=0), r_of, rows, box, fit_split=True, pop=pop, maxiter=maxiter,
+                                             tol=tol, atol=atol, F=F, CR=CR, seed=seed, ids=ids, **per)
+    out = _de_profile(R, 1, search, polish)
+    out["split"] = out["x"][:, -1].copy()
+    return out

@@ -165,3 +165,59 @@ def run_basinhopping(a, w, split, local_rank, rank, world, json_fd):
            "best": {"llh": float(np.max(r["llh"])), "params": [float(v) for v in r["x"][int(np.argmax(r["llh"]))]], "truth": [0.2, 0.05]}}
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
+
+
+def run_de_compare(n_rows=256, pop=16, gens=40, hops=(10, 30), seed=0, device=0, out=None):
+    """`python -m misti_amd.search_bench`: config 3's model as a GLOBAL search per bootstrap row, both ways - differential evolution
+    (misti_de_search: every generation one dense batch of rows x members points) and basin hopping on the rows path
+    (misti_basinhopping_box, hops in lockstep) - on the same rows, from the same start per row, inside the same box (the range config
+    3's random starts span).  Reports per leg the wall time of one call, the evaluations (sum of nfev) and the median over rows of the
+    best llh reached: what to compare is time and evaluations at equal median llh.  One JSON line per leg."""
+    import random
+    from . import io as mio, synth, workloads
+    from .engine import Engine, truth_spectrum
+    w = workloads.config3(lambda *a: truth_spectrum(*a), n_start=max(n_rows, 64))
+    split = float(w.split_time[0])
+    table = np.array(mio.bootstrap_table(synth.chunk_rows(w.jsfs[0], 20), n_rows - 1, random.Random(3)), dtype=np.float64)
+    R = table.shape[0]
+    rows = np.arange(R, dtype=np.int32)
+    starts = np.ascontiguousarray(w.params[:R])
+    box = (w.params.min(axis=0), w.params.max(axis=0))
+    splits = np.full(R, split)
+    lines = []
+    with Engine(w.times, w.lh, device=device, **w.engine_kwargs()) as eng:
+        legs = [("de pop=%d gens=%d seed=%d" % (pop, gens, seed),
+                 lambda: eng.differential_evolution(starts, rows, table, box, split_times=splits, pop=pop, maxiter=gens, tol=0.0, seed=seed))]
+        for n in hops:
+            legs.append(("basinhopping hops=%d seed=%d" % (n, seed),
+                         lambda n=n: eng.basinhopping_box(starts, rows, table, [seed + 1000 + j for j in range(R)], box, split_times=splits, niter=n)))
+        eng.differential_evolution(starts[:4], rows[:4], table, box, split_times=splits[:4], pop=4, maxiter=1)      # first calls allocate
+        eng.basinhopping_box(starts[:4], rows[:4], table, [0, 1, 2, 3], box, split_times=splits[:4], niter=1)
+        for name, call in legs:
+            eng.sync()
+            t0 = time.perf_counter()
+            r = call()
+            dt = time.perf_counter() - t0
+            lines.append({"leg": name, "rows": R, "box": [list(map(float, box[0])), list(map(float, box[1]))], "seconds": dt,
+                          "nfev": int(r["nfev"].sum()), "median_llh": float(np.median(r["llh"])), "min_llh": float(np.min(r["llh"])),
+                          "max_llh": float(np.max(r["llh"])), "evals_per_second": int(r["nfev"].sum()) / dt})
+    text = "\n".join(json.dumps(l) for l in lines) + "\n"
+    sys.stdout.write(text)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(text)
+    return lines
+
+
+if __name__ == "__main__":
+    import argparse
+    ap = argparse.ArgumentParser(description="differential evolution against basin hopping on config 3's model, per bootstrap row")
+    ap.add_argument("--rows", type=int, default=256)
+    ap.add_argument("--pop", type=int, default=16)
+    ap.add_argument("--gens", type=int, default=40)
+    ap.add_argument("--hops", type=int, nargs="+", default=[10, 30])
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    run_de_compare(a.rows, a.pop, a.gens, tuple(a.hops), a.seed, a.device, a.out)
