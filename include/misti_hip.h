@@ -682,6 +682,94 @@ int misti_de_search(misti_ctx* ctx, const misti_de_t* search);
 int misti_de_draws(uint64_t seed, uint64_t id, int64_t generation, int32_t member, int32_t pop, int32_t n,
                    int32_t* r1, int32_t* r2, int32_t* jrand, double* u_F, double* u /* HOST [n] */);
 
+/* ---- ensemble MCMC per search --------------------------------------------------------------- */
+/* A sampler beside the searches: n_start ensembles at once, every half-step of every ensemble ONE engine batch of walkers / 2 points
+ * per search.  The affine-invariant ensemble sampler (Goodman & Weare's stretch move, the algorithm of emcee): no proposal covariance
+ * to tune, invariant to the scaling of the coordinates, half an ensemble moves at once; like differential evolution it has no inner
+ * minimisation and no tail.  The reference has no counterpart, and emcee is no bit-parity target (it draws from a Mersenne Twister in
+ * an order that depends on the ensemble).  The rule is THE PROJECT'S OWN, stated once in NumPy (optimize.ensemble_rule); the device
+ * result is that, bit for bit, on the engine's own objective.
+ *
+ * Search s has N coordinates - n_param, or n_param + 1 with MISTI_SPLIT_FITTED (the split last; n_param == 0 allowed there) -, a row
+ * rows[s], optional band bounds and pulse times, a FINITE box [lo, hi] per coordinate (lo == hi holds the coordinate fixed), W =
+ * walkers walkers init[s][W][N], a temperature T > 0 and a stream id ids[s] (NULL: s).  The target density is exp(llk(x) / T) inside
+ * the box where the engine has a value and zero elsewhere: a uniform prior on the box.  The rule:
+ *   - the caller supplies the initial ensemble, every walker inside its box (a fixed coordinate at lo exactly); all W walkers of all
+ *     searches are evaluated as ONE batch.  A walker the engine refuses has no value (llh -inf);
+ *   - step t = 1 ... n_step has two half-steps: in half 0 walkers 0 ... W / 2 - 1 move against the second half as it stands, in half
+ *     1 walkers W / 2 ... W - 1 move against the first half as half 0 left it.  A half-step of all searches is ONE engine batch of
+ *     n_start x W / 2 slots;
+ *   - everything random is numpy.random.Philox(key=[seed, ids[s]]), the block bootstrap's counter convention.  Walker i of step t
+ *     owns block t W + i, four words w[0 ...]: w[0] gives the partner j, the w[0]-th walker of the other half (the high 64 bits of
+ *     raw x W / 2, no rejection); w[1] gives u_z and w[2] gives u_acc, each (raw >> 11) 2^-53.  (Blocks below W are never read.);
+ *   - the stretch z = ((a - 1) u_z + 1)^2 / a and the proposal y_k = x_j,k + z (x_i,k - x_j,k): every operation rounded on its own,
+ *     no fused multiply-add (a - 1 is rounded once).  A fixed coordinate is lo exactly.  A proposal with a coordinate outside
+ *     [lo, hi], or NaN, is rejected WITHOUT an evaluation: its batch slot carries a negative split and costs nothing;
+ *   - acceptance, with d = N_free - 1 and N_free the coordinates that are not fixed: a proposal without a value is rejected; a
+ *     walker without a value accepts any proposal that has one; otherwise g = z^d by d successive multiplications from 1.0,
+ *     e = (llk_new - llk_old) / T, p = g ens_exp(e), accepted iff u_acc < p;
+ *   - ens_exp is the project's own exponential (neither the C library's nor the device's exp is specified to the bit): 0 below -746,
+ *     +inf above 710, otherwise kd = (x INV_LN2 + 1.5 x 2^52) - 1.5 x 2^52 (the nearest integer), r = (x - kd LN2_HI) - kd LN2_LO,
+ *     the Taylor polynomial 1 + r + r^2 / 2 + ... + r^13 / 13! in Horner form (coefficients 1.0 / n!), and ldexp(., kd); INV_LN2 =
+ *     0x1.71547652b82fep+0, LN2_HI = 0x1.62e42feep-1, LN2_LO = 0x1.a39ef35793c76p-33.  Within 4 ulp of exp on [-745, 709];
+ *   - there is no stopping rule: every search runs n_step steps.  The ensemble after steps thin, 2 thin, ... is kept: n_keep =
+ *     n_step / thin rows of the chain.
+ * A search's result is a function of its own arguments alone: not of the other searches in the call, their number or order, the
+ * device or the launch geometry.  Ensembles, values, counters and the chain stay in HBM until one copy at the end; the host reads
+ * nothing back between steps.  Host buffers; synchronous.
+ *
+ * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this library's;
+ * a split mode that is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED; a negative n_start; a NULL pointer among init / rows /
+ * jsfs / box_lo / box_hi / temperature / last / last_llh (and split_times with MISTI_SPLIT_PER_START); n_rep < 1; walkers odd or
+ * < 4 (MISTI_E_LIMIT for walkers > MISTI_ENS_MAX_WALKERS); n_step < 0; thin < 1; a that is not finite or not > 1; n_temp neither 1
+ * nor n_start; a temperature that is not finite and positive; n_box neither 1 nor n_start; a row out of range; a non-finite split
+ * time; then a NULL context; a model without a coordinate to sample; MISTI_E_LIMIT for N > MISTI_MAX_PARAMS, n_start x walkers >
+ * INT32_MAX / 8 / (N + 1), n_rep > INT32_MAX, or a chain of more than INT32_MAX / 8 elements (n_start x n_keep x walkers x N, with a
+ * chain or chain_llh asked for); the box: a bound that is infinite or NaN, lo > hi, hi - lo not finite, or every coordinate fixed;
+ * a walker of init that is not finite or lies outside its box (the message names the search, the walker and the coordinate).
+ * n_start == 0 returns 0 once the arguments are accepted, and writes nothing; n_step == 0 evaluates the initial ensemble and returns
+ * it.  Points the engine refuses are no errors. */
+#define MISTI_ENS_MAX_WALKERS 256
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_ens_t) */
+    int32_t split;                   /* MISTI_SPLIT_PER_START or MISTI_SPLIT_FITTED */
+    const double* split_times;       /* MISTI_SPLIT_PER_START: [n_start], finite */
+    int64_t n_start;
+    const double* init;              /* [n_start][walkers][N]: the initial ensembles, every walker inside its box */
+    const int32_t* rows;             /* [n_start], 0 <= rows[s] < n_rep */
+    int64_t n_rep;
+    const double* jsfs;              /* [n_rep][8] */
+    const int32_t* band_bounds;      /* [n_start][n_band][2] or NULL; ignored when the model has no band */
+    const int32_t* pulse_times;      /* [n_start][n_pulse] or NULL; ignored when the model has no pulse */
+    int64_t n_box;                   /* 1: one box for every search; n_start: a box per search */
+    const double* box_lo;            /* [n_box][N] finite */
+    const double* box_hi;            /* [n_box][N] finite, >= box_lo */
+    int32_t walkers;                 /* W: even, 4 ... MISTI_ENS_MAX_WALKERS */
+    int32_t n_step;                  /* steps (two half-steps each) after the initial ensemble; 0 allowed */
+    int32_t thin;                    /* >= 1 */
+    int32_t n_temp;                  /* 1: one temperature for every search; n_start: one per search */
+    const double* temperature;       /* [n_temp] finite, > 0 */
+    double a;                        /* the stretch's scale: finite, > 1 (2 is Goodman & Weare's) */
+    uint64_t seed;
+    const uint64_t* ids;             /* [n_start] stream ids, or NULL: 0, 1, ... */
+    double* chain;                   /* [n_start][n_keep][walkers][N] or NULL: the ensembles after steps thin, 2 thin, ... */
+    double* chain_llh;               /* [n_start][n_keep][walkers] or NULL: their log-likelihoods (-inf: no value) */
+    int32_t* accepted;               /* [n_start][walkers] or NULL: proposals accepted per walker */
+    double* last;                    /* [n_start][walkers][N] the final ensemble: a later call continues from it (with other ids) */
+    double* last_llh;                /* [n_start][walkers] */
+    int64_t* n_points;               /* [1] or NULL: proposals the call handed the engine - every proposal inside its box; proposals
+                                      * rejected in advance are not counted, nor are the n_start x walkers initial evaluations */
+} misti_ens_t;
+int misti_ensemble_sample(misti_ctx* ctx, const misti_ens_t* sampler);
+/* What walker `walker` of step `step` of the stream (seed, id) draws in an ensemble of `walkers` walkers, its exponential, and its
+ * decision on an evaluated proposal (llk -inf or NaN: no value), on the host through the very functions the kernels call.  No
+ * context, no device.  MISTI_E_ARG for a negative step, walkers odd or < 4, a walker outside 0 ... walkers - 1, d outside 0 ...
+ * MISTI_MAX_PARAMS - 1, a temperature that is not finite and positive or a NULL pointer; MISTI_E_LIMIT for walkers >
+ * MISTI_ENS_MAX_WALKERS. */
+int misti_ens_draws(uint64_t seed, uint64_t id, int64_t step, int32_t walker, int32_t walkers, int32_t* partner, double* u_z, double* u_acc);
+int misti_ens_exp(double x, double* y);
+int misti_ens_accept(double z, int32_t d, double llk_old, double llk_new, double T, double u_acc, int32_t* accept);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

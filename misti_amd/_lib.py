@@ -82,6 +82,19 @@ class DeSearch(C.Structure):
                 ("n_points", C.c_void_p)]
 
 
+ENS_MAX_WALKERS = 256
+
+
+class EnsSample(C.Structure):
+    """``misti_ens_t``: ensemble MCMC per search; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("split", C.c_int32), ("split_times", C.c_void_p), ("n_start", C.c_int64), ("init", C.c_void_p),
+                ("rows", C.c_void_p), ("n_rep", C.c_int64), ("jsfs", C.c_void_p), ("band_bounds", C.c_void_p), ("pulse_times", C.c_void_p),
+                ("n_box", C.c_int64), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p), ("walkers", C.c_int32), ("n_step", C.c_int32),
+                ("thin", C.c_int32), ("n_temp", C.c_int32), ("temperature", C.c_void_p), ("a", C.c_double), ("seed", C.c_uint64),
+                ("ids", C.c_void_p), ("chain", C.c_void_p), ("chain_llh", C.c_void_p), ("accepted", C.c_void_p), ("last", C.c_void_p),
+                ("last_llh", C.c_void_p), ("n_points", C.c_void_p)]
+
+
 class MistiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmisti_hip error %d: %s" % (code, msg))
@@ -113,6 +126,10 @@ SYMBOLS = {
     "misti_de_search": (C.c_int, [C.c_void_p, C.POINTER(DeSearch)]),
     "misti_de_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_ensemble_sample": (C.c_int, [C.c_void_p, C.POINTER(EnsSample)]),
+    "misti_ens_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_ens_exp": (C.c_int, [C.c_double, C.c_void_p]),
+    "misti_ens_accept": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "misti_nm_solve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_nm_solve_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,

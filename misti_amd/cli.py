@@ -77,6 +77,22 @@ and the GNU-parallel recipe of ``README.md:110-115``):
     --de-F LO HI              with --de: the dither range of the differential weight (default 0.5 1)
     --de-CR C                 with --de: the crossover probability (default 0.7)
     --de-polish               with --de: one boxed Nelder-Mead call (misti_nm_solve_box, -tol) from the DE results; a search keeps the better
+    --mcmc W STEPS            after any fit of --fit-st or --grid-solve (local, --hops or --de): an ENSEMBLE MCMC of W walkers (even, 4 ... 256)
+                              over STEPS steps per printed fit, inside the box - one misti_ensemble_sample call over all fits, every
+                              half-step ONE dense engine batch.  The affine-invariant stretch move; the rule is this project's own
+                              (include/misti_hip.h states it).  Samples llh / T under a uniform prior on the box: needs a finite --box for
+                              EVERY coordinate (the split included under --fit-st).  The initial ensemble is drawn around each fit
+                              (--mcmc-spread) - or, where --de W GENS ran with the same W, it is DE's final population.  Behind every fit line one `mcmc:` line per coordinate: mean, median, 2.5 % and 97.5 %
+                              quantiles, the autocorrelation time of the ensemble mean and the acceptance fraction; `(short)` where
+                              fewer than 50 autocorrelation times were kept.  Not offered with --se, --sweep, --sweep-pu, --gpus N > 1
+                              or --devices
+    --mcmc-burn B             with --mcmc: kept steps dropped before the summary (default: half of them)
+    --mcmc-thin K             with --mcmc: keep every K-th step (default 1)
+    --mcmc-seed K             with --mcmc: every random number is numpy.random.Philox(key=[K, j]), j the fit's index within its row (default 0)
+    --mcmc-spread S           with --mcmc: the initial walkers are the fit + S x (box width) x uniform(-1, 1), clipped (default 1e-2)
+    --mcmc-temp T|auto        with --mcmc: the temperature (default 1).  auto: trace(H^-1 J) / p from the curvature at the data row's fit and
+                              the bootstrap rows' class counts - the magnitude adjustment of a composite likelihood; needs --all-bs
+    --mcmc-out FILE.npz       with --mcmc: the chains, their llh, the acceptance counters and the final ensembles
     --box K LO HI             with --grid-solve, --fit-st or --polish, with or without --hops; repeatable: every search runs inside a box -
                               SciPy's Nelder-Mead with bounds= (misti_nm_solve_box / misti_basinhopping_box): LO <= parameter K <= HI, K the
                               index of an optimised parameter as --grid-mi K names it, or `st` for the fitted split of --fit-st.  inf and
@@ -213,6 +229,15 @@ def build_parser():
     p.add_argument("--de-F", nargs=2, type=float, default=None, metavar=("LO", "HI"), dest="de_F", help="with --de: dither range of the differential weight (default 0.5 1)")
     p.add_argument("--de-CR", type=float, default=None, metavar="C", dest="de_CR", help="with --de: crossover probability (default 0.7)")
     p.add_argument("--de-polish", action="store_true", help="with --de: one boxed Nelder-Mead call from the DE results; a search keeps the better result")
+    p.add_argument("--mcmc", nargs=2, type=int, default=None, metavar=("W", "STEPS"),
+                   help="with --fit-st / --grid-solve: after the fit, an ensemble MCMC of W walkers over STEPS steps per printed fit inside the "
+                        "--box of every coordinate (the affine-invariant stretch move; the project's own rule)")
+    p.add_argument("--mcmc-burn", type=int, default=None, metavar="B", help="with --mcmc: kept steps dropped before the summary (default: half)")
+    p.add_argument("--mcmc-thin", type=int, default=None, metavar="K", help="with --mcmc: keep every K-th step (default 1)")
+    p.add_argument("--mcmc-seed", type=int, default=None, metavar="K", help="with --mcmc: seed of the ensembles' Philox streams (default 0)")
+    p.add_argument("--mcmc-spread", type=float, default=None, metavar="S", help="with --mcmc: spread of the initial ensemble in box widths (default 1e-2)")
+    p.add_argument("--mcmc-temp", default=None, metavar="T|auto", help="with --mcmc: the temperature (default 1), or auto: trace(H^-1 J) / p (needs --all-bs)")
+    p.add_argument("--mcmc-out", default=None, metavar="FILE.npz", help="with --mcmc: write chains, values, acceptance counters and final ensembles")
     p.add_argument("--box", nargs=3, action="append", default=[], metavar=("K", "LO", "HI"),
                    help="with --grid-solve / --fit-st / --polish: keep optimised parameter K (or `st`: the fitted split of --fit-st) within [LO, HI] "
                         "in every search (SciPy's bounds=; inf / -inf accepted); repeatable")
@@ -528,6 +553,122 @@ def de_error(a):
         if not all(np.isfinite(v) for v in boxed[name]):
             return "--de needs a finite box: --box %s has an infinite bound" % name
     return None
+
+
+def mcmc_error(a):
+    """Why ``--mcmc`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.mcmc is None:
+        if any(v is not None for v in (a.mcmc_burn, a.mcmc_thin, a.mcmc_seed, a.mcmc_spread, a.mcmc_temp, a.mcmc_out)):
+            return "--mcmc-burn / --mcmc-thin / --mcmc-seed / --mcmc-spread / --mcmc-temp / --mcmc-out set the sampler of --mcmc W STEPS: give --mcmc W STEPS"
+        return None
+    W, steps = a.mcmc
+    if not 4 <= W <= 256 or W % 2:
+        return "--mcmc W STEPS: W must be even, 4 ... 256 (got %d)" % W
+    if steps < 1:
+        return "--mcmc W STEPS: STEPS must be at least 1 (got %d)" % steps
+    if not (a.fit_st or a.grid_solve):
+        return "--mcmc samples around the fits of --fit-st or --grid-solve: give one of them"
+    if a.se:
+        return "--se and --mcmc are two answers to one question: give one of them (--mcmc-temp auto takes the curvature itself)"
+    if a.sweep or a.sweep_pu:
+        return "--mcmc samples ONE model: --sweep / --sweep-pu are not offered with it"
+    if a.gpus > 1 or a.devices:
+        return "--mcmc runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    thin = 1 if a.mcmc_thin is None else a.mcmc_thin
+    if thin < 1 or steps // thin < 1:
+        return "--mcmc-thin K: 1 <= K <= STEPS (got %d)" % thin
+    if a.mcmc_burn is not None and not 0 <= a.mcmc_burn < steps // thin:
+        return "--mcmc-burn B: 0 <= B < %d kept steps (got %d)" % (steps // thin, a.mcmc_burn)
+    if a.mcmc_seed is not None and not 0 <= a.mcmc_seed < 2 ** 64:
+        return "--mcmc-seed must be a uint64 (got %d)" % a.mcmc_seed
+    if a.mcmc_spread is not None and not (np.isfinite(a.mcmc_spread) and a.mcmc_spread >= 0):
+        return "--mcmc-spread must be finite and not negative (got %g)" % a.mcmc_spread
+    if a.mcmc_temp is not None and a.mcmc_temp != "auto":
+        try:
+            T = float(a.mcmc_temp)
+        except ValueError:
+            T = float("nan")
+        if not (np.isfinite(T) and T > 0):
+            return "--mcmc-temp T|auto: a finite temperature > 0, or auto (got %s)" % a.mcmc_temp
+    if a.mcmc_temp == "auto" and not a.all_bs:
+        return "--mcmc-temp auto takes the score covariance from the bootstrap rows: it needs --all-bs"
+    k = sum(1 for el in a.mi if int(el[4])) + sum(1 for el in a.pu if int(el[3]))
+    boxed = {}
+    for name, lo, hi in a.box:
+        try:
+            boxed[name] = (float(lo), float(hi))
+        except ValueError:
+            return None                                   # box_error names it
+    for name in [str(i) for i in range(k)] + (["st"] if a.fit_st else []):
+        if name not in boxed:
+            return "--mcmc samples a uniform prior on a box: coordinate %s has no --box %s LO HI" % (name, name)
+        if not all(np.isfinite(v) for v in boxed[name]):
+            return "--mcmc needs a finite box: --box %s has an infinite bound" % name
+    return None
+
+
+def _mcmc_from_de(a):
+    """--de W GENS ran with the sampler's W: the initial ensembles are DE's final populations."""
+    return bool(a.mcmc and a.de and a.de[0] == a.mcmc[0])
+
+
+def _mcmc_options(a):
+    """The options of --mcmc, or their defaults: burn half the kept steps, thin 1, seed 0, spread 1e-2, temperature 1."""
+    thin = 1 if a.mcmc_thin is None else a.mcmc_thin
+    return dict(walkers=a.mcmc[0], n_step=a.mcmc[1], thin=thin, burn=(a.mcmc[1] // thin) // 2 if a.mcmc_burn is None else a.mcmc_burn,
+                seed=0 if a.mcmc_seed is None else a.mcmc_seed, spread=1e-2 if a.mcmc_spread is None else a.mcmc_spread,
+                temperature="auto" if a.mcmc_temp == "auto" else 1.0 if a.mcmc_temp is None else float(a.mcmc_temp))
+
+
+def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=None):
+    """--mcmc behind the fits ``x[S][N]`` (fit s: row ``r_of[s]``, stream ``j_of[s]``; ``split_times[S]``, or None with the split as the
+    last coordinate): ONE Engine.ensemble_sample call from ensemble_start around every fit (a fit without a value: the middle of the
+    box) - or, with ``population[S][W][N]`` (``--de W GENS`` ran with the sampler's W), from DE's final populations: dispersed,
+    inside the box and already evaluated.  Returns (options, temperature, result) - or a string: why --mcmc-temp auto has no temperature."""
+    from .optimize import composite_temperature, ensemble_start, score_covariance
+    o = _mcmc_options(a)
+    lo, hi = box
+    x = np.where(np.isfinite(x), np.clip(x, lo, hi), 0.5 * (lo + hi))
+    T = o["temperature"]
+    if T == "auto":
+        P = e.n_param
+        if not P:
+            return "--mcmc-temp auto: the model has no optimised parameter, so no curvature"
+        if data.shape[0] < 3:
+            return "--mcmc-temp auto: the score covariance needs at least two bootstrap rows behind the data row"
+        first = int(np.flatnonzero(np.asarray(r_of) == 0)[0])
+        cur = e.curvature(x[first:first + 1, :P], [float(split_times[first]) if split_times is not None else float(x[first, -1])], [0], data)
+        if cur.status[0] != 0:
+            return "--mcmc-temp auto: no curvature at the data row's fit (status %d)" % int(cur.status[0])
+        try:
+            T = composite_temperature(cur.hess[0], score_covariance(cur.dlog, data, unfolded=unfolded)[0])
+        except ValueError as why:
+            return "--mcmc-temp auto: %s" % why
+    if population is not None:
+        init = np.ascontiguousarray(population, dtype=np.float64).reshape(x.shape[0], o["walkers"], x.shape[1])
+    else:
+        init = np.stack([ensemble_start(x[s], lo, hi, o["walkers"], o["spread"], o["seed"], int(j_of[s])) for s in range(x.shape[0])])
+    o["start"] = "DE's final population" if population is not None else "spread %g around the fit" % o["spread"]
+    res = e.ensemble_sample(init, np.asarray(r_of, dtype=np.int32), data, box, split_times=split_times, fit_split=split_times is None,
+                            n_step=o["n_step"], thin=o["thin"], temperature=T, seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
+    if a.mcmc_out:
+        np.savez(a.mcmc_out, chain=res["chain"], chain_llh=res["chain_llh"], accepted=res["accepted"], last=res["last"], last_llh=res["last_llh"],
+                 row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T))
+    return o, float(T), res
+
+
+def print_mcmc(label, o, res, s):
+    """The ``mcmc:`` lines of fit s: one per coordinate, from ensemble_summary of its chain."""
+    from .optimize import ensemble_summary
+    m = ensemble_summary(res["chain"][s], o["burn"], accepted=res["accepted"][s], n_step=o["n_step"])
+    for c in range(res["chain"].shape[3]):
+        print("mcmc:", label, "\tcoordinate %d" % c, "\tmean =", m["mean"][c], "\tmedian =", m["median"][c], "\t2.5% =", m["q025"][c], "\t97.5% =", m["q975"][c],
+              "\ttau =", m["tau"][c], "\taccepted =", m["acceptance"], *(["\t(short)"] if m["short"][c] else []))
+
+
+def _mcmc_text(o, T, res, dt):
+    return "ensemble MCMC with %d walkers, %d steps, thin %d, burn %d, from %s, temperature %r, seed %d: %d ensembles in one call, %.3f s, %d proposals evaluated" % (
+        o["walkers"], o["n_step"], o["thin"], o["burn"], o["start"], T, o["seed"], res["chain"].shape[0], dt, res["n_points"])
 
 
 def _de_options(a):
@@ -910,7 +1051,7 @@ def grid_solve(a, inp, rows):
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
         if a.de:
-            prof = bootstrap_profile_de(e, splits, data, starts[0], _box(a, k), polish_tol=a.tol, **_de_options(a))
+            prof = bootstrap_profile_de(e, splits, data, starts[0], _box(a, k), polish_tol=a.tol, return_population=_mcmc_from_de(a), **_de_options(a))
         elif a.hops:
             prof = bootstrap_profile_global(e, splits, data, starts, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
@@ -920,11 +1061,24 @@ def grid_solve(a, inp, rows):
             R_, P_ = data.shape[0], len(splits)
             cur = e.curvature(prof["x"].reshape(R_ * P_, k), np.tile(np.asarray(splits, dtype=float), R_), np.repeat(np.arange(R_), P_), data,
                               rel_step=_se_step(a))
-    dt = time.time() - t0
+        mc, dt_mc = None, 0.0
+        if a.mcmc:
+            # one ensemble per printed fit: row outermost, split innermost, as the lines; the stream of a fit is its split's index
+            t1 = time.time()
+            R_, P_ = data.shape[0], len(splits)
+            mc = run_mcmc(a, e, prof["x"].reshape(R_ * P_, k), np.repeat(np.arange(R_), P_), np.tile(np.arange(P_), R_), data, _box(a, k),
+                          np.tile(np.asarray(splits, dtype=float), R_), a.uf, prof["population"] if _mcmc_from_de(a) else None)
+            if isinstance(mc, str):
+                print(mc, file=sys.stderr)
+                return 2
+            dt_mc = time.time() - t1
+    dt = time.time() - t0 - dt_mc
     for r in range(data.shape[0]):
         for p, st in enumerate(splits):
             print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, prof["x"][r, p], prof["llh"][r, p])
                   + (_hops_text(prof, r, p) if a.hops else ""))
+            if mc:
+                print_mcmc("bs_id = %s \tsplitT = %s" % (ids[r], st), mc[0], mc[2], r * len(splits) + p)
     if a.se:
         print()
         print_se(["bs_id = %s \tsplitT = %s" % (ids[r], st) for r in range(data.shape[0]) for st in splits], cur,
@@ -950,6 +1104,8 @@ def grid_solve(a, inp, rows):
     n = prof["llh"].size
     if a.box:
         print("grid-solve:", _box_text(a))
+    if mc:
+        print("grid-solve:", _mcmc_text(mc[0], mc[1], mc[2], dt_mc))
     if a.de:
         print("grid-solve:", _de_text(_de_options(a)))
         print("grid-solve: %d pairs in one population search, %.3f s, %d points; %d pairs ended on the generation cap, %d without a value"
@@ -977,12 +1133,23 @@ def fit_st(a, inp, rows):
     t0 = time.time()
     with Engine(inp.times, inp.lambdas, bands, pulses, n_param=k, sample_date=inp.sampleDateDiscr, mixture_th=a.mth, device=a.device, **flags) as e:
         if a.de:
-            fit = split_fit_de(e, data, np.append(starts[0], splits[0]), _box(a, k), polish_tol=a.tol, **_de_options(a))
+            fit = split_fit_de(e, data, np.append(starts[0], splits[0]), _box(a, k), polish_tol=a.tol, return_population=_mcmc_from_de(a), **_de_options(a))
         elif a.hops:
             fit = split_fit_global(e, data, starts, splits, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
             fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000, box=_box(a, k))
-    dt = time.time() - t0
+        mc, dt_mc = None, 0.0
+        if a.mcmc:
+            # one ensemble per row over (optimised parameters, split); the rows of a bootstrap share stream 0
+            t1 = time.time()
+            R_ = data.shape[0]
+            mc = run_mcmc(a, e, np.hstack([fit["x"][:, :k], np.asarray(fit["split"], dtype=float)[:, None]]), np.arange(R_), np.zeros(R_, dtype=int),
+                          data, _box(a, k), None, a.uf, fit["population"] if _mcmc_from_de(a) else None)
+            if isinstance(mc, str):
+                print(mc, file=sys.stderr)
+                return 2
+            dt_mc = time.time() - t1
+    dt = time.time() - t0 - dt_mc
     for r in range(data.shape[0]):
         st = float(fit["split"][r])
         if not np.isfinite(fit["llh"][r]):
@@ -990,6 +1157,8 @@ def fit_st(a, inp, rows):
             continue
         print(result_line(ids[r], st, split_grid_times(inp.times, st), inp.scaleTime, a.mi, fit["x"][r, :k], fit["llh"][r])
               + (_hops_text(fit, r) if a.hops else ""))
+        if mc:
+            print_mcmc("bs_id = %s \tsplitT = %s" % (ids[r], st), mc[0], mc[2], r)
     print()
     if a.jackknife is not None:
         has = np.isfinite(fit["llh"]) & np.isfinite(fit["split"])
@@ -1004,6 +1173,8 @@ def fit_st(a, inp, rows):
                   "over %d replicates (%d without a value excluded)" % (iv["n_boot"], iv["n_excluded"]))
     if a.box:
         print("fit-st:", _box_text(a))
+    if mc:
+        print("fit-st:", _mcmc_text(mc[0], mc[1], mc[2], dt_mc))
     if a.de:
         print("fit-st:", _de_text(_de_options(a)))
         print("fit-st: %d rows in one population search, %.3f s, %d points; %d rows ended on the generation cap, %d without a value"
@@ -1142,7 +1313,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or de_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
+    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or de_error(a) or mcmc_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2

@@ -1694,9 +1694,175 @@ int de_run(misti_ctx* c, const misti_de_t& q, int N, bool whole) {
     return 0;
 }
 
+// ---- ensemble MCMC per search (misti_ens.hip) ------------------------------------------------------------------------------------
+// The arguments of misti_ensemble_sample, before the first HIP call, in the header's order.  Leaves the number of coordinates in N
+// and whether every split time is an integer in `whole`.
+int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
+    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
+    if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
+    if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.temperature || !q.last || !q.last_llh || (per_start && !q.split_times))
+        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / temperature / last / last_llh%s is NULL", per_start ? " / split_times" : "");
+    if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
+    if (q.walkers < 4 || (q.walkers & 1)) return fail(MISTI_E_ARG, "walkers must be even and >= 4 (got %d)", (int)q.walkers);
+    if (q.walkers > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "walkers = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)q.walkers, MISTI_ENS_MAX_WALKERS);
+    if (q.n_step < 0) return fail(MISTI_E_ARG, "n_step must not be negative");
+    if (q.thin < 1) return fail(MISTI_E_ARG, "thin must be >= 1");
+    if (!std::isfinite(q.a) || !(q.a > 1.0)) return fail(MISTI_E_ARG, "a must be finite and > 1 (got %g)", q.a);
+    if (q.n_temp != 1 && q.n_temp != q.n_start) return fail(MISTI_E_ARG, "n_temp must be 1 or n_start (got %d for %lld searches)", (int)q.n_temp, (long long)q.n_start);
+    for (int64_t s = 0; s < q.n_temp; ++s)
+        if (!std::isfinite(q.temperature[s]) || !(q.temperature[s] > 0.0))
+            return fail(MISTI_E_ARG, "temperature[%lld] = %g is not finite and positive", (long long)s, q.temperature[s]);
+    if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld searches)", (long long)q.n_box, (long long)q.n_start);
+    whole = per_start;
+    for (int64_t s = 0; s < q.n_start; ++s) {
+        if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
+        if (!per_start) continue;
+        if (!std::isfinite(q.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+        if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
+    }
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    N = c->dm.n_param + (fit_split ? 1 : 0);
+    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
+    if (q.n_start > INT32_MAX / 8 / (N + 1) / q.walkers) return fail(MISTI_E_LIMIT, "too many searches x walkers for one call");
+    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
+    if ((q.chain || q.chain_llh) && q.n_start > 0 && (int64_t)(q.n_step / q.thin) > INT32_MAX / 8 / N / q.walkers / q.n_start)
+        return fail(MISTI_E_LIMIT, "the chain of %lld searches x %d kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
+                    (long long)q.n_start, (int)(q.n_step / q.thin), (int)q.walkers, N);
+    for (int64_t b = 0; b < q.n_box; ++b) {
+        int n_free = 0;
+        for (int k = 0; k < N; ++k) {
+            const double lo = q.box_lo[b * N + k], hi = q.box_hi[b * N + k];
+            if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is not finite (the sampler's prior is uniform on a finite box)", (long long)b, k);
+            if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
+            if (!std::isfinite(hi - lo)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: hi - lo is not finite", (long long)b, k);
+            n_free += lo != hi ? 1 : 0;
+        }
+        if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
+    }
+    for (int64_t s = 0; s < q.n_start; ++s)
+        for (int i = 0; i < q.walkers; ++i)
+            for (int k = 0; k < N; ++k) {
+                const double v = q.init[(s * q.walkers + i) * N + k];
+                const int64_t o = (q.n_box > 1 ? s : 0) * N + k;
+                if (!std::isfinite(v)) return fail(MISTI_E_ARG, "init[%lld][%d][%d] is not finite", (long long)s, i, k);
+                if (v < q.box_lo[o] || v > q.box_hi[o])
+                    return fail(MISTI_E_ARG, "init[%lld][%d][%d] = %g is outside its box [%g, %g]", (long long)s, i, k, v, q.box_lo[o], q.box_hi[o]);
+            }
+    return 0;
+}
+
+// A checked call with n_start >= 1.  One batch record of n_start x walkers slots serves the initial ensemble and every half-step
+// (which fills the first half of it); the state and the chain lie in the search buffers of the context.  Nothing is read back before
+// the end.
+int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole) {
+    using namespace misti;
+    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, R = (size_t)q.n_rep;
+    const size_t NB2 = q.band_bounds ? 2 * (size_t)c->dm.n_band : 0, NP = q.pulse_times ? (size_t)c->dm.n_pulse : 0;
+    const size_t NQ = fit_split ? (size_t)N - 1 : 0, NX = (size_t)q.n_box * (size_t)N, NT = (size_t)q.n_temp;
+    const size_t K = (q.chain || q.chain_llh) ? (size_t)(q.n_step / q.thin) : 0;
+    EnsState st{};
+    st.S = q.n_start; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
+    st.temp_per_start = q.n_temp > 1 ? 1 : 0;
+    st.fit_split = fit_split ? 1 : 0; st.nb2 = (int)NB2; st.np = (int)NP; st.box_per_start = q.n_box > 1 ? 1 : 0;
+    st.n_keep = (int64_t)K;
+    double *llk = nullptr, *d_init = nullptr, *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr, *rjafs = nullptr;
+    double *d_lo = nullptr, *d_hi = nullptr, *d_temp = nullptr, *d_ids = nullptr, *d_points = nullptr;
+    int32_t *rstatus = nullptr, *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
+    auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        st.b.pts = f.take(M * N); st.x = f.take(M * N); st.llh = f.take(M); st.b.split = f.take(M); llk = f.take(M);
+        st.z = f.take(S * H); st.u_acc = f.take(S * H);
+        if (NQ) st.b.par = f.take(M * NQ);
+        d_init = f.take(M * N);
+        if (per_start) d_split = f.take(S);
+        d_table = f.take(R * 8); d_consts = f.take(R); rjafs = f.take(M * 7);
+        d_lo = f.take(NX); d_hi = f.take(NX); d_temp = f.take(NT);
+        if (q.ids) d_ids = f.take(S);                      // uint64 ids and the point counters: 8-byte words of the double buffer
+        d_points = f.take(S);                              // int64 per search
+        if (K) { st.chain = f.take(S * K * W * (size_t)N); st.chain_llh = f.take(S * K * W); }
+        st.b.row = i.take(M); rstatus = i.take(M); d_rowof = i.take(S);
+        if (NB2) { d_bounds = i.take(S * NB2); st.b.bnd = i.take(M * NB2); }
+        if (NP) { d_pulses = i.take(S * NP); st.b.put = i.take(M * NP); }
+        st.accepted = i.take(M); st.submitted = i.take(M);
+    };
+    Carver<double> f;
+    Carver<int32_t> i;
+    layout(f, i);
+    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
+    HIP_TRY(c->nm_i32.reserve(i.n * sizeof(int32_t)));
+    f = Carver<double>{c->nm_f64.as<double>()};
+    i = Carver<int32_t>{c->nm_i32.as<int32_t>()};
+    layout(f, i);
+    st.split_of = d_split; st.row_of = d_rowof; st.bounds_of = d_bounds; st.pulses_of = d_pulses;
+    st.box_lo = d_lo; st.box_hi = d_hi; st.temp = d_temp;
+    st.ids = reinterpret_cast<const uint64_t*>(d_ids);
+    st.points = reinterpret_cast<long long*>(d_points);
+    hipStream_t sm = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_init, q.init, M * N * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (per_start) HIP_TRY(hipMemcpyAsync(d_split, q.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_lo, q.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_hi, q.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_temp, q.temperature, NT * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (q.ids) HIP_TRY(hipMemcpyAsync(d_ids, q.ids, S * sizeof(uint64_t), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));
+    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
+    // the rows path's hints (nm_run): integer splits where the caller's are; a fitted split is never known to be whole
+    const unsigned hints = whole ? RUN_INTEGER_SPLITS : 0u;
+    auto eval = [&](int64_t n) { return eval_rows(c, st.b, n, fit_split ? st.b.par : st.b.pts, hints, rjafs, rstatus, d_table, d_consts, llk); };
+    HIP_TRY(launch_ens_init(st, d_init, sm));
+    if (int r = eval((int64_t)M)) return r;
+    HIP_TRY(launch_ens_accept(st, 0, -1, llk, sm));
+    for (int64_t step = 1; step <= q.n_step; ++step)
+        for (int half = 0; half < 2; ++half) {
+            HIP_TRY(launch_ens_propose(st, step, half, sm));
+            if (int r = eval((int64_t)(S * H))) return r;
+            HIP_TRY(launch_ens_accept(st, step, half, llk, sm));
+        }
+    c->nm_iterations = 2 * (int64_t)q.n_step;
+    c->nm_slots = 2 * (int64_t)q.n_step * (int64_t)(S * H);
+    HIP_TRY(launch_ens_result(st, sm));
+    HIP_TRY(hipMemcpyAsync(q.last, st.x, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(q.last_llh, st.llh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.accepted) HIP_TRY(hipMemcpyAsync(q.accepted, st.accepted, M * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.chain && K) HIP_TRY(hipMemcpyAsync(q.chain, st.chain, S * K * W * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.chain_llh && K) HIP_TRY(hipMemcpyAsync(q.chain_llh, st.chain_llh, S * K * W * sizeof(double), hipMemcpyDeviceToHost, sm));
+    std::vector<int64_t> per_search;
+    if (q.n_points) {
+        per_search.resize(S);
+        HIP_TRY(hipMemcpyAsync(per_search.data(), d_points, S * sizeof(int64_t), hipMemcpyDeviceToHost, sm));
+    }
+    HIP_TRY(hipStreamSynchronize(sm));
+    if (q.n_points) {
+        int64_t n = 0;
+        for (int64_t v : per_search) n += v;
+        *q.n_points = n;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) {
+    if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
+    if (q->size != sizeof(misti_ens_t))
+        return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_ens_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_ens_t));
+    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
+        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
+    int N = 0;
+    bool whole = false;
+    if (int r = ens_check(c, *q, N, whole)) return r;
+    if (q->n_start == 0) return 0;
+    return ens_run(c, *q, N, whole);
+}
 
 int misti_de_search(misti_ctx* c, const misti_de_t* q) {
     if (!q) return fail(MISTI_E_ARG, "the search descriptor is NULL");

@@ -259,6 +259,49 @@ hipError_t launch_de_select(const DeState& st, int64_t bound, int gen, const dou
 // x[S][N], llh[S], nit / nfev / status[S]; pop_llh[S][P] (or NULL): -f
 hipError_t launch_de_result(const DeState& st, double* x, double* llh, int32_t* nfev, int32_t* status, double* pop_llh, hipStream_t stream);
 
+// Ensemble sampler per search (misti_ens.hip; the rule is optimize.ensemble_rule, operation for operation): everything a search
+// owns, in HBM.  A half-step of every search is ONE engine batch of H = W / 2 points per search; batch slot s * H + m carries the
+// proposal of walker half * H + m of search s (the initial ensemble: slot s * W + i, walker i).  No search ever stops, so slots are
+// never compacted.  What a search hands its points are NmState's fields of the same names, and the batch is an NmBatch.
+struct EnsState {
+    int64_t S;              // searches
+    int N, W;               // coordinates, walkers (even)
+    int thin;               // the ensemble after steps thin, 2 thin, ... is kept
+    double a, am1;          // the stretch's scale and a - 1 as rounded once
+    uint64_t seed;
+    const uint64_t* ids;    // [S] or NULL: the stream of search s is Philox(key=[seed, ids[s]]); NULL: ids[s] = s
+    const double* temp;     // [1], or [S] with temp_per_start
+    int temp_per_start;
+    const double* split_of; // [S] or NULL (fit_split)
+    const int32_t* row_of;  // [S]
+    const int32_t* bounds_of;   // [S][nb2] or NULL
+    int nb2;
+    const int32_t* pulses_of;   // [S][np] or NULL
+    int np;
+    int fit_split;          // 1: the last coordinate is the point's split time, the N - 1 before it go to the batch's compact `par`
+    const double* box_lo;   // [N], or [S][N] with box_per_start: finite, lo <= hi
+    const double* box_hi;
+    int box_per_start;
+    double* x;              // [S][W][N] the ensemble
+    double* llh;            // [S][W]    its log-likelihood (-inf where the engine has no value)
+    double* z;              // [S * H]   the stretch of the slot's proposal; negative: rejected in advance, the slot carries no point
+    double* u_acc;          // [S * H]   the decision's uniform
+    int32_t* accepted;      // [S][W]    proposals accepted, per walker: plain stores by the walker's own thread
+    int32_t* submitted;     // [S][W]    proposals of the walker handed to the engine (those rejected in advance are not)
+    NmBatch b;              // [S * W] slots
+    double* chain;          // [S][n_keep][W][N] or NULL
+    double* chain_llh;      // [S][n_keep][W] or NULL
+    int64_t n_keep;
+    long long* points;      // [S] the sum of `submitted` over the walkers of a search (ens_result_kernel); the host adds the searches
+};
+hipError_t launch_ens_init(const EnsState& st, const double* init, hipStream_t stream);
+// proposals of half `half` (0, 1) of step `step` (>= 1)
+hipError_t launch_ens_propose(const EnsState& st, int64_t step, int half, hipStream_t stream);
+// values are in.  half < 0: the initial ensemble's; otherwise the decisions of that half-step, and behind half 1 of a kept step the
+// ensemble's row of the chain
+hipError_t launch_ens_accept(const EnsState& st, int64_t step, int half, const double* llk, hipStream_t stream);
+hipError_t launch_ens_result(const EnsState& st, hipStream_t stream);
+
 // Replicate epilogue fused into the spectrum kernel up to this many replicates (one launch less per batch).
 constexpr int LLK_INLINE_MAX = 8;
 

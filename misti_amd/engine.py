@@ -705,6 +705,50 @@ class Engine:
             out.update(population=popx, population_llh=popl)
         return out
 
+    def ensemble_sample(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
+                        thin=1, temperature=1.0, a=2.0, seed=0, ids=None):
+        """``misti_ensemble_sample``: ensemble MCMC per search - search s is an ensemble of W walkers ``init[s]`` (``[S][W][N]``, W even,
+        every walker inside its box) against ``table[rows[s]]`` (``[n_rep][8]``), sampling ``llk / temperature`` under a uniform prior on
+        its finite ``box`` (``(lo, hi)``, each ``[N]`` or ``[S][N]``; ``lo == hi`` holds a coordinate fixed); every half-step of all
+        searches is ONE engine batch.  The stretch move of Goodman & Weare with scale ``a``; the rule is the project's own
+        (``optimize.ensemble_rule`` states it; the result equals it bit for bit).  Exactly one of ``split_times`` (``[S]``, N =
+        ``n_param``) and ``fit_split=True`` (the split is the LAST coordinate).  ``temperature``: a scalar or ``[S]``.  Everything random
+        is ``numpy.random.Philox(key=[seed, ids[s]])`` (``ids`` default ``0 ... S - 1``): a search's result depends on its own arguments
+        alone; a later call continues from ``last`` with other ids.  ``band_bounds`` / ``pulse_times`` per search as in ``nm_solve_pulses``.
+        Returns dict(chain[S][n_keep][W][N], chain_llh[S][n_keep][W] (the ensembles after steps thin, 2 thin, ...), accepted[S][W],
+        last[S][W][N], last_llh[S][W], n_points (proposals the call handed the engine; those that leave the box are rejected without an
+        evaluation and not counted, nor are the S W initial evaluations))."""
+        if (split_times is None) != bool(fit_split):
+            raise ValueError("ensemble_sample: give exactly one of split_times and fit_split=True")
+        N = self.n_param + (1 if fit_split else 0)
+        x0 = _f64(init)
+        if x0.ndim != 3 or x0.shape[2] != N:
+            raise ValueError("ensemble_sample: init must be [S][W][%d] (got %s)" % (N, x0.shape))
+        S, W = x0.shape[0], x0.shape[1]
+        n_step, thin = int(n_step), int(thin)
+        ptr = lambda v: v.ctypes.data if v is not None else None
+        i32 = lambda v, shape: np.ascontiguousarray(np.asarray(v).reshape(shape), dtype=np.int32)
+        tab = _f64(table, (-1, 8))
+        sp = _f64(split_times, (S,)) if split_times is not None else None
+        r_of = i32(rows, (S,))
+        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
+        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
+        lo, hi = _box_arrays(box, N)
+        T = _f64(temperature).reshape(-1)
+        id_ = np.ascontiguousarray(np.asarray(ids).reshape(S), dtype=np.uint64) if ids is not None else None
+        K = n_step // thin if thin >= 1 and n_step >= 0 else 0
+        chain, chain_llh = np.empty((S, K, W, N)), np.empty((S, K, W))
+        accepted = np.zeros((S, W), dtype=np.int32)
+        last, last_llh = np.empty((S, W, N)), np.empty((S, W))
+        n_points = np.zeros(1, dtype=np.int64)
+        q = _lib.EnsSample(size=C.sizeof(_lib.EnsSample), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, split_times=ptr(sp),
+                           n_start=S, init=ptr(x0), rows=ptr(r_of), n_rep=tab.shape[0], jsfs=ptr(tab), band_bounds=ptr(bb), pulse_times=ptr(pt),
+                           n_box=lo.shape[0], box_lo=ptr(lo), box_hi=ptr(hi), walkers=W, n_step=n_step, thin=thin, n_temp=T.size,
+                           temperature=ptr(T), a=float(a), seed=int(seed), ids=ptr(id_), chain=ptr(chain), chain_llh=ptr(chain_llh),
+                           accepted=ptr(accepted), last=ptr(last), last_llh=ptr(last_llh), n_points=ptr(n_points))
+        _lib.check(self._lib.misti_ensemble_sample(self._ctx, C.byref(q)))
+        return dict(chain=chain, chain_llh=chain_llh, accepted=accepted, last=last, last_llh=last_llh, n_points=int(n_points[0]))
+
     def enable_solver_trace(self, on=True):
         """Record, for the following batches, SciPy-comparable solver statistics per candidate and interval
         (``misti_enable_solver_trace``; see ``solver_trace``)."""

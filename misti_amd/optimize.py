@@ -1410,13 +1410,15 @@ def _de_profile(R, n_per_row, search, polish):
 
 
 def bootstrap_profile_de(engine, split_values, jsfs_rows, start, box, pop=16, maxiter=50, tol=0.01, atol=0.0, F=(0.5, 1.0), CR=0.7, seed=0,
-                         polish=False, polish_tol=1e-4, polish_maxiter=1000):
+                         polish=False, polish_tol=1e-4, polish_maxiter=1000, return_population=False):
     """``bootstrap_profile_global`` with differential evolution in place of basin hopping: per (row, split) pair ONE population search
     inside ``box`` (``(lo, hi)``, each ``[n_param]``, finite), all R x P searches in ONE ``misti_de_search`` call - every generation one
     dense engine batch, no inner minimisations.  ``start`` ``[n_param]`` is member 0 of every search.  The stream id of a search is its
     split's index, so a row's result does not depend on the other rows.  ``polish``: one ``nm_solve_box`` call from the DE results
     under the same box (the ``scan_polish`` pattern); a search keeps the better result.
-    Returns dict(x[R][P][N], llh[R][P], de_llh[R][P], nit / nfev / status[R][P] (the DE's), polished[R][P], n_points)."""
+    Returns dict(x[R][P][N], llh[R][P], de_llh[R][P], nit / nfev / status[R][P] (the DE's), polished[R][P], n_points) and, with
+    ``return_population``, the DE's final population[R][P][pop][N] and population_llh[R][P][pop] (an initial ensemble for
+    ``bootstrap_profile_mcmc``)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_values, dtype=float).reshape(-1)
     R, Q = rows.shape[0], splits.size
@@ -1426,19 +1428,20 @@ def bootstrap_profile_de(engine, split_values, jsfs_rows, start, box, pop=16, ma
         if polish_from is not None:
             return engine.nm_solve_box(polish_from, r_of, rows, box, split_times=splits[j_of], tol=polish_tol, maxiter=polish_maxiter)
         return engine.differential_evolution(np.repeat(x0, r_of.size, axis=0), r_of, rows, box, split_times=splits[j_of], pop=pop,
-                                             maxiter=maxiter, tol=tol, atol=atol, F=F, CR=CR, seed=seed, ids=ids)
+                                             maxiter=maxiter, tol=tol, atol=atol, F=F, CR=CR, seed=seed, ids=ids, return_population=return_population)
     out = _de_profile(R, Q, search, polish)
     return {k: (v.reshape(R, Q, *v.shape[1:]) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
 
 
 def split_fit_de(engine, jsfs_rows, start, box, band_bounds=None, pulse_times=None, pop=16, maxiter=50, tol=0.01, atol=0.0, F=(0.5, 1.0), CR=0.7,
-                 seed=0, polish=False, polish_tol=1e-4, polish_maxiter=1000):
+                 seed=0, polish=False, polish_tol=1e-4, polish_maxiter=1000, return_population=False):
     """``split_fit_global`` with differential evolution in place of basin hopping: per row ONE population search over (optimised
     parameters, split) inside ``box`` (``(lo, hi)``, each ``[n_param + 1]``, finite, the split last), all R searches in ONE
     ``misti_de_search`` call.  ``start`` ``[n_param + 1]`` is member 0 of every search; every row draws from stream 0 (the rows of a
     bootstrap share their random numbers - only the data differ).  ``band_bounds`` / ``pulse_times`` apply to every search.
     ``polish``: one ``nm_solve_box`` call from the DE results under the same box; a row keeps the better result.
-    Returns dict(x[R][n_param + 1], split[R], llh[R], de_llh[R], nit / nfev / status[R] (the DE's), polished[R], n_points);
+    Returns dict(x[R][n_param + 1], split[R], llh[R], de_llh[R], nit / nfev / status[R] (the DE's), polished[R], n_points) and, with
+    ``return_population``, the DE's final population[R][pop][n_param + 1] and population_llh[R][pop];
     ``split_fit_interval`` takes ``split`` and ``llh`` unchanged."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     R = rows.shape[0]
@@ -1450,7 +1453,275 @@ def split_fit_de(engine, jsfs_rows, start, box, band_bounds=None, pulse_times=No
         if polish_from is not None:
             return engine.nm_solve_box(polish_from, r_of, rows, box, tol=polish_tol, maxiter=polish_maxiter, **per)
         return engine.differential_evolution(np.repeat(x0, r_of.size, axis=0), r_of, rows, box, fit_split=True, pop=pop, maxiter=maxiter,
-                                             tol=tol, atol=atol, F=F, CR=CR, seed=seed, ids=ids, **per)
+                                             tol=tol, atol=atol, F=F, CR=CR, seed=seed, ids=ids, return_population=return_population, **per)
     out = _de_profile(R, 1, search, polish)
     out["split"] = out["x"][:, -1].copy()
     return out
+
+
+# --------------------------------------------------------------------------------------------------- ensemble MCMC ----
+# The rule of misti_ensemble_sample stated on the host (include/misti_hip.h, "ensemble MCMC per search"): the device result is this, bit
+# for bit, on the engine's own objective.  The affine-invariant ensemble sampler (Goodman & Weare's stretch move, the algorithm of
+# emcee); the rule is the project's own - emcee draws from a Mersenne Twister in an order that depends on the ensemble; here walker i
+# of step t owns block t W + i of a counter-based stream - and so is the exponential of the decision: neither numpy.exp nor the
+# device's exp is specified to the bit.
+ENS_MAX_WALKERS = 256
+_ENS_INV_LN2, _ENS_LN2_HI, _ENS_LN2_LO = float.fromhex("0x1.71547652b82fep+0"), float.fromhex("0x1.62e42feep-1"), float.fromhex("0x1.a39ef35793c76p-33")
+_ENS_ROUND = 6755399441055744.0                                     # 1.5 x 2^52: adding and subtracting it rounds to the nearest integer
+_ENS_COEF = [1.0, 1.0, 1.0 / 2, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320, 1.0 / 362880, 1.0 / 3628800, 1.0 / 39916800,
+             1.0 / 479001600, 1.0 / 6227020800.0]
+
+
+def ens_exp(x):
+    """The sampler's exponential (``misti_ens_exp``), from additions, multiplications, comparisons and one ``ldexp``, each rounded on
+    its own: ``kd`` the integer nearest to ``x / ln 2``, ``r = (x - kd LN2_HI) - kd LN2_LO`` (``kd LN2_HI`` is exact: the constant has
+    32 trailing zero bits), the Taylor polynomial of degree 13 in Horner form on ``|r| <= 0.35``, then ``ldexp(., kd)``.  0 below -746,
+    ``+inf`` above 710, NaN for NaN.  Within 4 ulp of the exponential on [-745, 709] (measured: DESIGN.md)."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        kd = (x * _ENS_INV_LN2 + _ENS_ROUND) - _ENS_ROUND
+        r = x - kd * _ENS_LN2_HI
+        r = r - kd * _ENS_LN2_LO
+        p = np.full(x.shape, _ENS_COEF[13])
+        for n in range(12, -1, -1):
+            p = p * r + _ENS_COEF[n]
+        k = np.where(np.abs(kd) < 4096.0, kd, 0.0).astype(np.int32)
+        y = np.ldexp(p, k)
+    y = np.where(x > 710.0, np.inf, np.where(x < -746.0, 0.0, y))
+    y = np.where(np.isnan(x), x, y)
+    return y if y.ndim else float(y)
+
+
+def _ens_raw(seed, id_, first_step, n_steps, W):
+    """The words of steps ``first_step ... first_step + n_steps - 1``: ``[n_steps][W][4]`` uint64.  Walker i of step t owns block
+    ``t W + i`` (NumPy advances the counter before every block: a generator set to counter b starts with the stream's block b)."""
+    counter = np.array([int(first_step) * int(W), 0, 0, 0], dtype=np.uint64)
+    gen = np.random.Philox(key=np.array([int(seed), int(id_)], dtype=np.uint64), counter=counter)
+    return np.asarray(gen.random_raw(int(n_steps) * W * 4), dtype=np.uint64).reshape(int(n_steps), W, 4)
+
+
+def _ens_uniform(raw):
+    return (raw >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def ens_draws(seed, id_, step, walker, W):
+    """``misti_ens_draws``: what walker ``walker`` of step ``step`` of the stream ``numpy.random.Philox(key=[seed, id_])`` draws in an
+    ensemble of ``W`` walkers - block ``step W + walker``: ``w[0]`` the partner among the ``W / 2`` walkers of the other half (the high
+    64 bits of ``raw x W / 2``), ``w[1]`` the stretch's uniform, ``w[2]`` the decision's.  Returns dict(partner, u_z, u_acc)."""
+    W = int(W)
+    if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or int(step) < 0 or not 0 <= int(walker) < W:
+        raise ValueError("ens_draws: W must be even, 4 ... %d, the step not negative, the walker 0 ... W - 1" % ENS_MAX_WALKERS)
+    w = _ens_raw(seed, id_, step, 1, W)[0, int(walker)]
+    return dict(partner=int(_mulhi_index(w[0], W // 2)), u_z=float(_ens_uniform(w[1])), u_acc=float(_ens_uniform(w[2])))
+
+
+def ens_decision(z, d, llk_old, llk_new, T, u_acc):
+    """The decision on an evaluated proposal (``misti_ens_accept``), elementwise: a proposal without a value (not finite) is rejected, a
+    walker without a value accepts any proposal that has one, otherwise ``g = z^d`` by d successive multiplications from 1.0,
+    ``e = (llk_new - llk_old) / T``, ``p = g ens_exp(e)``, accepted iff ``u_acc < p``.  ``d`` broadcasts (an integer per element)."""
+    z, old, new, T, u = (np.asarray(v, dtype=np.float64) for v in (z, llk_old, llk_new, T, u_acc))
+    d = np.asarray(d, dtype=np.int64)
+    shape = np.broadcast(z, d, old, new, T, u).shape
+    z, d, old, new, T, u = (np.broadcast_to(v, shape) for v in (z, d, old, new, T, u))
+    g = np.ones(shape)
+    with np.errstate(all="ignore"):
+        for k in range(int(d.max()) if d.size else 0):
+            g = np.where(k < d, g * z, g)
+        p = g * ens_exp((new - old) / T)
+        take = u < p
+    return np.isfinite(new) & (~np.isfinite(old) | take)
+
+
+def ensemble_rule(fun_batch, init, lo, hi, n_step, thin=1, temperature=1.0, a=2.0, seed=0, ids=None):
+    """The rule of ``misti_ensemble_sample``, operation for operation.  ``fun_batch(X[M][N], s[M]) -> f[M]`` evaluates M points at once,
+    point m belonging to search ``s[m]`` (f = -llk; ``+inf``: no value; a NaN counts as ``+inf``).  ``init`` ``[S][W][N]``: the initial
+    ensembles, W even, every walker inside its box; ``lo`` / ``hi``: the finite box, ``[N]`` or ``[S][N]``, ``lo == hi`` holds a
+    coordinate fixed; ``temperature``: a scalar or ``[S]``, the target is ``llk / T`` inside the box (a uniform prior on it);
+    ``ids[s]`` (default s): the stream of search s is ``numpy.random.Philox(key=[seed, ids[s]])``.
+
+    All initial walkers are ONE batch.  Step t = 1 ... n_step: in half 0 walkers ``0 ... W/2 - 1`` move against the second half as it
+    stands, in half 1 walkers ``W/2 ... W - 1`` against the first half as half 0 left it; a half-step of all searches is ONE batch.
+    Walker i of step t owns block ``t W + i`` (``ens_draws``): partner j, ``z = ((a - 1) u_z + 1)^2 / a``, proposal
+    ``y = x_j + z (x_i - x_j)`` (a fixed coordinate: ``lo``), every operation rounded on its own.  A proposal with a coordinate outside
+    ``[lo, hi]`` (or NaN) is rejected without an evaluation - it is never passed to ``fun_batch``.  The decision is ``ens_decision`` with
+    ``d = N_free - 1``.  No stopping rule.
+    Returns dict(chain[S][n_keep][W][N], chain_llh[S][n_keep][W] (the ensembles after steps thin, 2 thin, ...; n_keep = n_step // thin),
+    accepted[S][W] int32, last[S][W][N], last_llh[S][W], n_points: the PROPOSALS handed to ``fun_batch`` - the S W initial evaluations
+    are not counted)."""
+    x = np.array(init, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("ensemble_rule: init must be [S][W][N]")
+    S, W, N = x.shape
+    H = W // 2
+    n_step, thin, a = int(n_step), int(thin), float(a)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=float), (S, N)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=float), (S, N)))
+    T = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=float), (S,)))
+    if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or n_step < 0 or thin < 1 or not (np.isfinite(a) and a > 1.0):
+        raise ValueError("ensemble_rule: W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
+    if not (np.isfinite(T) & (T > 0)).all():
+        raise ValueError("ensemble_rule: the temperature must be finite and positive")
+    with np.errstate(over="ignore", invalid="ignore"):
+        usable = np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(hi - lo).all()
+    if not usable:
+        raise ValueError("ensemble_rule: the box must be finite with lo <= hi")
+    fixed = lo == hi
+    if S and fixed.all(axis=1).any():
+        raise ValueError("ensemble_rule: every coordinate of a box is fixed")
+    if not (np.isfinite(x).all() and (x >= lo[:, None, :]).all() and (x <= hi[:, None, :]).all()):
+        raise ValueError("ensemble_rule: every walker of init must be finite and inside its box")
+    ids = np.arange(S) if ids is None else np.asarray(ids).reshape(S)
+    d = (~fixed).sum(axis=1) - 1
+    am1 = a - 1.0
+
+    def values(X, s_of):
+        f = np.asarray(fun_batch(X, s_of), dtype=float).reshape(-1)
+        llk = -np.where(np.isnan(f), np.inf, f)
+        return np.where(np.isfinite(llk), llk, -np.inf)
+
+    llh = values(x.reshape(-1, N).copy(), np.repeat(np.arange(S), W)).reshape(S, W) if S else np.empty((0, W))
+    n_points = 0
+    n_keep = n_step // thin
+    chain, chain_llh = np.empty((S, n_keep, W, N)), np.empty((S, n_keep, W))
+    accepted = np.zeros((S, W), dtype=np.int32)
+    CHUNK = 512
+    raw = None
+    sidx = np.arange(S)[:, None]
+    for t in range(1, n_step + 1):
+        if (t - 1) % CHUNK == 0:
+            raw = np.stack([_ens_raw(seed, ids[s], t, min(CHUNK, n_step - t + 1), W) for s in range(S)]) if S else np.empty((0, 1, W, 4), dtype=np.uint64)
+        w = raw[:, (t - 1) % CHUNK]                                       # [S][W][4]
+        for half in (0, 1):
+            mine = slice(half * H, half * H + H)
+            j = (1 - half) * H + _mulhi_index(w[:, mine, 0], H)            # [S][H]
+            u_z, u_acc = _ens_uniform(w[:, mine, 1]), _ens_uniform(w[:, mine, 2])
+            sz = am1 * u_z + 1.0
+            z = (sz * sz) / a
+            xi, xj = x[:, mine], x[sidx, j]
+            with np.errstate(all="ignore"):
+                y = xj + z[:, :, None] * (xi - xj)
+            y = np.where(fixed[:, None, :], lo[:, None, :], y)
+            inside = ((y >= lo[:, None, :]) & (y <= hi[:, None, :])).all(axis=2)
+            new = np.full((S, H), -np.inf)
+            if inside.any():
+                new[inside] = values(y[inside], np.broadcast_to(sidx, (S, H))[inside])
+                n_points += int(inside.sum())
+            take = inside & ens_decision(z, d[:, None], llh[:, mine], new, T[:, None], u_acc)
+            x[:, mine] = np.where(take[:, :, None], y, xi)
+            llh[:, mine] = np.where(take, new, llh[:, mine])
+            accepted[:, mine] += take
+        if t % thin == 0:
+            chain[:, t // thin - 1] = x
+            chain_llh[:, t // thin - 1] = llh
+    return dict(chain=chain, chain_llh=chain_llh, accepted=accepted, last=x, last_llh=llh, n_points=int(n_points))
+
+
+def ensemble_start(x, lo, hi, W, spread=1e-2, seed=0, id_=0):
+    """An initial ensemble ``[W][N]`` around the point ``x`` inside the box: walker 0 is ``clip(x)``, walker i > 0 is
+    ``clip(x + spread (hi - lo) (2 u - 1))`` per coordinate.  The uniforms are words ``i N + k`` of
+    ``numpy.random.Philox(key=[seed, id_], counter=[0, 1, 0, 0])``: the sampler's key, in a part of the counter space (second counter word
+    1) that no step of the sampler reaches - the W blocks below the first step's hold 4 W words, too few for ``(W - 1) N`` uniforms once
+    N > 4.  A fixed coordinate comes out at ``lo``.  Host only."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    N, W = x.size, int(W)
+    lo, hi = (np.broadcast_to(np.asarray(v, dtype=np.float64), (N,)) for v in (lo, hi))
+    gen = np.random.Philox(key=np.array([int(seed), int(id_)], dtype=np.uint64), counter=np.array([0, 1, 0, 0], dtype=np.uint64))
+    u = _ens_uniform(np.asarray(gen.random_raw(W * N), dtype=np.uint64)).reshape(W, N)
+    pts = x[None, :] + float(spread) * (hi - lo)[None, :] * (2.0 * u - 1.0)
+    pts[0] = x
+    return np.clip(pts, lo, hi)
+
+
+def composite_temperature(H, J):
+    """The magnitude adjustment of a composite likelihood: ``T = |trace(H^-1 J)| / p`` with ``H`` the Hessian of the log-likelihood at
+    the fit (``curvature``'s ``hess``, one point ``[p][p]``) and ``J`` the covariance of the score (``score_covariance``) - the two
+    matrices the sandwich covariance is built from.  Sampling ``llk / T`` gives the composite posterior the average spread of the
+    sandwich: ``curvature`` provides the calibration, the sampler the shape.  ``J = H`` gives 1, ``J = c H`` gives c (the Hessian's
+    sign drops out).  Raises where ``H`` is flagged not negative definite (``observed_covariance``) or ``J`` is not finite."""
+    H = np.asarray(H, dtype=np.float64)
+    J = np.asarray(J, dtype=np.float64).reshape(H.shape)
+    if H.ndim != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError("composite_temperature: H and J must be [p][p]")
+    if not observed_covariance(H)["ok"][0]:
+        raise ValueError("composite_temperature: the Hessian is not negative definite - no calibration at this point")
+    if not np.isfinite(J).all():
+        raise ValueError("composite_temperature: J is not finite")
+    T = abs(float(np.trace(np.linalg.solve(H, J)) / H.shape[0]))
+    if not (np.isfinite(T) and T > 0):
+        raise ValueError("composite_temperature: trace(H^-1 J) / p = %g is not a temperature" % T)
+    return T
+
+
+def autocorrelation_time(series, c=5.0):
+    """The integrated autocorrelation time of a 1-D series, ``tau = 1 + 2 sum_{k=1}^{M} rho_k`` with Sokal's window: the smallest M
+    with ``M >= c tau(M)``.  A constant series returns 1."""
+    y = np.asarray(series, dtype=np.float64).reshape(-1)
+    n = y.size
+    y = y - y.mean()
+    var = float(np.dot(y, y))
+    if n < 2 or var == 0.0:
+        return 1.0
+    size = 1 << (2 * n - 1).bit_length()
+    f = np.fft.rfft(y, size)
+    rho = np.fft.irfft(f * np.conj(f), size)[:n] / var
+    tau = 2.0 * np.cumsum(rho) - 1.0
+    ok = np.arange(n) >= c * tau
+    M = int(np.argmax(ok)) if ok.any() else n - 1
+    return float(max(tau[M], 1.0))
+
+
+def ensemble_summary(chain, burn=0, accepted=None, n_step=None):
+    """Per coordinate of one search's ``chain[n_keep][W][N]`` after dropping the first ``burn`` kept steps: ``mean``, ``median``,
+    ``q025`` / ``q975`` (the 2.5 % / 97.5 % quantiles over steps and walkers), ``tau`` (``autocorrelation_time`` of the ensemble-mean
+    series, in kept steps) and ``short`` (True where fewer than 50 ``tau`` kept steps remain).  ``acceptance``: the fraction of moves
+    accepted - ``accepted.sum() / (W n_step)`` where both are given, otherwise the fraction of kept (step, walker) pairs whose position
+    differs from the kept step before."""
+    c = np.asarray(chain, dtype=np.float64)
+    if c.ndim != 3:
+        raise ValueError("ensemble_summary: chain must be [n_keep][W][N]")
+    K, W, N = c.shape
+    burn = int(burn)
+    if not 0 <= burn < K:
+        raise ValueError("ensemble_summary: burn must be 0 ... n_keep - 1 (n_keep = %d)" % K)
+    k = c[burn:]
+    flat = k.reshape(-1, N)
+    tau = np.array([autocorrelation_time(k[:, :, j].mean(axis=1)) for j in range(N)])
+    if accepted is not None and n_step:
+        acc = float(np.sum(accepted)) / (W * int(n_step))
+    else:
+        acc = float((c[1:] != c[:-1]).any(axis=2).mean()) if K > 1 else float("nan")
+    q = np.quantile(flat, [0.025, 0.5, 0.975], axis=0)
+    return dict(mean=flat.mean(axis=0), median=q[1], q025=q[0], q975=q[2], tau=tau, short=(K - burn) < 50.0 * tau, acceptance=acc, n=K - burn)
+
+
+def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0):
+    """``bootstrap_profile_de``'s sampler: per (row, split) pair ONE ensemble inside ``box`` (``(lo, hi)``, each ``[n_param]``, finite), all
+    R x P ensembles in ONE ``misti_ensemble_sample`` call - every half-step one dense engine batch.  ``init`` is ``[W][n_param]`` (every
+    pair starts from it) or ``[R][P][W][n_param]``.  The stream id of an ensemble is its split's index: the rows of a bootstrap share
+    their random numbers, and a row's result does not depend on the other rows.
+    Returns what ``Engine.ensemble_sample`` returns with the leading axis reshaped to ``[R][P]``."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    splits = np.asarray(split_values, dtype=float).reshape(-1)
+    R, Q = rows.shape[0], splits.size
+    r_of, j_of = (v.ravel() for v in np.meshgrid(np.arange(R), np.arange(Q), indexing="ij"))
+    x0 = np.asarray(init, dtype=float)
+    x0 = np.broadcast_to(x0, (R, Q) + x0.shape[-2:]).reshape((R * Q,) + x0.shape[-2:])
+    out = engine.ensemble_sample(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin, temperature=temperature,
+                                 a=a, seed=seed, ids=j_of.astype(np.uint64))
+    return {k: (v.reshape(R, Q, *v.shape[1:]) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+
+
+def split_fit_mcmc(engine, jsfs_rows, init, box, band_bounds=None, pulse_times=None, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0):
+    """``split_fit_de``'s sampler: per row ONE ensemble over (optimised parameters, split) inside ``box`` (``(lo, hi)``, each
+    ``[n_param + 1]``, finite, the split last), all R ensembles in ONE ``misti_ensemble_sample`` call.  ``init`` is ``[W][n_param + 1]``
+    (every row starts from it) or ``[R][W][n_param + 1]``; every row draws from stream 0 (the rows of a bootstrap share their random
+    numbers - only the data differ).  ``band_bounds`` / ``pulse_times`` apply to every ensemble.
+    Returns what ``Engine.ensemble_sample`` returns (leading axis: the row)."""
+    rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
+    R = rows.shape[0]
+    x0 = np.asarray(init, dtype=float)
+    x0 = np.ascontiguousarray(np.broadcast_to(x0, (R,) + x0.shape[-2:]))
+    tile = lambda v, shape: None if v is None else np.repeat(np.asarray(v, dtype=np.int32).reshape(shape), R, axis=0)
+    return engine.ensemble_sample(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
+                                  pulse_times=tile(pulse_times, (1, -1)), n_step=n_step, thin=thin, temperature=temperature, a=a, seed=seed,
+                                  ids=np.zeros(R, dtype=np.uint64))

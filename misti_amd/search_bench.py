@@ -209,6 +209,59 @@ def run_de_compare(n_rows=256, pop=16, gens=40, hops=(10, 30), seed=0, device=0,
     return lines
 
 
+def run_mcmc_compare(n_rows=256, walkers=16, steps=40, pop=16, gens=40, seed=0, device=0, out=None, repeats=5):
+    """`python -m misti_amd.search_bench --mcmc W STEPS`: config 3's model, one ensemble per bootstrap row (misti_ensemble_sample: every
+    half-step one dense batch of rows x W / 2 slots) beside the differential-evolution leg of run_de_compare on the same rows and box -
+    the two in turns in one process, `repeats` times after a warm-up call each.  A half-step is an engine batch like a DE generation,
+    so what to compare is the time per submitted point.  Reports per leg the median and the least seconds of a call, the points handed to
+    the engine and, for the sampler, the acceptance fraction.  One JSON line per leg."""
+    import random
+    from . import io as mio, synth, workloads
+    from .engine import Engine, truth_spectrum
+    from .optimize import ensemble_start
+    w = workloads.config3(lambda *a: truth_spectrum(*a), n_start=max(n_rows, 64))
+    split = float(w.split_time[0])
+    table = np.array(mio.bootstrap_table(synth.chunk_rows(w.jsfs[0], 20), n_rows - 1, random.Random(3)), dtype=np.float64)
+    R = table.shape[0]
+    rows = np.arange(R, dtype=np.int32)
+    starts = np.ascontiguousarray(w.params[:R])
+    box = (w.params.min(axis=0), w.params.max(axis=0))
+    splits = np.full(R, split)
+    with Engine(w.times, w.lh, device=device, **w.engine_kwargs()) as eng:
+        de = lambda: eng.differential_evolution(starts, rows, table, box, split_times=splits, pop=pop, maxiter=gens, tol=0.0, seed=seed)
+        fit = de()["x"]                                                                     # (also the DE leg's warm-up)
+        init = np.stack([ensemble_start(fit[r], box[0], box[1], walkers, 1e-2, seed, 0) for r in range(R)])
+        mc = lambda: eng.ensemble_sample(init, rows, table, box, split_times=splits, n_step=steps, seed=seed, ids=np.zeros(R, dtype=np.uint64))
+        mc()
+        legs = [("de pop=%d gens=%d seed=%d" % (pop, gens, seed), de), ("mcmc walkers=%d steps=%d seed=%d" % (walkers, steps, seed), mc)]
+        times = {name: [] for name, _ in legs}
+        last = {}
+        for _ in range(repeats):
+            for name, call in legs:
+                eng.sync()
+                t0 = time.perf_counter()
+                last[name] = call()
+                times[name].append(time.perf_counter() - t0)
+    lines = []
+    for name, _ in legs:
+        r, t = last[name], times[name]
+        points = int(r["n_points"]) + (R * walkers if "accepted" in r else 0)           # the sampler's n_points leaves the initial ensembles out
+        line = {"leg": name, "rows": R, "repeats": repeats, "seconds_median": float(np.median(t)), "seconds_min": float(np.min(t)), "points": points,
+                "us_per_point_median": 1e6 * float(np.median(t)) / points}
+        if "accepted" in r:
+            line.update(acceptance=float(r["accepted"].sum()) / (R * walkers * steps), batches=1 + 2 * steps, slots=R * walkers + 2 * steps * R * (walkers // 2),
+                        median_last_llh=float(np.median(r["last_llh"])))
+        else:
+            line.update(batches=int(r["iterations_issued"]) + 1, median_llh=float(np.median(r["llh"])))
+        lines.append(line)
+    text = "\n".join(json.dumps(l) for l in lines) + "\n"
+    sys.stdout.write(text)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(text)
+    return lines
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser(description="differential evolution against basin hopping on config 3's model, per bootstrap row")
@@ -219,5 +272,10 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mcmc", type=int, nargs=2, default=None, metavar=("W", "STEPS"), help="the sampler's leg beside the DE leg: one ensemble of W walkers per row, STEPS steps")
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
+    if a.mcmc:
+        run_mcmc_compare(a.rows, a.mcmc[0], a.mcmc[1], a.pop, a.gens, a.seed, a.device, a.out, a.repeats)
+        sys.exit(0)
     run_de_compare(a.rows, a.pop, a.gens, tuple(a.hops), a.seed, a.device, a.out)
