@@ -991,7 +991,10 @@ int misti_last_solver_trace(misti_ctx* ctx, int64_t n_cand, int32_t* trace, int6
  *   lh   [n_cand][numT+1][2]   rows below the candidate's split: -log(P[no coalescence])/T
  *                              of that genome's pair chain; other rows: the model's rates
  *                              (row numT is used only by a fractional split, else 0);
- *                              NaN rows when status is not MISTI_OK / MISTI_INF_COAL
+ *                              NaN rows when status is not MISTI_OK / MISTI_INF_COAL;
+ *                              a single rate is NaN where the genome's no-coalescence mass before or
+ *                              after the interval is no normal double (the state is chained, not
+ *                              renormalised: a cumulated rate x length past ~708)
  *   pr   [n_cand][numT+2][6] or NULL   pair-state trace as in misti_eval_batch (rows 0..split)
  *   status [n_cand] or NULL
  *   hold_mu  0: every interval is evaluated with its own migration rates (the model as specified;

@@ -1443,7 +1443,10 @@ void forward_kernel(DevModel m, int64_t n_cand, const double* __restrict__ split
                 bool guard_unused = false;
                 pair_expv(a0, a1, b0, b1, v, q, 0.0, true, dg, guard_unused);
                 const double nc = (v[0] + v[1]) + v[2];
-                const double seen = -log(nc / before) / T;
+                // The state is chained without renormalisation, so past a cumulated rate x length of ~708 the mass is a subnormal
+                // double with a few digits left (finite rates wrong in the 11th digit were measured at e^-720) and past ~745 it is zero:
+                // such a rate is reported as NaN, never as a finite number.
+                const double seen = (nc >= 0x1p-1022 && before >= 0x1p-1022) ? -log(nc / before) / T : NAN;
                 if (k == 0) l0 = seen; else l1 = seen;
                 ps.p[k][0] = v[0]; ps.p[k][1] = v[1]; ps.p[k][2] = v[2];
             }

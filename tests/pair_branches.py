@@ -181,6 +181,126 @@ def coverage_forward(fx):
     return len(ivs)
 
 
+LN_DBL_MIN = math.log(2.2250738585072014e-308)       # masses above it are normal doubles
+
+
+def forward_bound(t, ratio, x):
+    """The bound on x_t = seen rate x length of interval t (tests/test_gpu_exact_forward.py): pair_expv is held to W_BOUND of the largest
+    component of its result, the state that enters interval t carries the errors of the t intervals before it, and x = -log(nc / before)
+    turns a relative error of nc into an absolute one of x - so (t + 1) W_BOUND max|v| / nc - plus the roundings of the logarithm, the
+    division by T and the products rate x length.  `ratio` is max|v_exact| / nc_exact."""
+    return (t + 1) * W_BOUND * ratio + 8 * EPS * max(1.0, x)
+
+
+def coverage_exact_forward(fx):
+    """The regimes tests/golden/golden_exact_forward.json.gz promises to reach: conditions on the inputs and their labels alone.
+    Returns the number of intervals per branch."""
+    regs = {r["name"]: r for r in fx["regimes"]}
+    assert set(regs) == {"branches", "tiny", "no_migration", "decay", "pulses", "hold_mu", "fractional", "statuses"}, sorted(regs)
+    per_branch = {}
+    for r in fx["regimes"]:
+        for m in r["models"]:
+            assert 6 <= len(m["lh"]) <= 12 and len(m["times"]) == len(m["lh"]) - 1 and len(m["candidates"]) <= 65, m["name"]
+            for c in m["candidates"]:
+                assert sorted(c["exact"]) == [str(h) for h in m["hold"]]
+                for e in c["exact"].values():
+                    for br in e.get("branch", ()):
+                        per_branch[br] = per_branch.get(br, 0) + 1
+    # -- every branch, through models
+    for br in BRANCHES:
+        assert per_branch.get(br, 0) >= 8, (br, per_branch)
+    walk = regs["branches"]["models"][0]
+    assert len(walk["candidates"]) == 65
+    walks = lambda b: b[0] == "taylor0" and len(set(b) & set(BRANCHES[:7])) >= 5 and "series" in b and b[-1] in BRANCHES[8:]
+    assert sum(1 for c in walk["candidates"] if walks(c["exact"]["0"]["branch"])) >= 3          # one per direction of migration
+    stiff, one_way = 0.0, set()
+    for m in regs["branches"]["models"]:
+        for c in m["candidates"]:
+            for t, br in enumerate(c["exact"]["0"]["branch"]):
+                if br == "eigen":
+                    stiff = max(stiff, max(m["lh"][t]) * m["times"][t])
+                if br.startswith("cascade") and max(c["params"]) > 0:
+                    one_way.add(br)
+    assert stiff >= 2e5, stiff
+    assert one_way == {"cascade1", "cascade2"}, one_way
+    # -- tiny intervals: every decade, at the chain's start and in a mixed state, with and without migration
+    decades = set()
+    for m in regs["tiny"]["models"]:
+        d = m["decade"]
+        for c in m["candidates"]:
+            e = c["exact"]["0"]
+            for t in (0, 2, 3):
+                assert all(0.2 * 10.0 ** -d <= x <= 1.5 * 10.0 ** -d for x in e["x"][t]), (m["name"], c["params"], t, e["x"][t])
+                decades.add((d, "no_migration" in c["tags"], t == 0))
+            assert c["params"] == [0.0, 0.0] if "no_migration" in c["tags"] else max(c["params"]) > 0
+            mixed = e["pr"][2]                                   # the state the tiny interval 2 starts from
+            assert "no_migration" in c["tags"] or max(mixed[4], mixed[5]) > 1e-3, (m["name"], mixed)
+    assert decades == {(d, nm, st) for d in range(2, 13) for nm in (False, True) for st in (False, True)}
+    # -- no migration at all
+    nm = regs["no_migration"]["models"][0]
+    assert not nm["bands"] and not nm["pulses"] and len(nm["candidates"]) >= 8
+    # -- decaying mass
+    reached, past, skew = set(), 0, 0.0
+    for m in regs["decay"]["models"]:
+        lowest = min(v for c in m["candidates"] for row in c["exact"]["0"]["ln_nc"] for v in row)
+        for c in m["candidates"]:
+            e = c["exact"]["0"]
+            cum = [sum(row[k] for row in e["x"]) for k in (0, 1)]
+            for target in (50, 300, 700):
+                if max(cum) >= target and lowest > LN_DBL_MIN:
+                    reached.add(target)
+            past += max(cum) > 745
+            for row in e["pr"][1:]:
+                for k in (0, 1):
+                    comp = [abs(row[j]) for j in (k, 2 + k, 4 + k) if row[j] != 0.0]
+                    if lowest > LN_DBL_MIN and comp:
+                        skew = max(skew, max(comp) / min(comp))
+    assert reached == {50, 300, 700}, reached
+    assert past == 2, past
+    assert skew >= 1e200, skew
+    # -- pulses
+    seen = set()
+    for m in regs["pulses"]["models"]:
+        assert [p[1] for p in m["pulses"]] == [0, 2, 3, 5] and all(c["split"] == 6.0 for c in m["candidates"])
+        pops = {p[0] for p in m["pulses"]}
+        for c in m["candidates"]:
+            for rate in ("rate_1e-12", "rate_0.5", "rate_1-2^-53"):
+                for where in ("first_interval", "last_before_split", "consecutive"):
+                    if rate in c["tags"] and where in c["tags"]:
+                        seen |= {(p, rate, where) for p in pops}
+            if "rate_0" in c["tags"]:
+                assert not any(c["params"])
+                seen |= {(p, "rate_0", "") for p in pops}
+    assert len(seen) == 2 * (9 + 1), sorted(seen)
+    # -- hold_mu
+    for m in regs["hold_mu"]["models"]:
+        numT = len(m["lh"])
+        assert m["hold"] == [0, 1] and [c["split"] for c in m["candidates"]] == [float(s) for s in range(1, numT + 1)]
+        last = m["candidates"][-1]["exact"]
+        assert all(last[h]["status"] == 3 and last[h]["n_eval"] == numT - 1 for h in ("0", "1")), m["name"]
+    by_name = {m["name"]: m for m in regs["hold_mu"]["models"]}
+    for name in ("fixed_ends", "end_at_split"):
+        for pop in (0, 1):
+            assert len({b[3] for b in by_name[name]["bands"] if b[0] == pop}) == 3
+    assert sum(1 for b in by_name["end_at_split"]["bands"] if b[2] == -1) == 2 and all(b[2] != -1 for b in by_name["fixed_ends"]["bands"])
+    assert all(c["exact"]["0"]["status"] in (0, 3) for c in by_name["fixed_ends"]["candidates"])
+    assert {c["exact"]["1"]["status"] for c in by_name["end_at_split"]["candidates"]} == {0, 3, 4}
+    assert all(b[1] == 0 and b[2] == -1 for b in by_name["constant"]["bands"])
+    # -- fractional splits
+    fr = regs["fractional"]["models"][0]
+    numT = len(fr["lh"])
+    assert fr["hold"] == [0, 1]
+    assert {(int(c["split"]), c["split"] - int(c["split"])) for c in fr["candidates"]} == {(s, f) for s in (0, 3, numT - 2) for f in (2.0 ** -20, 0.5, 1 - 2.0 ** -20)}
+    for c in fr["candidates"]:
+        e = c["exact"]["0"]
+        assert e["status"] == 0 and e["n_eval"] == int(c["split"]) + 1 and e["model_rows"][-1] == fr["lh"][-1], c["split"]
+    # -- statuses
+    st = {tag: c["exact"]["0"]["status"] for c in regs["statuses"]["models"][0]["candidates"] for tag in c["tags"]}
+    assert st == dict(split_0=0, ok=0, negative_parameter=1, split_below_0=4, split_above_numT=4, split_at_numT=3, fraction_of_the_last=4,
+                      fraction_before_the_band=0), st
+    return per_branch
+
+
 def coverage_residuals(fx):
     """The coverage the probe's fixture promises (the issue's part B)."""
     ps = fx["problems"]
