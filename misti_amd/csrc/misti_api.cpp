@@ -1137,6 +1137,237 @@ struct Carver {
     T* take(size_t k) { T* p = base ? base + n : nullptr; n += k; return p; }
 };
 
+// A workspace in the context's search buffers (one allocation per type: doubles | int32): `layout` run twice, as Carver says, and
+// the pinned words the live count of a paced search comes back in (Pacer).  `noun`: what the caller's count counts.
+template <class Layout>
+int carve(misti_ctx* c, const char* noun, Layout&& layout) {
+    Carver<double> f;
+    Carver<int32_t> q;
+    layout(f, q);
+    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
+    HIP_TRY(c->nm_i32.reserve(q.n * sizeof(int32_t)));
+    if (!c->nm_live_host) {
+        if (hipHostMalloc((void**)&c->nm_live_host, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            c->nm_live_host = nullptr;
+            return fail(MISTI_E_HIP, "pinned allocation for the live-%s count failed", noun);
+        }
+    }
+    f = Carver<double>{c->nm_f64.as<double>()};
+    q = Carver<int32_t>{c->nm_i32.as<int32_t>()};
+    layout(f, q);
+    return 0;
+}
+
+// One array per batch of a search, `width` elements per slot.  The arrays of a kind lie back to back: nm_run clears a whole kind
+// of its five batches with ONE memset over all their slots (a memset per batch would be four launches more per kind), so a kind is
+// carved here and nowhere else.
+template <class T>
+void nm_per_slot(NmBatch* b, const size_t* slots, int n_batch, T* NmBatch::*arr, Carver<T>& from, size_t width) {
+    size_t all = 0;
+    for (int k = 0; k < n_batch; ++k) { b[k].*arr = from.take(slots[k] * width); all += slots[k]; }
+    assert(!(b[0].*arr) || b[n_batch - 1].*arr + slots[n_batch - 1] * width == b[0].*arr + all * width);
+    (void)all;
+}
+
+// ---- the rows problem: what Nelder-Mead, differential evolution and the ensemble sampler are handed alike ------------------------------
+// A start or search s with a split time, a row of a replicate table, optional band bounds and pulse times, an optional box, and
+// optionally the split as the last coordinate.  A per-start field is added HERE, to RowsProblem below and to PointSource / put_point
+// (misti_device.h) - nowhere else.  The three public descriptors lay these fields out differently: one rows_args() each.
+struct RowsArgs {
+    int32_t split;                   // MISTI_SPLIT_*
+    double split_time;               // MISTI_SPLIT_ONE
+    const double* split_times;       // MISTI_SPLIT_PER_START
+    int64_t n_start;
+    const int32_t* rows;
+    int64_t n_rep;
+    const double* jsfs;
+    const int32_t *band_bounds, *pulse_times;
+    int64_t n_box;
+    const double *box_lo, *box_hi;
+    const uint64_t* ids;
+    bool rows_path() const { return split != MISTI_SPLIT_ONE; }
+    bool per_start() const { return split == MISTI_SPLIT_PER_START; }
+    bool fit_split() const { return split == MISTI_SPLIT_FITTED; }
+};
+RowsArgs rows_args(const misti_search_t& q) {
+    return {q.split, q.split_time, q.split_times, q.n_start, q.rows, q.n_rep, q.jsfs, q.band_bounds, q.pulse_times, q.n_box, q.box_lo, q.box_hi, nullptr};
+}
+RowsArgs rows_args(const misti_de_t& q) {
+    return {q.split, 0.0, q.split_times, q.n_start, q.rows, q.n_rep, q.jsfs, q.band_bounds, q.pulse_times, q.n_box, q.box_lo, q.box_hi, q.ids};
+}
+RowsArgs rows_args(const misti_ens_t& q) {
+    return {q.split, 0.0, q.split_times, q.n_start, q.rows, q.n_rep, q.jsfs, q.band_bounds, q.pulse_times, q.n_box, q.box_lo, q.box_hi, q.ids};
+}
+
+// The checks the three doors share.  Each door calls them where its header's order of refusals puts them (nm_check, de_check,
+// ens_check); `noun` is what the door calls its n_start.
+int check_n_box(const RowsArgs& a, const char* noun) {
+    if (a.n_box != 1 && a.n_box != a.n_start)
+        return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld %s)", (long long)a.n_box, (long long)a.n_start, noun);
+    return 0;
+}
+// every row inside the table, every split time of MISTI_SPLIT_PER_START finite; `whole`: every such split time is an integer (a
+// fitted split is whole by accident only: never the integer-splits hint)
+int check_rows(const RowsArgs& a, bool& whole) {
+    whole = a.per_start();
+    for (int64_t s = 0; a.rows_path() && s < a.n_start; ++s) {
+        if (a.rows[s] < 0 || a.rows[s] >= a.n_rep)
+            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)a.rows[s], (long long)a.n_rep);
+        if (!a.per_start()) continue;
+        if (!std::isfinite(a.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
+        if (a.split_times[s] != std::floor(a.split_times[s])) whole = false;
+    }
+    return 0;
+}
+// the context, the number of coordinates N it gives, and the limits: a search of `per` points per start (`noun` names the product)
+// keeps every slot index of its batches below INT32_MAX / 8.  (The limits before any scan of the starts: a call that is refused for
+// its size does not read n_start x N doubles first.)
+int check_limits(const misti_ctx* c, const RowsArgs& a, int64_t per, const char* noun, int& N) {
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    N = c->dm.n_param + (a.fit_split() ? 1 : 0);
+    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
+    // the sort's local arrays hold MISTI_MAX_PARAMS + 1 vertices (misti_nm.hip: sort_simplex)
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
+    if (a.n_start > INT32_MAX / 8 / (N + 1) / per) return fail(MISTI_E_LIMIT, "too many %s for one call", noun);
+    if (a.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
+    return 0;
+}
+int check_finite(const double* starts, int64_t n_start, int N) {
+    for (int64_t s = 0; s < n_start; ++s)
+        for (int k = 0; k < N; ++k)
+            if (!std::isfinite(starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
+    return 0;
+}
+// box b of the call: neither bound NaN, lo <= hi (lo == hi holds a coordinate fixed).  `finite`: why the door needs a finite box -
+// then an infinite bound or width is refused as well; NULL: +-inf leaves a side open.
+int check_box(const RowsArgs& a, int N, int64_t b, const char* finite) {
+    for (int k = 0; k < N; ++k) {
+        const double lo = a.box_lo[b * N + k], hi = a.box_hi[b * N + k];
+        if (!finite && (lo != lo || hi != hi)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is NaN", (long long)b, k);
+        if (finite && (!std::isfinite(lo) || !std::isfinite(hi))) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is not finite (%s)", (long long)b, k, finite);
+        if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
+        if (finite && !std::isfinite(hi - lo)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: hi - lo is not finite", (long long)b, k);
+    }
+    return 0;
+}
+
+// The device side of checked RowsArgs with n_start >= 1: what each start hands its points (split, row, bounds, pulse times, box, id),
+// one of each per slot of the batches it is given, the compact parameter array of a fitted split, the table with the llh_const of
+// every row, and where a batch of the rows path is evaluated into.  A path that is not taken allocates and writes nothing: without
+// bounds nothing of the bounds path, and so on; with MISTI_SPLIT_ONE only the box.
+struct RowsProblem {
+    RowsArgs a{};
+    int N = 0;
+    bool whole = false;              // every split time is an integer: the rows path's one hint
+    size_t S = 0, R = 0, NB2 = 0, NP = 0, NQ = 0, NX = 0;
+    double *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_ids = nullptr;
+    int32_t *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
+    double* rjafs = nullptr;         // [M][7]  a batch is evaluated without replicates into rjafs / rstatus, then llk_rows_kernel scores
+    int32_t* rstatus = nullptr;      // [M]     every candidate against its own row of the table
+
+    RowsProblem() = default;
+    RowsProblem(const misti_ctx* c, const RowsArgs& a_, int N_, bool whole_) : a(a_), N(N_), whole(whole_) {
+        S = (size_t)a.n_start; R = (size_t)a.n_rep;
+        // int32 per bound set and per pulse-time set (none for a model without bands / pulses: the engine has nothing to apply them
+        // to), doubles per compact parameter vector (no width for a model without parameters), doubles per box array
+        NB2 = a.rows_path() && a.band_bounds ? 2 * (size_t)c->dm.n_band : 0;
+        NP = a.rows_path() && a.pulse_times ? (size_t)c->dm.n_pulse : 0;
+        NQ = a.fit_split() ? (size_t)N - 1 : 0;
+        NX = (size_t)a.n_box * (size_t)N;
+    }
+    // `n_batch` batches of slots[.] slots, the largest evaluation M points
+    void layout(Carver<double>& f, Carver<int32_t>& i, NmBatch* b, const size_t* slots, int n_batch, size_t M) {
+        if (a.rows_path()) {
+            if (a.per_start()) d_split = f.take(S);
+            d_table = f.take(R * 8); d_consts = f.take(R); rjafs = f.take(M * 7);
+            if (NQ) nm_per_slot(b, slots, n_batch, &NmBatch::par, f, NQ);
+            d_rowof = i.take(S);
+            nm_per_slot(b, slots, n_batch, &NmBatch::row, i, 1);
+            rstatus = i.take(M);
+            if (NB2) { d_bounds = i.take(S * NB2); nm_per_slot(b, slots, n_batch, &NmBatch::bnd, i, NB2); }
+            if (NP) { d_pulses = i.take(S * NP); nm_per_slot(b, slots, n_batch, &NmBatch::put, i, NP); }
+        }
+        if (NX) { d_lo = f.take(NX); d_hi = f.take(NX); }
+        if (a.ids) d_ids = f.take(S);                      // uint64 ids: 8-byte words of the double buffer
+    }
+    // the caller's arrays to the device, and llh_const over the table: once per call, every row
+    int upload(misti_ctx* c) const {
+        hipStream_t sm = c->stream;
+        if (d_split) HIP_TRY(hipMemcpyAsync(d_split, a.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
+        if (d_rowof) HIP_TRY(hipMemcpyAsync(d_rowof, a.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+        if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, a.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+        if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, a.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+        if (NX) {
+            HIP_TRY(hipMemcpyAsync(d_lo, a.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+            HIP_TRY(hipMemcpyAsync(d_hi, a.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
+        }
+        if (d_ids) HIP_TRY(hipMemcpyAsync(d_ids, a.ids, S * sizeof(uint64_t), hipMemcpyHostToDevice, sm));
+        if (d_table) {
+            HIP_TRY(hipMemcpyAsync(d_table, a.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+            HIP_TRY(misti::launch_llh_const(a.n_rep, d_table, d_consts, c->unfolded, sm));
+        }
+        return 0;
+    }
+    void fill(misti::PointSource& src) const {
+        src.N = N; src.split = a.rows_path() ? 0.0 : a.split_time;
+        src.split_of = d_split; src.row_of = d_rowof;
+        src.bounds_of = d_bounds; src.nb2 = (int)NB2;
+        src.pulses_of = d_pulses; src.np = (int)NP;
+        src.fit_split = a.fit_split() ? 1 : 0;
+        src.box_lo = d_lo; src.box_hi = d_hi; src.box_per_start = a.n_box > 1 ? 1 : 0;
+        src.ids = reinterpret_cast<const uint64_t*>(d_ids);
+    }
+    // One batch of the rows path through the engine: the first n slots of `b` evaluated without replicates into rjafs / rstatus, with
+    // each slot's own band bounds and pulse times where the batch carries them, then every point scored against its own row of the
+    // table.  With the split as a coordinate the engine reads the batch's compact parameter vectors, not the points (NULL for a model
+    // without parameters, as misti_eval_batch allows).  The one hint: integer splits where the caller's are; a fitted split is never
+    // known to be whole.  `mask`: the hints a diagnostic run lets through.
+    int eval(misti_ctx* c, const NmBatch& b, int64_t n, double* llk, unsigned mask = ~0u) const {
+        const unsigned hints = (whole ? RUN_INTEGER_SPLITS : 0u) & mask;
+        if (int r = run_dev(c, n, b.split, a.fit_split() ? b.par : b.pts, b.bnd, 0, nullptr, nullptr, rjafs, nullptr, nullptr, rstatus, hints, b.put)) return r;
+        HIP_TRY(misti::launch_llk_rows(n, rjafs, rstatus, b.row, d_table, d_consts, llk, c->unfolded, c->stream));
+        return 0;
+    }
+};
+
+// A paced search: the host runs at most two iterations ahead of the device.  Before issuing iteration k it waits for the event of
+// iteration k - 2 and reads the count of live starts that iteration left in pinned memory (4 bytes; nothing else of the search
+// leaves the device).  That count bounds the live starts of iteration k from above - the number only falls - and sizes its
+// batches; zero -> stop issuing.
+struct Pacer {
+    hipStream_t sm;
+    volatile int32_t* live;          // the context's pinned words (carve): [it & 1] the count iteration `it` left
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    explicit Pacer(misti_ctx* c) : sm(c->stream), live(c->nm_live_host) {}
+    Pacer(const Pacer&) = delete;
+    ~Pacer() { for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
+    // the count the search's set-up left in d_count (stream order): the bound of iteration 0
+    int start(const int32_t* d_count, int64_t& bound) {
+        for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+        live[0] = live[1] = -1;
+        HIP_TRY(hipMemcpyAsync((void*)&live[0], d_count, sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+        HIP_TRY(hipEventRecord(ev[0], sm));
+        HIP_TRY(hipEventSynchronize(ev[0]));
+        bound = live[0];
+        return 0;
+    }
+    // the bound of iteration `it`: lowered to the count iteration it - 2 left
+    int bound(int it, int64_t& bound) {
+        if (it < 2) return 0;
+        HIP_TRY(hipEventSynchronize(ev[it & 1]));
+        if (live[it & 1] < bound) bound = live[it & 1];
+        return 0;
+    }
+    int32_t* word(int it) { return (int32_t*)&live[it & 1]; }
+    // iteration `it` is issued: its count from d_count, or (NULL) already on its way into word(it) by the iteration's own kernel
+    int record(int it, const int32_t* d_count) {
+        if (d_count) HIP_TRY(hipMemcpyAsync((void*)word(it), d_count, sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+        HIP_TRY(hipEventRecord(ev[it & 1], sm));
+        return 0;
+    }
+};
+
 // Device-resident state of one batched Nelder-Mead run, carved from the context's nm buffers.
 struct NmWork {
     misti::NmState st{};
@@ -1145,15 +1376,9 @@ struct NmWork {
     double* llk[NM_BATCHES] = {};    // [slots] the engine's values of every batch
     double *d_starts = nullptr;      // [S][N] in: start points; out: best vertices
     double *d_llh = nullptr;         // [S]    out: their log-likelihood
-    double *d_row = nullptr;         // [8]    the data JSFS
+    double *d_row = nullptr;         // [8]    the data JSFS (MISTI_SPLIT_ONE)
     int32_t *idx[2] = {nullptr, nullptr}, *cnt = nullptr;
-    // rows path (st.row_of set): a batch is evaluated without replicates into rjafs / rstatus, then llk_rows_kernel scores every
-    // candidate against its own row of the table
-    const double* table = nullptr;   // [n_rep][8]
-    const double* consts = nullptr;  // [n_rep]  llh_const of every row
-    double* rjafs = nullptr;         // [M][7]   M = the largest batch: max(S (N + 1), spec_cap (4 + N))
-    int32_t* rstatus = nullptr;      // [M]
-    bool whole = false;              // every split time of the rows path is an integer
+    RowsProblem rows;                // what each start hands its points; the rows path's table and evaluation
 };
 
 // Live starts up to which an iteration is speculative (misti_nm.hip): all 4 + N points of a start in one batch, as long as the
@@ -1165,66 +1390,6 @@ int64_t nm_spec_cap(int N) {
     return misti::FOLLOW_MAX_CHAINS / (4 + N);
 }
 
-// One array per batch of the search, `width` elements per slot.  The five of them lie back to back: nm_run clears a whole kind with
-// ONE memset over n_slots (a memset per batch would be four launches more per kind), so a kind is carved here and nowhere else.
-template <class T>
-void nm_per_slot(NmWork& w, T* NmBatch::*arr, Carver<T>& from, size_t width) {
-    for (int b = 0; b < NM_BATCHES; ++b) w.st.b[b].*arr = from.take(w.slots[b] * width);
-    const NmBatch &first = w.st.b[0], &last = w.st.b[NM_BATCHES - 1];
-    assert(!(first.*arr) || last.*arr + w.slots[NM_BATCHES - 1] * width == first.*arr + w.n_slots * width);
-}
-
-// The minimiser's own state for n_start simplices of N coordinates, then whatever `extra` takes behind it: one allocation per type
-// (simplices, points and values | counters and slot tables).
-template <class Extra>
-int nm_prepare(misti_ctx* c, int64_t n_start, int N, NmWork& w, Extra&& extra) {
-    const size_t S = (size_t)n_start, V = (size_t)N + 1;
-    const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
-    misti::NmState& st = w.st;
-    st.S = n_start; st.N = N; st.spec_cap = (int64_t)cap;
-    const size_t slots[NM_BATCHES] = {S * V, S, S, S * N, cap * K};
-    w.n_slots = 0;
-    for (int b = 0; b < NM_BATCHES; ++b) { w.slots[b] = slots[b]; w.n_slots += slots[b]; }
-    auto layout = [&](Carver<double>& f, Carver<int32_t>& q) {
-        nm_per_slot(w, &NmBatch::pts, f, N);
-        st.sim = st.b[misti::NM_B_INIT].pts;            // the initial batch is the simplices themselves
-        st.scratch = f.take(S * V * N); st.fsim = f.take(S * V); st.fxr = f.take(S);
-        nm_per_slot(w, &NmBatch::split, f, 1);
-        for (int b = 0; b < NM_BATCHES; ++b) w.llk[b] = f.take(w.slots[b]);
-        w.d_starts = f.take(S * N); w.d_llh = f.take(S); w.d_row = f.take(8);
-        st.nit = q.take(S); st.nfev = q.take(S); st.done = q.take(S); st.kind = q.take(S); st.shrunk = q.take(S);
-        w.idx[0] = q.take(S); w.idx[1] = q.take(S);
-        w.cnt = q.take(4);                              // [2] live starts of the iteration in progress / of the next one
-        extra(f, q);
-    };
-    Carver<double> f;
-    Carver<int32_t> q;
-    layout(f, q);
-    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
-    HIP_TRY(c->nm_i32.reserve(q.n * sizeof(int32_t)));
-    if (!c->nm_live_host) {
-        if (hipHostMalloc((void**)&c->nm_live_host, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            c->nm_live_host = nullptr;
-            return fail(MISTI_E_HIP, "pinned allocation for the live-start count failed");
-        }
-    }
-    f = Carver<double>{c->nm_f64.as<double>()};
-    q = Carver<int32_t>{c->nm_i32.as<int32_t>()};
-    layout(f, q);
-    return 0;
-}
-
-// One batch of the rows path through the engine (batched Nelder-Mead, differential evolution): the first n slots of `b` evaluated
-// without replicates into rjafs / rstatus, with each slot's own band bounds and pulse times where the batch carries them, then every
-// point scored against its own row of the table.
-int eval_rows(misti_ctx* c, const NmBatch& b, int64_t n, const double* params, unsigned hints, double* rjafs, int32_t* rstatus,
-              const double* table, const double* consts, double* llk) {
-    if (int r = run_dev(c, n, b.split, params, b.bnd, 0, nullptr, nullptr, rjafs, nullptr, nullptr, rstatus, hints, b.put)) return r;
-    HIP_TRY(misti::launch_llk_rows(n, rjafs, rstatus, b.row, table, consts, llk, c->unfolded, c->stream));
-    return 0;
-}
-
 // One minimisation of every start from w.d_starts (device); leaves best vertices in w.d_starts, their log-likelihood in w.d_llh,
 // SciPy's counters in st.nit / st.nfev and the termination status in st.shrunk (0 converged, 1 evaluation budget, 2 iteration
 // budget).  Asynchronous except for the 4-byte live counts; results are complete when the stream is.
@@ -1233,9 +1398,9 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     NmState& st = w.st;
     const int N = st.N;
     const size_t S = (size_t)st.S, V = (size_t)N + 1;
-    st.maxiter = maxiter; st.maxfun = maxfun; st.xatol = xatol; st.fatol = fatol; st.split = split_time;
+    st.maxiter = maxiter; st.maxfun = maxfun; st.xatol = xatol; st.fatol = fatol;
     hipStream_t sm = c->stream;
-    const bool rows = st.row_of != nullptr;
+    const bool rows = w.rows.a.rows_path();
     // what the search knows about its own batches: one split time for every point (empty slots carry -1), distinct points.
     // The rows path knows less: its chains end at different splits (not one length), and every start from the same initial
     // values submits the same initial simplex - one chain for all of them, computed once up to the largest split (shared).
@@ -1243,20 +1408,16 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     // split times alone: bounds are whole interval indices and never add a fractional interval (and the hint is verified on the
     // device).  RUN_UNSHARED stays off: starts with the same initial values AND the same bounds still share their chains (the
     // chain key holds the bounds).  RUN_ONE_LENGTH stays off: the splits differ, and so do the chain lengths.
-    // The split as a coordinate (misti_nm_solve_split) is a rows path whose splits are never known to be whole (w.whole is false):
+    // The split as a coordinate (misti_nm_solve_split) is a rows path whose splits are never known to be whole (rows.whole is false):
     // no hint at all - points of different starts with equal parameter bits and bounds still share a chain, computed to the largest
     // split among them.
     static const int hint_mask = [] { const char* e = getenv("MISTI_NM_HINTS"); return e ? atoi(e) : 7; }();       // diagnostic: which hints the search passes on
-    const unsigned nm_hints = (rows ? (w.whole ? RUN_INTEGER_SPLITS : 0u)
-                                    : ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH)) & (unsigned)hint_mask;
-    // the first n slots of one batch through the engine: their values against the one data row, or (rows path) each against its own
-    // row, with each slot's own band bounds and pulse times where the batch carries them.  With the split as a coordinate the engine
-    // reads the batch's compact parameter vectors, not the points (NULL for a model without parameters, as misti_eval_batch allows)
+    const unsigned one_hints = ((split_time == std::floor(split_time) ? RUN_INTEGER_SPLITS : 0u) | RUN_UNSHARED | RUN_ONE_LENGTH) & (unsigned)hint_mask;
+    // the first n slots of one batch through the engine: their values against the one data row, or (rows path) each against its own row
     auto eval = [&](int which, int64_t n) -> int {
         const NmBatch& b = st.b[which];
-        const double* params = st.fit_split ? b.par : b.pts;
-        if (!rows) return run_dev(c, n, b.split, params, nullptr, 1, w.d_row, w.llk[which], nullptr, nullptr, nullptr, nullptr, nm_hints);
-        return eval_rows(c, b, n, params, nm_hints, w.rjafs, w.rstatus, w.table, w.consts, w.llk[which]);
+        if (!rows) return run_dev(c, n, b.split, b.pts, nullptr, 1, w.d_row, w.llk[which], nullptr, nullptr, nullptr, nullptr, one_hints);
+        return w.rows.eval(c, b, n, w.llk[which], (unsigned)hint_mask);
     };
     int32_t* cnt = w.cnt;
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
@@ -1265,36 +1426,22 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
     // lie back to back: nm_per_slot)
     const NmBatch& b0 = st.b[NM_B_INIT];
     if (b0.row) HIP_TRY(hipMemsetAsync(b0.row, 0, w.n_slots * sizeof(int32_t), sm));
-    if (b0.bnd) HIP_TRY(hipMemsetAsync(b0.bnd, 0, w.n_slots * st.nb2 * sizeof(int32_t), sm));
-    if (b0.put) HIP_TRY(hipMemsetAsync(b0.put, 0, w.n_slots * st.np * sizeof(int32_t), sm));
+    if (b0.bnd) HIP_TRY(hipMemsetAsync(b0.bnd, 0, w.n_slots * st.src.nb2 * sizeof(int32_t), sm));
+    if (b0.put) HIP_TRY(hipMemsetAsync(b0.put, 0, w.n_slots * st.src.np * sizeof(int32_t), sm));
     HIP_TRY(launch_nm_init(st, w.d_starts, sm));
     if (int r = eval(NM_B_INIT, (int64_t)(S * V))) return r;
     int cur = 0;
     st.idx_next = w.idx[cur]; st.count_next = cnt + cur;
     HIP_TRY(launch_nm_begin(st, w.llk[NM_B_INIT], sm));
-    // The host runs at most two iterations ahead of the device: before issuing iteration k it waits for the event of
-    // iteration k - 2 and reads the count of live starts that iteration left in pinned memory (4 bytes; nothing else of
-    // the search leaves the device).  That count bounds the live starts of iteration k from above - the number only falls -
-    // and sizes its batches; zero -> stop issuing.
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 2; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    volatile int32_t* live_host = c->nm_live_host;
-    live_host[0] = live_host[1] = -1;
-    HIP_TRY(hipMemcpyAsync((void*)&live_host[0], cnt + cur, sizeof(int32_t), hipMemcpyDeviceToHost, sm));     // after nm_begin
-    HIP_TRY(hipEventRecord(ev[0], sm));
-    HIP_TRY(hipEventSynchronize(ev[0]));
-    int64_t bound = live_host[0];
+    Pacer pace(c);
+    int64_t bound = 0;
+    if (int r = pace.start(cnt + cur, bound)) return r;                 // after nm_begin
     int64_t issued = 0, slots = 0, spec_iters = 0;
     bool spec_primed = false;
     const int64_t K = 4 + N;
     for (int it = 0; bound > 0 && it < maxiter; ++it) {
-        const int slot = it & 1;
-        if (it >= 2) {
-            HIP_TRY(hipEventSynchronize(ev[slot]));
-            if (live_host[slot] < bound) bound = live_host[slot];
-            if (bound <= 0) break;
-        }
+        if (int r = pace.bound(it, bound)) return r;
+        if (bound <= 0) break;
         st.idx_cur = w.idx[cur]; st.count_cur = cnt + cur;
         st.idx_next = w.idx[cur ^ 1]; st.count_next = cnt + (cur ^ 1);
         const bool spec = bound <= st.spec_cap;
@@ -1307,7 +1454,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             if (int r = eval(NM_B_SPEC, bound * K)) return r;
             // (no memsets here: the points step zeroes the next slot counter, and the reflection batch's splits are only read by the
             //  three-batch path, which a search never returns to - the number of live starts only falls)
-            HIP_TRY(launch_nm_spec_step(st, bound, w.llk[NM_B_SPEC], (int32_t*)&live_host[slot], sm));
+            HIP_TRY(launch_nm_spec_step(st, bound, w.llk[NM_B_SPEC], pace.word(it), sm));
             ++spec_iters;
         } else {
             if (int r = eval(NM_B_REFLECT, bound)) return r;
@@ -1319,8 +1466,7 @@ int nm_run(misti_ctx* c, NmWork& w, double split_time, double xatol, double fato
             HIP_TRY(hipMemsetAsync(st.b[NM_B_REFLECT].split, 0xBF, (size_t)bound * sizeof(double), sm));
             HIP_TRY(launch_nm_finish(st, bound, w.llk[NM_B_SHRINK], sm));
         }
-        if (!spec) HIP_TRY(hipMemcpyAsync((void*)&live_host[slot], cnt + (cur ^ 1), sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-        HIP_TRY(hipEventRecord(ev[slot], sm));
+        if (int r = pace.record(it, spec ? nullptr : cnt + (cur ^ 1))) return r;
         cur ^= 1;
         ++issued;
         slots += bound;
@@ -1351,110 +1497,63 @@ int nm_copy_back(misti_ctx* c, const NmWork& w, double* x, double* llh, int32_t*
 // +inf - as SciPy sees -JAFSLikelihood.  Leaves the number of coordinates in N and, in `whole`, whether every split time of the
 // rows path is an integer.
 int nm_check(const misti_ctx* c, const misti_search_t& q, int& N, bool& whole) {
-    const bool rows_path = q.split != MISTI_SPLIT_ONE, fit_split = q.split == MISTI_SPLIT_FITTED;
-    const bool per_start = q.split == MISTI_SPLIT_PER_START;
+    const RowsArgs a = rows_args(q);
     const misti_hops_t* h = q.hops;
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
-    if (!q.starts || !q.jsfs || !q.x || !q.llh || (rows_path && !q.rows) || (per_start && !q.split_times))
-        return fail(MISTI_E_ARG, "starts / %s / x / llh is NULL", !rows_path ? "jsfs_row" : (per_start ? "split_times / rows / jsfs" : "rows / jsfs"));
+    if (!q.starts || !q.jsfs || !q.x || !q.llh || (a.rows_path() && !q.rows) || (a.per_start() && !q.split_times))
+        return fail(MISTI_E_ARG, "starts / %s / x / llh is NULL", !a.rows_path() ? "jsfs_row" : (a.per_start() ? "split_times / rows / jsfs" : "rows / jsfs"));
     if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
     if (!h && q.maxiter < 1) return fail(MISTI_E_ARG, "maxiter must be >= 1");
     if (h && h->niter < 0) return fail(MISTI_E_ARG, "negative number of hops");
     if (h && h->niter > 0 && !h->uniforms) return fail(MISTI_E_ARG, "uniforms is NULL");
     if (h && (q.maxiter < 1 || h->nm_maxfev < 1 || h->interval < 1)) return fail(MISTI_E_ARG, "nm_maxiter, nm_maxfev and interval must be >= 1");
-    whole = per_start;                           // a fitted split is whole by accident only: never the integer-splits hint
-    for (int64_t s = 0; rows_path && s < q.n_start; ++s) {
-        if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
-            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
-        if (!per_start) continue;
-        if (!std::isfinite(q.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
-        if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
-    }
-    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
-    N = c->dm.n_param + (fit_split ? 1 : 0);
-    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    // the sort's local arrays hold MISTI_MAX_PARAMS + 1 vertices (misti_nm.hip: sort_simplex)
-    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
-    // (the limits before the scan of the starts: a call that is refused for its size does not read n_start x N doubles first)
-    if (q.n_start > INT32_MAX / (8 * (N + 1))) return fail(MISTI_E_LIMIT, "too many starts for one call");
-    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
-    for (int64_t s = 0; fit_split && s < q.n_start; ++s)
-        for (int k = 0; k < N; ++k)
-            if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
+    if (int r = check_rows(a, whole)) return r;
+    if (int r = check_limits(c, a, 1, "starts", N)) return r;
+    if (a.fit_split()) if (int r = check_finite(q.starts, q.n_start, N)) return r;
     // the box: lo == hi holds a coordinate fixed, +-inf leaves a side open, and a start outside its box is clipped (SciPy only warns)
     if (q.n_box) {
-        if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld starts)", (long long)q.n_box, (long long)q.n_start);
+        if (int r = check_n_box(a, "starts")) return r;
         if (!q.box_lo || !q.box_hi) return fail(MISTI_E_ARG, "box_lo / box_hi is NULL");
-        for (int64_t b = 0; b < q.n_box; ++b)
-            for (int k = 0; k < N; ++k) {
-                const double lo = q.box_lo[b * N + k], hi = q.box_hi[b * N + k];
-                if (lo != lo || hi != hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is NaN", (long long)b, k);
-                if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
-            }
+        for (int64_t b = 0; b < q.n_box; ++b) if (int r = check_box(a, N, b, nullptr)) return r;
     }
     return 0;
 }
 
-// The device state of a checked search with n_start >= 1: the minimiser's state, behind it what each start hands its points on the rows
-// path (split, row, bounds, pulse times; one of each per slot of every batch; the compact parameter array of a fitted split; the
-// table), the box arrays of a boxed search, behind that whatever `extra` takes - still the same two allocations.  Uploads the caller's arrays, issues llh_const over
-// the table and clears the context's work counters.  A path that is not taken allocates and writes nothing: without bounds nothing
-// of the bounds path, and so on.
+// The device state of a checked search with n_start >= 1: the minimiser's own state for n_start simplices of N coordinates, behind it
+// the rows problem (RowsProblem: one of everything a start hands its points per slot of the five batches), behind that whatever
+// `extra` takes - one allocation per type (simplices, points and values | counters and slot tables).  Uploads the caller's arrays and
+// clears the context's work counters.
 template <class Extra>
 int nm_setup(misti_ctx* c, const misti_search_t& q, int N, bool whole, NmWork& w, Extra&& extra) {
-    const bool rows_path = q.split != MISTI_SPLIT_ONE, fit_split = q.split == MISTI_SPLIT_FITTED;
-    const bool per_start = q.split == MISTI_SPLIT_PER_START;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)q.n_start, V = (size_t)N + 1, R = (size_t)q.n_rep;
+    const size_t S = (size_t)q.n_start, V = (size_t)N + 1;
     const size_t cap = (size_t)nm_spec_cap(N), K = 4 + (size_t)N;
     const size_t M = S * V > cap * K ? S * V : cap * K;                         // the largest batch of the search
-    // int32 per bound set and per pulse-time set (none for a model without bands / pulses: the engine has nothing to apply them to),
-    // doubles per compact parameter vector (no width for a model without parameters)
-    const size_t NB2 = rows_path && q.band_bounds ? 2 * (size_t)c->dm.n_band : 0;
-    const size_t NP = rows_path && q.pulse_times ? (size_t)c->dm.n_pulse : 0;
-    const size_t NQ = fit_split ? (size_t)N - 1 : 0;
     misti::NmState& st = w.st;
-    double *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
-    int32_t *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
-    const size_t NX = (size_t)q.n_box * (size_t)N;                  // doubles per box array
-    double *d_lo = nullptr, *d_hi = nullptr;
-    // rows path: what each start hands its points, then one of it per slot of every batch
-    auto rows_layout = [&](Carver<double>& f, Carver<int32_t>& i) {
-        if (rows_path) {
-            if (per_start) d_split = f.take(S);
-            d_table = f.take(R * 8); d_consts = f.take(R); w.rjafs = f.take(M * 7);
-            if (NQ) nm_per_slot(w, &NmBatch::par, f, NQ);
-            d_rowof = i.take(S);
-            nm_per_slot(w, &NmBatch::row, i, 1);
-            w.rstatus = i.take(M);
-            if (NB2) { d_bounds = i.take(S * NB2); nm_per_slot(w, &NmBatch::bnd, i, NB2); }
-            if (NP) { d_pulses = i.take(S * NP); nm_per_slot(w, &NmBatch::put, i, NP); }
-        }
-        if (NX) { d_lo = f.take(NX); d_hi = f.take(NX); }
+    st.S = q.n_start; st.N = N; st.spec_cap = (int64_t)cap;
+    const size_t slots[NM_BATCHES] = {S * V, S, S, S * N, cap * K};
+    w.n_slots = 0;
+    for (int b = 0; b < NM_BATCHES; ++b) { w.slots[b] = slots[b]; w.n_slots += slots[b]; }
+    w.rows = RowsProblem(c, rows_args(q), N, whole);
+    auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        nm_per_slot(st.b, w.slots, NM_BATCHES, &NmBatch::pts, f, N);
+        st.sim = st.b[misti::NM_B_INIT].pts;            // the initial batch is the simplices themselves
+        st.scratch = f.take(S * V * N); st.fsim = f.take(S * V); st.fxr = f.take(S);
+        nm_per_slot(st.b, w.slots, NM_BATCHES, &NmBatch::split, f, 1);
+        for (int b = 0; b < NM_BATCHES; ++b) w.llk[b] = f.take(w.slots[b]);
+        w.d_starts = f.take(S * N); w.d_llh = f.take(S); w.d_row = f.take(8);
+        st.nit = i.take(S); st.nfev = i.take(S); st.done = i.take(S); st.kind = i.take(S); st.shrunk = i.take(S);
+        w.idx[0] = i.take(S); w.idx[1] = i.take(S);
+        w.cnt = i.take(4);                              // [2] live starts of the iteration in progress / of the next one
+        w.rows.layout(f, i, st.b, w.slots, NM_BATCHES, M);
         extra(f, i);
     };
-    if (int r = nm_prepare(c, q.n_start, N, w, rows_layout)) return r;
-    st.fit_split = fit_split ? 1 : 0;
-    st.split_of = d_split; st.row_of = d_rowof;
-    st.bounds_of = d_bounds; st.nb2 = (int)NB2;
-    st.pulses_of = d_pulses; st.np = (int)NP;
-    st.box_lo = d_lo; st.box_hi = d_hi; st.box_per_start = q.n_box > 1 ? 1 : 0;
-    w.table = d_table; w.consts = d_consts; w.whole = whole;
+    if (int r = carve(c, "start", layout)) return r;
+    w.rows.fill(st.src);
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(w.d_starts, q.starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (!rows_path) HIP_TRY(hipMemcpyAsync(w.d_row, q.jsfs, 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (per_start) HIP_TRY(hipMemcpyAsync(d_split, q.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (rows_path) HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NX) {
-        HIP_TRY(hipMemcpyAsync(d_lo, q.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
-        HIP_TRY(hipMemcpyAsync(d_hi, q.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
-    }
-    if (rows_path) {
-        HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-        HIP_TRY(misti::launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));      // once per call, every row
-    }
+    if (!w.rows.a.rows_path()) HIP_TRY(hipMemcpyAsync(w.d_row, q.jsfs, 8 * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (int r = w.rows.upload(c)) return r;
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
     return 0;
 }
@@ -1532,10 +1631,10 @@ int no_box(int64_t n_box, int64_t n_start) {
 // The arguments of misti_de_search, before the first HIP call, in the header's order: what does not depend on the context, the
 // context, what needs the model.  Leaves the number of coordinates in N and whether every split time is an integer in `whole`.
 int de_check(const misti_ctx* c, const misti_de_t& q, int& N, bool& whole) {
-    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
+    const RowsArgs a = rows_args(q);
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
-    if (!q.starts || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.x || !q.llh || (per_start && !q.split_times))
-        return fail(MISTI_E_ARG, "starts / rows / jsfs / box_lo / box_hi / x / llh%s is NULL", per_start ? " / split_times" : "");
+    if (!q.starts || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.x || !q.llh || (a.per_start() && !q.split_times))
+        return fail(MISTI_E_ARG, "starts / rows / jsfs / box_lo / box_hi / x / llh%s is NULL", a.per_start() ? " / split_times" : "");
     if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
     if (q.pop < 4) return fail(MISTI_E_ARG, "pop must be >= 4 (got %d)", (int)q.pop);
     if (q.pop > MISTI_DE_MAX_POP) return fail(MISTI_E_LIMIT, "pop = %d exceeds MISTI_DE_MAX_POP = %d", (int)q.pop, MISTI_DE_MAX_POP);
@@ -1544,31 +1643,11 @@ int de_check(const misti_ctx* c, const misti_de_t& q, int& N, bool& whole) {
     if (!std::isfinite(q.F_lo) || !std::isfinite(q.F_hi) || q.F_lo < 0.0 || q.F_lo > q.F_hi)
         return fail(MISTI_E_ARG, "F must be a finite range 0 <= F_lo <= F_hi (got %g, %g)", q.F_lo, q.F_hi);
     if (!(q.CR >= 0.0 && q.CR <= 1.0)) return fail(MISTI_E_ARG, "CR must lie in [0, 1] (got %g)", q.CR);
-    if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld searches)", (long long)q.n_box, (long long)q.n_start);
-    whole = per_start;
-    for (int64_t s = 0; s < q.n_start; ++s) {
-        if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
-            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
-        if (!per_start) continue;
-        if (!std::isfinite(q.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
-        if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
-    }
-    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
-    N = c->dm.n_param + (fit_split ? 1 : 0);
-    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
-    if (q.n_start > INT32_MAX / 8 / (N + 1) / q.pop) return fail(MISTI_E_LIMIT, "too many searches x members for one call");
-    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
-    for (int64_t s = 0; s < q.n_start; ++s)
-        for (int k = 0; k < N; ++k)
-            if (!std::isfinite(q.starts[s * N + k])) return fail(MISTI_E_ARG, "starts[%lld][%d] is not finite", (long long)s, k);
-    for (int64_t b = 0; b < q.n_box; ++b)
-        for (int k = 0; k < N; ++k) {
-            const double lo = q.box_lo[b * N + k], hi = q.box_hi[b * N + k];
-            if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is not finite (a population search needs a finite box)", (long long)b, k);
-            if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
-            if (!std::isfinite(hi - lo)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: hi - lo is not finite", (long long)b, k);
-        }
+    if (int r = check_n_box(a, "searches")) return r;
+    if (int r = check_rows(a, whole)) return r;
+    if (int r = check_limits(c, a, q.pop, "searches x members", N)) return r;
+    if (int r = check_finite(q.starts, q.n_start, N)) return r;
+    for (int64_t b = 0; b < q.n_box; ++b) if (int r = check_box(a, N, b, "a population search needs a finite box")) return r;
     return 0;
 }
 
@@ -1576,105 +1655,52 @@ int de_check(const misti_ctx* c, const misti_de_t& q, int& N, bool& whole) {
 // the state lies in the search buffers of the context (the batched Nelder-Mead's two allocations).
 int de_run(misti_ctx* c, const misti_de_t& q, int N, bool whole) {
     using namespace misti;
-    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)q.n_start, P = (size_t)q.pop, M = S * P, R = (size_t)q.n_rep;
-    const size_t NB2 = q.band_bounds ? 2 * (size_t)c->dm.n_band : 0, NP = q.pulse_times ? (size_t)c->dm.n_pulse : 0;
-    const size_t NQ = fit_split ? (size_t)N - 1 : 0, NX = (size_t)q.n_box * (size_t)N;
+    const size_t S = (size_t)q.n_start, P = (size_t)q.pop, M = S * P;
+    RowsProblem rows(c, rows_args(q), N, whole);
     DeState st{};
     st.S = q.n_start; st.N = N; st.P = q.pop; st.maxiter = q.maxiter;
     st.tol = q.tol; st.atol = q.atol; st.F_lo = q.F_lo; st.F_hi = q.F_hi; st.CR = q.CR; st.seed = q.seed;
-    st.fit_split = fit_split ? 1 : 0; st.nb2 = (int)NB2; st.np = (int)NP; st.box_per_start = q.n_box > 1 ? 1 : 0;
-    double *llk = nullptr, *d_starts = nullptr, *d_llh = nullptr, *d_popllh = nullptr, *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr;
-    double *rjafs = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_ids = nullptr, *d_points = nullptr;
-    int32_t *rstatus = nullptr, *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr, *d_nfev = nullptr, *d_status = nullptr;
-    int32_t *idx[2] = {nullptr, nullptr}, *cnt = nullptr;
+    double *llk = nullptr, *d_starts = nullptr, *d_llh = nullptr, *d_popllh = nullptr, *d_points = nullptr;
+    int32_t *d_nfev = nullptr, *d_status = nullptr, *idx[2] = {nullptr, nullptr}, *cnt = nullptr;
     auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
         st.b.pts = f.take(M * N); st.pop = f.take(M * N); st.f = f.take(M); st.b.split = f.take(M); llk = f.take(M);
-        if (NQ) st.b.par = f.take(M * NQ);
         d_starts = f.take(S * N); d_llh = f.take(S); d_popllh = f.take(M);
-        if (per_start) d_split = f.take(S);
-        d_table = f.take(R * 8); d_consts = f.take(R); rjafs = f.take(M * 7);
-        d_lo = f.take(NX); d_hi = f.take(NX);
-        if (q.ids) d_ids = f.take(S);                      // uint64 ids and the point counter: 8-byte words of the double buffer
-        d_points = f.take(1);
-        st.b.row = i.take(M); rstatus = i.take(M); d_rowof = i.take(S);
-        if (NB2) { d_bounds = i.take(S * NB2); st.b.bnd = i.take(M * NB2); }
-        if (NP) { d_pulses = i.take(S * NP); st.b.put = i.take(M * NP); }
+        d_points = f.take(1);                              // the point counter: an 8-byte word of the double buffer
         st.best = i.take(S); st.nit = i.take(S); st.done = i.take(S); d_nfev = i.take(S); d_status = i.take(S);
         idx[0] = i.take(S); idx[1] = i.take(S); cnt = i.take(4);
+        rows.layout(f, i, &st.b, &M, 1, M);
     };
-    Carver<double> f;
-    Carver<int32_t> i;
-    layout(f, i);
-    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
-    HIP_TRY(c->nm_i32.reserve(i.n * sizeof(int32_t)));
-    if (!c->nm_live_host) {
-        if (hipHostMalloc((void**)&c->nm_live_host, 4 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            c->nm_live_host = nullptr;
-            return fail(MISTI_E_HIP, "pinned allocation for the live-search count failed");
-        }
-    }
-    f = Carver<double>{c->nm_f64.as<double>()};
-    i = Carver<int32_t>{c->nm_i32.as<int32_t>()};
-    layout(f, i);
-    st.split_of = d_split; st.row_of = d_rowof; st.bounds_of = d_bounds; st.pulses_of = d_pulses;
-    st.box_lo = d_lo; st.box_hi = d_hi;
-    st.ids = reinterpret_cast<const uint64_t*>(d_ids);
+    if (int r = carve(c, "search", layout)) return r;
+    rows.fill(st.src);
     st.points = reinterpret_cast<unsigned long long*>(d_points);
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(d_starts, q.starts, S * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (per_start) HIP_TRY(hipMemcpyAsync(d_split, q.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_lo, q.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_hi, q.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (q.ids) HIP_TRY(hipMemcpyAsync(d_ids, q.ids, S * sizeof(uint64_t), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));
+    if (int r = rows.upload(c)) return r;
     HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(int32_t), sm));
     HIP_TRY(hipMemsetAsync(d_points, 0, sizeof(double), sm));
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    // the rows path's hints (nm_run): integer splits where the caller's are; a fitted split is never known to be whole
-    const unsigned hints = whole ? RUN_INTEGER_SPLITS : 0u;
-    auto eval = [&](int64_t n) { return eval_rows(c, st.b, n, fit_split ? st.b.par : st.b.pts, hints, rjafs, rstatus, d_table, d_consts, llk); };
     // generation 0: every search in its own slot
     HIP_TRY(launch_de_init(st, d_starts, sm));
-    if (int r = eval((int64_t)M)) return r;
+    if (int r = rows.eval(c, st.b, (int64_t)M, llk)) return r;
     int cur = 0;
     st.idx_cur = idx[cur ^ 1]; st.count_cur = cnt + (cur ^ 1);
     st.idx_next = idx[cur]; st.count_next = cnt + cur;
     HIP_TRY(launch_de_select(st, q.n_start, 0, llk, sm));
-    // The host runs at most two generations ahead of the device, as nm_run does: before issuing generation g it waits for the event of
-    // generation g - 2 and reads the count of live searches that generation left in pinned memory - an upper bound, the number only
-    // falls - which sizes the batch; zero: stop issuing.
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ev};
-    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    volatile int32_t* live_host = c->nm_live_host;
-    live_host[0] = live_host[1] = -1;
-    HIP_TRY(hipMemcpyAsync((void*)&live_host[0], cnt + cur, sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipEventRecord(ev[0], sm));
-    HIP_TRY(hipEventSynchronize(ev[0]));
-    int64_t bound = live_host[0];
+    Pacer pace(c);                                         // generations for iterations, live searches for live starts
+    int64_t bound = 0;
+    if (int r = pace.start(cnt + cur, bound)) return r;
     int64_t issued = 0, slots = 0;
     for (int it = 0; bound > 0 && it < q.maxiter; ++it) {
-        const int slot = it & 1;
-        if (it >= 2) {
-            HIP_TRY(hipEventSynchronize(ev[slot]));
-            if (live_host[slot] < bound) bound = live_host[slot];
-            if (bound <= 0) break;
-        }
+        if (int r = pace.bound(it, bound)) return r;
+        if (bound <= 0) break;
         st.idx_cur = idx[cur]; st.count_cur = cnt + cur;
         st.idx_next = idx[cur ^ 1]; st.count_next = cnt + (cur ^ 1);
         HIP_TRY(launch_de_trial(st, bound, it + 1, sm));
-        if (int r = eval(bound * (int64_t)P)) return r;
+        if (int r = rows.eval(c, st.b, bound * (int64_t)P, llk)) return r;
         HIP_TRY(hipMemsetAsync(cnt + (cur ^ 1), 0, sizeof(int32_t), sm));
         HIP_TRY(launch_de_select(st, bound, it + 1, llk, sm));
-        HIP_TRY(hipMemcpyAsync((void*)&live_host[slot], cnt + (cur ^ 1), sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-        HIP_TRY(hipEventRecord(ev[slot], sm));
+        if (int r = pace.record(it, cnt + (cur ^ 1))) return r;
         cur ^= 1;
         ++issued;
         slots += bound;
@@ -1698,10 +1724,10 @@ int de_run(misti_ctx* c, const misti_de_t& q, int N, bool whole) {
 // The arguments of misti_ensemble_sample, before the first HIP call, in the header's order.  Leaves the number of coordinates in N
 // and whether every split time is an integer in `whole`.
 int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
-    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
+    const RowsArgs a = rows_args(q);
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
-    if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.temperature || !q.last || !q.last_llh || (per_start && !q.split_times))
-        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / temperature / last / last_llh%s is NULL", per_start ? " / split_times" : "");
+    if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.temperature || !q.last || !q.last_llh || (a.per_start() && !q.split_times))
+        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / temperature / last / last_llh%s is NULL", a.per_start() ? " / split_times" : "");
     if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
     if (q.walkers < 4 || (q.walkers & 1)) return fail(MISTI_E_ARG, "walkers must be even and >= 4 (got %d)", (int)q.walkers);
     if (q.walkers > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "walkers = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)q.walkers, MISTI_ENS_MAX_WALKERS);
@@ -1712,33 +1738,16 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
     for (int64_t s = 0; s < q.n_temp; ++s)
         if (!std::isfinite(q.temperature[s]) || !(q.temperature[s] > 0.0))
             return fail(MISTI_E_ARG, "temperature[%lld] = %g is not finite and positive", (long long)s, q.temperature[s]);
-    if (q.n_box != 1 && q.n_box != q.n_start) return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld searches)", (long long)q.n_box, (long long)q.n_start);
-    whole = per_start;
-    for (int64_t s = 0; s < q.n_start; ++s) {
-        if (q.rows[s] < 0 || q.rows[s] >= q.n_rep)
-            return fail(MISTI_E_ARG, "rows[%lld] = %d is outside the table (n_rep = %lld)", (long long)s, (int)q.rows[s], (long long)q.n_rep);
-        if (!per_start) continue;
-        if (!std::isfinite(q.split_times[s])) return fail(MISTI_E_ARG, "split_times[%lld] is not finite", (long long)s);
-        if (q.split_times[s] != std::floor(q.split_times[s])) whole = false;
-    }
-    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
-    N = c->dm.n_param + (fit_split ? 1 : 0);
-    if (N < 1) return fail(MISTI_E_ARG, "the model has no optimised parameter");
-    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "the split as a coordinate needs n_param + 1 <= %d (n_param = %d)", MISTI_MAX_PARAMS, c->dm.n_param);
-    if (q.n_start > INT32_MAX / 8 / (N + 1) / q.walkers) return fail(MISTI_E_LIMIT, "too many searches x walkers for one call");
-    if (q.n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "too many replicate rows for one call");
+    if (int r = check_n_box(a, "searches")) return r;
+    if (int r = check_rows(a, whole)) return r;
+    if (int r = check_limits(c, a, q.walkers, "searches x walkers", N)) return r;
     if ((q.chain || q.chain_llh) && q.n_start > 0 && (int64_t)(q.n_step / q.thin) > INT32_MAX / 8 / N / q.walkers / q.n_start)
         return fail(MISTI_E_LIMIT, "the chain of %lld searches x %d kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
                     (long long)q.n_start, (int)(q.n_step / q.thin), (int)q.walkers, N);
     for (int64_t b = 0; b < q.n_box; ++b) {
+        if (int r = check_box(a, N, b, "the sampler's prior is uniform on a finite box")) return r;
         int n_free = 0;
-        for (int k = 0; k < N; ++k) {
-            const double lo = q.box_lo[b * N + k], hi = q.box_hi[b * N + k];
-            if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: a bound is not finite (the sampler's prior is uniform on a finite box)", (long long)b, k);
-            if (lo > hi) return fail(MISTI_E_ARG, "box %lld, coordinate %d: the lower bound %g is greater than the upper bound %g", (long long)b, k, lo, hi);
-            if (!std::isfinite(hi - lo)) return fail(MISTI_E_ARG, "box %lld, coordinate %d: hi - lo is not finite", (long long)b, k);
-            n_free += lo != hi ? 1 : 0;
-        }
+        for (int k = 0; k < N; ++k) n_free += q.box_lo[b * N + k] != q.box_hi[b * N + k] ? 1 : 0;
         if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
     }
     for (int64_t s = 0; s < q.n_start; ++s)
@@ -1758,71 +1767,40 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
 // the end.
 int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole) {
     using namespace misti;
-    const bool per_start = q.split == MISTI_SPLIT_PER_START, fit_split = q.split == MISTI_SPLIT_FITTED;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, R = (size_t)q.n_rep;
-    const size_t NB2 = q.band_bounds ? 2 * (size_t)c->dm.n_band : 0, NP = q.pulse_times ? (size_t)c->dm.n_pulse : 0;
-    const size_t NQ = fit_split ? (size_t)N - 1 : 0, NX = (size_t)q.n_box * (size_t)N, NT = (size_t)q.n_temp;
+    const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp;
     const size_t K = (q.chain || q.chain_llh) ? (size_t)(q.n_step / q.thin) : 0;
+    RowsProblem rows(c, rows_args(q), N, whole);
     EnsState st{};
     st.S = q.n_start; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
     st.temp_per_start = q.n_temp > 1 ? 1 : 0;
-    st.fit_split = fit_split ? 1 : 0; st.nb2 = (int)NB2; st.np = (int)NP; st.box_per_start = q.n_box > 1 ? 1 : 0;
     st.n_keep = (int64_t)K;
-    double *llk = nullptr, *d_init = nullptr, *d_split = nullptr, *d_table = nullptr, *d_consts = nullptr, *rjafs = nullptr;
-    double *d_lo = nullptr, *d_hi = nullptr, *d_temp = nullptr, *d_ids = nullptr, *d_points = nullptr;
-    int32_t *rstatus = nullptr, *d_rowof = nullptr, *d_bounds = nullptr, *d_pulses = nullptr;
+    double *llk = nullptr, *d_init = nullptr, *d_temp = nullptr, *d_points = nullptr;
     auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
         st.b.pts = f.take(M * N); st.x = f.take(M * N); st.llh = f.take(M); st.b.split = f.take(M); llk = f.take(M);
         st.z = f.take(S * H); st.u_acc = f.take(S * H);
-        if (NQ) st.b.par = f.take(M * NQ);
-        d_init = f.take(M * N);
-        if (per_start) d_split = f.take(S);
-        d_table = f.take(R * 8); d_consts = f.take(R); rjafs = f.take(M * 7);
-        d_lo = f.take(NX); d_hi = f.take(NX); d_temp = f.take(NT);
-        if (q.ids) d_ids = f.take(S);                      // uint64 ids and the point counters: 8-byte words of the double buffer
-        d_points = f.take(S);                              // int64 per search
+        d_init = f.take(M * N); d_temp = f.take(NT);
+        d_points = f.take(S);                              // int64 per search: 8-byte words of the double buffer
         if (K) { st.chain = f.take(S * K * W * (size_t)N); st.chain_llh = f.take(S * K * W); }
-        st.b.row = i.take(M); rstatus = i.take(M); d_rowof = i.take(S);
-        if (NB2) { d_bounds = i.take(S * NB2); st.b.bnd = i.take(M * NB2); }
-        if (NP) { d_pulses = i.take(S * NP); st.b.put = i.take(M * NP); }
         st.accepted = i.take(M); st.submitted = i.take(M);
+        rows.layout(f, i, &st.b, &M, 1, M);
     };
-    Carver<double> f;
-    Carver<int32_t> i;
-    layout(f, i);
-    HIP_TRY(c->nm_f64.reserve(f.n * sizeof(double)));
-    HIP_TRY(c->nm_i32.reserve(i.n * sizeof(int32_t)));
-    f = Carver<double>{c->nm_f64.as<double>()};
-    i = Carver<int32_t>{c->nm_i32.as<int32_t>()};
-    layout(f, i);
-    st.split_of = d_split; st.row_of = d_rowof; st.bounds_of = d_bounds; st.pulses_of = d_pulses;
-    st.box_lo = d_lo; st.box_hi = d_hi; st.temp = d_temp;
-    st.ids = reinterpret_cast<const uint64_t*>(d_ids);
+    if (int r = carve(c, "search", layout)) return r;
+    rows.fill(st.src);
+    st.temp = d_temp;
     st.points = reinterpret_cast<long long*>(d_points);
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(d_init, q.init, M * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (per_start) HIP_TRY(hipMemcpyAsync(d_split, q.split_times, S * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_rowof, q.rows, S * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NB2) HIP_TRY(hipMemcpyAsync(d_bounds, q.band_bounds, S * NB2 * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    if (NP) HIP_TRY(hipMemcpyAsync(d_pulses, q.pulse_times, S * NP * sizeof(int32_t), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_lo, q.box_lo, NX * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_hi, q.box_hi, NX * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_temp, q.temperature, NT * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (q.ids) HIP_TRY(hipMemcpyAsync(d_ids, q.ids, S * sizeof(uint64_t), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_table, q.jsfs, R * 8 * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(launch_llh_const(q.n_rep, d_table, d_consts, c->unfolded, sm));
+    if (int r = rows.upload(c)) return r;
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    // the rows path's hints (nm_run): integer splits where the caller's are; a fitted split is never known to be whole
-    const unsigned hints = whole ? RUN_INTEGER_SPLITS : 0u;
-    auto eval = [&](int64_t n) { return eval_rows(c, st.b, n, fit_split ? st.b.par : st.b.pts, hints, rjafs, rstatus, d_table, d_consts, llk); };
     HIP_TRY(launch_ens_init(st, d_init, sm));
-    if (int r = eval((int64_t)M)) return r;
+    if (int r = rows.eval(c, st.b, (int64_t)M, llk)) return r;
     HIP_TRY(launch_ens_accept(st, 0, -1, llk, sm));
     for (int64_t step = 1; step <= q.n_step; ++step)
         for (int half = 0; half < 2; ++half) {
             HIP_TRY(launch_ens_propose(st, step, half, sm));
-            if (int r = eval((int64_t)(S * H))) return r;
+            if (int r = rows.eval(c, st.b, (int64_t)(S * H), llk)) return r;
             HIP_TRY(launch_ens_accept(st, step, half, llk, sm));
         }
     c->nm_iterations = 2 * (int64_t)q.n_step;

@@ -60,30 +60,8 @@ __host__ __device__ __forceinline__ void de_indices(DeWords& g, int i, int P, in
     jrand = (int)boot_index(g.word(2), N);
 }
 
-// What slot t of the batch hands the engine beside its point (misti_nm.hip's put_point / put_none on this search's own fields).
-__device__ __forceinline__ void de_put(const DeState& st, int64_t t, int64_t s, const double* pt) {
-    const NmBatch& b = st.b;
-    const int Q = st.N - 1;
-    b.split[t] = st.split_of ? st.split_of[s] : 0.0;
-    b.row[t] = st.row_of[s];
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[t * st.nb2 + k] = st.bounds_of[s * st.nb2 + k];
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[t * st.np + k] = st.pulses_of[s * st.np + k];
-    if (st.fit_split) { b.split[t] = pt[Q]; for (int k = 0; k < Q; ++k) b.par[t * Q + k] = pt[k]; }
-}
-// no point in this slot: a negative split (refused before anything else of the slot is read), row 0, zeros
-__device__ __forceinline__ void de_none(const DeState& st, int64_t t, double* pt) {
-    const NmBatch& b = st.b;
-    const int Q = st.N - 1;
-    b.split[t] = -1.0;
-    b.row[t] = 0;
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[t * st.nb2 + k] = 0;
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[t * st.np + k] = 0;
-    for (int k = 0; k < st.N; ++k) pt[k] = 0.0;
-    if (st.fit_split) for (int k = 0; k < Q; ++k) b.par[t * Q + k] = 0.0;
-}
-
-__device__ __forceinline__ uint64_t de_id(const DeState& st, int64_t s) { return st.ids ? st.ids[s] : (uint64_t)s; }
-__device__ __forceinline__ int64_t de_box(const DeState& st, int64_t s) { return st.box_per_start ? s * st.N : 0; }
+// What a slot of the batch hands the engine beside its point, a search's box and the id of its stream: misti_device.h's put_point /
+// put_none / box_of / id_of on the search's PointSource.
 
 }  // namespace
 
@@ -97,14 +75,14 @@ void de_init_kernel(DeState st, const double* __restrict__ starts) {
     const int64_t s = t / P;
     const int i = (int)(t - s * P);
     double* pt = st.b.pts + t * N;
-    const int64_t o = de_box(st, s);
-    DeWords g(st.seed, de_id(st, s), 0, i, P);
+    const int64_t o = box_of(st.src, s);
+    DeWords g(st.seed, id_of(st.src, s), 0, i, P);
     for (int k = 0; k < N; ++k) {
-        const double lo = st.box_lo[o + k], hi = st.box_hi[o + k];
+        const double lo = st.src.box_lo[o + k], hi = st.src.box_hi[o + k];
         const double y = i == 0 ? starts[s * N + k] : lo + rn(g.uniform(4 + k) * rn(hi - lo));
         pt[k] = box_clip(y, lo, hi);
     }
-    de_put(st, t, s, pt);
+    put_point(st.src, st.b, t, s, pt);
     if (i == 0) { st.nit[s] = 0; st.done[s] = -1; atomicAdd(st.points, (unsigned long long)P); }
 }
 
@@ -117,18 +95,18 @@ void de_trial_kernel(DeState st, int64_t bound, int gen) {
     const int64_t j = t / P;
     const int i = (int)(t - j * P);
     double* pt = st.b.pts + t * N;
-    if (j >= st.count_cur[0]) { de_none(st, t, pt); return; }           // the host's count of live searches is an upper bound
+    if (j >= st.count_cur[0]) { put_none(st.src, st.b, t, pt); return; }           // the host's count of live searches is an upper bound
     const int64_t s = st.idx_cur[j];
     const double* x = st.pop + s * (int64_t)P * N;
     const double* xb = x + (int64_t)st.best[s] * N;
     const double* xi = x + (int64_t)i * N;
-    DeWords g(st.seed, de_id(st, s), gen, i, P);
+    DeWords g(st.seed, id_of(st.src, s), gen, i, P);
     int r1, r2, jrand;
     de_indices(g, i, P, N, r1, r2, jrand);
     const double F = st.F_lo + rn(g.uniform(3) * rn(st.F_hi - st.F_lo));                  // dither
-    const int64_t o = de_box(st, s);
+    const int64_t o = box_of(st.src, s);
     for (int k = 0; k < N; ++k) {
-        const double lo = st.box_lo[o + k], hi = st.box_hi[o + k];
+        const double lo = st.src.box_lo[o + k], hi = st.src.box_hi[o + k];
         const double u = g.uniform(4 + k);
         double y = xi[k];
         if (lo == hi) y = lo;                                                            // a fixed coordinate
@@ -140,7 +118,7 @@ void de_trial_kernel(DeState st, int64_t bound, int gen) {
         }
         pt[k] = y;
     }
-    de_put(st, t, s, pt);
+    put_point(st.src, st.b, t, s, pt);
     if (i == 0) atomicAdd(st.points, (unsigned long long)P);
 }
 

@@ -104,7 +104,7 @@ __host__ __device__ __forceinline__ int32_t solver_word(int nfev, int status, in
 __device__ __forceinline__ int64_t chain_of(const ChainBufs& cb, int64_t cand) { return cb.of[cand]; }
 __device__ __forceinline__ int chain_len(const ChainBufs& cb, int64_t ch) { return cb.slot_len[cb.chain_slot[ch]]; }
 
-// What the searches (misti_nm.hip, misti_de.hip) share on the device.
+// What the searches (misti_nm.hip, misti_de.hip, misti_ens.hip) share on the device.
 // -JAFSLikelihood as an optimiser sees it; no value = +inf
 __device__ __forceinline__ double objective(double llk) { return (llk == llk && llk > -INFINITY) ? -llk : INFINITY; }
 // the value as rounded so far: opaque to the optimiser, so a product passed through it is never contracted into an fma
@@ -132,18 +132,11 @@ struct NmBatch {
     double* par;            // [slots][N - 1]  the engine's parameter vectors (fit_split only; NULL otherwise, and for a model without a
                             //                 parameter: N == 1, the array has no width)
 };
-// The batches of a search and their slots: the initial simplices [S * V] (pts is `sim` itself); per iteration, live starts compacted,
-// the reflection points [S], the expansion / contraction points [S] and the shrunk vertices [S * N]; or, speculative iterations (few
-// live starts: latency-bound), every point SciPy COULD ask for in the iteration as one batch [spec_cap * (4 + N)]: per live start the
-// reflection, expansion, outside / inside contraction and the N shrunk vertices.
-enum { NM_B_INIT, NM_B_REFLECT, NM_B_SECOND, NM_B_SHRINK, NM_B_SPEC, NM_BATCHES };
-struct NmState {
-    int64_t S;              // starts
-    int N;                  // parameters
-    int maxiter;
-    int64_t maxfun;
-    double xatol, fatol;
-    double split;           // the split time every point is evaluated at (unless split_of is set)
+// What a search hands its points beyond their coordinates: start (or search) s of Nelder-Mead, differential evolution and the ensemble
+// sampler alike.  A per-start field is added HERE (and to put_point / put_none below, and to RowsProblem on the host) - nowhere else.
+struct PointSource {
+    int N;                  // coordinates of a point
+    double split;           // the split time every point is evaluated at (unless split_of is set; MISTI_SPLIT_ONE only, 0 otherwise)
     const double* split_of; // [S] or NULL: the split time of each start's points (misti_nm_solve_rows); NULL: `split` for all
     const int32_t* row_of;  // [S] or NULL: the replicate row of each start's points; set together with split_of
     const int32_t* bounds_of;   // [S][nb2] or NULL: the band bounds of each start's points (misti_nm_solve_bounds); only with row_of
@@ -156,10 +149,55 @@ struct NmState {
                             // written or read
     // The box (misti_nm_solve_box / misti_basinhopping_box): SciPy's Nelder-Mead with bounds=Bounds(lo, hi).  Every point the search lays
     // out is clipped to [lo, hi] per coordinate before put_point() reads it, a fitted split (coordinate N - 1) like any other.  Both NULL:
-    // no box - nothing of it is allocated, read or written, and a kernel branches on it by one wave-uniform pointer test.
+    // no box - nothing of it is allocated, read or written, and a kernel branches on it by one wave-uniform pointer test.  The population
+    // searches always have one: finite, lo <= hi.
     const double* box_lo;   // [N], or [S][N] with box_per_start; NULL: no box
     const double* box_hi;   // the same shape; NULL together with box_lo
     int box_per_start;      // 1: start s has its own box, rows s of the two arrays; 0: one box for every start
+    const uint64_t* ids;    // [S] or NULL: the random stream of search s is Philox(key=[seed, ids[s]]); NULL: ids[s] = s
+};
+// where start s's box begins in box_lo / box_hi, and the id of its random stream
+__device__ __forceinline__ int64_t box_of(const PointSource& src, int64_t s) { return src.box_per_start ? s * src.N : 0; }
+__device__ __forceinline__ uint64_t id_of(const PointSource& src, int64_t s) { return src.ids ? src.ids[s] : (uint64_t)s; }
+// What a slot of a batch hands the engine beside its point.  put_point: slot j of batch b carries start s's point pt (the slot's entry
+// of b.pts, already written) - the start's split time, replicate row, band bounds and pulse times: one split for all starts (misti_nm_solve), or per
+// start (misti_nm_solve_rows: row_of set; misti_nm_solve_bounds: bounds_of as well; misti_nm_solve_pulses: pulses_of).  With the split
+// as a coordinate (misti_nm_solve_split, fit_split) the split is the point's own last coordinate and the coordinates before it go to
+// the compact parameter array the engine reads.  Arrays of a path that is not taken are NULL and nothing is written to them.
+__device__ __forceinline__ void put_point(const PointSource& src, const NmBatch& b, int64_t j, int64_t s, const double* pt) {
+    const int P = src.N - 1;
+    b.split[j] = src.split_of ? src.split_of[s] : src.split;
+    if (src.row_of) b.row[j] = src.row_of[s];
+    if (src.bounds_of) for (int k = 0; k < src.nb2; ++k) b.bnd[j * src.nb2 + k] = src.bounds_of[s * src.nb2 + k];
+    if (src.pulses_of) for (int k = 0; k < src.np; ++k) b.put[j * src.np + k] = src.pulses_of[s * src.np + k];
+    if (src.fit_split) { b.split[j] = pt[P]; for (int k = 0; k < P; ++k) b.par[j * P + k] = pt[k]; }
+}
+// put_none: slot j carries no point (a start that needs none in this phase) - a negative split, row 0, all-zero bounds, pulse times and
+// parameters, a zeroed point: no row index ever leaves the table, and a negative split is refused (setup_candidate) before any bound or
+// time of its slot is read.  pt: the slot's entry of b.pts, or NULL for a slot that has no START either: such a slot keeps whatever
+// point and parameters it held.
+__device__ __forceinline__ void put_none(const PointSource& src, const NmBatch& b, int64_t j, double* pt) {
+    const int P = src.N - 1;
+    b.split[j] = -1.0;
+    if (src.row_of) b.row[j] = 0;
+    if (src.bounds_of) for (int k = 0; k < src.nb2; ++k) b.bnd[j * src.nb2 + k] = 0;
+    if (src.pulses_of) for (int k = 0; k < src.np; ++k) b.put[j * src.np + k] = 0;
+    if (!pt) return;
+    for (int k = 0; k < src.N; ++k) pt[k] = 0.0;
+    if (src.fit_split) for (int k = 0; k < P; ++k) b.par[j * P + k] = 0.0;
+}
+// The batches of a search and their slots: the initial simplices [S * V] (pts is `sim` itself); per iteration, live starts compacted,
+// the reflection points [S], the expansion / contraction points [S] and the shrunk vertices [S * N]; or, speculative iterations (few
+// live starts: latency-bound), every point SciPy COULD ask for in the iteration as one batch [spec_cap * (4 + N)]: per live start the
+// reflection, expansion, outside / inside contraction and the N shrunk vertices.
+enum { NM_B_INIT, NM_B_REFLECT, NM_B_SECOND, NM_B_SHRINK, NM_B_SPEC, NM_BATCHES };
+struct NmState {
+    int64_t S;              // starts
+    int N;                  // parameters
+    int maxiter;
+    int64_t maxfun;
+    double xatol, fatol;
+    PointSource src;        // what a start hands its points
     // per start
     double* sim;            // [S][V][N] simplices, best vertex first after every sort
     double* fsim;           // [S][V]    objective (-llk, +inf where the engine has no value)
@@ -218,8 +256,8 @@ hipError_t launch_bh_result(const BhState& bh, double* x, double* llh, hipStream
 
 // Differential evolution per search (misti_de.hip; the rule is optimize.differential_evolution_rule, operation for operation):
 // everything a search owns, in HBM.  A generation of every live search is ONE engine batch of P points per search; batch slot
-// j * P + i carries member i of the search in live slot j.  What a search hands its points (split, row, bounds, pulse times, the box)
-// are NmState's fields of the same names, and the batch is an NmBatch: the engine sees what a Nelder-Mead batch hands it.
+// j * P + i carries member i of the search in live slot j.  What a search hands its points (split, row, bounds, pulse times, the box, its id) is a
+// PointSource, and the batch is an NmBatch: the engine sees what a Nelder-Mead batch hands it.
 struct DeState {
     int64_t S;              // searches
     int N, P;               // coordinates, members
@@ -227,17 +265,7 @@ struct DeState {
     double tol, atol;       // stop: var(f) <= (atol + tol |mean(f)|)^2 over members that all have a value
     double F_lo, F_hi, CR;
     uint64_t seed;
-    const uint64_t* ids;    // [S] or NULL: the stream of search s is Philox(key=[seed, ids[s]]); NULL: ids[s] = s
-    const double* split_of; // [S] or NULL (fit_split)
-    const int32_t* row_of;  // [S]
-    const int32_t* bounds_of;   // [S][nb2] or NULL
-    int nb2;
-    const int32_t* pulses_of;   // [S][np] or NULL
-    int np;
-    int fit_split;          // 1: the last coordinate is the point's split time, the N - 1 before it go to the batch's compact `par`
-    const double* box_lo;   // [N], or [S][N] with box_per_start: finite, lo <= hi
-    const double* box_hi;
-    int box_per_start;
+    PointSource src;        // what a search hands its points; always with rows and a finite box
     double* pop;            // [S][P][N] the population
     double* f;              // [S][P]    its objective (-llk, +inf where the engine has no value)
     int32_t* best;          // [S] the member with the lowest objective (ties: the lowest index)
@@ -262,26 +290,16 @@ hipError_t launch_de_result(const DeState& st, double* x, double* llh, int32_t* 
 // Ensemble sampler per search (misti_ens.hip; the rule is optimize.ensemble_rule, operation for operation): everything a search
 // owns, in HBM.  A half-step of every search is ONE engine batch of H = W / 2 points per search; batch slot s * H + m carries the
 // proposal of walker half * H + m of search s (the initial ensemble: slot s * W + i, walker i).  No search ever stops, so slots are
-// never compacted.  What a search hands its points are NmState's fields of the same names, and the batch is an NmBatch.
+// never compacted.  What a search hands its points is a PointSource, and the batch is an NmBatch.
 struct EnsState {
     int64_t S;              // searches
     int N, W;               // coordinates, walkers (even)
     int thin;               // the ensemble after steps thin, 2 thin, ... is kept
     double a, am1;          // the stretch's scale and a - 1 as rounded once
     uint64_t seed;
-    const uint64_t* ids;    // [S] or NULL: the stream of search s is Philox(key=[seed, ids[s]]); NULL: ids[s] = s
     const double* temp;     // [1], or [S] with temp_per_start
     int temp_per_start;
-    const double* split_of; // [S] or NULL (fit_split)
-    const int32_t* row_of;  // [S]
-    const int32_t* bounds_of;   // [S][nb2] or NULL
-    int nb2;
-    const int32_t* pulses_of;   // [S][np] or NULL
-    int np;
-    int fit_split;          // 1: the last coordinate is the point's split time, the N - 1 before it go to the batch's compact `par`
-    const double* box_lo;   // [N], or [S][N] with box_per_start: finite, lo <= hi
-    const double* box_hi;
-    int box_per_start;
+    PointSource src;        // what a search hands its points; always with rows and a finite box
     double* x;              // [S][W][N] the ensemble
     double* llh;            // [S][W]    its log-likelihood (-inf where the engine has no value)
     double* z;              // [S * H]   the stretch of the slot's proposal; negative: rejected in advance, the slot carries no point

@@ -31,30 +31,9 @@ namespace {
 
 constexpr int ENS_THREADS = 256;
 
-// What slot t of the batch hands the engine beside its point (misti_de.hip's de_put / de_none on this search's own fields).
-__device__ __forceinline__ void ens_put(const EnsState& st, int64_t t, int64_t s, const double* pt) {
-    const NmBatch& b = st.b;
-    const int Q = st.N - 1;
-    b.split[t] = st.split_of ? st.split_of[s] : 0.0;
-    b.row[t] = st.row_of[s];
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[t * st.nb2 + k] = st.bounds_of[s * st.nb2 + k];
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[t * st.np + k] = st.pulses_of[s * st.np + k];
-    if (st.fit_split) { b.split[t] = pt[Q]; for (int k = 0; k < Q; ++k) b.par[t * Q + k] = pt[k]; }
-}
-// no point in this slot: a negative split, row 0, zeros
-__device__ __forceinline__ void ens_none(const EnsState& st, int64_t t, double* pt) {
-    const NmBatch& b = st.b;
-    const int Q = st.N - 1;
-    b.split[t] = -1.0;
-    b.row[t] = 0;
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[t * st.nb2 + k] = 0;
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[t * st.np + k] = 0;
-    for (int k = 0; k < st.N; ++k) pt[k] = 0.0;
-    if (st.fit_split) for (int k = 0; k < Q; ++k) b.par[t * Q + k] = 0.0;
-}
+// What a slot of the batch hands the engine beside its point, a search's box and the id of its stream: misti_device.h's put_point /
+// put_none / box_of / id_of on the search's PointSource.
 
-__device__ __forceinline__ uint64_t ens_id(const EnsState& st, int64_t s) { return st.ids ? st.ids[s] : (uint64_t)s; }
-__device__ __forceinline__ int64_t ens_box(const EnsState& st, int64_t s) { return st.box_per_start ? s * st.N : 0; }
 // the engine's value as the sampler keeps it: -inf where there is none
 __device__ __forceinline__ double ens_value(double llk) { return ens_has(llk) ? llk : -INFINITY; }
 
@@ -70,7 +49,7 @@ void ens_init_kernel(EnsState st, const double* __restrict__ init) {
     double* pt = st.b.pts + t * N;
     double* x = st.x + t * N;
     for (int k = 0; k < N; ++k) { const double v = init[t * N + k]; pt[k] = v; x[k] = v; }
-    ens_put(st, t, s, pt);
+    put_point(st.src, st.b, t, s, pt);
 }
 
 // Half `half` of step `step`: walker i = half H + m moves against walker j of the other half.  Thread = (search, m).
@@ -81,23 +60,23 @@ void ens_propose_kernel(EnsState st, int64_t step, int half) {
     if (t >= st.S * H) return;
     const int64_t s = t / H;
     const int i = half * H + (int)(t - s * H);
-    const EnsDraw dr = ens_draw(st.seed, ens_id(st, s), step, i, W);
+    const EnsDraw dr = ens_draw(st.seed, id_of(st.src, s), step, i, W);
     const int j = (1 - half) * H + dr.partner;
     const double* xi = st.x + (s * W + i) * (int64_t)N;
     const double* xj = st.x + (s * W + j) * (int64_t)N;
     const double z = ens_stretch(st.a, st.am1, dr.u_z);
-    const int64_t o = ens_box(st, s);
+    const int64_t o = box_of(st.src, s);
     double* pt = st.b.pts + t * N;
     bool inside = true;
     for (int k = 0; k < N; ++k) {
-        const double lo = st.box_lo[o + k], hi = st.box_hi[o + k];
+        const double lo = st.src.box_lo[o + k], hi = st.src.box_hi[o + k];
         const double y = lo == hi ? lo : xj[k] + ens_rn(z * (xi[k] - xj[k]));
         inside = inside && y >= lo && y <= hi;                                 // a NaN is outside
         pt[k] = y;
     }
     st.u_acc[t] = dr.u_acc;
-    if (inside) { st.z[t] = z; ens_put(st, t, s, pt); }
-    else { st.z[t] = -1.0; ens_none(st, t, pt); }
+    if (inside) { st.z[t] = z; put_point(st.src, st.b, t, s, pt); }
+    else { st.z[t] = -1.0; put_none(st.src, st.b, t, pt); }
 }
 
 // The values of the batch are in.  half < 0: the initial ensemble's, thread = (search, walker).  Otherwise thread = (search, m): the
@@ -120,9 +99,9 @@ void ens_accept_kernel(EnsState st, int64_t step, int half, const double* __rest
     const int64_t wi = s * W + i;
     const double z = st.z[t];
     if (z > 0.0) {                                          // the proposal was evaluated
-        const int64_t o = ens_box(st, s);
+        const int64_t o = box_of(st.src, s);
         int d = -1;
-        for (int k = 0; k < N; ++k) d += st.box_lo[o + k] != st.box_hi[o + k] ? 1 : 0;
+        for (int k = 0; k < N; ++k) d += st.src.box_lo[o + k] != st.src.box_hi[o + k] ? 1 : 0;
         const double T = st.temp[st.temp_per_start ? s : 0];
         const double v = ens_value(llk[t]);
         st.submitted[wi] = st.submitted[wi] + 1;

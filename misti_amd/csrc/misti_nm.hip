@@ -19,7 +19,7 @@
 // (which keeps its old value) - the simplex is sorted and the loop ends with warnflag 1.  Restated here per evaluation
 // (NM_CUT, NmState::shrunk): nfev never exceeds maxfev.
 //
-// The box (NmState::box_lo / box_hi; misti_nm_solve_box, misti_basinhopping_box): SciPy's bounds=Bounds(lo, hi) for this method is a rule
+// The box (PointSource::box_lo / box_hi; misti_nm_solve_box, misti_basinhopping_box): SciPy's bounds=Bounds(lo, hi) for this method is a rule
 // of a dozen lines, restated here point by point - x0 is clipped, the initial simplex is built from the clipped x0, a vertex beyond its
 // upper bound is reflected into the interior (2 ub - x, one rounding after the product) and the simplex clipped, and every reflection,
 // expansion, contraction and shrunk vertex is clipped (np.clip per coordinate: box_clip) before put_point() hands it on; with the split
@@ -44,44 +44,16 @@ namespace {
 constexpr double NM_RHO = 1.0, NM_CHI = 2.0, NM_PSI = 0.5, NM_SIGMA = 0.5;
 constexpr double NM_NONZDELT = 0.05, NM_ZDELT = 0.00025;
 
-// objective(), rn() and box_clip() are misti_device.h's: the population search (misti_de.hip) rounds, clips and scores by the same three.
-// Where start s's box begins in box_lo / box_hi, and coordinate k of one of its points clipped to it (SciPy: np.clip(x, lower_bound,
-// upper_bound) on every point before func sees it); without a box the value as it is.
-__device__ __forceinline__ int64_t box_of(const NmState& st, int64_t s) { return st.box_per_start ? s * st.N : 0; }
+// objective(), rn(), box_clip(), box_of(), put_point() and put_none() are misti_device.h's: the population searches (misti_de.hip,
+// misti_ens.hip) round, clip, score and lay out their slots by the same functions.
+// Coordinate k of a point of the start whose box begins at o = box_of(st.src, s), clipped to it (SciPy: np.clip(x, lower_bound,
+// upper_bound) on every point before func sees it); without a box - only this search ever runs without one - the value as it is.
 __device__ __forceinline__ double boxed(const NmState& st, int64_t o, int k, double v) {
-    return st.box_lo ? box_clip(v, st.box_lo[o + k], st.box_hi[o + k]) : v;
+    return st.src.box_lo ? box_clip(v, st.src.box_lo[o + k], st.src.box_hi[o + k]) : v;
 }
 
 // a*x - b*y with a rounding after each product and after the difference (NumPy elementwise semantics)
 __device__ __forceinline__ double lin2(double a, double x, double b, double y) { return rn(a * x) - rn(b * y); }
-
-// What a slot of a batch hands the engine beside its point.  put_point: slot j of batch b carries start s's point pt (the slot's entry
-// of b.pts, already written) - the start's split time, replicate row, band bounds and pulse times: one split for all starts (misti_nm_solve), or per
-// start (misti_nm_solve_rows: row_of set; misti_nm_solve_bounds: bounds_of as well; misti_nm_solve_pulses: pulses_of).  With the split
-// as a coordinate (misti_nm_solve_split, fit_split) the split is the point's own last coordinate and the coordinates before it go to
-// the compact parameter array the engine reads.  Arrays of a path that is not taken are NULL and nothing is written to them.
-__device__ __forceinline__ void put_point(const NmState& st, const NmBatch& b, int64_t j, int64_t s, const double* pt) {
-    const int P = st.N - 1;
-    b.split[j] = st.split_of ? st.split_of[s] : st.split;
-    if (st.row_of) b.row[j] = st.row_of[s];
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[j * st.nb2 + k] = st.bounds_of[s * st.nb2 + k];
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[j * st.np + k] = st.pulses_of[s * st.np + k];
-    if (st.fit_split) { b.split[j] = pt[P]; for (int k = 0; k < P; ++k) b.par[j * P + k] = pt[k]; }
-}
-// put_none: slot j carries no point (a start that needs none in this phase) - a negative split, row 0, all-zero bounds, pulse times and
-// parameters, a zeroed point: no row index ever leaves the table, and a negative split is refused (setup_candidate) before any bound or
-// time of its slot is read.  pt: the slot's entry of b.pts, or NULL for a slot that has no START either: such a slot keeps whatever
-// point and parameters it held.
-__device__ __forceinline__ void put_none(const NmState& st, const NmBatch& b, int64_t j, double* pt) {
-    const int P = st.N - 1;
-    b.split[j] = -1.0;
-    if (st.row_of) b.row[j] = 0;
-    if (st.bounds_of) for (int k = 0; k < st.nb2; ++k) b.bnd[j * st.nb2 + k] = 0;
-    if (st.pulses_of) for (int k = 0; k < st.np; ++k) b.put[j * st.np + k] = 0;
-    if (!pt) return;
-    for (int k = 0; k < st.N; ++k) pt[k] = 0.0;
-    if (st.fit_split) for (int k = 0; k < P; ++k) b.par[j * P + k] = 0.0;
-}
 
 // numpy.argsort on <= 17 values: insertion sort (stable), NaN last
 __device__ __forceinline__ bool before(double a, double b) { return a < b || (b != b && a == a); }
@@ -144,9 +116,9 @@ __device__ void next_reflection(const NmState& st, int64_t s) {
     st.idx_next[slot] = (int32_t)s;
     const NmBatch& b = st.b[NM_B_REFLECT];
     double* p1 = b.pts + (int64_t)slot * N;
-    const int64_t o = box_of(st, s);
+    const int64_t o = box_of(st.src, s);
     for (int k = 0; k < N; ++k) p1[k] = boxed(st, o, k, lin2(1.0 + NM_RHO, centroid(x, N, k), NM_RHO, x[N * N + k]));     // xr
-    put_point(st, b, slot, s, p1);
+    put_point(st.src, b, slot, s, p1);
 }
 
 }  // namespace
@@ -158,19 +130,19 @@ void nm_init_kernel(NmState st, const double* __restrict__ starts) {
     if (s >= st.S) return;
     const int N = st.N, V = N + 1;
     double* x = st.sim + s * (int64_t)V * N;
-    const int64_t o = box_of(st, s);
+    const int64_t o = box_of(st.src, s);
     for (int i = 0; i < V; ++i) {
         for (int k = 0; k < N; ++k) {
             double y = boxed(st, o, k, starts[s * N + k]);             // SciPy clips x0 before it builds the simplex
             if (i == k + 1) y = (y != 0.0) ? rn((1.0 + NM_NONZDELT) * y) : NM_ZDELT;
-            if (st.box_lo) {                                           // a vertex beyond the upper bound is reflected into the interior
-                const double hi = st.box_hi[o + k];                    // (sim > ub -> 2 ub - sim), then the whole simplex is clipped
+            if (st.src.box_lo) {                                           // a vertex beyond the upper bound is reflected into the interior
+                const double hi = st.src.box_hi[o + k];                    // (sim > ub -> 2 ub - sim), then the whole simplex is clipped
                 if (y > hi) y = rn(2.0 * hi) - y;
-                y = box_clip(y, st.box_lo[o + k], hi);
+                y = box_clip(y, st.src.box_lo[o + k], hi);
             }
             x[i * N + k] = y;
         }
-        put_point(st, st.b[NM_B_INIT], s * V + i, s, x + i * N);
+        put_point(st.src, st.b[NM_B_INIT], s * V + i, s, x + i * N);
     }
     st.nit[s] = 1; st.nfev[s] = 0; st.done[s] = -1;
 }
@@ -195,7 +167,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     if (i >= bound) return;
     const int N = st.N, V = N + 1;
     const NmBatch& b = st.b[NM_B_SECOND];
-    if (i >= st.count_cur[0]) { put_none(st, b, i, nullptr); return; }         // no start in this slot
+    if (i >= st.count_cur[0]) { put_none(st.src, b, i, nullptr); return; }         // no start in this slot
     const int64_t s = st.idx_cur[i];
     double* p2 = b.pts + i * N;
     const double* f = st.fsim + s * V;
@@ -203,7 +175,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     const double fxr = objective(llk1[i]);
     st.fxr[s] = fxr;
     st.nfev[s] += 1;
-    const int64_t o = box_of(st, s);
+    const int64_t o = box_of(st.src, s);
     int kind;
     if (fxr < f[0]) {
         kind = NM_EXPAND;
@@ -219,7 +191,7 @@ void nm_reflect_kernel(NmState st, int64_t bound, const double* __restrict__ llk
     }
     if (kind != NM_REFLECT && (int64_t)st.nfev[s] >= st.maxfun) kind = NM_CUT;      // the second point's evaluation is refused
     st.kind[s] = kind;
-    if (kind != NM_REFLECT && kind != NM_CUT) put_point(st, b, i, s, p2); else put_none(st, b, i, p2);
+    if (kind != NM_REFLECT && kind != NM_CUT) put_point(st.src, b, i, s, p2); else put_none(st.src, b, i, p2);
 }
 
 // the second value is in: replace the worst vertex, or shrink (then the N shrunk vertices are the third batch)
@@ -230,7 +202,7 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
     const int N = st.N, V = N + 1;
     const NmBatch& b = st.b[NM_B_SHRINK];
     double* p3 = b.pts + i * (int64_t)N * N;
-    if (i >= st.count_cur[0]) { for (int j = 0; j < N; ++j) put_none(st, b, i * N + j, nullptr); return; }
+    if (i >= st.count_cur[0]) { for (int j = 0; j < N; ++j) put_none(st.src, b, i * N + j, nullptr); return; }
     const int64_t s = st.idx_cur[i];
     double* f = st.fsim + s * V;
     double* x = st.sim + s * (int64_t)V * N;
@@ -256,7 +228,7 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
         const int64_t left = st.maxfun - (int64_t)st.nfev[s];
         n_eval = left >= N ? N : (left > 0 ? (int)left : 0);
         const int n_move = n_eval < N ? n_eval + 1 : N;      // SciPy moves sim[j] before the call that is refused
-        const int64_t o = box_of(st, s);
+        const int64_t o = box_of(st.src, s);
         for (int j = 1; j <= n_move; ++j)
             for (int k = 0; k < N; ++k) {
                 const double v = boxed(st, o, k, x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k])));   // sim[0] + sigma (sim[j] - sim[0]), clipped
@@ -265,8 +237,8 @@ void nm_accept_kernel(NmState st, int64_t bound, const double* __restrict__ llk2
             }
     }
     st.shrunk[s] = shrink ? 1 + n_eval : 0;
-    for (int j = 0; j < n_eval; ++j) put_point(st, b, i * N + j, s, p3 + j * N);
-    for (int j = n_eval; j < N; ++j) put_none(st, b, i * N + j, p3 + j * N);
+    for (int j = 0; j < n_eval; ++j) put_point(st.src, b, i * N + j, s, p3 + j * N);
+    for (int j = n_eval; j < N; ++j) put_none(st.src, b, i * N + j, p3 + j * N);
 }
 
 // shrink values are in: end of the iteration (count, sort) and the top of the next one
@@ -301,11 +273,11 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
     const int N = st.N, V = N + 1, K = 4 + N;
     const NmBatch& b = st.b[NM_B_SPEC];           // start i's points are its slots i * K + j
     double* pt = b.pts + i * (int64_t)K * N;
-    if (i >= st.count_cur[0]) { for (int j = 0; j < K; ++j) put_none(st, b, i * K + j, pt + j * N); return; }
+    if (i >= st.count_cur[0]) { for (int j = 0; j < K; ++j) put_none(st.src, b, i * K + j, pt + j * N); return; }
     const int64_t s = st.idx_cur[i];
     const double* x = st.sim + s * (int64_t)V * N;
     const double* p1 = st.b[NM_B_REFLECT].pts + i * N;
-    const int64_t o = box_of(st, s);
+    const int64_t o = box_of(st.src, s);
     for (int k = 0; k < N; ++k) {
         const double xb = centroid(x, N, k), w = x[N * N + k];
         pt[0 * N + k] = p1[k];                                                            // xr (next_reflection: clipped there)
@@ -314,7 +286,7 @@ __device__ __forceinline__ void spec_points(const NmState& st, int64_t bound, in
         pt[3 * N + k] = boxed(st, o, k, rn((1.0 - NM_PSI) * xb) + rn(NM_PSI * w));                         // xcc
         for (int j = 1; j < V; ++j) pt[(3 + j) * N + k] = boxed(st, o, k, x[k] + rn(NM_SIGMA * rn(x[j * N + k] - x[k])));   // shrunk vertex j
     }
-    for (int j = 0; j < K; ++j) put_point(st, b, i * K + j, s, pt + j * N);
+    for (int j = 0; j < K; ++j) put_point(st.src, b, i * K + j, s, pt + j * N);
 }
 
 __global__ __launch_bounds__(256)

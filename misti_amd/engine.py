@@ -504,6 +504,20 @@ class Engine:
         _lib.check(self._lib.misti_nm_last_spec_iterations(self._ctx, C.byref(spec)))
         return dict(iterations_issued=int(stats[0]), slots=int(stats[1]), speculative_iterations=int(spec.value))
 
+    def _rows_problem(self, S, N, table, split_times, rows, band_bounds, pulse_times, box, ids):
+        """What ``misti_search_t``, ``misti_de_t`` and ``misti_ens_t`` share, marshalled once: the arrays (to be kept alive until the
+        call returns) and the descriptor fields they fill.  ``table`` is already an array (``[8]``: one data row, or ``[n_rep][8]``)."""
+        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
+        lo, hi = _box_arrays(box, N) if box is not None else (None, None)
+        keep = dict(jsfs=table, split_times=_f64(split_times, (S,)) if split_times is not None else None,
+                    rows=i32(rows, (S,)) if rows is not None else None,
+                    band_bounds=i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None,
+                    pulse_times=i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None,
+                    box_lo=lo, box_hi=hi, ids=np.ascontiguousarray(np.asarray(ids).reshape(S), dtype=np.uint64) if ids is not None else None)
+        fields = {k: v.ctypes.data if v is not None else None for k, v in keep.items()}
+        fields.update(n_start=S, n_rep=1 if table.ndim == 1 else table.shape[0], n_box=0 if lo is None else lo.shape[0])
+        return keep, fields
+
     def search(self, starts, table, *, split_time=None, split_times=None, rows=None, band_bounds=None, pulse_times=None, box=None,
                hops=None, rngs=None, xatol=1e-4, fatol=1e-4, maxiter=None):
         """``misti_search``: every batched search and every basin hopping is this call (``misti_search_t`` in include/misti_hip.h
@@ -519,21 +533,14 @@ class Engine:
         st = _f64(starts, (-1, N))
         S = st.shape[0]
         ptr = lambda a: a.ctypes.data if a is not None else None
-        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
-        tab = _f64(table, (8,) if one else (-1, 8))
-        sp = _f64(split_times, (S,)) if split_times is not None else None
-        r_of = i32(rows, (S,)) if rows is not None else None
-        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
-        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
-        lo, hi = _box_arrays(box, N) if box is not None else (None, None)
+        arrays, fields = self._rows_problem(S, N, _f64(table, (8,) if one else (-1, 8)), split_times, rows, band_bounds, pulse_times, box, None)
+        del fields["ids"]
         x, llh = np.empty((S, N)), np.empty(S)
         counters = dict(zip(("nit", "nfev", "status") if hops is None else ("nfev", "failures", "accepted"),
                             (np.empty(S, dtype=np.int32) for _ in range(3))))
-        q = _lib.Search(size=C.sizeof(_lib.Search), split=_lib.SPLIT_ONE if one else _lib.SPLIT_PER_START if sp is not None else _lib.SPLIT_FITTED,
-                        split_time=float(split_time) if one else 0.0, split_times=ptr(sp), n_start=S, starts=ptr(st), rows=ptr(r_of),
-                        n_rep=1 if one else tab.shape[0], jsfs=ptr(tab), band_bounds=ptr(bb), pulse_times=ptr(pt),
-                        n_box=0 if lo is None else lo.shape[0], box_lo=ptr(lo), box_hi=ptr(hi), xatol=float(xatol), fatol=float(fatol),
-                        x=ptr(x), llh=ptr(llh))
+        q = _lib.Search(size=C.sizeof(_lib.Search), split=_lib.SPLIT_ONE if one else _lib.SPLIT_PER_START if split_times is not None else _lib.SPLIT_FITTED,
+                        split_time=float(split_time) if one else 0.0, starts=ptr(st), xatol=float(xatol), fatol=float(fatol), x=ptr(x), llh=ptr(llh),
+                        **fields)
         if hops is None:
             q.maxiter = int(maxiter if maxiter is not None else 1000)
             q.nit, q.nfev, q.status = (ptr(a) for a in counters.values())
@@ -679,28 +686,20 @@ class Engine:
         st = _f64(starts, (-1, N))
         S, P = st.shape[0], int(pop)
         ptr = lambda a: a.ctypes.data if a is not None else None
-        i32 = lambda a, shape: np.ascontiguousarray(np.asarray(a).reshape(shape), dtype=np.int32)
-        tab = _f64(jsfs, (-1, 8))
-        sp = _f64(split_times, (S,)) if split_times is not None else None
-        r_of = i32(rows, (S,))
-        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
-        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
-        lo, hi = _box_arrays(box, N)
-        id_ = np.ascontiguousarray(np.asarray(ids).reshape(S), dtype=np.uint64) if ids is not None else None
+        arrays, fields = self._rows_problem(S, N, _f64(jsfs, (-1, 8)), split_times, rows, band_bounds, pulse_times, box, ids)
         x, llh = np.empty((S, N)), np.empty(S)
         nit, nfev, status = (np.empty(S, dtype=np.int32) for _ in range(3))
         keep = return_population and 4 <= P <= _lib.DE_MAX_POP
         popx, popl = (np.empty((S, P, N)), np.empty((S, P))) if keep else (None, None)
         n_points = np.zeros(1, dtype=np.int64)
-        q = _lib.DeSearch(size=C.sizeof(_lib.DeSearch), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, split_times=ptr(sp),
-                          n_start=S, starts=ptr(st), rows=ptr(r_of), n_rep=tab.shape[0], jsfs=ptr(tab), band_bounds=ptr(bb), pulse_times=ptr(pt),
-                          n_box=lo.shape[0], box_lo=ptr(lo), box_hi=ptr(hi), pop=P, maxiter=int(maxiter), tol=float(tol), atol=float(atol),
-                          F_lo=float(F[0]), F_hi=float(F[1]), CR=float(CR), seed=int(seed), ids=ptr(id_), x=ptr(x), llh=ptr(llh), nit=ptr(nit),
-                          nfev=ptr(nfev), status=ptr(status), population=ptr(popx), population_llh=ptr(popl), n_points=ptr(n_points))
+        q = _lib.DeSearch(size=C.sizeof(_lib.DeSearch), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, starts=ptr(st),
+                          pop=P, maxiter=int(maxiter), tol=float(tol), atol=float(atol), F_lo=float(F[0]), F_hi=float(F[1]), CR=float(CR),
+                          seed=int(seed), x=ptr(x), llh=ptr(llh), nit=ptr(nit), nfev=ptr(nfev), status=ptr(status), population=ptr(popx),
+                          population_llh=ptr(popl), n_points=ptr(n_points), **fields)
         _lib.check(self._lib.misti_de_search(self._ctx, C.byref(q)))
         stats = self._nm_stats()
         out = dict(x=x, llh=llh, nit=nit, nfev=nfev, status=status, n_points=int(n_points[0]),
-                   split=x[:, -1].copy() if fit_split else sp.copy(), iterations_issued=stats["iterations_issued"], slots=stats["slots"])
+                   split=x[:, -1].copy() if fit_split else arrays["split_times"].copy(), iterations_issued=stats["iterations_issued"], slots=stats["slots"])
         if return_population:
             out.update(population=popx, population_llh=popl)
         return out
@@ -727,25 +726,17 @@ class Engine:
         S, W = x0.shape[0], x0.shape[1]
         n_step, thin = int(n_step), int(thin)
         ptr = lambda v: v.ctypes.data if v is not None else None
-        i32 = lambda v, shape: np.ascontiguousarray(np.asarray(v).reshape(shape), dtype=np.int32)
-        tab = _f64(table, (-1, 8))
-        sp = _f64(split_times, (S,)) if split_times is not None else None
-        r_of = i32(rows, (S,))
-        bb = i32(band_bounds, (S, self.n_band, 2)) if band_bounds is not None and self.n_band else None
-        pt = i32(pulse_times, (S, self.n_pulse)) if pulse_times is not None and self.n_pulse else None
-        lo, hi = _box_arrays(box, N)
+        arrays, fields = self._rows_problem(S, N, _f64(table, (-1, 8)), split_times, rows, band_bounds, pulse_times, box, ids)
         T = _f64(temperature).reshape(-1)
-        id_ = np.ascontiguousarray(np.asarray(ids).reshape(S), dtype=np.uint64) if ids is not None else None
         K = n_step // thin if thin >= 1 and n_step >= 0 else 0
         chain, chain_llh = np.empty((S, K, W, N)), np.empty((S, K, W))
         accepted = np.zeros((S, W), dtype=np.int32)
         last, last_llh = np.empty((S, W, N)), np.empty((S, W))
         n_points = np.zeros(1, dtype=np.int64)
-        q = _lib.EnsSample(size=C.sizeof(_lib.EnsSample), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, split_times=ptr(sp),
-                           n_start=S, init=ptr(x0), rows=ptr(r_of), n_rep=tab.shape[0], jsfs=ptr(tab), band_bounds=ptr(bb), pulse_times=ptr(pt),
-                           n_box=lo.shape[0], box_lo=ptr(lo), box_hi=ptr(hi), walkers=W, n_step=n_step, thin=thin, n_temp=T.size,
-                           temperature=ptr(T), a=float(a), seed=int(seed), ids=ptr(id_), chain=ptr(chain), chain_llh=ptr(chain_llh),
-                           accepted=ptr(accepted), last=ptr(last), last_llh=ptr(last_llh), n_points=ptr(n_points))
+        q = _lib.EnsSample(size=C.sizeof(_lib.EnsSample), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, init=ptr(x0),
+                           walkers=W, n_step=n_step, thin=thin, n_temp=T.size, temperature=ptr(T), a=float(a), seed=int(seed), chain=ptr(chain),
+                           chain_llh=ptr(chain_llh), accepted=ptr(accepted), last=ptr(last), last_llh=ptr(last_llh), n_points=ptr(n_points),
+                           **fields)
         _lib.check(self._lib.misti_ensemble_sample(self._ctx, C.byref(q)))
         return dict(chain=chain, chain_llh=chain_llh, accepted=accepted, last=last, last_llh=last_llh, n_points=int(n_points[0]))
 
