@@ -770,6 +770,72 @@ int misti_ens_draws(uint64_t seed, uint64_t id, int64_t step, int32_t walker, in
 int misti_ens_exp(double x, double* y);
 int misti_ens_accept(double z, int32_t d, double llk_old, double llk_new, double T, double u_acc, int32_t* accept);
 
+/* ---- posterior summaries on the device ---------------------------------------------------------- */
+/* What a user wants from the sampler is a handful of numbers per search, not the chain: per coordinate the mean, the covariance,
+ * quantiles (a credible interval, the median), the integrated autocorrelation time that says whether the run was long enough, and
+ * the best sample.  The chain [S][K][W][N] is already in HBM; these entries reduce it there, per search, and only the summaries
+ * leave the device.  The rule is THE PROJECT'S OWN, stated once in NumPy (optimize.ensemble_posterior_rule); the device result is
+ * that, bit for bit.  A search's result is a function of its own chain alone: not of S, the other searches or the launch geometry.
+ *
+ * Search s has x[t][w][j] for the kept steps t = burn ... K - 1: n = K - burn >= 1 steps, m = n W samples.  Every operation is
+ * rounded on its own, no fused multiply-add.
+ *   - order: the samples of coordinate j are ordered by the 64-bit key of their bits - a set sign bit flips all bits, a clear one
+ *     only the sign bit: a total order, -0.0 before +0.0, NaN last.  x_(0) <= ... <= x_(m-1);
+ *   - quantile of p in [0, 1]: h = double(m - 1) p, i = floor(h), g = h - i; g == 0 or i >= m - 1: x_(min(i, m - 1)) exactly,
+ *     otherwise x_(i) + g (x_(i+1) - x_(i)).  p = 0 is the minimum, p = 1 the maximum;
+ *   - lsum(v[0 .. count)), the only way sums over steps are taken: 64 partials, partial l = v[l] + v[l + 64] + ... in increasing
+ *     index over ceil(count / 64) terms, an absent term being +0.0; then partial[l] += partial[l + stride] for l < stride, stride =
+ *     32, 16, 8, 4, 2, 1; the result is partial[0];
+ *   - ensemble-mean series e_t[j] = (x[t][0][j] + x[t][1][j] + ... in walker order) / W; mean[j] = lsum(e_.[j]) / n;
+ *   - cov[j][k] = lsum_t(sum over w in walker order of (x[t][w][j] - mean[j]) (x[t][w][k] - mean[k])) / (m - 1), computed for
+ *     j <= k and mirrored; the variance is the diagonal;
+ *   - autocorrelation of y_t = e_t[j] - mean[j] with L = min(max_lag, n - 1): c_k = lsum_{t = 0 .. n-k-1}(y_t y_{t+k}); with
+ *     c_0 == 0 and L >= 1: tau = 1, window = 0; otherwise rho_k = c_k / c_0, tau_0 = 1, tau_M = tau_{M-1} + 2 rho_M, and window is
+ *     the smallest M in 0 ... L with double(M) >= c tau_M; none: window = -1 and tau_L is used (so L == 0 gives window = -1, tau =
+ *     1: no lag can close the window).  The reported tau is tau_window, or 1 where that is below 1.  Lags behind the window are not
+ *     computed;
+ *   - best sample: among the kept (t, w) whose chain_llh is neither NaN nor -inf the largest value, ties to the lowest t, then the
+ *     lowest w: best_llh, best_x[N], best_at = (t - burn, w); none, or no chain_llh: -inf, NaN, (-1, -1).
+ * Beyond the chain the call keeps the series y[S][N][n] (1 / W of the kept chain) in the context; nothing of the chain's size.
+ * Shortest (HPD) intervals need a sort and are not offered.
+ *
+ * misti_ens_summary_dev: every chain and output pointer is DEVICE memory (probs is HOST); asynchronous on the context's stream.
+ * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this
+ * library's; S < 0, W < 1 or N < 1; burn outside 0 ... K - 1; n_prob outside 1 ... MISTI_POST_MAX_PROBS; a NULL probs; a p outside
+ * [0, 1] or NaN; max_lag < 0; a c that is not finite and positive; a NULL chain with S > 0; MISTI_E_LIMIT for W >
+ * MISTI_ENS_MAX_WALKERS, N > MISTI_MAX_PARAMS, m > INT32_MAX or S > INT32_MAX; then a NULL context.  S == 0 writes nothing.  A chain element that
+ * is not finite is no error: the key order and IEEE arithmetic define the result - and since IEEE leaves the sign and the payload
+ * of a NaN open, a NaN in mean, cov, quant or tau is stored as the canonical quiet NaN (0x7ff8000000000000; best_x copies the
+ * sample's bits).  Any output may be NULL: it is not computed, and
+ * the others' bits do not change. */
+#define MISTI_POST_MAX_PROBS 8
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_ens_post_t) */
+    int32_t burn;                    /* kept steps dropped before the summary: 0 ... K - 1 */
+    int32_t n_prob;                  /* 1 ... MISTI_POST_MAX_PROBS */
+    const double* probs;             /* HOST [n_prob], each in [0, 1] */
+    int32_t max_lag;                 /* >= 0: the lag cap (n - 1 or more: every lag) */
+    double c;                        /* Sokal's window constant: finite, > 0 (5 is usual) */
+    double* mean;                    /* [S][N] or NULL */
+    double* cov;                     /* [S][N][N] or NULL */
+    double* quant;                   /* [S][N][n_prob] or NULL */
+    double* tau;                     /* [S][N] or NULL, in kept steps */
+    int32_t* window;                 /* [S][N] or NULL; -1: no lag up to the cap closed the window */
+    double* best_llh;                /* [S] or NULL */
+    double* best_x;                  /* [S][N] or NULL */
+    int32_t* best_at;                /* [S][2] or NULL: (kept step - burn, walker) */
+} misti_ens_post_t;
+int misti_ens_summary_dev(misti_ctx* ctx, int64_t S, int64_t K, int32_t W, int32_t N, const double* d_chain, const double* d_chain_llh /* or NULL */,
+                          const misti_ens_post_t* post);
+/* misti_ensemble_sample followed by the summary of its chain, without the chain leaving the device: the sampler runs exactly as
+ * misti_ensemble_sample does (the same kernels, stream and bits) and keeps the chain [n_start][n_keep][walkers][N] in the context's
+ * search buffers whether or not sampler->chain is NULL; the summary runs on it (K = n_keep); the summaries are copied to the HOST
+ * buffers of `post`, the sampler's last / last_llh / accepted / n_points as before, and chain / chain_llh only where the sampler
+ * gives them.  Synchronous.  Errors: a NULL or wrong-size sampler or post descriptor, then misti_ensemble_sample's in its order -
+ * its limit of INT32_MAX / 8 chain elements applies to the DEVICE chain here, asked for or not -, then misti_ens_summary_dev's with
+ * K = n_keep (n_keep == 0 leaves no burn to give).  n_start == 0 returns 0 and writes nothing. */
+int misti_ensemble_posterior(misti_ctx* ctx, const misti_ens_t* sampler, const misti_ens_post_t* post);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

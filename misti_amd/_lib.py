@@ -95,6 +95,16 @@ class EnsSample(C.Structure):
                 ("last_llh", C.c_void_p), ("n_points", C.c_void_p)]
 
 
+POST_MAX_PROBS = 8
+
+
+class EnsPost(C.Structure):
+    """``misti_ens_post_t``: posterior summaries of a chain; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("burn", C.c_int32), ("n_prob", C.c_int32), ("probs", C.c_void_p), ("max_lag", C.c_int32), ("c", C.c_double),
+                ("mean", C.c_void_p), ("cov", C.c_void_p), ("quant", C.c_void_p), ("tau", C.c_void_p), ("window", C.c_void_p),
+                ("best_llh", C.c_void_p), ("best_x", C.c_void_p), ("best_at", C.c_void_p)]
+
+
 class MistiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmisti_hip error %d: %s" % (code, msg))
@@ -127,6 +137,8 @@ SYMBOLS = {
     "misti_de_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_ensemble_sample": (C.c_int, [C.c_void_p, C.POINTER(EnsSample)]),
+    "misti_ens_summary_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(EnsPost)]),
+    "misti_ensemble_posterior": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost)]),
     "misti_ens_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_ens_exp": (C.c_int, [C.c_double, C.c_void_p]),
     "misti_ens_accept": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

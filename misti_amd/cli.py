@@ -93,6 +93,12 @@ and the GNU-parallel recipe of ``README.md:110-115``):
     --mcmc-temp T|auto        with --mcmc: the temperature (default 1).  auto: trace(H^-1 J) / p from the curvature at the data row's fit and
                               the bootstrap rows' class counts - the magnitude adjustment of a composite likelihood; needs --all-bs
     --mcmc-out FILE.npz       with --mcmc: the chains, their llh, the acceptance counters and the final ensembles
+    --mcmc-post [P ...]       with --mcmc: the posterior summaries are reduced ON THE DEVICE (misti_ensemble_posterior) - without --mcmc-out the
+                              chain never leaves it.  In place of the `mcmc:` lines one `post:` line per coordinate: mean, standard
+                              deviation, the quantiles P ... (1 ... 8 probabilities in [0, 1]; default 0.025 0.5 0.975; exact order
+                              statistics, interpolated), tau, n_eff = samples / tau, `(short)`, the coordinate's row of the correlation
+                              matrix, and the best sample
+    --mcmc-lag L              with --mcmc-post: the autocorrelation's lag cap (default: every lag)
     --box K LO HI             with --grid-solve, --fit-st or --polish, with or without --hops; repeatable: every search runs inside a box -
                               SciPy's Nelder-Mead with bounds= (misti_nm_solve_box / misti_basinhopping_box): LO <= parameter K <= HI, K the
                               index of an optimised parameter as --grid-mi K names it, or `st` for the fitted split of --fit-st.  inf and
@@ -238,6 +244,9 @@ def build_parser():
     p.add_argument("--mcmc-spread", type=float, default=None, metavar="S", help="with --mcmc: spread of the initial ensemble in box widths (default 1e-2)")
     p.add_argument("--mcmc-temp", default=None, metavar="T|auto", help="with --mcmc: the temperature (default 1), or auto: trace(H^-1 J) / p (needs --all-bs)")
     p.add_argument("--mcmc-out", default=None, metavar="FILE.npz", help="with --mcmc: write chains, values, acceptance counters and final ensembles")
+    p.add_argument("--mcmc-post", nargs="*", type=float, default=None, metavar="P",
+                   help="with --mcmc: posterior summaries reduced on the device, `post:` lines in place of `mcmc:` lines; P ...: the quantiles (default 0.025 0.5 0.975)")
+    p.add_argument("--mcmc-lag", type=int, default=None, metavar="L", help="with --mcmc-post: the autocorrelation's lag cap (default: every lag)")
     p.add_argument("--box", nargs=3, action="append", default=[], metavar=("K", "LO", "HI"),
                    help="with --grid-solve / --fit-st / --polish: keep optimised parameter K (or `st`: the fitted split of --fit-st) within [LO, HI] "
                         "in every search (SciPy's bounds=; inf / -inf accepted); repeatable")
@@ -558,6 +567,8 @@ def de_error(a):
 def mcmc_error(a):
     """Why ``--mcmc`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
     if a.mcmc is None:
+        if a.mcmc_post is not None or a.mcmc_lag is not None:
+            return "--mcmc-post / --mcmc-lag summarise the chains of --mcmc W STEPS: give --mcmc W STEPS"
         if any(v is not None for v in (a.mcmc_burn, a.mcmc_thin, a.mcmc_seed, a.mcmc_spread, a.mcmc_temp, a.mcmc_out)):
             return "--mcmc-burn / --mcmc-thin / --mcmc-seed / --mcmc-spread / --mcmc-temp / --mcmc-out set the sampler of --mcmc W STEPS: give --mcmc W STEPS"
         return None
@@ -592,6 +603,10 @@ def mcmc_error(a):
             return "--mcmc-temp T|auto: a finite temperature > 0, or auto (got %s)" % a.mcmc_temp
     if a.mcmc_temp == "auto" and not a.all_bs:
         return "--mcmc-temp auto takes the score covariance from the bootstrap rows: it needs --all-bs"
+    if a.mcmc_post is not None and (len(a.mcmc_post) > 8 or not all(0.0 <= v <= 1.0 for v in a.mcmc_post)):
+        return "--mcmc-post [P ...]: at most 8 probabilities, each in [0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_post)
+    if a.mcmc_lag is not None and (a.mcmc_post is None or a.mcmc_lag < 0):
+        return "--mcmc-lag L caps the lags of --mcmc-post: give --mcmc-post, and L >= 0"
     k = sum(1 for el in a.mi if int(el[4])) + sum(1 for el in a.pu if int(el[3]))
     boxed = {}
     for name, lo, hi in a.box:
@@ -649,16 +664,42 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     else:
         init = np.stack([ensemble_start(x[s], lo, hi, o["walkers"], o["spread"], o["seed"], int(j_of[s])) for s in range(x.shape[0])])
     o["start"] = "DE's final population" if population is not None else "spread %g around the fit" % o["spread"]
-    res = e.ensemble_sample(init, np.asarray(r_of, dtype=np.int32), data, box, split_times=split_times, fit_split=split_times is None,
-                            n_step=o["n_step"], thin=o["thin"], temperature=T, seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
+    if a.mcmc_post is not None:
+        o["probs"] = _mcmc_post_options(a)["probs"]
+    sampler = e.ensemble_sample
+    if a.mcmc_post is not None:                            # the summaries on the device; the chain comes back only for --mcmc-out
+        post = _mcmc_post_options(a)
+        sampler = lambda *args, **kw: e.ensemble_posterior(*args, **kw, burn=o["burn"], keep_chain=bool(a.mcmc_out), **post)
+    res = sampler(init, np.asarray(r_of, dtype=np.int32), data, box, split_times=split_times, fit_split=split_times is None,
+                  n_step=o["n_step"], thin=o["thin"], temperature=T, seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
     if a.mcmc_out:
         np.savez(a.mcmc_out, chain=res["chain"], chain_llh=res["chain_llh"], accepted=res["accepted"], last=res["last"], last_llh=res["last_llh"],
                  row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T))
     return o, float(T), res
 
 
+def _mcmc_post_options(a):
+    """The options of --mcmc-post, or their defaults: the quantiles 0.025 0.5 0.975, every lag."""
+    return dict(probs=tuple(a.mcmc_post) if a.mcmc_post else (0.025, 0.5, 0.975), max_lag=a.mcmc_lag)
+
+
+def print_post(label, o, res, s):
+    """The ``post:`` lines of fit s: one per coordinate, from the summaries the device reduced (Engine.ensemble_posterior)."""
+    from .optimize import posterior_table
+    n = o["n_step"] // o["thin"] - o["burn"]
+    t = posterior_table({k: res[k][s] for k in ("mean", "cov", "quant", "tau", "window", "last")}, n)
+    probs = o["probs"]
+    for c in range(res["mean"].shape[1]):
+        print("post:", label, "\tcoordinate %d" % c, "\tmean =", t["mean"][c], "\tsd =", t["sd"][c],
+              *("\tq%g = %r" % (p, float(t["quant"][c][i])) for i, p in enumerate(probs)), "\ttau =", t["tau"][c], "\tn_eff =", t["n_eff"][c],
+              *(["\t(short)"] if t["short"][c] else []), "\tcorr = [" + ", ".join(repr(float(v)) for v in t["corr"][c]) + "]",
+              "\tbest llh =", res["best_llh"][s], "at = (%d, %d)" % tuple(res["best_at"][s]), "x =", res["best_x"][s][c])
+
+
 def print_mcmc(label, o, res, s):
-    """The ``mcmc:`` lines of fit s: one per coordinate, from ensemble_summary of its chain."""
+    """The ``mcmc:`` lines of fit s: one per coordinate, from ensemble_summary of its chain - or, with --mcmc-post, its ``post:`` lines."""
+    if "quant" in res:
+        return print_post(label, o, res, s)
     from .optimize import ensemble_summary
     m = ensemble_summary(res["chain"][s], o["burn"], accepted=res["accepted"][s], n_step=o["n_step"])
     for c in range(res["chain"].shape[3]):
@@ -668,7 +709,7 @@ def print_mcmc(label, o, res, s):
 
 def _mcmc_text(o, T, res, dt):
     return "ensemble MCMC with %d walkers, %d steps, thin %d, burn %d, from %s, temperature %r, seed %d: %d ensembles in one call, %.3f s, %d proposals evaluated" % (
-        o["walkers"], o["n_step"], o["thin"], o["burn"], o["start"], T, o["seed"], res["chain"].shape[0], dt, res["n_points"])
+        o["walkers"], o["n_step"], o["thin"], o["burn"], o["start"], T, o["seed"], res["last"].shape[0], dt, res["n_points"])
 
 
 def _de_options(a):

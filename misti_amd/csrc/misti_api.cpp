@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "misti_device.h"
+#include "misti_post.h"
 #include "misti_tables.hpp"
 
 namespace {
@@ -120,6 +121,7 @@ struct misti_ctx {
     DevBuf curv_f64, curv_i32;          // misti_curvature: points, stencil candidates, their spectra, derivatives | rows, slots, statuses
     DevBuf boot_chunks;                 // misti_bootstrap_rows_dev: the chunk table [n_chunk][8]
     DevBuf param_totals;                // misti_parametric_rows_dev: the draw counts of one slice of replicates, [n][6] uint64
+    DevBuf post_ws;                     // misti_ens_summary_dev: means [S][N] | the centred ensemble-mean series [S][N][n]
     int32_t* nm_live_host = nullptr;    // pinned: live starts after the last two finished iterations
     int64_t nm_iterations = 0;          // iterations issued by the last misti_nm_solve
     int64_t nm_slots = 0;               // and the batch slots they had in total (live starts + the stale-count slack)
@@ -724,7 +726,7 @@ int misti_destroy(misti_ctx* c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     (void)hipGetLastError();
     for (auto* b : {&c->model_f64, &c->model_i32, &c->consts, &c->ws_jafs, &c->ws_status, &c->ws_chain_f64, &c->ws_chain_i32, &c->ws_order, &c->ws_diag, &c->ws_trunk, &c->ws_solver, &c->ws_iters, &c->ws_post,
-                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx, &c->curv_f64, &c->curv_i32, &c->boot_chunks, &c->param_totals})
+                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx, &c->curv_f64, &c->curv_i32, &c->boot_chunks, &c->param_totals, &c->post_ws})
         b->release();
     c->pin_in.release();
     c->pin_out.release();
@@ -1720,10 +1722,40 @@ int de_run(misti_ctx* c, const misti_de_t& q, int N, bool whole) {
     return 0;
 }
 
+// ---- posterior summaries of a chain (misti_post.hip) ---------------------------------------------------------------------------------
+// The arguments of misti_ens_summary_dev, before the first HIP call, in the header's order, up to the context (the caller's).
+int post_check(const misti_ens_post_t* p, int64_t S, int64_t K, int32_t W, int32_t N, bool have_chain) {
+    if (!p) return fail(MISTI_E_ARG, "the summary descriptor is NULL");
+    if (p->size != sizeof(misti_ens_post_t))
+        return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
+    if (S < 0 || W < 1 || N < 1) return fail(MISTI_E_ARG, "negative number of searches, or no walker or coordinate (S = %lld, W = %d, N = %d)", (long long)S, (int)W, (int)N);
+    if (p->burn < 0 || p->burn >= K) return fail(MISTI_E_ARG, "burn must be 0 ... K - 1 (got %d for %lld kept steps)", (int)p->burn, (long long)K);
+    if (p->n_prob < 1 || p->n_prob > MISTI_POST_MAX_PROBS) return fail(MISTI_E_ARG, "n_prob must be 1 ... %d (got %d)", MISTI_POST_MAX_PROBS, (int)p->n_prob);
+    if (!p->probs) return fail(MISTI_E_ARG, "probs is NULL");
+    for (int i = 0; i < p->n_prob; ++i)
+        if (!(p->probs[i] >= 0.0 && p->probs[i] <= 1.0)) return fail(MISTI_E_ARG, "probs[%d] = %g is not in [0, 1]", i, p->probs[i]);
+    if (p->max_lag < 0) return fail(MISTI_E_ARG, "max_lag must not be negative (got %d)", (int)p->max_lag);
+    if (!std::isfinite(p->c) || !(p->c > 0.0)) return fail(MISTI_E_ARG, "c must be finite and positive (got %g)", p->c);
+    if (!have_chain && S > 0) return fail(MISTI_E_ARG, "the chain is NULL");
+    if (W > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "W = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)W, MISTI_ENS_MAX_WALKERS);
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "N = %d exceeds MISTI_MAX_PARAMS = %d", (int)N, MISTI_MAX_PARAMS);
+    if ((K - p->burn) > INT32_MAX / W) return fail(MISTI_E_LIMIT, "%lld kept steps x %d walkers exceed INT32_MAX samples per search", (long long)(K - p->burn), (int)W);
+    if (S > INT32_MAX) return fail(MISTI_E_LIMIT, "too many searches for one call");
+    return 0;
+}
+
+// the launch record of a checked descriptor, without its pointers
+void post_fill(misti::PostArgs& a, int64_t S, int64_t K, int32_t W, int32_t N, const misti_ens_post_t& p) {
+    a.S = S; a.K = K; a.W = W; a.N = N; a.burn = p.burn; a.n = K - p.burn; a.c = p.c;
+    a.L = p.max_lag < a.n - 1 ? p.max_lag : a.n - 1;
+    a.sel = misti::post_select(a.n * W, p.n_prob, p.probs);
+}
+
 // ---- ensemble MCMC per search (misti_ens.hip) ------------------------------------------------------------------------------------
 // The arguments of misti_ensemble_sample, before the first HIP call, in the header's order.  Leaves the number of coordinates in N
-// and whether every split time is an integer in `whole`.
-int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
+// and whether every split time is an integer in `whole`.  `keep`: the chain is kept on the device whether it is asked for or not
+// (misti_ensemble_posterior), so its limit applies.
+int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, bool keep = false) {
     const RowsArgs a = rows_args(q);
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
     if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.temperature || !q.last || !q.last_llh || (a.per_start() && !q.split_times))
@@ -1741,9 +1773,9 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
     if (int r = check_n_box(a, "searches")) return r;
     if (int r = check_rows(a, whole)) return r;
     if (int r = check_limits(c, a, q.walkers, "searches x walkers", N)) return r;
-    if ((q.chain || q.chain_llh) && q.n_start > 0 && (int64_t)(q.n_step / q.thin) > INT32_MAX / 8 / N / q.walkers / q.n_start)
-        return fail(MISTI_E_LIMIT, "the chain of %lld searches x %d kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
-                    (long long)q.n_start, (int)(q.n_step / q.thin), (int)q.walkers, N);
+    if ((q.chain || q.chain_llh || keep) && q.n_start > 0 && (int64_t)(q.n_step / q.thin) > INT32_MAX / 8 / N / q.walkers / q.n_start)
+        return fail(MISTI_E_LIMIT, "the %schain of %lld searches x %d kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
+                    keep ? "device " : "", (long long)q.n_start, (int)(q.n_step / q.thin), (int)q.walkers, N);
     for (int64_t b = 0; b < q.n_box; ++b) {
         if (int r = check_box(a, N, b, "the sampler's prior is uniform on a finite box")) return r;
         int n_free = 0;
@@ -1764,12 +1796,16 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole) {
 
 // A checked call with n_start >= 1.  One batch record of n_start x walkers slots serves the initial ensemble and every half-step
 // (which fills the first half of it); the state and the chain lie in the search buffers of the context.  Nothing is read back before
-// the end.
-int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole) {
+// the end.  With `post` (checked: post_check) the chain is kept whether it is asked for or not, the summary kernels run on it where
+// it lies, and the summaries come back with the rest; the series workspace and the summaries' device side are carved with the chain.
+int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_ens_post_t* post = nullptr) {
     using namespace misti;
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp;
-    const size_t K = (q.chain || q.chain_llh) ? (size_t)(q.n_step / q.thin) : 0;
+    const size_t K = (q.chain || q.chain_llh || post) ? (size_t)(q.n_step / q.thin) : 0;
+    PostArgs pa{};
+    const size_t NP = post ? (size_t)post->n_prob : 0, SN = S * (size_t)N;
+    if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
     RowsProblem rows(c, rows_args(q), N, whole);
     EnsState st{};
     st.S = q.n_start; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
@@ -1784,6 +1820,13 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole) {
         if (K) { st.chain = f.take(S * K * W * (size_t)N); st.chain_llh = f.take(S * K * W); }
         st.accepted = i.take(M); st.submitted = i.take(M);
         rows.layout(f, i, &st.b, &M, 1, M);
+        if (post) {                                        // behind everything the sampler carves: its layout does not move
+            pa.ws_mean = f.take(SN); pa.ws_y = f.take(SN * (size_t)pa.n);
+            pa.mean = post->mean ? f.take(SN) : nullptr; pa.cov = post->cov ? f.take(SN * (size_t)N) : nullptr;
+            pa.quant = post->quant ? f.take(SN * NP) : nullptr; pa.tau = post->tau ? f.take(SN) : nullptr;
+            pa.best_llh = post->best_llh ? f.take(S) : nullptr; pa.best_x = post->best_x ? f.take(SN) : nullptr;
+            pa.window = post->window ? i.take(SN) : nullptr; pa.best_at = post->best_at ? i.take(2 * S) : nullptr;
+        }
     };
     if (int r = carve(c, "search", layout)) return r;
     rows.fill(st.src);
@@ -1806,6 +1849,19 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole) {
     c->nm_iterations = 2 * (int64_t)q.n_step;
     c->nm_slots = 2 * (int64_t)q.n_step * (int64_t)(S * H);
     HIP_TRY(launch_ens_result(st, sm));
+    if (post) {
+        pa.chain = st.chain; pa.chain_llh = st.chain_llh;
+        HIP_TRY(launch_post(pa, sm));
+        auto back = [&](void* host, const void* dev, size_t bytes) { return host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm) : hipSuccess; };
+        HIP_TRY(back(post->mean, pa.mean, SN * sizeof(double)));
+        HIP_TRY(back(post->cov, pa.cov, SN * N * sizeof(double)));
+        HIP_TRY(back(post->quant, pa.quant, SN * NP * sizeof(double)));
+        HIP_TRY(back(post->tau, pa.tau, SN * sizeof(double)));
+        HIP_TRY(back(post->window, pa.window, SN * sizeof(int32_t)));
+        HIP_TRY(back(post->best_llh, pa.best_llh, S * sizeof(double)));
+        HIP_TRY(back(post->best_x, pa.best_x, SN * sizeof(double)));
+        HIP_TRY(back(post->best_at, pa.best_at, 2 * S * sizeof(int32_t)));
+    }
     HIP_TRY(hipMemcpyAsync(q.last, st.x, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
     HIP_TRY(hipMemcpyAsync(q.last_llh, st.llh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
     if (q.accepted) HIP_TRY(hipMemcpyAsync(q.accepted, st.accepted, M * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
@@ -1840,6 +1896,40 @@ int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) {
     if (int r = ens_check(c, *q, N, whole)) return r;
     if (q->n_start == 0) return 0;
     return ens_run(c, *q, N, whole);
+}
+
+int misti_ens_summary_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t N, const double* d_chain, const double* d_chain_llh, const misti_ens_post_t* p) {
+    if (int r = post_check(p, S, K, W, N, d_chain != nullptr)) return r;
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (S == 0) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    misti::PostArgs a{};
+    post_fill(a, S, K, W, N, *p);
+    const size_t SN = (size_t)S * (size_t)N;
+    HIP_TRY(c->post_ws.reserve(SN * (size_t)(a.n + 1) * sizeof(double)));
+    a.ws_mean = c->post_ws.as<double>(); a.ws_y = a.ws_mean + SN;
+    a.chain = d_chain; a.chain_llh = d_chain_llh;
+    a.mean = p->mean; a.cov = p->cov; a.quant = p->quant; a.tau = p->tau; a.window = p->window;
+    a.best_llh = p->best_llh; a.best_x = p->best_x; a.best_at = p->best_at;
+    HIP_TRY(misti::launch_post(a, c->stream));
+    return 0;
+}
+
+int misti_ensemble_posterior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p) {
+    if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
+    if (q->size != sizeof(misti_ens_t))
+        return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_ens_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_ens_t));
+    if (!p) return fail(MISTI_E_ARG, "the summary descriptor is NULL");
+    if (p->size != sizeof(misti_ens_post_t))
+        return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
+    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
+        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
+    int N = 0;
+    bool whole = false;
+    if (int r = ens_check(c, *q, N, whole, true)) return r;
+    if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
+    if (q->n_start == 0) return 0;
+    return ens_run(c, *q, N, whole, p);
 }
 
 int misti_de_search(misti_ctx* c, const misti_de_t* q) {

@@ -1,0 +1,82 @@
+// What the posterior summaries of a chain (misti_ens_summary_dev / misti_ensemble_posterior; the rule is
+// optimize.ensemble_posterior_rule, operation for operation) share between the host layer and the kernels of misti_post.hip: the
+// order key, the wanted order statistics of a search (a function of m = n W and the probabilities alone, so the host computes them
+// once), and the launch record.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/misti_hip.h"
+
+namespace misti {
+
+constexpr int POST_MAX_RANKS = 2 * MISTI_POST_MAX_PROBS;   // a probability needs x_(i) and x_(i+1)
+constexpr int POST_LANES = 64;                             // lsum's partials: one per lane of a wave
+
+// The total order of the rule: the 64-bit key of a double's bits.  A set sign bit flips all bits, a clear one only the sign bit:
+// -0.0 before +0.0, NaNs of a clear sign bit last.
+__host__ __device__ __forceinline__ uint64_t post_key(uint64_t bits) { return (bits >> 63) ? ~bits : bits ^ 0x8000000000000000ull; }
+__host__ __device__ __forceinline__ uint64_t post_unkey(uint64_t key) { return (key >> 63) ? key ^ 0x8000000000000000ull : ~key; }
+
+// The order statistics a search's quantiles need: rank[] ascending and distinct; probability p reads x_(rank[lo[p]]) and, where it
+// interpolates (hi[p] != lo[p]), x_(rank[hi[p]]) with weight g[p].
+struct PostSelect {
+    int32_t n_prob, n_rank;
+    int32_t rank[POST_MAX_RANKS];
+    int32_t lo[MISTI_POST_MAX_PROBS], hi[MISTI_POST_MAX_PROBS];
+    double g[MISTI_POST_MAX_PROBS];
+};
+
+// h = double(m - 1) p, i = floor(h), g = h - i; g == 0 or i >= m - 1: x_(min(i, m - 1)) exactly.  probs: n_prob values in [0, 1].
+inline PostSelect post_select(int64_t m, int n_prob, const double* probs) {
+    PostSelect s{};
+    s.n_prob = n_prob;
+    int32_t want[POST_MAX_RANKS];
+    int n_want = 0;
+    int32_t a[MISTI_POST_MAX_PROBS], b[MISTI_POST_MAX_PROBS];
+    for (int p = 0; p < n_prob; ++p) {
+        const double h = (double)(m - 1) * probs[p];
+        const double fl = floor(h);
+        int64_t i = (int64_t)fl;
+        s.g[p] = h - fl;
+        if (s.g[p] == 0.0 || i >= m - 1) {
+            if (i > m - 1) i = m - 1;
+            a[p] = b[p] = (int32_t)i;
+            want[n_want++] = (int32_t)i;
+        } else {
+            a[p] = (int32_t)i; b[p] = (int32_t)(i + 1);
+            want[n_want++] = a[p]; want[n_want++] = b[p];
+        }
+    }
+    for (int i = 1; i < n_want; ++i)                        // insertion sort: at most 16
+        for (int k = i; k > 0 && want[k] < want[k - 1]; --k) { const int32_t t = want[k]; want[k] = want[k - 1]; want[k - 1] = t; }
+    for (int i = 0; i < n_want; ++i)
+        if (!s.n_rank || s.rank[s.n_rank - 1] != want[i]) s.rank[s.n_rank++] = want[i];
+    for (int p = 0; p < n_prob; ++p)
+        for (int r = 0; r < s.n_rank; ++r) {
+            if (s.rank[r] == a[p]) s.lo[p] = r;
+            if (s.rank[r] == b[p]) s.hi[p] = r;
+        }
+    return s;
+}
+
+// One call: S searches of chain[S][K][W][N], the kept steps burn ... K - 1 (n of them), lags 0 ... L.  Every pointer is device
+// memory; an output that is NULL is not computed.  ws_mean[S][N] and ws_y[S][N][n] are the call's workspace: the mean and the
+// centred ensemble-mean series (1 / W of the kept chain).
+struct PostArgs {
+    int64_t S, K, burn, n, L;
+    int32_t W, N;
+    double c;
+    const double* chain;
+    const double* chain_llh;         // or NULL: no best sample
+    double *ws_mean, *ws_y;
+    double *mean, *cov, *quant, *tau;
+    int32_t* window;
+    double *best_llh, *best_x;
+    int32_t* best_at;
+    PostSelect sel;
+};
+hipError_t launch_post(const PostArgs& a, hipStream_t stream);
+
+}  // namespace misti

@@ -1,0 +1,255 @@
+// Posterior summaries of a chain that is already in HBM (MI355X / gfx950): misti_ens_summary_dev, misti_ensemble_posterior.
+//
+// Per search: exact order statistics and the quantiles interpolated between them, the mean and the covariance, the integrated
+// autocorrelation time of the ensemble-mean series with Sokal's window, and the best sample.  The rule is THE PROJECT'S OWN:
+// optimize.ensemble_posterior_rule states it in NumPy and every kernel here restates it operation for operation - one rounding per
+// operation, a product that feeds a sum passes through ens_rn().  A search's result is a function of its own chain alone.
+//
+// Every sum over steps is lsum: 64 partials, partial l = v[l] + v[l + 64] + ... over ceil(count / 64) terms with +0.0 for an absent
+// one, then partial[l] += partial[l + stride] for stride 32 ... 1.  Here a partial is a lane of a wave and the fold six shuffles.
+//
+//   post_mean_kernel    wave = (search, coordinate): the ensemble-mean series e_t, its lsum, and y_t = e_t - mean into the workspace
+//   post_cov_kernel     wave = (search, j <= k)
+//   post_acf_kernel     workgroup = (search, coordinate), a wave per lag, four lags at a time; a thread walks the window over each
+//                       four and the workgroup stops at the first lag that closes it: lags behind the window are never computed
+//   post_select_kernel  workgroup = (search, coordinate): most-significant-digit radix select on the order key, 8 passes of 8 bits,
+//                       LDS histograms; ranks that still share a prefix share a histogram.  No second buffer, no sort
+//   post_best_kernel    workgroup = search
+// The only memory beyond the chain is the series y[S][N][n]: 1 / W of the kept chain.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "misti_ens.h"
+#include "misti_post.h"
+
+namespace misti {
+
+namespace {
+
+constexpr int POST_THREADS = 256;
+constexpr int POST_WAVES = POST_THREADS / POST_LANES;
+
+// lsum's fold: lane 0 ends with partial[0]
+__device__ __forceinline__ double post_fold(double v) {
+#pragma unroll
+    for (int stride = POST_LANES / 2; stride >= 1; stride >>= 1) v = v + __shfl_down(v, stride, POST_LANES);
+    return __shfl(v, 0, POST_LANES);
+}
+
+// what is stored of a result: IEEE leaves the sign and the payload of a NaN to the implementation, the rule does not - the canonical quiet NaN
+__device__ __forceinline__ double post_out(double v) { return v != v ? __longlong_as_double(0x7ff8000000000000ll) : v; }
+
+__device__ __forceinline__ const double* kept(const PostArgs& a, int64_t s) { return a.chain + (s * a.K + a.burn) * a.W * (int64_t)a.N; }
+
+}  // namespace
+
+__global__ __launch_bounds__(POST_LANES)
+void post_mean_kernel(PostArgs a) {
+    const int64_t s = blockIdx.x;
+    const int j = blockIdx.y, l = threadIdx.x, W = a.W, N = a.N;
+    const int64_t n = a.n, rows = (n + POST_LANES - 1) / POST_LANES;
+    const double* x = kept(a, s) + j;
+    double* y = a.ws_y + (s * N + j) * n;
+    double acc = 0.0;
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t t = r * POST_LANES + l;
+        double v = 0.0;
+        if (t < n) {
+            const double* p = x + t * W * (int64_t)N;
+            double e = p[0];
+            for (int w = 1; w < W; ++w) e = e + p[(int64_t)w * N];
+            v = e / (double)W;
+            y[t] = v;
+        }
+        acc = r == 0 ? v : acc + v;
+    }
+    const double mean = post_fold(acc) / (double)n;
+    if (l == 0) {
+        a.ws_mean[s * N + j] = mean;
+        if (a.mean) a.mean[s * N + j] = post_out(mean);
+    }
+    for (int64_t t = l; t < n; t += POST_LANES) y[t] = y[t] - mean;      // each lane rereads what it wrote
+}
+
+__global__ __launch_bounds__(POST_LANES)
+void post_cov_kernel(PostArgs a) {
+    const int64_t s = blockIdx.x;
+    const int l = threadIdx.x, W = a.W, N = a.N;
+    int j = 0, k = (int)blockIdx.y;                           // pair index -> j <= k, rows of the upper triangle
+    while (k >= N - j) { k -= N - j; ++j; }
+    k += j;
+    const int64_t n = a.n, rows = (n + POST_LANES - 1) / POST_LANES;
+    const double mj = a.ws_mean[s * N + j], mk = a.ws_mean[s * N + k];
+    const double* x = kept(a, s);
+    double acc = 0.0;
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t t = r * POST_LANES + l;
+        double v = 0.0;
+        if (t < n) {
+            const double* p = x + t * W * (int64_t)N;
+            v = ens_rn((p[j] - mj) * (p[k] - mk));
+            for (int w = 1; w < W; ++w) v = v + ens_rn((p[(int64_t)w * N + j] - mj) * (p[(int64_t)w * N + k] - mk));
+        }
+        acc = r == 0 ? v : acc + v;
+    }
+    const double cv = post_out(post_fold(acc) / (double)(n * W - 1));
+    if (l == 0) {
+        a.cov[(s * N + j) * N + k] = cv;
+        a.cov[(s * N + k) * N + j] = cv;
+    }
+}
+
+__global__ __launch_bounds__(POST_THREADS)
+void post_acf_kernel(PostArgs a) {
+    __shared__ double c_blk[POST_WAVES];
+    __shared__ int stop;
+    const int64_t s = blockIdx.x;
+    const int j = blockIdx.y, N = a.N, wave = threadIdx.x / POST_LANES, l = threadIdx.x % POST_LANES;
+    const int64_t n = a.n, L = a.L;
+    const double* y = a.ws_y + (s * N + j) * n;
+    double c0 = 0.0, tau = 1.0;                               // thread 0's: the window scan
+    int64_t window = -1;
+    for (int64_t k0 = 0; k0 <= L; k0 += POST_WAVES) {
+        const int64_t k = k0 + wave;
+        if (k <= L) {
+            const int64_t cnt = n - k, rows = (cnt + POST_LANES - 1) / POST_LANES;
+            double acc = 0.0;
+            for (int64_t r = 0; r < rows; ++r) {
+                const int64_t t = r * POST_LANES + l;
+                const double v = t < cnt ? ens_rn(y[t] * y[t + k]) : 0.0;
+                acc = r == 0 ? v : acc + v;
+            }
+            acc = post_fold(acc);
+            if (l == 0) c_blk[wave] = acc;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            bool found = false;
+            for (int i = 0; i < POST_WAVES && k0 + i <= L && !found; ++i) {
+                const int64_t M = k0 + i;
+                if (M == 0) {
+                    c0 = c_blk[0];
+                    if (c0 == 0.0 && L >= 1) { window = 0; found = true; continue; }
+                } else {
+                    const double rho = c_blk[i] / c0;
+                    tau = tau + ens_rn(2.0 * rho);
+                }
+                if ((double)M >= ens_rn(a.c * tau)) { window = M; found = true; }
+            }
+            stop = found ? 1 : 0;
+        }
+        __syncthreads();
+        if (stop) break;
+    }
+    if (threadIdx.x == 0) {
+        if (a.tau) a.tau[s * N + j] = post_out(tau < 1.0 ? 1.0 : tau);
+        if (a.window) a.window[s * N + j] = (int32_t)window;
+    }
+}
+
+__global__ __launch_bounds__(POST_THREADS)
+void post_select_kernel(PostArgs a) {
+    __shared__ uint32_t hist[POST_MAX_RANKS][256];
+    __shared__ uint64_t prefix[POST_MAX_RANKS];
+    __shared__ uint32_t rem[POST_MAX_RANKS];
+    __shared__ int32_t leader[POST_MAX_RANKS];                // the lowest rank with this rank's prefix: its histogram serves both
+    const int64_t s = blockIdx.x;
+    const int j = blockIdx.y, N = a.N, tid = threadIdx.x, R = a.sel.n_rank;
+    const int64_t m = a.n * a.W;
+    const double* x = kept(a, s) + j;
+    if (tid < R) { prefix[tid] = 0; rem[tid] = (uint32_t)a.sel.rank[tid]; leader[tid] = 0; }
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        for (int i = tid; i < POST_MAX_RANKS * 256; i += POST_THREADS) (&hist[0][0])[i] = 0;
+        __syncthreads();
+        for (int64_t idx = tid; idx < m; idx += POST_THREADS) {
+            const uint64_t key = post_key((uint64_t)__double_as_longlong(x[idx * N]));
+            const uint64_t head = pass ? key >> (shift + 8) : 0;
+            for (int r = 0; r < R; ++r)
+                if (leader[r] == r && prefix[r] == head) { atomicAdd(&hist[r][(key >> shift) & 255], 1u); break; }
+        }
+        __syncthreads();
+        uint64_t np_ = 0;
+        uint32_t nr = 0;
+        if (tid < R) {
+            const uint32_t* h = hist[leader[tid]];
+            const uint32_t want = rem[tid];
+            uint32_t below = 0;
+            int b = 0;
+            for (; b < 255; ++b) {                            // the bucket that holds the wanted rank
+                const uint32_t cnt = h[b];
+                if (want - below < cnt) break;
+                below += cnt;
+            }
+            np_ = (prefix[tid] << 8) | (uint64_t)b;
+            nr = want - below;
+        }
+        __syncthreads();
+        if (tid < R) { prefix[tid] = np_; rem[tid] = nr; }
+        __syncthreads();
+        if (tid == 0)
+            for (int r = 1; r < R; ++r) leader[r] = prefix[r] == prefix[r - 1] ? leader[r - 1] : r;
+        __syncthreads();
+    }
+    if (tid < a.sel.n_prob) {
+        const double lo = __longlong_as_double((long long)post_unkey(prefix[a.sel.lo[tid]]));
+        double q = lo;
+        if (a.sel.hi[tid] != a.sel.lo[tid]) {
+            const double hi = __longlong_as_double((long long)post_unkey(prefix[a.sel.hi[tid]]));
+            q = lo + ens_rn(a.sel.g[tid] * (hi - lo));
+        }
+        a.quant[(s * N + j) * a.sel.n_prob + tid] = post_out(q);
+    }
+}
+
+__global__ __launch_bounds__(POST_THREADS)
+void post_best_kernel(PostArgs a) {
+    __shared__ double sv[POST_THREADS];
+    __shared__ int64_t si[POST_THREADS];
+    const int64_t s = blockIdx.x;
+    const int tid = threadIdx.x, N = a.N;
+    const int64_t m = a.n * a.W;
+    double bv = -INFINITY;
+    int64_t bi = -1;
+    if (a.chain_llh) {
+        const double* v = a.chain_llh + (s * a.K + a.burn) * a.W;
+        for (int64_t idx = tid; idx < m; idx += POST_THREADS) {
+            const double f = v[idx];
+            if (f == f && f != -INFINITY && (bi < 0 || f > bv)) { bv = f; bi = idx; }
+        }
+    }
+    sv[tid] = bv; si[tid] = bi;
+    __syncthreads();
+    for (int stride = POST_THREADS / 2; stride >= 1; stride >>= 1) {
+        if (tid < stride) {
+            const double ov = sv[tid + stride];
+            const int64_t oi = si[tid + stride];
+            if (oi >= 0 && (si[tid] < 0 || ov > sv[tid] || (ov == sv[tid] && oi < si[tid]))) { sv[tid] = ov; si[tid] = oi; }
+        }
+        __syncthreads();
+    }
+    bv = sv[0]; bi = si[0];
+    if (tid == 0) {
+        if (a.best_llh) a.best_llh[s] = bi >= 0 ? bv : -INFINITY;
+        if (a.best_at) {
+            a.best_at[2 * s] = bi >= 0 ? (int32_t)(bi / a.W) : -1;
+            a.best_at[2 * s + 1] = bi >= 0 ? (int32_t)(bi % a.W) : -1;
+        }
+    }
+    if (a.best_x && tid < N)
+        a.best_x[s * N + tid] = bi >= 0 ? kept(a, s)[bi * N + tid] : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+hipError_t launch_post(const PostArgs& a, hipStream_t stream) {
+    const dim3 per_coord((unsigned)a.S, (unsigned)a.N);             // searches along x: the axis without a 65535 limit
+    const bool series = a.mean || a.cov || a.tau || a.window;
+    if (series) hipLaunchKernelGGL(post_mean_kernel, per_coord, dim3(POST_LANES), 0, stream, a);
+    if (a.cov) hipLaunchKernelGGL(post_cov_kernel, dim3((unsigned)a.S, (unsigned)(a.N * (a.N + 1) / 2)), dim3(POST_LANES), 0, stream, a);
+    if (a.tau || a.window) hipLaunchKernelGGL(post_acf_kernel, per_coord, dim3(POST_THREADS), 0, stream, a);
+    if (a.quant) hipLaunchKernelGGL(post_select_kernel, per_coord, dim3(POST_THREADS), 0, stream, a);
+    if (a.best_llh || a.best_x || a.best_at) hipLaunchKernelGGL(post_best_kernel, dim3((unsigned)a.S), dim3(POST_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace misti

@@ -717,19 +717,26 @@ class Engine:
         Returns dict(chain[S][n_keep][W][N], chain_llh[S][n_keep][W] (the ensembles after steps thin, 2 thin, ...), accepted[S][W],
         last[S][W][N], last_llh[S][W], n_points (proposals the call handed the engine; those that leave the box are rejected without an
         evaluation and not counted, nor are the S W initial evaluations))."""
+        return self._ensemble("ensemble_sample", None, True, init, rows, table, box, split_times, fit_split, band_bounds, pulse_times, n_step, thin,
+                              temperature, a, seed, ids)
+
+    def _ensemble(self, who, post, keep_chain, init, rows, table, box, split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature,
+                  a, seed, ids):
+        """``misti_ensemble_sample`` (``post`` None) or ``misti_ensemble_posterior`` (``post``: dict(burn, probs, max_lag, c)): one
+        marshalling of the sampler's descriptor for both."""
         if (split_times is None) != bool(fit_split):
-            raise ValueError("ensemble_sample: give exactly one of split_times and fit_split=True")
+            raise ValueError("%s: give exactly one of split_times and fit_split=True" % who)
         N = self.n_param + (1 if fit_split else 0)
         x0 = _f64(init)
         if x0.ndim != 3 or x0.shape[2] != N:
-            raise ValueError("ensemble_sample: init must be [S][W][%d] (got %s)" % (N, x0.shape))
+            raise ValueError("%s: init must be [S][W][%d] (got %s)" % (who, N, x0.shape))
         S, W = x0.shape[0], x0.shape[1]
         n_step, thin = int(n_step), int(thin)
         ptr = lambda v: v.ctypes.data if v is not None else None
         arrays, fields = self._rows_problem(S, N, _f64(table, (-1, 8)), split_times, rows, band_bounds, pulse_times, box, ids)
         T = _f64(temperature).reshape(-1)
         K = n_step // thin if thin >= 1 and n_step >= 0 else 0
-        chain, chain_llh = np.empty((S, K, W, N)), np.empty((S, K, W))
+        chain, chain_llh = (np.empty((S, K, W, N)), np.empty((S, K, W))) if keep_chain else (None, None)
         accepted = np.zeros((S, W), dtype=np.int32)
         last, last_llh = np.empty((S, W, N)), np.empty((S, W))
         n_points = np.zeros(1, dtype=np.int64)
@@ -737,8 +744,63 @@ class Engine:
                            walkers=W, n_step=n_step, thin=thin, n_temp=T.size, temperature=ptr(T), a=float(a), seed=int(seed), chain=ptr(chain),
                            chain_llh=ptr(chain_llh), accepted=ptr(accepted), last=ptr(last), last_llh=ptr(last_llh), n_points=ptr(n_points),
                            **fields)
-        _lib.check(self._lib.misti_ensemble_sample(self._ctx, C.byref(q)))
-        return dict(chain=chain, chain_llh=chain_llh, accepted=accepted, last=last, last_llh=last_llh, n_points=int(n_points[0]))
+        out = dict(chain=chain, chain_llh=chain_llh) if post is None else {}
+        out.update(accepted=accepted, last=last, last_llh=last_llh)
+        if post is None:
+            _lib.check(self._lib.misti_ensemble_sample(self._ctx, C.byref(q)))
+        else:
+            probs = _f64(post["probs"]).reshape(-1)
+            P = probs.size
+            burn = int(post["burn"])
+            max_lag = max(K - burn - 1, 0) if post["max_lag"] is None else int(post["max_lag"])
+            s = dict(mean=np.empty((S, N)), cov=np.empty((S, N, N)), quant=np.empty((S, N, P)), tau=np.empty((S, N)),
+                     window=np.empty((S, N), dtype=np.int32), best_llh=np.empty(S), best_x=np.empty((S, N)), best_at=np.empty((S, 2), dtype=np.int32))
+            p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=burn, n_prob=P, probs=ptr(probs), max_lag=min(max_lag, 2 ** 31 - 1), c=float(post["c"]),
+                             **{k: ptr(v) for k, v in s.items()})
+            _lib.check(self._lib.misti_ensemble_posterior(self._ctx, C.byref(q), C.byref(p)))
+            out.update(s)
+        if keep_chain and post is not None:
+            out.update(chain=chain, chain_llh=chain_llh)
+        out["n_points"] = int(n_points[0])
+        return out
+
+    def ensemble_posterior(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
+                           thin=1, temperature=1.0, a=2.0, seed=0, ids=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, keep_chain=False, c=5.0):
+        """``misti_ensemble_posterior``: ``ensemble_sample`` on the same arguments - the same kernels, stream and bits - followed by the
+        posterior summaries of its chain, reduced per search ON THE DEVICE: without ``keep_chain`` the chain never leaves it.  The rule is
+        ``optimize.ensemble_posterior_rule`` on the kept steps ``burn ... n_keep - 1`` (n of them), bit for bit: ``probs`` (1 ... 8
+        probabilities in [0, 1]) give exact order statistics interpolated, ``max_lag`` caps the lags of the autocorrelation (None:
+        ``n - 1``, every lag), ``c`` is Sokal's window constant.
+        Returns dict(mean[S][N], cov[S][N][N], quant[S][N][len(probs)], tau[S][N] (in kept steps), window[S][N] (-1: no lag up to the
+        cap closed the window), best_llh[S], best_x[S][N], best_at[S][2] ((kept step - burn, walker); (-1, -1): no sample has a value),
+        accepted, last, last_llh, n_points as ``ensemble_sample``), and chain, chain_llh with ``keep_chain``."""
+        return self._ensemble("ensemble_posterior", dict(burn=burn, probs=probs, max_lag=max_lag, c=c), bool(keep_chain), init, rows, table, box,
+                              split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature, a, seed, ids)
+
+    def ensemble_summary_dev(self, chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0, want=None):
+        """``misti_ens_summary_dev``: the posterior summaries of a chain that is already on the device - ``chain`` a contiguous float64
+        torch tensor ``[S][K][W][N]`` on this engine's device, ``chain_llh`` ``[S][K][W]`` or None (no best sample).  Asynchronous on
+        the engine's stream; the rule is ``optimize.ensemble_posterior_rule``, bit for bit.  ``want``: the outputs to compute (default
+        all of mean, cov, quant, tau, window, best_llh, best_x, best_at); one that is left out is not computed and the others' bits do
+        not change.  Returns a dict of torch tensors on the device."""
+        import torch
+        names = ("mean", "cov", "quant", "tau", "window", "best_llh", "best_x", "best_at")
+        want = names if want is None else tuple(want)
+        if chain.dim() != 4 or chain.dtype != torch.float64 or not chain.is_contiguous():
+            raise ValueError("ensemble_summary_dev: chain must be a contiguous float64 tensor [S][K][W][N]")
+        S, K, W, N = chain.shape
+        if chain_llh is not None and (tuple(chain_llh.shape) != (S, K, W) or chain_llh.dtype != torch.float64 or not chain_llh.is_contiguous()):
+            raise ValueError("ensemble_summary_dev: chain_llh must be a contiguous float64 tensor [S][K][W]")
+        pr = _f64(probs).reshape(-1)
+        P = pr.size
+        shapes = dict(mean=(S, N), cov=(S, N, N), quant=(S, N, P), tau=(S, N), window=(S, N), best_llh=(S,), best_x=(S, N), best_at=(S, 2))
+        out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("window", "best_at") else torch.float64, device=chain.device) for k in names if k in want}
+        max_lag = max(K - int(burn) - 1, 0) if max_lag is None else int(max_lag)
+        p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=int(burn), n_prob=P, probs=pr.ctypes.data, max_lag=min(max_lag, 2 ** 31 - 1), c=float(c),
+                         **{k: v.data_ptr() or None for k, v in out.items()})
+        _lib.check(self._lib.misti_ens_summary_dev(self._ctx, S, K, W, N, C.c_void_p(chain.data_ptr()) if chain.data_ptr() else None,
+                                                   C.c_void_p(chain_llh.data_ptr()) if chain_llh is not None and chain_llh.data_ptr() else None, C.byref(p)))
+        return out
 
     def enable_solver_trace(self, on=True):
         """Record, for the following batches, SciPy-comparable solver statistics per candidate and interval

@@ -1694,34 +1694,195 @@ def ensemble_summary(chain, burn=0, accepted=None, n_step=None):
     return dict(mean=flat.mean(axis=0), median=q[1], q025=q[0], q975=q[2], tau=tau, short=(K - burn) < 50.0 * tau, acceptance=acc, n=K - burn)
 
 
-def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0):
+# ----------------------------------------------------------------------------------- posterior summaries on the device ----
+# The rule of misti_ens_summary_dev / misti_ensemble_posterior stated on the host (include/misti_hip.h, "posterior summaries on the
+# device"): the device result is this, bit for bit.  Every operation is rounded on its own; NumPy's elementwise arithmetic does that.
+POST_MAX_PROBS = 8
+_POST_LANES = 64
+
+
+def post_order_key(x):
+    """The rule's total order: the 64-bit key of a double's bits - a set sign bit flips all bits, a clear one only the sign bit.
+    -0.0 sorts before +0.0, NaN (of a clear sign bit) last."""
+    b = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    return np.where(b >> np.uint64(63) != 0, ~b, b ^ np.uint64(1 << 63))
+
+
+def lsum(v):
+    """The only way the rule sums over steps, along axis 0 of ``v[count][...]`` (count >= 1): 64 partials, partial l =
+    ``v[l] + v[l + 64] + ...`` in increasing index over ``ceil(count / 64)`` terms, an absent term being +0.0; then
+    ``partial[l] += partial[l + stride]`` for ``l < stride``, stride = 32, 16, 8, 4, 2, 1; the result is ``partial[0]``."""
+    v = np.asarray(v, dtype=np.float64)
+    rows = -(-v.shape[0] // _POST_LANES)
+    pad = np.zeros((rows * _POST_LANES,) + v.shape[1:])
+    pad[:v.shape[0]] = v
+    pad = pad.reshape((rows, _POST_LANES) + v.shape[1:])
+    with np.errstate(all="ignore"):
+        part = pad[0].copy()
+        for r in range(1, rows):
+            part = part + pad[r]
+        stride = _POST_LANES // 2
+        while stride >= 1:
+            part[:stride] = part[:stride] + part[stride:2 * stride]
+            stride //= 2
+    return part[0]
+
+
+def ensemble_posterior_rule(chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0):
+    """The rule of ``misti_ens_summary_dev``, operation for operation, for ``chain[S][K][W][N]`` (or one search ``[K][W][N]``) and
+    ``chain_llh[S][K][W]`` (or None).  Search s has ``x[t][w][j]`` for the kept steps ``t = burn ... K - 1``: ``n = K - burn`` steps,
+    ``m = n W`` samples.
+      order     the samples of a coordinate by ``post_order_key``: ``x_(0) <= ... <= x_(m-1)``
+      quantile  ``h = double(m - 1) p``, ``i = floor(h)``, ``g = h - i``; ``g == 0`` or ``i >= m - 1``: ``x_(min(i, m - 1))``
+                exactly, otherwise ``x_(i) + g (x_(i+1) - x_(i))``
+      mean      ``e_t[j] = (x[t][0][j] + x[t][1][j] + ...) / W`` in walker order, ``mean[j] = lsum(e)[j] / n``
+      cov       ``lsum_t(sum over w in walker order of (x[t][w][j] - mean[j]) (x[t][w][k] - mean[k])) / (m - 1)``, j <= k, mirrored
+      tau       ``y_t = e_t[j] - mean[j]``, ``L = min(max_lag, n - 1)`` (``max_lag`` None: ``n - 1``), ``c_k = lsum_{t < n - k}(y_t
+                y_{t+k})``; ``c_0 == 0`` and ``L >= 1``: tau = 1, window = 0; otherwise ``rho_k = c_k / c_0``, ``tau_0 = 1``, ``tau_M =
+                tau_{M-1} + 2 rho_M``, window the smallest M in 0 ... L with ``double(M) >= c tau_M``; none: window = -1 and ``tau_L``
+                (so ``L == 0`` gives window = -1 and tau = 1).  Reported: ``tau_window``, or 1 where that is below 1.  This is
+                ``autocorrelation_time``'s estimator by direct sums, with the lag capped
+      best      among the kept (t, w) whose ``chain_llh`` is neither NaN nor -inf the largest, ties to the lowest t, then the lowest w:
+                ``best_llh``, ``best_x``, ``best_at = (t - burn, w)``; none, or no ``chain_llh``: -inf, NaN, (-1, -1)
+    A chain element that is not finite is no error: the key order and IEEE arithmetic define the result, and since IEEE leaves a NaN's
+    sign and payload open, a NaN in ``mean``, ``cov``, ``quant`` or ``tau`` is the canonical quiet NaN (``best_x`` copies the sample's bits).
+    Returns dict(mean[S][N], cov[S][N][N], quant[S][N][P], tau[S][N], window[S][N] int32, best_llh[S], best_x[S][N], best_at[S][2]
+    int32, order[S][N][m]: the order statistics themselves) - without the leading axis for one search."""
+    x = np.asarray(chain, dtype=np.float64)
+    one = x.ndim == 3
+    if one:
+        x = x[None]
+        chain_llh = None if chain_llh is None else np.asarray(chain_llh, dtype=np.float64)[None]
+    if x.ndim != 4:
+        raise ValueError("ensemble_posterior_rule: chain must be [S][K][W][N] or [K][W][N]")
+    S, K, W, N = x.shape
+    burn = int(burn)
+    pr = np.asarray(probs, dtype=np.float64).reshape(-1)
+    P = pr.size
+    if not 0 <= burn < K or not 1 <= P <= POST_MAX_PROBS or not ((pr >= 0) & (pr <= 1)).all() or W < 1 or N < 1:
+        raise ValueError("ensemble_posterior_rule: burn must be 0 ... K - 1, 1 ... %d probabilities in [0, 1]" % POST_MAX_PROBS)
+    n = K - burn
+    m = n * W
+    max_lag = n - 1 if max_lag is None else int(max_lag)
+    c = float(c)
+    if max_lag < 0 or not (np.isfinite(c) and c > 0):
+        raise ValueError("ensemble_posterior_rule: max_lag must not be negative, c finite and positive")
+    L = min(max_lag, n - 1)
+    llh = None if chain_llh is None else np.asarray(chain_llh, dtype=np.float64).reshape(S, K, W)
+    out = dict(mean=np.empty((S, N)), cov=np.empty((S, N, N)), quant=np.empty((S, N, P)), tau=np.empty((S, N)), window=np.empty((S, N), dtype=np.int32),
+               best_llh=np.full(S, -np.inf), best_x=np.full((S, N), np.nan), best_at=np.full((S, 2), -1, dtype=np.int32), order=np.empty((S, N, m)))
+    with np.errstate(all="ignore"):
+        for s in range(S):
+            k = x[s, burn:]                                                   # [n][W][N]
+            flat = k.reshape(m, N)
+            for j in range(N):
+                v = np.ascontiguousarray(flat[:, j])
+                o = v[np.argsort(post_order_key(v), kind="stable")]
+                out["order"][s, j] = o
+                for p in range(P):
+                    h = float(m - 1) * pr[p]
+                    i = int(np.floor(h))
+                    g = h - np.floor(h)
+                    out["quant"][s, j, p] = o[min(i, m - 1)] if g == 0.0 or i >= m - 1 else o[i] + g * (o[i + 1] - o[i])
+            e = k[:, 0, :].copy()
+            for w in range(1, W):
+                e = e + k[:, w, :]
+            e = e / float(W)
+            mean = lsum(e) / float(n)
+            out["mean"][s] = mean
+            d = k - mean                                                      # [n][W][N]
+            for j in range(N):
+                for q in range(j, N):
+                    prod = d[:, :, j] * d[:, :, q]
+                    acc = prod[:, 0].copy()
+                    for w in range(1, W):
+                        acc = acc + prod[:, w]
+                    out["cov"][s, j, q] = out["cov"][s, q, j] = lsum(acc) / float(m - 1)
+            y = e - mean
+            for j in range(N):
+                yj = y[:, j]
+                c0 = lsum(yj * yj)
+                tau, window = 1.0, -1
+                if c0 == 0.0 and L >= 1:
+                    window = 0
+                else:
+                    for M in range(0, L + 1):
+                        if M:
+                            tau = tau + 2.0 * (lsum(yj[:n - M] * yj[M:]) / c0)
+                        if float(M) >= c * tau:
+                            window = M
+                            break
+                out["tau"][s, j] = 1.0 if tau < 1.0 else tau
+                out["window"][s, j] = window
+            if llh is not None:
+                f = llh[s, burn:].reshape(m)
+                ok = ~np.isnan(f) & (f != -np.inf)
+                if ok.any():
+                    i = int(np.argmax(np.where(ok, f, -np.inf)))
+                    out["best_llh"][s], out["best_x"][s], out["best_at"][s] = f[i], flat[i], (i // W, i % W)
+    for k_ in ("mean", "cov", "quant", "tau"):                                 # a NaN result: the canonical quiet NaN
+        out[k_][np.isnan(out[k_])] = np.nan
+    return {k_: v[0] for k_, v in out.items()} if one else out
+
+
+def posterior_table(result, n_step, walkers=None):
+    """What one reads off ``ensemble_posterior`` / ``ensemble_posterior_rule`` per coordinate, with ``n_step`` = n, the kept steps
+    behind the summary, and W ``walkers`` (default: those of ``result["last"]``): dict(mean, sd (the square root of the covariance's
+    diagonal), quant, tau, n_eff = n W / tau, short: fewer than 50 tau kept steps or no lag closed the window (window == -1), corr: the
+    correlation matrix)."""
+    n, W = int(n_step), int(np.asarray(result["last"]).shape[-2] if walkers is None else walkers)
+    cov = np.asarray(result["cov"], dtype=np.float64)
+    tau = np.asarray(result["tau"], dtype=np.float64)
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(np.diagonal(cov, axis1=-2, axis2=-1))
+        corr = cov / (sd[..., :, None] * sd[..., None, :])
+        n_eff = float(n * W) / tau
+    return dict(mean=np.asarray(result["mean"]), sd=sd, quant=np.asarray(result["quant"]), tau=tau, n_eff=n_eff,
+                short=(n < 50.0 * tau) | (np.asarray(result["window"]) == -1), corr=corr)
+
+
+def _mcmc_call(engine, summary, n_step, thin):
+    """``Engine.ensemble_sample``, or with ``summary`` (a dict of ``burn``, ``probs``, ``max_lag``, ``keep_chain``, ``c``; ``burn``
+    defaults to half the kept steps) ``Engine.ensemble_posterior``."""
+    if summary is None:
+        return engine.ensemble_sample
+    opts = dict(summary)
+    opts.setdefault("burn", (int(n_step) // int(thin)) // 2)
+    return lambda *a, **kw: engine.ensemble_posterior(*a, **kw, **opts)
+
+
+def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None):
     """``bootstrap_profile_de``'s sampler: per (row, split) pair ONE ensemble inside ``box`` (``(lo, hi)``, each ``[n_param]``, finite), all
     R x P ensembles in ONE ``misti_ensemble_sample`` call - every half-step one dense engine batch.  ``init`` is ``[W][n_param]`` (every
     pair starts from it) or ``[R][P][W][n_param]``.  The stream id of an ensemble is its split's index: the rows of a bootstrap share
     their random numbers, and a row's result does not depend on the other rows.
-    Returns what ``Engine.ensemble_sample`` returns with the leading axis reshaped to ``[R][P]``."""
+    ``summary``: None, or a dict of ``Engine.ensemble_posterior``'s options (``burn`` - default half the kept steps -, ``probs``,
+    ``max_lag``, ``keep_chain``, ``c``): the call goes through ``misti_ensemble_posterior`` and the chain stays on the device.
+    Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``) returns with the leading axis reshaped to ``[R][P]``."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_values, dtype=float).reshape(-1)
     R, Q = rows.shape[0], splits.size
     r_of, j_of = (v.ravel() for v in np.meshgrid(np.arange(R), np.arange(Q), indexing="ij"))
     x0 = np.asarray(init, dtype=float)
     x0 = np.broadcast_to(x0, (R, Q) + x0.shape[-2:]).reshape((R * Q,) + x0.shape[-2:])
-    out = engine.ensemble_sample(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin, temperature=temperature,
-                                 a=a, seed=seed, ids=j_of.astype(np.uint64))
+    out = _mcmc_call(engine, summary, n_step, thin)(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin,
+                                                    temperature=temperature, a=a, seed=seed, ids=j_of.astype(np.uint64))
     return {k: (v.reshape(R, Q, *v.shape[1:]) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
 
 
-def split_fit_mcmc(engine, jsfs_rows, init, box, band_bounds=None, pulse_times=None, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0):
+def split_fit_mcmc(engine, jsfs_rows, init, box, band_bounds=None, pulse_times=None, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None):
     """``split_fit_de``'s sampler: per row ONE ensemble over (optimised parameters, split) inside ``box`` (``(lo, hi)``, each
     ``[n_param + 1]``, finite, the split last), all R ensembles in ONE ``misti_ensemble_sample`` call.  ``init`` is ``[W][n_param + 1]``
     (every row starts from it) or ``[R][W][n_param + 1]``; every row draws from stream 0 (the rows of a bootstrap share their random
     numbers - only the data differ).  ``band_bounds`` / ``pulse_times`` apply to every ensemble.
-    Returns what ``Engine.ensemble_sample`` returns (leading axis: the row)."""
+    ``summary``: None, or a dict of ``Engine.ensemble_posterior``'s options (``burn`` - default half the kept steps -, ``probs``,
+    ``max_lag``, ``keep_chain``, ``c``): the call goes through ``misti_ensemble_posterior`` and the chain stays on the device.
+    Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``) returns (leading axis: the row)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     R = rows.shape[0]
     x0 = np.asarray(init, dtype=float)
     x0 = np.ascontiguousarray(np.broadcast_to(x0, (R,) + x0.shape[-2:]))
     tile = lambda v, shape: None if v is None else np.repeat(np.asarray(v, dtype=np.int32).reshape(shape), R, axis=0)
-    return engine.ensemble_sample(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
-                                  pulse_times=tile(pulse_times, (1, -1)), n_step=n_step, thin=thin, temperature=temperature, a=a, seed=seed,
-                                  ids=np.zeros(R, dtype=np.uint64))
+    return _mcmc_call(engine, summary, n_step, thin)(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
+                                                     pulse_times=tile(pulse_times, (1, -1)), n_step=n_step, thin=thin, temperature=temperature,
+                                                     a=a, seed=seed, ids=np.zeros(R, dtype=np.uint64))
