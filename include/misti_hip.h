@@ -836,6 +836,99 @@ int misti_ens_summary_dev(misti_ctx* ctx, int64_t S, int64_t K, int32_t W, int32
  * K = n_keep (n_keep == 0 leaves no burn to give).  n_start == 0 returns 0 and writes nothing. */
 int misti_ensemble_posterior(misti_ctx* ctx, const misti_ens_t* sampler, const misti_ens_post_t* post);
 
+/* ---- tempered ensemble MCMC -------------------------------------------------------------------- */
+/* Parallel tempering (replica exchange) over misti_ensemble_sample, for a likelihood with several basins: an affine-invariant ensemble
+ * that starts in one basin stays there.  Fit s is a ladder of L = n_rung ensembles at the temperatures T_0 < T_1 < ... < T_{L-1};
+ * every rung samples llk / T_l, neighbouring rungs trade walkers, and the cold rung (rung 0) carries the posterior.  A swap needs no
+ * evaluation - both log-likelihoods are already in HBM -, and all rungs of all fits move in the same engine batch: a half-step is ONE
+ * batch of n_start x n_rung x walkers / 2 slots.  The rule is THE PROJECT'S OWN, stated once in NumPy (optimize.tempered_rule); the
+ * device result is that, bit for bit, on the engine's own objective.
+ *
+ * Row, split, band bounds, pulse times, box and stream id belong to the FIT; the temperature to the rung; rung l is W = walkers walkers
+ * init[s][l][W][N] inside the fit's box.  The rule:
+ *   - a rung moves exactly as a search of misti_ensemble_sample moves (the initial batch, the halves, the stretch, rejection in
+ *     advance outside the box, the decision with d = N_free - 1 and T = T_l, ens_exp), with one difference: walker i of rung l of
+ *     step t owns block (t L + l) W + i of numpy.random.Philox(key=[seed, ids[s]]).  With L = 1 that is block t W + i: a one-rung
+ *     call equals misti_ensemble_sample at temperature ladder[s][0] bit for bit;
+ *   - a swap round comes behind half 1 of step t when swap_every >= 1 and t % swap_every == 0 (swap_every == 0: no swaps).  Round
+ *     n = t / swap_every treats the pairs (l, l + 1) for l = p, p + 2, ... < L - 1 with p = (n - 1) & 1; walker i of rung l faces
+ *     walker i of rung l + 1.  Its uniform u = (w[3] >> 11) 2^-53 is the fourth word, read by nothing else, of the LOWER rung's own
+ *     block (t L + l) W + i.  If either walker has no value nothing happens and nothing is counted; otherwise db = 1.0 / T_l -
+ *     1.0 / T_{l+1}, e = db (llk_{l+1,i} - llk_{l,i}), and the walkers trade places - coordinates and values - iff u < ens_exp(e).
+ *     Every operation is rounded on its own, no fused multiply-add.  swap_proposed[s][l] counts the pairs (l, l + 1) that had two
+ *     values, swap_accepted[s][l] those that traded; accepted[s][l][i] counts stretch moves per rung and walker SLOT;
+ *   - the chain row of a kept step (t % thin == 0, K = n_step / thin rows) is the state AFTER that step's swap round.  The
+ *     coordinates of the cold rung only are kept, chain[n_start][K][W][N] - the layout misti_ens_summary_dev reads -, and the values
+ *     of every rung, chain_llh[n_start][L][K][W];
+ *   - thermodynamic integration over the kept steps t = burn ... K - 1 (n of them): e_t = (llh[t][0] + ... + llh[t][W-1] in walker
+ *     order) / W, rung_llh[s][l] = lsum(e) / n (lsum: "posterior summaries on the device"), beta_l = 1.0 / T_l, and logz[s] the sum
+ *     for l = 0 ... L - 2 in increasing l, from +0.0, of (0.5 (E_l + E_{l+1})) (beta_l - beta_{l+1}), each operation rounded on its
+ *     own; L = 1 gives +0.0.  IEEE arithmetic defines the result where a value is -inf; a NaN is stored as the canonical quiet NaN;
+ *     K == 0 leaves no step to average: every rung_llh is NaN.
+ *     WHAT logz IS: the trapezoid rule, on the ladder's own L points, for log Z(beta_0) - log Z(beta_{L-1}), Z(beta) the integral of
+ *     exp(beta llk) against the NORMALISED uniform prior on the box.  The piece below beta_{L-1}, down to the prior at beta = 0, is
+ *     NOT included, and a coarse ladder biases the rule.  For a composite likelihood the number means something only at the
+ *     calibrated temperature (T_0 = optimize.composite_temperature).
+ * A fit's result is a function of its own arguments alone.  Rungs, values, counters and both chains stay in HBM until one copy at the
+ * end; per step the host issues propose, evaluation, accept, twice, and a swap launch on swap steps, and reads nothing back.  With
+ * `post` (or NULL) the summary kernels of misti_ens_summary_dev run on the cold chain where it lies (K = n_step / thin) and the
+ * summaries are copied to post's HOST buffers; the chain itself comes back only where `chain` is given.  Host buffers; synchronous.
+ *
+ * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this library's
+ * (then the same for `post` where it is given); a split mode that is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED; a negative
+ * n_start; a NULL pointer among init / rows / jsfs / box_lo / box_hi / ladder / last / last_llh / rung_llh / logz (and split_times
+ * with MISTI_SPLIT_PER_START); n_rep < 1; walkers odd or < 4 (MISTI_E_LIMIT for walkers > MISTI_ENS_MAX_WALKERS); n_step < 0; thin <
+ * 1; a that is not finite or not > 1; n_rung < 1 (MISTI_E_LIMIT for n_rung > MISTI_PT_MAX_RUNGS); n_ladder neither 1 nor n_start; a
+ * ladder entry that is not finite and positive, or not above the entry before it (the message names the fit and the rung);
+ * swap_every < 0; burn outside 0 ... K - 1 where K > 0; n_box neither 1 nor n_start; a row out of range; a non-finite split time;
+ * then a NULL context; a model without a coordinate to sample; MISTI_E_LIMIT for N > MISTI_MAX_PARAMS, n_start x n_rung x walkers >
+ * INT32_MAX / 8 / (N + 1), n_rep > INT32_MAX, or kept steps beyond INT32_MAX / 8 / N / (n_start x n_rung x walkers); the box as in
+ * misti_ensemble_sample; a walker of init that is not finite or lies outside its box (the message names the fit, the rung, the walker
+ * and the coordinate); then misti_ens_summary_dev's for `post` with K = n_step / thin.  A refused call writes nothing.  n_start == 0
+ * returns 0 once the arguments are accepted, and writes nothing; n_step == 0 evaluates the initial rungs and returns them. */
+#define MISTI_PT_MAX_RUNGS 64
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_pt_t) */
+    int32_t split;                   /* MISTI_SPLIT_PER_START or MISTI_SPLIT_FITTED */
+    const double* split_times;       /* MISTI_SPLIT_PER_START: [n_start], finite */
+    int64_t n_start;                 /* fits */
+    const double* init;              /* [n_start][n_rung][walkers][N]: the initial rungs, every walker inside the fit's box */
+    const int32_t* rows;             /* [n_start], 0 <= rows[s] < n_rep */
+    int64_t n_rep;
+    const double* jsfs;              /* [n_rep][8] */
+    const int32_t* band_bounds;      /* [n_start][n_band][2] or NULL; ignored when the model has no band */
+    const int32_t* pulse_times;      /* [n_start][n_pulse] or NULL; ignored when the model has no pulse */
+    int64_t n_box;                   /* 1: one box for every fit; n_start: a box per fit */
+    const double* box_lo;            /* [n_box][N] finite */
+    const double* box_hi;            /* [n_box][N] finite, >= box_lo */
+    int32_t walkers;                 /* W: even, 4 ... MISTI_ENS_MAX_WALKERS */
+    int32_t n_rung;                  /* L: 1 ... MISTI_PT_MAX_RUNGS */
+    int32_t n_ladder;                /* 1: one ladder for every fit; n_start: a ladder per fit */
+    int32_t n_step;                  /* steps after the initial rungs; 0 allowed */
+    const double* ladder;            /* [n_ladder][n_rung] finite, > 0, strictly increasing along a ladder */
+    int32_t thin;                    /* >= 1 */
+    int32_t swap_every;              /* >= 0; 0: no swaps */
+    int32_t burn;                    /* kept steps dropped before rung_llh / logz: 0 ... K - 1 (K == 0: not looked at) */
+    double a;                        /* the stretch's scale: finite, > 1 */
+    uint64_t seed;
+    const uint64_t* ids;             /* [n_start] stream ids, or NULL: 0, 1, ... */
+    double* chain;                   /* [n_start][K][walkers][N] or NULL: the COLD rung after steps thin, 2 thin, ... */
+    double* chain_llh;               /* [n_start][n_rung][K][walkers] or NULL: the log-likelihoods of every rung (-inf: no value) */
+    int32_t* accepted;               /* [n_start][n_rung][walkers] or NULL: stretch moves accepted per rung and walker slot */
+    int32_t* swap_proposed;          /* [n_start][n_rung - 1] or NULL */
+    int32_t* swap_accepted;          /* [n_start][n_rung - 1] or NULL */
+    double* last;                    /* [n_start][n_rung][walkers][N] the final rungs */
+    double* last_llh;                /* [n_start][n_rung][walkers] */
+    double* rung_llh;                /* [n_start][n_rung] */
+    double* logz;                    /* [n_start] */
+    int64_t* n_points;               /* [1] or NULL: proposals the call handed the engine, as in misti_ens_t */
+} misti_pt_t;
+int misti_tempered_sample(misti_ctx* ctx, const misti_pt_t* sampler, const misti_ens_post_t* post /* or NULL */);
+/* The decision on one pair of walkers, on the host through the very function the swap kernel calls (llk -inf or NaN: no value, no
+ * swap).  No context, no device.  MISTI_E_ARG for a NULL swap, a temperature that is not finite and positive, T_lo not below T_hi, or
+ * u outside [0, 1). */
+int misti_pt_swap(double T_lo, double T_hi, double llk_lo, double llk_hi, double u, int32_t* swap);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

@@ -95,6 +95,20 @@ class EnsSample(C.Structure):
                 ("last_llh", C.c_void_p), ("n_points", C.c_void_p)]
 
 
+PT_MAX_RUNGS = 64
+
+
+class PtSample(C.Structure):
+    """``misti_pt_t``: tempered ensemble MCMC per fit; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("split", C.c_int32), ("split_times", C.c_void_p), ("n_start", C.c_int64), ("init", C.c_void_p),
+                ("rows", C.c_void_p), ("n_rep", C.c_int64), ("jsfs", C.c_void_p), ("band_bounds", C.c_void_p), ("pulse_times", C.c_void_p),
+                ("n_box", C.c_int64), ("box_lo", C.c_void_p), ("box_hi", C.c_void_p), ("walkers", C.c_int32), ("n_rung", C.c_int32),
+                ("n_ladder", C.c_int32), ("n_step", C.c_int32), ("ladder", C.c_void_p), ("thin", C.c_int32), ("swap_every", C.c_int32),
+                ("burn", C.c_int32), ("a", C.c_double), ("seed", C.c_uint64), ("ids", C.c_void_p), ("chain", C.c_void_p),
+                ("chain_llh", C.c_void_p), ("accepted", C.c_void_p), ("swap_proposed", C.c_void_p), ("swap_accepted", C.c_void_p),
+                ("last", C.c_void_p), ("last_llh", C.c_void_p), ("rung_llh", C.c_void_p), ("logz", C.c_void_p), ("n_points", C.c_void_p)]
+
+
 POST_MAX_PROBS = 8
 
 
@@ -139,6 +153,8 @@ SYMBOLS = {
     "misti_ensemble_sample": (C.c_int, [C.c_void_p, C.POINTER(EnsSample)]),
     "misti_ens_summary_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(EnsPost)]),
     "misti_ensemble_posterior": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost)]),
+    "misti_tempered_sample": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost)]),
+    "misti_pt_swap": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "misti_ens_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_ens_exp": (C.c_int, [C.c_double, C.c_void_p]),
     "misti_ens_accept": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

@@ -93,6 +93,15 @@ and the GNU-parallel recipe of ``README.md:110-115``):
     --mcmc-temp T|auto        with --mcmc: the temperature (default 1).  auto: trace(H^-1 J) / p from the curvature at the data row's fit and
                               the bootstrap rows' class counts - the magnitude adjustment of a composite likelihood; needs --all-bs
     --mcmc-out FILE.npz       with --mcmc: the chains, their llh, the acceptance counters and the final ensembles
+    --mcmc-ladder L RATIO     with --mcmc: PARALLEL TEMPERING (misti_tempered_sample) - per fit a ladder of L ensembles (1 ... 64) at the temperatures
+                              T0 RATIO^(l / (L - 1)), T0 the temperature of --mcmc-temp (auto included), RATIO finite and > 1; every rung starts from
+                              the ensemble the cold rung starts from, neighbouring rungs trade walkers, all rungs ride in the same engine batches.
+                              The `mcmc:` / `post:` lines are the cold rung's; behind them one `ladder:` line per fit: the temperatures, the swap
+                              acceptance per pair, the mean llh per rung and logz, the trapezoid estimate of log Z(1 / T0) - log Z(1 / T_max) under
+                              the normalised uniform prior on the box (the piece above T_max is not in it; for a composite likelihood it means
+                              something only at the calibrated temperature, --mcmc-temp auto).  --mcmc-out gains ladder, swap_proposed,
+                              swap_accepted, rung_llh and logz; its chain is the cold rung's, its chain_llh every rung's
+    --mcmc-swap E             with --mcmc-ladder: a swap round every E steps (default 1; 0: never)
     --mcmc-post [P ...]       with --mcmc: the posterior summaries are reduced ON THE DEVICE (misti_ensemble_posterior) - without --mcmc-out the
                               chain never leaves it.  In place of the `mcmc:` lines one `post:` line per coordinate: mean, standard
                               deviation, the quantiles P ... (1 ... 8 probabilities in [0, 1]; default 0.025 0.5 0.975; exact order
@@ -244,6 +253,9 @@ def build_parser():
     p.add_argument("--mcmc-spread", type=float, default=None, metavar="S", help="with --mcmc: spread of the initial ensemble in box widths (default 1e-2)")
     p.add_argument("--mcmc-temp", default=None, metavar="T|auto", help="with --mcmc: the temperature (default 1), or auto: trace(H^-1 J) / p (needs --all-bs)")
     p.add_argument("--mcmc-out", default=None, metavar="FILE.npz", help="with --mcmc: write chains, values, acceptance counters and final ensembles")
+    p.add_argument("--mcmc-ladder", nargs=2, default=None, metavar=("L", "RATIO"),
+                   help="with --mcmc: parallel tempering, L rungs per fit at T0 RATIO^(l / (L - 1)); `ladder:` lines behind the cold rung's summary")
+    p.add_argument("--mcmc-swap", type=int, default=None, metavar="E", help="with --mcmc-ladder: a swap round every E steps (default 1; 0: never)")
     p.add_argument("--mcmc-post", nargs="*", type=float, default=None, metavar="P",
                    help="with --mcmc: posterior summaries reduced on the device, `post:` lines in place of `mcmc:` lines; P ...: the quantiles (default 0.025 0.5 0.975)")
     p.add_argument("--mcmc-lag", type=int, default=None, metavar="L", help="with --mcmc-post: the autocorrelation's lag cap (default: every lag)")
@@ -571,6 +583,8 @@ def mcmc_error(a):
             return "--mcmc-post / --mcmc-lag summarise the chains of --mcmc W STEPS: give --mcmc W STEPS"
         if any(v is not None for v in (a.mcmc_burn, a.mcmc_thin, a.mcmc_seed, a.mcmc_spread, a.mcmc_temp, a.mcmc_out)):
             return "--mcmc-burn / --mcmc-thin / --mcmc-seed / --mcmc-spread / --mcmc-temp / --mcmc-out set the sampler of --mcmc W STEPS: give --mcmc W STEPS"
+        if a.mcmc_ladder is not None or a.mcmc_swap is not None:
+            return "--mcmc-ladder / --mcmc-swap temper the sampler of --mcmc W STEPS: give --mcmc W STEPS"
         return None
     W, steps = a.mcmc
     if not 4 <= W <= 256 or W % 2:
@@ -607,6 +621,17 @@ def mcmc_error(a):
         return "--mcmc-post [P ...]: at most 8 probabilities, each in [0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_post)
     if a.mcmc_lag is not None and (a.mcmc_post is None or a.mcmc_lag < 0):
         return "--mcmc-lag L caps the lags of --mcmc-post: give --mcmc-post, and L >= 0"
+    if a.mcmc_swap is not None and (a.mcmc_ladder is None or a.mcmc_swap < 0):
+        return "--mcmc-swap E sets the swap rounds of --mcmc-ladder: give --mcmc-ladder, and E >= 0"
+    if a.mcmc_ladder is not None:
+        try:
+            L, ratio = int(a.mcmc_ladder[0]), float(a.mcmc_ladder[1])
+        except ValueError:
+            return "--mcmc-ladder L RATIO: an integer and a number (got %s %s)" % tuple(a.mcmc_ladder)
+        if not 1 <= L <= 64:
+            return "--mcmc-ladder L RATIO: 1 <= L <= 64 rungs (got %d)" % L
+        if L > 1 and not (np.isfinite(ratio) and ratio > 1.0):
+            return "--mcmc-ladder L RATIO: RATIO must be finite and > 1 (got %s)" % a.mcmc_ladder[1]
     k = sum(1 for el in a.mi if int(el[4])) + sum(1 for el in a.pu if int(el[3]))
     boxed = {}
     for name, lo, hi in a.box:
@@ -635,13 +660,20 @@ def _mcmc_options(a):
                 temperature="auto" if a.mcmc_temp == "auto" else 1.0 if a.mcmc_temp is None else float(a.mcmc_temp))
 
 
+def _mcmc_ladder_options(a):
+    """The options of --mcmc-ladder: ladder (L, RATIO), or None without it, and swap_every (default 1)."""
+    return dict(ladder=None if a.mcmc_ladder is None else (int(a.mcmc_ladder[0]), float(a.mcmc_ladder[1])), swap_every=1 if a.mcmc_swap is None else a.mcmc_swap)
+
+
 def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=None):
     """--mcmc behind the fits ``x[S][N]`` (fit s: row ``r_of[s]``, stream ``j_of[s]``; ``split_times[S]``, or None with the split as the
     last coordinate): ONE Engine.ensemble_sample call from ensemble_start around every fit (a fit without a value: the middle of the
     box) - or, with ``population[S][W][N]`` (``--de W GENS`` ran with the sampler's W), from DE's final populations: dispersed,
-    inside the box and already evaluated.  Returns (options, temperature, result) - or a string: why --mcmc-temp auto has no temperature."""
-    from .optimize import composite_temperature, ensemble_start, score_covariance
-    o = _mcmc_options(a)
+    inside the box and already evaluated.  With --mcmc-ladder L RATIO: ONE Engine.tempered_sample call on temperature_ladder(T, RATIO, L),
+    every rung from that initial ensemble; the result's ``ladder`` holds the temperatures.
+    Returns (options, temperature, result) - or a string: why --mcmc-temp auto has no temperature."""
+    from .optimize import composite_temperature, ensemble_start, score_covariance, temperature_ladder
+    o = dict(_mcmc_options(a), **_mcmc_ladder_options(a))
     lo, hi = box
     x = np.where(np.isfinite(x), np.clip(x, lo, hi), 0.5 * (lo + hi))
     T = o["temperature"]
@@ -670,11 +702,20 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     if a.mcmc_post is not None:                            # the summaries on the device; the chain comes back only for --mcmc-out
         post = _mcmc_post_options(a)
         sampler = lambda *args, **kw: e.ensemble_posterior(*args, **kw, burn=o["burn"], keep_chain=bool(a.mcmc_out), **post)
-    res = sampler(init, np.asarray(r_of, dtype=np.int32), data, box, split_times=split_times, fit_split=split_times is None,
-                  n_step=o["n_step"], thin=o["thin"], temperature=T, seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
+    common = dict(split_times=split_times, fit_split=split_times is None, n_step=o["n_step"], thin=o["thin"], seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
+    extra = {}
+    if o["ladder"] is not None:
+        ladder = temperature_ladder(T, o["ladder"][1], o["ladder"][0])
+        post = None if a.mcmc_post is None else dict(_mcmc_post_options(a), keep_chain=bool(a.mcmc_out))
+        res = e.tempered_sample(np.ascontiguousarray(np.repeat(init[:, None], ladder.size, axis=1)), np.asarray(r_of, dtype=np.int32), data, box, ladder,
+                                swap_every=o["swap_every"], burn=o["burn"], post=post, **common)
+        res["ladder"] = ladder
+        extra = {k: res[k] for k in ("ladder", "swap_proposed", "swap_accepted", "rung_llh", "logz")}
+    else:
+        res = sampler(init, np.asarray(r_of, dtype=np.int32), data, box, temperature=T, **common)
     if a.mcmc_out:
         np.savez(a.mcmc_out, chain=res["chain"], chain_llh=res["chain_llh"], accepted=res["accepted"], last=res["last"], last_llh=res["last_llh"],
-                 row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T))
+                 row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T), **extra)
     return o, float(T), res
 
 
@@ -696,8 +737,22 @@ def print_post(label, o, res, s):
               "\tbest llh =", res["best_llh"][s], "at = (%d, %d)" % tuple(res["best_at"][s]), "x =", res["best_x"][s][c])
 
 
+def print_ladder(label, res, s):
+    """The ``ladder:`` line of fit s of a tempered run: the temperatures, the swap acceptance per pair (nan: no pair had two values),
+    the mean llh per rung and logz."""
+    with np.errstate(all="ignore"):
+        rate = res["swap_accepted"][s] / res["swap_proposed"][s].astype(float)
+    fmt = lambda v: "[" + ", ".join(repr(float(t)) for t in v) + "]"
+    print("ladder:", label, "\tT =", fmt(res["ladder"]), "\tswaps accepted =", fmt(rate), "\trung llh =", fmt(res["rung_llh"][s]), "\tlogz =", repr(float(res["logz"][s])))
+
+
 def print_mcmc(label, o, res, s):
-    """The ``mcmc:`` lines of fit s: one per coordinate, from ensemble_summary of its chain - or, with --mcmc-post, its ``post:`` lines."""
+    """The ``mcmc:`` lines of fit s: one per coordinate, from ensemble_summary of its chain - or, with --mcmc-post, its ``post:`` lines;
+    of a tempered run (--mcmc-ladder) the cold rung's, and behind them the fit's ``ladder:`` line."""
+    if "logz" in res:
+        cold = {k: v for k, v in res.items() if k not in ("logz", "accepted")}
+        print_mcmc(label, o, dict(cold, accepted=res["accepted"][:, 0]), s)
+        return print_ladder(label, res, s)
     if "quant" in res:
         return print_post(label, o, res, s)
     from .optimize import ensemble_summary
@@ -708,6 +763,9 @@ def print_mcmc(label, o, res, s):
 
 
 def _mcmc_text(o, T, res, dt):
+    if o["ladder"] is not None:
+        return "tempered ensemble MCMC with %d rungs up to %r x the temperature, a swap round every %d steps, %d walkers per rung, %d steps, thin %d, burn %d, from %s, temperature %r, seed %d: %d ladders in one call, %.3f s, %d proposals evaluated" % (
+            o["ladder"][0], o["ladder"][1], o["swap_every"], o["walkers"], o["n_step"], o["thin"], o["burn"], o["start"], T, o["seed"], res["last"].shape[0], dt, res["n_points"])
     return "ensemble MCMC with %d walkers, %d steps, thin %d, burn %d, from %s, temperature %r, seed %d: %d ensembles in one call, %.3f s, %d proposals evaluated" % (
         o["walkers"], o["n_step"], o["thin"], o["burn"], o["start"], T, o["seed"], res["last"].shape[0], dt, res["n_points"])
 

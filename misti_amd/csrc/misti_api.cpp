@@ -1175,7 +1175,7 @@ void nm_per_slot(NmBatch* b, const size_t* slots, int n_batch, T* NmBatch::*arr,
 // ---- the rows problem: what Nelder-Mead, differential evolution and the ensemble sampler are handed alike ------------------------------
 // A start or search s with a split time, a row of a replicate table, optional band bounds and pulse times, an optional box, and
 // optionally the split as the last coordinate.  A per-start field is added HERE, to RowsProblem below and to PointSource / put_point
-// (misti_device.h) - nowhere else.  The three public descriptors lay these fields out differently: one rows_args() each.
+// (misti_device.h) - nowhere else.  The public descriptors lay these fields out differently: one rows_args() each.
 struct RowsArgs {
     int32_t split;                   // MISTI_SPLIT_*
     double split_time;               // MISTI_SPLIT_ONE
@@ -1199,6 +1199,9 @@ RowsArgs rows_args(const misti_de_t& q) {
     return {q.split, 0.0, q.split_times, q.n_start, q.rows, q.n_rep, q.jsfs, q.band_bounds, q.pulse_times, q.n_box, q.box_lo, q.box_hi, q.ids};
 }
 RowsArgs rows_args(const misti_ens_t& q) {
+    return {q.split, 0.0, q.split_times, q.n_start, q.rows, q.n_rep, q.jsfs, q.band_bounds, q.pulse_times, q.n_box, q.box_lo, q.box_hi, q.ids};
+}
+RowsArgs rows_args(const misti_pt_t& q) {
     return {q.split, 0.0, q.split_times, q.n_start, q.rows, q.n_rep, q.jsfs, q.band_bounds, q.pulse_times, q.n_box, q.box_lo, q.box_hi, q.ids};
 }
 
@@ -1746,9 +1749,33 @@ int post_check(const misti_ens_post_t* p, int64_t S, int64_t K, int32_t W, int32
 
 // the launch record of a checked descriptor, without its pointers
 void post_fill(misti::PostArgs& a, int64_t S, int64_t K, int32_t W, int32_t N, const misti_ens_post_t& p) {
-    a.S = S; a.K = K; a.W = W; a.N = N; a.burn = p.burn; a.n = K - p.burn; a.c = p.c;
+    a.S = S; a.K = K; a.llh_K = K; a.W = W; a.N = N; a.burn = p.burn; a.n = K - p.burn; a.c = p.c;
     a.L = p.max_lag < a.n - 1 ? p.max_lag : a.n - 1;
     a.sel = misti::post_select(a.n * W, p.n_prob, p.probs);
+}
+
+// The device side of the summaries of a sampler that keeps its chain (ens_run, pt_run): carved behind everything the sampler carves,
+// so its layout does not move; an output the caller does not ask for is not carved.  back(): the summaries to post's host buffers.
+void post_carve(misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, int N, Carver<double>& f, Carver<int32_t>& i) {
+    const size_t SN = S * (size_t)N, NP = (size_t)p.n_prob;
+    pa.ws_mean = f.take(SN); pa.ws_y = f.take(SN * (size_t)pa.n);
+    pa.mean = p.mean ? f.take(SN) : nullptr; pa.cov = p.cov ? f.take(SN * (size_t)N) : nullptr;
+    pa.quant = p.quant ? f.take(SN * NP) : nullptr; pa.tau = p.tau ? f.take(SN) : nullptr;
+    pa.best_llh = p.best_llh ? f.take(S) : nullptr; pa.best_x = p.best_x ? f.take(SN) : nullptr;
+    pa.window = p.window ? i.take(SN) : nullptr; pa.best_at = p.best_at ? i.take(2 * S) : nullptr;
+}
+int post_back(const misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, int N, hipStream_t sm) {
+    const size_t SN = S * (size_t)N, NP = (size_t)p.n_prob;
+    auto back = [&](void* host, const void* dev, size_t bytes) { return host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm) : hipSuccess; };
+    HIP_TRY(back(p.mean, pa.mean, SN * sizeof(double)));
+    HIP_TRY(back(p.cov, pa.cov, SN * N * sizeof(double)));
+    HIP_TRY(back(p.quant, pa.quant, SN * NP * sizeof(double)));
+    HIP_TRY(back(p.tau, pa.tau, SN * sizeof(double)));
+    HIP_TRY(back(p.window, pa.window, SN * sizeof(int32_t)));
+    HIP_TRY(back(p.best_llh, pa.best_llh, S * sizeof(double)));
+    HIP_TRY(back(p.best_x, pa.best_x, SN * sizeof(double)));
+    HIP_TRY(back(p.best_at, pa.best_at, 2 * S * sizeof(int32_t)));
+    return 0;
 }
 
 // ---- ensemble MCMC per search (misti_ens.hip) ------------------------------------------------------------------------------------
@@ -1804,7 +1831,6 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
     const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp;
     const size_t K = (q.chain || q.chain_llh || post) ? (size_t)(q.n_step / q.thin) : 0;
     PostArgs pa{};
-    const size_t NP = post ? (size_t)post->n_prob : 0, SN = S * (size_t)N;
     if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
     RowsProblem rows(c, rows_args(q), N, whole);
     EnsState st{};
@@ -1820,13 +1846,7 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
         if (K) { st.chain = f.take(S * K * W * (size_t)N); st.chain_llh = f.take(S * K * W); }
         st.accepted = i.take(M); st.submitted = i.take(M);
         rows.layout(f, i, &st.b, &M, 1, M);
-        if (post) {                                        // behind everything the sampler carves: its layout does not move
-            pa.ws_mean = f.take(SN); pa.ws_y = f.take(SN * (size_t)pa.n);
-            pa.mean = post->mean ? f.take(SN) : nullptr; pa.cov = post->cov ? f.take(SN * (size_t)N) : nullptr;
-            pa.quant = post->quant ? f.take(SN * NP) : nullptr; pa.tau = post->tau ? f.take(SN) : nullptr;
-            pa.best_llh = post->best_llh ? f.take(S) : nullptr; pa.best_x = post->best_x ? f.take(SN) : nullptr;
-            pa.window = post->window ? i.take(SN) : nullptr; pa.best_at = post->best_at ? i.take(2 * S) : nullptr;
-        }
+        if (post) post_carve(pa, *post, S, N, f, i);
     };
     if (int r = carve(c, "search", layout)) return r;
     rows.fill(st.src);
@@ -1852,15 +1872,7 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
     if (post) {
         pa.chain = st.chain; pa.chain_llh = st.chain_llh;
         HIP_TRY(launch_post(pa, sm));
-        auto back = [&](void* host, const void* dev, size_t bytes) { return host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm) : hipSuccess; };
-        HIP_TRY(back(post->mean, pa.mean, SN * sizeof(double)));
-        HIP_TRY(back(post->cov, pa.cov, SN * N * sizeof(double)));
-        HIP_TRY(back(post->quant, pa.quant, SN * NP * sizeof(double)));
-        HIP_TRY(back(post->tau, pa.tau, SN * sizeof(double)));
-        HIP_TRY(back(post->window, pa.window, SN * sizeof(int32_t)));
-        HIP_TRY(back(post->best_llh, pa.best_llh, S * sizeof(double)));
-        HIP_TRY(back(post->best_x, pa.best_x, SN * sizeof(double)));
-        HIP_TRY(back(post->best_at, pa.best_at, 2 * S * sizeof(int32_t)));
+        if (int r = post_back(pa, *post, S, N, sm)) return r;
     }
     HIP_TRY(hipMemcpyAsync(q.last, st.x, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
     HIP_TRY(hipMemcpyAsync(q.last_llh, st.llh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
@@ -1881,9 +1893,165 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
     return 0;
 }
 
+// ---- tempered ensemble MCMC per fit (misti_pt.hip) -----------------------------------------------------------------------------------
+// The arguments of misti_tempered_sample, before the first HIP call, in the header's order: ens_check's, with the ladder where the
+// temperature stands and n_start x n_rung x walkers where the limits count.
+int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole) {
+    const RowsArgs a = rows_args(q);
+    if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of fits");
+    if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.ladder || !q.last || !q.last_llh || !q.rung_llh || !q.logz || (a.per_start() && !q.split_times))
+        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / ladder / last / last_llh / rung_llh / logz%s is NULL", a.per_start() ? " / split_times" : "");
+    if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
+    if (q.walkers < 4 || (q.walkers & 1)) return fail(MISTI_E_ARG, "walkers must be even and >= 4 (got %d)", (int)q.walkers);
+    if (q.walkers > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "walkers = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)q.walkers, MISTI_ENS_MAX_WALKERS);
+    if (q.n_step < 0) return fail(MISTI_E_ARG, "n_step must not be negative");
+    if (q.thin < 1) return fail(MISTI_E_ARG, "thin must be >= 1");
+    if (!std::isfinite(q.a) || !(q.a > 1.0)) return fail(MISTI_E_ARG, "a must be finite and > 1 (got %g)", q.a);
+    if (q.n_rung < 1) return fail(MISTI_E_ARG, "n_rung must be >= 1 (got %d)", (int)q.n_rung);
+    if (q.n_rung > MISTI_PT_MAX_RUNGS) return fail(MISTI_E_LIMIT, "n_rung = %d exceeds MISTI_PT_MAX_RUNGS = %d", (int)q.n_rung, MISTI_PT_MAX_RUNGS);
+    if (q.n_ladder != 1 && q.n_ladder != q.n_start) return fail(MISTI_E_ARG, "n_ladder must be 1 or n_start (got %d for %lld fits)", (int)q.n_ladder, (long long)q.n_start);
+    for (int64_t s = 0; s < q.n_ladder; ++s)
+        for (int l = 0; l < q.n_rung; ++l) {
+            const double T = q.ladder[s * q.n_rung + l];
+            if (!std::isfinite(T) || !(T > 0.0)) return fail(MISTI_E_ARG, "ladder[%lld][%d] = %g is not finite and positive", (long long)s, l, T);
+            if (l && !(T > q.ladder[s * q.n_rung + l - 1]))
+                return fail(MISTI_E_ARG, "ladder[%lld][%d] = %g is not above ladder[%lld][%d] = %g: a ladder is strictly increasing", (long long)s, l, T,
+                            (long long)s, l - 1, q.ladder[s * q.n_rung + l - 1]);
+        }
+    if (q.swap_every < 0) return fail(MISTI_E_ARG, "swap_every must not be negative (got %d)", (int)q.swap_every);
+    const int64_t K = q.n_step / q.thin;
+    if (K > 0 && (q.burn < 0 || q.burn >= K)) return fail(MISTI_E_ARG, "burn must be 0 ... K - 1 (got %d for %lld kept steps)", (int)q.burn, (long long)K);
+    if (int r = check_n_box(a, "fits")) return r;
+    if (int r = check_rows(a, whole)) return r;
+    const int64_t per = (int64_t)q.walkers * q.n_rung;
+    if (int r = check_limits(c, a, per, "fits x rungs x walkers", N)) return r;
+    if (q.n_start > 0 && K > INT32_MAX / 8 / N / per / q.n_start)
+        return fail(MISTI_E_LIMIT, "the chain of %lld fits x %d rungs x %lld kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
+                    (long long)q.n_start, (int)q.n_rung, (long long)K, (int)q.walkers, N);
+    for (int64_t b = 0; b < q.n_box; ++b) {
+        if (int r = check_box(a, N, b, "the sampler's prior is uniform on a finite box")) return r;
+        int n_free = 0;
+        for (int k = 0; k < N; ++k) n_free += q.box_lo[b * N + k] != q.box_hi[b * N + k] ? 1 : 0;
+        if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
+    }
+    for (int64_t s = 0; s < q.n_start; ++s)
+        for (int l = 0; l < q.n_rung; ++l)
+            for (int i = 0; i < q.walkers; ++i)
+                for (int k = 0; k < N; ++k) {
+                    const double v = q.init[((s * q.n_rung + l) * q.walkers + i) * N + k];
+                    const int64_t o = (q.n_box > 1 ? s : 0) * N + k;
+                    if (!std::isfinite(v)) return fail(MISTI_E_ARG, "init[%lld][%d][%d][%d] is not finite", (long long)s, l, i, k);
+                    if (v < q.box_lo[o] || v > q.box_hi[o])
+                        return fail(MISTI_E_ARG, "init[%lld][%d][%d][%d] = %g is outside its box [%g, %g]", (long long)s, l, i, k, v, q.box_lo[o], q.box_hi[o]);
+                }
+    return 0;
+}
+
+// A checked call with n_start >= 1: ens_run over n_start x n_rung searches (EnsState::L), with a swap launch behind the steps that
+// have a round and the reduction at the end.  The values of every rung are always kept on the device (the reduction reads them), the
+// cold rung's coordinates where the caller or `post` wants them.
+int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens_post_t* post) {
+    using namespace misti;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t F = (size_t)q.n_start, L = (size_t)q.n_rung, S = F * L, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_ladder * L;
+    const size_t K = (size_t)(q.n_step / q.thin), KX = (q.chain || post) ? K : 0, P = F * (L - 1);
+    PostArgs pa{};
+    if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
+    RowsProblem rows(c, rows_args(q), N, whole);
+    EnsState st{};
+    st.S = (int64_t)S; st.L = q.n_rung; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
+    st.temp_per_start = q.n_ladder > 1 ? 1 : 0;
+    st.n_keep = (int64_t)K;
+    PtState pt{};
+    double *llk = nullptr, *d_init = nullptr, *d_temp = nullptr, *d_points = nullptr, *d_rung = nullptr, *d_logz = nullptr;
+    auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
+        st.b.pts = f.take(M * N); st.x = f.take(M * N); st.llh = f.take(M); st.b.split = f.take(M); llk = f.take(M);
+        st.z = f.take(S * H); st.u_acc = f.take(S * H);
+        d_init = f.take(M * N); d_temp = f.take(NT);
+        d_points = f.take(S);                              // int64 per search: 8-byte words of the double buffer
+        d_rung = f.take(S); d_logz = f.take(F);
+        if (KX) st.chain = f.take(F * K * W * (size_t)N);
+        if (K) st.chain_llh = f.take(S * K * W);
+        st.accepted = i.take(M); st.submitted = i.take(M);
+        pt.swap_proposed = i.take(P); pt.swap_accepted = i.take(P);
+        rows.layout(f, i, &st.b, &M, 1, M);
+        if (post) post_carve(pa, *post, F, N, f, i);
+    };
+    if (int r = carve(c, "search", layout)) return r;
+    rows.fill(st.src);
+    st.temp = d_temp;
+    st.points = reinterpret_cast<long long*>(d_points);
+    hipStream_t sm = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_init, q.init, M * N * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_temp, q.ladder, NT * sizeof(double), hipMemcpyHostToDevice, sm));
+    if (P) HIP_TRY(hipMemsetAsync(pt.swap_proposed, 0, 2 * P * sizeof(int32_t), sm));     // the two counters lie back to back
+    if (int r = rows.upload(c)) return r;
+    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
+    HIP_TRY(launch_ens_init(st, d_init, sm));
+    if (int r = rows.eval(c, st.b, (int64_t)M, llk)) return r;
+    HIP_TRY(launch_ens_accept(st, 0, -1, llk, sm));
+    for (int64_t step = 1; step <= q.n_step; ++step) {
+        for (int half = 0; half < 2; ++half) {
+            HIP_TRY(launch_ens_propose(st, step, half, sm));
+            if (int r = rows.eval(c, st.b, (int64_t)(S * H), llk)) return r;
+            HIP_TRY(launch_ens_accept(st, step, half, llk, sm));
+        }
+        if (q.swap_every >= 1 && step % q.swap_every == 0) {
+            const int first = (int)((step / q.swap_every - 1) & 1);
+            if (first + 1 < q.n_rung) HIP_TRY(launch_pt_swap(st, pt, step, first, sm));
+        }
+    }
+    c->nm_iterations = 2 * (int64_t)q.n_step;
+    c->nm_slots = 2 * (int64_t)q.n_step * (int64_t)(S * H);
+    HIP_TRY(launch_ens_result(st, sm));
+    HIP_TRY(launch_pt_reduce(st, K ? q.burn : 0, d_rung, d_logz, sm));
+    if (post) {
+        pa.chain = st.chain; pa.chain_llh = st.chain_llh; pa.llh_K = (int64_t)(L * K);     // rung 0 of fit s: the first K rows of its L K
+        HIP_TRY(launch_post(pa, sm));
+        if (int r = post_back(pa, *post, F, N, sm)) return r;
+    }
+    HIP_TRY(hipMemcpyAsync(q.last, st.x, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(q.last_llh, st.llh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(q.rung_llh, d_rung, S * sizeof(double), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(q.logz, d_logz, F * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.accepted) HIP_TRY(hipMemcpyAsync(q.accepted, st.accepted, M * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.swap_proposed && P) HIP_TRY(hipMemcpyAsync(q.swap_proposed, pt.swap_proposed, P * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.swap_accepted && P) HIP_TRY(hipMemcpyAsync(q.swap_accepted, pt.swap_accepted, P * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
+    if (q.chain && K) HIP_TRY(hipMemcpyAsync(q.chain, st.chain, F * K * W * N * sizeof(double), hipMemcpyDeviceToHost, sm));
+    if (q.chain_llh && K) HIP_TRY(hipMemcpyAsync(q.chain_llh, st.chain_llh, S * K * W * sizeof(double), hipMemcpyDeviceToHost, sm));
+    std::vector<int64_t> per_search;
+    if (q.n_points) {
+        per_search.resize(S);
+        HIP_TRY(hipMemcpyAsync(per_search.data(), d_points, S * sizeof(int64_t), hipMemcpyDeviceToHost, sm));
+    }
+    HIP_TRY(hipStreamSynchronize(sm));
+    if (q.n_points) {
+        int64_t n = 0;
+        for (int64_t v : per_search) n += v;
+        *q.n_points = n;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int misti_tempered_sample(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p) {
+    if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
+    if (q->size != sizeof(misti_pt_t))
+        return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_pt_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_pt_t));
+    if (p && p->size != sizeof(misti_ens_post_t))
+        return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
+    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
+        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
+    int N = 0;
+    bool whole = false;
+    if (int r = pt_check(c, *q, N, whole)) return r;
+    if (p) if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
+    if (q->n_start == 0) return 0;
+    return pt_run(c, *q, N, whole, p);
+}
 
 int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) {
     if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");

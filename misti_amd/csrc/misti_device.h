@@ -291,13 +291,19 @@ hipError_t launch_de_result(const DeState& st, double* x, double* llh, int32_t* 
 // owns, in HBM.  A half-step of every search is ONE engine batch of H = W / 2 points per search; batch slot s * H + m carries the
 // proposal of walker half * H + m of search s (the initial ensemble: slot s * W + i, walker i).  No search ever stops, so slots are
 // never compacted.  What a search hands its points is a PointSource, and the batch is an NmBatch.
+//
+// The tempered sampler (misti_pt.hip) runs the L rungs of its fits through the same kernels as S = fits x L searches: search s is rung
+// s % L of fit s / L.  Row, split, bounds, pulse times, box and stream id are the FIT's (src is indexed by s / L), the temperature is
+// the rung's (temp[(fit or 0) L + l]), the step handed to ens_draw is step L + l, and the chain keeps the coordinates of rung 0 only
+// ([fits][n_keep][W][N]) beside the values of every rung ([S][n_keep][W]).  L = 1 is misti_ensemble_sample.
 struct EnsState {
     int64_t S;              // searches
+    int L = 1;              // rungs per fit: S is a multiple of it
     int N, W;               // coordinates, walkers (even)
     int thin;               // the ensemble after steps thin, 2 thin, ... is kept
     double a, am1;          // the stretch's scale and a - 1 as rounded once
     uint64_t seed;
-    const double* temp;     // [1], or [S] with temp_per_start
+    const double* temp;     // [L], or [S / L][L] with temp_per_start
     int temp_per_start;
     PointSource src;        // what a search hands its points; always with rows and a finite box
     double* x;              // [S][W][N] the ensemble
@@ -307,7 +313,7 @@ struct EnsState {
     int32_t* accepted;      // [S][W]    proposals accepted, per walker: plain stores by the walker's own thread
     int32_t* submitted;     // [S][W]    proposals of the walker handed to the engine (those rejected in advance are not)
     NmBatch b;              // [S * W] slots
-    double* chain;          // [S][n_keep][W][N] or NULL
+    double* chain;          // [S / L][n_keep][W][N] or NULL: rung 0 of every fit
     double* chain_llh;      // [S][n_keep][W] or NULL
     int64_t n_keep;
     long long* points;      // [S] the sum of `submitted` over the walkers of a search (ens_result_kernel); the host adds the searches
@@ -319,6 +325,18 @@ hipError_t launch_ens_propose(const EnsState& st, int64_t step, int half, hipStr
 // ensemble's row of the chain
 hipError_t launch_ens_accept(const EnsState& st, int64_t step, int half, const double* llk, hipStream_t stream);
 hipError_t launch_ens_result(const EnsState& st, hipStream_t stream);
+
+// Tempered ensemble sampler (misti_pt.hip; the rule is optimize.tempered_rule, operation for operation): what the swap rounds and the
+// reduction add to an EnsState with L rungs.
+struct PtState {
+    int32_t* swap_proposed; // [fits][L - 1] pairs in which both walkers had a value
+    int32_t* swap_accepted; // [fits][L - 1] pairs that traded places
+};
+// the swap round behind half 1 of step `step`: pairs (l, l + 1) for l = first, first + 2, ... < L - 1; the caller launches it only where
+// there is such a pair
+hipError_t launch_pt_swap(const EnsState& st, const PtState& pt, int64_t step, int first, hipStream_t stream);
+// rung_llh[fits][L] and logz[fits] from st.chain_llh over the kept steps burn ... n_keep - 1
+hipError_t launch_pt_reduce(const EnsState& st, int64_t burn, double* rung_llh, double* logz, hipStream_t stream);
 
 // Replicate epilogue fused into the spectrum kernel up to this many replicates (one launch less per batch).
 constexpr int LLK_INLINE_MAX = 8;

@@ -45,11 +45,11 @@ void ens_init_kernel(EnsState st, const double* __restrict__ init) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int W = st.W, N = st.N;
     if (t >= st.S * W) return;
-    const int64_t s = t / W;
+    const int64_t fit = t / W / st.L;
     double* pt = st.b.pts + t * N;
     double* x = st.x + t * N;
     for (int k = 0; k < N; ++k) { const double v = init[t * N + k]; pt[k] = v; x[k] = v; }
-    put_point(st.src, st.b, t, s, pt);
+    put_point(st.src, st.b, t, fit, pt);
 }
 
 // Half `half` of step `step`: walker i = half H + m moves against walker j of the other half.  Thread = (search, m).
@@ -58,14 +58,14 @@ void ens_propose_kernel(EnsState st, int64_t step, int half) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int W = st.W, N = st.N, H = W / 2;
     if (t >= st.S * H) return;
-    const int64_t s = t / H;
+    const int64_t s = t / H, fit = s / st.L;               // search s is rung s % L of fit s / L (misti_device.h)
     const int i = half * H + (int)(t - s * H);
-    const EnsDraw dr = ens_draw(st.seed, id_of(st.src, s), step, i, W);
+    const EnsDraw dr = ens_draw(st.seed, id_of(st.src, fit), step * st.L + (s - fit * st.L), i, W);
     const int j = (1 - half) * H + dr.partner;
     const double* xi = st.x + (s * W + i) * (int64_t)N;
     const double* xj = st.x + (s * W + j) * (int64_t)N;
     const double z = ens_stretch(st.a, st.am1, dr.u_z);
-    const int64_t o = box_of(st.src, s);
+    const int64_t o = box_of(st.src, fit);
     double* pt = st.b.pts + t * N;
     bool inside = true;
     for (int k = 0; k < N; ++k) {
@@ -75,13 +75,13 @@ void ens_propose_kernel(EnsState st, int64_t step, int half) {
         pt[k] = y;
     }
     st.u_acc[t] = dr.u_acc;
-    if (inside) { st.z[t] = z; put_point(st.src, st.b, t, s, pt); }
+    if (inside) { st.z[t] = z; put_point(st.src, st.b, t, fit, pt); }
     else { st.z[t] = -1.0; put_none(st.src, st.b, t, pt); }
 }
 
 // The values of the batch are in.  half < 0: the initial ensemble's, thread = (search, walker).  Otherwise thread = (search, m): the
 // decision on walker i = half H + m; behind half 1 of a kept step the thread writes walkers m and H + m of the ensemble's chain row
-// (walker m was settled by the launch of half 0).
+// (walker m was settled by the launch of half 0): the values of every search, the coordinates of rung 0 of a fit.
 __global__ __launch_bounds__(ENS_THREADS)
 void ens_accept_kernel(EnsState st, int64_t step, int half, const double* __restrict__ llk) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -94,15 +94,15 @@ void ens_accept_kernel(EnsState st, int64_t step, int half, const double* __rest
         return;
     }
     if (t >= st.S * H) return;
-    const int64_t s = t / H;
-    const int m = (int)(t - s * H), i = half * H + m;
+    const int64_t s = t / H, fit = s / st.L;
+    const int m = (int)(t - s * H), i = half * H + m, l = (int)(s - fit * st.L);
     const int64_t wi = s * W + i;
     const double z = st.z[t];
     if (z > 0.0) {                                          // the proposal was evaluated
-        const int64_t o = box_of(st.src, s);
+        const int64_t o = box_of(st.src, fit);
         int d = -1;
         for (int k = 0; k < N; ++k) d += st.src.box_lo[o + k] != st.src.box_hi[o + k] ? 1 : 0;
-        const double T = st.temp[st.temp_per_start ? s : 0];
+        const double T = st.temp[(st.temp_per_start ? fit : 0) * st.L + l];
         const double v = ens_value(llk[t]);
         st.submitted[wi] = st.submitted[wi] + 1;
         if (ens_decide(z, d, st.llh[wi], v, T, st.u_acc[t])) {
@@ -114,12 +114,12 @@ void ens_accept_kernel(EnsState st, int64_t step, int half, const double* __rest
         }
     }
     if (half == 1 && st.chain_llh && step % st.thin == 0) {
-        const int64_t row = s * st.n_keep + (step / st.thin - 1);
+        const int64_t at = step / st.thin - 1, row = s * st.n_keep + at, xrow = fit * st.n_keep + at;
         for (int h = 0; h < 2; ++h) {
             const int w = h * H + m;
-            const int64_t src = s * W + w, dst = row * W + w;
-            st.chain_llh[dst] = st.llh[src];
-            if (st.chain) for (int k = 0; k < N; ++k) st.chain[dst * N + k] = st.x[src * N + k];
+            const int64_t src = s * W + w;
+            st.chain_llh[row * W + w] = st.llh[src];
+            if (st.chain && l == 0) for (int k = 0; k < N; ++k) st.chain[(xrow * W + w) * N + k] = st.x[src * N + k];
         }
     }
 }

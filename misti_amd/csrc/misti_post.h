@@ -14,6 +14,16 @@ namespace misti {
 constexpr int POST_MAX_RANKS = 2 * MISTI_POST_MAX_PROBS;   // a probability needs x_(i) and x_(i+1)
 constexpr int POST_LANES = 64;                             // lsum's partials: one per lane of a wave
 
+// lsum's fold (misti_post.hip's sums over steps, misti_pt.hip's reduction): a partial is a lane of a wave; every lane ends with partial[0]
+__device__ __forceinline__ double post_fold(double v) {
+#pragma unroll
+    for (int stride = POST_LANES / 2; stride >= 1; stride >>= 1) v = v + __shfl_down(v, stride, POST_LANES);
+    return __shfl(v, 0, POST_LANES);
+}
+
+// what is stored of a result: IEEE leaves the sign and the payload of a NaN to the implementation, the rule does not - the canonical quiet NaN
+__device__ __forceinline__ double post_out(double v) { return v != v ? __longlong_as_double(0x7ff8000000000000ll) : v; }
+
 // The total order of the rule: the 64-bit key of a double's bits.  A set sign bit flips all bits, a clear one only the sign bit:
 // -0.0 before +0.0, NaNs of a clear sign bit last.
 __host__ __device__ __forceinline__ uint64_t post_key(uint64_t bits) { return (bits >> 63) ? ~bits : bits ^ 0x8000000000000000ull; }
@@ -66,6 +76,8 @@ inline PostSelect post_select(int64_t m, int n_prob, const double* probs) {
 // centred ensemble-mean series (1 / W of the kept chain).
 struct PostArgs {
     int64_t S, K, burn, n, L;
+    int64_t llh_K;                   // rows of chain_llh from one search to the next: K, or (the tempered sampler keeps the values of
+                                     // every rung, [S][rungs][K][W], and summarises rung 0) rungs x K
     int32_t W, N;
     double c;
     const double* chain;

@@ -30,16 +30,6 @@ namespace {
 constexpr int POST_THREADS = 256;
 constexpr int POST_WAVES = POST_THREADS / POST_LANES;
 
-// lsum's fold: lane 0 ends with partial[0]
-__device__ __forceinline__ double post_fold(double v) {
-#pragma unroll
-    for (int stride = POST_LANES / 2; stride >= 1; stride >>= 1) v = v + __shfl_down(v, stride, POST_LANES);
-    return __shfl(v, 0, POST_LANES);
-}
-
-// what is stored of a result: IEEE leaves the sign and the payload of a NaN to the implementation, the rule does not - the canonical quiet NaN
-__device__ __forceinline__ double post_out(double v) { return v != v ? __longlong_as_double(0x7ff8000000000000ll) : v; }
-
 __device__ __forceinline__ const double* kept(const PostArgs& a, int64_t s) { return a.chain + (s * a.K + a.burn) * a.W * (int64_t)a.N; }
 
 }  // namespace
@@ -213,7 +203,7 @@ void post_best_kernel(PostArgs a) {
     double bv = -INFINITY;
     int64_t bi = -1;
     if (a.chain_llh) {
-        const double* v = a.chain_llh + (s * a.K + a.burn) * a.W;
+        const double* v = a.chain_llh + (s * a.llh_K + a.burn) * a.W;
         for (int64_t idx = tid; idx < m; idx += POST_THREADS) {
             const double f = v[idx];
             if (f == f && f != -INFINITY && (bi < 0 || f > bv)) { bv = f; bi = idx; }

@@ -777,6 +777,59 @@ class Engine:
         return self._ensemble("ensemble_posterior", dict(burn=burn, probs=probs, max_lag=max_lag, c=c), bool(keep_chain), init, rows, table, box,
                               split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature, a, seed, ids)
 
+    def tempered_sample(self, init, rows, table, box, ladder, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
+                        thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None, post=None):
+        """``misti_tempered_sample``: parallel tempering over ``ensemble_sample`` - fit s is a ladder of L ensembles ``init[s]``
+        (``[S][L][W][N]``) at the temperatures ``ladder`` (``[L]`` or ``[S][L]``, strictly increasing); rung l samples ``llk / T_l``,
+        neighbouring rungs trade walkers every ``swap_every`` steps (0: never), the cold rung carries the posterior, and all rungs of all
+        fits move in the same engine batch.  The rule is ``optimize.tempered_rule``, bit for bit; L = 1 is ``ensemble_sample``.  The other
+        arguments as in ``ensemble_sample``; ``burn``: kept steps dropped before ``rung_llh`` / ``logz``.  ``post``: None, or a dict of
+        ``burn`` (default: this call's), ``probs``, ``max_lag``, ``c`` and ``keep_chain`` (default False) - the summaries of
+        ``ensemble_posterior`` reduced on the device from the cold chain, which then comes back only with ``keep_chain``.
+        Returns dict(chain[S][K][W][N] (the cold rung), chain_llh[S][L][K][W], accepted[S][L][W], swap_proposed[S][L-1],
+        swap_accepted[S][L-1], last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S] (see ``optimize.tempered_rule`` for what it
+        is and is not), n_points), plus the summaries with ``post``."""
+        if (split_times is None) != bool(fit_split):
+            raise ValueError("tempered_sample: give exactly one of split_times and fit_split=True")
+        N = self.n_param + (1 if fit_split else 0)
+        x0 = _f64(init)
+        if x0.ndim != 4 or x0.shape[3] != N:
+            raise ValueError("tempered_sample: init must be [S][L][W][%d] (got %s)" % (N, x0.shape))
+        S, L, W = x0.shape[:3]
+        T = _f64(ladder)
+        if T.shape not in ((L,), (S, L)):
+            raise ValueError("tempered_sample: the ladder must be [%d] or [%d][%d] (got %s)" % (L, S, L, T.shape))
+        n_step, thin = int(n_step), int(thin)
+        ptr = lambda v: v.ctypes.data if v is not None else None
+        arrays, fields = self._rows_problem(S, N, _f64(table, (-1, 8)), split_times, rows, band_bounds, pulse_times, box, ids)
+        K = n_step // thin if thin >= 1 and n_step >= 0 else 0
+        opts = dict(post) if post is not None else None
+        keep_chain = opts is None or bool(opts.pop("keep_chain", False))
+        out = dict(chain=np.empty((S, K, W, N)) if keep_chain else None, chain_llh=np.empty((S, L, K, W)), accepted=np.zeros((S, L, W), dtype=np.int32),
+                   swap_proposed=np.zeros((S, max(L - 1, 0)), dtype=np.int32), swap_accepted=np.zeros((S, max(L - 1, 0)), dtype=np.int32),
+                   last=np.empty((S, L, W, N)), last_llh=np.empty((S, L, W)), rung_llh=np.empty((S, L)), logz=np.empty(S))
+        n_points = np.zeros(1, dtype=np.int64)
+        q = _lib.PtSample(size=C.sizeof(_lib.PtSample), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, init=ptr(x0), walkers=W,
+                          n_rung=L, n_ladder=1 if T.ndim == 1 else S, n_step=n_step, ladder=ptr(T), thin=thin, swap_every=int(swap_every), burn=int(burn),
+                          a=float(a), seed=int(seed), n_points=ptr(n_points), **{k: ptr(v) for k, v in out.items()}, **fields)
+        p = None
+        if opts is not None:
+            probs = _f64(opts.get("probs", (0.025, 0.5, 0.975))).reshape(-1)
+            P = probs.size
+            pburn = int(opts.get("burn", burn))
+            max_lag = max(K - pburn - 1, 0) if opts.get("max_lag") is None else int(opts["max_lag"])
+            s = dict(mean=np.empty((S, N)), cov=np.empty((S, N, N)), quant=np.empty((S, N, P)), tau=np.empty((S, N)),
+                     window=np.empty((S, N), dtype=np.int32), best_llh=np.empty(S), best_x=np.empty((S, N)), best_at=np.empty((S, 2), dtype=np.int32))
+            p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=pburn, n_prob=P, probs=ptr(probs), max_lag=min(max_lag, 2 ** 31 - 1), c=float(opts.get("c", 5.0)),
+                             **{k: ptr(v) for k, v in s.items()})
+        _lib.check(self._lib.misti_tempered_sample(self._ctx, C.byref(q), C.byref(p) if p is not None else None))
+        if not keep_chain:
+            del out["chain"]
+        if p is not None:
+            out.update(s)
+        out["n_points"] = int(n_points[0])
+        return out
+
     def ensemble_summary_dev(self, chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0, want=None):
         """``misti_ens_summary_dev``: the posterior summaries of a chain that is already on the device - ``chain`` a contiguous float64
         torch tensor ``[S][K][W][N]`` on this engine's device, ``chain_llh`` ``[S][K][W]`` or None (no best sample).  Asynchronous on

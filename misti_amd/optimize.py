@@ -1841,48 +1841,252 @@ def posterior_table(result, n_step, walkers=None):
                 short=(n < 50.0 * tau) | (np.asarray(result["window"]) == -1), corr=corr)
 
 
-def _mcmc_call(engine, summary, n_step, thin):
+# ------------------------------------------------------------------------------------------- tempered ensemble MCMC ----
+# The rule of misti_tempered_sample stated on the host (include/misti_hip.h, "tempered ensemble MCMC"): the device result is this, bit
+# for bit, on the engine's own objective.  Replica exchange over the ensemble sampler: a ladder of ensembles per fit, neighbouring rungs
+# trading walkers, the cold rung carrying the posterior.
+PT_MAX_RUNGS = 64
+
+
+def temperature_ladder(T0, Tmax_ratio, L):
+    """A geometric ladder of L temperatures from ``T0`` to ``T0 Tmax_ratio``: ``T_l = T0 ratio^(l / (L - 1))``, and ``T0`` alone for
+    L = 1 (the ratio is not looked at).  Host only."""
+    T0, ratio, L = float(T0), float(Tmax_ratio), int(L)
+    if not 1 <= L <= PT_MAX_RUNGS or not (np.isfinite(T0) and T0 > 0):
+        raise ValueError("temperature_ladder: 1 ... %d rungs, T0 finite and positive" % PT_MAX_RUNGS)
+    if L == 1:
+        return np.array([T0])
+    if not (np.isfinite(ratio) and ratio > 1.0):
+        raise ValueError("temperature_ladder: the ratio must be finite and > 1")
+    return T0 * ratio ** (np.arange(L) / float(L - 1))
+
+
+def pt_swap_decision(T_lo, T_hi, llk_lo, llk_hi, u):
+    """The decision on a pair of walkers of neighbouring rungs (``misti_pt_swap``), elementwise: no swap where either walker has no
+    value (not finite); otherwise ``db = 1.0 / T_lo - 1.0 / T_hi``, ``e = db (llk_hi - llk_lo)``, swapped iff ``u < ens_exp(e)`` -
+    every operation rounded on its own."""
+    T_lo, T_hi, lo, hi, u = np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (T_lo, T_hi, llk_lo, llk_hi, u)))
+    with np.errstate(all="ignore"):
+        db = 1.0 / T_lo - 1.0 / T_hi
+        take = u < ens_exp(db * (hi - lo))
+    return np.isfinite(lo) & np.isfinite(hi) & take
+
+
+def tempered_reduction(chain_llh, ladder, burn=0):
+    """The thermodynamic-integration part of ``tempered_rule`` on ``chain_llh[S][L][K][W]`` (or one fit ``[L][K][W]``) with ``ladder``
+    ``[L]`` or ``[S][L]``: over the kept steps ``burn ... K - 1`` (n of them) ``e_t = (llh[t][0] + ... + llh[t][W - 1] in walker order)
+    / W``, ``rung_llh[l] = lsum(e) / n``; ``beta_l = 1.0 / T_l``; ``logz`` the sum for l = 0 ... L - 2 in increasing l, from +0.0, of
+    ``(0.5 (E_l + E_{l+1})) (beta_l - beta_{l+1})``, every operation rounded on its own (L = 1: +0.0).  K = 0 leaves no step: every
+    ``rung_llh`` is NaN.  A NaN is the canonical quiet NaN.  Returns (rung_llh, logz)."""
+    v = np.asarray(chain_llh, dtype=np.float64)
+    one = v.ndim == 3
+    if one:
+        v = v[None]
+    S, L, K, W = v.shape
+    T = np.ascontiguousarray(np.broadcast_to(np.asarray(ladder, dtype=np.float64), (S, L)))
+    burn = int(burn)
+    if K and not 0 <= burn < K:
+        raise ValueError("tempered_reduction: burn must be 0 ... K - 1 (K = %d)" % K)
+    n = K - burn
+    with np.errstate(all="ignore"):
+        if K:
+            k = np.moveaxis(v[:, :, burn:], 2, 0)                            # [n][S][L][W]
+            e = k[..., 0].copy()
+            for w in range(1, W):
+                e = e + k[..., w]
+            E = lsum(e / float(W)) / float(n)
+        else:
+            E = np.full((S, L), np.nan)
+        beta = 1.0 / T
+        logz = np.zeros(S)
+        for l in range(L - 1):
+            logz = logz + (0.5 * (E[:, l] + E[:, l + 1])) * (beta[:, l] - beta[:, l + 1])
+    E = E.copy()
+    E[np.isnan(E)] = np.nan
+    logz[np.isnan(logz)] = np.nan
+    return (E[0], float(logz[0])) if one else (E, logz)
+
+
+def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None):
+    """The rule of ``misti_tempered_sample``, operation for operation: parallel tempering (replica exchange) over ``ensemble_rule``.
+    Fit s has L rungs (1 ... ``PT_MAX_RUNGS``) at the temperatures ``ladder[s][0] < ladder[s][1] < ...`` (finite, positive; ``ladder``
+    is ``[L]`` or ``[S][L]``); rung l is an ensemble of W walkers ``init[s][l][W][N]`` inside the fit's box whose target is
+    ``llk / T_l``.  ``fun_batch``, ``lo`` / ``hi``, ``a``, ``seed`` and ``ids`` as in ``ensemble_rule`` (``s`` handed to ``fun_batch``
+    is the FIT).
+
+    A rung moves exactly as a search of ``ensemble_rule`` moves - the halves, the stretch, rejection in advance outside the box,
+    ``ens_decision`` with ``d = N_free - 1`` and ``T = T_l`` - except that walker i of rung l of step t owns block ``(t L + l) W + i``
+    of ``Philox(key=[seed, ids[s]])``: with L = 1 this IS ``ensemble_rule``.  The initial evaluation of all rungs of all fits is ONE
+    batch, and so is a half-step of all rungs of all fits.
+
+    Swaps: behind half 1 of step t with ``swap_every >= 1`` and ``t % swap_every == 0``, round ``n = t / swap_every`` treats the pairs
+    (l, l + 1) for l = p, p + 2, ... < L - 1 with ``p = (n - 1) & 1``.  Walker i of rung l faces walker i of rung l + 1; its uniform
+    is the fourth word of the lower rung's own block ``(t L + l) W + i``, ``(w[3] >> 11) 2^-53``.  ``pt_swap_decision`` decides; the
+    walkers trade coordinates and values.  A pair in which either walker has no value is neither proposed nor counted.
+    ``swap_every = 0``: no swaps.
+
+    Kept: step t with ``t % thin == 0`` leaves row ``t / thin - 1`` (K = n_step // thin rows), the state AFTER the step's swap round:
+    the coordinates of the cold rung only, the values of every rung.  ``rung_llh`` and ``logz`` are ``tempered_reduction`` of
+    ``chain_llh`` over the kept steps ``burn ... K - 1``: ``logz[s]`` is the thermodynamic-integration estimate, by the trapezoid rule
+    on the ladder's own points, of ``log Z(beta_0) - log Z(beta_{L-1})`` with ``Z(beta) = integral of exp(beta llk)`` against the
+    NORMALISED uniform prior on the box.  The piece below ``beta_{L-1}`` (down to the prior, beta = 0) is NOT included.
+    Returns dict(chain[S][K][W][N], chain_llh[S][L][K][W], accepted[S][L][W] int32 (stretch moves), swap_proposed[S][L-1] and
+    swap_accepted[S][L-1] int32, last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S], n_points: the PROPOSALS handed to
+    ``fun_batch``)."""
+    x = np.array(init, dtype=np.float64)
+    if x.ndim != 4:
+        raise ValueError("tempered_rule: init must be [S][L][W][N]")
+    S, L, W, N = x.shape
+    H = W // 2
+    n_step, thin, swap_every, burn, a = int(n_step), int(thin), int(swap_every), int(burn), float(a)
+    if not 1 <= L <= PT_MAX_RUNGS:
+        raise ValueError("tempered_rule: 1 ... %d rungs" % PT_MAX_RUNGS)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=float), (S, N)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=float), (S, N)))
+    T = np.ascontiguousarray(np.broadcast_to(np.asarray(ladder, dtype=float), (S, L)))
+    if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or n_step < 0 or thin < 1 or not (np.isfinite(a) and a > 1.0):
+        raise ValueError("tempered_rule: W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
+    if not (np.isfinite(T) & (T > 0)).all() or not (T[:, 1:] > T[:, :-1]).all():
+        raise ValueError("tempered_rule: a ladder must be finite, positive and strictly increasing")
+    K = n_step // thin
+    if swap_every < 0 or (K and not 0 <= burn < K):
+        raise ValueError("tempered_rule: swap_every >= 0, burn 0 ... K - 1")
+    with np.errstate(over="ignore", invalid="ignore"):
+        usable = np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(hi - lo).all()
+    if not usable:
+        raise ValueError("tempered_rule: the box must be finite with lo <= hi")
+    fixed = lo == hi
+    if S and fixed.all(axis=1).any():
+        raise ValueError("tempered_rule: every coordinate of a box is fixed")
+    if not (np.isfinite(x).all() and (x >= lo[:, None, None, :]).all() and (x <= hi[:, None, None, :]).all()):
+        raise ValueError("tempered_rule: every walker of init must be finite and inside its box")
+    ids = np.arange(S) if ids is None else np.asarray(ids).reshape(S)
+    am1 = a - 1.0
+    # the S L rungs as searches: everything but the temperature and the block is the fit's
+    G = S * L
+    x = x.reshape(G, W, N)
+    fit = np.repeat(np.arange(S), L)
+    glo, ghi, gfixed, gT = lo[fit], hi[fit], fixed[fit], T.reshape(G)
+    d = (~gfixed).sum(axis=1) - 1
+
+    def values(X, s_of):
+        f = np.asarray(fun_batch(X, s_of), dtype=float).reshape(-1)
+        llk = -np.where(np.isnan(f), np.inf, f)
+        return np.where(np.isfinite(llk), llk, -np.inf)
+
+    llh = values(x.reshape(-1, N).copy(), np.repeat(fit, W)).reshape(G, W) if G else np.empty((0, W))
+    n_points = 0
+    chain, chain_llh = np.empty((S, K, W, N)), np.empty((S, L, K, W))
+    accepted = np.zeros((G, W), dtype=np.int32)
+    proposed, swapped = np.zeros((S, max(L - 1, 0)), dtype=np.int32), np.zeros((S, max(L - 1, 0)), dtype=np.int32)
+    CHUNK = max(512 // L, 1)
+    raw = None
+    gidx, fidx = np.arange(G)[:, None], fit[:, None]
+    for t in range(1, n_step + 1):
+        if (t - 1) % CHUNK == 0:                                          # steps t ...: blocks t L W ... of every fit's stream
+            n = min(CHUNK, n_step - t + 1)
+            raw = (np.stack([_ens_raw(seed, ids[s], t * L, n * L, W).reshape(n, L, W, 4) for s in range(S)]) if S
+                   else np.empty((0, 1, L, W, 4), dtype=np.uint64))
+        w = raw[:, (t - 1) % CHUNK].reshape(G, W, 4)
+        for half in (0, 1):
+            mine = slice(half * H, half * H + H)
+            j = (1 - half) * H + _mulhi_index(w[:, mine, 0], H)            # [G][H]
+            u_z, u_acc = _ens_uniform(w[:, mine, 1]), _ens_uniform(w[:, mine, 2])
+            sz = am1 * u_z + 1.0
+            z = (sz * sz) / a
+            xi, xj = x[:, mine], x[gidx, j]
+            with np.errstate(all="ignore"):
+                y = xj + z[:, :, None] * (xi - xj)
+            y = np.where(gfixed[:, None, :], glo[:, None, :], y)
+            inside = ((y >= glo[:, None, :]) & (y <= ghi[:, None, :])).all(axis=2)
+            new = np.full((G, H), -np.inf)
+            if inside.any():
+                new[inside] = values(y[inside], np.broadcast_to(fidx, (G, H))[inside])
+                n_points += int(inside.sum())
+            take = inside & ens_decision(z, d[:, None], llh[:, mine], new, gT[:, None], u_acc)
+            x[:, mine] = np.where(take[:, :, None], y, xi)
+            llh[:, mine] = np.where(take, new, llh[:, mine])
+            accepted[:, mine] += take
+        if swap_every >= 1 and t % swap_every == 0:
+            xs, ls, us = x.reshape(S, L, W, N), llh.reshape(S, L, W), _ens_uniform(w[:, :, 3]).reshape(S, L, W)
+            for l in range((t // swap_every - 1) & 1, L - 1, 2):
+                both = np.isfinite(ls[:, l]) & np.isfinite(ls[:, l + 1])
+                take = pt_swap_decision(T[:, l, None], T[:, l + 1, None], ls[:, l], ls[:, l + 1], us[:, l])     # [S][W]
+                proposed[:, l] += both.sum(axis=1).astype(np.int32)
+                swapped[:, l] += take.sum(axis=1).astype(np.int32)
+                a_, b_ = xs[:, l].copy(), ls[:, l].copy()
+                xs[:, l] = np.where(take[:, :, None], xs[:, l + 1], a_)
+                xs[:, l + 1] = np.where(take[:, :, None], a_, xs[:, l + 1])
+                ls[:, l] = np.where(take, ls[:, l + 1], b_)
+                ls[:, l + 1] = np.where(take, b_, ls[:, l + 1])
+        if t % thin == 0:
+            chain[:, t // thin - 1] = x.reshape(S, L, W, N)[:, 0]
+            chain_llh[:, :, t // thin - 1] = llh.reshape(S, L, W)
+    rung_llh, logz = tempered_reduction(chain_llh, T, burn) if S else (np.empty((0, L)), np.empty(0))
+    return dict(chain=chain, chain_llh=chain_llh, accepted=accepted.reshape(S, L, W), swap_proposed=proposed, swap_accepted=swapped,
+                last=x.reshape(S, L, W, N), last_llh=llh.reshape(S, L, W), rung_llh=rung_llh, logz=logz, n_points=int(n_points))
+
+
+def _mcmc_call(engine, summary, n_step, thin, ladder=None, swap_every=1):
     """``Engine.ensemble_sample``, or with ``summary`` (a dict of ``burn``, ``probs``, ``max_lag``, ``keep_chain``, ``c``; ``burn``
-    defaults to half the kept steps) ``Engine.ensemble_posterior``."""
+    defaults to half the kept steps) ``Engine.ensemble_posterior``.  With ``ladder`` (``[L]`` or per ensemble ``[S][L]``):
+    ``Engine.tempered_sample`` on it - every rung starts from the ensemble's ``init``, ``temperature`` is not looked at (the ladder's
+    first entry is the cold rung's), ``rung_llh`` / ``logz`` drop the summary's ``burn`` (without a summary: half the kept steps)."""
+    half = (int(n_step) // int(thin)) // 2
+    if ladder is not None:
+        L = np.asarray(ladder).shape[-1]
+        opts = None if summary is None else dict(summary)
+
+        def tempered(x0, *a, temperature=None, **kw):
+            x0 = np.asarray(x0, dtype=float)
+            return engine.tempered_sample(np.ascontiguousarray(np.broadcast_to(x0[:, None], (x0.shape[0], L) + x0.shape[1:])), *a, ladder=ladder,
+                                          swap_every=swap_every, burn=half if opts is None else opts.setdefault("burn", half), post=opts, **kw)
+        return tempered
     if summary is None:
         return engine.ensemble_sample
     opts = dict(summary)
-    opts.setdefault("burn", (int(n_step) // int(thin)) // 2)
+    opts.setdefault("burn", half)
     return lambda *a, **kw: engine.ensemble_posterior(*a, **kw, **opts)
 
 
-def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None):
+def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None,
+                           ladder=None, swap_every=1):
     """``bootstrap_profile_de``'s sampler: per (row, split) pair ONE ensemble inside ``box`` (``(lo, hi)``, each ``[n_param]``, finite), all
     R x P ensembles in ONE ``misti_ensemble_sample`` call - every half-step one dense engine batch.  ``init`` is ``[W][n_param]`` (every
     pair starts from it) or ``[R][P][W][n_param]``.  The stream id of an ensemble is its split's index: the rows of a bootstrap share
     their random numbers, and a row's result does not depend on the other rows.
     ``summary``: None, or a dict of ``Engine.ensemble_posterior``'s options (``burn`` - default half the kept steps -, ``probs``,
     ``max_lag``, ``keep_chain``, ``c``): the call goes through ``misti_ensemble_posterior`` and the chain stays on the device.
-    Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``) returns with the leading axis reshaped to ``[R][P]``."""
+    ``ladder`` (``[L]`` temperatures, strictly increasing, in place of ``temperature``) with ``swap_every``: every pair is a tempered
+    ladder of L ensembles started from ``init`` and the call goes through ``misti_tempered_sample`` (``Engine.tempered_sample``).
+    Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``, ``Engine.tempered_sample``) returns with the leading axis
+    reshaped to ``[R][P]``."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     splits = np.asarray(split_values, dtype=float).reshape(-1)
     R, Q = rows.shape[0], splits.size
     r_of, j_of = (v.ravel() for v in np.meshgrid(np.arange(R), np.arange(Q), indexing="ij"))
     x0 = np.asarray(init, dtype=float)
     x0 = np.broadcast_to(x0, (R, Q) + x0.shape[-2:]).reshape((R * Q,) + x0.shape[-2:])
-    out = _mcmc_call(engine, summary, n_step, thin)(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin,
+    out = _mcmc_call(engine, summary, n_step, thin, ladder, swap_every)(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin,
                                                     temperature=temperature, a=a, seed=seed, ids=j_of.astype(np.uint64))
     return {k: (v.reshape(R, Q, *v.shape[1:]) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
 
 
-def split_fit_mcmc(engine, jsfs_rows, init, box, band_bounds=None, pulse_times=None, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None):
+def split_fit_mcmc(engine, jsfs_rows, init, box, band_bounds=None, pulse_times=None, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None,
+                   ladder=None, swap_every=1):
     """``split_fit_de``'s sampler: per row ONE ensemble over (optimised parameters, split) inside ``box`` (``(lo, hi)``, each
     ``[n_param + 1]``, finite, the split last), all R ensembles in ONE ``misti_ensemble_sample`` call.  ``init`` is ``[W][n_param + 1]``
     (every row starts from it) or ``[R][W][n_param + 1]``; every row draws from stream 0 (the rows of a bootstrap share their random
     numbers - only the data differ).  ``band_bounds`` / ``pulse_times`` apply to every ensemble.
     ``summary``: None, or a dict of ``Engine.ensemble_posterior``'s options (``burn`` - default half the kept steps -, ``probs``,
     ``max_lag``, ``keep_chain``, ``c``): the call goes through ``misti_ensemble_posterior`` and the chain stays on the device.
-    Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``) returns (leading axis: the row)."""
+    ``ladder`` / ``swap_every`` as in ``bootstrap_profile_mcmc``: ``misti_tempered_sample``.
+    Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``, ``Engine.tempered_sample``) returns (leading axis: the row)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     R = rows.shape[0]
     x0 = np.asarray(init, dtype=float)
     x0 = np.ascontiguousarray(np.broadcast_to(x0, (R,) + x0.shape[-2:]))
     tile = lambda v, shape: None if v is None else np.repeat(np.asarray(v, dtype=np.int32).reshape(shape), R, axis=0)
-    return _mcmc_call(engine, summary, n_step, thin)(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
+    return _mcmc_call(engine, summary, n_step, thin, ladder, swap_every)(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
                                                      pulse_times=tile(pulse_times, (1, -1)), n_step=n_step, thin=thin, temperature=temperature,
                                                      a=a, seed=seed, ids=np.zeros(R, dtype=np.uint64))
