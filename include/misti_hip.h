@@ -929,6 +929,58 @@ int misti_tempered_sample(misti_ctx* ctx, const misti_pt_t* sampler, const misti
  * u outside [0, 1). */
 int misti_pt_swap(double T_lo, double T_hi, double llk_lo, double llk_hi, double u, int32_t* swap);
 
+/* ---- priors and log-scale coordinates ---------------------------------------------------------- */
+/* The samplers above know one prior: flat on the box, in the engine's own units.  A migration rate is a scale parameter that spans
+ * decades, and a split time often has outside information; a prior descriptor beside the sampler's states both per coordinate k:
+ *   - scale[k]: the SAMPLING COORDINATE y_k is the engine's value (MISTI_COORD_LINEAR) or its logarithm (MISTI_COORD_LOG);
+ *   - kind[k] with p0[k], p1[k]: the prior density ON THAT COORDINATE - MISTI_PRIOR_FLAT, MISTI_PRIOR_NORMAL (mean p0, sd p1) or
+ *     MISTI_PRIOR_EXPONENTIAL (scale p0, measured from the box's lower bound).  Flat on a log coordinate is the log-uniform prior,
+ *     normal on it the log-normal.
+ * The rule is optimize.ensemble_prior_rule / optimize.tempered_prior_rule, bit for bit.  Everything the caller sees is in the sampling
+ * coordinate: init, the box (finite, as before), the stretch, the test against the box, chain, last, and the summaries of `post`.
+ * Only the point handed to the engine changes: its coordinate k is y_k (LINEAR) or ens_exp(y_k) (LOG) - a fitted split (the last
+ * coordinate) and the initial ensemble alike, a fixed coordinate being lo, or ens_exp(lo), exactly.  The log prior of a walker, lp(y),
+ * is the sum, in increasing k from +0.0, over the coordinates that are neither fixed nor FLAT, of one term each, every operation rounded
+ * on its own (no fused multiply-add):
+ *     NORMAL:       u = (y - p0) / p1, term = -0.5 (u u)
+ *     EXPONENTIAL:  term = -((y - lo) / p0)
+ * The density is unnormalised.  The decision on an evaluated proposal is misti_ensemble_sample's (no value: rejected; an old walker
+ * without a value accepts; g = z^d) with e = (llk_new - llk_old) / T + (lp_new - lp_old), p = g ens_exp(e), accepted iff u_acc < p.
+ * The prior is NOT tempered: rung l of a ladder targets prior(y) exp(llk / T_l), so the prior cancels in a swap and the swap rule is
+ * misti_tempered_sample's.  The draws, the Philox blocks, the halves, the rejection in advance and the counters do not change.
+ * WHAT logz IS NOW: the same trapezoid rule for log Z(beta_0) - log Z(beta_{L-1}), with Z(beta) the integral of exp(beta llk) against
+ * the NORMALISED prior on the box, in sampling coordinates (the prior's constant is never needed: it cancels in the difference).
+ *
+ * prior == NULL makes the two entries misti_ensemble_sample (post == NULL) / misti_ensemble_posterior, and misti_tempered_sample; so
+ * does a prior whose every coordinate is LINEAR and FLAT: such a call takes the prior-less path, not the formula with a zero added.
+ * Errors: the sampler's own in their order (a wrong size of `prior` beside the other descriptors' sizes), with the prior's placed behind
+ * the box's - behind n_box: n_prior neither 1 nor n_start, a NULL array; behind the box itself (so behind the context): an unknown scale
+ * or kind, a NORMAL sd or an EXPONENTIAL scale that is not finite and positive, a NORMAL mean that is not finite, a LOG coordinate whose
+ * hi > 709 or lo < -745 (its natural value would leave the doubles).  Each of these messages names the search and the coordinate.  A
+ * refused call writes nothing. */
+#define MISTI_COORD_LINEAR 0
+#define MISTI_COORD_LOG 1
+#define MISTI_PRIOR_FLAT 0
+#define MISTI_PRIOR_NORMAL 1
+#define MISTI_PRIOR_EXPONENTIAL 2
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_prior_t) */
+    int32_t n_prior;                 /* 1: one prior for every search / fit; n_start: a prior per search / fit */
+    const int32_t* scale;            /* [n_prior][N] MISTI_COORD_* */
+    const int32_t* kind;             /* [n_prior][N] MISTI_PRIOR_* */
+    const double* p0;                /* [n_prior][N] NORMAL: the mean; EXPONENTIAL: the scale; unused entries are not looked at */
+    const double* p1;                /* [n_prior][N] NORMAL: the sd */
+} misti_prior_t;
+int misti_ensemble_sample_prior(misti_ctx* ctx, const misti_ens_t* sampler, const misti_ens_post_t* post /* or NULL */, const misti_prior_t* prior /* or NULL */);
+int misti_tempered_sample_prior(misti_ctx* ctx, const misti_pt_t* sampler, const misti_ens_post_t* post /* or NULL */, const misti_prior_t* prior /* or NULL */);
+/* The log prior of one walker y[N] in the box [lo, hi] (and, with `natural`, the point the engine is handed), and the decision with a
+ * prior, on the host through the very functions the kernels call.  No context, no device.  misti_ens_log_prior: MISTI_E_ARG for N
+ * outside 1 ... MISTI_MAX_PARAMS, a NULL pointer (natural may be NULL), and the per-coordinate refusals above (search 0).
+ * misti_ens_accept_prior: misti_ens_accept's refusals. */
+int misti_ens_log_prior(int32_t N, const int32_t* scale, const int32_t* kind, const double* p0, const double* p1, const double* lo, const double* hi,
+                        const double* y, double* lp, double* natural /* [N] or NULL */);
+int misti_ens_accept_prior(double z, int32_t d, double llk_old, double llk_new, double T, double lp_old, double lp_new, double u_acc, int32_t* accept);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

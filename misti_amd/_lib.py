@@ -109,6 +109,15 @@ class PtSample(C.Structure):
                 ("last", C.c_void_p), ("last_llh", C.c_void_p), ("rung_llh", C.c_void_p), ("logz", C.c_void_p), ("n_points", C.c_void_p)]
 
 
+COORD_LINEAR, COORD_LOG = 0, 1
+PRIOR_FLAT, PRIOR_NORMAL, PRIOR_EXPONENTIAL = 0, 1, 2
+
+
+class Prior(C.Structure):
+    """``misti_prior_t``: sampling coordinate and prior per coordinate; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("n_prior", C.c_int32), ("scale", C.c_void_p), ("kind", C.c_void_p), ("p0", C.c_void_p), ("p1", C.c_void_p)]
+
+
 POST_MAX_PROBS = 8
 
 
@@ -154,6 +163,10 @@ SYMBOLS = {
     "misti_ens_summary_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(EnsPost)]),
     "misti_ensemble_posterior": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost)]),
     "misti_tempered_sample": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost)]),
+    "misti_ensemble_sample_prior": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost), C.POINTER(Prior)]),
+    "misti_tempered_sample_prior": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost), C.POINTER(Prior)]),
+    "misti_ens_log_prior": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misti_ens_accept_prior": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "misti_pt_swap": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "misti_ens_draws": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_ens_exp": (C.c_int, [C.c_double, C.c_void_p]),

@@ -108,6 +108,13 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               statistics, interpolated), tau, n_eff = samples / tau, `(short)`, the coordinate's row of the correlation
                               matrix, and the best sample
     --mcmc-lag L              with --mcmc-post: the autocorrelation's lag cap (default: every lag)
+    --mcmc-log K [K ...]      with --mcmc: coordinate K (an index, or st - as --box names them) is SAMPLED ON THE LOG SCALE (misti_ensemble_sample_prior):
+                              the stretch, the box test and the chain are in ln(value), the engine is handed the value.  Its --box is given in
+                              natural units and needs LO > 0; flat on the log scale is the log-uniform prior.  The `mcmc:` / `post:` lines print
+                              quantiles and the best sample in natural units and the mean (sd) of the logarithm, and say so
+    --mcmc-prior K normal MEAN SD | K exponential SCALE
+                              with --mcmc: a prior on coordinate K's SAMPLING coordinate (repeatable) - on a --mcmc-log coordinate a normal is a
+                              log-normal; the exponential is measured from the box's lower bound.  Not tempered by --mcmc-temp / --mcmc-ladder
     --box K LO HI             with --grid-solve, --fit-st or --polish, with or without --hops; repeatable: every search runs inside a box -
                               SciPy's Nelder-Mead with bounds= (misti_nm_solve_box / misti_basinhopping_box): LO <= parameter K <= HI, K the
                               index of an optimised parameter as --grid-mi K names it, or `st` for the fitted split of --fit-st.  inf and
@@ -258,6 +265,9 @@ def build_parser():
     p.add_argument("--mcmc-swap", type=int, default=None, metavar="E", help="with --mcmc-ladder: a swap round every E steps (default 1; 0: never)")
     p.add_argument("--mcmc-post", nargs="*", type=float, default=None, metavar="P",
                    help="with --mcmc: posterior summaries reduced on the device, `post:` lines in place of `mcmc:` lines; P ...: the quantiles (default 0.025 0.5 0.975)")
+    p.add_argument("--mcmc-log", nargs="+", default=None, metavar="K", help="with --mcmc: coordinates (an index, or st) sampled on the log scale; their --box is in natural units, LO > 0")
+    p.add_argument("--mcmc-prior", nargs="+", action="append", default=None, metavar="K",
+                   help="with --mcmc: K normal MEAN SD | K exponential SCALE - a prior on coordinate K's sampling coordinate (repeatable)")
     p.add_argument("--mcmc-lag", type=int, default=None, metavar="L", help="with --mcmc-post: the autocorrelation's lag cap (default: every lag)")
     p.add_argument("--box", nargs=3, action="append", default=[], metavar=("K", "LO", "HI"),
                    help="with --grid-solve / --fit-st / --polish: keep optimised parameter K (or `st`: the fitted split of --fit-st) within [LO, HI] "
@@ -585,6 +595,8 @@ def mcmc_error(a):
             return "--mcmc-burn / --mcmc-thin / --mcmc-seed / --mcmc-spread / --mcmc-temp / --mcmc-out set the sampler of --mcmc W STEPS: give --mcmc W STEPS"
         if a.mcmc_ladder is not None or a.mcmc_swap is not None:
             return "--mcmc-ladder / --mcmc-swap temper the sampler of --mcmc W STEPS: give --mcmc W STEPS"
+        if a.mcmc_log is not None or a.mcmc_prior is not None:
+            return "--mcmc-log / --mcmc-prior state the coordinates and priors of --mcmc W STEPS: give --mcmc W STEPS"
         return None
     W, steps = a.mcmc
     if not 4 <= W <= 256 or W % 2:
@@ -644,7 +656,44 @@ def mcmc_error(a):
             return "--mcmc samples a uniform prior on a box: coordinate %s has no --box %s LO HI" % (name, name)
         if not all(np.isfinite(v) for v in boxed[name]):
             return "--mcmc needs a finite box: --box %s has an infinite bound" % name
+    names = [str(i) for i in range(k)] + (["st"] if a.fit_st else [])
+    for name in a.mcmc_log or ():
+        if name not in names:
+            return "--mcmc-log K: %s is no coordinate of this run (%s)" % (name, ", ".join(names))
+        if not boxed[name][0] > 0:
+            return "--mcmc-log %s samples the logarithm: --box %s needs LO > 0 (got %g)" % (name, name, boxed[name][0])
+    if a.mcmc_log and len(set(a.mcmc_log)) != len(a.mcmc_log):
+        return "--mcmc-log names a coordinate twice"
+    seen = set()
+    for spec in a.mcmc_prior or ():
+        text = " ".join(spec)
+        if spec[0] not in names:
+            return "--mcmc-prior %s: %s is no coordinate of this run (%s)" % (text, spec[0], ", ".join(names))
+        if spec[0] in seen:
+            return "--mcmc-prior %s: coordinate %s already has a prior" % (text, spec[0])
+        seen.add(spec[0])
+        want = {"normal": 2, "exponential": 1}.get(spec[1] if len(spec) > 1 else "")
+        if want is None or len(spec) != 2 + want:
+            return "--mcmc-prior K normal MEAN SD | K exponential SCALE (got %s)" % text
+        try:
+            v = [float(t) for t in spec[2:]]
+        except ValueError:
+            return "--mcmc-prior %s: the parameters must be numbers" % text
+        if not (np.isfinite(v).all() and v[-1] > 0):
+            return "--mcmc-prior %s: %s" % (text, "MEAN must be finite, SD finite and > 0" if want == 2 else "SCALE must be finite and > 0")
     return None
+
+
+def _mcmc_prior(a, k):
+    """The prior of --mcmc-log / --mcmc-prior over the k parameters (and the split, with --fit-st) as optimize.prior_spec states it, or
+    None without either option."""
+    if not (a.mcmc_log or a.mcmc_prior):
+        return None
+    from .optimize import prior_spec
+    at = lambda name: k if name == "st" else int(name)
+    specs = [(at(sp[0]), sp[1], [float(t) for t in sp[2:]]) for sp in a.mcmc_prior or ()]
+    return prior_spec(k + (1 if a.fit_st else 0), log=[at(n) for n in a.mcmc_log or ()], normal={c: tuple(v) for c, kind, v in specs if kind == "normal"},
+                      exponential={c: v[0] for c, kind, v in specs if kind == "exponential"})
 
 
 def _mcmc_from_de(a):
@@ -672,10 +721,11 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     inside the box and already evaluated.  With --mcmc-ladder L RATIO: ONE Engine.tempered_sample call on temperature_ladder(T, RATIO, L),
     every rung from that initial ensemble; the result's ``ladder`` holds the temperatures.
     Returns (options, temperature, result) - or a string: why --mcmc-temp auto has no temperature."""
-    from .optimize import composite_temperature, ensemble_start, score_covariance, temperature_ladder
+    from .optimize import composite_temperature, ensemble_start, score_covariance, temperature_ladder, to_sampling
     o = dict(_mcmc_options(a), **_mcmc_ladder_options(a))
     lo, hi = box
     x = np.where(np.isfinite(x), np.clip(x, lo, hi), 0.5 * (lo + hi))
+    prior = o["prior"] = _mcmc_prior(a, x.shape[1] - (1 if split_times is None else 0))
     T = o["temperature"]
     if T == "auto":
         P = e.n_param
@@ -691,6 +741,14 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
             T = composite_temperature(cur.hess[0], score_covariance(cur.dlog, data, unfolded=unfolded)[0])
         except ValueError as why:
             return "--mcmc-temp auto: %s" % why
+    if prior is not None:
+        # everything from here on is in sampling coordinates: the box of a --mcmc-log coordinate is the logarithm of its --box, the fits
+        # and DE's population are mapped with to_sampling (and clipped: a logarithm may land one ulp outside)
+        lo, hi = (to_sampling(np.asarray(v, dtype=float), prior) for v in box)
+        box = (lo, hi)
+        x = to_sampling(x, prior, box)
+        if population is not None:
+            population = to_sampling(np.asarray(population, dtype=float).reshape(x.shape[0], o["walkers"], x.shape[1]), prior, box)
     if population is not None:
         init = np.ascontiguousarray(population, dtype=np.float64).reshape(x.shape[0], o["walkers"], x.shape[1])
     else:
@@ -703,6 +761,8 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
         post = _mcmc_post_options(a)
         sampler = lambda *args, **kw: e.ensemble_posterior(*args, **kw, burn=o["burn"], keep_chain=bool(a.mcmc_out), **post)
     common = dict(split_times=split_times, fit_split=split_times is None, n_step=o["n_step"], thin=o["thin"], seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
+    if prior is not None:
+        common["prior"] = prior
     extra = {}
     if o["ladder"] is not None:
         ladder = temperature_ladder(T, o["ladder"][1], o["ladder"][0])
@@ -715,7 +775,8 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
         res = sampler(init, np.asarray(r_of, dtype=np.int32), data, box, temperature=T, **common)
     if a.mcmc_out:
         np.savez(a.mcmc_out, chain=res["chain"], chain_llh=res["chain_llh"], accepted=res["accepted"], last=res["last"], last_llh=res["last_llh"],
-                 row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T), **extra)
+                 row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T), **extra,
+                 **({} if prior is None else {"prior_" + k: v for k, v in prior.items()}))
     return o, float(T), res
 
 
@@ -728,13 +789,20 @@ def print_post(label, o, res, s):
     """The ``post:`` lines of fit s: one per coordinate, from the summaries the device reduced (Engine.ensemble_posterior)."""
     from .optimize import posterior_table
     n = o["n_step"] // o["thin"] - o["burn"]
-    t = posterior_table({k: res[k][s] for k in ("mean", "cov", "quant", "tau", "window", "last")}, n)
+    t = posterior_table({k: res[k][s] for k in ("mean", "cov", "quant", "tau", "window", "last", "best_x")}, n, prior=o.get("prior"))
     probs = o["probs"]
+    quant, best_x = t.get("quant_natural", t["quant"]), t.get("best_x_natural", res["best_x"][s])
     for c in range(res["mean"].shape[1]):
         print("post:", label, "\tcoordinate %d" % c, "\tmean =", t["mean"][c], "\tsd =", t["sd"][c],
-              *("\tq%g = %r" % (p, float(t["quant"][c][i])) for i, p in enumerate(probs)), "\ttau =", t["tau"][c], "\tn_eff =", t["n_eff"][c],
+              *("\tq%g = %r" % (p, float(quant[c][i])) for i, p in enumerate(probs)), "\ttau =", t["tau"][c], "\tn_eff =", t["n_eff"][c],
               *(["\t(short)"] if t["short"][c] else []), "\tcorr = [" + ", ".join(repr(float(v)) for v in t["corr"][c]) + "]",
-              "\tbest llh =", res["best_llh"][s], "at = (%d, %d)" % tuple(res["best_at"][s]), "x =", res["best_x"][s][c])
+              "\tbest llh =", res["best_llh"][s], "at = (%d, %d)" % tuple(res["best_at"][s]), "x =", best_x[c], *_log_note(o, c))
+
+
+def _log_note(o, c):
+    """What a summary line of coordinate c ends on where the coordinate was sampled on the log scale (--mcmc-log)."""
+    prior = o.get("prior")
+    return ["\t(log scale: quantiles and best sample in natural units, mean, sd and corr of the logarithm)"] if prior is not None and prior["scale"][c] else []
 
 
 def print_ladder(label, res, s):
@@ -757,12 +825,30 @@ def print_mcmc(label, o, res, s):
         return print_post(label, o, res, s)
     from .optimize import ensemble_summary
     m = ensemble_summary(res["chain"][s], o["burn"], accepted=res["accepted"][s], n_step=o["n_step"])
+    if o.get("prior") is not None:                         # quantiles are monotone under exp: natural units for the log-scale coordinates
+        from .optimize import from_sampling
+        m.update({k: from_sampling(m[k], o["prior"]) for k in ("median", "q025", "q975")})
     for c in range(res["chain"].shape[3]):
         print("mcmc:", label, "\tcoordinate %d" % c, "\tmean =", m["mean"][c], "\tmedian =", m["median"][c], "\t2.5% =", m["q025"][c], "\t97.5% =", m["q975"][c],
-              "\ttau =", m["tau"][c], "\taccepted =", m["acceptance"], *(["\t(short)"] if m["short"][c] else []))
+              "\ttau =", m["tau"][c], "\taccepted =", m["acceptance"], *(["\t(short)"] if m["short"][c] else []), *_log_note(o, c))
+
+
+def _prior_text(o):
+    """The sampler's prior in words, behind _mcmc_text; nothing without --mcmc-log / --mcmc-prior."""
+    p = o.get("prior")
+    if p is None:
+        return ""
+    parts = ["coordinate %d %s%s" % (c, "on the log scale" if p["scale"][c] else "linear",
+                                     ", normal(%r, %r)" % (float(p["p0"][c]), float(p["p1"][c])) if p["kind"][c] == 1 else
+                                     ", exponential(%r)" % float(p["p0"][c]) if p["kind"][c] == 2 else ", flat") for c in range(len(p["scale"]))]
+    return "; prior on the sampling coordinates (not tempered): " + "; ".join(parts)
 
 
 def _mcmc_text(o, T, res, dt):
+    return _mcmc_text_(o, T, res, dt) + _prior_text(o)
+
+
+def _mcmc_text_(o, T, res, dt):
     if o["ladder"] is not None:
         return "tempered ensemble MCMC with %d rungs up to %r x the temperature, a swap round every %d steps, %d walkers per rung, %d steps, thin %d, burn %d, from %s, temperature %r, seed %d: %d ladders in one call, %.3f s, %d proposals evaluated" % (
             o["ladder"][0], o["ladder"][1], o["swap_every"], o["walkers"], o["n_step"], o["thin"], o["burn"], o["start"], T, o["seed"], res["last"].shape[0], dt, res["n_points"])

@@ -20,6 +20,7 @@
 
 #include "misti_device.h"
 #include "misti_post.h"
+#include "misti_prior.h"
 #include "misti_tables.hpp"
 
 namespace {
@@ -1778,11 +1779,81 @@ int post_back(const misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, in
     return 0;
 }
 
+// ---- priors and log-scale coordinates (misti_prior.h) ----------------------------------------------------------------------------------
+// The prior descriptor of the two samplers, or NULL: its shape (behind check_n_box, before the context is looked at) ...
+int check_prior_shape(const misti_prior_t* p, int64_t n_start, const char* noun) {
+    if (!p) return 0;
+    if (p->n_prior != 1 && p->n_prior != n_start)
+        return fail(MISTI_E_ARG, "n_prior must be 1 or n_start (got %d for %lld %s)", (int)p->n_prior, (long long)n_start, noun);
+    if (!p->scale || !p->kind || !p->p0 || !p->p1) return fail(MISTI_E_ARG, "the prior's scale / kind / p0 / p1 is NULL");
+    return 0;
+}
+// ... one coordinate of search s (p0 / p1 are looked at only where the kind reads them) ...
+int check_prior_coord(int64_t s, int k, int32_t scale, int32_t kind, const double* p0, const double* p1, double lo, double hi) {
+    if (scale != MISTI_COORD_LINEAR && scale != MISTI_COORD_LOG)
+        return fail(MISTI_E_ARG, "prior of search %lld, coordinate %d: the scale %d is neither MISTI_COORD_LINEAR nor MISTI_COORD_LOG", (long long)s, k, (int)scale);
+    if (kind != MISTI_PRIOR_FLAT && kind != MISTI_PRIOR_NORMAL && kind != MISTI_PRIOR_EXPONENTIAL)
+        return fail(MISTI_E_ARG, "prior of search %lld, coordinate %d: the kind %d is none of MISTI_PRIOR_FLAT / NORMAL / EXPONENTIAL", (long long)s, k, (int)kind);
+    if (kind == MISTI_PRIOR_NORMAL && (!std::isfinite(*p1) || !(*p1 > 0.0)))
+        return fail(MISTI_E_ARG, "prior of search %lld, coordinate %d: the normal's sd %g is not finite and positive", (long long)s, k, *p1);
+    if (kind == MISTI_PRIOR_EXPONENTIAL && (!std::isfinite(*p0) || !(*p0 > 0.0)))
+        return fail(MISTI_E_ARG, "prior of search %lld, coordinate %d: the exponential's scale %g is not finite and positive", (long long)s, k, *p0);
+    if (kind == MISTI_PRIOR_NORMAL && !std::isfinite(*p0))
+        return fail(MISTI_E_ARG, "prior of search %lld, coordinate %d: the normal's mean is not finite", (long long)s, k);
+    if (scale == MISTI_COORD_LOG && (hi > 709.0 || lo < -745.0))
+        return fail(MISTI_E_ARG, "prior of search %lld, coordinate %d: the log-scale box [%g, %g] leaves [-745, 709] - its natural value would leave the doubles",
+                    (long long)s, k, lo, hi);
+    return 0;
+}
+// ... and every coordinate against its search's box (behind check_box: N comes from the context).
+int check_prior(const misti_prior_t* p, const RowsArgs& a, int N) {
+    if (!p || p->n_prior < 1 || a.n_box < 1) return 0;
+    const int64_t n = p->n_prior > a.n_box ? p->n_prior : a.n_box;
+    for (int64_t s = 0; s < n; ++s)
+        for (int k = 0; k < N; ++k) {
+            const int64_t q = (p->n_prior > 1 ? s : 0) * N + k, o = (a.n_box > 1 ? s : 0) * N + k;
+            if (int r = check_prior_coord(s, k, p->scale[q], p->kind[q], p->p0 + q, p->p1 + q, a.box_lo[o], a.box_hi[o])) return r;
+        }
+    return 0;
+}
+
+// The device side of a checked prior: carved and uploaded only where a coordinate is not LINEAR and FLAT - a prior that says nothing
+// takes the prior-less path.  `slots`: the proposals of a half-step.
+struct PriorProblem {
+    const misti_prior_t* p = nullptr;
+    size_t n = 0, ny = 0;            // n_prior x N; slots x N.  n == 0: no prior
+    int32_t *d_scale = nullptr, *d_kind = nullptr;
+    double *d_p0 = nullptr, *d_p1 = nullptr, *d_y = nullptr;
+    PriorProblem(const misti_prior_t* p_, int N, size_t slots) {
+        if (!p_) return;
+        const size_t all = (size_t)p_->n_prior * (size_t)N;
+        bool says = false;
+        for (size_t q = 0; q < all; ++q) says = says || p_->scale[q] != MISTI_COORD_LINEAR || p_->kind[q] != MISTI_PRIOR_FLAT;
+        if (says) { p = p_; n = all; ny = slots * (size_t)N; }
+    }
+    void layout(Carver<double>& f, Carver<int32_t>& i) {
+        if (!n) return;
+        d_p0 = f.take(n); d_p1 = f.take(n); d_y = f.take(ny);
+        d_scale = i.take(n); d_kind = i.take(n);
+    }
+    int upload(hipStream_t sm) const {
+        if (!n) return 0;
+        HIP_TRY(hipMemcpyAsync(d_scale, p->scale, n * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+        HIP_TRY(hipMemcpyAsync(d_kind, p->kind, n * sizeof(int32_t), hipMemcpyHostToDevice, sm));
+        HIP_TRY(hipMemcpyAsync(d_p0, p->p0, n * sizeof(double), hipMemcpyHostToDevice, sm));
+        HIP_TRY(hipMemcpyAsync(d_p1, p->p1, n * sizeof(double), hipMemcpyHostToDevice, sm));
+        return 0;
+    }
+    void fill(misti::EnsPrior& pr) const {
+        pr.scale = d_scale; pr.kind = d_kind; pr.p0 = d_p0; pr.p1 = d_p1; pr.per_start = n && p->n_prior > 1 ? 1 : 0; pr.y = d_y;
+    }
+};
+
 // ---- ensemble MCMC per search (misti_ens.hip) ------------------------------------------------------------------------------------
 // The arguments of misti_ensemble_sample, before the first HIP call, in the header's order.  Leaves the number of coordinates in N
 // and whether every split time is an integer in `whole`.  `keep`: the chain is kept on the device whether it is asked for or not
 // (misti_ensemble_posterior), so its limit applies.
-int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, bool keep = false) {
+int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, bool keep = false, const misti_prior_t* prior = nullptr) {
     const RowsArgs a = rows_args(q);
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
     if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.temperature || !q.last || !q.last_llh || (a.per_start() && !q.split_times))
@@ -1798,6 +1869,7 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, boo
         if (!std::isfinite(q.temperature[s]) || !(q.temperature[s] > 0.0))
             return fail(MISTI_E_ARG, "temperature[%lld] = %g is not finite and positive", (long long)s, q.temperature[s]);
     if (int r = check_n_box(a, "searches")) return r;
+    if (int r = check_prior_shape(prior, q.n_start, "searches")) return r;
     if (int r = check_rows(a, whole)) return r;
     if (int r = check_limits(c, a, q.walkers, "searches x walkers", N)) return r;
     if ((q.chain || q.chain_llh || keep) && q.n_start > 0 && (int64_t)(q.n_step / q.thin) > INT32_MAX / 8 / N / q.walkers / q.n_start)
@@ -1809,6 +1881,7 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, boo
         for (int k = 0; k < N; ++k) n_free += q.box_lo[b * N + k] != q.box_hi[b * N + k] ? 1 : 0;
         if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
     }
+    if (int r = check_prior(prior, a, N)) return r;
     for (int64_t s = 0; s < q.n_start; ++s)
         for (int i = 0; i < q.walkers; ++i)
             for (int k = 0; k < N; ++k) {
@@ -1825,7 +1898,7 @@ int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, boo
 // (which fills the first half of it); the state and the chain lie in the search buffers of the context.  Nothing is read back before
 // the end.  With `post` (checked: post_check) the chain is kept whether it is asked for or not, the summary kernels run on it where
 // it lies, and the summaries come back with the rest; the series workspace and the summaries' device side are carved with the chain.
-int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_ens_post_t* post = nullptr) {
+int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_ens_post_t* post = nullptr, const misti_prior_t* prior = nullptr) {
     using namespace misti;
     HIP_TRY(hipSetDevice(c->device));
     const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp;
@@ -1833,6 +1906,7 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
     PostArgs pa{};
     if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
     RowsProblem rows(c, rows_args(q), N, whole);
+    PriorProblem pri(prior, N, S * H);
     EnsState st{};
     st.S = q.n_start; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
     st.temp_per_start = q.n_temp > 1 ? 1 : 0;
@@ -1846,16 +1920,19 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
         if (K) { st.chain = f.take(S * K * W * (size_t)N); st.chain_llh = f.take(S * K * W); }
         st.accepted = i.take(M); st.submitted = i.take(M);
         rows.layout(f, i, &st.b, &M, 1, M);
+        pri.layout(f, i);
         if (post) post_carve(pa, *post, S, N, f, i);
     };
     if (int r = carve(c, "search", layout)) return r;
     rows.fill(st.src);
+    pri.fill(st.prior);
     st.temp = d_temp;
     st.points = reinterpret_cast<long long*>(d_points);
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(d_init, q.init, M * N * sizeof(double), hipMemcpyHostToDevice, sm));
     HIP_TRY(hipMemcpyAsync(d_temp, q.temperature, NT * sizeof(double), hipMemcpyHostToDevice, sm));
     if (int r = rows.upload(c)) return r;
+    if (int r = pri.upload(sm)) return r;
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
     HIP_TRY(launch_ens_init(st, d_init, sm));
     if (int r = rows.eval(c, st.b, (int64_t)M, llk)) return r;
@@ -1896,7 +1973,7 @@ int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_e
 // ---- tempered ensemble MCMC per fit (misti_pt.hip) -----------------------------------------------------------------------------------
 // The arguments of misti_tempered_sample, before the first HIP call, in the header's order: ens_check's, with the ladder where the
 // temperature stands and n_start x n_rung x walkers where the limits count.
-int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole) {
+int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole, const misti_prior_t* prior = nullptr) {
     const RowsArgs a = rows_args(q);
     if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of fits");
     if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.ladder || !q.last || !q.last_llh || !q.rung_llh || !q.logz || (a.per_start() && !q.split_times))
@@ -1922,6 +1999,7 @@ int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole) {
     const int64_t K = q.n_step / q.thin;
     if (K > 0 && (q.burn < 0 || q.burn >= K)) return fail(MISTI_E_ARG, "burn must be 0 ... K - 1 (got %d for %lld kept steps)", (int)q.burn, (long long)K);
     if (int r = check_n_box(a, "fits")) return r;
+    if (int r = check_prior_shape(prior, q.n_start, "fits")) return r;
     if (int r = check_rows(a, whole)) return r;
     const int64_t per = (int64_t)q.walkers * q.n_rung;
     if (int r = check_limits(c, a, per, "fits x rungs x walkers", N)) return r;
@@ -1934,6 +2012,7 @@ int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole) {
         for (int k = 0; k < N; ++k) n_free += q.box_lo[b * N + k] != q.box_hi[b * N + k] ? 1 : 0;
         if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
     }
+    if (int r = check_prior(prior, a, N)) return r;
     for (int64_t s = 0; s < q.n_start; ++s)
         for (int l = 0; l < q.n_rung; ++l)
             for (int i = 0; i < q.walkers; ++i)
@@ -1950,7 +2029,7 @@ int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole) {
 // A checked call with n_start >= 1: ens_run over n_start x n_rung searches (EnsState::L), with a swap launch behind the steps that
 // have a round and the reduction at the end.  The values of every rung are always kept on the device (the reduction reads them), the
 // cold rung's coordinates where the caller or `post` wants them.
-int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens_post_t* post) {
+int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens_post_t* post, const misti_prior_t* prior) {
     using namespace misti;
     HIP_TRY(hipSetDevice(c->device));
     const size_t F = (size_t)q.n_start, L = (size_t)q.n_rung, S = F * L, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_ladder * L;
@@ -1958,6 +2037,7 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
     PostArgs pa{};
     if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
     RowsProblem rows(c, rows_args(q), N, whole);
+    PriorProblem pri(prior, N, S * H);
     EnsState st{};
     st.S = (int64_t)S; st.L = q.n_rung; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
     st.temp_per_start = q.n_ladder > 1 ? 1 : 0;
@@ -1975,10 +2055,12 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
         st.accepted = i.take(M); st.submitted = i.take(M);
         pt.swap_proposed = i.take(P); pt.swap_accepted = i.take(P);
         rows.layout(f, i, &st.b, &M, 1, M);
+        pri.layout(f, i);
         if (post) post_carve(pa, *post, F, N, f, i);
     };
     if (int r = carve(c, "search", layout)) return r;
     rows.fill(st.src);
+    pri.fill(st.prior);
     st.temp = d_temp;
     st.points = reinterpret_cast<long long*>(d_points);
     hipStream_t sm = c->stream;
@@ -1986,6 +2068,7 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
     HIP_TRY(hipMemcpyAsync(d_temp, q.ladder, NT * sizeof(double), hipMemcpyHostToDevice, sm));
     if (P) HIP_TRY(hipMemsetAsync(pt.swap_proposed, 0, 2 * P * sizeof(int32_t), sm));     // the two counters lie back to back
     if (int r = rows.upload(c)) return r;
+    if (int r = pri.upload(sm)) return r;
     c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
     HIP_TRY(launch_ens_init(st, d_init, sm));
     if (int r = rows.eval(c, st.b, (int64_t)M, llk)) return r;
@@ -2037,33 +2120,67 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
 
 extern "C" {
 
-int misti_tempered_sample(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p) {
+int misti_tempered_sample_prior(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) {
     if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
     if (q->size != sizeof(misti_pt_t))
         return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_pt_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_pt_t));
     if (p && p->size != sizeof(misti_ens_post_t))
         return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
+    if (pr && pr->size != sizeof(misti_prior_t))
+        return fail(MISTI_E_ARG, "the prior descriptor's size is %u, this library's misti_prior_t has %u bytes", (unsigned)pr->size, (unsigned)sizeof(misti_prior_t));
     if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
         return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
     int N = 0;
     bool whole = false;
-    if (int r = pt_check(c, *q, N, whole)) return r;
+    if (int r = pt_check(c, *q, N, whole, pr)) return r;
     if (p) if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
     if (q->n_start == 0) return 0;
-    return pt_run(c, *q, N, whole, p);
+    return pt_run(c, *q, N, whole, p, pr);
 }
 
-int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) {
+int misti_tempered_sample(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p) { return misti_tempered_sample_prior(c, q, p, nullptr); }
+
+// misti_ensemble_sample (no post), misti_ensemble_posterior (`need_post`: a post there must be) and misti_ensemble_sample_prior: one door
+static int ens_entry(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post) {
     if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
     if (q->size != sizeof(misti_ens_t))
         return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_ens_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_ens_t));
+    if (need_post && !p) return fail(MISTI_E_ARG, "the summary descriptor is NULL");
+    if (p && p->size != sizeof(misti_ens_post_t))
+        return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
+    if (pr && pr->size != sizeof(misti_prior_t))
+        return fail(MISTI_E_ARG, "the prior descriptor's size is %u, this library's misti_prior_t has %u bytes", (unsigned)pr->size, (unsigned)sizeof(misti_prior_t));
     if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
         return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
     int N = 0;
     bool whole = false;
-    if (int r = ens_check(c, *q, N, whole)) return r;
+    if (int r = ens_check(c, *q, N, whole, p != nullptr, pr)) return r;
+    if (p) if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
     if (q->n_start == 0) return 0;
-    return ens_run(c, *q, N, whole);
+    return ens_run(c, *q, N, whole, p, pr);
+}
+
+int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) { return ens_entry(c, q, nullptr, nullptr, false); }
+
+int misti_ensemble_sample_prior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) { return ens_entry(c, q, p, pr, false); }
+
+int misti_ens_log_prior(int32_t N, const int32_t* scale, const int32_t* kind, const double* p0, const double* p1, const double* lo, const double* hi,
+                        const double* y, double* lp, double* natural) {
+    if (N < 1 || N > MISTI_MAX_PARAMS) return fail(MISTI_E_ARG, "N must be 1 ... %d (got %d)", MISTI_MAX_PARAMS, (int)N);
+    if (!scale || !kind || !p0 || !p1 || !lo || !hi || !y || !lp) return fail(MISTI_E_ARG, "scale / kind / p0 / p1 / lo / hi / y / lp is NULL");
+    for (int k = 0; k < N; ++k)
+        if (int r = check_prior_coord(0, k, scale[k], kind[k], p0 + k, p1 + k, lo[k], hi[k])) return r;
+    *lp = misti::ens_log_prior(N, kind, p0, p1, lo, hi, y);
+    for (int k = 0; natural && k < N; ++k) natural[k] = misti::ens_natural(scale[k], y[k]);
+    return 0;
+}
+
+int misti_ens_accept_prior(double z, int32_t d, double llk_old, double llk_new, double T, double lp_old, double lp_new, double u_acc, int32_t* accept) {
+    if (!accept) return fail(MISTI_E_ARG, "accept is NULL");
+    if (d < 0 || d >= MISTI_MAX_PARAMS) return fail(MISTI_E_ARG, "d must be 0 ... MISTI_MAX_PARAMS - 1");
+    if (!(T > 0.0) || !std::isfinite(T)) return fail(MISTI_E_ARG, "the temperature must be finite and positive");
+    *accept = misti::ens_decide_prior(z, d, llk_old, llk_new, T, lp_old, lp_new, u_acc) ? 1 : 0;
+    return 0;
 }
 
 int misti_ens_summary_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t N, const double* d_chain, const double* d_chain_llh, const misti_ens_post_t* p) {
@@ -2083,22 +2200,7 @@ int misti_ens_summary_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t
     return 0;
 }
 
-int misti_ensemble_posterior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p) {
-    if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
-    if (q->size != sizeof(misti_ens_t))
-        return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_ens_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_ens_t));
-    if (!p) return fail(MISTI_E_ARG, "the summary descriptor is NULL");
-    if (p->size != sizeof(misti_ens_post_t))
-        return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
-    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
-        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
-    int N = 0;
-    bool whole = false;
-    if (int r = ens_check(c, *q, N, whole, true)) return r;
-    if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
-    if (q->n_start == 0) return 0;
-    return ens_run(c, *q, N, whole, p);
-}
+int misti_ensemble_posterior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p) { return ens_entry(c, q, p, nullptr, true); }
 
 int misti_de_search(misti_ctx* c, const misti_de_t* q) {
     if (!q) return fail(MISTI_E_ARG, "the search descriptor is NULL");

@@ -287,6 +287,19 @@ hipError_t launch_de_select(const DeState& st, int64_t bound, int gen, const dou
 // x[S][N], llh[S], nit / nfev / status[S]; pop_llh[S][P] (or NULL): -f
 hipError_t launch_de_result(const DeState& st, double* x, double* llh, int32_t* nfev, int32_t* status, double* pop_llh, hipStream_t stream);
 
+// The prior of misti_ensemble_sample_prior / misti_tempered_sample_prior (misti_prior.h), per coordinate of a search or fit.  All NULL
+// for the entries without one: nothing of it is allocated, read or written, and a kernel branches on it by one wave-uniform pointer
+// test (`kind`), as on PointSource's box.
+struct EnsPrior {
+    const int32_t* scale;   // [N], or [S / L][N] with per_start: MISTI_COORD_*
+    const int32_t* kind;    // the same shape: MISTI_PRIOR_*; NULL: no prior
+    const double* p0;       // the same shape
+    const double* p1;
+    int per_start;
+    double* y;              // [S * H][N] the sampling coordinates of the slot's proposal: with a prior the slot's `pts` holds the natural point
+};
+__device__ __forceinline__ int64_t prior_of(const EnsPrior& pr, int64_t fit, int N) { return pr.per_start ? fit * N : 0; }
+
 // Ensemble sampler per search (misti_ens.hip; the rule is optimize.ensemble_rule, operation for operation): everything a search
 // owns, in HBM.  A half-step of every search is ONE engine batch of H = W / 2 points per search; batch slot s * H + m carries the
 // proposal of walker half * H + m of search s (the initial ensemble: slot s * W + i, walker i).  No search ever stops, so slots are
@@ -306,7 +319,8 @@ struct EnsState {
     const double* temp;     // [L], or [S / L][L] with temp_per_start
     int temp_per_start;
     PointSource src;        // what a search hands its points; always with rows and a finite box
-    double* x;              // [S][W][N] the ensemble
+    EnsPrior prior;         // all NULL without a prior
+    double* x;              // [S][W][N] the ensemble (with a prior: in sampling coordinates)
     double* llh;            // [S][W]    its log-likelihood (-inf where the engine has no value)
     double* z;              // [S * H]   the stretch of the slot's proposal; negative: rejected in advance, the slot carries no point
     double* u_acc;          // [S * H]   the decision's uniform

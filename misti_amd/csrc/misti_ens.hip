@@ -15,6 +15,10 @@
 // walker), the engine evaluates them as an ordinary rows-path batch (run_dev, launch_llk_rows), and one kernel takes the decisions.
 // A proposal that leaves the box is rejected without an evaluation: its slot carries a negative split, which the engine refuses
 // before it reads anything else of the slot.
+//
+// With a prior (EnsState::prior, misti_prior.h; the rule is optimize.ensemble_prior_rule) the ensemble, the stretch and the box are in
+// sampling coordinates; the slot's point is their natural image (ens_natural), the proposal itself waits in prior.y, and the decision
+// carries the log prior of the old walker and of the proposal (ens_decide_prior).  Without one nothing of this is read or written.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -24,6 +28,7 @@
 #include "misti_boot.h"
 #include "misti_device.h"
 #include "misti_ens.h"
+#include "misti_prior.h"
 
 namespace misti {
 
@@ -48,7 +53,12 @@ void ens_init_kernel(EnsState st, const double* __restrict__ init) {
     const int64_t fit = t / W / st.L;
     double* pt = st.b.pts + t * N;
     double* x = st.x + t * N;
-    for (int k = 0; k < N; ++k) { const double v = init[t * N + k]; pt[k] = v; x[k] = v; }
+    if (st.prior.kind) {
+        const int32_t* scale = st.prior.scale + prior_of(st.prior, fit, N);
+        for (int k = 0; k < N; ++k) { const double v = init[t * N + k]; pt[k] = ens_natural(scale[k], v); x[k] = v; }
+    } else {
+        for (int k = 0; k < N; ++k) { const double v = init[t * N + k]; pt[k] = v; x[k] = v; }
+    }
     put_point(st.src, st.b, t, fit, pt);
 }
 
@@ -68,11 +78,23 @@ void ens_propose_kernel(EnsState st, int64_t step, int half) {
     const int64_t o = box_of(st.src, fit);
     double* pt = st.b.pts + t * N;
     bool inside = true;
-    for (int k = 0; k < N; ++k) {
-        const double lo = st.src.box_lo[o + k], hi = st.src.box_hi[o + k];
-        const double y = lo == hi ? lo : xj[k] + ens_rn(z * (xi[k] - xj[k]));
-        inside = inside && y >= lo && y <= hi;                                 // a NaN is outside
-        pt[k] = y;
+    if (st.prior.kind) {
+        const int32_t* scale = st.prior.scale + prior_of(st.prior, fit, N);
+        double* yt = st.prior.y + t * N;
+        for (int k = 0; k < N; ++k) {
+            const double lo = st.src.box_lo[o + k], hi = st.src.box_hi[o + k];
+            const double y = lo == hi ? lo : xj[k] + ens_rn(z * (xi[k] - xj[k]));
+            inside = inside && y >= lo && y <= hi;
+            yt[k] = y;
+            pt[k] = ens_natural(scale[k], y);
+        }
+    } else {
+        for (int k = 0; k < N; ++k) {
+            const double lo = st.src.box_lo[o + k], hi = st.src.box_hi[o + k];
+            const double y = lo == hi ? lo : xj[k] + ens_rn(z * (xi[k] - xj[k]));
+            inside = inside && y >= lo && y <= hi;                                 // a NaN is outside
+            pt[k] = y;
+        }
     }
     st.u_acc[t] = dr.u_acc;
     if (inside) { st.z[t] = z; put_point(st.src, st.b, t, fit, pt); }
@@ -105,8 +127,21 @@ void ens_accept_kernel(EnsState st, int64_t step, int half, const double* __rest
         const double T = st.temp[(st.temp_per_start ? fit : 0) * st.L + l];
         const double v = ens_value(llk[t]);
         st.submitted[wi] = st.submitted[wi] + 1;
-        if (ens_decide(z, d, st.llh[wi], v, T, st.u_acc[t])) {
-            const double* pt = st.b.pts + t * N;
+        bool take;
+        const double* pt;
+        if (st.prior.kind) {                                // the proposal is in prior.y: the slot's point is its natural image
+            const int64_t q = prior_of(st.prior, fit, N);
+            const int32_t* kind = st.prior.kind + q;
+            const double *p0 = st.prior.p0 + q, *p1 = st.prior.p1 + q, *lo = st.src.box_lo + o, *hi = st.src.box_hi + o;
+            pt = st.prior.y + t * N;
+            const double lp_old = ens_log_prior(N, kind, p0, p1, lo, hi, st.x + wi * N);
+            const double lp_new = ens_log_prior(N, kind, p0, p1, lo, hi, pt);
+            take = ens_decide_prior(z, d, st.llh[wi], v, T, lp_old, lp_new, st.u_acc[t]);
+        } else {
+            pt = st.b.pts + t * N;
+            take = ens_decide(z, d, st.llh[wi], v, T, st.u_acc[t]);
+        }
+        if (take) {
             double* x = st.x + wi * N;
             for (int k = 0; k < N; ++k) x[k] = pt[k];
             st.llh[wi] = v;

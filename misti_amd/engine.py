@@ -704,8 +704,23 @@ class Engine:
             out.update(population=popx, population_llh=popl)
         return out
 
+    @staticmethod
+    def _prior(prior, S, N, who):
+        """``misti_prior_t`` of ``prior`` (dict(scale, kind, p0, p1), each ``[N]`` or ``[S][N]``; ``optimize.prior_spec``): the
+        descriptor and the arrays it points into (to be kept alive until the call returns)."""
+        try:
+            scale, kind = (np.ascontiguousarray(np.asarray(prior[k]), dtype=np.int32) for k in ("scale", "kind"))
+            p0, p1 = (_f64(prior[k]) for k in ("p0", "p1"))
+        except (KeyError, TypeError):
+            raise ValueError("%s: a prior is dict(scale, kind, p0, p1)" % who)
+        if any(v.shape != scale.shape for v in (kind, p0, p1)) or scale.shape not in ((N,), (S, N)):
+            raise ValueError("%s: the prior's arrays must all be [%d] or [%d][%d] (got %s)" % (who, N, S, N, scale.shape))
+        keep = (scale, kind, p0, p1)
+        return _lib.Prior(size=C.sizeof(_lib.Prior), n_prior=1 if scale.ndim == 1 else S, scale=scale.ctypes.data, kind=kind.ctypes.data,
+                          p0=p0.ctypes.data, p1=p1.ctypes.data), keep
+
     def ensemble_sample(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
-                        thin=1, temperature=1.0, a=2.0, seed=0, ids=None):
+                        thin=1, temperature=1.0, a=2.0, seed=0, ids=None, prior=None):
         """``misti_ensemble_sample``: ensemble MCMC per search - search s is an ensemble of W walkers ``init[s]`` (``[S][W][N]``, W even,
         every walker inside its box) against ``table[rows[s]]`` (``[n_rep][8]``), sampling ``llk / temperature`` under a uniform prior on
         its finite ``box`` (``(lo, hi)``, each ``[N]`` or ``[S][N]``; ``lo == hi`` holds a coordinate fixed); every half-step of all
@@ -716,12 +731,16 @@ class Engine:
         alone; a later call continues from ``last`` with other ids.  ``band_bounds`` / ``pulse_times`` per search as in ``nm_solve_pulses``.
         Returns dict(chain[S][n_keep][W][N], chain_llh[S][n_keep][W] (the ensembles after steps thin, 2 thin, ...), accepted[S][W],
         last[S][W][N], last_llh[S][W], n_points (proposals the call handed the engine; those that leave the box are rejected without an
-        evaluation and not counted, nor are the S W initial evaluations))."""
+        evaluation and not counted, nor are the S W initial evaluations)).
+        ``prior`` (None, or dict(scale, kind, p0, p1), each ``[N]`` or ``[S][N]``: ``optimize.prior_spec``): a sampling coordinate (the
+        engine's value or its logarithm) and a prior density per coordinate - ``misti_ensemble_sample_prior``, the rule is
+        ``optimize.ensemble_prior_rule``.  ``init``, ``box``, ``chain`` and ``last`` are then in SAMPLING coordinates
+        (``optimize.to_sampling`` / ``from_sampling``); the engine is handed their natural image."""
         return self._ensemble("ensemble_sample", None, True, init, rows, table, box, split_times, fit_split, band_bounds, pulse_times, n_step, thin,
-                              temperature, a, seed, ids)
+                              temperature, a, seed, ids, prior)
 
     def _ensemble(self, who, post, keep_chain, init, rows, table, box, split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature,
-                  a, seed, ids):
+                  a, seed, ids, prior=None):
         """``misti_ensemble_sample`` (``post`` None) or ``misti_ensemble_posterior`` (``post``: dict(burn, probs, max_lag, c)): one
         marshalling of the sampler's descriptor for both."""
         if (split_times is None) != bool(fit_split):
@@ -746,8 +765,11 @@ class Engine:
                            **fields)
         out = dict(chain=chain, chain_llh=chain_llh) if post is None else {}
         out.update(accepted=accepted, last=last, last_llh=last_llh)
-        if post is None:
+        pr, pr_arrays = self._prior(prior, S, N, who) if prior is not None else (None, None)
+        if post is None and pr is None:
             _lib.check(self._lib.misti_ensemble_sample(self._ctx, C.byref(q)))
+        elif post is None:
+            _lib.check(self._lib.misti_ensemble_sample_prior(self._ctx, C.byref(q), None, C.byref(pr)))
         else:
             probs = _f64(post["probs"]).reshape(-1)
             P = probs.size
@@ -757,7 +779,10 @@ class Engine:
                      window=np.empty((S, N), dtype=np.int32), best_llh=np.empty(S), best_x=np.empty((S, N)), best_at=np.empty((S, 2), dtype=np.int32))
             p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=burn, n_prob=P, probs=ptr(probs), max_lag=min(max_lag, 2 ** 31 - 1), c=float(post["c"]),
                              **{k: ptr(v) for k, v in s.items()})
-            _lib.check(self._lib.misti_ensemble_posterior(self._ctx, C.byref(q), C.byref(p)))
+            if pr is None:
+                _lib.check(self._lib.misti_ensemble_posterior(self._ctx, C.byref(q), C.byref(p)))
+            else:
+                _lib.check(self._lib.misti_ensemble_sample_prior(self._ctx, C.byref(q), C.byref(p), C.byref(pr)))
             out.update(s)
         if keep_chain and post is not None:
             out.update(chain=chain, chain_llh=chain_llh)
@@ -765,7 +790,8 @@ class Engine:
         return out
 
     def ensemble_posterior(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
-                           thin=1, temperature=1.0, a=2.0, seed=0, ids=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, keep_chain=False, c=5.0):
+                           thin=1, temperature=1.0, a=2.0, seed=0, ids=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, keep_chain=False, c=5.0,
+                           prior=None):
         """``misti_ensemble_posterior``: ``ensemble_sample`` on the same arguments - the same kernels, stream and bits - followed by the
         posterior summaries of its chain, reduced per search ON THE DEVICE: without ``keep_chain`` the chain never leaves it.  The rule is
         ``optimize.ensemble_posterior_rule`` on the kept steps ``burn ... n_keep - 1`` (n of them), bit for bit: ``probs`` (1 ... 8
@@ -773,12 +799,14 @@ class Engine:
         ``n - 1``, every lag), ``c`` is Sokal's window constant.
         Returns dict(mean[S][N], cov[S][N][N], quant[S][N][len(probs)], tau[S][N] (in kept steps), window[S][N] (-1: no lag up to the
         cap closed the window), best_llh[S], best_x[S][N], best_at[S][2] ((kept step - burn, walker); (-1, -1): no sample has a value),
-        accepted, last, last_llh, n_points as ``ensemble_sample``), and chain, chain_llh with ``keep_chain``."""
+        accepted, last, last_llh, n_points as ``ensemble_sample``), and chain, chain_llh with ``keep_chain``.  ``prior`` as in
+        ``ensemble_sample``: the summaries are then those of the chain in SAMPLING coordinates (``optimize.posterior_table`` reports
+        quantiles and the best sample in natural units too)."""
         return self._ensemble("ensemble_posterior", dict(burn=burn, probs=probs, max_lag=max_lag, c=c), bool(keep_chain), init, rows, table, box,
-                              split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature, a, seed, ids)
+                              split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature, a, seed, ids, prior)
 
     def tempered_sample(self, init, rows, table, box, ladder, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
-                        thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None, post=None):
+                        thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None, post=None, prior=None):
         """``misti_tempered_sample``: parallel tempering over ``ensemble_sample`` - fit s is a ladder of L ensembles ``init[s]``
         (``[S][L][W][N]``) at the temperatures ``ladder`` (``[L]`` or ``[S][L]``, strictly increasing); rung l samples ``llk / T_l``,
         neighbouring rungs trade walkers every ``swap_every`` steps (0: never), the cold rung carries the posterior, and all rungs of all
@@ -788,7 +816,8 @@ class Engine:
         ``ensemble_posterior`` reduced on the device from the cold chain, which then comes back only with ``keep_chain``.
         Returns dict(chain[S][K][W][N] (the cold rung), chain_llh[S][L][K][W], accepted[S][L][W], swap_proposed[S][L-1],
         swap_accepted[S][L-1], last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S] (see ``optimize.tempered_rule`` for what it
-        is and is not), n_points), plus the summaries with ``post``."""
+        is and is not), n_points), plus the summaries with ``post``.  ``prior`` as in ``ensemble_sample`` (one per fit): every rung
+        targets ``prior(y) exp(llk / T_l)`` - ``misti_tempered_sample_prior``, the rule is ``optimize.tempered_prior_rule``."""
         if (split_times is None) != bool(fit_split):
             raise ValueError("tempered_sample: give exactly one of split_times and fit_split=True")
         N = self.n_param + (1 if fit_split else 0)
@@ -822,7 +851,11 @@ class Engine:
                      window=np.empty((S, N), dtype=np.int32), best_llh=np.empty(S), best_x=np.empty((S, N)), best_at=np.empty((S, 2), dtype=np.int32))
             p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=pburn, n_prob=P, probs=ptr(probs), max_lag=min(max_lag, 2 ** 31 - 1), c=float(opts.get("c", 5.0)),
                              **{k: ptr(v) for k, v in s.items()})
-        _lib.check(self._lib.misti_tempered_sample(self._ctx, C.byref(q), C.byref(p) if p is not None else None))
+        if prior is None:
+            _lib.check(self._lib.misti_tempered_sample(self._ctx, C.byref(q), C.byref(p) if p is not None else None))
+        else:
+            pr, pr_arrays = self._prior(prior, S, N, "tempered_sample")
+            _lib.check(self._lib.misti_tempered_sample_prior(self._ctx, C.byref(q), C.byref(p) if p is not None else None, C.byref(pr)))
         if not keep_chain:
             del out["chain"]
         if p is not None:

@@ -1533,6 +1533,10 @@ def ens_decision(z, d, llk_old, llk_new, T, u_acc):
 
 
 def ensemble_rule(fun_batch, init, lo, hi, n_step, thin=1, temperature=1.0, a=2.0, seed=0, ids=None):
+    return _ensemble_rule("ensemble_rule", fun_batch, init, lo, hi, n_step, None, thin, temperature, a, seed, ids)
+
+
+def _ensemble_rule(who, fun_batch, init, lo, hi, n_step, prior, thin, temperature, a, seed, ids):
     """The rule of ``misti_ensemble_sample``, operation for operation.  ``fun_batch(X[M][N], s[M]) -> f[M]`` evaluates M points at once,
     point m belonging to search ``s[m]`` (f = -llk; ``+inf``: no value; a NaN counts as ``+inf``).  ``init`` ``[S][W][N]``: the initial
     ensembles, W even, every walker inside its box; ``lo`` / ``hi``: the finite box, ``[N]`` or ``[S][N]``, ``lo == hi`` holds a
@@ -1547,10 +1551,13 @@ def ensemble_rule(fun_batch, init, lo, hi, n_step, thin=1, temperature=1.0, a=2.
     ``d = N_free - 1``.  No stopping rule.
     Returns dict(chain[S][n_keep][W][N], chain_llh[S][n_keep][W] (the ensembles after steps thin, 2 thin, ...; n_keep = n_step // thin),
     accepted[S][W] int32, last[S][W][N], last_llh[S][W], n_points: the PROPOSALS handed to ``fun_batch`` - the S W initial evaluations
-    are not counted)."""
+    are not counted).
+
+    ``prior`` (``ensemble_prior_rule``; None here): see there - the one difference is the point handed to ``fun_batch`` and the ``e`` of
+    the decision; a prior that says nothing takes the lines without one."""
     x = np.array(init, dtype=np.float64)
     if x.ndim != 3:
-        raise ValueError("ensemble_rule: init must be [S][W][N]")
+        raise ValueError("%s: init must be [S][W][N]" % who)
     S, W, N = x.shape
     H = W // 2
     n_step, thin, a = int(n_step), int(thin), float(a)
@@ -1558,23 +1565,26 @@ def ensemble_rule(fun_batch, init, lo, hi, n_step, thin=1, temperature=1.0, a=2.
     hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=float), (S, N)))
     T = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=float), (S,)))
     if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or n_step < 0 or thin < 1 or not (np.isfinite(a) and a > 1.0):
-        raise ValueError("ensemble_rule: W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
+        raise ValueError(who + ": W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
     if not (np.isfinite(T) & (T > 0)).all():
-        raise ValueError("ensemble_rule: the temperature must be finite and positive")
+        raise ValueError(who + ": the temperature must be finite and positive")
     with np.errstate(over="ignore", invalid="ignore"):
         usable = np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(hi - lo).all()
     if not usable:
-        raise ValueError("ensemble_rule: the box must be finite with lo <= hi")
+        raise ValueError(who + ": the box must be finite with lo <= hi")
     fixed = lo == hi
     if S and fixed.all(axis=1).any():
-        raise ValueError("ensemble_rule: every coordinate of a box is fixed")
+        raise ValueError(who + ": every coordinate of a box is fixed")
     if not (np.isfinite(x).all() and (x >= lo[:, None, :]).all() and (x <= hi[:, None, :]).all()):
-        raise ValueError("ensemble_rule: every walker of init must be finite and inside its box")
+        raise ValueError(who + ": every walker of init must be finite and inside its box")
     ids = np.arange(S) if ids is None else np.asarray(ids).reshape(S)
     d = (~fixed).sum(axis=1) - 1
+    pr = _prior_arrays(prior, S, N, lo, hi, who)
     am1 = a - 1.0
 
     def values(X, s_of):
+        if pr is not None:
+            X = ens_natural(pr["scale"][s_of], X)
         f = np.asarray(fun_batch(X, s_of), dtype=float).reshape(-1)
         llk = -np.where(np.isnan(f), np.inf, f)
         return np.where(np.isfinite(llk), llk, -np.inf)
@@ -1606,7 +1616,11 @@ def ensemble_rule(fun_batch, init, lo, hi, n_step, thin=1, temperature=1.0, a=2.
             if inside.any():
                 new[inside] = values(y[inside], np.broadcast_to(sidx, (S, H))[inside])
                 n_points += int(inside.sum())
-            take = inside & ens_decision(z, d[:, None], llh[:, mine], new, T[:, None], u_acc)
+            if pr is None:
+                take = inside & ens_decision(z, d[:, None], llh[:, mine], new, T[:, None], u_acc)
+            else:
+                lp_old, lp_new = (ens_log_prior(pr["kind"][:, None], pr["p0"][:, None], pr["p1"][:, None], lo[:, None], hi[:, None], v) for v in (xi, y))
+                take = inside & ens_decision_prior(z, d[:, None], llh[:, mine], new, T[:, None], lp_old, lp_new, u_acc)
             x[:, mine] = np.where(take[:, :, None], y, xi)
             llh[:, mine] = np.where(take, new, llh[:, mine])
             accepted[:, mine] += take
@@ -1825,11 +1839,13 @@ def ensemble_posterior_rule(chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.
     return {k_: v[0] for k_, v in out.items()} if one else out
 
 
-def posterior_table(result, n_step, walkers=None):
+def posterior_table(result, n_step, walkers=None, prior=None):
     """What one reads off ``ensemble_posterior`` / ``ensemble_posterior_rule`` per coordinate, with ``n_step`` = n, the kept steps
     behind the summary, and W ``walkers`` (default: those of ``result["last"]``): dict(mean, sd (the square root of the covariance's
     diagonal), quant, tau, n_eff = n W / tau, short: fewer than 50 tau kept steps or no lag closed the window (window == -1), corr: the
-    correlation matrix)."""
+    correlation matrix).  With ``prior`` (the call's) also ``coordinate`` (per coordinate "linear" or "log": what ``mean`` and ``sd``
+    are in), ``quant_natural`` (``quant`` with the LOG coordinates in natural units) and, where the result has ``best_x``,
+    ``best_x_natural``."""
     n, W = int(n_step), int(np.asarray(result["last"]).shape[-2] if walkers is None else walkers)
     cov = np.asarray(result["cov"], dtype=np.float64)
     tau = np.asarray(result["tau"], dtype=np.float64)
@@ -1837,8 +1853,138 @@ def posterior_table(result, n_step, walkers=None):
         sd = np.sqrt(np.diagonal(cov, axis1=-2, axis2=-1))
         corr = cov / (sd[..., :, None] * sd[..., None, :])
         n_eff = float(n * W) / tau
-    return dict(mean=np.asarray(result["mean"]), sd=sd, quant=np.asarray(result["quant"]), tau=tau, n_eff=n_eff,
+    out = dict(mean=np.asarray(result["mean"]), sd=sd, quant=np.asarray(result["quant"]), tau=tau, n_eff=n_eff,
                 short=(n < 50.0 * tau) | (np.asarray(result["window"]) == -1), corr=corr)
+    if prior is not None:
+        # quantiles and the best sample of a LOG coordinate in natural units as well (monotone: exact up to numpy.exp); mean and sd stay
+        # in the sampling coordinate, which `coordinate` names
+        log = np.asarray(prior["scale"]) == COORD_LOG
+        out.update(coordinate=np.where(log, "log", "linear"), quant_natural=from_sampling(np.swapaxes(out["quant"], -1, -2), prior).swapaxes(-1, -2))
+        if "best_x" in result:
+            out.update(best_x_natural=from_sampling(result["best_x"], prior))
+    return out
+
+
+# ------------------------------------------------------------------------------- priors and log-scale coordinates ----
+# What a prior adds to the rules above and below (include/misti_hip.h, "priors and log-scale coordinates"; misti_prior.h): per
+# coordinate a SAMPLING COORDINATE (the engine's value or its logarithm) and a prior density on it.  Stated here once; the device result
+# is ensemble_prior_rule / tempered_prior_rule, bit for bit.
+COORD_LINEAR, COORD_LOG = 0, 1
+PRIOR_FLAT, PRIOR_NORMAL, PRIOR_EXPONENTIAL = 0, 1, 2
+
+
+def prior_spec(N, log=(), normal=None, exponential=None):
+    """The four arrays of a prior over N coordinates: dict(scale[N], kind[N] int32, p0[N], p1[N]).  ``log``: the coordinates sampled on
+    the log scale; ``normal``: ``{k: (mean, sd)}``; ``exponential``: ``{k: scale}`` - both on the SAMPLING coordinate, so a normal on a
+    log coordinate is a log-normal and a coordinate named in neither is flat (on a log coordinate: log-uniform).  Host only."""
+    N = int(N)
+    normal, exponential = dict(normal or {}), dict(exponential or {})
+    names = list(log) + list(normal) + list(exponential)
+    if any(not 0 <= int(k) < N for k in names) or set(normal) & set(exponential):
+        raise ValueError("prior_spec: a coordinate is outside 0 ... %d, or has two priors" % (N - 1))
+    out = dict(scale=np.zeros(N, dtype=np.int32), kind=np.zeros(N, dtype=np.int32), p0=np.zeros(N), p1=np.zeros(N))
+    for k in log:
+        out["scale"][int(k)] = COORD_LOG
+    for k, (mean, sd) in normal.items():
+        out["kind"][int(k)], out["p0"][int(k)], out["p1"][int(k)] = PRIOR_NORMAL, float(mean), float(sd)
+    for k, scale in exponential.items():
+        out["kind"][int(k)], out["p0"][int(k)] = PRIOR_EXPONENTIAL, float(scale)
+    return out
+
+
+def _prior_arrays(prior, S, N, lo, hi, who):
+    """``prior`` (None, or dict(scale, kind, p0, p1), each ``[N]`` or ``[S][N]``) against the boxes ``lo`` / ``hi`` ``[S][N]``: the four
+    arrays as ``[S][N]``, or None for a prior that says nothing (None, or every coordinate LINEAR and FLAT): such a call takes the path
+    without one.  Raises what the library refuses."""
+    if prior is None:
+        return None
+    try:
+        scale, kind = (np.ascontiguousarray(np.broadcast_to(np.asarray(prior[k]), (S, N)), dtype=np.int32) for k in ("scale", "kind"))
+        p0, p1 = (np.ascontiguousarray(np.broadcast_to(np.asarray(prior[k], dtype=np.float64), (S, N))) for k in ("p0", "p1"))
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("%s: a prior is dict(scale, kind, p0, p1), each [N] or [S][N]" % who)
+    if not (np.isin(scale, (COORD_LINEAR, COORD_LOG)).all() and np.isin(kind, (PRIOR_FLAT, PRIOR_NORMAL, PRIOR_EXPONENTIAL)).all()):
+        raise ValueError("%s: an unknown scale or kind" % who)
+    nrm, exn, log = kind == PRIOR_NORMAL, kind == PRIOR_EXPONENTIAL, scale == COORD_LOG
+    if not ((np.isfinite(p1) & (p1 > 0))[nrm].all() and (np.isfinite(p0) & (p0 > 0))[exn].all()):
+        raise ValueError("%s: a normal's sd or an exponential's scale is not finite and positive" % who)
+    if not np.isfinite(p0[nrm]).all():
+        raise ValueError("%s: a normal's mean is not finite" % who)
+    if ((hi > 709.0) | (lo < -745.0))[log].any():
+        raise ValueError("%s: the box of a log-scale coordinate leaves [-745, 709]" % who)
+    if not (log.any() or nrm.any() or exn.any()):
+        return None
+    return dict(scale=scale, kind=kind, p0=p0, p1=p1)
+
+
+def ens_natural(scale, y):
+    """The point the engine is handed, elementwise: ``y`` where ``scale`` is LINEAR, ``ens_exp(y)`` where it is LOG."""
+    y = np.asarray(y, dtype=np.float64)
+    return np.where(np.asarray(scale) == COORD_LOG, ens_exp(y), y)
+
+
+def ens_log_prior(kind, p0, p1, lo, hi, y):
+    """The log prior of walkers ``y[...][N]`` (``misti_ens_log_prior``; the arguments broadcast against ``y``): the sum, in increasing k
+    from +0.0, over the coordinates that are neither fixed (``lo == hi``) nor FLAT, of one term each - NORMAL(mean ``p0``, sd ``p1``):
+    ``u = (y - p0) / p1``, ``-0.5 (u u)``; EXPONENTIAL(scale ``p0``): ``-((y - lo) / p0)`` - every operation rounded on its own.
+    Unnormalised.  Entries of ``p0`` / ``p1`` that the kind does not read are not looked at."""
+    y = np.asarray(y, dtype=np.float64)
+    kind, p0, p1, lo, hi = (np.broadcast_to(np.asarray(v), y.shape) for v in (kind, p0, p1, lo, hi))
+    lp = np.zeros(y.shape[:-1])
+    with np.errstate(all="ignore"):
+        for k in range(y.shape[-1]):
+            u = (y[..., k] - p0[..., k]) / p1[..., k]
+            term = np.where(kind[..., k] == PRIOR_NORMAL, -0.5 * (u * u), -((y[..., k] - lo[..., k]) / p0[..., k]))
+            lp = np.where((lo[..., k] != hi[..., k]) & (kind[..., k] != PRIOR_FLAT), lp + term, lp)
+    return lp
+
+
+def ens_decision_prior(z, d, llk_old, llk_new, T, lp_old, lp_new, u_acc):
+    """``ens_decision`` with a prior (``misti_ens_accept_prior``): the same, with ``e = (llk_new - llk_old) / T + (lp_new - lp_old)`` -
+    the prior is not tempered."""
+    z, old, new, T, lo_, ln_, u = (np.asarray(v, dtype=np.float64) for v in (z, llk_old, llk_new, T, lp_old, lp_new, u_acc))
+    d = np.asarray(d, dtype=np.int64)
+    shape = np.broadcast(z, d, old, new, T, lo_, ln_, u).shape
+    z, d, old, new, T, lo_, ln_, u = (np.broadcast_to(v, shape) for v in (z, d, old, new, T, lo_, ln_, u))
+    g = np.ones(shape)
+    with np.errstate(all="ignore"):
+        for k in range(int(d.max()) if d.size else 0):
+            g = np.where(k < d, g * z, g)
+        p = g * ens_exp((new - old) / T + (ln_ - lo_))
+        take = u < p
+    return np.isfinite(new) & (~np.isfinite(old) | take)
+
+
+def ensemble_prior_rule(fun_batch, init, lo, hi, n_step, prior, thin=1, temperature=1.0, a=2.0, seed=0, ids=None):
+    """The rule of ``misti_ensemble_sample_prior``, operation for operation: ``ensemble_rule`` with a sampling coordinate and a prior per
+    coordinate.  ``prior``: None, or dict(scale, kind, p0, p1) (``prior_spec``), each ``[N]`` (one for all searches) or ``[S][N]``.
+
+    Everything the caller sees is in the sampling coordinate y: ``init``, the box ``[lo, hi]`` (finite), the stretch, the test against
+    the box, ``chain`` and ``last``.  Only the point handed to ``fun_batch`` changes: its coordinate k is ``y_k`` (LINEAR) or
+    ``ens_exp(y_k)`` (LOG) - ``ens_natural`` -, the initial ensemble's and a fitted split's alike; a fixed coordinate is ``lo``, or
+    ``ens_exp(lo)``, exactly.  The decision on an evaluated proposal is ``ens_decision_prior`` with ``lp = ens_log_prior`` of the old
+    walker and of the proposal: ``e = (llk_new - llk_old) / T + (lp_new - lp_old)``.  The prior is NOT tempered.  The draws, the blocks,
+    the halves, the rejection in advance and the counters are ``ensemble_rule``'s.
+    A prior that says nothing (None, or every coordinate LINEAR and FLAT) IS ``ensemble_rule``: the existing lines, not the new formula
+    with a zero added.  Returns what ``ensemble_rule`` returns."""
+    return _ensemble_rule("ensemble_prior_rule", fun_batch, init, lo, hi, n_step, prior, thin, temperature, a, seed, ids)
+
+
+def to_sampling(x, prior, box=None):
+    """Natural values ``x[...][N]`` as sampling coordinates: ``numpy.log`` of the LOG coordinates.  ``box`` (``(lo, hi)`` in sampling
+    coordinates): the result is clipped into it - a bound whose logarithm lands one ulp outside stays a point of the box.  Host only;
+    never part of a rule's bits."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        y = np.where(np.asarray(prior["scale"]) == COORD_LOG, np.log(x), x)
+    return y if box is None else np.clip(y, np.asarray(box[0], dtype=np.float64), np.asarray(box[1], dtype=np.float64))
+
+
+def from_sampling(y, prior):
+    """Sampling coordinates ``y[...][N]`` in natural units: ``numpy.exp`` of the LOG coordinates.  Host only, for reports."""
+    y = np.asarray(y, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.where(np.asarray(prior["scale"]) == COORD_LOG, np.exp(y), y)
 
 
 # ------------------------------------------------------------------------------------------- tempered ensemble MCMC ----
@@ -1908,6 +2054,10 @@ def tempered_reduction(chain_llh, ladder, burn=0):
 
 
 def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None):
+    return _tempered_rule("tempered_rule", fun_batch, init, lo, hi, ladder, n_step, None, thin, swap_every, burn, a, seed, ids)
+
+
+def _tempered_rule(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids):
     """The rule of ``misti_tempered_sample``, operation for operation: parallel tempering (replica exchange) over ``ensemble_rule``.
     Fit s has L rungs (1 ... ``PT_MAX_RUNGS``) at the temperatures ``ladder[s][0] < ladder[s][1] < ...`` (finite, positive; ``ladder``
     is ``[L]`` or ``[S][L]``); rung l is an ensemble of W walkers ``init[s][l][W][N]`` inside the fit's box whose target is
@@ -1932,34 +2082,37 @@ def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1,
     NORMALISED uniform prior on the box.  The piece below ``beta_{L-1}`` (down to the prior, beta = 0) is NOT included.
     Returns dict(chain[S][K][W][N], chain_llh[S][L][K][W], accepted[S][L][W] int32 (stretch moves), swap_proposed[S][L-1] and
     swap_accepted[S][L-1] int32, last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S], n_points: the PROPOSALS handed to
-    ``fun_batch``)."""
+    ``fun_batch``).
+
+    ``prior`` (``tempered_prior_rule``; None here): see there - the point handed to ``fun_batch`` and the ``e`` of a rung's decision
+    change, the swaps do not."""
     x = np.array(init, dtype=np.float64)
     if x.ndim != 4:
-        raise ValueError("tempered_rule: init must be [S][L][W][N]")
+        raise ValueError(who + ": init must be [S][L][W][N]")
     S, L, W, N = x.shape
     H = W // 2
     n_step, thin, swap_every, burn, a = int(n_step), int(thin), int(swap_every), int(burn), float(a)
     if not 1 <= L <= PT_MAX_RUNGS:
-        raise ValueError("tempered_rule: 1 ... %d rungs" % PT_MAX_RUNGS)
+        raise ValueError(who + ": 1 ... %d rungs" % PT_MAX_RUNGS)
     lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=float), (S, N)))
     hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=float), (S, N)))
     T = np.ascontiguousarray(np.broadcast_to(np.asarray(ladder, dtype=float), (S, L)))
     if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or n_step < 0 or thin < 1 or not (np.isfinite(a) and a > 1.0):
-        raise ValueError("tempered_rule: W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
+        raise ValueError(who + ": W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
     if not (np.isfinite(T) & (T > 0)).all() or not (T[:, 1:] > T[:, :-1]).all():
-        raise ValueError("tempered_rule: a ladder must be finite, positive and strictly increasing")
+        raise ValueError(who + ": a ladder must be finite, positive and strictly increasing")
     K = n_step // thin
     if swap_every < 0 or (K and not 0 <= burn < K):
-        raise ValueError("tempered_rule: swap_every >= 0, burn 0 ... K - 1")
+        raise ValueError(who + ": swap_every >= 0, burn 0 ... K - 1")
     with np.errstate(over="ignore", invalid="ignore"):
         usable = np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(hi - lo).all()
     if not usable:
-        raise ValueError("tempered_rule: the box must be finite with lo <= hi")
+        raise ValueError(who + ": the box must be finite with lo <= hi")
     fixed = lo == hi
     if S and fixed.all(axis=1).any():
-        raise ValueError("tempered_rule: every coordinate of a box is fixed")
+        raise ValueError(who + ": every coordinate of a box is fixed")
     if not (np.isfinite(x).all() and (x >= lo[:, None, None, :]).all() and (x <= hi[:, None, None, :]).all()):
-        raise ValueError("tempered_rule: every walker of init must be finite and inside its box")
+        raise ValueError(who + ": every walker of init must be finite and inside its box")
     ids = np.arange(S) if ids is None else np.asarray(ids).reshape(S)
     am1 = a - 1.0
     # the S L rungs as searches: everything but the temperature and the block is the fit's
@@ -1968,8 +2121,12 @@ def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1,
     fit = np.repeat(np.arange(S), L)
     glo, ghi, gfixed, gT = lo[fit], hi[fit], fixed[fit], T.reshape(G)
     d = (~gfixed).sum(axis=1) - 1
+    pr = _prior_arrays(prior, S, N, lo, hi, who)
+    gpr = None if pr is None else {k: v[fit][:, None] for k, v in pr.items()}                 # [G][1][N]
 
     def values(X, s_of):
+        if pr is not None:
+            X = ens_natural(pr["scale"][s_of], X)
         f = np.asarray(fun_batch(X, s_of), dtype=float).reshape(-1)
         llk = -np.where(np.isnan(f), np.inf, f)
         return np.where(np.isfinite(llk), llk, -np.inf)
@@ -2003,7 +2160,11 @@ def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1,
             if inside.any():
                 new[inside] = values(y[inside], np.broadcast_to(fidx, (G, H))[inside])
                 n_points += int(inside.sum())
-            take = inside & ens_decision(z, d[:, None], llh[:, mine], new, gT[:, None], u_acc)
+            if pr is None:
+                take = inside & ens_decision(z, d[:, None], llh[:, mine], new, gT[:, None], u_acc)
+            else:
+                lp_old, lp_new = (ens_log_prior(gpr["kind"], gpr["p0"], gpr["p1"], glo[:, None], ghi[:, None], v) for v in (xi, y))
+                take = inside & ens_decision_prior(z, d[:, None], llh[:, mine], new, gT[:, None], lp_old, lp_new, u_acc)
             x[:, mine] = np.where(take[:, :, None], y, xi)
             llh[:, mine] = np.where(take, new, llh[:, mine])
             accepted[:, mine] += take
@@ -2027,12 +2188,23 @@ def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1,
                 last=x.reshape(S, L, W, N), last_llh=llh.reshape(S, L, W), rung_llh=rung_llh, logz=logz, n_points=int(n_points))
 
 
-def _mcmc_call(engine, summary, n_step, thin, ladder=None, swap_every=1):
+def tempered_prior_rule(fun_batch, init, lo, hi, ladder, n_step, prior, thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None):
+    """The rule of ``misti_tempered_sample_prior``, operation for operation: ``tempered_rule`` whose rungs move as the searches of
+    ``ensemble_prior_rule`` move (``prior`` per fit: ``[N]`` or ``[S][N]``).  Rung l targets ``prior(y) exp(llk / T_l)`` - the prior is
+    not tempered -, so it cancels in a swap: ``pt_swap_decision`` decides as before.  ``logz`` is the same trapezoid rule, now for
+    ``Z(beta)`` = the integral of ``exp(beta llk)`` against the NORMALISED prior on the box, in sampling coordinates.  One rung is
+    ``ensemble_prior_rule``; a prior that says nothing is ``tempered_rule``.  Returns what ``tempered_rule`` returns."""
+    return _tempered_rule("tempered_prior_rule", fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids)
+
+
+def _mcmc_call(engine, summary, n_step, thin, ladder=None, swap_every=1, prior=None):
     """``Engine.ensemble_sample``, or with ``summary`` (a dict of ``burn``, ``probs``, ``max_lag``, ``keep_chain``, ``c``; ``burn``
     defaults to half the kept steps) ``Engine.ensemble_posterior``.  With ``ladder`` (``[L]`` or per ensemble ``[S][L]``):
     ``Engine.tempered_sample`` on it - every rung starts from the ensemble's ``init``, ``temperature`` is not looked at (the ladder's
-    first entry is the cold rung's), ``rung_llh`` / ``logz`` drop the summary's ``burn`` (without a summary: half the kept steps)."""
+    first entry is the cold rung's), ``rung_llh`` / ``logz`` drop the summary's ``burn`` (without a summary: half the kept steps).
+    ``prior`` (``prior_spec``; None: none) is passed on."""
     half = (int(n_step) // int(thin)) // 2
+    extra = {} if prior is None else dict(prior=prior)                  # without one the existing calls, argument for argument
     if ladder is not None:
         L = np.asarray(ladder).shape[-1]
         opts = None if summary is None else dict(summary)
@@ -2040,17 +2212,17 @@ def _mcmc_call(engine, summary, n_step, thin, ladder=None, swap_every=1):
         def tempered(x0, *a, temperature=None, **kw):
             x0 = np.asarray(x0, dtype=float)
             return engine.tempered_sample(np.ascontiguousarray(np.broadcast_to(x0[:, None], (x0.shape[0], L) + x0.shape[1:])), *a, ladder=ladder,
-                                          swap_every=swap_every, burn=half if opts is None else opts.setdefault("burn", half), post=opts, **kw)
+                                          swap_every=swap_every, burn=half if opts is None else opts.setdefault("burn", half), post=opts, **extra, **kw)
         return tempered
     if summary is None:
-        return engine.ensemble_sample
+        return lambda *a, **kw: engine.ensemble_sample(*a, **kw, **extra)
     opts = dict(summary)
     opts.setdefault("burn", half)
-    return lambda *a, **kw: engine.ensemble_posterior(*a, **kw, **opts)
+    return lambda *a, **kw: engine.ensemble_posterior(*a, **kw, **opts, **extra)
 
 
 def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None,
-                           ladder=None, swap_every=1):
+                           ladder=None, swap_every=1, prior=None):
     """``bootstrap_profile_de``'s sampler: per (row, split) pair ONE ensemble inside ``box`` (``(lo, hi)``, each ``[n_param]``, finite), all
     R x P ensembles in ONE ``misti_ensemble_sample`` call - every half-step one dense engine batch.  ``init`` is ``[W][n_param]`` (every
     pair starts from it) or ``[R][P][W][n_param]``.  The stream id of an ensemble is its split's index: the rows of a bootstrap share
@@ -2059,6 +2231,8 @@ def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=10
     ``max_lag``, ``keep_chain``, ``c``): the call goes through ``misti_ensemble_posterior`` and the chain stays on the device.
     ``ladder`` (``[L]`` temperatures, strictly increasing, in place of ``temperature``) with ``swap_every``: every pair is a tempered
     ladder of L ensembles started from ``init`` and the call goes through ``misti_tempered_sample`` (``Engine.tempered_sample``).
+    ``prior`` (``prior_spec``, one for all pairs): sampling coordinates and priors per coordinate - ``init``, ``box`` and the result
+    are then in sampling coordinates (``to_sampling`` / ``from_sampling``).
     Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``, ``Engine.tempered_sample``) returns with the leading axis
     reshaped to ``[R][P]``."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
@@ -2067,26 +2241,27 @@ def bootstrap_profile_mcmc(engine, split_values, jsfs_rows, init, box, n_step=10
     r_of, j_of = (v.ravel() for v in np.meshgrid(np.arange(R), np.arange(Q), indexing="ij"))
     x0 = np.asarray(init, dtype=float)
     x0 = np.broadcast_to(x0, (R, Q) + x0.shape[-2:]).reshape((R * Q,) + x0.shape[-2:])
-    out = _mcmc_call(engine, summary, n_step, thin, ladder, swap_every)(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin,
+    out = _mcmc_call(engine, summary, n_step, thin, ladder, swap_every, prior)(x0, r_of.astype(np.int32), rows, box, split_times=splits[j_of], n_step=n_step, thin=thin,
                                                     temperature=temperature, a=a, seed=seed, ids=j_of.astype(np.uint64))
     return {k: (v.reshape(R, Q, *v.shape[1:]) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
 
 
 def split_fit_mcmc(engine, jsfs_rows, init, box, band_bounds=None, pulse_times=None, n_step=100, thin=1, temperature=1.0, a=2.0, seed=0, summary=None,
-                   ladder=None, swap_every=1):
+                   ladder=None, swap_every=1, prior=None):
     """``split_fit_de``'s sampler: per row ONE ensemble over (optimised parameters, split) inside ``box`` (``(lo, hi)``, each
     ``[n_param + 1]``, finite, the split last), all R ensembles in ONE ``misti_ensemble_sample`` call.  ``init`` is ``[W][n_param + 1]``
     (every row starts from it) or ``[R][W][n_param + 1]``; every row draws from stream 0 (the rows of a bootstrap share their random
     numbers - only the data differ).  ``band_bounds`` / ``pulse_times`` apply to every ensemble.
     ``summary``: None, or a dict of ``Engine.ensemble_posterior``'s options (``burn`` - default half the kept steps -, ``probs``,
     ``max_lag``, ``keep_chain``, ``c``): the call goes through ``misti_ensemble_posterior`` and the chain stays on the device.
-    ``ladder`` / ``swap_every`` as in ``bootstrap_profile_mcmc``: ``misti_tempered_sample``.
+    ``ladder`` / ``swap_every`` / ``prior`` as in ``bootstrap_profile_mcmc``: ``misti_tempered_sample``; the prior covers the split
+    (the last coordinate) too.
     Returns what ``Engine.ensemble_sample`` (``Engine.ensemble_posterior``, ``Engine.tempered_sample``) returns (leading axis: the row)."""
     rows = np.asarray(jsfs_rows, dtype=float).reshape(-1, 8)
     R = rows.shape[0]
     x0 = np.asarray(init, dtype=float)
     x0 = np.ascontiguousarray(np.broadcast_to(x0, (R,) + x0.shape[-2:]))
     tile = lambda v, shape: None if v is None else np.repeat(np.asarray(v, dtype=np.int32).reshape(shape), R, axis=0)
-    return _mcmc_call(engine, summary, n_step, thin, ladder, swap_every)(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
+    return _mcmc_call(engine, summary, n_step, thin, ladder, swap_every, prior)(x0, np.arange(R, dtype=np.int32), rows, box, fit_split=True, band_bounds=tile(band_bounds, (1, -1, 2)),
                                                      pulse_times=tile(pulse_times, (1, -1)), n_step=n_step, thin=thin, temperature=temperature,
                                                      a=a, seed=seed, ids=np.zeros(R, dtype=np.uint64))

@@ -209,12 +209,14 @@ def run_de_compare(n_rows=256, pop=16, gens=40, hops=(10, 30), seed=0, device=0,
     return lines
 
 
-def run_mcmc_compare(n_rows=256, walkers=16, steps=40, pop=16, gens=40, seed=0, device=0, out=None, repeats=5):
+def run_mcmc_compare(n_rows=256, walkers=16, steps=40, pop=16, gens=40, seed=0, device=0, out=None, repeats=5, log_prior=False):
     """`python -m misti_amd.search_bench --mcmc W STEPS`: config 3's model, one ensemble per bootstrap row (misti_ensemble_sample: every
     half-step one dense batch of rows x W / 2 slots) beside the differential-evolution leg of run_de_compare on the same rows and box -
     the two in turns in one process, `repeats` times after a warm-up call each.  A half-step is an engine batch like a DE generation,
     so what to compare is the time per submitted point.  Reports per leg the median and the least seconds of a call, the points handed to
-    the engine and, for the sampler, the acceptance fraction.  One JSON line per leg."""
+    the engine and, for the sampler, the acceptance fraction.  One JSON line per leg.  `log_prior` (`--mcmc-log-prior`): a third leg, the
+    sampler with every rate on the log scale under a normal prior (misti_ensemble_sample_prior) centred on the middle of the box of
+    logarithms with a quarter of its width as sd, from the same ensembles mapped with to_sampling."""
     import random
     from . import io as mio, synth, workloads
     from .engine import Engine, truth_spectrum
@@ -234,6 +236,15 @@ def run_mcmc_compare(n_rows=256, walkers=16, steps=40, pop=16, gens=40, seed=0, 
         mc = lambda: eng.ensemble_sample(init, rows, table, box, split_times=splits, n_step=steps, seed=seed, ids=np.zeros(R, dtype=np.uint64))
         mc()
         legs = [("de pop=%d gens=%d seed=%d" % (pop, gens, seed), de), ("mcmc walkers=%d steps=%d seed=%d" % (walkers, steps, seed), mc)]
+        if log_prior:
+            from .optimize import prior_spec, to_sampling
+            N = init.shape[2]
+            ybox = (np.log(box[0]), np.log(box[1]))
+            prior = prior_spec(N, log=range(N), normal={k: (0.5 * (ybox[0][k] + ybox[1][k]), 0.25 * (ybox[1][k] - ybox[0][k])) for k in range(N)})
+            yinit = to_sampling(init, prior, ybox)
+            mp = lambda: eng.ensemble_sample(yinit, rows, table, ybox, split_times=splits, n_step=steps, seed=seed, ids=np.zeros(R, dtype=np.uint64), prior=prior)
+            mp()
+            legs.append(("mcmc log scale, normal prior walkers=%d steps=%d seed=%d" % (walkers, steps, seed), mp))
         times = {name: [] for name, _ in legs}
         last = {}
         for _ in range(repeats):
@@ -273,9 +284,10 @@ if __name__ == "__main__":
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--mcmc", type=int, nargs=2, default=None, metavar=("W", "STEPS"), help="the sampler's leg beside the DE leg: one ensemble of W walkers per row, STEPS steps")
+    ap.add_argument("--mcmc-log-prior", action="store_true", help="with --mcmc: a third leg, the sampler with every rate on the log scale under a normal prior")
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     if a.mcmc:
-        run_mcmc_compare(a.rows, a.mcmc[0], a.mcmc[1], a.pop, a.gens, a.seed, a.device, a.out, a.repeats)
+        run_mcmc_compare(a.rows, a.mcmc[0], a.mcmc[1], a.pop, a.gens, a.seed, a.device, a.out, a.repeats, a.mcmc_log_prior)
         sys.exit(0)
     run_de_compare(a.rows, a.pop, a.gens, tuple(a.hops), a.seed, a.device, a.out)
