@@ -1207,7 +1207,7 @@ RowsArgs rows_args(const misti_pt_t& q) {
 }
 
 // The checks the three doors share.  Each door calls them where its header's order of refusals puts them (nm_check, de_check,
-// ens_check); `noun` is what the door calls its n_start.
+// sampler_check); `noun` is what the door calls its n_start.
 int check_n_box(const RowsArgs& a, const char* noun) {
     if (a.n_box != 1 && a.n_box != a.n_start)
         return fail(MISTI_E_ARG, "n_box must be 1 or n_start (got %lld for %lld %s)", (long long)a.n_box, (long long)a.n_start, noun);
@@ -1755,7 +1755,7 @@ void post_fill(misti::PostArgs& a, int64_t S, int64_t K, int32_t W, int32_t N, c
     a.sel = misti::post_select(a.n * W, p.n_prob, p.probs);
 }
 
-// The device side of the summaries of a sampler that keeps its chain (ens_run, pt_run): carved behind everything the sampler carves,
+// The device side of the summaries of a sampler that keeps its chain (sampler_run): carved behind everything the sampler carves,
 // so its layout does not move; an output the caller does not ask for is not carved.  back(): the summaries to post's host buffers.
 void post_carve(misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, int N, Carver<double>& f, Carver<int32_t>& i) {
     const size_t SN = S * (size_t)N, NP = (size_t)p.n_prob;
@@ -1849,198 +1849,130 @@ struct PriorProblem {
     }
 };
 
-// ---- ensemble MCMC per search (misti_ens.hip) ------------------------------------------------------------------------------------
-// The arguments of misti_ensemble_sample, before the first HIP call, in the header's order.  Leaves the number of coordinates in N
-// and whether every split time is an integer in `whole`.  `keep`: the chain is kept on the device whether it is asked for or not
-// (misti_ensemble_posterior), so its limit applies.
-int ens_check(const misti_ctx* c, const misti_ens_t& q, int& N, bool& whole, bool keep = false, const misti_prior_t* prior = nullptr) {
-    const RowsArgs a = rows_args(q);
-    if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of searches");
-    if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.temperature || !q.last || !q.last_llh || (a.per_start() && !q.split_times))
-        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / temperature / last / last_llh%s is NULL", a.per_start() ? " / split_times" : "");
-    if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
+// ---- the samplers: ensemble MCMC per search (misti_ens.hip) and its tempered form per fit (misti_pt.hip) ---------------------------
+// What a sampler call is: the rows problem, n_rung ensembles of `walkers` walkers per start at temperatures of their own, the steps,
+// and where the results go.  misti_ensemble_sample is the call of ONE rung (EnsState::L = 1) without swap rounds and without the
+// reduction.  A per-sampler field is added HERE, to sampler_check and sampler_run below and to EnsState (misti_device.h) - nowhere
+// else.  The two public descriptors lay these fields out differently: one sampler_args() each.
+struct SamplerArgs {
+    RowsArgs rows;
+    const double* init;              // [n_start][n_rung][walkers][N]
+    int32_t walkers, n_rung;         // n_rung: 1 at the plain door
+    bool tempered;                   // misti_tempered_sample: a ladder, swap rounds and the reduction - also where n_rung == 1
+    int32_t n_temp;                  // 1 or n_start: temp is [n_temp][n_rung]
+    const double* temp;
+    int32_t n_step, thin;
+    double a;
+    uint64_t seed;
+    int32_t swap_every, burn;        // the tempered door's; 0 at the plain door
+    bool keep_x, keep_llh;           // the chain of the cold rung / of every rung's values is kept on the device
+    double *chain, *chain_llh;       // what is copied back: NULL, not copied.  rung_llh, logz and the swap counters: NULL at the plain door
+    int32_t *accepted, *swap_proposed, *swap_accepted;
+    double *last, *last_llh, *rung_llh, *logz;
+    int64_t* n_points;
+    const char *noun, *per, *kept;   // the words the doors' texts differ in: "searches" | "fits"; what the limits count; "device " chain
+};
+// the plain door keeps both chains or none: where the caller or a summary (`post`) asks for one
+SamplerArgs sampler_args(const misti_ens_t& q, const misti_ens_post_t* post) {
+    const bool keep = q.chain || q.chain_llh || post;
+    return {rows_args(q), q.init, q.walkers, 1, false, q.n_temp, q.temperature, q.n_step, q.thin, q.a, q.seed, 0, 0, keep, keep,
+            q.chain, q.chain_llh, q.accepted, nullptr, nullptr, q.last, q.last_llh, nullptr, nullptr, q.n_points,
+            "searches", "searches x walkers", post ? "device " : ""};
+}
+// the tempered door always keeps the values of every rung (the reduction reads them), the cold rung's coordinates where they are wanted
+SamplerArgs sampler_args(const misti_pt_t& q, const misti_ens_post_t* post) {
+    return {rows_args(q), q.init, q.walkers, q.n_rung, true, q.n_ladder, q.ladder, q.n_step, q.thin, q.a, q.seed, q.swap_every, q.burn,
+            q.chain || post, true, q.chain, q.chain_llh, q.accepted, q.swap_proposed, q.swap_accepted, q.last, q.last_llh, q.rung_llh, q.logz,
+            q.n_points, "fits", "fits x rungs x walkers", ""};
+}
+
+// The arguments of a sampler call, before the first HIP call, in the order of its door's header.  The two orders are one order: where
+// misti_ensemble_sample has n_temp and temperature, misti_tempered_sample has n_rung, n_ladder, the ladder, swap_every and burn.  Leaves
+// the number of coordinates in N and whether every split time is an integer in `whole`.
+int sampler_check(const misti_ctx* c, const SamplerArgs& q, const misti_prior_t* prior, int& N, bool& whole) {
+    const RowsArgs& a = q.rows;
+    const bool pt = q.tempered;
+    if (a.n_start < 0) return fail(MISTI_E_ARG, "negative number of %s", q.noun);
+    if (!q.init || !a.rows || !a.jsfs || !a.box_lo || !a.box_hi || !q.temp || !q.last || !q.last_llh || (pt && (!q.rung_llh || !q.logz)) || (a.per_start() && !a.split_times))
+        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / %s / last / last_llh%s%s is NULL", pt ? "ladder" : "temperature",
+                    pt ? " / rung_llh / logz" : "", a.per_start() ? " / split_times" : "");
+    if (a.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)a.n_rep);
     if (q.walkers < 4 || (q.walkers & 1)) return fail(MISTI_E_ARG, "walkers must be even and >= 4 (got %d)", (int)q.walkers);
     if (q.walkers > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "walkers = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)q.walkers, MISTI_ENS_MAX_WALKERS);
     if (q.n_step < 0) return fail(MISTI_E_ARG, "n_step must not be negative");
     if (q.thin < 1) return fail(MISTI_E_ARG, "thin must be >= 1");
     if (!std::isfinite(q.a) || !(q.a > 1.0)) return fail(MISTI_E_ARG, "a must be finite and > 1 (got %g)", q.a);
-    if (q.n_temp != 1 && q.n_temp != q.n_start) return fail(MISTI_E_ARG, "n_temp must be 1 or n_start (got %d for %lld searches)", (int)q.n_temp, (long long)q.n_start);
+    // the temperatures: n_temp / temperature | n_rung / n_ladder / ladder / swap_every / burn
+    if (pt && q.n_rung < 1) return fail(MISTI_E_ARG, "n_rung must be >= 1 (got %d)", (int)q.n_rung);
+    if (pt && q.n_rung > MISTI_PT_MAX_RUNGS) return fail(MISTI_E_LIMIT, "n_rung = %d exceeds MISTI_PT_MAX_RUNGS = %d", (int)q.n_rung, MISTI_PT_MAX_RUNGS);
+    if (q.n_temp != 1 && q.n_temp != a.n_start)
+        return fail(MISTI_E_ARG, "%s must be 1 or n_start (got %d for %lld %s)", pt ? "n_ladder" : "n_temp", (int)q.n_temp, (long long)a.n_start, q.noun);
     for (int64_t s = 0; s < q.n_temp; ++s)
-        if (!std::isfinite(q.temperature[s]) || !(q.temperature[s] > 0.0))
-            return fail(MISTI_E_ARG, "temperature[%lld] = %g is not finite and positive", (long long)s, q.temperature[s]);
-    if (int r = check_n_box(a, "searches")) return r;
-    if (int r = check_prior_shape(prior, q.n_start, "searches")) return r;
-    if (int r = check_rows(a, whole)) return r;
-    if (int r = check_limits(c, a, q.walkers, "searches x walkers", N)) return r;
-    if ((q.chain || q.chain_llh || keep) && q.n_start > 0 && (int64_t)(q.n_step / q.thin) > INT32_MAX / 8 / N / q.walkers / q.n_start)
-        return fail(MISTI_E_LIMIT, "the %schain of %lld searches x %d kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
-                    keep ? "device " : "", (long long)q.n_start, (int)(q.n_step / q.thin), (int)q.walkers, N);
-    for (int64_t b = 0; b < q.n_box; ++b) {
-        if (int r = check_box(a, N, b, "the sampler's prior is uniform on a finite box")) return r;
-        int n_free = 0;
-        for (int k = 0; k < N; ++k) n_free += q.box_lo[b * N + k] != q.box_hi[b * N + k] ? 1 : 0;
-        if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
-    }
-    if (int r = check_prior(prior, a, N)) return r;
-    for (int64_t s = 0; s < q.n_start; ++s)
-        for (int i = 0; i < q.walkers; ++i)
-            for (int k = 0; k < N; ++k) {
-                const double v = q.init[(s * q.walkers + i) * N + k];
-                const int64_t o = (q.n_box > 1 ? s : 0) * N + k;
-                if (!std::isfinite(v)) return fail(MISTI_E_ARG, "init[%lld][%d][%d] is not finite", (long long)s, i, k);
-                if (v < q.box_lo[o] || v > q.box_hi[o])
-                    return fail(MISTI_E_ARG, "init[%lld][%d][%d] = %g is outside its box [%g, %g]", (long long)s, i, k, v, q.box_lo[o], q.box_hi[o]);
-            }
-    return 0;
-}
-
-// A checked call with n_start >= 1.  One batch record of n_start x walkers slots serves the initial ensemble and every half-step
-// (which fills the first half of it); the state and the chain lie in the search buffers of the context.  Nothing is read back before
-// the end.  With `post` (checked: post_check) the chain is kept whether it is asked for or not, the summary kernels run on it where
-// it lies, and the summaries come back with the rest; the series workspace and the summaries' device side are carved with the chain.
-int ens_run(misti_ctx* c, const misti_ens_t& q, int N, bool whole, const misti_ens_post_t* post = nullptr, const misti_prior_t* prior = nullptr) {
-    using namespace misti;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t S = (size_t)q.n_start, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp;
-    const size_t K = (q.chain || q.chain_llh || post) ? (size_t)(q.n_step / q.thin) : 0;
-    PostArgs pa{};
-    if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
-    RowsProblem rows(c, rows_args(q), N, whole);
-    PriorProblem pri(prior, N, S * H);
-    EnsState st{};
-    st.S = q.n_start; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
-    st.temp_per_start = q.n_temp > 1 ? 1 : 0;
-    st.n_keep = (int64_t)K;
-    double *llk = nullptr, *d_init = nullptr, *d_temp = nullptr, *d_points = nullptr;
-    auto layout = [&](Carver<double>& f, Carver<int32_t>& i) {
-        st.b.pts = f.take(M * N); st.x = f.take(M * N); st.llh = f.take(M); st.b.split = f.take(M); llk = f.take(M);
-        st.z = f.take(S * H); st.u_acc = f.take(S * H);
-        d_init = f.take(M * N); d_temp = f.take(NT);
-        d_points = f.take(S);                              // int64 per search: 8-byte words of the double buffer
-        if (K) { st.chain = f.take(S * K * W * (size_t)N); st.chain_llh = f.take(S * K * W); }
-        st.accepted = i.take(M); st.submitted = i.take(M);
-        rows.layout(f, i, &st.b, &M, 1, M);
-        pri.layout(f, i);
-        if (post) post_carve(pa, *post, S, N, f, i);
-    };
-    if (int r = carve(c, "search", layout)) return r;
-    rows.fill(st.src);
-    pri.fill(st.prior);
-    st.temp = d_temp;
-    st.points = reinterpret_cast<long long*>(d_points);
-    hipStream_t sm = c->stream;
-    HIP_TRY(hipMemcpyAsync(d_init, q.init, M * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_temp, q.temperature, NT * sizeof(double), hipMemcpyHostToDevice, sm));
-    if (int r = rows.upload(c)) return r;
-    if (int r = pri.upload(sm)) return r;
-    c->nm_iterations = c->nm_slots = c->nm_spec_iterations = 0;
-    HIP_TRY(launch_ens_init(st, d_init, sm));
-    if (int r = rows.eval(c, st.b, (int64_t)M, llk)) return r;
-    HIP_TRY(launch_ens_accept(st, 0, -1, llk, sm));
-    for (int64_t step = 1; step <= q.n_step; ++step)
-        for (int half = 0; half < 2; ++half) {
-            HIP_TRY(launch_ens_propose(st, step, half, sm));
-            if (int r = rows.eval(c, st.b, (int64_t)(S * H), llk)) return r;
-            HIP_TRY(launch_ens_accept(st, step, half, llk, sm));
-        }
-    c->nm_iterations = 2 * (int64_t)q.n_step;
-    c->nm_slots = 2 * (int64_t)q.n_step * (int64_t)(S * H);
-    HIP_TRY(launch_ens_result(st, sm));
-    if (post) {
-        pa.chain = st.chain; pa.chain_llh = st.chain_llh;
-        HIP_TRY(launch_post(pa, sm));
-        if (int r = post_back(pa, *post, S, N, sm)) return r;
-    }
-    HIP_TRY(hipMemcpyAsync(q.last, st.x, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(q.last_llh, st.llh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
-    if (q.accepted) HIP_TRY(hipMemcpyAsync(q.accepted, st.accepted, M * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (q.chain && K) HIP_TRY(hipMemcpyAsync(q.chain, st.chain, S * K * W * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    if (q.chain_llh && K) HIP_TRY(hipMemcpyAsync(q.chain_llh, st.chain_llh, S * K * W * sizeof(double), hipMemcpyDeviceToHost, sm));
-    std::vector<int64_t> per_search;
-    if (q.n_points) {
-        per_search.resize(S);
-        HIP_TRY(hipMemcpyAsync(per_search.data(), d_points, S * sizeof(int64_t), hipMemcpyDeviceToHost, sm));
-    }
-    HIP_TRY(hipStreamSynchronize(sm));
-    if (q.n_points) {
-        int64_t n = 0;
-        for (int64_t v : per_search) n += v;
-        *q.n_points = n;
-    }
-    return 0;
-}
-
-// ---- tempered ensemble MCMC per fit (misti_pt.hip) -----------------------------------------------------------------------------------
-// The arguments of misti_tempered_sample, before the first HIP call, in the header's order: ens_check's, with the ladder where the
-// temperature stands and n_start x n_rung x walkers where the limits count.
-int pt_check(const misti_ctx* c, const misti_pt_t& q, int& N, bool& whole, const misti_prior_t* prior = nullptr) {
-    const RowsArgs a = rows_args(q);
-    if (q.n_start < 0) return fail(MISTI_E_ARG, "negative number of fits");
-    if (!q.init || !q.rows || !q.jsfs || !q.box_lo || !q.box_hi || !q.ladder || !q.last || !q.last_llh || !q.rung_llh || !q.logz || (a.per_start() && !q.split_times))
-        return fail(MISTI_E_ARG, "init / rows / jsfs / box_lo / box_hi / ladder / last / last_llh / rung_llh / logz%s is NULL", a.per_start() ? " / split_times" : "");
-    if (q.n_rep < 1) return fail(MISTI_E_ARG, "n_rep must be >= 1 (got %lld)", (long long)q.n_rep);
-    if (q.walkers < 4 || (q.walkers & 1)) return fail(MISTI_E_ARG, "walkers must be even and >= 4 (got %d)", (int)q.walkers);
-    if (q.walkers > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "walkers = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)q.walkers, MISTI_ENS_MAX_WALKERS);
-    if (q.n_step < 0) return fail(MISTI_E_ARG, "n_step must not be negative");
-    if (q.thin < 1) return fail(MISTI_E_ARG, "thin must be >= 1");
-    if (!std::isfinite(q.a) || !(q.a > 1.0)) return fail(MISTI_E_ARG, "a must be finite and > 1 (got %g)", q.a);
-    if (q.n_rung < 1) return fail(MISTI_E_ARG, "n_rung must be >= 1 (got %d)", (int)q.n_rung);
-    if (q.n_rung > MISTI_PT_MAX_RUNGS) return fail(MISTI_E_LIMIT, "n_rung = %d exceeds MISTI_PT_MAX_RUNGS = %d", (int)q.n_rung, MISTI_PT_MAX_RUNGS);
-    if (q.n_ladder != 1 && q.n_ladder != q.n_start) return fail(MISTI_E_ARG, "n_ladder must be 1 or n_start (got %d for %lld fits)", (int)q.n_ladder, (long long)q.n_start);
-    for (int64_t s = 0; s < q.n_ladder; ++s)
         for (int l = 0; l < q.n_rung; ++l) {
-            const double T = q.ladder[s * q.n_rung + l];
-            if (!std::isfinite(T) || !(T > 0.0)) return fail(MISTI_E_ARG, "ladder[%lld][%d] = %g is not finite and positive", (long long)s, l, T);
-            if (l && !(T > q.ladder[s * q.n_rung + l - 1]))
+            const double T = q.temp[s * q.n_rung + l];
+            if (!std::isfinite(T) || !(T > 0.0))
+                return pt ? fail(MISTI_E_ARG, "ladder[%lld][%d] = %g is not finite and positive", (long long)s, l, T)
+                          : fail(MISTI_E_ARG, "temperature[%lld] = %g is not finite and positive", (long long)s, T);
+            if (l && !(T > q.temp[s * q.n_rung + l - 1]))
                 return fail(MISTI_E_ARG, "ladder[%lld][%d] = %g is not above ladder[%lld][%d] = %g: a ladder is strictly increasing", (long long)s, l, T,
-                            (long long)s, l - 1, q.ladder[s * q.n_rung + l - 1]);
+                            (long long)s, l - 1, q.temp[s * q.n_rung + l - 1]);
         }
-    if (q.swap_every < 0) return fail(MISTI_E_ARG, "swap_every must not be negative (got %d)", (int)q.swap_every);
     const int64_t K = q.n_step / q.thin;
-    if (K > 0 && (q.burn < 0 || q.burn >= K)) return fail(MISTI_E_ARG, "burn must be 0 ... K - 1 (got %d for %lld kept steps)", (int)q.burn, (long long)K);
-    if (int r = check_n_box(a, "fits")) return r;
-    if (int r = check_prior_shape(prior, q.n_start, "fits")) return r;
+    if (pt && q.swap_every < 0) return fail(MISTI_E_ARG, "swap_every must not be negative (got %d)", (int)q.swap_every);
+    if (pt && K > 0 && (q.burn < 0 || q.burn >= K)) return fail(MISTI_E_ARG, "burn must be 0 ... K - 1 (got %d for %lld kept steps)", (int)q.burn, (long long)K);
+    // the rows problem and the prior's shape; then the context and what needs the model
+    if (int r = check_n_box(a, q.noun)) return r;
+    if (int r = check_prior_shape(prior, a.n_start, q.noun)) return r;
     if (int r = check_rows(a, whole)) return r;
     const int64_t per = (int64_t)q.walkers * q.n_rung;
-    if (int r = check_limits(c, a, per, "fits x rungs x walkers", N)) return r;
-    if (q.n_start > 0 && K > INT32_MAX / 8 / N / per / q.n_start)
-        return fail(MISTI_E_LIMIT, "the chain of %lld fits x %d rungs x %lld kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)",
-                    (long long)q.n_start, (int)q.n_rung, (long long)K, (int)q.walkers, N);
-    for (int64_t b = 0; b < q.n_box; ++b) {
+    if (int r = check_limits(c, a, per, q.per, N)) return r;
+    if ((q.keep_x || q.keep_llh) && a.n_start > 0 && K > INT32_MAX / 8 / N / per / a.n_start) {
+        char rungs[32] = "";
+        if (pt) snprintf(rungs, sizeof(rungs), " x %d rungs", (int)q.n_rung);
+        return fail(MISTI_E_LIMIT, "the %schain of %lld %s%s x %lld kept steps x %d walkers x %d coordinates exceeds INT32_MAX / 8 elements (raise thin)", q.kept,
+                    (long long)a.n_start, q.noun, rungs, (long long)K, (int)q.walkers, N);
+    }
+    for (int64_t b = 0; b < a.n_box; ++b) {
         if (int r = check_box(a, N, b, "the sampler's prior is uniform on a finite box")) return r;
         int n_free = 0;
-        for (int k = 0; k < N; ++k) n_free += q.box_lo[b * N + k] != q.box_hi[b * N + k] ? 1 : 0;
+        for (int k = 0; k < N; ++k) n_free += a.box_lo[b * N + k] != a.box_hi[b * N + k] ? 1 : 0;
         if (n_free == 0) return fail(MISTI_E_ARG, "box %lld: every coordinate is fixed", (long long)b);
     }
     if (int r = check_prior(prior, a, N)) return r;
-    for (int64_t s = 0; s < q.n_start; ++s)
+    for (int64_t s = 0; s < a.n_start; ++s)
         for (int l = 0; l < q.n_rung; ++l)
             for (int i = 0; i < q.walkers; ++i)
                 for (int k = 0; k < N; ++k) {
                     const double v = q.init[((s * q.n_rung + l) * q.walkers + i) * N + k];
-                    const int64_t o = (q.n_box > 1 ? s : 0) * N + k;
-                    if (!std::isfinite(v)) return fail(MISTI_E_ARG, "init[%lld][%d][%d][%d] is not finite", (long long)s, l, i, k);
-                    if (v < q.box_lo[o] || v > q.box_hi[o])
-                        return fail(MISTI_E_ARG, "init[%lld][%d][%d][%d] = %g is outside its box [%g, %g]", (long long)s, l, i, k, v, q.box_lo[o], q.box_hi[o]);
+                    const int64_t o = (a.n_box > 1 ? s : 0) * N + k;
+                    if (std::isfinite(v) && v >= a.box_lo[o] && v <= a.box_hi[o]) continue;
+                    char at[80];                           // the walker: the plain door names no rung
+                    if (pt) snprintf(at, sizeof(at), "init[%lld][%d][%d][%d]", (long long)s, l, i, k);
+                    else snprintf(at, sizeof(at), "init[%lld][%d][%d]", (long long)s, i, k);
+                    if (!std::isfinite(v)) return fail(MISTI_E_ARG, "%s is not finite", at);
+                    return fail(MISTI_E_ARG, "%s = %g is outside its box [%g, %g]", at, v, a.box_lo[o], a.box_hi[o]);
                 }
     return 0;
 }
 
-// A checked call with n_start >= 1: ens_run over n_start x n_rung searches (EnsState::L), with a swap launch behind the steps that
-// have a round and the reduction at the end.  The values of every rung are always kept on the device (the reduction reads them), the
-// cold rung's coordinates where the caller or `post` wants them.
-int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens_post_t* post, const misti_prior_t* prior) {
+// A checked call with n_start >= 1: n_start x n_rung searches of the device's one sampler (EnsState::L).  One batch record of
+// n_start x n_rung x walkers slots serves the initial ensembles and every half-step (which fills the first half of it); the state and
+// the chains lie in the search buffers of the context, and nothing is read back before the end.  A tempered call adds a swap launch
+// behind the steps that have a round, the reduction at the end, and their four arrays; a plain call issues neither launch and carves
+// none of them.  With `post` (checked: post_check) the summary kernels run on the cold chain where it lies and the summaries come back
+// with the rest; the series workspace and the summaries' device side are carved with the chain.
+int sampler_run(misti_ctx* c, const SamplerArgs& q, int N, bool whole, const misti_ens_post_t* post, const misti_prior_t* prior) {
     using namespace misti;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t F = (size_t)q.n_start, L = (size_t)q.n_rung, S = F * L, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_ladder * L;
-    const size_t K = (size_t)(q.n_step / q.thin), KX = (q.chain || post) ? K : 0, P = F * (L - 1);
+    const size_t F = (size_t)q.rows.n_start, L = (size_t)q.n_rung, S = F * L, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp * L;
+    const size_t K = (q.keep_x || q.keep_llh) ? (size_t)(q.n_step / q.thin) : 0, P = F * (L - 1);
     PostArgs pa{};
-    if (post) post_fill(pa, q.n_start, (int64_t)K, q.walkers, N, *post);
-    RowsProblem rows(c, rows_args(q), N, whole);
+    if (post) post_fill(pa, q.rows.n_start, (int64_t)K, q.walkers, N, *post);
+    RowsProblem rows(c, q.rows, N, whole);
     PriorProblem pri(prior, N, S * H);
     EnsState st{};
     st.S = (int64_t)S; st.L = q.n_rung; st.N = N; st.W = q.walkers; st.thin = q.thin; st.a = q.a; st.am1 = q.a - 1.0; st.seed = q.seed;
-    st.temp_per_start = q.n_ladder > 1 ? 1 : 0;
+    st.temp_per_start = q.n_temp > 1 ? 1 : 0;
     st.n_keep = (int64_t)K;
     PtState pt{};
     double *llk = nullptr, *d_init = nullptr, *d_temp = nullptr, *d_points = nullptr, *d_rung = nullptr, *d_logz = nullptr;
@@ -2049,11 +1981,13 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
         st.z = f.take(S * H); st.u_acc = f.take(S * H);
         d_init = f.take(M * N); d_temp = f.take(NT);
         d_points = f.take(S);                              // int64 per search: 8-byte words of the double buffer
-        d_rung = f.take(S); d_logz = f.take(F);
-        if (KX) st.chain = f.take(F * K * W * (size_t)N);
-        if (K) st.chain_llh = f.take(S * K * W);
+        if (q.keep_x && K) st.chain = f.take(F * K * W * (size_t)N);
+        if (q.keep_llh && K) st.chain_llh = f.take(S * K * W);
         st.accepted = i.take(M); st.submitted = i.take(M);
-        pt.swap_proposed = i.take(P); pt.swap_accepted = i.take(P);
+        if (q.tempered) {
+            d_rung = f.take(S); d_logz = f.take(F);
+            pt.swap_proposed = i.take(P); pt.swap_accepted = i.take(P);
+        }
         rows.layout(f, i, &st.b, &M, 1, M);
         pri.layout(f, i);
         if (post) post_carve(pa, *post, F, N, f, i);
@@ -2065,7 +1999,7 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
     st.points = reinterpret_cast<long long*>(d_points);
     hipStream_t sm = c->stream;
     HIP_TRY(hipMemcpyAsync(d_init, q.init, M * N * sizeof(double), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_temp, q.ladder, NT * sizeof(double), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_temp, q.temp, NT * sizeof(double), hipMemcpyHostToDevice, sm));
     if (P) HIP_TRY(hipMemsetAsync(pt.swap_proposed, 0, 2 * P * sizeof(int32_t), sm));     // the two counters lie back to back
     if (int r = rows.upload(c)) return r;
     if (int r = pri.upload(sm)) return r;
@@ -2087,21 +2021,22 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
     c->nm_iterations = 2 * (int64_t)q.n_step;
     c->nm_slots = 2 * (int64_t)q.n_step * (int64_t)(S * H);
     HIP_TRY(launch_ens_result(st, sm));
-    HIP_TRY(launch_pt_reduce(st, K ? q.burn : 0, d_rung, d_logz, sm));
+    if (q.tempered) HIP_TRY(launch_pt_reduce(st, K ? q.burn : 0, d_rung, d_logz, sm));
     if (post) {
         pa.chain = st.chain; pa.chain_llh = st.chain_llh; pa.llh_K = (int64_t)(L * K);     // rung 0 of fit s: the first K rows of its L K
         HIP_TRY(launch_post(pa, sm));
         if (int r = post_back(pa, *post, F, N, sm)) return r;
     }
-    HIP_TRY(hipMemcpyAsync(q.last, st.x, M * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(q.last_llh, st.llh, M * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(q.rung_llh, d_rung, S * sizeof(double), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(q.logz, d_logz, F * sizeof(double), hipMemcpyDeviceToHost, sm));
-    if (q.accepted) HIP_TRY(hipMemcpyAsync(q.accepted, st.accepted, M * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (q.swap_proposed && P) HIP_TRY(hipMemcpyAsync(q.swap_proposed, pt.swap_proposed, P * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (q.swap_accepted && P) HIP_TRY(hipMemcpyAsync(q.swap_accepted, pt.swap_accepted, P * sizeof(int32_t), hipMemcpyDeviceToHost, sm));
-    if (q.chain && K) HIP_TRY(hipMemcpyAsync(q.chain, st.chain, F * K * W * N * sizeof(double), hipMemcpyDeviceToHost, sm));
-    if (q.chain_llh && K) HIP_TRY(hipMemcpyAsync(q.chain_llh, st.chain_llh, S * K * W * sizeof(double), hipMemcpyDeviceToHost, sm));
+    auto back = [&](void* host, const void* dev, size_t bytes) { return host && bytes ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm) : hipSuccess; };
+    HIP_TRY(back(q.last, st.x, M * N * sizeof(double)));
+    HIP_TRY(back(q.last_llh, st.llh, M * sizeof(double)));
+    HIP_TRY(back(q.rung_llh, d_rung, S * sizeof(double)));
+    HIP_TRY(back(q.logz, d_logz, F * sizeof(double)));
+    HIP_TRY(back(q.accepted, st.accepted, M * sizeof(int32_t)));
+    HIP_TRY(back(q.swap_proposed, pt.swap_proposed, P * sizeof(int32_t)));
+    HIP_TRY(back(q.swap_accepted, pt.swap_accepted, P * sizeof(int32_t)));
+    HIP_TRY(back(q.chain, st.chain, F * K * W * N * sizeof(double)));
+    HIP_TRY(back(q.chain_llh, st.chain_llh, S * K * W * sizeof(double)));
     std::vector<int64_t> per_search;
     if (q.n_points) {
         per_search.resize(S);
@@ -2116,53 +2051,49 @@ int pt_run(misti_ctx* c, const misti_pt_t& q, int N, bool whole, const misti_ens
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int misti_tempered_sample_prior(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) {
+// The one door behind the five sampling entry points, entered once the sampler descriptor's own size is known to be this library's
+// (sampler_size: nothing else of a descriptor is read before).  `need_post`: a summary there must be (misti_ensemble_posterior).
+int sampler_size(const void* q, uint32_t size, uint32_t want, const char* type) {
     if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
-    if (q->size != sizeof(misti_pt_t))
-        return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_pt_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_pt_t));
-    if (p && p->size != sizeof(misti_ens_post_t))
-        return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
-    if (pr && pr->size != sizeof(misti_prior_t))
-        return fail(MISTI_E_ARG, "the prior descriptor's size is %u, this library's misti_prior_t has %u bytes", (unsigned)pr->size, (unsigned)sizeof(misti_prior_t));
-    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
-        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
-    int N = 0;
-    bool whole = false;
-    if (int r = pt_check(c, *q, N, whole, pr)) return r;
-    if (p) if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
-    if (q->n_start == 0) return 0;
-    return pt_run(c, *q, N, whole, p, pr);
+    if (size != want) return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's %s has %u bytes", (unsigned)size, type, (unsigned)want);
+    return 0;
 }
-
-int misti_tempered_sample(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p) { return misti_tempered_sample_prior(c, q, p, nullptr); }
-
-// misti_ensemble_sample (no post), misti_ensemble_posterior (`need_post`: a post there must be) and misti_ensemble_sample_prior: one door
-static int ens_entry(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post) {
-    if (!q) return fail(MISTI_E_ARG, "the sampler descriptor is NULL");
-    if (q->size != sizeof(misti_ens_t))
-        return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's misti_ens_t has %u bytes", (unsigned)q->size, (unsigned)sizeof(misti_ens_t));
+int sampler_door(misti_ctx* c, const SamplerArgs& q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post) {
     if (need_post && !p) return fail(MISTI_E_ARG, "the summary descriptor is NULL");
     if (p && p->size != sizeof(misti_ens_post_t))
         return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
     if (pr && pr->size != sizeof(misti_prior_t))
         return fail(MISTI_E_ARG, "the prior descriptor's size is %u, this library's misti_prior_t has %u bytes", (unsigned)pr->size, (unsigned)sizeof(misti_prior_t));
-    if (q->split != MISTI_SPLIT_PER_START && q->split != MISTI_SPLIT_FITTED)
-        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q->split);
+    if (q.rows.split != MISTI_SPLIT_PER_START && q.rows.split != MISTI_SPLIT_FITTED)
+        return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q.rows.split);
     int N = 0;
     bool whole = false;
-    if (int r = ens_check(c, *q, N, whole, p != nullptr, pr)) return r;
-    if (p) if (int r = post_check(p, q->n_start, q->n_step / q->thin, q->walkers, N, true)) return r;
-    if (q->n_start == 0) return 0;
-    return ens_run(c, *q, N, whole, p, pr);
+    if (int r = sampler_check(c, q, pr, N, whole)) return r;
+    if (p) if (int r = post_check(p, q.rows.n_start, q.n_step / q.thin, q.walkers, N, true)) return r;
+    if (q.rows.n_start == 0) return 0;
+    return sampler_run(c, q, N, whole, p, pr);
+}
+int ens_door(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post) {
+    if (int r = sampler_size(q, q ? q->size : 0, sizeof(misti_ens_t), "misti_ens_t")) return r;
+    return sampler_door(c, sampler_args(*q, p), p, pr, need_post);
 }
 
-int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) { return ens_entry(c, q, nullptr, nullptr, false); }
+}  // namespace
 
-int misti_ensemble_sample_prior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) { return ens_entry(c, q, p, pr, false); }
+extern "C" {
+
+int misti_ensemble_sample(misti_ctx* c, const misti_ens_t* q) { return ens_door(c, q, nullptr, nullptr, false); }
+
+int misti_ensemble_posterior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p) { return ens_door(c, q, p, nullptr, true); }
+
+int misti_ensemble_sample_prior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) { return ens_door(c, q, p, pr, false); }
+
+int misti_tempered_sample_prior(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) {
+    if (int r = sampler_size(q, q ? q->size : 0, sizeof(misti_pt_t), "misti_pt_t")) return r;
+    return sampler_door(c, sampler_args(*q, p), p, pr, false);
+}
+
+int misti_tempered_sample(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p) { return misti_tempered_sample_prior(c, q, p, nullptr); }
 
 int misti_ens_log_prior(int32_t N, const int32_t* scale, const int32_t* kind, const double* p0, const double* p1, const double* lo, const double* hi,
                         const double* y, double* lp, double* natural) {
@@ -2199,8 +2130,6 @@ int misti_ens_summary_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t
     HIP_TRY(misti::launch_post(a, c->stream));
     return 0;
 }
-
-int misti_ensemble_posterior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p) { return ens_entry(c, q, p, nullptr, true); }
 
 int misti_de_search(misti_ctx* c, const misti_de_t* q) {
     if (!q) return fail(MISTI_E_ARG, "the search descriptor is NULL");

@@ -736,58 +736,81 @@ class Engine:
         engine's value or its logarithm) and a prior density per coordinate - ``misti_ensemble_sample_prior``, the rule is
         ``optimize.ensemble_prior_rule``.  ``init``, ``box``, ``chain`` and ``last`` are then in SAMPLING coordinates
         (``optimize.to_sampling`` / ``from_sampling``); the engine is handed their natural image."""
-        return self._ensemble("ensemble_sample", None, True, init, rows, table, box, split_times, fit_split, band_bounds, pulse_times, n_step, thin,
-                              temperature, a, seed, ids, prior)
+        return self._sampler("ensemble_sample", False, None, True, init, rows, table, box, temperature, split_times, fit_split, band_bounds,
+                             pulse_times, n_step, thin, 0, 0, a, seed, ids, prior)
 
-    def _ensemble(self, who, post, keep_chain, init, rows, table, box, split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature,
-                  a, seed, ids, prior=None):
-        """``misti_ensemble_sample`` (``post`` None) or ``misti_ensemble_posterior`` (``post``: dict(burn, probs, max_lag, c)): one
-        marshalling of the sampler's descriptor for both."""
+    _POST_OUTPUTS = ("mean", "cov", "quant", "tau", "window", "best_llh", "best_x", "best_at")
+
+    @staticmethod
+    def _post(S, N, K, burn, probs, max_lag, c, empty=None, want=_POST_OUTPUTS):
+        """``misti_ens_post_t`` for the chains of S searches, N coordinates and K kept steps, and the outputs of ``want`` it points
+        into.  ``max_lag`` None: every lag.  ``empty(shape, integer)`` allocates one output and returns it with its address (default:
+        NumPy, on the host).  Returns (descriptor, outputs, what must stay alive until the call returns)."""
+        probs = _f64(probs).reshape(-1)
+        P, burn = probs.size, int(burn)
+        max_lag = max(K - burn - 1, 0) if max_lag is None else int(max_lag)
+        shapes = dict(mean=(S, N), cov=(S, N, N), quant=(S, N, P), tau=(S, N), window=(S, N), best_llh=(S,), best_x=(S, N), best_at=(S, 2))
+        if empty is None:
+            def empty(shape, integer):
+                v = np.empty(shape, dtype=np.int32 if integer else np.float64)
+                return v, v.ctypes.data
+        made = {k: empty(shapes[k], k in ("window", "best_at")) for k in Engine._POST_OUTPUTS if k in want}
+        p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=burn, n_prob=P, probs=probs.ctypes.data, max_lag=min(max_lag, 2 ** 31 - 1), c=float(c),
+                         **{k: at or None for k, (_, at) in made.items()})
+        return p, {k: v for k, (v, _) in made.items()}, probs
+
+    def _sampler(self, who, tempered, post, keep_chain, init, rows, table, box, temps, split_times, fit_split, band_bounds, pulse_times, n_step,
+                 thin, swap_every, burn, a, seed, ids, prior):
+        """One marshalling for the two sampler descriptors - the rows problem, the outputs, the summaries and the prior - and the call.
+        ``tempered`` False: ``misti_ens_t``, ``init`` is ``[S][W][N]`` and ``temps`` the temperature (a scalar or ``[S]``); True:
+        ``misti_pt_t``, ``init`` is ``[S][L][W][N]`` and ``temps`` the ladder.  ``post``: None or dict(burn, probs, max_lag, c).
+        Returns the door's outputs in the descriptor's order (the coordinate chain only with ``keep_chain``; the plain door's value
+        chain too), then the summaries, then ``n_points``."""
         if (split_times is None) != bool(fit_split):
             raise ValueError("%s: give exactly one of split_times and fit_split=True" % who)
         N = self.n_param + (1 if fit_split else 0)
         x0 = _f64(init)
-        if x0.ndim != 3 or x0.shape[2] != N:
-            raise ValueError("%s: init must be [S][W][%d] (got %s)" % (who, N, x0.shape))
-        S, W = x0.shape[0], x0.shape[1]
+        dims = "[S][L][W]" if tempered else "[S][W]"
+        if x0.ndim != (4 if tempered else 3) or x0.shape[-1] != N:
+            raise ValueError("%s: init must be %s[%d] (got %s)" % (who, dims, N, x0.shape))
+        S, W, rung = x0.shape[0], x0.shape[-2], x0.shape[1:-2]              # rung: (L,) | ()
+        T = _f64(temps)
+        if tempered and T.shape not in (rung, (S,) + rung):
+            raise ValueError("%s: the ladder must be [%d] or [%d][%d] (got %s)" % (who, rung[0], S, rung[0], T.shape))
         n_step, thin = int(n_step), int(thin)
         ptr = lambda v: v.ctypes.data if v is not None else None
         arrays, fields = self._rows_problem(S, N, _f64(table, (-1, 8)), split_times, rows, band_bounds, pulse_times, box, ids)
-        T = _f64(temperature).reshape(-1)
         K = n_step // thin if thin >= 1 and n_step >= 0 else 0
-        chain, chain_llh = (np.empty((S, K, W, N)), np.empty((S, K, W))) if keep_chain else (None, None)
-        accepted = np.zeros((S, W), dtype=np.int32)
-        last, last_llh = np.empty((S, W, N)), np.empty((S, W))
+        out = dict(chain=np.empty((S, K, W, N)) if keep_chain else None, chain_llh=np.empty((S,) + rung + (K, W)) if keep_chain or tempered else None,
+                   accepted=np.zeros((S,) + rung + (W,), dtype=np.int32))
+        if tempered:
+            out.update(swap_proposed=np.zeros((S, max(rung[0] - 1, 0)), dtype=np.int32), swap_accepted=np.zeros((S, max(rung[0] - 1, 0)), dtype=np.int32))
+        out.update(last=np.empty((S,) + rung + (W, N)), last_llh=np.empty((S,) + rung + (W,)))
+        if tempered:
+            out.update(rung_llh=np.empty((S,) + rung), logz=np.empty(S))
         n_points = np.zeros(1, dtype=np.int64)
-        q = _lib.EnsSample(size=C.sizeof(_lib.EnsSample), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, init=ptr(x0),
-                           walkers=W, n_step=n_step, thin=thin, n_temp=T.size, temperature=ptr(T), a=float(a), seed=int(seed), chain=ptr(chain),
-                           chain_llh=ptr(chain_llh), accepted=ptr(accepted), last=ptr(last), last_llh=ptr(last_llh), n_points=ptr(n_points),
-                           **fields)
-        out = dict(chain=chain, chain_llh=chain_llh) if post is None else {}
-        out.update(accepted=accepted, last=last, last_llh=last_llh)
-        pr, pr_arrays = self._prior(prior, S, N, who) if prior is not None else (None, None)
-        if post is None and pr is None:
-            _lib.check(self._lib.misti_ensemble_sample(self._ctx, C.byref(q)))
-        elif post is None:
-            _lib.check(self._lib.misti_ensemble_sample_prior(self._ctx, C.byref(q), None, C.byref(pr)))
+        common = dict(split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, init=ptr(x0), walkers=W, n_step=n_step, thin=thin, a=float(a),
+                      seed=int(seed), n_points=ptr(n_points), **{k: ptr(v) for k, v in out.items()}, **fields)
+        if tempered:
+            q = _lib.PtSample(size=C.sizeof(_lib.PtSample), n_rung=rung[0], n_ladder=1 if T.ndim == 1 else S, ladder=ptr(T), swap_every=int(swap_every),
+                              burn=int(burn), **common)
         else:
-            probs = _f64(post["probs"]).reshape(-1)
-            P = probs.size
-            burn = int(post["burn"])
-            max_lag = max(K - burn - 1, 0) if post["max_lag"] is None else int(post["max_lag"])
-            s = dict(mean=np.empty((S, N)), cov=np.empty((S, N, N)), quant=np.empty((S, N, P)), tau=np.empty((S, N)),
-                     window=np.empty((S, N), dtype=np.int32), best_llh=np.empty(S), best_x=np.empty((S, N)), best_at=np.empty((S, 2), dtype=np.int32))
-            p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=burn, n_prob=P, probs=ptr(probs), max_lag=min(max_lag, 2 ** 31 - 1), c=float(post["c"]),
-                             **{k: ptr(v) for k, v in s.items()})
-            if pr is None:
-                _lib.check(self._lib.misti_ensemble_posterior(self._ctx, C.byref(q), C.byref(p)))
-            else:
-                _lib.check(self._lib.misti_ensemble_sample_prior(self._ctx, C.byref(q), C.byref(p), C.byref(pr)))
-            out.update(s)
-        if keep_chain and post is not None:
-            out.update(chain=chain, chain_llh=chain_llh)
-        out["n_points"] = int(n_points[0])
-        return out
+            T = T.reshape(-1)
+            q = _lib.EnsSample(size=C.sizeof(_lib.EnsSample), n_temp=T.size, temperature=ptr(T), **common)
+        p, s, p_keep = self._post(S, N, K, **post) if post is not None else (None, {}, None)
+        pr, pr_keep = self._prior(prior, S, N, who) if prior is not None else (None, None)
+        ref = lambda d: C.byref(d) if d is not None else None
+        if pr is not None:
+            door = self._lib.misti_tempered_sample_prior if tempered else self._lib.misti_ensemble_sample_prior
+            rc = door(self._ctx, C.byref(q), ref(p), C.byref(pr))
+        elif tempered:
+            rc = self._lib.misti_tempered_sample(self._ctx, C.byref(q), ref(p))
+        elif p is not None:
+            rc = self._lib.misti_ensemble_posterior(self._ctx, C.byref(q), C.byref(p))
+        else:
+            rc = self._lib.misti_ensemble_sample(self._ctx, C.byref(q))
+        _lib.check(rc)
+        return dict({k: v for k, v in out.items() if v is not None}, **s, n_points=int(n_points[0]))
 
     def ensemble_posterior(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
                            thin=1, temperature=1.0, a=2.0, seed=0, ids=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, keep_chain=False, c=5.0,
@@ -802,8 +825,12 @@ class Engine:
         accepted, last, last_llh, n_points as ``ensemble_sample``), and chain, chain_llh with ``keep_chain``.  ``prior`` as in
         ``ensemble_sample``: the summaries are then those of the chain in SAMPLING coordinates (``optimize.posterior_table`` reports
         quantiles and the best sample in natural units too)."""
-        return self._ensemble("ensemble_posterior", dict(burn=burn, probs=probs, max_lag=max_lag, c=c), bool(keep_chain), init, rows, table, box,
-                              split_times, fit_split, band_bounds, pulse_times, n_step, thin, temperature, a, seed, ids, prior)
+        r = self._sampler("ensemble_posterior", False, dict(burn=burn, probs=probs, max_lag=max_lag, c=c), bool(keep_chain), init, rows, table, box,
+                          temperature, split_times, fit_split, band_bounds, pulse_times, n_step, thin, 0, 0, a, seed, ids, prior)
+        for k in ("chain", "chain_llh") if keep_chain else ():             # this door's order: the chain behind the summaries
+            r[k] = r.pop(k)
+        r["n_points"] = r.pop("n_points")
+        return r
 
     def tempered_sample(self, init, rows, table, box, ladder, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
                         thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None, post=None, prior=None):
@@ -818,50 +845,12 @@ class Engine:
         swap_accepted[S][L-1], last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S] (see ``optimize.tempered_rule`` for what it
         is and is not), n_points), plus the summaries with ``post``.  ``prior`` as in ``ensemble_sample`` (one per fit): every rung
         targets ``prior(y) exp(llk / T_l)`` - ``misti_tempered_sample_prior``, the rule is ``optimize.tempered_prior_rule``."""
-        if (split_times is None) != bool(fit_split):
-            raise ValueError("tempered_sample: give exactly one of split_times and fit_split=True")
-        N = self.n_param + (1 if fit_split else 0)
-        x0 = _f64(init)
-        if x0.ndim != 4 or x0.shape[3] != N:
-            raise ValueError("tempered_sample: init must be [S][L][W][%d] (got %s)" % (N, x0.shape))
-        S, L, W = x0.shape[:3]
-        T = _f64(ladder)
-        if T.shape not in ((L,), (S, L)):
-            raise ValueError("tempered_sample: the ladder must be [%d] or [%d][%d] (got %s)" % (L, S, L, T.shape))
-        n_step, thin = int(n_step), int(thin)
-        ptr = lambda v: v.ctypes.data if v is not None else None
-        arrays, fields = self._rows_problem(S, N, _f64(table, (-1, 8)), split_times, rows, band_bounds, pulse_times, box, ids)
-        K = n_step // thin if thin >= 1 and n_step >= 0 else 0
         opts = dict(post) if post is not None else None
         keep_chain = opts is None or bool(opts.pop("keep_chain", False))
-        out = dict(chain=np.empty((S, K, W, N)) if keep_chain else None, chain_llh=np.empty((S, L, K, W)), accepted=np.zeros((S, L, W), dtype=np.int32),
-                   swap_proposed=np.zeros((S, max(L - 1, 0)), dtype=np.int32), swap_accepted=np.zeros((S, max(L - 1, 0)), dtype=np.int32),
-                   last=np.empty((S, L, W, N)), last_llh=np.empty((S, L, W)), rung_llh=np.empty((S, L)), logz=np.empty(S))
-        n_points = np.zeros(1, dtype=np.int64)
-        q = _lib.PtSample(size=C.sizeof(_lib.PtSample), split=_lib.SPLIT_FITTED if fit_split else _lib.SPLIT_PER_START, init=ptr(x0), walkers=W,
-                          n_rung=L, n_ladder=1 if T.ndim == 1 else S, n_step=n_step, ladder=ptr(T), thin=thin, swap_every=int(swap_every), burn=int(burn),
-                          a=float(a), seed=int(seed), n_points=ptr(n_points), **{k: ptr(v) for k, v in out.items()}, **fields)
-        p = None
         if opts is not None:
-            probs = _f64(opts.get("probs", (0.025, 0.5, 0.975))).reshape(-1)
-            P = probs.size
-            pburn = int(opts.get("burn", burn))
-            max_lag = max(K - pburn - 1, 0) if opts.get("max_lag") is None else int(opts["max_lag"])
-            s = dict(mean=np.empty((S, N)), cov=np.empty((S, N, N)), quant=np.empty((S, N, P)), tau=np.empty((S, N)),
-                     window=np.empty((S, N), dtype=np.int32), best_llh=np.empty(S), best_x=np.empty((S, N)), best_at=np.empty((S, 2), dtype=np.int32))
-            p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=pburn, n_prob=P, probs=ptr(probs), max_lag=min(max_lag, 2 ** 31 - 1), c=float(opts.get("c", 5.0)),
-                             **{k: ptr(v) for k, v in s.items()})
-        if prior is None:
-            _lib.check(self._lib.misti_tempered_sample(self._ctx, C.byref(q), C.byref(p) if p is not None else None))
-        else:
-            pr, pr_arrays = self._prior(prior, S, N, "tempered_sample")
-            _lib.check(self._lib.misti_tempered_sample_prior(self._ctx, C.byref(q), C.byref(p) if p is not None else None, C.byref(pr)))
-        if not keep_chain:
-            del out["chain"]
-        if p is not None:
-            out.update(s)
-        out["n_points"] = int(n_points[0])
-        return out
+            opts = dict(burn=opts.get("burn", burn), probs=opts.get("probs", (0.025, 0.5, 0.975)), max_lag=opts.get("max_lag"), c=opts.get("c", 5.0))
+        return self._sampler("tempered_sample", True, opts, keep_chain, init, rows, table, box, ladder, split_times, fit_split, band_bounds,
+                             pulse_times, n_step, thin, swap_every, burn, a, seed, ids, prior)
 
     def ensemble_summary_dev(self, chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0, want=None):
         """``misti_ens_summary_dev``: the posterior summaries of a chain that is already on the device - ``chain`` a contiguous float64
@@ -877,13 +866,10 @@ class Engine:
         S, K, W, N = chain.shape
         if chain_llh is not None and (tuple(chain_llh.shape) != (S, K, W) or chain_llh.dtype != torch.float64 or not chain_llh.is_contiguous()):
             raise ValueError("ensemble_summary_dev: chain_llh must be a contiguous float64 tensor [S][K][W]")
-        pr = _f64(probs).reshape(-1)
-        P = pr.size
-        shapes = dict(mean=(S, N), cov=(S, N, N), quant=(S, N, P), tau=(S, N), window=(S, N), best_llh=(S,), best_x=(S, N), best_at=(S, 2))
-        out = {k: torch.empty(shapes[k], dtype=torch.int32 if k in ("window", "best_at") else torch.float64, device=chain.device) for k in names if k in want}
-        max_lag = max(K - int(burn) - 1, 0) if max_lag is None else int(max_lag)
-        p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=int(burn), n_prob=P, probs=pr.ctypes.data, max_lag=min(max_lag, 2 ** 31 - 1), c=float(c),
-                         **{k: v.data_ptr() or None for k, v in out.items()})
+        def empty(shape, integer):
+            v = torch.empty(shape, dtype=torch.int32 if integer else torch.float64, device=chain.device)
+            return v, v.data_ptr()
+        p, out, p_keep = self._post(S, N, K, burn, probs, max_lag, c, empty, want)
         _lib.check(self._lib.misti_ens_summary_dev(self._ctx, S, K, W, N, C.c_void_p(chain.data_ptr()) if chain.data_ptr() else None,
                                                    C.c_void_p(chain_llh.data_ptr()) if chain_llh is not None and chain_llh.data_ptr() else None, C.byref(p)))
         return out

@@ -1533,10 +1533,6 @@ def ens_decision(z, d, llk_old, llk_new, T, u_acc):
 
 
 def ensemble_rule(fun_batch, init, lo, hi, n_step, thin=1, temperature=1.0, a=2.0, seed=0, ids=None):
-    return _ensemble_rule("ensemble_rule", fun_batch, init, lo, hi, n_step, None, thin, temperature, a, seed, ids)
-
-
-def _ensemble_rule(who, fun_batch, init, lo, hi, n_step, prior, thin, temperature, a, seed, ids):
     """The rule of ``misti_ensemble_sample``, operation for operation.  ``fun_batch(X[M][N], s[M]) -> f[M]`` evaluates M points at once,
     point m belonging to search ``s[m]`` (f = -llk; ``+inf``: no value; a NaN counts as ``+inf``).  ``init`` ``[S][W][N]``: the initial
     ensembles, W even, every walker inside its box; ``lo`` / ``hi``: the finite box, ``[N]`` or ``[S][N]``, ``lo == hi`` holds a
@@ -1553,81 +1549,20 @@ def _ensemble_rule(who, fun_batch, init, lo, hi, n_step, prior, thin, temperatur
     accepted[S][W] int32, last[S][W][N], last_llh[S][W], n_points: the PROPOSALS handed to ``fun_batch`` - the S W initial evaluations
     are not counted).
 
-    ``prior`` (``ensemble_prior_rule``; None here): see there - the one difference is the point handed to ``fun_batch`` and the ``e`` of
-    the decision; a prior that says nothing takes the lines without one."""
-    x = np.array(init, dtype=np.float64)
+    A search is a fit of ONE rung at its temperature, without swap rounds: the lines are ``_sampler_steps``'s."""
+    return _one_rung("ensemble_rule", fun_batch, init, lo, hi, n_step, None, thin, temperature, a, seed, ids)
+
+
+def _one_rung(who, fun_batch, init, lo, hi, n_step, prior, thin, temperature, a, seed, ids):
+    """``ensemble_rule`` / ``ensemble_prior_rule`` through ``_sampler_steps``: every search a fit of one rung at its own temperature, no
+    swap rounds; what comes back loses the rung's axis."""
+    x = np.asarray(init, dtype=np.float64)
     if x.ndim != 3:
         raise ValueError("%s: init must be [S][W][N]" % who)
-    S, W, N = x.shape
-    H = W // 2
-    n_step, thin, a = int(n_step), int(thin), float(a)
-    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=float), (S, N)))
-    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=float), (S, N)))
-    T = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=float), (S,)))
-    if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or n_step < 0 or thin < 1 or not (np.isfinite(a) and a > 1.0):
-        raise ValueError(who + ": W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
-    if not (np.isfinite(T) & (T > 0)).all():
-        raise ValueError(who + ": the temperature must be finite and positive")
-    with np.errstate(over="ignore", invalid="ignore"):
-        usable = np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all() and np.isfinite(hi - lo).all()
-    if not usable:
-        raise ValueError(who + ": the box must be finite with lo <= hi")
-    fixed = lo == hi
-    if S and fixed.all(axis=1).any():
-        raise ValueError(who + ": every coordinate of a box is fixed")
-    if not (np.isfinite(x).all() and (x >= lo[:, None, :]).all() and (x <= hi[:, None, :]).all()):
-        raise ValueError(who + ": every walker of init must be finite and inside its box")
-    ids = np.arange(S) if ids is None else np.asarray(ids).reshape(S)
-    d = (~fixed).sum(axis=1) - 1
-    pr = _prior_arrays(prior, S, N, lo, hi, who)
-    am1 = a - 1.0
-
-    def values(X, s_of):
-        if pr is not None:
-            X = ens_natural(pr["scale"][s_of], X)
-        f = np.asarray(fun_batch(X, s_of), dtype=float).reshape(-1)
-        llk = -np.where(np.isnan(f), np.inf, f)
-        return np.where(np.isfinite(llk), llk, -np.inf)
-
-    llh = values(x.reshape(-1, N).copy(), np.repeat(np.arange(S), W)).reshape(S, W) if S else np.empty((0, W))
-    n_points = 0
-    n_keep = n_step // thin
-    chain, chain_llh = np.empty((S, n_keep, W, N)), np.empty((S, n_keep, W))
-    accepted = np.zeros((S, W), dtype=np.int32)
-    CHUNK = 512
-    raw = None
-    sidx = np.arange(S)[:, None]
-    for t in range(1, n_step + 1):
-        if (t - 1) % CHUNK == 0:
-            raw = np.stack([_ens_raw(seed, ids[s], t, min(CHUNK, n_step - t + 1), W) for s in range(S)]) if S else np.empty((0, 1, W, 4), dtype=np.uint64)
-        w = raw[:, (t - 1) % CHUNK]                                       # [S][W][4]
-        for half in (0, 1):
-            mine = slice(half * H, half * H + H)
-            j = (1 - half) * H + _mulhi_index(w[:, mine, 0], H)            # [S][H]
-            u_z, u_acc = _ens_uniform(w[:, mine, 1]), _ens_uniform(w[:, mine, 2])
-            sz = am1 * u_z + 1.0
-            z = (sz * sz) / a
-            xi, xj = x[:, mine], x[sidx, j]
-            with np.errstate(all="ignore"):
-                y = xj + z[:, :, None] * (xi - xj)
-            y = np.where(fixed[:, None, :], lo[:, None, :], y)
-            inside = ((y >= lo[:, None, :]) & (y <= hi[:, None, :])).all(axis=2)
-            new = np.full((S, H), -np.inf)
-            if inside.any():
-                new[inside] = values(y[inside], np.broadcast_to(sidx, (S, H))[inside])
-                n_points += int(inside.sum())
-            if pr is None:
-                take = inside & ens_decision(z, d[:, None], llh[:, mine], new, T[:, None], u_acc)
-            else:
-                lp_old, lp_new = (ens_log_prior(pr["kind"][:, None], pr["p0"][:, None], pr["p1"][:, None], lo[:, None], hi[:, None], v) for v in (xi, y))
-                take = inside & ens_decision_prior(z, d[:, None], llh[:, mine], new, T[:, None], lp_old, lp_new, u_acc)
-            x[:, mine] = np.where(take[:, :, None], y, xi)
-            llh[:, mine] = np.where(take, new, llh[:, mine])
-            accepted[:, mine] += take
-        if t % thin == 0:
-            chain[:, t // thin - 1] = x
-            chain_llh[:, t // thin - 1] = llh
-    return dict(chain=chain, chain_llh=chain_llh, accepted=accepted, last=x, last_llh=llh, n_points=int(n_points))
+    T = np.broadcast_to(np.asarray(temperature, dtype=float), x.shape[:1])[:, None]
+    r = _sampler_steps(who, fun_batch, x[:, None], lo, hi, T, n_step, prior, thin, 0, 0, a, seed, ids, "the temperature must be finite and positive")
+    return dict(chain=r["chain"], chain_llh=r["chain_llh"][:, 0], accepted=r["accepted"][:, 0], last=r["last"][:, 0], last_llh=r["last_llh"][:, 0],
+                n_points=r["n_points"])
 
 
 def ensemble_start(x, lo, hi, W, spread=1e-2, seed=0, id_=0):
@@ -1967,7 +1902,7 @@ def ensemble_prior_rule(fun_batch, init, lo, hi, n_step, prior, thin=1, temperat
     the halves, the rejection in advance and the counters are ``ensemble_rule``'s.
     A prior that says nothing (None, or every coordinate LINEAR and FLAT) IS ``ensemble_rule``: the existing lines, not the new formula
     with a zero added.  Returns what ``ensemble_rule`` returns."""
-    return _ensemble_rule("ensemble_prior_rule", fun_batch, init, lo, hi, n_step, prior, thin, temperature, a, seed, ids)
+    return _one_rung("ensemble_prior_rule", fun_batch, init, lo, hi, n_step, prior, thin, temperature, a, seed, ids)
 
 
 def to_sampling(x, prior, box=None):
@@ -2054,10 +1989,6 @@ def tempered_reduction(chain_llh, ladder, burn=0):
 
 
 def tempered_rule(fun_batch, init, lo, hi, ladder, n_step, thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None):
-    return _tempered_rule("tempered_rule", fun_batch, init, lo, hi, ladder, n_step, None, thin, swap_every, burn, a, seed, ids)
-
-
-def _tempered_rule(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids):
     """The rule of ``misti_tempered_sample``, operation for operation: parallel tempering (replica exchange) over ``ensemble_rule``.
     Fit s has L rungs (1 ... ``PT_MAX_RUNGS``) at the temperatures ``ladder[s][0] < ladder[s][1] < ...`` (finite, positive; ``ladder``
     is ``[L]`` or ``[S][L]``); rung l is an ensemble of W walkers ``init[s][l][W][N]`` inside the fit's box whose target is
@@ -2084,8 +2015,25 @@ def _tempered_rule(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, sw
     swap_accepted[S][L-1] int32, last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S], n_points: the PROPOSALS handed to
     ``fun_batch``).
 
-    ``prior`` (``tempered_prior_rule``; None here): see there - the point handed to ``fun_batch`` and the ``e`` of a rung's decision
-    change, the swaps do not."""
+    The lines are ``_sampler_steps``'s; the reduction is ``tempered_reduction``."""
+    return _tempered("tempered_rule", fun_batch, init, lo, hi, ladder, n_step, None, thin, swap_every, burn, a, seed, ids)
+
+
+def _tempered(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids):
+    """``tempered_rule`` / ``tempered_prior_rule``: ``_sampler_steps`` and the reduction of the values it kept."""
+    r = _sampler_steps(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids,
+                       "a ladder must be finite, positive and strictly increasing")
+    T, n_points = r.pop("T"), r.pop("n_points")
+    rung_llh, logz = tempered_reduction(r["chain_llh"], T, burn) if len(T) else (np.empty((0, T.shape[1])), np.empty(0))
+    return dict(r, rung_llh=rung_llh, logz=logz, n_points=n_points)
+
+
+def _sampler_steps(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids, ladder_says):
+    """The one stepping loop behind the four sampler rules, as ``tempered_rule`` states it: the arguments checked (``who`` and
+    ``ladder_says`` word the refusals), the S L rungs moved as S L searches - the temperature and the block are the rung's, everything
+    else the fit's -, the swap rounds, the kept rows.  ``prior`` (None: without one; a prior that says nothing takes the lines without
+    one): the point handed to ``fun_batch`` and the ``e`` of a rung's decision change (``ensemble_prior_rule``), the swaps do not.
+    Returns dict(chain, chain_llh, accepted, swap_proposed, swap_accepted, last, last_llh, T[S][L], n_points)."""
     x = np.array(init, dtype=np.float64)
     if x.ndim != 4:
         raise ValueError(who + ": init must be [S][L][W][N]")
@@ -2100,7 +2048,7 @@ def _tempered_rule(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, sw
     if not 4 <= W <= ENS_MAX_WALKERS or W % 2 or n_step < 0 or thin < 1 or not (np.isfinite(a) and a > 1.0):
         raise ValueError(who + ": W must be even, 4 ... %d, n_step >= 0, thin >= 1, a finite and > 1" % ENS_MAX_WALKERS)
     if not (np.isfinite(T) & (T > 0)).all() or not (T[:, 1:] > T[:, :-1]).all():
-        raise ValueError(who + ": a ladder must be finite, positive and strictly increasing")
+        raise ValueError(who + ": " + ladder_says)
     K = n_step // thin
     if swap_every < 0 or (K and not 0 <= burn < K):
         raise ValueError(who + ": swap_every >= 0, burn 0 ... K - 1")
@@ -2183,9 +2131,8 @@ def _tempered_rule(who, fun_batch, init, lo, hi, ladder, n_step, prior, thin, sw
         if t % thin == 0:
             chain[:, t // thin - 1] = x.reshape(S, L, W, N)[:, 0]
             chain_llh[:, :, t // thin - 1] = llh.reshape(S, L, W)
-    rung_llh, logz = tempered_reduction(chain_llh, T, burn) if S else (np.empty((0, L)), np.empty(0))
     return dict(chain=chain, chain_llh=chain_llh, accepted=accepted.reshape(S, L, W), swap_proposed=proposed, swap_accepted=swapped,
-                last=x.reshape(S, L, W, N), last_llh=llh.reshape(S, L, W), rung_llh=rung_llh, logz=logz, n_points=int(n_points))
+                last=x.reshape(S, L, W, N), last_llh=llh.reshape(S, L, W), T=T, n_points=int(n_points))
 
 
 def tempered_prior_rule(fun_batch, init, lo, hi, ladder, n_step, prior, thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None):
@@ -2194,7 +2141,7 @@ def tempered_prior_rule(fun_batch, init, lo, hi, ladder, n_step, prior, thin=1, 
     not tempered -, so it cancels in a swap: ``pt_swap_decision`` decides as before.  ``logz`` is the same trapezoid rule, now for
     ``Z(beta)`` = the integral of ``exp(beta llk)`` against the NORMALISED prior on the box, in sampling coordinates.  One rung is
     ``ensemble_prior_rule``; a prior that says nothing is ``tempered_rule``.  Returns what ``tempered_rule`` returns."""
-    return _tempered_rule("tempered_prior_rule", fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids)
+    return _tempered("tempered_prior_rule", fun_batch, init, lo, hi, ladder, n_step, prior, thin, swap_every, burn, a, seed, ids)
 
 
 def _mcmc_call(engine, summary, n_step, thin, ladder=None, swap_every=1, prior=None):

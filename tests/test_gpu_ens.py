@@ -252,26 +252,34 @@ def bad(what, **kw):
     return dict(init=init, lo=lo, hi=hi, **kw)
 
 
-@pytest.mark.parametrize("case, code, word", [
-    (bad({}, n_step=10 ** 9, thin=1), -4, "exceeds INT32_MAX / 8 elements"),
-    (bad({("hi", 1, 0): np.inf}), -1, "box 1, coordinate 0: a bound is not finite"),
-    (bad({("lo", 0, 1): np.nan}), -1, "box 0, coordinate 1: a bound is not finite"),
-    (bad({("lo", 1, 1): 0.6}), -1, "box 1, coordinate 1: the lower bound 0.6 is greater than the upper bound 0.5"),
-    (bad({("lo", 1, 0): 0.5, ("lo", 1, 1): 0.5}), -1, "box 1: every coordinate is fixed"),
-    (bad({("init", 1, 2, 1): np.nan}), -1, "init[1][2][1] is not finite"),
-    (bad({("init", 0, 3, 0): np.inf}), -1, "init[0][3][0] is not finite"),
-    (bad({("init", 1, 0, 0): 0.05}), -1, "init[1][0][0] = 0.05 is outside its box [0.1, 0.5]"),       # inside box 0, outside its own
-    (bad({("init", 0, 1, 1): 1.5}), -1, "init[0][1][1] = 1.5 is outside its box [0.01, 1]"),
+FINITE = " (the sampler's prior is uniform on a finite box)"
+TOO_LONG = "the chain of 2 searches x 1000000000 kept steps x 4 walkers x 2 coordinates exceeds INT32_MAX / 8 elements (raise thin)"
+
+
+# (arguments, code, the word the case is named by, the whole text)
+BEHIND = [
+    (bad({}, n_step=10 ** 9, thin=1), -4, "exceeds INT32_MAX / 8 elements", TOO_LONG),
+    (bad({("hi", 1, 0): np.inf}), -1, "box 1, coordinate 0: a bound is not finite", "box 1, coordinate 0: a bound is not finite" + FINITE),
+    (bad({("lo", 0, 1): np.nan}), -1, "box 0, coordinate 1: a bound is not finite", "box 0, coordinate 1: a bound is not finite" + FINITE),
+    (bad({("lo", 1, 1): 0.6}), -1, "box 1, coordinate 1: the lower bound 0.6 is greater than the upper bound 0.5", None),
+    (bad({("lo", 1, 0): 0.5, ("lo", 1, 1): 0.5}), -1, "box 1: every coordinate is fixed", None),
+    (bad({("init", 1, 2, 1): np.nan}), -1, "init[1][2][1] is not finite", None),
+    (bad({("init", 0, 3, 0): np.inf}), -1, "init[0][3][0] is not finite", None),
+    (bad({("init", 1, 0, 0): 0.05}), -1, "init[1][0][0] = 0.05 is outside its box [0.1, 0.5]", None),       # inside box 0, outside its own
+    (bad({("init", 0, 1, 1): 1.5}), -1, "init[0][1][1] = 1.5 is outside its box [0.01, 1]", None),
     # the order: the chain limit before the box, the box before init, a lower box index and walker first
-    (bad({("hi", 1, 0): np.inf, ("init", 0, 0, 0): np.nan}, n_step=10 ** 9), -4, "exceeds INT32_MAX / 8"),
-    (bad({("lo", 1, 1): 0.6, ("init", 0, 0, 0): np.nan}), -1, "lower bound"),
-    (bad({("lo", 0, 0): 2.0, ("hi", 1, 0): np.inf}), -1, "box 0, coordinate 0: the lower bound"),
-    (bad({("init", 0, 3, 1): 7.0, ("init", 1, 0, 0): np.nan}), -1, "init[0][3][1]"),
-])
-def test_errors_behind_the_context_come_in_the_headers_order_and_write_nothing(two_rates, case, code, word):
+    (bad({("hi", 1, 0): np.inf, ("init", 0, 0, 0): np.nan}, n_step=10 ** 9), -4, "exceeds INT32_MAX / 8", TOO_LONG),
+    (bad({("lo", 1, 1): 0.6, ("init", 0, 0, 0): np.nan}), -1, "lower bound", "box 1, coordinate 1: the lower bound 0.6 is greater than the upper bound 0.5"),
+    (bad({("lo", 0, 0): 2.0, ("hi", 1, 0): np.inf}), -1, "box 0, coordinate 0: the lower bound", "box 0, coordinate 0: the lower bound 2 is greater than the upper bound 1"),
+    (bad({("init", 0, 3, 1): 7.0, ("init", 1, 0, 0): np.nan}), -1, "init[0][3][1]", "init[0][3][1] = 7 is outside its box [0.01, 1]"),
+]
+
+
+@pytest.mark.parametrize("case, code, word, text", BEHIND, ids=["case%d-%d-%s" % (i, c[1], c[2]) for i, c in enumerate(BEHIND)])
+def test_errors_behind_the_context_come_in_the_headers_order_and_write_nothing(two_rates, case, code, word, text):
     kw = dict(case)
     rc, why, out = raw_call(two_rates, kw.pop("init"), ROWS[:2], kw.pop("lo"), kw.pop("hi"), SPLITS[:2], **kw)
-    assert rc == code and word in why, (rc, why)
+    assert (rc, why) == (code, text or word)             # None: the word is the whole text already
     assert untouched(out)
 
 
@@ -283,7 +291,7 @@ def test_the_limits_of_the_model_and_the_accepted_descriptor(grid, two_rates):
     # a model without an optimised parameter has no coordinate at a split per search
     with engine(grid, [(0, 2, -1, 0.2, -1)]) as e:
         rc, why, out = raw_call(e, np.zeros((1, 4, 0)), ROWS[:1], np.zeros((1, 0)), np.zeros((1, 0)), SPLITS[:1])
-        assert rc == -1 and "no optimised parameter" in why and untouched(out)
+        assert (rc, why) == (-1, "the model has no optimised parameter") and untouched(out)
 
 
 def test_no_step_returns_the_initial_ensemble_with_its_values(two_rates):

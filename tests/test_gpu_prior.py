@@ -259,29 +259,32 @@ def raw_call(eng, entry, init, prior, n_prior, lo=LO, hi=HI):
 @pytest.mark.parametrize("entry", ["ensemble", "tempered"])
 def test_refusals_behind_the_context_write_nothing(two_rates, mixed, entry):
     init = mixed[0]
+    SCALE_2 = "prior of search 1, coordinate 0: the scale 2 is neither MISTI_COORD_LINEAR nor MISTI_COORD_LOG"
     bad = lambda **kw: {k: np.array(kw.get(k, PRIOR[k]), dtype=PRIOR[k].dtype) for k in PRIOR}
 
     def at(k, s, c, v):
         a = PRIOR[k].copy()
         a[s, c] = v
         return {k: a}
-    cases = [(bad(**at("scale", 1, 0, 2)), 3, HI, "search 1, coordinate 0: the scale 2"),
-             (bad(**at("kind", 2, 1, 7)), 3, HI, "search 2, coordinate 1: the kind 7"),
-             (bad(**at("p1", 0, 1, 0.0)), 3, HI, "search 0, coordinate 1: the normal's sd"),
-             (bad(**at("p0", 2, 0, np.inf)), 3, HI, "search 2, coordinate 0: the exponential's scale"),
-             (bad(**at("p0", 0, 1, np.nan)), 3, HI, "search 0, coordinate 1: the normal's mean"),
-             ({k: v[0] for k, v in PRIOR.items()}, 1, np.array([[710.0, 1.0], HI[1], HI[2]]), "search 0, coordinate 0: the log-scale box"),
+    cases = [(bad(**at("scale", 1, 0, 2)), 3, HI, SCALE_2),
+             (bad(**at("kind", 2, 1, 7)), 3, HI, "prior of search 2, coordinate 1: the kind 7 is none of MISTI_PRIOR_FLAT / NORMAL / EXPONENTIAL"),
+             (bad(**at("p1", 0, 1, 0.0)), 3, HI, "prior of search 0, coordinate 1: the normal's sd 0 is not finite and positive"),
+             (bad(**at("p0", 2, 0, np.inf)), 3, HI, "prior of search 2, coordinate 0: the exponential's scale inf is not finite and positive"),
+             (bad(**at("p0", 0, 1, np.nan)), 3, HI, "prior of search 0, coordinate 1: the normal's mean is not finite"),
+             ({k: v[0] for k, v in PRIOR.items()}, 1, np.array([[710.0, 1.0], HI[1], HI[2]]), 
+              "prior of search 0, coordinate 0: the log-scale box [-4.60517, 710] leaves [-745, 709] - its natural value would leave the doubles"),
              # the box's refusals come first, the walkers' last
-             (bad(**at("scale", 1, 0, 2)), 3, np.array([[np.inf, 1.0], HI[1], HI[2]]), "box 0, coordinate 0: a bound is not finite")]
-    for prior, n_prior, hi, word in cases:
+             (bad(**at("scale", 1, 0, 2)), 3, np.array([[np.inf, 1.0], HI[1], HI[2]]), 
+              "box 0, coordinate 0: a bound is not finite (the sampler's prior is uniform on a finite box)")]
+    for prior, n_prior, hi, text in cases:
         rc, why, untouched = raw_call(two_rates, entry, init, prior, n_prior, hi=hi)
-        assert rc == -1 and word in why and untouched, (word, why)
+        assert (rc, why) == (-1, text) and untouched
     worse = init.copy()
     worse[2, 3, 0] = 0.001
     rc, why, untouched = raw_call(two_rates, entry, worse, bad(**at("scale", 1, 0, 2)), 3)
-    assert rc == -1 and "the scale 2" in why and untouched
+    assert (rc, why) == (-1, SCALE_2) and untouched
     rc, why, untouched = raw_call(two_rates, entry, worse, PRIOR, 3)
-    assert rc == -1 and "is outside its box" in why and untouched
+    assert (rc, why) == (-1, "init[2]%s[3][0] = 0.001 is outside its box [0.01, 1]" % ("" if entry == "ensemble" else "[0]")) and untouched
     rc, why, untouched = raw_call(two_rates, entry, init, PRIOR, 3)
     assert rc == 0 and not untouched, why
 

@@ -1,8 +1,9 @@
-"""Every refusal misti_search, misti_de_search and misti_ensemble_sample make before they look at a context, with its exact code and
-its exact misti_last_error() text - the three doors share their checks of the rows problem (rows, split times, the limits, the
-box), and of two faults each names the one its header puts first.  The existing tests (test_search_cpu.py, test_de_cpu.py,
-test_ens_cpu.py, whose descriptor builders these are) assert a code and one word per refusal; the texts below are the library's
-as they stood before the checks were shared."""
+"""Every refusal misti_search, misti_de_search, misti_ensemble_sample and misti_tempered_sample make before they look at a context, and
+the prior-shape refusals of the two samplers' prior doors, with its exact code and its exact misti_last_error() text - the doors share
+their checks of the rows problem (rows, split times, the limits, the box), the two samplers share one check altogether, and of two
+faults each names the one its header puts first.  The existing tests (test_search_cpu.py, test_de_cpu.py, test_ens_cpu.py,
+test_pt_cpu.py, test_prior_cpu.py, whose descriptor builders these are) assert a code and one word per refusal; the texts below are
+the library's as they stood before the checks were shared."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,8 @@ import pytest
 import search_forms as F
 from test_de_cpu import de_search
 from test_ens_cpu import ens_sample
+from test_prior_cpu import sample_prior
+from test_pt_cpu import pt_sample
 from test_search_cpu import _full
 
 E_ARG, E_LIMIT = -1, -4
@@ -32,6 +35,8 @@ def nm_search(form="misti_nm_solve_box", fitted=False, split=None, **change):
 
 ROWS_PER, ROWS_FIT, ONE, HOP = "misti_nm_solve_box", "misti_nm_solve_split", "misti_nm_solve", "misti_basinhopping_box"
 I32 = lambda *v: np.array(v, dtype=np.int32)      # noqa: E731
+
+PT_NULL = "init / rows / jsfs / box_lo / box_hi / ladder / last / last_llh / rung_llh / logz"
 
 CASES = [
     # ---- misti_search -------------------------------------------------------------------------------------------------------------
@@ -124,6 +129,76 @@ CASES = [
     (ens_sample, dict(temperature=[-1.0, 1.0], rows=[0, 9]), E_ARG, "temperature[0] = -1 is not finite and positive"),
     (ens_sample, dict(n_box=3, split_times=[INF, 5.0]), E_ARG, "n_box must be 1 or n_start (got 3 for 2 searches)"),
     (ens_sample, dict(rows=[0, 3], split_times=[INF, 5.0]), E_ARG, "split_times[0] is not finite"),
+    # ---- misti_tempered_sample: every case of test_pt_cpu.py::test_tempered_sample_argument_checks --------------------------------
+    (pt_sample, dict(), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(n_start=0, n_box=0), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(n_step=0, burn=7), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(n_rung=1), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(n_rung=64), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(swap_every=0), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(n_ladder=2), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(size=8), E_ARG, "the sampler descriptor's size is 8, this library's misti_pt_t has 240 bytes"),
+    (pt_sample, dict(split=0), E_ARG, "the sampler descriptor's split mode 0 is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED"),
+    (pt_sample, dict(n_start=-1), E_ARG, "negative number of fits"),
+    (pt_sample, dict(null=("init",)), E_ARG, PT_NULL + " / split_times is NULL"),
+    (pt_sample, dict(null=("ladder",)), E_ARG, PT_NULL + " / split_times is NULL"),
+    (pt_sample, dict(null=("rung_llh",)), E_ARG, PT_NULL + " / split_times is NULL"),
+    (pt_sample, dict(null=("logz",)), E_ARG, PT_NULL + " / split_times is NULL"),
+    (pt_sample, dict(null=("split_times",)), E_ARG, PT_NULL + " / split_times is NULL"),
+    (pt_sample, dict(null=("split_times",), split=2), E_ARG, "ctx is NULL"),
+    (pt_sample, dict(null=("last",), split=2), E_ARG, PT_NULL + " is NULL"),
+    (pt_sample, dict(n_rep=0), E_ARG, "n_rep must be >= 1 (got 0)"),
+    (pt_sample, dict(walkers=5), E_ARG, "walkers must be even and >= 4 (got 5)"),
+    (pt_sample, dict(walkers=258), E_LIMIT, "walkers = 258 exceeds MISTI_ENS_MAX_WALKERS = 256"),
+    (pt_sample, dict(n_step=-1), E_ARG, "n_step must not be negative"),
+    (pt_sample, dict(thin=0), E_ARG, "thin must be >= 1"),
+    (pt_sample, dict(a=1.0), E_ARG, "a must be finite and > 1 (got 1)"),
+    (pt_sample, dict(n_rung=0), E_ARG, "n_rung must be >= 1 (got 0)"),
+    (pt_sample, dict(n_rung=65), E_LIMIT, "n_rung = 65 exceeds MISTI_PT_MAX_RUNGS = 64"),
+    (pt_sample, dict(n_ladder=3), E_ARG, "n_ladder must be 1 or n_start (got 3 for 2 fits)"),
+    (pt_sample, dict(ladder=[[0.0, 1.0, 2.0], [1.0, 2.0, 3.0]]), E_ARG, "ladder[0][0] = 0 is not finite and positive"),
+    (pt_sample, dict(ladder=[[1.0, INF, 2.0], [1.0, 2.0, 3.0]]), E_ARG, "ladder[0][1] = inf is not finite and positive"),
+    (pt_sample, dict(ladder=[[1.0, 2.0, 2.0], [1.0, 2.0, 3.0]]), E_ARG, "ladder[0][2] = 2 is not above ladder[0][1] = 2: a ladder is strictly increasing"),
+    (pt_sample, dict(n_ladder=2, ladder=[[1.0, 2.0, 3.0], [1.0, 3.0, 2.5]]), E_ARG,
+     "ladder[1][2] = 2.5 is not above ladder[1][1] = 3: a ladder is strictly increasing"),
+    (pt_sample, dict(n_ladder=2, ladder=[[1.0, 2.0, 3.0], [1.0, NAN, 2.5]]), E_ARG, "ladder[1][1] = nan is not finite and positive"),
+    (pt_sample, dict(swap_every=-1), E_ARG, "swap_every must not be negative (got -1)"),
+    (pt_sample, dict(burn=3), E_ARG, "burn must be 0 ... K - 1 (got 3 for 3 kept steps)"),
+    (pt_sample, dict(burn=-1), E_ARG, "burn must be 0 ... K - 1 (got -1 for 3 kept steps)"),
+    (pt_sample, dict(n_box=3), E_ARG, "n_box must be 1 or n_start (got 3 for 2 fits)"),
+    (pt_sample, dict(rows=[0, 3]), E_ARG, "rows[1] = 3 is outside the table (n_rep = 3)"),
+    (pt_sample, dict(split_times=[5.0, INF]), E_ARG, "split_times[1] is not finite"),
+    # two faults
+    (pt_sample, dict(a=0.5, n_rung=0), E_ARG, "a must be finite and > 1 (got 0.5)"),
+    (pt_sample, dict(n_rung=0, n_ladder=3), E_ARG, "n_rung must be >= 1 (got 0)"),
+    (pt_sample, dict(n_rung=65, n_ladder=3), E_LIMIT, "n_rung = 65 exceeds MISTI_PT_MAX_RUNGS = 64"),
+    (pt_sample, dict(n_ladder=3, swap_every=-1), E_ARG, "n_ladder must be 1 or n_start (got 3 for 2 fits)"),
+    (pt_sample, dict(ladder=[[1.0, 1.0, 2.0], [1.0, 2.0, 3.0]], swap_every=-1), E_ARG,
+     "ladder[0][1] = 1 is not above ladder[0][0] = 1: a ladder is strictly increasing"),
+    (pt_sample, dict(swap_every=-1, burn=9), E_ARG, "swap_every must not be negative (got -1)"),
+    (pt_sample, dict(burn=9, n_box=3), E_ARG, "burn must be 0 ... K - 1 (got 9 for 3 kept steps)"),
+    (pt_sample, dict(burn=9, rows=[0, 9]), E_ARG, "burn must be 0 ... K - 1 (got 9 for 3 kept steps)"),
+    # ---- the prior's shape at both samplers' prior doors: behind n_box, before the context ------------------------------------------
+    (sample_prior, dict(entry="ensemble", prior=1), E_ARG, "ctx is NULL"),
+    (sample_prior, dict(entry="tempered", prior=2), E_ARG, "ctx is NULL"),
+    (sample_prior, dict(entry="ensemble", prior=1, size=8), E_ARG, "the prior descriptor's size is 8, this library's misti_prior_t has 40 bytes"),
+    (sample_prior, dict(entry="tempered", prior=1, size=8), E_ARG, "the prior descriptor's size is 8, this library's misti_prior_t has 40 bytes"),
+    (sample_prior, dict(entry="ensemble", prior=3), E_ARG, "n_prior must be 1 or n_start (got 3 for 2 searches)"),
+    (sample_prior, dict(entry="tempered", prior=3), E_ARG, "n_prior must be 1 or n_start (got 3 for 2 fits)"),
+    (sample_prior, dict(entry="ensemble", prior=0), E_ARG, "n_prior must be 1 or n_start (got 0 for 2 searches)"),
+    (sample_prior, dict(entry="tempered", prior=0), E_ARG, "n_prior must be 1 or n_start (got 0 for 2 fits)"),
+    (sample_prior, dict(entry="ensemble", prior=1, null=("scale",)), E_ARG, "the prior's scale / kind / p0 / p1 is NULL"),
+    (sample_prior, dict(entry="tempered", prior=1, null=("kind",)), E_ARG, "the prior's scale / kind / p0 / p1 is NULL"),
+    (sample_prior, dict(entry="ensemble", prior=2, null=("p0",)), E_ARG, "the prior's scale / kind / p0 / p1 is NULL"),
+    (sample_prior, dict(entry="tempered", prior=2, null=("p1",)), E_ARG, "the prior's scale / kind / p0 / p1 is NULL"),
+    # two faults
+    (sample_prior, dict(entry="ensemble", prior=1, size=8, split=0), E_ARG, "the prior descriptor's size is 8, this library's misti_prior_t has 40 bytes"),
+    (sample_prior, dict(entry="ensemble", prior=3, n_box=3), E_ARG, "n_box must be 1 or n_start (got 3 for 2 searches)"),
+    (sample_prior, dict(entry="tempered", prior=3, n_box=3), E_ARG, "n_box must be 1 or n_start (got 3 for 2 fits)"),
+    (sample_prior, dict(entry="ensemble", prior=3, null=("scale",)), E_ARG, "n_prior must be 1 or n_start (got 3 for 2 searches)"),
+    (sample_prior, dict(entry="tempered", prior=3, null=("scale",)), E_ARG, "n_prior must be 1 or n_start (got 3 for 2 fits)"),
+    (sample_prior, dict(entry="tempered", prior=3, thin=0), E_ARG, "thin must be >= 1"),
+    (sample_prior, dict(entry="ensemble", prior=3, n_rep=0), E_ARG, "n_rep must be >= 1 (got 0)"),
 ]
 
 
