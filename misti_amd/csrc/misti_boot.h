@@ -43,3 +43,13 @@ __host__ __device__ __forceinline__ void philox4x64_10_block(uint64_t key0, uint
 __host__ __device__ __forceinline__ int64_t boot_index(uint64_t raw, int64_t n_chunk) { return (int64_t)boot_mulhi(raw, (uint64_t)n_chunk); }
 
 }  // namespace misti
+
+// ---- the host part (misti_boot.hip), shared with the jackknife (misti_jack.hip) ----------------------------------------------------------
+struct misti_ctx;
+namespace misti_host __attribute__((visibility("hidden"))) {
+// What every entry of a chunk table must be, whoever resamples it - finite, a length > 0, no negative count, sums that stay finite -
+// and the sums themselves with the shortest length.  The bootstrap's draw limit is not part of it.
+int chunk_entries(int64_t n_chunk, const double* chunks, double* genome, double* seg, double* shortest);
+// The table of `bytes` bytes into the context's chunk buffer (c->boot_chunks), on its stream and with its device current.
+int upload_chunks(misti_ctx* c, size_t bytes, const double* chunks);
+}  // namespace misti_host

@@ -6,15 +6,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
-#include "../../include/misti_hip.h"
 #include "misti_boot.h"
-
-extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp: sets the calling thread's misti_last_error
-// misti_api.cpp: makes the context's device current and hands out its stream and its buffer for the chunk table, grown to `bytes`
-extern "C" int misti_boot_ctx_(misti_ctx* ctx, size_t bytes, void** stream, void** d_chunks);
+#include "misti_ctx.h"
 
 namespace misti {
 
@@ -67,38 +61,35 @@ void bootstrap_rows_kernel(int n_chunk, const double* __restrict__ chunks, doubl
 
 }  // namespace misti
 
-namespace {
+using namespace misti_host;
 
-int failb(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return misti_set_error_(code, buf);
-}
-
-}  // namespace
-
-// internal (misti_jack.hip shares it): what every entry of a chunk table must be, whoever resamples it - finite, a length > 0, no negative
-// count, sums that stay finite - and the sums themselves with the shortest length.  The bootstrap's draw limit is not part of it.
-extern "C" int misti_chunk_entries_(int64_t n_chunk, const double* chunks, double* genome, double* seg, double* shortest_out) {
+int misti_host::chunk_entries(int64_t n_chunk, const double* chunks, double* genome, double* seg, double* shortest_out) {
     double g = 0.0, sg = 0.0, shortest = INFINITY;
     for (int64_t i = 0; i < n_chunk; ++i) {
         const double* c = chunks + i * 8;
         for (int k = 0; k < 8; ++k)
-            if (!std::isfinite(c[k])) return failb(MISTI_E_ARG, "chunks[%lld][%d] is not finite", (long long)i, k);
-        if (!(c[0] > 0.0)) return failb(MISTI_E_ARG, "chunks[%lld][0] = %g: a chunk's length must be > 0", (long long)i, c[0]);
+            if (!std::isfinite(c[k])) return fail(MISTI_E_ARG, "chunks[%lld][%d] is not finite", (long long)i, k);
+        if (!(c[0] > 0.0)) return fail(MISTI_E_ARG, "chunks[%lld][0] = %g: a chunk's length must be > 0", (long long)i, c[0]);
         for (int k = 1; k < 8; ++k)
-            if (c[k] < 0.0) return failb(MISTI_E_ARG, "chunks[%lld][%d] = %g: a count must not be negative", (long long)i, k, c[k]);
+            if (c[k] < 0.0) return fail(MISTI_E_ARG, "chunks[%lld][%d] = %g: a count must not be negative", (long long)i, k, c[k]);
         g += c[0];
         sg += (((((c[1] + c[2]) + c[3]) + c[4]) + c[5]) + c[6]) + c[7];
         shortest = c[0] < shortest ? c[0] : shortest;
     }
-    if (!std::isfinite(g) || !std::isfinite(sg)) return failb(MISTI_E_ARG, "the chunk lengths or counts do not sum to a finite number");
+    if (!std::isfinite(g) || !std::isfinite(sg)) return fail(MISTI_E_ARG, "the chunk lengths or counts do not sum to a finite number");
     *genome = g;
     *seg = sg;
     *shortest_out = shortest;
+    return 0;
+}
+
+// A table that grows frees the old buffer, which waits for the device: no kernel of an earlier call still reads it.
+int misti_host::upload_chunks(misti_ctx* c, size_t bytes, const double* chunks) {
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->boot_chunks.reserve(bytes));
+    // (the caller's table is pageable host memory: the runtime has taken its bytes when this returns)
+    hipError_t e = hipMemcpyAsync(c->boot_chunks.p, chunks, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return fail(MISTI_E_HIP, "hipMemcpyAsync of the chunk table: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -108,11 +99,11 @@ namespace {
 // running sum over the chunks of ((c1 + c2) + ... + c7).
 int check_chunks(int64_t n_chunk, const double* chunks, double* genome, double* seg) {
     double shortest = INFINITY;
-    if (int r = misti_chunk_entries_(n_chunk, chunks, genome, seg, &shortest)) return r;
+    if (int r = chunk_entries(n_chunk, chunks, genome, seg, &shortest)) return r;
     const double g = *genome;
     // the most draws a replicate can need; the comparison is made in floating point, where an infinite quotient is simply too large
     if (!(std::ceil(g / shortest) <= (double)MISTI_BOOT_MAX_DRAWS))
-        return failb(MISTI_E_LIMIT, "a replicate may need ceil(%g / %g) draws, beyond MISTI_BOOT_MAX_DRAWS = %d", g, shortest, (int)MISTI_BOOT_MAX_DRAWS);
+        return fail(MISTI_E_LIMIT, "a replicate may need ceil(%g / %g) draws, beyond MISTI_BOOT_MAX_DRAWS = %d", g, shortest, (int)MISTI_BOOT_MAX_DRAWS);
     return 0;
 }
 
@@ -123,44 +114,40 @@ extern "C" {
 int misti_bootstrap_rows_dev(misti_ctx* ctx, int64_t n_chunk, const double* chunks, uint64_t seed, int64_t first_rep, int64_t n_rep, uint32_t flags,
                              double* d_rows, int32_t* d_draws) {
     // everything that can be said about the arguments is said before the context is looked at
-    if (n_chunk < 1) return failb(MISTI_E_ARG, "n_chunk must be at least 1 (got %lld)", (long long)n_chunk);
-    if (n_rep < 0 || first_rep < 0) return failb(MISTI_E_ARG, "negative n_rep or first_rep");
-    if (flags & ~MISTI_BOOT_NORMALIZE) return failb(MISTI_E_ARG, "unknown flag bits 0x%x", (unsigned)(flags & ~MISTI_BOOT_NORMALIZE));
-    if (n_chunk > MISTI_BOOT_MAX_CHUNKS) return failb(MISTI_E_LIMIT, "n_chunk beyond MISTI_BOOT_MAX_CHUNKS = %d (got %lld)", (int)MISTI_BOOT_MAX_CHUNKS, (long long)n_chunk);
-    if (n_rep > INT32_MAX || first_rep > INT64_MAX - n_rep) return failb(MISTI_E_LIMIT, "too many replicates for one call");
-    if (n_rep > 0 && (!chunks || !d_rows)) return failb(MISTI_E_ARG, "chunks / rows is NULL");
+    if (n_chunk < 1) return fail(MISTI_E_ARG, "n_chunk must be at least 1 (got %lld)", (long long)n_chunk);
+    if (n_rep < 0 || first_rep < 0) return fail(MISTI_E_ARG, "negative n_rep or first_rep");
+    if (flags & ~MISTI_BOOT_NORMALIZE) return fail(MISTI_E_ARG, "unknown flag bits 0x%x", (unsigned)(flags & ~MISTI_BOOT_NORMALIZE));
+    if (n_chunk > MISTI_BOOT_MAX_CHUNKS) return fail(MISTI_E_LIMIT, "n_chunk beyond MISTI_BOOT_MAX_CHUNKS = %d (got %lld)", (int)MISTI_BOOT_MAX_CHUNKS, (long long)n_chunk);
+    if (n_rep > INT32_MAX || first_rep > INT64_MAX - n_rep) return fail(MISTI_E_LIMIT, "too many replicates for one call");
+    if (n_rep > 0 && (!chunks || !d_rows)) return fail(MISTI_E_ARG, "chunks / rows is NULL");
     double genome = 0.0, seg = 0.0;
     if (chunks)
         if (int r = check_chunks(n_chunk, chunks, &genome, &seg)) return r;
-    if (!ctx) return failb(MISTI_E_ARG, "ctx is NULL");
+    if (!ctx) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_rep == 0) return 0;
     const size_t bytes = (size_t)n_chunk * 8 * sizeof(double);
-    void* stream = nullptr;
-    void* d_chunks = nullptr;
-    if (int r = misti_boot_ctx_(ctx, bytes, &stream, &d_chunks)) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // (the caller's table is pageable host memory: the runtime has taken its bytes when this returns)
-    hipError_t e = hipMemcpyAsync(d_chunks, chunks, bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return failb(MISTI_E_HIP, "hipMemcpyAsync of the chunk table: %s", hipGetErrorString(e));
+    if (int r = upload_chunks(ctx, bytes, chunks)) return r;
+    hipStream_t s = ctx->stream;
+    const double* d_chunks = ctx->boot_chunks.as<double>();
     const dim3 grid((unsigned)((n_rep + 255) / 256)), block(256);
     const int normalize = (flags & MISTI_BOOT_NORMALIZE) ? 1 : 0;
     if (n_chunk <= misti::BOOT_STAGED_MAX_CHUNKS)
-        hipLaunchKernelGGL(misti::bootstrap_rows_kernel<true>, grid, block, bytes, s, (int)n_chunk, static_cast<const double*>(d_chunks), genome, seg, seed,
+        hipLaunchKernelGGL(misti::bootstrap_rows_kernel<true>, grid, block, bytes, s, (int)n_chunk, d_chunks, genome, seg, seed,
                            first_rep, n_rep, normalize, (int)MISTI_BOOT_MAX_DRAWS, d_rows, d_draws);
     else
-        hipLaunchKernelGGL(misti::bootstrap_rows_kernel<false>, grid, block, 0, s, (int)n_chunk, static_cast<const double*>(d_chunks), genome, seg, seed,
+        hipLaunchKernelGGL(misti::bootstrap_rows_kernel<false>, grid, block, 0, s, (int)n_chunk, d_chunks, genome, seg, seed,
                            first_rep, n_rep, normalize, (int)MISTI_BOOT_MAX_DRAWS, d_rows, d_draws);
-    e = hipGetLastError();
-    if (e != hipSuccess) return failb(MISTI_E_HIP, "bootstrap_rows_kernel: %s", hipGetErrorString(e));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MISTI_E_HIP, "bootstrap_rows_kernel: %s", hipGetErrorString(e));
     return 0;
 }
 
 int misti_bootstrap_draws(uint64_t seed, int64_t rep, int64_t n_chunk, int64_t n, int64_t* idx) {
-    if (rep < 0 || n < 0) return failb(MISTI_E_ARG, "negative rep or n");
-    if (n_chunk < 1) return failb(MISTI_E_ARG, "n_chunk must be at least 1 (got %lld)", (long long)n_chunk);
-    if (n_chunk > MISTI_BOOT_MAX_CHUNKS) return failb(MISTI_E_LIMIT, "n_chunk beyond MISTI_BOOT_MAX_CHUNKS = %d (got %lld)", (int)MISTI_BOOT_MAX_CHUNKS, (long long)n_chunk);
-    if (n > MISTI_BOOT_MAX_DRAWS) return failb(MISTI_E_LIMIT, "n beyond MISTI_BOOT_MAX_DRAWS = %d (got %lld)", (int)MISTI_BOOT_MAX_DRAWS, (long long)n);
-    if (n > 0 && !idx) return failb(MISTI_E_ARG, "idx is NULL");
+    if (rep < 0 || n < 0) return fail(MISTI_E_ARG, "negative rep or n");
+    if (n_chunk < 1) return fail(MISTI_E_ARG, "n_chunk must be at least 1 (got %lld)", (long long)n_chunk);
+    if (n_chunk > MISTI_BOOT_MAX_CHUNKS) return fail(MISTI_E_LIMIT, "n_chunk beyond MISTI_BOOT_MAX_CHUNKS = %d (got %lld)", (int)MISTI_BOOT_MAX_CHUNKS, (long long)n_chunk);
+    if (n > MISTI_BOOT_MAX_DRAWS) return fail(MISTI_E_LIMIT, "n beyond MISTI_BOOT_MAX_DRAWS = %d (got %lld)", (int)MISTI_BOOT_MAX_DRAWS, (long long)n);
+    if (n > 0 && !idx) return fail(MISTI_E_ARG, "idx is NULL");
     for (int64_t j = 0; j < n; j += 4) {
         uint64_t raw[4];
         misti::philox4x64_10_block(seed, (uint64_t)rep, (uint64_t)(j >> 2), raw);

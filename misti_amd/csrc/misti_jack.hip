@@ -4,16 +4,8 @@
 // The reference has no counterpart (its confidence statement is the bootstrap's t-interval, test.bs/bs_conf_int.ipynb).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
-#include "../../include/misti_hip.h"
-
-extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp: sets the calling thread's misti_last_error
-// misti_api.cpp: makes the context's device current and hands out its stream and its buffer for the chunk table, grown to `bytes`
-extern "C" int misti_boot_ctx_(misti_ctx* ctx, size_t bytes, void** stream, void** d_chunks);
-// misti_boot.hip: what every entry of a chunk table must be (finite, a length > 0, no negative count, finite sums), with the bootstrap's messages
-extern "C" int misti_chunk_entries_(int64_t n_chunk, const double* chunks, double* genome, double* seg, double* shortest);
+#include "misti_boot.h"
+#include "misti_ctx.h"
 
 namespace misti {
 
@@ -62,23 +54,16 @@ void jackknife_rows_kernel(int n_chunk, const double* __restrict__ chunks, int m
 
 }  // namespace misti
 
-namespace {
+using namespace misti_host;
 
-int failj(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return misti_set_error_(code, buf);
-}
+namespace {
 
 // What both entry points say about (n_chunk, m): 0 and *G = ceil(n_chunk / m), or the code.
 int check_groups(int64_t n_chunk, int64_t m, int64_t* G) {
-    if (n_chunk < 2) return failj(MISTI_E_ARG, "n_chunk must be at least 2 (got %lld): one chunk leaves nothing behind", (long long)n_chunk);
-    if (m < 1) return failj(MISTI_E_ARG, "m must be at least 1 (got %lld)", (long long)m);
-    if (m >= n_chunk) return failj(MISTI_E_ARG, "m = %lld of n_chunk = %lld: a single group would leave nothing behind", (long long)m, (long long)n_chunk);
-    if (n_chunk > MISTI_BOOT_MAX_CHUNKS) return failj(MISTI_E_LIMIT, "n_chunk beyond MISTI_BOOT_MAX_CHUNKS = %d (got %lld)", (int)MISTI_BOOT_MAX_CHUNKS, (long long)n_chunk);
+    if (n_chunk < 2) return fail(MISTI_E_ARG, "n_chunk must be at least 2 (got %lld): one chunk leaves nothing behind", (long long)n_chunk);
+    if (m < 1) return fail(MISTI_E_ARG, "m must be at least 1 (got %lld)", (long long)m);
+    if (m >= n_chunk) return fail(MISTI_E_ARG, "m = %lld of n_chunk = %lld: a single group would leave nothing behind", (long long)m, (long long)n_chunk);
+    if (n_chunk > MISTI_BOOT_MAX_CHUNKS) return fail(MISTI_E_LIMIT, "n_chunk beyond MISTI_BOOT_MAX_CHUNKS = %d (got %lld)", (int)MISTI_BOOT_MAX_CHUNKS, (long long)n_chunk);
     *G = (n_chunk + m - 1) / m;
     return 0;
 }
@@ -92,38 +77,32 @@ int misti_jackknife_rows_dev(misti_ctx* ctx, int64_t n_chunk, const double* chun
     // everything that can be said about the arguments is said before the context is looked at
     int64_t G = 0;
     if (int r = check_groups(n_chunk, m, &G)) return r;
-    if (n_group < 0 || first_group < 0) return failj(MISTI_E_ARG, "negative n_group or first_group");
+    if (n_group < 0 || first_group < 0) return fail(MISTI_E_ARG, "negative n_group or first_group");
     if (first_group > G || n_group > G - first_group)
-        return failj(MISTI_E_ARG, "groups %lld ... %lld of G = %lld", (long long)first_group, (long long)first_group + (long long)n_group - 1, (long long)G);
-    if (flags) return failj(MISTI_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
-    if (n_group > 0 && (!chunks || !d_rows)) return failj(MISTI_E_ARG, "chunks / rows is NULL");
+        return fail(MISTI_E_ARG, "groups %lld ... %lld of G = %lld", (long long)first_group, (long long)first_group + (long long)n_group - 1, (long long)G);
+    if (flags) return fail(MISTI_E_ARG, "unknown flag bits 0x%x", (unsigned)flags);
+    if (n_group > 0 && (!chunks || !d_rows)) return fail(MISTI_E_ARG, "chunks / rows is NULL");
     if (chunks) {
         double genome = 0.0, seg = 0.0, shortest = 0.0;   // (the bootstrap's draw limit has no meaning here: nothing is drawn)
-        if (int r = misti_chunk_entries_(n_chunk, chunks, &genome, &seg, &shortest)) return r;
+        if (int r = chunk_entries(n_chunk, chunks, &genome, &seg, &shortest)) return r;   // (with the bootstrap's messages)
     }
-    if (!ctx) return failj(MISTI_E_ARG, "ctx is NULL");
+    if (!ctx) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_group == 0) return 0;
     const size_t bytes = (size_t)n_chunk * 8 * sizeof(double);
-    void* stream = nullptr;
-    void* d_chunks = nullptr;
-    if (int r = misti_boot_ctx_(ctx, bytes, &stream, &d_chunks)) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // (the caller's table is pageable host memory: the runtime has taken its bytes when this returns)
-    hipError_t e = hipMemcpyAsync(d_chunks, chunks, bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return failj(MISTI_E_HIP, "hipMemcpyAsync of the chunk table: %s", hipGetErrorString(e));
+    if (int r = upload_chunks(ctx, bytes, chunks)) return r;
     const int64_t tile = n_chunk < misti::JACK_TILE_CHUNKS ? n_chunk : misti::JACK_TILE_CHUNKS;
     const dim3 grid((unsigned)((n_group + misti::JACK_THREADS - 1) / misti::JACK_THREADS)), block(misti::JACK_THREADS);
-    hipLaunchKernelGGL(misti::jackknife_rows_kernel, grid, block, (size_t)tile * 8 * sizeof(double), s, (int)n_chunk, static_cast<const double*>(d_chunks),
-                       (int)m, first_group, n_group, d_rows);
-    e = hipGetLastError();
-    if (e != hipSuccess) return failj(MISTI_E_HIP, "jackknife_rows_kernel: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(misti::jackknife_rows_kernel, grid, block, (size_t)tile * 8 * sizeof(double), ctx->stream, (int)n_chunk,
+                       ctx->boot_chunks.as<const double>(), (int)m, first_group, n_group, d_rows);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MISTI_E_HIP, "jackknife_rows_kernel: %s", hipGetErrorString(e));
     return 0;
 }
 
 int misti_jackknife_geometry(int64_t n_chunk, int64_t m, int64_t* n_group) {
     int64_t G = 0;
     if (int r = check_groups(n_chunk, m, &G)) return r;
-    if (!n_group) return failj(MISTI_E_ARG, "n_group is NULL");
+    if (!n_group) return fail(MISTI_E_ARG, "n_group is NULL");
     *n_group = G;
     return 0;
 }

@@ -3,8 +3,6 @@
 // item 5; until round 6 the pool lived in Python, misti_amd/lanes.py).  The reference's counterpart: one MigrationInference object per
 // process, as many processes as cores (/root/reference/MiSTI.py:213-214 under `parallel -j 20`, README.md:110-115).
 // Built on the public single-context entry points; no C++ exception leaves this file.
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <exception>
 #include <new>
@@ -14,8 +12,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/misti_hip.h"
+#include "misti_fail.h"
 
-extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp: sets the calling thread's misti_last_error
 // misti_api.cpp: misti_create on a stream priority.  This and the runtime's priority range are the only things here beyond the public
 // single-context entry points and the event calls, and both are WEAK references: the library always has them; the host-only build of
 // this file against stand-ins (tests/multi_host) has not, and is then a pool on one level made by misti_create, as before the plan.
@@ -25,16 +23,9 @@ extern "C" hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest)
 // lane records its own event behind every batch, as before)
 extern "C" void* misti_batch_event_(misti_ctx* c, int64_t* recorded, int64_t* begun) __attribute__((weak));
 
-namespace {
+using misti_host::fail;
 
-int faill(int code, const char* fmt, ...) {
-    char buf[640];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return misti_set_error_(code, buf);
-}
+namespace {
 
 // A hardware queue per lane where the runtime grants one.  The HIP runtime keeps one pool of hardware queues PER STREAM PRIORITY and
 // opens at most GPU_MAX_HW_QUEUES queues in each (default 4; it says so itself at AMD_LOG_LEVEL=3: "Number of allocated hardware queues
@@ -129,11 +120,11 @@ int guarded(const char* where, F&& fn) noexcept {
     try {
         return fn();
     } catch (const std::bad_alloc&) {
-        return faill(MISTI_E_NOMEM, "%s: out of host memory", where);
+        return fail(MISTI_E_NOMEM, "%s: out of host memory", where);
     } catch (const std::exception& e) {
-        return faill(MISTI_E_ARG, "%s: %s", where, e.what());
+        return fail(MISTI_E_ARG, "%s: %s", where, e.what());
     } catch (...) {
-        return faill(MISTI_E_ARG, "%s: unknown C++ exception", where);
+        return fail(MISTI_E_ARG, "%s: unknown C++ exception", where);
     }
 }
 
@@ -144,7 +135,7 @@ int lane_busy(misti_lanes* L, int i) {
     if (e == hipSuccess) return 0;
     (void)hipGetLastError();
     if (e == hipErrorNotReady) return 1;
-    return faill(MISTI_E_HIP, "hipEventQuery on lane %d: %s", i, hipGetErrorString(e));
+    return fail(MISTI_E_HIP, "hipEventQuery on lane %d: %s", i, hipGetErrorString(e));
 }
 
 void release(misti_lanes* L) {
@@ -160,9 +151,9 @@ void release(misti_lanes* L) {
 extern "C" {
 
 int misti_create_lanes(const misti_model_t* model, int device, int n_lanes, misti_lanes** out) {
-    if (!out) return faill(MISTI_E_ARG, "out is NULL");
+    if (!out) return fail(MISTI_E_ARG, "out is NULL");
     *out = nullptr;
-    if (n_lanes < 1 || n_lanes > MISTI_MAX_LANES) return faill(MISTI_E_LIMIT, "n_lanes %d out of range (1..%d)", n_lanes, MISTI_MAX_LANES);
+    if (n_lanes < 1 || n_lanes > MISTI_MAX_LANES) return fail(MISTI_E_LIMIT, "n_lanes %d out of range (1..%d)", n_lanes, MISTI_MAX_LANES);
     misti_lanes* L = nullptr;
     const int r = guarded("misti_create_lanes", [&]() -> int {
         L = new misti_lanes;
@@ -185,14 +176,14 @@ int misti_create_lanes(const misti_model_t* model, int device, int n_lanes, mist
             L->stream.push_back(static_cast<hipStream_t>(s));
             hipEvent_t e = nullptr;
             const hipError_t he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-            if (he != hipSuccess) return faill(MISTI_E_HIP, "hipEventCreateWithFlags: %s", hipGetErrorString(he));
+            if (he != hipSuccess) return fail(MISTI_E_HIP, "hipEventCreateWithFlags: %s", hipGetErrorString(he));
             L->done.push_back(e);
             L->last.push_back(nullptr);
         }
         return 0;
     });
     if (r != 0) {
-        if (L) { const std::string why = misti_last_error(); release(L); return faill(r, "%s", why.c_str()); }
+        if (L) { const std::string why = misti_last_error(); release(L); return fail(r, "%s", why.c_str()); }
         return r;
     }
     *out = L;
@@ -208,7 +199,7 @@ int misti_destroy_lanes(misti_lanes* L) {
 // internal (tests): the plan without a device.  `queues_per_level` > 0: lane_plan itself with that limit and `max_queues`;
 // 0: what misti_create_lanes would do in this environment on a device with `n_levels` levels.  levels[n_lanes] receives each lane's level.
 int misti_lane_plan_(int n_lanes, int queues_per_level, int n_levels, int max_queues, int* levels) {
-    if (n_lanes < 1 || n_lanes > MISTI_MAX_LANES || n_levels < 1 || !levels) return faill(MISTI_E_ARG, "misti_lane_plan_: bad argument");
+    if (n_lanes < 1 || n_lanes > MISTI_MAX_LANES || n_levels < 1 || !levels) return fail(MISTI_E_ARG, "misti_lane_plan_: bad argument");
     return guarded("misti_lane_plan_", [&]() -> int {
         std::vector<int> level;
         if (queues_per_level > 0) lane_plan(n_lanes, queues_per_level, n_levels, max_queues, level);
@@ -220,34 +211,34 @@ int misti_lane_plan_(int n_lanes, int queues_per_level, int n_levels, int max_qu
 
 // internal (tests): the priority level lane i's stream was created on (0: the default level); < 0: no such lane
 int misti_lanes_level_(misti_lanes* L, int i) {
-    if (!L || i < 0 || i >= (int)L->level.size()) return faill(MISTI_E_ARG, "no such lane");
+    if (!L || i < 0 || i >= (int)L->level.size()) return fail(MISTI_E_ARG, "no such lane");
     return L->level[(size_t)i];
 }
 
 int misti_lanes_size(misti_lanes* L) { return L ? (int)L->ctx.size() : 0; }
 
 int misti_lanes_context(misti_lanes* L, int i, misti_ctx** ctx) {
-    if (!L || !ctx || i < 0 || i >= (int)L->ctx.size()) return faill(MISTI_E_ARG, "no such lane");
+    if (!L || !ctx || i < 0 || i >= (int)L->ctx.size()) return fail(MISTI_E_ARG, "no such lane");
     *ctx = L->ctx[(size_t)i];
     return 0;
 }
 
 int misti_lanes_set_hints(misti_lanes* L, uint32_t hints) {
-    if (!L) return faill(MISTI_E_ARG, "lanes is NULL");
+    if (!L) return fail(MISTI_E_ARG, "lanes is NULL");
     for (misti_ctx* c : L->ctx) if (int r = misti_set_hints(c, hints)) return r;
     return 0;
 }
 
 int misti_lanes_busy(misti_lanes* L, int lane) {
-    if (!L || lane < 0 || lane >= (int)L->ctx.size()) return faill(MISTI_E_ARG, "no such lane");
+    if (!L || lane < 0 || lane >= (int)L->ctx.size()) return fail(MISTI_E_ARG, "no such lane");
     return lane_busy(L, lane);
 }
 
 int misti_lanes_eval_batch_dev(misti_lanes* L, int lane, int64_t n_cand, const double* d_split, const double* d_params, const int32_t* d_bounds,
                                int64_t n_rep, const double* d_jsfs, double* d_llk, double* d_jafs, double* d_lc, double* d_pr, int32_t* d_status, int* lane_used) {
-    if (!L) return faill(MISTI_E_ARG, "lanes is NULL");
+    if (!L) return fail(MISTI_E_ARG, "lanes is NULL");
     const int n = (int)L->ctx.size();
-    if (lane != MISTI_LANE_ANY && (lane < 0 || lane >= n)) return faill(MISTI_E_ARG, "lane %d out of range (0..%d, or MISTI_LANE_ANY)", lane, n - 1);
+    if (lane != MISTI_LANE_ANY && (lane < 0 || lane >= n)) return fail(MISTI_E_ARG, "lane %d out of range (0..%d, or MISTI_LANE_ANY)", lane, n - 1);
     if (lane == MISTI_LANE_ANY) {
         // a lane with nothing in flight, looked for from the round-robin position on; if every lane is busy, the round-robin one
         lane = L->next;
@@ -274,7 +265,7 @@ int misti_lanes_eval_batch_dev(misti_lanes* L, int lane, int64_t n_cand, const d
     } else if (r == 0 || beg1 != beg0) {
         const hipError_t e = hipEventRecord(L->done[(size_t)lane], L->stream[(size_t)lane]);
         if (e == hipSuccess) L->last[(size_t)lane] = L->done[(size_t)lane];
-        else if (r == 0) return faill(MISTI_E_HIP, "hipEventRecord on lane %d: %s", lane, hipGetErrorString(e));
+        else if (r == 0) return fail(MISTI_E_HIP, "hipEventRecord on lane %d: %s", lane, hipGetErrorString(e));
         else (void)hipGetLastError();                    // the batch's own error is the one to report
     }
     if (r != 0) return r;
@@ -295,23 +286,23 @@ int misti_lanes_eval_batch_dev(misti_lanes* L, int lane, int64_t n_cand, const d
 static int wait_done(misti_lanes* L, size_t i) {
     if (!L->last[i]) return 0;
     const hipError_t e = hipEventSynchronize(L->last[i]);
-    if (e != hipSuccess) return faill(MISTI_E_HIP, "hipEventSynchronize on lane %d: %s", (int)i, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MISTI_E_HIP, "hipEventSynchronize on lane %d: %s", (int)i, hipGetErrorString(e));
     return 0;
 }
 
 int misti_lanes_wait(misti_lanes* L, int lane) {
-    if (!L || lane < 0 || lane >= (int)L->ctx.size()) return faill(MISTI_E_ARG, "no such lane");
+    if (!L || lane < 0 || lane >= (int)L->ctx.size()) return fail(MISTI_E_ARG, "no such lane");
     if (int r = wait_done(L, (size_t)lane)) return r;
     return misti_sync(L->ctx[(size_t)lane]);
 }
 
 int misti_lanes_sync(misti_lanes* L) {
-    if (!L) return faill(MISTI_E_ARG, "lanes is NULL");
+    if (!L) return fail(MISTI_E_ARG, "lanes is NULL");
     (void)hipSetDevice(L->device);
     for (size_t i = 0; i < L->ctx.size(); ++i)
         if (int r = wait_done(L, i)) return r;
     for (size_t i = 0; i < L->ctx.size(); ++i)
-        if (int r = misti_sync(L->ctx[i])) { const std::string why = misti_last_error(); return faill(r, "lane %d: %s", (int)i, why.c_str()); }
+        if (int r = misti_sync(L->ctx[i])) { const std::string why = misti_last_error(); return fail(r, "lane %d: %s", (int)i, why.c_str()); }
     return 0;
 }
 

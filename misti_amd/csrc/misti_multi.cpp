@@ -19,8 +19,6 @@
 #include <algorithm>
 #include <cmath>
 #include <condition_variable>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -36,24 +34,17 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/misti_hip.h"
+#include "misti_fail.h"
 
-extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp: sets the calling thread's misti_last_error
 // misti_eval_batch on the rows idx[0 .. n) of the caller's arrays (gathered into the context's pinned block, results scattered
 // back to rows idx[i]): no staging copy in between.  misti_api.cpp; not part of the public ABI.
 extern "C" int misti_eval_batch_indexed_(misti_ctx* ctx, int64_t n, const int64_t* idx, const double* split, const double* params,
                                          const int32_t* band_bounds, int64_t n_rep, const double* jsfs,
                                          double* llk, double* jafs, double* lc, double* pr, int32_t* status);
 
-namespace {
+using misti_host::fail;
 
-int failm(int code, const char* fmt, ...) {
-    char buf[640];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return misti_set_error_(code, buf);
-}
+namespace {
 
 // fn() -> int with every exception turned into an error code + message (never across the ABI, never out of a thread)
 template <class F>
@@ -61,11 +52,11 @@ int guarded(const char* where, F&& fn) noexcept {
     try {
         return fn();
     } catch (const std::bad_alloc&) {
-        return failm(MISTI_E_NOMEM, "%s: out of host memory", where);
+        return fail(MISTI_E_NOMEM, "%s: out of host memory", where);
     } catch (const std::exception& e) {
-        return failm(MISTI_E_ARG, "%s: %s", where, e.what());
+        return fail(MISTI_E_ARG, "%s: %s", where, e.what());
     } catch (...) {
-        return failm(MISTI_E_ARG, "%s: unknown C++ exception", where);
+        return fail(MISTI_E_ARG, "%s: unknown C++ exception", where);
     }
 }
 
@@ -185,7 +176,7 @@ int on_every_device(misti_multi* m, const std::function<int(int)>& fn) {
     const int D = (int)m->ctx.size();
     if (D == 1) {
         const int r = guarded("misti_multi", [&] { return fn(0); });
-        if (r != 0) { const std::string why = misti_last_error(); return failm(r, "device %d (context 0 of 1): %s", m->device[0], why.c_str()); }
+        if (r != 0) { const std::string why = misti_last_error(); return fail(r, "device %d (context 0 of 1): %s", m->device[0], why.c_str()); }
         return 0;
     }
     {
@@ -199,7 +190,7 @@ int on_every_device(misti_multi* m, const std::function<int(int)>& fn) {
         m->job = nullptr;
     }
     for (int d = 0; d < D; ++d)
-        if (m->rc[d] != 0) return failm(m->rc[d], "device %d (context %d of %d): %s", m->device[d], d, D, m->msg[d].c_str());
+        if (m->rc[d] != 0) return fail(m->rc[d], "device %d (context %d of %d): %s", m->device[d], d, D, m->msg[d].c_str());
     return 0;
 }
 
@@ -292,12 +283,12 @@ void deal_chains(misti_multi* m, int64_t n_cand, const double* split, const doub
 extern "C" {
 
 int misti_create_multi(const misti_model_t* model, int n_dev, const int* devices, misti_multi** out) {
-    if (!model || !out) return failm(MISTI_E_ARG, "model / out is NULL");
-    if (n_dev < 1 || !devices) return failm(MISTI_E_ARG, "the device list is empty");
+    if (!model || !out) return fail(MISTI_E_ARG, "model / out is NULL");
+    if (n_dev < 1 || !devices) return fail(MISTI_E_ARG, "the device list is empty");
     const int have = misti_device_count();
-    if (have < 1) return failm(MISTI_E_NODEV, "no usable HIP device");
+    if (have < 1) return fail(MISTI_E_NODEV, "no usable HIP device");
     for (int d = 0; d < n_dev; ++d)
-        if (devices[d] < 0 || devices[d] >= have) return failm(MISTI_E_ARG, "device %d is not one of the %d visible HIP devices", devices[d], have);
+        if (devices[d] < 0 || devices[d] >= have) return fail(MISTI_E_ARG, "device %d is not one of the %d visible HIP devices", devices[d], have);
     misti_multi* m = nullptr;
     const int r = guarded("misti_create_multi", [&]() -> int {
         m = new misti_multi;
@@ -305,7 +296,7 @@ int misti_create_multi(const misti_model_t* model, int n_dev, const int* devices
         for (int d = 0; d < n_dev; ++d) {
             misti_ctx* c = nullptr;
             const int q = misti_create(model, devices[d], &c);
-            if (q != 0) { const std::string why = misti_last_error(); return failm(q, "device %d: %s", devices[d], why.c_str()); }
+            if (q != 0) { const std::string why = misti_last_error(); return fail(q, "device %d: %s", devices[d], why.c_str()); }
             m->ctx.push_back(c);
             m->device.push_back(devices[d]);
         }
@@ -327,7 +318,7 @@ int misti_create_multi(const misti_model_t* model, int n_dev, const int* devices
             m->shutdown();
             for (misti_ctx* q : m->ctx) (void)misti_destroy(q);
             delete m;
-            return failm(r, "%s", why.c_str());
+            return fail(r, "%s", why.c_str());
         }
         return r;
     }
@@ -353,7 +344,7 @@ int misti_destroy_multi(misti_multi* m) {
 // with an error code and message while the process, the workers and later calls live on.  Nothing in the library reads the environment
 // for it any more (a set variable made every multi call of a production process fail).
 int misti_multi_test_throw_in_worker_(misti_multi* m, int d) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     m->throw_in_worker = d;
     return 0;
@@ -362,14 +353,14 @@ int misti_multi_test_throw_in_worker_(misti_multi* m, int d) {
 int misti_multi_size(misti_multi* m) { return m ? (int)m->ctx.size() : 0; }
 
 int misti_multi_context(misti_multi* m, int i, misti_ctx** ctx, int* device) {
-    if (!m || i < 0 || i >= (int)m->ctx.size()) return failm(MISTI_E_ARG, "no such context");
+    if (!m || i < 0 || i >= (int)m->ctx.size()) return fail(MISTI_E_ARG, "no such context");
     if (ctx) *ctx = m->ctx[i];
     if (device) *device = m->device[i];
     return 0;
 }
 
 int misti_multi_last_shards(misti_multi* m, int64_t* n_cand, int64_t* n_chain) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     for (size_t d = 0; d < m->ctx.size(); ++d) {
         if (n_cand) n_cand[d] = m->last_cands[d];
@@ -379,34 +370,34 @@ int misti_multi_last_shards(misti_multi* m, int64_t* n_cand, int64_t* n_chain) {
 }
 
 int misti_multi_last_cost(misti_multi* m, double* cost) {
-    if (!m || !cost) return failm(MISTI_E_ARG, "multi context / cost is NULL");
+    if (!m || !cost) return fail(MISTI_E_ARG, "multi context / cost is NULL");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     for (size_t d = 0; d < m->ctx.size(); ++d) cost[d] = m->last_cost[d];
     return 0;
 }
 
 int misti_multi_sync(misti_multi* m) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     for (size_t d = 0; d < m->ctx.size(); ++d) {
         const int r = misti_sync(m->ctx[d]);
-        if (r != 0) { const std::string why = misti_last_error(); return failm(r, "device %d (context %d): %s", m->device[d], (int)d, why.c_str()); }
+        if (r != 0) { const std::string why = misti_last_error(); return fail(r, "device %d (context %d): %s", m->device[d], (int)d, why.c_str()); }
     }
     return 0;
 }
 
 int misti_multi_eval_batch(misti_multi* m, int64_t n_cand, const double* split, const double* params, const int32_t* band_bounds,
                            int64_t n_rep, const double* jsfs, double* llk, double* jafs, double* lc, double* pr, int32_t* status) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
-    if (n_cand < 0 || n_rep < 0) return failm(MISTI_E_ARG, "negative batch size");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
+    if (n_cand < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative batch size");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     const int D = (int)m->ctx.size();
     for (int d = 0; d < D; ++d) { m->last_cands[d] = m->last_chains[d] = 0; m->last_cost[d] = 0.0; }
     if (n_cand == 0) return 0;
-    if (!split) return failm(MISTI_E_ARG, "split_time is NULL");
+    if (!split) return fail(MISTI_E_ARG, "split_time is NULL");
     const int P = m->n_param;
-    if (P > 0 && !params) return failm(MISTI_E_ARG, "params is NULL but the model has %d parameters", P);
-    if (n_rep > 0 && (!jsfs || !llk)) return failm(MISTI_E_ARG, "jsfs / llk is NULL with n_rep > 0");
+    if (P > 0 && !params) return fail(MISTI_E_ARG, "params is NULL but the model has %d parameters", P);
+    if (n_rep > 0 && (!jsfs || !llk)) return fail(MISTI_E_ARG, "jsfs / llk is NULL with n_rep > 0");
     if (D == 1) {
         m->last_cands[0] = n_cand;
         return misti_eval_batch(m->ctx[0], n_cand, split, params, band_bounds, n_rep, jsfs, llk, jafs, lc, pr, status);
@@ -429,17 +420,17 @@ int misti_multi_eval_batch(misti_multi* m, int64_t n_cand, const double* split, 
 int misti_multi_eval_batch_dev(misti_multi* m, const int64_t* n_cand, int64_t rows_per_shard,
                                const double* const* d_split_time, const double* const* d_params, const int32_t* const* d_band_bounds,
                                int64_t n_rep, const double* const* d_jsfs, double* const* d_llk_all, int32_t* const* d_status_all) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
-    if (!n_cand || !d_split_time || !d_llk_all || !d_jsfs) return failm(MISTI_E_ARG, "n_cand / d_split_time / d_jsfs / d_llk_all is NULL");
-    if (n_rep < 1) return failm(MISTI_E_ARG, "the gathered form needs at least one replicate");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
+    if (!n_cand || !d_split_time || !d_llk_all || !d_jsfs) return fail(MISTI_E_ARG, "n_cand / d_split_time / d_jsfs / d_llk_all is NULL");
+    if (n_rep < 1) return fail(MISTI_E_ARG, "the gathered form needs at least one replicate");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     const int D = (int)m->ctx.size(), P = m->n_param;
-    if (P > 0 && !d_params) return failm(MISTI_E_ARG, "d_params is NULL but the model has %d parameters", P);
+    if (P > 0 && !d_params) return fail(MISTI_E_ARG, "d_params is NULL but the model has %d parameters", P);
     bool repeated = false;
     for (int d = 0; d < D; ++d) {
-        if (n_cand[d] < 0 || n_cand[d] > rows_per_shard) return failm(MISTI_E_ARG, "shard %d: %lld candidates do not fit rows_per_shard = %lld", d, (long long)n_cand[d], (long long)rows_per_shard);
-        if (!d_llk_all[d] || !d_jsfs[d] || (n_cand[d] > 0 && (!d_split_time[d] || (P > 0 && !d_params[d])))) return failm(MISTI_E_ARG, "shard %d: a device pointer is NULL", d);
-        if (d_status_all && !d_status_all[d]) return failm(MISTI_E_ARG, "shard %d: d_status_all is NULL", d);
+        if (n_cand[d] < 0 || n_cand[d] > rows_per_shard) return fail(MISTI_E_ARG, "shard %d: %lld candidates do not fit rows_per_shard = %lld", d, (long long)n_cand[d], (long long)rows_per_shard);
+        if (!d_llk_all[d] || !d_jsfs[d] || (n_cand[d] > 0 && (!d_split_time[d] || (P > 0 && !d_params[d])))) return fail(MISTI_E_ARG, "shard %d: a device pointer is NULL", d);
+        if (d_status_all && !d_status_all[d]) return fail(MISTI_E_ARG, "shard %d: d_status_all is NULL", d);
         for (int e = 0; e < d; ++e) if (m->device[e] == m->device[d]) repeated = true;
     }
     // an RCCL communicator holds every device once (ncclCommInitAll refuses a repeated entry); only the tests' double, which copies
@@ -448,17 +439,17 @@ int misti_multi_eval_batch_dev(misti_multi* m, const int64_t* n_cand, int64_t ro
         Rccl* R = rccl();
         if (!R->test_double)
             for (int d = 0; d < D; ++d) for (int e = 0; e < d; ++e)
-                if (m->device[e] == m->device[d]) return failm(MISTI_E_ARG, "device %d is listed twice: an RCCL communicator holds every device once", m->device[d]);
+                if (m->device[e] == m->device[d]) return fail(MISTI_E_ARG, "device %d is listed twice: an RCCL communicator holds every device once", m->device[d]);
     }
     if (rows_per_shard == 0) return 0;
     return guarded("misti_multi_eval_batch_dev", [&]() -> int {
         Rccl* R = rccl();
-        if (!R->handle || !R->why.empty()) return failm(MISTI_E_NODEV, "%s", R->why.c_str());
+        if (!R->handle || !R->why.empty()) return fail(MISTI_E_NODEV, "%s", R->why.c_str());
         if (m->comm.empty()) {
             // one communicator over the device list, created once per multi context (ncclCommInitAll: all ranks in this process)
             std::vector<void*> comms(D, nullptr);
             const int q = R->CommInitAll(comms.data(), D, m->device.data());
-            if (q != 0) return failm(MISTI_E_HIP, "ncclCommInitAll over %d devices: %s", D, R->GetErrorString(q));
+            if (q != 0) return fail(MISTI_E_HIP, "ncclCommInitAll over %d devices: %s", D, R->GetErrorString(q));
             m->comm = comms;
         }
         const size_t blk = (size_t)rows_per_shard * (size_t)n_rep;
@@ -473,14 +464,14 @@ int misti_multi_eval_batch_dev(misti_multi* m, const int64_t* n_cand, int64_t ro
             // (a worker thread starts on device 0) and, with one context - this IS the caller's thread - put back afterwards
             int before = -1;
             (void)hipGetDevice(&before);
-            if (hipSetDevice(m->device[d]) != hipSuccess) return failm(MISTI_E_HIP, "hipSetDevice(%d) failed", m->device[d]);
+            if (hipSetDevice(m->device[d]) != hipSuccess) return fail(MISTI_E_HIP, "hipSetDevice(%d) failed", m->device[d]);
             struct Restore { int dev; ~Restore() { if (dev >= 0) (void)hipSetDevice(dev); } } restore{D == 1 ? before : -1};
             double* mine = d_llk_all[d] + (size_t)d * blk;
             const size_t used = (size_t)n_cand[d] * (size_t)n_rep;
-            if (used < blk && hipMemsetAsync(mine + used, 0xFF, (blk - used) * sizeof(double), s) != hipSuccess) return failm(MISTI_E_HIP, "hipMemsetAsync failed");
+            if (used < blk && hipMemsetAsync(mine + used, 0xFF, (blk - used) * sizeof(double), s) != hipSuccess) return fail(MISTI_E_HIP, "hipMemsetAsync failed");
             int32_t* st = d_status_all ? d_status_all[d] + (size_t)d * (size_t)rows_per_shard : nullptr;
             if (st && n_cand[d] < rows_per_shard &&
-                hipMemsetAsync(st + n_cand[d], 0xFF, (size_t)(rows_per_shard - n_cand[d]) * sizeof(int32_t), s) != hipSuccess) return failm(MISTI_E_HIP, "hipMemsetAsync failed");
+                hipMemsetAsync(st + n_cand[d], 0xFF, (size_t)(rows_per_shard - n_cand[d]) * sizeof(int32_t), s) != hipSuccess) return fail(MISTI_E_HIP, "hipMemsetAsync failed");
             if (n_cand[d] == 0) return 0;
             return misti_eval_batch_dev(m->ctx[d], n_cand[d], d_split_time[d], P > 0 ? d_params[d] : nullptr, d_band_bounds ? d_band_bounds[d] : nullptr,
                                         n_rep, d_jsfs[d], mine, nullptr, nullptr, nullptr, st);
@@ -498,7 +489,7 @@ int misti_multi_eval_batch_dev(misti_multi* m, const int64_t* n_cand, int64_t ro
         }
         const int qe = R->GroupEnd();
         if (q == 0) q = qe;
-        if (q != 0) return failm(MISTI_E_HIP, "ncclAllGather: %s", R->GetErrorString(q));
+        if (q != 0) return fail(MISTI_E_HIP, "ncclAllGather: %s", R->GetErrorString(q));
         for (int d = 0; d < D; ++d) m->last_cands[d] = n_cand[d];
         return 0;
     });
@@ -508,10 +499,10 @@ int misti_multi_eval_batch_dev(misti_multi* m, const int64_t* n_cand, int64_t ro
 // same time.  A start's trajectory does not depend on what else is in its batches, so the result equals the single-device call's.
 int misti_multi_nm_solve(misti_multi* m, int64_t n_start, const double* starts, double split_time, const double* jsfs_row,
                          double xatol, double fatol, int32_t maxiter, double* x, double* llh, int32_t* nit, int32_t* nfev, int32_t* status) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
-    if (n_start < 0) return failm(MISTI_E_ARG, "negative number of starts");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
+    if (n_start < 0) return fail(MISTI_E_ARG, "negative number of starts");
     if (n_start == 0) return 0;
-    if (!starts || !jsfs_row || !x || !llh) return failm(MISTI_E_ARG, "starts / jsfs_row / x / llh is NULL");
+    if (!starts || !jsfs_row || !x || !llh) return fail(MISTI_E_ARG, "starts / jsfs_row / x / llh is NULL");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     return guarded("misti_multi_nm_solve", [&]() -> int {
         const int D = (int)m->ctx.size(), N = m->n_param;
@@ -531,10 +522,10 @@ int misti_multi_basinhopping(misti_multi* m, int64_t n_start, const double* star
                              int32_t niter, double T, double stepsize, int32_t interval, double target_accept_rate, double stepwise_factor,
                              double xatol, double fatol, int32_t nm_maxiter, int64_t nm_maxfev, const double* uniforms,
                              double* x, double* llh, int32_t* nfev, int32_t* failures, int32_t* accepted) {
-    if (!m) return failm(MISTI_E_ARG, "multi context is NULL");
-    if (n_start < 0 || niter < 0) return failm(MISTI_E_ARG, "negative number of starts / hops");
+    if (!m) return fail(MISTI_E_ARG, "multi context is NULL");
+    if (n_start < 0 || niter < 0) return fail(MISTI_E_ARG, "negative number of starts / hops");
     if (n_start == 0) return 0;
-    if (!starts || !jsfs_row || !x || !llh || (niter > 0 && !uniforms)) return failm(MISTI_E_ARG, "starts / jsfs_row / uniforms / x / llh is NULL");
+    if (!starts || !jsfs_row || !x || !llh || (niter > 0 && !uniforms)) return fail(MISTI_E_ARG, "starts / jsfs_row / uniforms / x / llh is NULL");
     std::lock_guard<std::mutex> one_call(m->call_mu);
     return guarded("misti_multi_basinhopping", [&]() -> int {
         const int D = (int)m->ctx.size(), N = m->n_param;

@@ -11,16 +11,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
-#include "../../include/misti_hip.h"
+#include "misti_ctx.h"
 #include "misti_parametric.h"
 #include "misti_score.h"
-
-extern "C" int misti_set_error_(int code, const char* msg);     // misti_api.cpp: sets the calling thread's misti_last_error
-// misti_api.cpp: makes the context's device current and hands out its stream and its buffer for the draw counts, grown to `bytes`
-extern "C" int misti_param_ctx_(misti_ctx* ctx, size_t bytes, void** stream, void** d_totals);
 
 namespace misti {
 
@@ -159,67 +153,56 @@ void parametric_finish_kernel(int64_t n_spec, const double* __restrict__ spectra
 
 }  // namespace misti
 
-namespace {
-
-int failp(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return misti_set_error_(code, buf);
-}
-
-}  // namespace
+using namespace misti_host;
 
 extern "C" {
 
-int misti_parametric_rows_dev(misti_ctx* ctx, int64_t n_spec, const double* d_spectra, const int32_t* d_status, const int32_t* d_spec_of,
+int misti_parametric_rows_dev(misti_ctx* c, int64_t n_spec, const double* d_spectra, const int32_t* d_status, const int32_t* d_spec_of,
                               double genome, int64_t n_sites, uint64_t seed, int64_t first_rep, int64_t n_rep, double* d_rows,
                               int32_t* d_row_status) {
     // everything that can be said about the arguments is said before the context is looked at
-    if (n_spec < 1) return failp(MISTI_E_ARG, "n_spec must be at least 1 (got %lld)", (long long)n_spec);
-    if (n_sites < 0 || n_rep < 0 || first_rep < 0) return failp(MISTI_E_ARG, "negative n_sites, n_rep or first_rep");
-    if (!std::isfinite(genome)) return failp(MISTI_E_ARG, "genome is not finite");
-    if (n_sites > MISTI_PARAM_MAX_SITES) return failp(MISTI_E_LIMIT, "n_sites beyond MISTI_PARAM_MAX_SITES = 2^36 (got %lld)", (long long)n_sites);
-    if (n_rep > INT32_MAX || first_rep > INT64_MAX - n_rep) return failp(MISTI_E_LIMIT, "too many replicates for one call");
-    if (n_rep > 0 && (!d_spectra || !d_rows)) return failp(MISTI_E_ARG, "spectra / rows is NULL");
-    if (!ctx) return failp(MISTI_E_ARG, "ctx is NULL");
+    if (n_spec < 1) return fail(MISTI_E_ARG, "n_spec must be at least 1 (got %lld)", (long long)n_spec);
+    if (n_sites < 0 || n_rep < 0 || first_rep < 0) return fail(MISTI_E_ARG, "negative n_sites, n_rep or first_rep");
+    if (!std::isfinite(genome)) return fail(MISTI_E_ARG, "genome is not finite");
+    if (n_sites > MISTI_PARAM_MAX_SITES) return fail(MISTI_E_LIMIT, "n_sites beyond MISTI_PARAM_MAX_SITES = 2^36 (got %lld)", (long long)n_sites);
+    if (n_rep > INT32_MAX || first_rep > INT64_MAX - n_rep) return fail(MISTI_E_LIMIT, "too many replicates for one call");
+    if (n_rep > 0 && (!d_spectra || !d_rows)) return fail(MISTI_E_ARG, "spectra / rows is NULL");
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
     if (n_rep == 0) return 0;
     const int64_t slice = n_rep < misti::PARAM_SLICE ? n_rep : misti::PARAM_SLICE;
     const size_t bytes = (size_t)slice * 6 * sizeof(unsigned long long);
-    void* stream = nullptr;
-    void* d_totals = nullptr;
-    if (int r = misti_param_ctx_(ctx, bytes, &stream, &d_totals)) return r;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    unsigned long long* totals = static_cast<unsigned long long*>(d_totals);
+    // (a buffer that grows frees the old one, which waits for the device: no kernel of an earlier call still adds to it)
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->param_totals.reserve(bytes));
+    hipStream_t s = c->stream;
+    unsigned long long* totals = c->param_totals.as<unsigned long long>();
     const unsigned bpr = (unsigned)misti::param_blocks_per_rep(n_sites, n_rep);
     // slices of at most 65 535 replicates, one behind the other on the stream: each zeroes the counts, counts, and writes its rows
     for (int64_t r0 = 0; r0 < n_rep; r0 += misti::PARAM_SLICE) {
         const int64_t n = n_rep - r0 < misti::PARAM_SLICE ? n_rep - r0 : misti::PARAM_SLICE;
         const int32_t* spec_of = d_spec_of ? d_spec_of + r0 : nullptr;
         hipError_t e = hipMemsetAsync(totals, 0, (size_t)n * 6 * sizeof(unsigned long long), s);
-        if (e != hipSuccess) return failp(MISTI_E_HIP, "hipMemsetAsync of the draw counts: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(MISTI_E_HIP, "hipMemsetAsync of the draw counts: %s", hipGetErrorString(e));
         if (n_sites > 0)
             hipLaunchKernelGGL(misti::parametric_count_kernel, dim3(bpr, (unsigned)n), dim3(misti::PARAM_THREADS), 0, s, n_spec, d_spectra, d_status,
                                spec_of, n_sites, seed, first_rep + r0, totals);
         hipLaunchKernelGGL(misti::parametric_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_spec, d_spectra, d_status, spec_of,
                            genome, n_sites, n, totals, d_rows + r0 * 8, d_row_status ? d_row_status + r0 : nullptr);
         e = hipGetLastError();
-        if (e != hipSuccess) return failp(MISTI_E_HIP, "parametric_count_kernel / parametric_finish_kernel: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(MISTI_E_HIP, "parametric_count_kernel / parametric_finish_kernel: %s", hipGetErrorString(e));
     }
     return 0;
 }
 
 int misti_parametric_thresholds(const double p[7], uint64_t T[6]) {
-    if (!p || !T) return failp(MISTI_E_ARG, "p / T is NULL");
+    if (!p || !T) return fail(MISTI_E_ARG, "p / T is NULL");
     return misti::param_thresholds(p, T) ? 0 : 1;
 }
 
 int misti_parametric_counts(const double p[7], int64_t n_sites, uint64_t seed, int64_t rep, int64_t counts[7]) {
-    if (n_sites < 0 || rep < 0) return failp(MISTI_E_ARG, "negative n_sites or rep");
-    if (n_sites > MISTI_PARAM_MAX_SITES) return failp(MISTI_E_LIMIT, "n_sites beyond MISTI_PARAM_MAX_SITES = 2^36 (got %lld)", (long long)n_sites);
-    if (!p || !counts) return failp(MISTI_E_ARG, "p / counts is NULL");
+    if (n_sites < 0 || rep < 0) return fail(MISTI_E_ARG, "negative n_sites or rep");
+    if (n_sites > MISTI_PARAM_MAX_SITES) return fail(MISTI_E_LIMIT, "n_sites beyond MISTI_PARAM_MAX_SITES = 2^36 (got %lld)", (long long)n_sites);
+    if (!p || !counts) return fail(MISTI_E_ARG, "p / counts is NULL");
     for (int k = 0; k < 7; ++k) counts[k] = 0;
     uint64_t T[6];
     if (!misti::param_thresholds(p, T)) return 1;
@@ -232,9 +215,9 @@ int misti_parametric_counts(const double p[7], int64_t n_sites, uint64_t seed, i
 }
 
 int misti_parametric_geometry(int64_t n_sites, int64_t n_rep, int32_t* blocks_per_rep) {
-    if (n_sites < 0 || n_rep < 0) return failp(MISTI_E_ARG, "negative n_sites or n_rep");
-    if (n_sites > MISTI_PARAM_MAX_SITES || n_rep > INT32_MAX) return failp(MISTI_E_LIMIT, "n_sites beyond MISTI_PARAM_MAX_SITES = 2^36 or n_rep beyond INT32_MAX");
-    if (!blocks_per_rep) return failp(MISTI_E_ARG, "blocks_per_rep is NULL");
+    if (n_sites < 0 || n_rep < 0) return fail(MISTI_E_ARG, "negative n_sites or n_rep");
+    if (n_sites > MISTI_PARAM_MAX_SITES || n_rep > INT32_MAX) return fail(MISTI_E_LIMIT, "n_sites beyond MISTI_PARAM_MAX_SITES = 2^36 or n_rep beyond INT32_MAX");
+    if (!blocks_per_rep) return fail(MISTI_E_ARG, "blocks_per_rep is NULL");
     *blocks_per_rep = (int32_t)misti::param_blocks_per_rep(n_sites, n_rep);
     return 0;
 }

@@ -219,7 +219,7 @@ def test_header_keeps_abi_6_and_declares_the_two_entries():
         m = re.search(r"^int %s\(([^;]*)\);" % name, text, flags=re.M)
         assert m, name
         assert len(m.group(1).split(",")) == n_args == len(_lib.SYMBOLS[name][1]), name
-    api = open(os.path.join(ROOT, "misti_amd", "csrc", "misti_api.cpp")).read()
+    api = open(os.path.join(ROOT, "misti_amd", "csrc", "misti_curv.cpp")).read()
     assert "int misti_curvature(" in api and "int misti_curvature_assemble_dev(" in api
 
 

@@ -1,5 +1,5 @@
 """What the plain and the tempered ensemble sampler share on the host: one check, one run and one carve of the context's search
-buffers (misti_api.cpp: SamplerArgs, sampler_run).  Seven calls one after another on ONE context, consecutive calls carving layouts
+buffers (misti_sampler.cpp: SamplerArgs, sampler_run).  Seven calls one after another on ONE context, consecutive calls carving layouts
 of different sizes and different optional parts - rungs, the reduction's arrays, the swap counters, a prior's arrays, the summaries'
 workspace, a chain kept on the device or not at all - and every one of them must equal the same call on a fresh context, field by
 field and bit for bit; the first and the last call are the same call; and the tempered call of one rung is the plain call.  Once with
