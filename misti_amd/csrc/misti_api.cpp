@@ -327,7 +327,7 @@ int run_dev_impl(misti_ctx* c, int64_t n_cand, const double* d_split, const doub
         const int busy_from = c->tune.busy_contexts >= 0 ? c->tune.busy_contexts : misti::FOLLOW_BUSY_CONTEXTS;
         if (yield_nfev > 0 && busy_from > 0 && busy() >= busy_from) yield_nfev = 0;
     }
-    // Two phases behind a packed launch that lets chains yield (--cpfit; misti_kernels.hip: wrong_phase): what waits for the chains that launch
+    // Two phases behind a packed launch that lets chains yield (--cpfit; misti_chain.h: wrong_phase): what waits for the chains that launch
     // completed - trunks, tails, the candidate kernel of their members: 91 % of BASELINE config 3 - runs on a second stream BESIDE the resume
     // launch, which is one chain latency long and leaves most of the chip idle; the members of the chains that yielded follow behind it on the
     // batch's own stream, which then waits for the second one.  MISTI_TWO_PHASE=0 keeps everything on one stream.
@@ -521,7 +521,7 @@ int misti_create_prio_(const misti_model_t* model, int device, int priority, mis
             std::memcpy(runs.data() + (2 + k) * numT, re.data(), sizeof(int) * numT);
         }
         {
-            // Where can a candidate leave its chain's trunk?  (trunk_leave in misti_kernels.hip, for every split an integer or a
+            // Where can a candidate leave its chain's trunk?  (trunk_leave in misti_model.h, for every split an integer or a
             // fractional split time can produce.)  A function of the smoothing runs alone: the trunk stores records only there.
             const int* rs0 = runs.data(), *rs1 = runs.data() + numT, *re0 = runs.data() + 2 * numT, *re1 = runs.data() + 3 * numT;
             std::vector<int> ok((size_t)numT, 0);

@@ -14,6 +14,20 @@ constexpr int MAXPULSE = 12;          // entries per row of the pulse operator
 #ifndef MISTI_SMALL_LAUNCH_PRIO
 #define MISTI_SMALL_LAUNCH_PRIO 1
 #endif
+// Defaults of the other build switches that take a value (misti_kernels.hip and its headers; the ones that are only defined or not -
+// MISTI_STAMP, MISTI_STAMP2, MISTI_TREE_STATS, MISTI_NO_STALL_RULE, MISTI_NO_NOISE_RULE - have none):
+#ifndef MISTI_WORK_COUNTERS
+#define MISTI_WORK_COUNTERS 0         // 1: diagnostic build that also counts the per-lane work of a chain (Diag, misti_model.h)
+#endif
+#ifndef MISTI_NOISE_PROBE
+#define MISTI_NOISE_PROBE 1           // 0: diagnostic build, the default fit's noise rule from its width model alone (correct_body, misti_chain.h)
+#endif
+#ifndef MISTI_DEFAULT_FIT_WAVES
+#define MISTI_DEFAULT_FIT_WAVES 1     // waves per SIMD of the default fit's packed chain kernel (correct_kernel)
+#endif
+#ifndef MISTI_FOLLOW_WAVES
+#define MISTI_FOLLOW_WAVES 2          // waves per SIMD of the --cpfit one-chain-per-wave kernels (correct_follow_kernel, correct_resume_kernel)
+#endif
 constexpr int WAVES_PER_BLOCK = MISTI_WAVES_PER_BLOCK;    // candidates per workgroup of kernel 2 (one wavefront each)
 constexpr int TALBOT_N = 28;           // nodes of the Talbot contour (conjugate pairs folded: TALBOT_HALF solves)
 constexpr int TALBOT_HALF = TALBOT_N / 2;

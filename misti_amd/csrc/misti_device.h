@@ -1,4 +1,4 @@
-// Shared between the kernels (misti_kernels.hip) and the C-ABI host layer (misti_api.cpp).
+// Shared between the kernels (misti_kernels.hip and its headers) and the C-ABI host layer (misti_api.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -52,7 +52,7 @@ def pulse(v, pu0, pu1):
 
 
 class Grid:
-    """A candidate's view of the model's grid and its status, by the header's rules (setup_candidate, misti_kernels.hip)."""
+    """A candidate's view of the model's grid and its status, by the header's rules (setup_candidate, misti_model.h)."""
 
     def __init__(self, times, lh, bands, split_time, params, sample_date=0):
         numT0 = len(lh)

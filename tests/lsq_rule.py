@@ -1,4 +1,4 @@
-"""The solver's linear algebra (the "least squares" section of misti_amd/csrc/misti_kernels.hip and its helpers) restated in Python,
+"""The solver's linear algebra (the "least squares" unit, misti_amd/csrc/misti_lsq.h) restated in Python,
 operation for operation: the counterpart of tests/pair_branches.py for misti_lsq_probe.
 
 Every function takes a KIT of arithmetic as its first argument.  With F64 the operations are numpy's float64 - correctly rounded

@@ -1,4 +1,4 @@
-"""The branch choice of the pair-chain residual (pair_eval -> pair_expv / pair_reduced, misti_kernels.hip) restated in plain float64
+"""The branch choice of the pair-chain residual (pair_eval -> pair_expv / pair_reduced, misti_pair.h) restated in plain float64
 Python, and float64 restatements of its cascade, Taylor and uniformisation forms: what tests/golden/make_pair_branches.py labels
 the fixtures with, and what tests/test_pair_branches_cpu.py holds to the same bounds as the device.  Every product that decides a
 branch is exact or a single rounding in both places (2 * x is exact), so the labels are the device's branches to the bit."""

@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 # candidates with a value on both sides, those within 1e-9, FIRST-PASS outside (against the compiled baseline, SELF_FACTOR = 3: round 4's
 # factor 10 gave 0 / 10 / 0 / 1).  Every first-pass outlier carries a reference-run study and lies inside the contract against the REFERENCE.
 MEASURED = {"config2": dict(both=4096, tight=3584, outside=0),
-            "config2:default": dict(both=3264, tight=6, outside=19),       # before the stall rule (misti_kernels.hip: correct_body): tight 0, outside 23
+            "config2:default": dict(both=3264, tight=6, outside=19),       # before the stall rule (misti_chain.h: correct_body): tight 0, outside 23
             # the HELD-OUT instance of the headline grid (workloads.config2b: other PSMC curves, another true history; made at the end of round 5)
             "config2b": dict(both=4096, tight=3359, outside=15),           # one chain (rate index 35), rate x length 509 ... 672: reference-studied, golden_config2b.json
             # ... and the SECOND held-out instance, made after the stall rule (workloads.config2c): the whole grids by tools/fullsize_report.py - --cpfit 4 096 / 3 512 tight /

@@ -200,7 +200,7 @@ def test_held_out_grid_config2b(case):
     """`config2b` (misti_amd/workloads.py): the headline grid's shape on OTHER data - other PSMC curves, another true history, another truth - made at the end of
     round 5, after every kernel, rule and tolerance was fixed.  Its first pass under the default fit (270 of 3 430 candidates outside at factor 3, 8 of them
     sampled through the reference: 3 beyond 3 x, up to 5.5 x its own spread) is what found the reference's STALLED solves on very short intervals (the stall rule,
-    misti_kernels.hip: correct_body); with the rule none of 3 429 is outside.  Here: those 8 and the 15 candidates (one chain) the --cpfit first pass
+    misti_chain.h: correct_body); with the rule none of 3 429 is outside.  Here: those 8 and the 15 candidates (one chain) the --cpfit first pass
     leaves outside, each against the REFERENCE's own value and spreads (16 + 16 runs; --cpfit: 64 + 16 + 16)."""
     check(case)
 

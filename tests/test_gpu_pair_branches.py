@@ -1,4 +1,4 @@
-"""Every branch of the pair chain's exponential (pair_expv, misti_kernels.hip) against 50-digit arithmetic through the forward map
+"""Every branch of the pair chain's exponential (pair_expv, misti_pair.h) against 50-digit arithmetic through the forward map
 (misti_forward_rates: one exp(M T) v per genome and interval, no solver): the seven Taylor classes and their edges, the
 uniformisation series and its hand-over at nbmax = 6, the one-way closed form in divided differences (pair_cascade, both
 directions, rate x length up to 3e5, coinciding rates) - and the claim that a lane's bits do not depend on its company in the wave.

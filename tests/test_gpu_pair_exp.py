@@ -1,4 +1,4 @@
-"""The pair chain's exponential with migration in BOTH directions (pair_eigen, misti_kernels.hip: the closed form over the three
+"""The pair chain's exponential with migration in BOTH directions (pair_eigen, misti_pair.h: the closed form over the three
 eigenvalues of the symmetrisable generator, CorrectLambda.py:55-62) against 50-digit arithmetic, through the forward map of the C ABI
 (misti_forward_rates: one exp(M T) v per genome and interval, no solver): stiff generators - rate x length up to 3e5 - strong, weak and
 lopsided migration, coinciding poles (d0 == d1), and the non-stiff neighbours that take the series."""

@@ -243,3 +243,23 @@ def test_cli_rejects_gpus_together_with_devices(capsys):
     from misti_amd import cli
     rc = cli.main(["a.psmc", "b.psmc", "d.sfs", "20", "--grid-st", "18", "20", "--gpus", "2", "--devices", "0,1"])
     assert rc == 2 and "exclude each other" in capsys.readouterr().err
+
+
+def test_every_included_project_header_is_in_the_build_lists():
+    """`build.stale()` and `build.source_hash()` (the build id) read `build.SOURCES + build.HEADERS` and nothing else: a header one of
+    those files includes but the lists do not name could change without a rebuild and without a new build id.  Every
+    `#include "misti_*.h"`, `#include "misti_*.hpp"` and `#include "../../include/..."` in a listed file therefore names a listed header,
+    and the file exists."""
+    from misti_amd import build
+    headers = {os.path.normpath(h) for h in build.HEADERS}
+    seen = 0
+    for f in build.SOURCES + build.HEADERS:
+        path = os.path.join(build.CSRC, f)
+        assert os.path.isfile(path), f
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"((?:misti_[^"]*\.(?:h|hpp))|(?:\.\./\.\./include/[^"]*))"', open(path).read(), flags=re.M):
+            seen += 1
+            # a quoted include is looked up beside the including file; every listed file but the public header stands in csrc/
+            target = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+            assert target in headers, "%s includes %s, which build.HEADERS does not list" % (f, inc)
+            assert os.path.isfile(os.path.join(build.CSRC, target)), (f, inc)
+    assert seen > 20          # the pattern still finds the includes it is about

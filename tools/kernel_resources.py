@@ -16,7 +16,7 @@ def main():
     cmd = [build.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-gpu-rdc", "-ffp-contract=on", "--cuda-device-only", "-c",
            "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null"]
     rows = {}
-    for src in ("misti_kernels.hip", "misti_score.hip", "misti_nm.hip", "misti_parametric.hip"):
+    for src in (s for s in build.SOURCES if s.endswith(".hip")):
         out = subprocess.run(cmd + ["-x", "hip", os.path.join(build.CSRC, src)], capture_output=True, text=True).stderr
         cur = None
         for line in out.splitlines():

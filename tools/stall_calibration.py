@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where does the REFERENCE's default-fit solve of one two-population interval stall?  (build container only: imports /root/reference)
 
-The stall rule of the HIP path (misti_kernels.hip: correct_body) returns the starting point where  rho = 0.29 W / (h max|J|) > 1,  W = eps / (1.4 min(d0, d1)^2) the
+The stall rule of the HIP path (misti_chain.h: correct_body) returns the starting point where  rho = 0.29 W / (h max|J|) > 1,  W = eps / (1.4 min(d0, d1)^2) the
 modelled noise width of the reference's residual, h = 1.5e-8 the forward-difference step, J the noise-free Jacobian at the start.  The reference's own traces in the
 fixtures hold solves at rho >= 2 (205, all stalled) and rho <= 0.15 (15 000, 24 stalled) only.  Here the reference's CorrectLambda.SolveLambdaSystem(cpfit=False) is
 run on ONE interval whose length T is swept (rates, migration and pair-state vectors drawn like BASELINE's grids), so that rho covers 0.02 ... 50, and each result is
