@@ -796,18 +796,32 @@ int misti_ens_accept(double z, int32_t d, double llk_old, double llk_new, double
  *     computed;
  *   - best sample: among the kept (t, w) whose chain_llh is neither NaN nor -inf the largest value, ties to the lowest t, then the
  *     lowest w: best_llh, best_x[N], best_at = (t - burn, w); none, or no chain_llh: -inf, NaN, (-1, -1).
- * Beyond the chain the call keeps the series y[S][N][n] (1 / W of the kept chain) in the context; nothing of the chain's size.
- * Shortest (HPD) intervals need a sort and are not offered.
+ *   - shortest (HPD) interval of mass p in (0, 1] (optimize.ensemble_hpd_rule): k is the smallest integer with double(k) >=
+ *     double(m) p (one rounded product), clamped to 1 ... m; w_i = x_(i+k-1) - x_(i) for i = 0 ... m - k, one rounded subtraction
+ *     each; i* is found by walking i upward from i* = 0, i replacing i* iff w_i < w_i*, or w_i* is NaN and w_i is not - the lowest
+ *     i among the minima, any number before a NaN (inf - inf, a NaN sample), all NaN: i* = 0; as a comparison of the pairs
+ *     (isnan(w), w, i) a total order, which the device reduces in parallel.  hpd = (x_(i*), x_(i*+k-1)): the two samples' own bits,
+ *     copied - no arithmetic, no canonical NaN; hpd_at = i*.  p = 1 is (minimum, maximum), m = 1 the sample twice.  order is the
+ *     sorted marginal x_(0) ... x_(m-1) itself, bits copied.  The interval is the shortest IN THE SAMPLING COORDINATE: HPD is
+ *     not invariant under a map of the coordinate, so the shortest interval of a log-scale coordinate ("priors and log-scale
+ *     coordinates") is not the image of the shortest interval of its natural value.
+ * Beyond the chain the call keeps the series y[S][N][n] (1 / W of the kept chain) in the context; nothing of the chain's size -
+ * unless hpd, hpd_at or order is asked for: they need a full sort of every marginal (tiles of 2048 keys sorted in LDS, merged through
+ * HBM: misti_post.hip), whose ping-pong workspace is 2 x S x N x m keys of 8 bytes - TWICE THE KEPT CHAIN'S BYTES, never more -,
+ * taken from the context's growable buffers only by a call that asks for one of the three, and grown only where a call needs more
+ * than the call before.  A call that asks for none of them launches and allocates exactly what it did before they existed.
  *
  * misti_ens_summary_dev: every chain and output pointer is DEVICE memory (probs is HOST); asynchronous on the context's stream.
  * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this
  * library's; S < 0, W < 1 or N < 1; burn outside 0 ... K - 1; n_prob outside 1 ... MISTI_POST_MAX_PROBS; a NULL probs; a p outside
  * [0, 1] or NaN; max_lag < 0; a c that is not finite and positive; a NULL chain with S > 0; MISTI_E_LIMIT for W >
- * MISTI_ENS_MAX_WALKERS, N > MISTI_MAX_PARAMS, m > INT32_MAX or S > INT32_MAX; then a NULL context.  S == 0 writes nothing.  A chain element that
+ * MISTI_ENS_MAX_WALKERS, N > MISTI_MAX_PARAMS, m > INT32_MAX or S > INT32_MAX; then MISTI_E_ARG for n_mass outside 0 ...
+ * MISTI_POST_MAX_PROBS; n_mass > 0 with a NULL masses; a mass outside (0, 1] or NaN; hpd or hpd_at given with n_mass == 0; then a
+ * NULL context.  S == 0 writes nothing.  A chain element that
  * is not finite is no error: the key order and IEEE arithmetic define the result - and since IEEE leaves the sign and the payload
- * of a NaN open, a NaN in mean, cov, quant or tau is stored as the canonical quiet NaN (0x7ff8000000000000; best_x copies the
- * sample's bits).  Any output may be NULL: it is not computed, and
- * the others' bits do not change. */
+ * of a NaN open, a NaN in mean, cov, quant or tau is stored as the canonical quiet NaN (0x7ff8000000000000; best_x, hpd and
+ * order copy the samples' bits).  Any output may be NULL: it is not computed, its kernels are not launched, and the others' bits do
+ * not change.  Through the sampling doors below hpd, hpd_at and order are HOST buffers like the other summaries. */
 #define MISTI_POST_MAX_PROBS 8
 typedef struct {
     uint32_t size;                   /* sizeof(misti_ens_post_t) */
@@ -824,6 +838,11 @@ typedef struct {
     double* best_llh;                /* [S] or NULL */
     double* best_x;                  /* [S][N] or NULL */
     int32_t* best_at;                /* [S][2] or NULL: (kept step - burn, walker) */
+    int32_t n_mass;                  /* 0 ... MISTI_POST_MAX_PROBS: the masses of the shortest intervals; 0: none */
+    const double* masses;            /* HOST [n_mass], each in (0, 1]; not read where n_mass == 0 */
+    double* hpd;                     /* [S][N][n_mass][2] or NULL: (lower end, upper end) */
+    int32_t* hpd_at;                 /* [S][N][n_mass] or NULL: i*, the rank of the lower end */
+    double* order;                   /* [S][N][m] or NULL: the sorted marginal; needs no mass */
 } misti_ens_post_t;
 int misti_ens_summary_dev(misti_ctx* ctx, int64_t S, int64_t K, int32_t W, int32_t N, const double* d_chain, const double* d_chain_llh /* or NULL */,
                           const misti_ens_post_t* post);

@@ -119,13 +119,15 @@ class Prior(C.Structure):
 
 
 POST_MAX_PROBS = 8
+POST_SORT_TILE = 2048                # MISTI_POST_SORT_TILE (csrc/misti_post.h): the samples a workgroup sorts in LDS
 
 
 class EnsPost(C.Structure):
     """``misti_ens_post_t``: posterior summaries of a chain; the header documents the fields."""
     _fields_ = [("size", C.c_uint32), ("burn", C.c_int32), ("n_prob", C.c_int32), ("probs", C.c_void_p), ("max_lag", C.c_int32), ("c", C.c_double),
                 ("mean", C.c_void_p), ("cov", C.c_void_p), ("quant", C.c_void_p), ("tau", C.c_void_p), ("window", C.c_void_p),
-                ("best_llh", C.c_void_p), ("best_x", C.c_void_p), ("best_at", C.c_void_p)]
+                ("best_llh", C.c_void_p), ("best_x", C.c_void_p), ("best_at", C.c_void_p),
+                ("n_mass", C.c_int32), ("masses", C.c_void_p), ("hpd", C.c_void_p), ("hpd_at", C.c_void_p), ("order", C.c_void_p)]
 
 
 class MistiError(RuntimeError):

@@ -108,6 +108,11 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               statistics, interpolated), tau, n_eff = samples / tau, `(short)`, the coordinate's row of the correlation
                               matrix, and the best sample
     --mcmc-lag L              with --mcmc-post: the autocorrelation's lag cap (default: every lag)
+    --mcmc-hpd [MASS ...]     with --mcmc-post: the SHORTEST (highest-posterior-density) interval of each MASS (1 ... 8 masses in (0, 1];
+                              default 0.95) per coordinate, from a full sort of every marginal on the device; each `post:` line gains
+                              ` hpd MASS = [lo, hi]` behind its quantiles.  An equal-tailed interval cuts 2.5 % off the low side even where the
+                              posterior piles up at the edge of the box; the shortest one does not.  For a --mcmc-log coordinate the ends are
+                              printed in natural units, but the interval is the shortest on the log scale: HPD is not invariant under the map
     --mcmc-log K [K ...]      with --mcmc: coordinate K (an index, or st - as --box names them) is SAMPLED ON THE LOG SCALE (misti_ensemble_sample_prior):
                               the stretch, the box test and the chain are in ln(value), the engine is handed the value.  Its --box is given in
                               natural units and needs LO > 0; flat on the log scale is the log-uniform prior.  The `mcmc:` / `post:` lines print
@@ -269,6 +274,8 @@ def build_parser():
     p.add_argument("--mcmc-prior", nargs="+", action="append", default=None, metavar="K",
                    help="with --mcmc: K normal MEAN SD | K exponential SCALE - a prior on coordinate K's sampling coordinate (repeatable)")
     p.add_argument("--mcmc-lag", type=int, default=None, metavar="L", help="with --mcmc-post: the autocorrelation's lag cap (default: every lag)")
+    p.add_argument("--mcmc-hpd", nargs="*", type=float, default=None, metavar="MASS",
+                   help="with --mcmc-post: the shortest (HPD) interval of each MASS per coordinate, ` hpd MASS = [lo, hi]` on the `post:` lines (default 0.95)")
     p.add_argument("--box", nargs=3, action="append", default=[], metavar=("K", "LO", "HI"),
                    help="with --grid-solve / --fit-st / --polish: keep optimised parameter K (or `st`: the fitted split of --fit-st) within [LO, HI] "
                         "in every search (SciPy's bounds=; inf / -inf accepted); repeatable")
@@ -591,6 +598,8 @@ def mcmc_error(a):
     if a.mcmc is None:
         if a.mcmc_post is not None or a.mcmc_lag is not None:
             return "--mcmc-post / --mcmc-lag summarise the chains of --mcmc W STEPS: give --mcmc W STEPS"
+        if a.mcmc_hpd is not None:
+            return "--mcmc-hpd gives the shortest intervals of --mcmc W STEPS --mcmc-post: give --mcmc W STEPS"
         if any(v is not None for v in (a.mcmc_burn, a.mcmc_thin, a.mcmc_seed, a.mcmc_spread, a.mcmc_temp, a.mcmc_out)):
             return "--mcmc-burn / --mcmc-thin / --mcmc-seed / --mcmc-spread / --mcmc-temp / --mcmc-out set the sampler of --mcmc W STEPS: give --mcmc W STEPS"
         if a.mcmc_ladder is not None or a.mcmc_swap is not None:
@@ -633,6 +642,10 @@ def mcmc_error(a):
         return "--mcmc-post [P ...]: at most 8 probabilities, each in [0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_post)
     if a.mcmc_lag is not None and (a.mcmc_post is None or a.mcmc_lag < 0):
         return "--mcmc-lag L caps the lags of --mcmc-post: give --mcmc-post, and L >= 0"
+    if a.mcmc_hpd is not None and a.mcmc_post is None:
+        return "--mcmc-hpd [MASS ...] adds the shortest intervals to the summaries of --mcmc-post: give --mcmc-post"
+    if a.mcmc_hpd is not None and (len(a.mcmc_hpd) > 8 or not all(0.0 < v <= 1.0 for v in a.mcmc_hpd)):
+        return "--mcmc-hpd [MASS ...]: at most 8 masses, each in (0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_hpd)
     if a.mcmc_swap is not None and (a.mcmc_ladder is None or a.mcmc_swap < 0):
         return "--mcmc-swap E sets the swap rounds of --mcmc-ladder: give --mcmc-ladder, and E >= 0"
     if a.mcmc_ladder is not None:
@@ -756,9 +769,10 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     o["start"] = "DE's final population" if population is not None else "spread %g around the fit" % o["spread"]
     if a.mcmc_post is not None:
         o["probs"] = _mcmc_post_options(a)["probs"]
+        o["masses"] = _mcmc_hpd_masses(a)
     sampler = e.ensemble_sample
     if a.mcmc_post is not None:                            # the summaries on the device; the chain comes back only for --mcmc-out
-        post = _mcmc_post_options(a)
+        post = dict(_mcmc_post_options(a), masses=_mcmc_hpd_masses(a))
         sampler = lambda *args, **kw: e.ensemble_posterior(*args, **kw, burn=o["burn"], keep_chain=bool(a.mcmc_out), **post)
     common = dict(split_times=split_times, fit_split=split_times is None, n_step=o["n_step"], thin=o["thin"], seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
     if prior is not None:
@@ -766,7 +780,7 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     extra = {}
     if o["ladder"] is not None:
         ladder = temperature_ladder(T, o["ladder"][1], o["ladder"][0])
-        post = None if a.mcmc_post is None else dict(_mcmc_post_options(a), keep_chain=bool(a.mcmc_out))
+        post = None if a.mcmc_post is None else dict(_mcmc_post_options(a), masses=_mcmc_hpd_masses(a), keep_chain=bool(a.mcmc_out))
         res = e.tempered_sample(np.ascontiguousarray(np.repeat(init[:, None], ladder.size, axis=1)), np.asarray(r_of, dtype=np.int32), data, box, ladder,
                                 swap_every=o["swap_every"], burn=o["burn"], post=post, **common)
         res["ladder"] = ladder
@@ -785,18 +799,27 @@ def _mcmc_post_options(a):
     return dict(probs=tuple(a.mcmc_post) if a.mcmc_post else (0.025, 0.5, 0.975), max_lag=a.mcmc_lag)
 
 
+def _mcmc_hpd_masses(a):
+    """The masses of --mcmc-hpd: None without the option, 0.95 where it names none."""
+    if a.mcmc_hpd is None:
+        return None
+    return tuple(a.mcmc_hpd) if a.mcmc_hpd else (0.95,)
+
+
 def print_post(label, o, res, s):
     """The ``post:`` lines of fit s: one per coordinate, from the summaries the device reduced (Engine.ensemble_posterior)."""
     from .optimize import posterior_table
     n = o["n_step"] // o["thin"] - o["burn"]
-    t = posterior_table({k: res[k][s] for k in ("mean", "cov", "quant", "tau", "window", "last", "best_x")}, n, prior=o.get("prior"))
-    probs = o["probs"]
-    quant, best_x = t.get("quant_natural", t["quant"]), t.get("best_x_natural", res["best_x"][s])
+    t = posterior_table({k: res[k][s] for k in ("mean", "cov", "quant", "tau", "window", "last", "best_x", "hpd") if k in res}, n, prior=o.get("prior"))
+    probs, masses = o["probs"], o.get("masses") or ()
+    quant, best_x, hpd = t.get("quant_natural", t["quant"]), t.get("best_x_natural", res["best_x"][s]), t.get("hpd_natural", t.get("hpd"))
     for c in range(res["mean"].shape[1]):
         print("post:", label, "\tcoordinate %d" % c, "\tmean =", t["mean"][c], "\tsd =", t["sd"][c],
-              *("\tq%g = %r" % (p, float(quant[c][i])) for i, p in enumerate(probs)), "\ttau =", t["tau"][c], "\tn_eff =", t["n_eff"][c],
+              *("\tq%g = %r" % (p, float(quant[c][i])) for i, p in enumerate(probs)),
+              *("\thpd %g = [%r, %r]" % (p, float(hpd[c][i][0]), float(hpd[c][i][1])) for i, p in enumerate(masses)), "\ttau =", t["tau"][c], "\tn_eff =", t["n_eff"][c],
               *(["\t(short)"] if t["short"][c] else []), "\tcorr = [" + ", ".join(repr(float(v)) for v in t["corr"][c]) + "]",
-              "\tbest llh =", res["best_llh"][s], "at = (%d, %d)" % tuple(res["best_at"][s]), "x =", best_x[c], *_log_note(o, c))
+              "\tbest llh =", res["best_llh"][s], "at = (%d, %d)" % tuple(res["best_at"][s]), "x =", best_x[c], *_log_note(o, c),
+              *(["\t(hpd: the shortest interval of the logarithm, its ends in natural units)"] if masses and _log_note(o, c) else []))
 
 
 def _log_note(o, c):

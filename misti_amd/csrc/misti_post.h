@@ -1,7 +1,8 @@
 // What the posterior summaries of a chain (misti_ens_summary_dev / misti_ensemble_posterior; the rule is
 // optimize.ensemble_posterior_rule, operation for operation) share between the host layer and the kernels of misti_post.hip: the
 // order key, the wanted order statistics of a search (a function of m = n W and the probabilities alone, so the host computes them
-// once), and the launch record.
+// once), the window length of a shortest (HPD) interval (optimize.ensemble_hpd_rule; a function of m and the mass alone), the tile of
+// the sort, and the launch record.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -13,6 +14,8 @@ namespace misti {
 
 constexpr int POST_MAX_RANKS = 2 * MISTI_POST_MAX_PROBS;   // a probability needs x_(i) and x_(i+1)
 constexpr int POST_LANES = 64;                             // lsum's partials: one per lane of a wave
+#define MISTI_POST_SORT_TILE 2048                          /* mirrored as _lib.POST_SORT_TILE: the tests aim at its edges */
+constexpr int POST_SORT_TILE = MISTI_POST_SORT_TILE;       // keys a workgroup sorts in LDS (16 KiB), and the keys a merge workgroup emits
 
 // lsum's fold (misti_post.hip's sums over steps, misti_pt.hip's reduction): a partial is a lane of a wave; every lane ends with partial[0]
 __device__ __forceinline__ double post_fold(double v) {
@@ -71,9 +74,19 @@ inline PostSelect post_select(int64_t m, int n_prob, const double* probs) {
     return s;
 }
 
+// The window of a shortest interval of mass p in (0, 1]: k samples, the smallest integer with double(k) >= double(m) p (one rounded
+// product), clamped to 1 ... m.
+inline int32_t post_hpd_window(int64_t m, double p) {
+    int64_t k = (int64_t)ceil((double)m * p);
+    if (k < 1) k = 1;
+    if (k > m) k = m;
+    return (int32_t)k;
+}
+
 // One call: S searches of chain[S][K][W][N], the kept steps burn ... K - 1 (n of them), lags 0 ... L.  Every pointer is device
 // memory; an output that is NULL is not computed.  ws_mean[S][N] and ws_y[S][N][n] are the call's workspace: the mean and the
-// centred ensemble-mean series (1 / W of the kept chain).
+// centred ensemble-mean series (1 / W of the kept chain).  hpd / hpd_at / order need the sorted marginals: ws_sort[2][S][N][m], the
+// ping-pong pair of the sort, is theirs alone (NULL where none of the three is asked for) - twice the kept chain's bytes, no more.
 struct PostArgs {
     int64_t S, K, burn, n, L;
     int64_t llh_K;                   // rows of chain_llh from one search to the next: K, or (the tempered sampler keeps the values of
@@ -88,6 +101,13 @@ struct PostArgs {
     double *best_llh, *best_x;
     int32_t* best_at;
     PostSelect sel;
+    int32_t n_mass;
+    int32_t hpd_k[MISTI_POST_MAX_PROBS];                   // post_hpd_window per mass
+    uint64_t* ws_sort;
+    double* hpd;                     // [S][N][n_mass][2]
+    int32_t* hpd_at;                 // [S][N][n_mass]
+    double* order;                   // [S][N][m]
+    bool sorted() const { return hpd || hpd_at || order; }
 };
 hipError_t launch_post(const PostArgs& a, hipStream_t stream);
 

@@ -16,6 +16,16 @@
 //                       LDS histograms; ranks that still share a prefix share a histogram.  No second buffer, no sort
 //   post_best_kernel    workgroup = search
 // The only memory beyond the chain is the series y[S][N][n]: 1 / W of the kept chain.
+//
+// Shortest (HPD) intervals and the sorted marginal itself (optimize.ensemble_hpd_rule) need every order statistic - a full sort per
+// (search, coordinate), launched only where hpd, hpd_at or order is asked for:
+//   post_sort_tile_kernel  workgroup = (search, tile of POST_SORT_TILE samples; coordinate): the strided chain gathered into keys, once,
+//                          and a bitonic network in 16 KiB of LDS - eight workgroups a CU, the wave limit, not LDS, caps residency
+//   post_merge_kernel      one pass per doubling of the run length, through the ping-pong pair ws_sort[2][S][N][m] in HBM: a marginal
+//                          (32 000 keys = 250 KiB at W = 16, 2 000 steps) does not fit one workgroup's LDS; merge-path cuts per tile
+//   post_hpd_kernel        workgroup = (search, coordinate): the window scan per mass with the rule's pair reduction; plain stores
+// Consecutive lanes touch consecutive 8-byte keys in the gather's stores, the merge's loads and stores and the scan (a 32-lane half
+// covers one 256-byte bank row: no conflict); the network's strides below 32 and the serial merge's data-dependent reads do conflict.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -231,6 +241,154 @@ void post_best_kernel(PostArgs a) {
         a.best_x[s * N + tid] = bi >= 0 ? kept(a, s)[bi * N + tid] : __longlong_as_double(0x7ff8000000000000ll);
 }
 
+// ---- the sorted marginals and the shortest intervals (optimize.ensemble_hpd_rule) -----------------------------------------------------
+// Keys only: equal keys are equal bits, so no payload travels and stability does not matter.  A marginal lies at
+// ws_sort[side][(s N + j) m ...], side 0 or 1.
+__device__ __forceinline__ uint64_t* sort_side(const PostArgs& a, int side, int64_t s, int j) {
+    const int64_t m = a.n * a.W;
+    return a.ws_sort + ((int64_t)side * a.S * a.N + s * a.N + j) * m;
+}
+
+// workgroup = (search, tile; coordinate): gathers the tile's keys from the strided chain - the only strided read of the sort - and
+// sorts them in LDS by a bitonic network over the next power of two, the absent keys being the largest key.
+__global__ __launch_bounds__(POST_THREADS)
+void post_sort_tile_kernel(PostArgs a) {
+    __shared__ uint64_t key[POST_SORT_TILE];
+    const int64_t m = a.n * a.W, tiles = (m + POST_SORT_TILE - 1) / POST_SORT_TILE;
+    const int64_t s = blockIdx.x / tiles, first = (blockIdx.x % tiles) * POST_SORT_TILE;
+    const int j = blockIdx.y, N = a.N, tid = threadIdx.x;
+    const int cnt = (int)(m - first < POST_SORT_TILE ? m - first : POST_SORT_TILE);
+    int Tp = 2;
+    while (Tp < cnt) Tp <<= 1;
+    const double* x = kept(a, s) + j;
+    for (int e = tid; e < Tp; e += POST_THREADS)
+        key[e] = e < cnt ? post_key((uint64_t)__double_as_longlong(x[(first + e) * N])) : ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= Tp; k <<= 1)
+        for (int h = k >> 1; h > 0; h >>= 1) {
+            for (int p = tid; p < Tp / 2; p += POST_THREADS) {
+                const int i = ((p & ~(h - 1)) << 1) | (p & (h - 1)), l = i | h;
+                const uint64_t u = key[i], v = key[l];
+                if ((u > v) == ((i & k) == 0)) { key[i] = v; key[l] = u; }
+            }
+            __syncthreads();
+        }
+    uint64_t* out = sort_side(a, 0, s, j) + first;
+    for (int e = tid; e < cnt; e += POST_THREADS) out[e] = key[e];
+}
+
+// the merge path: how many of the first d keys of merge(A[0 .. la), B[0 .. lb)) come from A; a tie takes A's
+template <class P>
+__device__ __forceinline__ int64_t merge_split(P A, int64_t la, P B, int64_t lb, int64_t d) {
+    int64_t lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (A[mid] <= B[d - 1 - mid]) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One merge pass, runs of `width` keys (a multiple of the tile; the last run of a marginal may be short or absent) to runs of twice
+// that, from side `src` to the other.  workgroup = (search, a tile of the OUTPUT; coordinate): two searches in HBM cut the piece of
+// each run that the tile comes from (together at most a tile), LDS takes them, a thread cuts its POST_SORT_ITEMS outputs out of LDS
+// and merges them serially, and the tile leaves through LDS in whole lines.
+constexpr int POST_SORT_ITEMS = POST_SORT_TILE / POST_THREADS;
+
+__global__ __launch_bounds__(POST_THREADS)
+void post_merge_kernel(PostArgs a, int64_t width, int src) {
+    __shared__ uint64_t key[POST_SORT_TILE];
+    __shared__ int64_t cut[2];
+    const int64_t m = a.n * a.W, tiles = (m + POST_SORT_TILE - 1) / POST_SORT_TILE;
+    const int64_t s = blockIdx.x / tiles, first = (blockIdx.x % tiles) * POST_SORT_TILE;
+    const int j = blockIdx.y, tid = threadIdx.x;
+    const uint64_t* in = sort_side(a, src, s, j);
+    uint64_t* out = sort_side(a, src ^ 1, s, j);
+    const int64_t start = first / (2 * width) * (2 * width);            // the pair of runs this tile lies in
+    const int64_t la = m - start < width ? m - start : width, lb = m - start - la < width ? m - start - la : width;
+    const uint64_t *A = in + start, *B = A + la;
+    const int64_t d0 = first - start, d1 = d0 + POST_SORT_TILE < la + lb ? d0 + POST_SORT_TILE : la + lb;
+    if (tid < 2) cut[tid] = merge_split(A, la, B, lb, tid ? d1 : d0);
+    __syncthreads();
+    const int64_t a0 = cut[0], b0 = d0 - a0;
+    const int na = (int)(cut[1] - a0), total = (int)(d1 - d0), nb = total - na;
+    for (int e = tid; e < total; e += POST_THREADS) key[e] = e < na ? A[a0 + e] : B[b0 + (e - na)];
+    __syncthreads();
+    const uint64_t *sa = key, *sb = key + na;
+    const int o = tid * POST_SORT_ITEMS;
+    uint64_t r[POST_SORT_ITEMS];
+    if (o < total) {
+        int ai = (int)merge_split(sa, (int64_t)na, sb, (int64_t)nb, (int64_t)o), bi = o - ai;
+#pragma unroll
+        for (int q = 0; q < POST_SORT_ITEMS; ++q)
+            if (o + q < total) {
+                const bool from_a = bi >= nb || (ai < na && sa[ai] <= sb[bi]);
+                r[q] = from_a ? sa[ai] : sb[bi];
+                ai += from_a ? 1 : 0; bi += from_a ? 0 : 1;
+            }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < POST_SORT_ITEMS; ++q)
+        if (o + q < total) key[o + q] = r[q];
+    __syncthreads();
+    for (int e = tid; e < total; e += POST_THREADS) out[first + e] = key[e];
+}
+
+// the rule's order on (isnan(w), w, i): does window (wa, ia) come before window (wb, ib)?  A total order, so the reduction below and
+// the rule's walk over i agree: any number before a NaN, the narrower before the wider, the lower i before the higher.
+__device__ __forceinline__ bool hpd_before(double wa, int64_t ia, double wb, int64_t ib) {
+    const bool na = wa != wa, nb = wb != wb;
+    if (na != nb) return nb;
+    if (!na && wa != wb) return wa < wb;
+    return ia < ib;
+}
+
+// workgroup = (search, coordinate), on the sorted marginal: `order`, and per mass the window scan - w_i = x_(i+k-1) - x_(i), one
+// rounded subtraction - with the pair reduction; hpd copies the two samples' bits.
+__global__ __launch_bounds__(POST_THREADS)
+void post_hpd_kernel(PostArgs a, int side) {
+    __shared__ double sw[POST_THREADS];
+    __shared__ int64_t si[POST_THREADS];
+    const int64_t s = blockIdx.x, m = a.n * a.W;
+    const int j = blockIdx.y, N = a.N, tid = threadIdx.x;
+    const uint64_t* key = sort_side(a, side, s, j);
+    if (a.order) {
+        long long* o = reinterpret_cast<long long*>(a.order) + (s * N + j) * m;
+        for (int64_t i = tid; i < m; i += POST_THREADS) o[i] = (long long)post_unkey(key[i]);
+    }
+    if (!a.hpd && !a.hpd_at) return;
+    for (int q = 0; q < a.n_mass; ++q) {
+        const int64_t k = a.hpd_k[q], count = m - k + 1;
+        double bw = 0.0;
+        int64_t bi = -1;                                      // none yet
+        for (int64_t i = tid; i < count; i += POST_THREADS) {
+            const double lo = __longlong_as_double((long long)post_unkey(key[i])), hi = __longlong_as_double((long long)post_unkey(key[i + k - 1]));
+            const double w = hi - lo;
+            if (bi < 0 || hpd_before(w, i, bw, bi)) { bw = w; bi = i; }
+        }
+        sw[tid] = bw; si[tid] = bi;
+        __syncthreads();
+        for (int stride = POST_THREADS / 2; stride >= 1; stride >>= 1) {
+            if (tid < stride) {
+                const double ow = sw[tid + stride];
+                const int64_t oi = si[tid + stride];
+                if (oi >= 0 && (si[tid] < 0 || hpd_before(ow, oi, sw[tid], si[tid]))) { sw[tid] = ow; si[tid] = oi; }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const int64_t at = si[0], slot = (s * N + j) * a.n_mass + q;
+            if (a.hpd) {
+                long long* h = reinterpret_cast<long long*>(a.hpd) + 2 * slot;
+                h[0] = (long long)post_unkey(key[at]);
+                h[1] = (long long)post_unkey(key[at + k - 1]);
+            }
+            if (a.hpd_at) a.hpd_at[slot] = (int32_t)at;
+        }
+        __syncthreads();
+    }
+}
+
 hipError_t launch_post(const PostArgs& a, hipStream_t stream) {
     const dim3 per_coord((unsigned)a.S, (unsigned)a.N);             // searches along x: the axis without a 65535 limit
     const bool series = a.mean || a.cov || a.tau || a.window;
@@ -239,6 +397,16 @@ hipError_t launch_post(const PostArgs& a, hipStream_t stream) {
     if (a.tau || a.window) hipLaunchKernelGGL(post_acf_kernel, per_coord, dim3(POST_THREADS), 0, stream, a);
     if (a.quant) hipLaunchKernelGGL(post_select_kernel, per_coord, dim3(POST_THREADS), 0, stream, a);
     if (a.best_llh || a.best_x || a.best_at) hipLaunchKernelGGL(post_best_kernel, dim3((unsigned)a.S), dim3(POST_THREADS), 0, stream, a);
+    if (a.sorted()) {
+        const int64_t m = a.n * a.W, tiles = (m + POST_SORT_TILE - 1) / POST_SORT_TILE;
+        if (a.S * tiles > INT32_MAX) return hipErrorInvalidValue;
+        const dim3 per_tile((unsigned)(a.S * tiles), (unsigned)a.N);
+        hipLaunchKernelGGL(post_sort_tile_kernel, per_tile, dim3(POST_THREADS), 0, stream, a);
+        int side = 0;
+        for (int64_t width = POST_SORT_TILE; width < m; width *= 2, side ^= 1)
+            hipLaunchKernelGGL(post_merge_kernel, per_tile, dim3(POST_THREADS), 0, stream, a, width, side);
+        hipLaunchKernelGGL(post_hpd_kernel, per_coord, dim3(POST_THREADS), 0, stream, a, side);
+    }
     return hipGetLastError();
 }
 

@@ -29,6 +29,12 @@ int post_check(const misti_ens_post_t* p, int64_t S, int64_t K, int32_t W, int32
     if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "N = %d exceeds MISTI_MAX_PARAMS = %d", (int)N, MISTI_MAX_PARAMS);
     if ((K - p->burn) > INT32_MAX / W) return fail(MISTI_E_LIMIT, "%lld kept steps x %d walkers exceed INT32_MAX samples per search", (long long)(K - p->burn), (int)W);
     if (S > INT32_MAX) return fail(MISTI_E_LIMIT, "too many searches for one call");
+    // the shortest intervals: behind everything older, so that no older refusal changes its text
+    if (p->n_mass < 0 || p->n_mass > MISTI_POST_MAX_PROBS) return fail(MISTI_E_ARG, "n_mass must be 0 ... %d (got %d)", MISTI_POST_MAX_PROBS, (int)p->n_mass);
+    if (p->n_mass > 0 && !p->masses) return fail(MISTI_E_ARG, "masses is NULL");
+    for (int i = 0; i < p->n_mass; ++i)
+        if (!(p->masses[i] > 0.0 && p->masses[i] <= 1.0)) return fail(MISTI_E_ARG, "masses[%d] = %g is not in (0, 1]", i, p->masses[i]);
+    if (p->n_mass == 0 && (p->hpd || p->hpd_at)) return fail(MISTI_E_ARG, "hpd / hpd_at given with n_mass == 0: a shortest interval needs its mass");
     return 0;
 }
 
@@ -37,6 +43,12 @@ void post_fill(misti::PostArgs& a, int64_t S, int64_t K, int32_t W, int32_t N, c
     a.S = S; a.K = K; a.llh_K = K; a.W = W; a.N = N; a.burn = p.burn; a.n = K - p.burn; a.c = p.c;
     a.L = p.max_lag < a.n - 1 ? p.max_lag : a.n - 1;
     a.sel = misti::post_select(a.n * W, p.n_prob, p.probs);
+    a.n_mass = p.n_mass;
+    for (int i = 0; i < p.n_mass; ++i) a.hpd_k[i] = misti::post_hpd_window(a.n * W, p.masses[i]);
+}
+// the keys of the sort's ping-pong pair (misti_post.hip) where the descriptor asks for a sorted output, else none
+size_t post_sort_keys(const misti_ens_post_t& p, size_t S, int N, const misti::PostArgs& a) {
+    return p.hpd || p.hpd_at || p.order ? 2 * S * (size_t)N * (size_t)a.n * (size_t)a.W : 0;
 }
 
 // The device side of the summaries of a sampler that keeps its chain (sampler_run): carved behind everything the sampler carves,
@@ -48,6 +60,10 @@ void post_carve(misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, int N,
     pa.quant = p.quant ? f.take(SN * NP) : nullptr; pa.tau = p.tau ? f.take(SN) : nullptr;
     pa.best_llh = p.best_llh ? f.take(S) : nullptr; pa.best_x = p.best_x ? f.take(SN) : nullptr;
     pa.window = p.window ? i.take(SN) : nullptr; pa.best_at = p.best_at ? i.take(2 * S) : nullptr;
+    const size_t NM = (size_t)p.n_mass, keys = post_sort_keys(p, S, N, pa);
+    pa.ws_sort = keys ? reinterpret_cast<uint64_t*>(f.take(keys)) : nullptr;                // 8-byte words of the double buffer
+    pa.hpd = p.hpd ? f.take(SN * NM * 2) : nullptr; pa.order = p.order ? f.take(keys / 2) : nullptr;
+    pa.hpd_at = p.hpd_at ? i.take(SN * NM) : nullptr;
 }
 int post_back(const misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, int N, hipStream_t sm) {
     const size_t SN = S * (size_t)N, NP = (size_t)p.n_prob;
@@ -60,6 +76,9 @@ int post_back(const misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, in
     HIP_TRY(back(p.best_llh, pa.best_llh, S * sizeof(double)));
     HIP_TRY(back(p.best_x, pa.best_x, SN * sizeof(double)));
     HIP_TRY(back(p.best_at, pa.best_at, 2 * S * sizeof(int32_t)));
+    HIP_TRY(back(p.hpd, pa.hpd, SN * (size_t)p.n_mass * 2 * sizeof(double)));
+    HIP_TRY(back(p.hpd_at, pa.hpd_at, SN * (size_t)p.n_mass * sizeof(int32_t)));
+    HIP_TRY(back(p.order, pa.order, SN * (size_t)pa.n * (size_t)pa.W * sizeof(double)));
     return 0;
 }
 
@@ -406,11 +425,14 @@ int misti_ens_summary_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t
     misti::PostArgs a{};
     post_fill(a, S, K, W, N, *p);
     const size_t SN = (size_t)S * (size_t)N;
-    HIP_TRY(c->post_ws.reserve(SN * (size_t)(a.n + 1) * sizeof(double)));
+    const size_t keys = post_sort_keys(*p, (size_t)S, N, a);
+    HIP_TRY(c->post_ws.reserve((SN * (size_t)(a.n + 1) + keys) * sizeof(double)));
     a.ws_mean = c->post_ws.as<double>(); a.ws_y = a.ws_mean + SN;
+    a.ws_sort = keys ? reinterpret_cast<uint64_t*>(a.ws_y + SN * (size_t)a.n) : nullptr;
     a.chain = d_chain; a.chain_llh = d_chain_llh;
     a.mean = p->mean; a.cov = p->cov; a.quant = p->quant; a.tau = p->tau; a.window = p->window;
     a.best_llh = p->best_llh; a.best_x = p->best_x; a.best_at = p->best_at;
+    a.hpd = p->hpd; a.hpd_at = p->hpd_at; a.order = p->order;
     HIP_TRY(misti::launch_post(a, c->stream));
     return 0;
 }

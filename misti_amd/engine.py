@@ -740,30 +740,37 @@ class Engine:
                              pulse_times, n_step, thin, 0, 0, a, seed, ids, prior)
 
     _POST_OUTPUTS = ("mean", "cov", "quant", "tau", "window", "best_llh", "best_x", "best_at")
+    _POST_SORTED = ("hpd", "hpd_at", "order")              # what needs the sorted marginals: only on request
 
     @staticmethod
-    def _post(S, N, K, burn, probs, max_lag, c, empty=None, want=_POST_OUTPUTS):
-        """``misti_ens_post_t`` for the chains of S searches, N coordinates and K kept steps, and the outputs of ``want`` it points
-        into.  ``max_lag`` None: every lag.  ``empty(shape, integer)`` allocates one output and returns it with its address (default:
-        NumPy, on the host).  Returns (descriptor, outputs, what must stay alive until the call returns)."""
+    def _post(S, N, K, burn, probs, max_lag, c, empty=None, want=None, masses=None, W=1):
+        """``misti_ens_post_t`` for the chains of S searches, N coordinates, K kept steps and W walkers, and the outputs of ``want`` it
+        points into (None: the eight summaries, and ``hpd`` / ``hpd_at`` where ``masses`` are given; ``order`` only by name).
+        ``max_lag`` None: every lag.  ``masses`` None: no shortest interval.  ``empty(shape, integer)`` allocates one output and
+        returns it with its address (default: NumPy, on the host).  Returns (descriptor, outputs, what must stay alive until the call
+        returns)."""
         probs = _f64(probs).reshape(-1)
-        P, burn = probs.size, int(burn)
+        masses = _f64(() if masses is None else masses).reshape(-1)
+        if want is None:
+            want = Engine._POST_OUTPUTS + (("hpd", "hpd_at") if masses.size else ())
+        P, M, burn = probs.size, masses.size, int(burn)
         max_lag = max(K - burn - 1, 0) if max_lag is None else int(max_lag)
-        shapes = dict(mean=(S, N), cov=(S, N, N), quant=(S, N, P), tau=(S, N), window=(S, N), best_llh=(S,), best_x=(S, N), best_at=(S, 2))
+        shapes = dict(mean=(S, N), cov=(S, N, N), quant=(S, N, P), tau=(S, N), window=(S, N), best_llh=(S,), best_x=(S, N), best_at=(S, 2),
+                      hpd=(S, N, M, 2), hpd_at=(S, N, M), order=(S, N, max(K - burn, 0) * int(W)))
         if empty is None:
             def empty(shape, integer):
                 v = np.empty(shape, dtype=np.int32 if integer else np.float64)
                 return v, v.ctypes.data
-        made = {k: empty(shapes[k], k in ("window", "best_at")) for k in Engine._POST_OUTPUTS if k in want}
+        made = {k: empty(shapes[k], k in ("window", "best_at", "hpd_at")) for k in Engine._POST_OUTPUTS + Engine._POST_SORTED if k in want}
         p = _lib.EnsPost(size=C.sizeof(_lib.EnsPost), burn=burn, n_prob=P, probs=probs.ctypes.data, max_lag=min(max_lag, 2 ** 31 - 1), c=float(c),
-                         **{k: at or None for k, (_, at) in made.items()})
-        return p, {k: v for k, (v, _) in made.items()}, probs
+                         n_mass=M, masses=masses.ctypes.data if M else None, **{k: at or None for k, (_, at) in made.items()})
+        return p, {k: v for k, (v, _) in made.items()}, (probs, masses)
 
     def _sampler(self, who, tempered, post, keep_chain, init, rows, table, box, temps, split_times, fit_split, band_bounds, pulse_times, n_step,
                  thin, swap_every, burn, a, seed, ids, prior):
         """One marshalling for the two sampler descriptors - the rows problem, the outputs, the summaries and the prior - and the call.
         ``tempered`` False: ``misti_ens_t``, ``init`` is ``[S][W][N]`` and ``temps`` the temperature (a scalar or ``[S]``); True:
-        ``misti_pt_t``, ``init`` is ``[S][L][W][N]`` and ``temps`` the ladder.  ``post``: None or dict(burn, probs, max_lag, c).
+        ``misti_pt_t``, ``init`` is ``[S][L][W][N]`` and ``temps`` the ladder.  ``post``: None or dict(burn, probs, max_lag, c, masses, want).
         Returns the door's outputs in the descriptor's order (the coordinate chain only with ``keep_chain``; the plain door's value
         chain too), then the summaries, then ``n_points``."""
         if (split_times is None) != bool(fit_split):
@@ -797,7 +804,7 @@ class Engine:
         else:
             T = T.reshape(-1)
             q = _lib.EnsSample(size=C.sizeof(_lib.EnsSample), n_temp=T.size, temperature=ptr(T), **common)
-        p, s, p_keep = self._post(S, N, K, **post) if post is not None else (None, {}, None)
+        p, s, p_keep = self._post(S, N, K, W=W, **post) if post is not None else (None, {}, None)
         pr, pr_keep = self._prior(prior, S, N, who) if prior is not None else (None, None)
         ref = lambda d: C.byref(d) if d is not None else None
         if pr is not None:
@@ -814,7 +821,7 @@ class Engine:
 
     def ensemble_posterior(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
                            thin=1, temperature=1.0, a=2.0, seed=0, ids=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, keep_chain=False, c=5.0,
-                           prior=None):
+                           prior=None, masses=None, want=None):
         """``misti_ensemble_posterior``: ``ensemble_sample`` on the same arguments - the same kernels, stream and bits - followed by the
         posterior summaries of its chain, reduced per search ON THE DEVICE: without ``keep_chain`` the chain never leaves it.  The rule is
         ``optimize.ensemble_posterior_rule`` on the kept steps ``burn ... n_keep - 1`` (n of them), bit for bit: ``probs`` (1 ... 8
@@ -824,8 +831,13 @@ class Engine:
         cap closed the window), best_llh[S], best_x[S][N], best_at[S][2] ((kept step - burn, walker); (-1, -1): no sample has a value),
         accepted, last, last_llh, n_points as ``ensemble_sample``), and chain, chain_llh with ``keep_chain``.  ``prior`` as in
         ``ensemble_sample``: the summaries are then those of the chain in SAMPLING coordinates (``optimize.posterior_table`` reports
-        quantiles and the best sample in natural units too)."""
-        r = self._sampler("ensemble_posterior", False, dict(burn=burn, probs=probs, max_lag=max_lag, c=c), bool(keep_chain), init, rows, table, box,
+        quantiles and the best sample in natural units too).
+        ``masses`` (None, or 1 ... 8 masses in (0, 1]): the SHORTEST (HPD) interval of each mass per coordinate, from a full sort of
+        every marginal on the device (``optimize.ensemble_hpd_rule``, bit for bit) - ``hpd[S][N][len(masses)][2]`` and
+        ``hpd_at[S][N][len(masses)]`` (the rank of the lower end) join the result; shortest in the SAMPLING coordinate, HPD is not
+        invariant under the log map.  ``want``: the summaries to compute, by name (default: the eight above, and hpd, hpd_at with
+        ``masses``); ``"order"`` adds the sorted marginals ``order[S][N][n W]`` themselves."""
+        r = self._sampler("ensemble_posterior", False, dict(burn=burn, probs=probs, max_lag=max_lag, c=c, masses=masses, want=want), bool(keep_chain), init, rows, table, box,
                           temperature, split_times, fit_split, band_bounds, pulse_times, n_step, thin, 0, 0, a, seed, ids, prior)
         for k in ("chain", "chain_llh") if keep_chain else ():             # this door's order: the chain behind the summaries
             r[k] = r.pop(k)
@@ -839,7 +851,7 @@ class Engine:
         neighbouring rungs trade walkers every ``swap_every`` steps (0: never), the cold rung carries the posterior, and all rungs of all
         fits move in the same engine batch.  The rule is ``optimize.tempered_rule``, bit for bit; L = 1 is ``ensemble_sample``.  The other
         arguments as in ``ensemble_sample``; ``burn``: kept steps dropped before ``rung_llh`` / ``logz``.  ``post``: None, or a dict of
-        ``burn`` (default: this call's), ``probs``, ``max_lag``, ``c`` and ``keep_chain`` (default False) - the summaries of
+        ``burn`` (default: this call's), ``probs``, ``max_lag``, ``c``, ``masses``, ``want`` and ``keep_chain`` (default False) - the summaries of
         ``ensemble_posterior`` reduced on the device from the cold chain, which then comes back only with ``keep_chain``.
         Returns dict(chain[S][K][W][N] (the cold rung), chain_llh[S][L][K][W], accepted[S][L][W], swap_proposed[S][L-1],
         swap_accepted[S][L-1], last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S] (see ``optimize.tempered_rule`` for what it
@@ -848,19 +860,21 @@ class Engine:
         opts = dict(post) if post is not None else None
         keep_chain = opts is None or bool(opts.pop("keep_chain", False))
         if opts is not None:
-            opts = dict(burn=opts.get("burn", burn), probs=opts.get("probs", (0.025, 0.5, 0.975)), max_lag=opts.get("max_lag"), c=opts.get("c", 5.0))
+            opts = dict(burn=opts.get("burn", burn), probs=opts.get("probs", (0.025, 0.5, 0.975)), max_lag=opts.get("max_lag"), c=opts.get("c", 5.0),
+                        masses=opts.get("masses"), want=opts.get("want"))
         return self._sampler("tempered_sample", True, opts, keep_chain, init, rows, table, box, ladder, split_times, fit_split, band_bounds,
                              pulse_times, n_step, thin, swap_every, burn, a, seed, ids, prior)
 
-    def ensemble_summary_dev(self, chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0, want=None):
+    def ensemble_summary_dev(self, chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0, want=None, masses=None):
         """``misti_ens_summary_dev``: the posterior summaries of a chain that is already on the device - ``chain`` a contiguous float64
         torch tensor ``[S][K][W][N]`` on this engine's device, ``chain_llh`` ``[S][K][W]`` or None (no best sample).  Asynchronous on
         the engine's stream; the rule is ``optimize.ensemble_posterior_rule``, bit for bit.  ``want``: the outputs to compute (default
         all of mean, cov, quant, tau, window, best_llh, best_x, best_at); one that is left out is not computed and the others' bits do
-        not change.  Returns a dict of torch tensors on the device."""
+        not change.  ``masses`` (None, or 1 ... 8 masses in (0, 1]) adds ``hpd[S][N][len(masses)][2]`` and ``hpd_at``, the shortest
+        intervals of ``optimize.ensemble_hpd_rule`` from a full sort on the device; ``"order"`` in ``want`` the sorted marginals
+        ``order[S][N][(K - burn) W]``.  Returns a dict of torch tensors on the device."""
         import torch
-        names = ("mean", "cov", "quant", "tau", "window", "best_llh", "best_x", "best_at")
-        want = names if want is None else tuple(want)
+        want = None if want is None else tuple(want)
         if chain.dim() != 4 or chain.dtype != torch.float64 or not chain.is_contiguous():
             raise ValueError("ensemble_summary_dev: chain must be a contiguous float64 tensor [S][K][W][N]")
         S, K, W, N = chain.shape
@@ -869,7 +883,7 @@ class Engine:
         def empty(shape, integer):
             v = torch.empty(shape, dtype=torch.int32 if integer else torch.float64, device=chain.device)
             return v, v.data_ptr()
-        p, out, p_keep = self._post(S, N, K, burn, probs, max_lag, c, empty, want)
+        p, out, p_keep = self._post(S, N, K, burn, probs, max_lag, c, empty, want, masses, W)
         _lib.check(self._lib.misti_ens_summary_dev(self._ctx, S, K, W, N, C.c_void_p(chain.data_ptr()) if chain.data_ptr() else None,
                                                    C.c_void_p(chain_llh.data_ptr()) if chain_llh is not None and chain_llh.data_ptr() else None, C.byref(p)))
         return out

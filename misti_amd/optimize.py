@@ -1774,13 +1774,69 @@ def ensemble_posterior_rule(chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.
     return {k_: v[0] for k_, v in out.items()} if one else out
 
 
+def hpd_window(m, mass):
+    """The samples in the window of a shortest interval of ``mass`` in (0, 1] over m samples: the smallest integer k with
+    ``double(k) >= double(m) mass`` (one rounded product), clamped to 1 ... m."""
+    import math
+    return min(max(int(math.ceil(float(m) * float(mass))), 1), int(m))
+
+
+def ensemble_hpd_rule(chain, burn=0, masses=(0.95,), order=False):
+    """The rule of the shortest (highest-posterior-density) intervals of ``misti_ens_summary_dev`` (``hpd``, ``hpd_at``, ``order``),
+    operation for operation, for ``chain[S][K][W][N]`` (or one search ``[K][W][N]``).  Per search and coordinate, with the ``m = n W``
+    kept samples in the order of ``post_order_key`` (``ensemble_posterior_rule``'s ``order``), ``x_(0) <= ... <= x_(m-1)``, and per mass:
+      k         ``hpd_window(m, mass)`` samples in the window
+      w_i       ``x_(i+k-1) - x_(i)`` for ``i = 0 ... m - k``, one rounded subtraction each
+      i*        walking i upward from ``i* = 0``, i replaces i* iff ``w_i < w_i*``, or ``w_i*`` is NaN and ``w_i`` is not: the lowest
+                i among the minima, any number before a NaN (``inf - inf``, a NaN sample), all NaN: 0.  On the pairs
+                ``(isnan(w), w, i)`` this is a total order - the device reduces it in parallel
+      hpd       ``(x_(i*), x_(i*+k-1))``: the samples' own bits, copied - no arithmetic, no canonical NaN; ``hpd_at = i*``
+    ``mass = 1`` is (minimum, maximum), ``m = 1`` the sample twice.  The interval is the shortest IN THE SAMPLING COORDINATE: HPD is not
+    invariant under the log map, so for a LOG coordinate the image of this interval is an interval of that mass in natural units, not
+    the shortest one there.  A search's result depends on its own chain alone.
+    Returns dict(hpd[S][N][len(masses)][2], hpd_at[S][N][len(masses)] int32), and with ``order`` the sorted marginals
+    ``order[S][N][m]`` - without the leading axis for one search."""
+    x = np.asarray(chain, dtype=np.float64)
+    one = x.ndim == 3
+    if one:
+        x = x[None]
+    if x.ndim != 4:
+        raise ValueError("ensemble_hpd_rule: chain must be [S][K][W][N] or [K][W][N]")
+    S, K, W, N = x.shape
+    burn = int(burn)
+    ms = np.asarray(masses, dtype=np.float64).reshape(-1)
+    if not 0 <= burn < K or ms.size > POST_MAX_PROBS or not ((ms > 0) & (ms <= 1)).all() or W < 1 or N < 1:
+        raise ValueError("ensemble_hpd_rule: burn must be 0 ... K - 1, at most %d masses in (0, 1]" % POST_MAX_PROBS)
+    m = (K - burn) * W
+    out = dict(hpd=np.empty((S, N, ms.size, 2)), hpd_at=np.empty((S, N, ms.size), dtype=np.int32), order=np.empty((S, N, m)))
+    with np.errstate(all="ignore"):
+        for s in range(S):
+            flat = x[s, burn:].reshape(m, N)
+            for j in range(N):
+                v = np.ascontiguousarray(flat[:, j])
+                o = v[np.argsort(post_order_key(v), kind="stable")]
+                out["order"][s, j] = o
+                for q, mass in enumerate(ms):
+                    k = hpd_window(m, mass)
+                    w = o[k - 1:] - o[:m - k + 1]
+                    ok = np.flatnonzero(~np.isnan(w))
+                    at = int(ok[np.argmin(w[ok])]) if ok.size else 0        # argmin: the first of the minima
+                    out["hpd"][s, j, q] = o[[at, at + k - 1]]                # an indexed copy: the bits, NaN payloads included
+                    out["hpd_at"][s, j, q] = at
+    if not order:
+        del out["order"]
+    return {k_: v[0] for k_, v in out.items()} if one else out
+
+
 def posterior_table(result, n_step, walkers=None, prior=None):
     """What one reads off ``ensemble_posterior`` / ``ensemble_posterior_rule`` per coordinate, with ``n_step`` = n, the kept steps
     behind the summary, and W ``walkers`` (default: those of ``result["last"]``): dict(mean, sd (the square root of the covariance's
     diagonal), quant, tau, n_eff = n W / tau, short: fewer than 50 tau kept steps or no lag closed the window (window == -1), corr: the
     correlation matrix).  With ``prior`` (the call's) also ``coordinate`` (per coordinate "linear" or "log": what ``mean`` and ``sd``
     are in), ``quant_natural`` (``quant`` with the LOG coordinates in natural units) and, where the result has ``best_x``,
-    ``best_x_natural``."""
+    ``best_x_natural``.  Where the result has ``hpd`` (``masses``: the shortest intervals), ``hpd`` too, and with ``prior``
+    ``hpd_natural``: its endpoints in natural units - an interval of that mass, but shortest in the SAMPLING coordinate only: HPD is
+    not invariant under the log map."""
     n, W = int(n_step), int(np.asarray(result["last"]).shape[-2] if walkers is None else walkers)
     cov = np.asarray(result["cov"], dtype=np.float64)
     tau = np.asarray(result["tau"], dtype=np.float64)
@@ -1797,6 +1853,10 @@ def posterior_table(result, n_step, walkers=None, prior=None):
         out.update(coordinate=np.where(log, "log", "linear"), quant_natural=from_sampling(np.swapaxes(out["quant"], -1, -2), prior).swapaxes(-1, -2))
         if "best_x" in result:
             out.update(best_x_natural=from_sampling(result["best_x"], prior))
+    if "hpd" in result:
+        out.update(hpd=np.asarray(result["hpd"]))
+        if prior is not None:                                  # [...][N][masses][2]: the coordinate axis last for from_sampling, and back
+            out.update(hpd_natural=np.moveaxis(from_sampling(np.moveaxis(out["hpd"], -3, -1), prior), -1, -3))
     return out
 
 
