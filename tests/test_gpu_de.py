@@ -2,9 +2,11 @@
 bootstrap_profile_de and `--de` - against optimize.differential_evolution_rule driven by Engine.evaluate as its objective, bit for
 bit: x, llh, nit, nfev, status, the final population and its values, and the number of points handed to the engine.
 
-The shapes are the smallest at which the kernels can still go wrong: a synthetic model on a 16-interval grid (the pulse case: the
-32-interval grid of the pulse golden), populations of 4 and 7 (7 does not divide the selection kernel's workgroup), at most 6
-generations, 3 - 4 searches over 3 rows: a generation is at most 28 points.  The rule's side of a case is computed once."""
+The shapes are the smallest at which the rule's branches can still go wrong, all inside one workgroup: a synthetic model on a
+16-interval grid (the pulse case: the 32-interval grid of the pulse golden), populations of 4 and 7 (7 does not divide the selection
+kernel's workgroup), at most 6 generations, 3 - 4 searches over 3 rows: a generation is at most 28 points.  The widths - searches over
+several workgroups, up to 256 members, 16 coordinates - are held by tests/test_gpu_population_widths.py.  The rule's side of a case is
+computed once."""
 import random
 import re
 import subprocess

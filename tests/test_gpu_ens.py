@@ -4,7 +4,8 @@ and the number of points handed to the engine.
 
 The shapes are those of tests/test_gpu_de.py: its synthetic model on a 16-interval grid (the pulse case: the 32-interval grid of the
 pulse golden), the three-row table, at most 4 searches, ensembles of 4 - 8 walkers, at most 6 steps: a half-step is at most 12
-points.  The rule's side of a case is computed once."""
+points, all inside one workgroup.  The widths - searches over several workgroups, 256 walkers, 16 coordinates - are held by
+tests/test_gpu_population_widths.py.  The rule's side of a case is computed once."""
 import random
 import re
 import subprocess
