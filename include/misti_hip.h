@@ -1000,6 +1000,77 @@ int misti_ens_log_prior(int32_t N, const int32_t* scale, const int32_t* kind, co
                         const double* y, double* lp, double* natural /* [N] or NULL */);
 int misti_ens_accept_prior(double z, int32_t d, double llk_old, double llk_new, double T, double lp_old, double lp_new, double u_acc, int32_t* accept);
 
+/* ---- joint credible regions of coordinate pairs -------------------------------------------------- */
+/* The summaries above are marginal.  The joint uncertainty of two coordinates - the ridge between a split time and a migration rate,
+ * a rate cut off by the edge of its box - is neither an interval nor an ellipse: it needs the two-dimensional density.  These entries
+ * reduce the chain [S][K][W][N], where it lies in HBM, to a two-dimensional histogram per search and coordinate pair, its mode, and
+ * the count level that encloses a given mass: a handful of KiB per search leaves the device, not the chain.  The rule is THE PROJECT'S
+ * OWN, stated once in NumPy (optimize.ensemble_joint_rule); the counts are integers, so the device result is that, bit for bit, and a
+ * search's result is a function of its own chain (and ranges) alone.
+ *
+ * Per search s and pair q = (a, b) of distinct coordinates, on the kept samples t = burn ... K - 1, w = 0 ... W - 1 (m = n W of
+ * them), with Ba x Bb bins; every floating-point operation is rounded on its own:
+ *   - range of an axis: (lo, hi) is given by the caller (`range`), or taken from the data: the smallest and the largest FINITE kept
+ *     sample of that coordinate in the key order of the summaries above (so -0.0 before +0.0), bits copied; no finite sample: both
+ *     are the canonical quiet NaN (0x7ff8000000000000);
+ *   - a sample is INSIDE the pair's window iff lo <= x && x <= hi holds on both axes: a NaN anywhere - in the sample or in the range -
+ *     makes it outside, and lo > hi makes every sample outside;
+ *   - bin of an inside sample on one axis with B bins: scale = double(B) / (hi - lo), t = (x - lo) scale; i = 0 where !(t >= 0)
+ *     (hi == lo, where 0 inf is NaN, and an infinite hi - lo); i = B - 1 where t >= double(B); otherwise i = (int)t.  x == hi lands
+ *     in the last bin; the index is monotone in x;
+ *   - counts[ia][ib]: the inside samples per cell; inside: their sum; outside = m - inside;
+ *   - mode: the cell with the largest count, ties to the lowest ia, then the lowest ib; (-1, -1) where inside == 0;
+ *   - region of mass p in (0, 1]: k is the smallest integer with double(k) >= double(inside) p (one rounded product), clamped to
+ *     1 ... inside; level is the LARGEST count c >= 1 such that the cells with count >= c hold at least k samples; cells the number
+ *     of cells with count >= level, held the samples in them.  Ties at the level are all in the region - the region is {cells:
+ *     count >= level}, no order among equal cells is needed.  inside == 0: level = cells = held = 0.
+ * The histogram lives in the SAMPLING COORDINATE, like the shortest intervals: a highest-density region is not invariant under a map
+ * of a coordinate, so the region of a log-scale coordinate ("priors and log-scale coordinates") is not the image of the region of its
+ * natural value.
+ *
+ * misti_ens_joint_dev: every chain, range and output pointer is DEVICE memory; pairs, bins and masses are HOST memory; asynchronous
+ * on the context's stream.  Any output may be NULL: it is not computed and its kernel is not launched.  counts is zeroed by the call.
+ * Beyond the chain the call keeps nothing of the chain's size: where counts is NULL and the mode or a region is asked for, the
+ * histograms [S][sum_q Ba Bb] of int32 (and the ranges, where range_out is NULL) lie in a growable buffer of the context.
+ * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this library's;
+ * S < 0, W < 1 or N < 1; burn outside 0 ... K - 1; a NULL chain with S > 0; MISTI_E_LIMIT for W > MISTI_ENS_MAX_WALKERS, N >
+ * MISTI_MAX_PARAMS, m > INT32_MAX or S > INT32_MAX (these as misti_ens_summary_dev words them); then MISTI_E_ARG for n_pair outside
+ * 1 ... MISTI_JOINT_MAX_PAIRS; a NULL pairs or bins; a coordinate outside 0 ... N - 1 or a == b; a bin count outside 1 ...
+ * MISTI_JOINT_MAX_BINS; n_mass outside 0 ... MISTI_POST_MAX_PROBS; n_mass > 0 with a NULL masses; a mass outside (0, 1] or NaN;
+ * level, cells or held given with n_mass == 0; then a NULL context.  A given range is not checked - it may be device memory -: the
+ * rule defines what a bad range does.  S == 0 writes nothing.
+ *
+ * misti_ensemble_sample_joint / misti_tempered_sample_joint: misti_ensemble_sample_prior / misti_tempered_sample_prior with the
+ * joint reduction run on the kept (cold) chain where it lies, K = n_step / thin; `range` and the outputs are HOST buffers there,
+ * copied with the rest, and the chain itself comes back only where the sampler gives `chain`.  joint == NULL IS the older entry; with
+ * a joint the sampler's and post's outputs keep their bits.  Errors: the older entry's in their order (a wrong size of `joint` beside
+ * the other descriptors' sizes), then the list above for `joint` from `burn` on, behind post's.  Every older entry launches and
+ * allocates exactly what it did before these existed. */
+#define MISTI_JOINT_MAX_PAIRS 120
+#define MISTI_JOINT_MAX_BINS 128
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_ens_joint_t) */
+    int32_t burn;                    /* kept steps dropped before the reduction: 0 ... K - 1 */
+    int32_t n_pair;                  /* 1 ... MISTI_JOINT_MAX_PAIRS (every pair of 16 coordinates) */
+    const int32_t* pairs;            /* HOST [n_pair][2]: the coordinates (a, b) of each pair, distinct, 0 ... N - 1 */
+    const int32_t* bins;             /* HOST [n_pair][2]: (Ba, Bb), each 1 ... MISTI_JOINT_MAX_BINS */
+    const double* range;             /* [S][n_pair][2][2] or NULL: (lo, hi) per axis; NULL: taken from the data */
+    int32_t n_mass;                  /* 0 ... MISTI_POST_MAX_PROBS */
+    const double* masses;            /* HOST [n_mass], each in (0, 1]; not read where n_mass == 0 */
+    int32_t* counts;                 /* [S][sum_q Ba Bb] or NULL: the pairs packed in order, pair q row-major [Ba][Bb] */
+    double* range_out;               /* [S][n_pair][2][2] or NULL: the ranges used */
+    int32_t* inside;                 /* [S][n_pair] or NULL: the samples inside the window */
+    int32_t* mode;                   /* [S][n_pair][2] or NULL: the mode cell (ia, ib) */
+    int32_t* level;                  /* [S][n_pair][n_mass] or NULL: the region's count level */
+    int32_t* cells;                  /* [S][n_pair][n_mass] or NULL: the cells in the region */
+    int32_t* held;                   /* [S][n_pair][n_mass] or NULL: the samples in the region */
+} misti_ens_joint_t;
+int misti_ens_joint_dev(misti_ctx* ctx, int64_t S, int64_t K, int32_t W, int32_t N, const double* d_chain, const misti_ens_joint_t* joint);
+int misti_ensemble_sample_joint(misti_ctx* ctx, const misti_ens_t* sampler, const misti_ens_post_t* post /* or NULL */, const misti_prior_t* prior /* or NULL */,
+                                const misti_ens_joint_t* joint /* or NULL */);
+int misti_tempered_sample_joint(misti_ctx* ctx, const misti_pt_t* sampler, const misti_ens_post_t* post /* or NULL */, const misti_prior_t* prior /* or NULL */,
+                                const misti_ens_joint_t* joint /* or NULL */);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

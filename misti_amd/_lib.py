@@ -130,6 +130,17 @@ class EnsPost(C.Structure):
                 ("n_mass", C.c_int32), ("masses", C.c_void_p), ("hpd", C.c_void_p), ("hpd_at", C.c_void_p), ("order", C.c_void_p)]
 
 
+JOINT_MAX_PAIRS, JOINT_MAX_BINS = 120, 128
+JOINT_SLAB = 4096                    # MISTI_JOINT_SLAB (csrc/misti_joint.h): the samples a histogram workgroup bins
+
+
+class EnsJoint(C.Structure):
+    """``misti_ens_joint_t``: joint regions of coordinate pairs of a chain; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("burn", C.c_int32), ("n_pair", C.c_int32), ("pairs", C.c_void_p), ("bins", C.c_void_p), ("range", C.c_void_p),
+                ("n_mass", C.c_int32), ("masses", C.c_void_p), ("counts", C.c_void_p), ("range_out", C.c_void_p), ("inside", C.c_void_p),
+                ("mode", C.c_void_p), ("level", C.c_void_p), ("cells", C.c_void_p), ("held", C.c_void_p)]
+
+
 class MistiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmisti_hip error %d: %s" % (code, msg))
@@ -167,6 +178,9 @@ SYMBOLS = {
     "misti_tempered_sample": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost)]),
     "misti_ensemble_sample_prior": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost), C.POINTER(Prior)]),
     "misti_tempered_sample_prior": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost), C.POINTER(Prior)]),
+    "misti_ens_joint_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(EnsJoint)]),
+    "misti_ensemble_sample_joint": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost), C.POINTER(Prior), C.POINTER(EnsJoint)]),
+    "misti_tempered_sample_joint": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost), C.POINTER(Prior), C.POINTER(EnsJoint)]),
     "misti_ens_log_prior": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_ens_accept_prior": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "misti_pt_swap": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

@@ -113,6 +113,15 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               ` hpd MASS = [lo, hi]` behind its quantiles.  An equal-tailed interval cuts 2.5 % off the low side even where the
                               posterior piles up at the edge of the box; the shortest one does not.  For a --mcmc-log coordinate the ends are
                               printed in natural units, but the interval is the shortest on the log scale: HPD is not invariant under the map
+    --mcmc-joint A B [BINS]   with --mcmc; repeatable: the JOINT region of the coordinates A and B (an index, or st - as --box names them), reduced
+                              ON THE DEVICE (misti_ensemble_sample_joint): a histogram of BINS x BINS cells (1 ... 128; default 32) over the
+                              pair's --box, its mode, and per mass the count level whose cells enclose it - the ridge between a split time and
+                              a rate is neither an interval nor an ellipse.  One `joint:` line per fit and pair: the window, the mode cell's
+                              centre, and per mass `level`, `cells`, `held / inside` and the extent per axis.  Works with and without
+                              --mcmc-post, --mcmc-ladder, --mcmc-log and --mcmc-prior.  The histogram lives in the SAMPLING coordinate: for a
+                              --mcmc-log coordinate the line prints natural units, the IMAGE of a region that is highest-density on the log scale
+    --mcmc-joint-mass P ...   with --mcmc-joint: the masses of the regions (1 ... 8, each in (0, 1]; default 0.95)
+    --mcmc-joint-out FILE.npz with --mcmc-joint: the counts, ranges, bin edges and levels of every fit and pair, as NumPy arrays
     --mcmc-log K [K ...]      with --mcmc: coordinate K (an index, or st - as --box names them) is SAMPLED ON THE LOG SCALE (misti_ensemble_sample_prior):
                               the stretch, the box test and the chain are in ln(value), the engine is handed the value.  Its --box is given in
                               natural units and needs LO > 0; flat on the log scale is the log-uniform prior.  The `mcmc:` / `post:` lines print
@@ -270,6 +279,11 @@ def build_parser():
     p.add_argument("--mcmc-swap", type=int, default=None, metavar="E", help="with --mcmc-ladder: a swap round every E steps (default 1; 0: never)")
     p.add_argument("--mcmc-post", nargs="*", type=float, default=None, metavar="P",
                    help="with --mcmc: posterior summaries reduced on the device, `post:` lines in place of `mcmc:` lines; P ...: the quantiles (default 0.025 0.5 0.975)")
+    p.add_argument("--mcmc-joint", nargs="+", action="append", default=None, metavar="A",
+                   help="with --mcmc; repeatable: A B [BINS] - the joint region of the coordinates A and B (an index, or st), a BINS x BINS histogram (default 32) "
+                        "reduced on the device; one `joint:` line per fit and pair")
+    p.add_argument("--mcmc-joint-mass", nargs="+", type=float, default=None, metavar="P", help="with --mcmc-joint: the masses of the regions (default 0.95)")
+    p.add_argument("--mcmc-joint-out", default=None, metavar="FILE.npz", help="with --mcmc-joint: write counts, ranges, edges and levels")
     p.add_argument("--mcmc-log", nargs="+", default=None, metavar="K", help="with --mcmc: coordinates (an index, or st) sampled on the log scale; their --box is in natural units, LO > 0")
     p.add_argument("--mcmc-prior", nargs="+", action="append", default=None, metavar="K",
                    help="with --mcmc: K normal MEAN SD | K exponential SCALE - a prior on coordinate K's sampling coordinate (repeatable)")
@@ -606,6 +620,8 @@ def mcmc_error(a):
             return "--mcmc-ladder / --mcmc-swap temper the sampler of --mcmc W STEPS: give --mcmc W STEPS"
         if a.mcmc_log is not None or a.mcmc_prior is not None:
             return "--mcmc-log / --mcmc-prior state the coordinates and priors of --mcmc W STEPS: give --mcmc W STEPS"
+        if a.mcmc_joint is not None or a.mcmc_joint_mass is not None or a.mcmc_joint_out is not None:
+            return "--mcmc-joint / --mcmc-joint-mass / --mcmc-joint-out give the joint regions of --mcmc W STEPS: give --mcmc W STEPS"
         return None
     W, steps = a.mcmc
     if not 4 <= W <= 256 or W % 2:
@@ -670,6 +686,23 @@ def mcmc_error(a):
         if not all(np.isfinite(v) for v in boxed[name]):
             return "--mcmc needs a finite box: --box %s has an infinite bound" % name
     names = [str(i) for i in range(k)] + (["st"] if a.fit_st else [])
+    if a.mcmc_joint is None and (a.mcmc_joint_mass is not None or a.mcmc_joint_out is not None):
+        return "--mcmc-joint-mass / --mcmc-joint-out belong to --mcmc-joint A B [BINS]: give it"
+    for spec in a.mcmc_joint or ():
+        text = " ".join(spec)
+        if not 2 <= len(spec) <= 3:
+            return "--mcmc-joint A B [BINS]: two coordinates and at most a bin count (got %s)" % text
+        for name in spec[:2]:
+            if name not in names:
+                return "--mcmc-joint %s: %s is no coordinate of this run (%s)" % (text, name, ", ".join(names))
+        if spec[0] == spec[1]:
+            return "--mcmc-joint %s: A == B - a pair needs two distinct coordinates" % text
+        if len(spec) == 3 and not (spec[2].isdigit() and 1 <= int(spec[2]) <= 128):
+            return "--mcmc-joint %s: BINS must be an integer, 1 ... 128" % text
+    if a.mcmc_joint is not None and len(a.mcmc_joint) > 120:
+        return "--mcmc-joint: at most 120 pairs (got %d)" % len(a.mcmc_joint)
+    if a.mcmc_joint_mass is not None and (len(a.mcmc_joint_mass) > 8 or not all(0.0 < v <= 1.0 for v in a.mcmc_joint_mass)):
+        return "--mcmc-joint-mass P ...: at most 8 masses, each in (0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_joint_mass)
     for name in a.mcmc_log or ():
         if name not in names:
             return "--mcmc-log K: %s is no coordinate of this run (%s)" % (name, ", ".join(names))
@@ -709,6 +742,16 @@ def _mcmc_prior(a, k):
                       exponential={c: v[0] for c, kind, v in specs if kind == "exponential"})
 
 
+def _mcmc_joint(a, k):
+    """The ``joint=`` of the samplers for --mcmc-joint / --mcmc-joint-mass over the k parameters (st: coordinate k), or None without
+    the option: every window is the pair's --box, in sampling coordinates."""
+    if a.mcmc_joint is None:
+        return None
+    at = lambda name: k if name == "st" else int(name)
+    return dict(pairs=[(at(sp[0]), at(sp[1])) for sp in a.mcmc_joint], bins=[[int(sp[2]) if len(sp) == 3 else 32] * 2 for sp in a.mcmc_joint],
+                range="box", masses=tuple(a.mcmc_joint_mass) if a.mcmc_joint_mass else (0.95,))
+
+
 def _mcmc_from_de(a):
     """--de W GENS ran with the sampler's W: the initial ensembles are DE's final populations."""
     return bool(a.mcmc and a.de and a.de[0] == a.mcmc[0])
@@ -739,6 +782,7 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     lo, hi = box
     x = np.where(np.isfinite(x), np.clip(x, lo, hi), 0.5 * (lo + hi))
     prior = o["prior"] = _mcmc_prior(a, x.shape[1] - (1 if split_times is None else 0))
+    o["fit_split"] = split_times is None
     T = o["temperature"]
     if T == "auto":
         P = e.n_param
@@ -777,6 +821,9 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     common = dict(split_times=split_times, fit_split=split_times is None, n_step=o["n_step"], thin=o["thin"], seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
     if prior is not None:
         common["prior"] = prior
+    joint = _mcmc_joint(a, x.shape[1] - (1 if split_times is None else 0))
+    if joint is not None:                                  # the regions on the device, over the kept steps behind the burn-in
+        common["joint"] = dict(joint, burn=o["burn"])
     extra = {}
     if o["ladder"] is not None:
         ladder = temperature_ladder(T, o["ladder"][1], o["ladder"][0])
@@ -791,7 +838,31 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
         np.savez(a.mcmc_out, chain=res["chain"], chain_llh=res["chain_llh"], accepted=res["accepted"], last=res["last"], last_llh=res["last_llh"],
                  row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T), **extra,
                  **({} if prior is None else {"prior_" + k: v for k, v in prior.items()}))
+    if a.mcmc_joint_out:
+        from .optimize import joint_table
+        j = res["joint"]
+        edges = {"edges_%d_%d" % (q, ax): np.stack([t[q]["edges"][ax] for t in joint_table(j)]) for q in range(len(j["pairs"])) for ax in (0, 1)}
+        np.savez(a.mcmc_joint_out, **{k_: j[k_] for k_ in ("counts", "range", "inside", "mode", "level", "cells", "held", "pairs", "bins", "offsets", "masses")},
+                 burn=o["burn"], **edges, **({} if prior is None else {"prior_scale": prior["scale"]}))
     return o, float(T), res
+
+
+def print_joint(label, o, res, s):
+    """The ``joint:`` lines of fit s: one per pair of --mcmc-joint, from the histograms the device reduced.  Sampling units, except for
+    a --mcmc-log coordinate: natural units, the image of a region that is highest-density on the log scale - the line says so."""
+    from .optimize import joint_table
+    j = res["joint"]
+    rows = joint_table({k: (v[s] if k in ("counts", "range", "inside", "mode", "level", "cells", "held") else v) for k, v in j.items()}, prior=o.get("prior"))
+    name = lambda c: "st" if o.get("fit_split") and c == res["last"].shape[-1] - 1 else str(c)
+    pair = lambda v: "[%r, %r] x [%r, %r]" % (v[0][0], v[0][1], v[1][0], v[1][1])
+    for t in rows:
+        log = t.get("natural_is_image", False)
+        print("joint:", label, "\tcoordinates (%s, %s)" % (name(t["pair"][0]), name(t["pair"][1])), "\tbins = %d x %d" % (len(t["edges"][0]) - 1, len(t["edges"][1]) - 1),
+              "\twindow =", pair(t.get("window_natural", t["window"])), "\tinside = %d" % t["inside"],
+              "\tmode = (%r, %r)" % tuple(t.get("mode_centre_natural", t["mode_centre"])),
+              *("\tmass %g: level = %d cells = %d held = %d / %d extent = %s" % (r["mass"], r["level"], r["cells"], r["held"], t["inside"], pair(r.get("extent_natural", r["extent"])))
+                for r in t["regions"]),
+              *(["\t(log scale: the region is highest-density in the logarithm; window, mode and extent are its image in natural units)"] if log else []))
 
 
 def _mcmc_post_options(a):
@@ -840,6 +911,9 @@ def print_ladder(label, res, s):
 def print_mcmc(label, o, res, s):
     """The ``mcmc:`` lines of fit s: one per coordinate, from ensemble_summary of its chain - or, with --mcmc-post, its ``post:`` lines;
     of a tempered run (--mcmc-ladder) the cold rung's, and behind them the fit's ``ladder:`` line."""
+    if "joint" in res:                                     # behind everything else of the fit
+        print_mcmc(label, o, {k: v for k, v in res.items() if k != "joint"}, s)
+        return print_joint(label, o, res, s)
     if "logz" in res:
         cold = {k: v for k, v in res.items() if k not in ("logz", "accepted")}
         print_mcmc(label, o, dict(cold, accepted=res["accepted"][:, 0]), s)

@@ -1,7 +1,9 @@
 // The samplers of the C ABI (include/misti_hip.h) over the rows problem (misti_rows.h): ensemble MCMC per search (misti_ens.hip), its
-// tempered form per fit (misti_pt.hip), priors and log-scale coordinates (misti_prior.h) and the posterior summaries (misti_post.hip).
+// tempered form per fit (misti_pt.hip), priors and log-scale coordinates (misti_prior.h), the posterior summaries (misti_post.hip) and
+// the joint regions of coordinate pairs (misti_joint.hip).
 #include <cstdio>
 
+#include "misti_joint.h"
 #include "misti_post.h"
 #include "misti_prior.h"
 #include "misti_rows.h"
@@ -79,6 +81,80 @@ int post_back(const misti::PostArgs& pa, const misti_ens_post_t& p, size_t S, in
     HIP_TRY(back(p.hpd, pa.hpd, SN * (size_t)p.n_mass * 2 * sizeof(double)));
     HIP_TRY(back(p.hpd_at, pa.hpd_at, SN * (size_t)p.n_mass * sizeof(int32_t)));
     HIP_TRY(back(p.order, pa.order, SN * (size_t)pa.n * (size_t)pa.W * sizeof(double)));
+    return 0;
+}
+
+// ---- joint regions of coordinate pairs (misti_joint.hip) --------------------------------------------------------------------------------
+// The arguments of misti_ens_joint_dev, before the first HIP call, in the header's order, up to the context (the caller's).  The shape
+// errors are misti_ens_summary_dev's, worded as there.
+int joint_check(const misti_ens_joint_t* j, int64_t S, int64_t K, int32_t W, int32_t N, bool have_chain) {
+    if (!j) return fail(MISTI_E_ARG, "the joint descriptor is NULL");
+    if (j->size != sizeof(misti_ens_joint_t))
+        return fail(MISTI_E_ARG, "the joint descriptor's size is %u, this library's misti_ens_joint_t has %u bytes", (unsigned)j->size, (unsigned)sizeof(misti_ens_joint_t));
+    if (S < 0 || W < 1 || N < 1) return fail(MISTI_E_ARG, "negative number of searches, or no walker or coordinate (S = %lld, W = %d, N = %d)", (long long)S, (int)W, (int)N);
+    if (j->burn < 0 || j->burn >= K) return fail(MISTI_E_ARG, "burn must be 0 ... K - 1 (got %d for %lld kept steps)", (int)j->burn, (long long)K);
+    if (!have_chain && S > 0) return fail(MISTI_E_ARG, "the chain is NULL");
+    if (W > MISTI_ENS_MAX_WALKERS) return fail(MISTI_E_LIMIT, "W = %d exceeds MISTI_ENS_MAX_WALKERS = %d", (int)W, MISTI_ENS_MAX_WALKERS);
+    if (N > MISTI_MAX_PARAMS) return fail(MISTI_E_LIMIT, "N = %d exceeds MISTI_MAX_PARAMS = %d", (int)N, MISTI_MAX_PARAMS);
+    if ((K - j->burn) > INT32_MAX / W) return fail(MISTI_E_LIMIT, "%lld kept steps x %d walkers exceed INT32_MAX samples per search", (long long)(K - j->burn), (int)W);
+    if (S > INT32_MAX) return fail(MISTI_E_LIMIT, "too many searches for one call");
+    if (j->n_pair < 1 || j->n_pair > MISTI_JOINT_MAX_PAIRS) return fail(MISTI_E_ARG, "n_pair must be 1 ... %d (got %d)", MISTI_JOINT_MAX_PAIRS, (int)j->n_pair);
+    if (!j->pairs || !j->bins) return fail(MISTI_E_ARG, "pairs / bins is NULL");
+    for (int q = 0; q < j->n_pair; ++q) {
+        const int32_t a = j->pairs[2 * q], b = j->pairs[2 * q + 1];
+        if (a < 0 || a >= N || b < 0 || b >= N) return fail(MISTI_E_ARG, "pairs[%d] = (%d, %d): a coordinate is outside 0 ... %d", q, (int)a, (int)b, (int)N - 1);
+        if (a == b) return fail(MISTI_E_ARG, "pairs[%d] = (%d, %d): a pair needs two distinct coordinates", q, (int)a, (int)b);
+    }
+    for (int q = 0; q < 2 * j->n_pair; ++q)
+        if (j->bins[q] < 1 || j->bins[q] > MISTI_JOINT_MAX_BINS)
+            return fail(MISTI_E_ARG, "bins[%d][%d] = %d: a bin count must be 1 ... %d", q / 2, q % 2, (int)j->bins[q], MISTI_JOINT_MAX_BINS);
+    if (j->n_mass < 0 || j->n_mass > MISTI_POST_MAX_PROBS) return fail(MISTI_E_ARG, "the joint n_mass must be 0 ... %d (got %d)", MISTI_POST_MAX_PROBS, (int)j->n_mass);
+    if (j->n_mass > 0 && !j->masses) return fail(MISTI_E_ARG, "the joint masses is NULL");
+    for (int i = 0; i < j->n_mass; ++i)
+        if (!(j->masses[i] > 0.0 && j->masses[i] <= 1.0)) return fail(MISTI_E_ARG, "the joint masses[%d] = %g is not in (0, 1]", i, j->masses[i]);
+    if (j->n_mass == 0 && (j->level || j->cells || j->held)) return fail(MISTI_E_ARG, "level / cells / held given with n_mass == 0: a region needs its mass");
+    return 0;
+}
+
+// the launch record of a checked descriptor, without its pointers
+void joint_fill(misti::JointArgs& a, int64_t S, int64_t K, int32_t W, int32_t N, const misti_ens_joint_t& j) {
+    a.S = S; a.K = K; a.burn = j.burn; a.n = K - j.burn; a.W = W; a.N = N; a.n_pair = j.n_pair; a.n_mass = j.n_mass;
+    a.slabs = (int32_t)((a.n * W + misti::JOINT_SLAB - 1) / misti::JOINT_SLAB);
+    bool used[MISTI_MAX_PARAMS] = {};
+    for (int q = 0; q < j.n_pair; ++q) {
+        a.a[q] = (uint8_t)j.pairs[2 * q]; a.b[q] = (uint8_t)j.pairs[2 * q + 1];
+        a.Ba[q] = (uint8_t)j.bins[2 * q]; a.Bb[q] = (uint8_t)j.bins[2 * q + 1];
+        a.off[q] = (int32_t)a.cells;
+        a.cells += (int64_t)j.bins[2 * q] * j.bins[2 * q + 1];
+        used[a.a[q]] = used[a.b[q]] = true;
+    }
+    for (int k = 0; k < N; ++k)
+        if (used[k]) a.coord[a.n_coord++] = (uint8_t)k;
+    for (int i = 0; i < j.n_mass; ++i) a.mass[i] = j.masses[i];
+}
+bool joint_levels(const misti_ens_joint_t& j) { return j.inside || j.mode || j.level || j.cells || j.held; }
+
+// The device side of the regions of a sampler that keeps its chain (sampler_run): carved behind everything else, the summaries'
+// included, so no older layout moves.  The window is always carved - a given range is uploaded into it -, the histograms where they
+// or what is read off them are asked for.  back(): to the descriptor's host buffers.
+void joint_carve(misti::JointArgs& ja, const misti_ens_joint_t& j, size_t S, Carver<double>& f, Carver<int32_t>& i) {
+    const size_t SP = S * (size_t)j.n_pair, NM = (size_t)j.n_mass;
+    double* window = f.take(SP * 4);
+    ja.window = window; ja.from_data = j.range ? nullptr : window;
+    ja.counts = j.counts || joint_levels(j) ? i.take(S * (size_t)ja.cells) : nullptr;
+    ja.inside = j.inside ? i.take(SP) : nullptr; ja.mode = j.mode ? i.take(2 * SP) : nullptr;
+    ja.level = j.level ? i.take(SP * NM) : nullptr; ja.n_cells = j.cells ? i.take(SP * NM) : nullptr; ja.held = j.held ? i.take(SP * NM) : nullptr;
+}
+int joint_back(const misti::JointArgs& ja, const misti_ens_joint_t& j, size_t S, hipStream_t sm) {
+    const size_t SP = S * (size_t)j.n_pair, NM = (size_t)j.n_mass;
+    auto back = [&](void* host, const void* dev, size_t bytes) { return host && bytes ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm) : hipSuccess; };
+    HIP_TRY(back(j.counts, ja.counts, S * (size_t)ja.cells * sizeof(int32_t)));
+    HIP_TRY(back(j.range_out, ja.window, SP * 4 * sizeof(double)));
+    HIP_TRY(back(j.inside, ja.inside, SP * sizeof(int32_t)));
+    HIP_TRY(back(j.mode, ja.mode, 2 * SP * sizeof(int32_t)));
+    HIP_TRY(back(j.level, ja.level, SP * NM * sizeof(int32_t)));
+    HIP_TRY(back(j.cells, ja.n_cells, SP * NM * sizeof(int32_t)));
+    HIP_TRY(back(j.held, ja.held, SP * NM * sizeof(int32_t)));
     return 0;
 }
 
@@ -175,15 +251,15 @@ struct SamplerArgs {
     int64_t* n_points;
     const char *noun, *per, *kept;   // the words the doors' texts differ in: "searches" | "fits"; what the limits count; "device " chain
 };
-// the plain door keeps both chains or none: where the caller or a summary (`post`) asks for one
-SamplerArgs sampler_args(const misti_ens_t& q, const misti_ens_post_t* post) {
+// the plain door keeps both chains or none: where the caller or a reduction (`post`: a summary or a joint descriptor) asks for one
+SamplerArgs sampler_args(const misti_ens_t& q, const void* post) {
     const bool keep = q.chain || q.chain_llh || post;
     return {rows_args(q), q.init, q.walkers, 1, false, q.n_temp, q.temperature, q.n_step, q.thin, q.a, q.seed, 0, 0, keep, keep,
             q.chain, q.chain_llh, q.accepted, nullptr, nullptr, q.last, q.last_llh, nullptr, nullptr, q.n_points,
             "searches", "searches x walkers", post ? "device " : ""};
 }
 // the tempered door always keeps the values of every rung (the reduction reads them), the cold rung's coordinates where they are wanted
-SamplerArgs sampler_args(const misti_pt_t& q, const misti_ens_post_t* post) {
+SamplerArgs sampler_args(const misti_pt_t& q, const void* post) {
     return {rows_args(q), q.init, q.walkers, q.n_rung, true, q.n_ladder, q.ladder, q.n_step, q.thin, q.a, q.seed, q.swap_every, q.burn,
             q.chain || post, true, q.chain, q.chain_llh, q.accepted, q.swap_proposed, q.swap_accepted, q.last, q.last_llh, q.rung_llh, q.logz,
             q.n_points, "fits", "fits x rungs x walkers", ""};
@@ -263,14 +339,17 @@ int sampler_check(const misti_ctx* c, const SamplerArgs& q, const misti_prior_t*
 // the chains lie in the search buffers of the context, and nothing is read back before the end.  A tempered call adds a swap launch
 // behind the steps that have a round, the reduction at the end, and their four arrays; a plain call issues neither launch and carves
 // none of them.  With `post` (checked: post_check) the summary kernels run on the cold chain where it lies and the summaries come back
-// with the rest; the series workspace and the summaries' device side are carved with the chain.
-int sampler_run(misti_ctx* c, const SamplerArgs& q, int N, bool whole, const misti_ens_post_t* post, const misti_prior_t* prior) {
+// with the rest; the series workspace and the summaries' device side are carved with the chain.  With `joint` (checked: joint_check)
+// the kernels of misti_joint.hip follow on the same chain, their device side carved behind the summaries'.
+int sampler_run(misti_ctx* c, const SamplerArgs& q, int N, bool whole, const misti_ens_post_t* post, const misti_prior_t* prior, const misti_ens_joint_t* joint) {
     using namespace misti;
     HIP_TRY(hipSetDevice(c->device));
     const size_t F = (size_t)q.rows.n_start, L = (size_t)q.n_rung, S = F * L, W = (size_t)q.walkers, H = W / 2, M = S * W, NT = (size_t)q.n_temp * L;
     const size_t K = (q.keep_x || q.keep_llh) ? (size_t)(q.n_step / q.thin) : 0, P = F * (L - 1);
     PostArgs pa{};
     if (post) post_fill(pa, q.rows.n_start, (int64_t)K, q.walkers, N, *post);
+    JointArgs ja{};
+    if (joint) joint_fill(ja, q.rows.n_start, (int64_t)K, q.walkers, N, *joint);
     RowsProblem rows(c, q.rows, N, whole);
     PriorProblem pri(prior, N, S * H);
     EnsState st{};
@@ -294,6 +373,7 @@ int sampler_run(misti_ctx* c, const SamplerArgs& q, int N, bool whole, const mis
         rows.layout(f, i, &st.b, &M, 1, M);
         pri.layout(f, i);
         if (post) post_carve(pa, *post, F, N, f, i);
+        if (joint) joint_carve(ja, *joint, F, f, i);
     };
     if (int r = carve(c->nm_f64, c->nm_i32, layout)) return r;
     rows.fill(st.src);
@@ -330,6 +410,12 @@ int sampler_run(misti_ctx* c, const SamplerArgs& q, int N, bool whole, const mis
         HIP_TRY(launch_post(pa, sm));
         if (int r = post_back(pa, *post, F, N, sm)) return r;
     }
+    if (joint) {
+        ja.chain = st.chain;
+        if (joint->range) HIP_TRY(hipMemcpyAsync(const_cast<double*>(ja.window), joint->range, F * (size_t)joint->n_pair * 4 * sizeof(double), hipMemcpyHostToDevice, sm));
+        HIP_TRY(launch_joint(ja, sm));
+        if (int r = joint_back(ja, *joint, F, sm)) return r;
+    }
     auto back = [&](void* host, const void* dev, size_t bytes) { return host && bytes ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sm) : hipSuccess; };
     HIP_TRY(back(q.last, st.x, M * N * sizeof(double)));
     HIP_TRY(back(q.last_llh, st.llh, M * sizeof(double)));
@@ -361,24 +447,32 @@ int sampler_size(const void* q, uint32_t size, uint32_t want, const char* type) 
     if (size != want) return fail(MISTI_E_ARG, "the sampler descriptor's size is %u, this library's %s has %u bytes", (unsigned)size, type, (unsigned)want);
     return 0;
 }
-int sampler_door(misti_ctx* c, const SamplerArgs& q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post) {
+int sampler_door(misti_ctx* c, const SamplerArgs& q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post, const misti_ens_joint_t* j) {
     if (need_post && !p) return fail(MISTI_E_ARG, "the summary descriptor is NULL");
     if (p && p->size != sizeof(misti_ens_post_t))
         return fail(MISTI_E_ARG, "the summary descriptor's size is %u, this library's misti_ens_post_t has %u bytes", (unsigned)p->size, (unsigned)sizeof(misti_ens_post_t));
     if (pr && pr->size != sizeof(misti_prior_t))
         return fail(MISTI_E_ARG, "the prior descriptor's size is %u, this library's misti_prior_t has %u bytes", (unsigned)pr->size, (unsigned)sizeof(misti_prior_t));
+    if (j && j->size != sizeof(misti_ens_joint_t))
+        return fail(MISTI_E_ARG, "the joint descriptor's size is %u, this library's misti_ens_joint_t has %u bytes", (unsigned)j->size, (unsigned)sizeof(misti_ens_joint_t));
     if (q.rows.split != MISTI_SPLIT_PER_START && q.rows.split != MISTI_SPLIT_FITTED)
         return fail(MISTI_E_ARG, "the sampler descriptor's split mode %d is neither MISTI_SPLIT_PER_START nor MISTI_SPLIT_FITTED", (int)q.rows.split);
     int N = 0;
     bool whole = false;
     if (int r = sampler_check(c, q, pr, N, whole)) return r;
     if (p) if (int r = post_check(p, q.rows.n_start, q.n_step / q.thin, q.walkers, N, true)) return r;
+    if (j) if (int r = joint_check(j, q.rows.n_start, q.n_step / q.thin, q.walkers, N, true)) return r;
     if (q.rows.n_start == 0) return 0;
-    return sampler_run(c, q, N, whole, p, pr);
+    return sampler_run(c, q, N, whole, p, pr, j);
 }
-int ens_door(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post) {
+const void* reduced(const misti_ens_post_t* p, const misti_ens_joint_t* j) { return p ? static_cast<const void*>(p) : static_cast<const void*>(j); }
+int ens_door(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, bool need_post, const misti_ens_joint_t* j = nullptr) {
     if (int r = sampler_size(q, q ? q->size : 0, sizeof(misti_ens_t), "misti_ens_t")) return r;
-    return sampler_door(c, sampler_args(*q, p), p, pr, need_post);
+    return sampler_door(c, sampler_args(*q, reduced(p, j)), p, pr, need_post, j);
+}
+int pt_door(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, const misti_ens_joint_t* j) {
+    if (int r = sampler_size(q, q ? q->size : 0, sizeof(misti_pt_t), "misti_pt_t")) return r;
+    return sampler_door(c, sampler_args(*q, reduced(p, j)), p, pr, false, j);
 }
 
 }  // namespace
@@ -391,9 +485,14 @@ int misti_ensemble_posterior(misti_ctx* c, const misti_ens_t* q, const misti_ens
 
 int misti_ensemble_sample_prior(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) { return ens_door(c, q, p, pr, false); }
 
-int misti_tempered_sample_prior(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) {
-    if (int r = sampler_size(q, q ? q->size : 0, sizeof(misti_pt_t), "misti_pt_t")) return r;
-    return sampler_door(c, sampler_args(*q, p), p, pr, false);
+int misti_tempered_sample_prior(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr) { return pt_door(c, q, p, pr, nullptr); }
+
+int misti_ensemble_sample_joint(misti_ctx* c, const misti_ens_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, const misti_ens_joint_t* j) {
+    return ens_door(c, q, p, pr, false, j);
+}
+
+int misti_tempered_sample_joint(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p, const misti_prior_t* pr, const misti_ens_joint_t* j) {
+    return pt_door(c, q, p, pr, j);
 }
 
 int misti_tempered_sample(misti_ctx* c, const misti_pt_t* q, const misti_ens_post_t* p) { return misti_tempered_sample_prior(c, q, p, nullptr); }
@@ -434,6 +533,30 @@ int misti_ens_summary_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t
     a.best_llh = p->best_llh; a.best_x = p->best_x; a.best_at = p->best_at;
     a.hpd = p->hpd; a.hpd_at = p->hpd_at; a.order = p->order;
     HIP_TRY(misti::launch_post(a, c->stream));
+    return 0;
+}
+
+int misti_ens_joint_dev(misti_ctx* c, int64_t S, int64_t K, int32_t W, int32_t N, const double* d_chain, const misti_ens_joint_t* j) {
+    if (int r = joint_check(j, S, K, W, N, d_chain != nullptr)) return r;
+    if (!c) return fail(MISTI_E_ARG, "ctx is NULL");
+    if (S == 0 || !(j->counts || j->range_out || joint_levels(*j))) return 0;   // nothing asked for: nothing launched
+    HIP_TRY(hipSetDevice(c->device));
+    misti::JointArgs a{};
+    joint_fill(a, S, K, W, N, *j);
+    // the context's workspace: the window where the data gives it and the caller does not take it | the histograms where only what is
+    // read off them is asked for.  Doubles first: both parts stay aligned.
+    const size_t window = !j->range && !j->range_out ? (size_t)S * (size_t)j->n_pair * 4 : 0;
+    const size_t counts = !j->counts && joint_levels(*j) ? (size_t)S * (size_t)a.cells : 0;
+    if (window || counts) HIP_TRY(c->joint_ws.reserve(window * sizeof(double) + counts * sizeof(int32_t)));
+    a.chain = d_chain;
+    a.from_data = j->range ? nullptr : window ? c->joint_ws.as<double>() : j->range_out;
+    a.window = j->range ? j->range : a.from_data;
+    a.counts = j->counts ? j->counts : counts ? reinterpret_cast<int32_t*>(c->joint_ws.as<double>() + window) : nullptr;
+    a.inside = j->inside; a.mode = j->mode; a.level = j->level; a.n_cells = j->cells; a.held = j->held;
+    if (j->range && j->range_out)
+        HIP_TRY(hipMemcpyAsync(j->range_out, j->range, (size_t)S * (size_t)j->n_pair * 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (!a.counts && !a.from_data) return 0;                                    // only range_out of a given range: the copy above
+    HIP_TRY(misti::launch_joint(a, c->stream));
     return 0;
 }
 

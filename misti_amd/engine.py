@@ -720,7 +720,7 @@ class Engine:
                           p0=p0.ctypes.data, p1=p1.ctypes.data), keep
 
     def ensemble_sample(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
-                        thin=1, temperature=1.0, a=2.0, seed=0, ids=None, prior=None):
+                        thin=1, temperature=1.0, a=2.0, seed=0, ids=None, prior=None, joint=None):
         """``misti_ensemble_sample``: ensemble MCMC per search - search s is an ensemble of W walkers ``init[s]`` (``[S][W][N]``, W even,
         every walker inside its box) against ``table[rows[s]]`` (``[n_rep][8]``), sampling ``llk / temperature`` under a uniform prior on
         its finite ``box`` (``(lo, hi)``, each ``[N]`` or ``[S][N]``; ``lo == hi`` holds a coordinate fixed); every half-step of all
@@ -735,9 +735,13 @@ class Engine:
         ``prior`` (None, or dict(scale, kind, p0, p1), each ``[N]`` or ``[S][N]``: ``optimize.prior_spec``): a sampling coordinate (the
         engine's value or its logarithm) and a prior density per coordinate - ``misti_ensemble_sample_prior``, the rule is
         ``optimize.ensemble_prior_rule``.  ``init``, ``box``, ``chain`` and ``last`` are then in SAMPLING coordinates
-        (``optimize.to_sampling`` / ``from_sampling``); the engine is handed their natural image."""
+        (``optimize.to_sampling`` / ``from_sampling``); the engine is handed their natural image.
+        ``joint`` (None, or dict(pairs, bins=32, range=None, masses=(0.95,), burn=0, want=None)): the joint regions of coordinate
+        pairs of ``ensemble_joint_dev``, reduced on the device from the kept chain - ``misti_ensemble_sample_joint``, the rule is
+        ``optimize.ensemble_joint_rule`` -, under ``r["joint"]``; ``range="box"`` takes each window from the search box (finite sides
+        only).  The other outputs keep their bits."""
         return self._sampler("ensemble_sample", False, None, True, init, rows, table, box, temperature, split_times, fit_split, band_bounds,
-                             pulse_times, n_step, thin, 0, 0, a, seed, ids, prior)
+                             pulse_times, n_step, thin, 0, 0, a, seed, ids, prior, joint)
 
     _POST_OUTPUTS = ("mean", "cov", "quant", "tau", "window", "best_llh", "best_x", "best_at")
     _POST_SORTED = ("hpd", "hpd_at", "order")              # what needs the sorted marginals: only on request
@@ -766,13 +770,90 @@ class Engine:
                          n_mass=M, masses=masses.ctypes.data if M else None, **{k: at or None for k, (_, at) in made.items()})
         return p, {k: v for k, (v, _) in made.items()}, (probs, masses)
 
+    _JOINT_OUTPUTS = ("counts", "range", "inside", "mode", "level", "cells", "held")
+
+    @staticmethod
+    def _joint(S, N, pairs, bins=32, burn=0, range=None, masses=(0.95,), want=None, empty=None, box=None, address=None):
+        """``misti_ens_joint_t`` for the chains of S searches and N coordinates, and the outputs of ``want`` it points into (None:
+        all of counts, range, inside, mode, and level, cells, held where ``masses`` are given).  ``range``: None (taken from the
+        data), ``"box"`` (the search box ``box`` = ``(lo, hi)`` in sampling coordinates; an infinite side is refused) or what
+        broadcasts to ``[S][n_pair][2][2]``; ``address(range)`` turns it into the pointer the door reads (default: NumPy, on the
+        host).  ``empty(shape, integer)`` as in ``_post``.  Returns (descriptor, outputs, what must stay alive until the call returns)."""
+        from .optimize import joint_pairs
+        pr, bn, off = joint_pairs(pairs, bins, N)
+        P = pr.shape[0]
+        ms = _f64(() if masses is None else masses).reshape(-1)
+        if want is None:
+            want = ("counts", "range", "inside", "mode") + (("level", "cells", "held") if ms.size else ())
+        unknown = [k for k in want if k not in Engine._JOINT_OUTPUTS]
+        if unknown:
+            raise ValueError("joint: unknown outputs %s (there are %s)" % (unknown, ", ".join(Engine._JOINT_OUTPUTS)))
+        if isinstance(range, str):
+            if range != "box" or box is None:
+                raise ValueError("joint: range is None, \"box\" (where the call has a box) or [S][n_pair][2][2]")
+            lo, hi = _box_arrays(box, N)
+            if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+                raise ValueError("joint: range=\"box\" needs a finite box")
+            lo, hi = (np.broadcast_to(v, (S, N)) for v in (lo, hi))
+            range = np.stack([lo[:, pr], hi[:, pr]], axis=-1)                  # [S][n_pair][2 axes][lo, hi]
+        rg_at = None
+        if range is not None:
+            if address is None:
+                range = np.ascontiguousarray(np.broadcast_to(_f64(range), (S, P, 2, 2)))
+                rg_at = range.ctypes.data
+            else:
+                range, rg_at = address(range, (S, P, 2, 2))
+        if empty is None:
+            def empty(shape, integer):
+                v = np.empty(shape, dtype=np.int32 if integer else np.float64)
+                return v, v.ctypes.data
+        M = ms.size
+        shapes = dict(counts=(S, int(off[-1])), range=(S, P, 2, 2), inside=(S, P), mode=(S, P, 2), level=(S, P, M), cells=(S, P, M), held=(S, P, M))
+        made = {k: empty(shapes[k], k != "range") for k in Engine._JOINT_OUTPUTS if k in want}
+        at = {("range_out" if k == "range" else k): a or None for k, (_, a) in made.items()}
+        j = _lib.EnsJoint(size=C.sizeof(_lib.EnsJoint), burn=int(burn), n_pair=P, pairs=pr.ctypes.data, bins=bn.ctypes.data, range=rg_at or None,
+                          n_mass=M, masses=ms.ctypes.data if M else None, **at)
+        out = {k: v for k, (v, _) in made.items()}
+        out.update(pairs=pr, bins=bn, offsets=off, masses=ms)
+        return j, out, (pr, bn, ms, range)
+
+    def ensemble_joint_dev(self, chain, pairs, bins=32, burn=0, range=None, masses=(0.95,), want=None):
+        """``misti_ens_joint_dev``: joint regions of coordinate pairs of a chain that is already on the device - ``chain`` a contiguous
+        float64 torch tensor ``[S][K][W][N]`` on this engine's device.  Per search and pair ``(a, b)`` of ``pairs`` (``[n_pair][2]``)
+        a histogram of ``bins`` (a scalar, ``(Ba, Bb)`` or ``[n_pair][2]``; each 1 ... 128) cells over the kept steps ``burn ... K -
+        1``, inside the window ``range`` (None: the finite extremes of the data; else a torch tensor on the device or an array that
+        broadcasts to ``[S][n_pair][2][2]``), its mode, and per mass the count level whose cells enclose it.  Asynchronous on the
+        engine's stream; the rule is ``optimize.ensemble_joint_rule``, bit for bit, in the SAMPLING coordinate.  ``want``: the outputs
+        to compute among counts, range, inside, mode, level, cells, held (default: all; the last three need ``masses``); one that is
+        left out is not computed and the others' bits do not change.  Returns a dict of int32 torch tensors on the device
+        (``counts[S][sum_q Ba Bb]`` packed as ``offsets`` says - ``optimize.joint_counts`` -, ``range`` float64), with pairs, bins,
+        offsets and masses (NumPy) as they were read."""
+        import torch
+        want = None if want is None else tuple(want)
+        if chain.dim() != 4 or chain.dtype != torch.float64 or not chain.is_contiguous():
+            raise ValueError("ensemble_joint_dev: chain must be a contiguous float64 tensor [S][K][W][N]")
+        S, K, W, N = chain.shape
+        def empty(shape, integer):
+            v = torch.empty(shape, dtype=torch.int32 if integer else torch.float64, device=chain.device)
+            return v, v.data_ptr()
+        def address(r, shape):
+            r = torch.as_tensor(r, dtype=torch.float64).to(chain.device).broadcast_to(shape).contiguous()
+            return r, r.data_ptr()
+        if isinstance(range, str):
+            raise ValueError("ensemble_joint_dev: a chain has no box; give the ranges themselves")
+        j, out, keep = self._joint(S, N, pairs, bins, burn, range, masses, want, empty, None, address)
+        _lib.check(self._lib.misti_ens_joint_dev(self._ctx, S, K, W, N, C.c_void_p(chain.data_ptr()) if chain.data_ptr() else None, C.byref(j)))
+        return out
+
     def _sampler(self, who, tempered, post, keep_chain, init, rows, table, box, temps, split_times, fit_split, band_bounds, pulse_times, n_step,
-                 thin, swap_every, burn, a, seed, ids, prior):
+                 thin, swap_every, burn, a, seed, ids, prior, joint=None):
         """One marshalling for the two sampler descriptors - the rows problem, the outputs, the summaries and the prior - and the call.
         ``tempered`` False: ``misti_ens_t``, ``init`` is ``[S][W][N]`` and ``temps`` the temperature (a scalar or ``[S]``); True:
         ``misti_pt_t``, ``init`` is ``[S][L][W][N]`` and ``temps`` the ladder.  ``post``: None or dict(burn, probs, max_lag, c, masses, want).
+        ``joint``: None or dict(pairs, bins, range, masses, burn, want) - the regions of ``_joint`` through ``misti_*_sample_joint``;
+        None takes the older entries.
         Returns the door's outputs in the descriptor's order (the coordinate chain only with ``keep_chain``; the plain door's value
-        chain too), then the summaries, then ``n_points``."""
+        chain too), then the summaries, then ``joint`` (a dict of its own), then ``n_points``."""
         if (split_times is None) != bool(fit_split):
             raise ValueError("%s: give exactly one of split_times and fit_split=True" % who)
         N = self.n_param + (1 if fit_split else 0)
@@ -807,7 +888,17 @@ class Engine:
         p, s, p_keep = self._post(S, N, K, W=W, **post) if post is not None else (None, {}, None)
         pr, pr_keep = self._prior(prior, S, N, who) if prior is not None else (None, None)
         ref = lambda d: C.byref(d) if d is not None else None
-        if pr is not None:
+        jd, jout = None, None
+        if joint is not None:
+            try:
+                opts = dict(joint)
+                jd, jout, j_keep = self._joint(S, N, opts.pop("pairs"), box=box, **opts)
+            except (KeyError, TypeError):
+                raise ValueError("%s: joint is dict(pairs, bins, range, masses, burn, want)" % who)
+        if jd is not None:
+            door = self._lib.misti_tempered_sample_joint if tempered else self._lib.misti_ensemble_sample_joint
+            rc = door(self._ctx, C.byref(q), ref(p), ref(pr), C.byref(jd))
+        elif pr is not None:
             door = self._lib.misti_tempered_sample_prior if tempered else self._lib.misti_ensemble_sample_prior
             rc = door(self._ctx, C.byref(q), ref(p), C.byref(pr))
         elif tempered:
@@ -817,11 +908,11 @@ class Engine:
         else:
             rc = self._lib.misti_ensemble_sample(self._ctx, C.byref(q))
         _lib.check(rc)
-        return dict({k: v for k, v in out.items() if v is not None}, **s, n_points=int(n_points[0]))
+        return dict({k: v for k, v in out.items() if v is not None}, **s, **({"joint": jout} if jout is not None else {}), n_points=int(n_points[0]))
 
     def ensemble_posterior(self, init, rows, table, box, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
                            thin=1, temperature=1.0, a=2.0, seed=0, ids=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, keep_chain=False, c=5.0,
-                           prior=None, masses=None, want=None):
+                           prior=None, masses=None, want=None, joint=None):
         """``misti_ensemble_posterior``: ``ensemble_sample`` on the same arguments - the same kernels, stream and bits - followed by the
         posterior summaries of its chain, reduced per search ON THE DEVICE: without ``keep_chain`` the chain never leaves it.  The rule is
         ``optimize.ensemble_posterior_rule`` on the kept steps ``burn ... n_keep - 1`` (n of them), bit for bit: ``probs`` (1 ... 8
@@ -836,16 +927,19 @@ class Engine:
         every marginal on the device (``optimize.ensemble_hpd_rule``, bit for bit) - ``hpd[S][N][len(masses)][2]`` and
         ``hpd_at[S][N][len(masses)]`` (the rank of the lower end) join the result; shortest in the SAMPLING coordinate, HPD is not
         invariant under the log map.  ``want``: the summaries to compute, by name (default: the eight above, and hpd, hpd_at with
-        ``masses``); ``"order"`` adds the sorted marginals ``order[S][N][n W]`` themselves."""
+        ``masses``); ``"order"`` adds the sorted marginals ``order[S][N][n W]`` themselves.
+        ``joint`` as in ``ensemble_sample`` (its ``burn`` defaults to this call's): ``r["joint"]``, without the chain leaving the device."""
+        if joint is not None:
+            joint = dict(joint, burn=dict(joint).get("burn", burn))
         r = self._sampler("ensemble_posterior", False, dict(burn=burn, probs=probs, max_lag=max_lag, c=c, masses=masses, want=want), bool(keep_chain), init, rows, table, box,
-                          temperature, split_times, fit_split, band_bounds, pulse_times, n_step, thin, 0, 0, a, seed, ids, prior)
+                          temperature, split_times, fit_split, band_bounds, pulse_times, n_step, thin, 0, 0, a, seed, ids, prior, joint)
         for k in ("chain", "chain_llh") if keep_chain else ():             # this door's order: the chain behind the summaries
             r[k] = r.pop(k)
         r["n_points"] = r.pop("n_points")
         return r
 
     def tempered_sample(self, init, rows, table, box, ladder, split_times=None, fit_split=False, band_bounds=None, pulse_times=None, n_step=100,
-                        thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None, post=None, prior=None):
+                        thin=1, swap_every=1, burn=0, a=2.0, seed=0, ids=None, post=None, prior=None, joint=None):
         """``misti_tempered_sample``: parallel tempering over ``ensemble_sample`` - fit s is a ladder of L ensembles ``init[s]``
         (``[S][L][W][N]``) at the temperatures ``ladder`` (``[L]`` or ``[S][L]``, strictly increasing); rung l samples ``llk / T_l``,
         neighbouring rungs trade walkers every ``swap_every`` steps (0: never), the cold rung carries the posterior, and all rungs of all
@@ -856,14 +950,17 @@ class Engine:
         Returns dict(chain[S][K][W][N] (the cold rung), chain_llh[S][L][K][W], accepted[S][L][W], swap_proposed[S][L-1],
         swap_accepted[S][L-1], last[S][L][W][N], last_llh[S][L][W], rung_llh[S][L], logz[S] (see ``optimize.tempered_rule`` for what it
         is and is not), n_points), plus the summaries with ``post``.  ``prior`` as in ``ensemble_sample`` (one per fit): every rung
-        targets ``prior(y) exp(llk / T_l)`` - ``misti_tempered_sample_prior``, the rule is ``optimize.tempered_prior_rule``."""
+        targets ``prior(y) exp(llk / T_l)`` - ``misti_tempered_sample_prior``, the rule is ``optimize.tempered_prior_rule``.
+        ``joint`` as in ``ensemble_sample`` (its ``burn`` defaults to this call's), on the cold chain - ``misti_tempered_sample_joint``."""
+        if joint is not None:
+            joint = dict(joint, burn=dict(joint).get("burn", burn))
         opts = dict(post) if post is not None else None
         keep_chain = opts is None or bool(opts.pop("keep_chain", False))
         if opts is not None:
             opts = dict(burn=opts.get("burn", burn), probs=opts.get("probs", (0.025, 0.5, 0.975)), max_lag=opts.get("max_lag"), c=opts.get("c", 5.0),
                         masses=opts.get("masses"), want=opts.get("want"))
         return self._sampler("tempered_sample", True, opts, keep_chain, init, rows, table, box, ladder, split_times, fit_split, band_bounds,
-                             pulse_times, n_step, thin, swap_every, burn, a, seed, ids, prior)
+                             pulse_times, n_step, thin, swap_every, burn, a, seed, ids, prior, joint)
 
     def ensemble_summary_dev(self, chain, chain_llh=None, burn=0, probs=(0.025, 0.5, 0.975), max_lag=None, c=5.0, want=None, masses=None):
         """``misti_ens_summary_dev``: the posterior summaries of a chain that is already on the device - ``chain`` a contiguous float64

@@ -1860,6 +1860,183 @@ def posterior_table(result, n_step, walkers=None, prior=None):
     return out
 
 
+# ---------------------------------------------------------------------------- joint regions of coordinate pairs ----
+# The rule of misti_ens_joint_dev stated on the host (include/misti_hip.h, "joint credible regions of coordinate pairs"): a
+# two-dimensional histogram per search and pair, its mode, and the count level that encloses a mass.  Behind the bin of a sample
+# everything is integer arithmetic: the device result is this, bit for bit.
+JOINT_MAX_PAIRS, JOINT_MAX_BINS = 120, 128
+
+
+def joint_pairs(pairs, bins, N=None):
+    """``pairs`` as ``[n_pair][2]`` int32 and ``bins`` (a scalar, ``(Ba, Bb)`` for every pair, or ``[n_pair][2]``) as ``[n_pair][2]``
+    int32, checked as the C ABI checks them, with ``offsets[n_pair + 1]``: pair q's ``Ba x Bb`` cells lie at ``offsets[q] ...
+    offsets[q + 1]`` of a search's packed counts."""
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), dtype=np.int32)
+    if not 1 <= pr.shape[0] <= JOINT_MAX_PAIRS or (pr[:, 0] == pr[:, 1]).any() or (pr < 0).any() or (N is not None and (pr >= N).any()):
+        raise ValueError("joint: 1 ... %d pairs of two distinct coordinates in 0 ... N - 1 (got %s)" % (JOINT_MAX_PAIRS, pr.tolist()))
+    try:
+        bn = np.ascontiguousarray(np.broadcast_to(np.asarray(bins, dtype=np.int64), pr.shape), dtype=np.int32)
+    except ValueError:
+        raise ValueError("joint: bins must be a scalar, (Ba, Bb) or [n_pair][2]")
+    if (bn < 1).any() or (bn > JOINT_MAX_BINS).any():
+        raise ValueError("joint: a bin count must be 1 ... %d" % JOINT_MAX_BINS)
+    return pr, bn, np.concatenate([[0], np.cumsum(bn[:, 0].astype(np.int64) * bn[:, 1])])
+
+
+def joint_bin(x, lo, hi, B):
+    """The bin of INSIDE samples ``x`` (``lo <= x <= hi``) on an axis of B bins: ``scale = double(B) / (hi - lo)``, ``t = (x - lo)
+    scale``, each operation rounded on its own; 0 where ``!(t >= 0)`` (``hi == lo``: 0 inf is NaN; an infinite ``hi - lo``), ``B - 1``
+    where ``t >= double(B)`` (so ``x == hi``), otherwise ``(int)t``."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        scale = np.float64(B) / (np.float64(hi) - np.float64(lo))
+        t = (x - np.float64(lo)) * scale
+        top = t >= float(B)
+        mid = (t >= 0.0) & ~top
+    i = np.zeros(x.shape, dtype=np.int64)
+    i[mid] = t[mid].astype(np.int64)
+    i[top] = B - 1
+    return i
+
+
+def joint_need(inside, mass):
+    """The samples a region of ``mass`` must hold: ``hpd_window`` on the samples inside the window."""
+    return hpd_window(inside, mass)
+
+
+def joint_counts(result, q, s=None):
+    """Pair q's histogram ``[S][Ba][Bb]`` (``[Ba][Bb]`` for search ``s``, or where the result has no search axis) out of a result's
+    packed ``counts``."""
+    c = np.asarray(result["counts"])
+    Ba, Bb = (int(v) for v in np.asarray(result["bins"])[q])
+    c = c[..., int(result["offsets"][q]):int(result["offsets"][q + 1])].reshape(c.shape[:-1] + (Ba, Bb))
+    return c if s is None or c.ndim == 2 else c[s]
+
+
+def ensemble_joint_rule(chain, pairs, bins=32, burn=0, range=None, masses=(0.95,)):
+    """The rule of ``misti_ens_joint_dev`` for ``chain[S][K][W][N]`` (or one search ``[K][W][N]``): per search and pair ``(a, b)`` of
+    distinct coordinates, on the ``m = n W`` kept samples ``t = burn ... K - 1``, with ``Ba x Bb`` bins (``joint_pairs``):
+      range     ``(lo, hi)`` per axis from ``range[S][n_pair][2][2]`` (anything that broadcasts to it), or with None taken from the
+                data: the smallest and largest FINITE kept sample of the coordinate in the order of ``post_order_key`` (-0.0 before
+                +0.0), bits copied; no finite sample: both the canonical quiet NaN
+      inside    a sample is inside the window iff ``lo <= x && x <= hi`` on both axes: a NaN anywhere, or ``lo > hi``, is outside
+      bin       ``joint_bin`` per axis; ``counts[ia][ib]`` the inside samples per cell, ``inside`` their sum, ``outside = m - inside``
+      mode      the cell with the largest count, ties to the lowest ia, then the lowest ib; (-1, -1) where ``inside == 0``
+      region    per mass p in (0, 1]: ``k = joint_need(inside, p)``; ``level`` the LARGEST count c >= 1 such that the cells with count
+                >= c hold at least k samples; ``cells`` their number, ``held`` the samples in them; ties at the level are all in the
+                region ``{cells: count >= level}``; ``inside == 0``: 0, 0, 0
+    The histogram lives in the SAMPLING coordinate: the region of a LOG coordinate is not the image of the region of its natural
+    value.  A search's result depends on its own chain and ranges alone.
+    Returns dict(counts[S][sum_q Ba Bb] int32 (pairs packed in order, row-major: ``joint_counts``), range[S][n_pair][2][2], inside,
+    outside [S][n_pair], mode[S][n_pair][2], level, cells, held [S][n_pair][len(masses)] - all int32 -, and pairs, bins, offsets,
+    masses as they were read) - without the search axis for one search."""
+    x = np.asarray(chain, dtype=np.float64)
+    one = x.ndim == 3
+    if one:
+        x = x[None]
+    if x.ndim != 4:
+        raise ValueError("ensemble_joint_rule: chain must be [S][K][W][N] or [K][W][N]")
+    S, K, W, N = x.shape
+    burn = int(burn)
+    ms = np.asarray(masses, dtype=np.float64).reshape(-1)
+    if not 0 <= burn < K or ms.size > POST_MAX_PROBS or not ((ms > 0) & (ms <= 1)).all() or W < 1 or N < 1:
+        raise ValueError("ensemble_joint_rule: burn must be 0 ... K - 1, at most %d masses in (0, 1]" % POST_MAX_PROBS)
+    pr, bn, off = joint_pairs(pairs, bins, N)
+    P, m = pr.shape[0], (K - burn) * W
+    if range is None:
+        rg = np.full((S, P, 2, 2), np.nan)
+    else:
+        rg = np.array(np.broadcast_to(np.asarray(range, dtype=np.float64), (S, P, 2, 2)))
+    out = dict(counts=np.zeros((S, int(off[-1])), dtype=np.int32), range=rg, inside=np.zeros((S, P), dtype=np.int32), outside=np.zeros((S, P), dtype=np.int32),
+               mode=np.full((S, P, 2), -1, dtype=np.int32), level=np.zeros((S, P, ms.size), dtype=np.int32), cells=np.zeros((S, P, ms.size), dtype=np.int32),
+               held=np.zeros((S, P, ms.size), dtype=np.int32))
+    for s in np.arange(S):
+        flat = x[s, burn:].reshape(m, N)
+        for q in np.arange(P):
+            Ba, Bb = int(bn[q, 0]), int(bn[q, 1])
+            v = [np.ascontiguousarray(flat[:, pr[q, ax]]) for ax in (0, 1)]
+            if range is None:
+                for ax in (0, 1):
+                    f = v[ax][np.isfinite(v[ax])]
+                    if f.size:
+                        key = post_order_key(f)
+                        rg[s, q, ax] = f[[np.argmin(key), np.argmax(key)]]          # an indexed copy: the bits
+            (lo_a, hi_a), (lo_b, hi_b) = rg[s, q]
+            with np.errstate(all="ignore"):
+                ok = (lo_a <= v[0]) & (v[0] <= hi_a) & (lo_b <= v[1]) & (v[1] <= hi_b)
+            cell = joint_bin(v[0][ok], lo_a, hi_a, Ba) * Bb + joint_bin(v[1][ok], lo_b, hi_b, Bb)
+            cnt = np.bincount(cell, minlength=Ba * Bb).astype(np.int64)
+            inside = int(cnt.sum())
+            out["counts"][s, off[q]:off[q + 1]] = cnt
+            out["inside"][s, q], out["outside"][s, q] = inside, m - inside
+            if not inside:
+                continue
+            top = int(np.argmax(cnt))                                               # argmax: the first of the maxima, row-major
+            out["mode"][s, q] = top // Bb, top % Bb
+            levels = np.unique(cnt[cnt > 0])
+            holds = np.array([cnt[cnt >= c].sum() for c in levels])
+            for i, mass in enumerate(ms):
+                level = int(levels[holds >= joint_need(inside, mass)].max())
+                out["level"][s, q, i], out["cells"][s, q, i], out["held"][s, q, i] = level, (cnt >= level).sum(), cnt[cnt >= level].sum()
+    out = {k_: v[0] for k_, v in out.items()} if one else out
+    out.update(pairs=pr, bins=bn, offsets=off, masses=ms)
+    return out
+
+
+def joint_table(result, prior=None):
+    """What one reads off a joint result (``ensemble_joint_rule``, ``Engine.ensemble_joint_dev``, ``r["joint"]`` of the samplers; it
+    must hold counts, range, inside, mode, and level with masses): per search a list over the pairs of dict(pair, window ((lo, hi) per
+    axis), edges (the ``B + 1`` bin edges per axis: ``lo + i (hi - lo) / B``, the last one ``hi``), inside, mode, mode_centre (the
+    centre of the mode cell per axis; NaN where no sample is inside), regions: per mass dict(mass, level, cells, held, mask[Ba][Bb]
+    (``count >= level``), area (the region's share of the window's cells), extent ((lo, hi) per axis: the edges that enclose the
+    region; NaN where it is empty))).  Everything is in SAMPLING units.  With ``prior`` (the call's) each pair also has ``coordinate``
+    ("linear" | "log" per axis) and, flagged by ``natural_is_image`` (True where an axis is LOG), ``window_natural``,
+    ``edges_natural``, ``mode_centre_natural`` and per region ``extent_natural``: the IMAGE of the sampling-unit values in natural
+    units - a region of that mass, but highest-density in the sampling coordinate only.  A result without a search axis gives one such
+    list."""
+    cnt_all = np.asarray(result["counts"])
+    one = cnt_all.ndim == 1
+    get = lambda k: np.asarray(result[k])[None] if one else np.asarray(result[k])
+    rg, inside, mode = get("range"), get("inside"), get("mode")
+    masses = np.asarray(result.get("masses", ()), dtype=np.float64).reshape(-1)
+    level = get("level") if "level" in result and masses.size else None
+    pairs, bins = np.asarray(result["pairs"]), np.asarray(result["bins"])
+    scale = None if prior is None else np.asarray(prior["scale"])
+    tables = []
+    for s in np.arange(rg.shape[0]):
+        rows = []
+        for q in np.arange(pairs.shape[0]):
+            B = [int(bins[q, 0]), int(bins[q, 1])]
+            cnt = joint_counts(result, q, s).astype(np.int64)
+            with np.errstate(all="ignore"):
+                edges = [np.linspace(rg[s, q, ax, 0], rg[s, q, ax, 1], B[ax] + 1) for ax in (0, 1)]
+            centre = [float(0.5 * (edges[ax][mode[s, q, ax]] + edges[ax][mode[s, q, ax] + 1])) if inside[s, q] else np.nan for ax in (0, 1)]
+            row = dict(pair=(int(pairs[q, 0]), int(pairs[q, 1])), window=tuple((float(rg[s, q, ax, 0]), float(rg[s, q, ax, 1])) for ax in (0, 1)),
+                       edges=edges, inside=int(inside[s, q]), mode=(int(mode[s, q, 0]), int(mode[s, q, 1])), mode_centre=tuple(centre), regions=[])
+            for i in np.arange(masses.size if level is not None else 0):
+                lv = int(level[s, q, i])
+                mask = (cnt >= lv) if lv >= 1 else np.zeros(cnt.shape, dtype=bool)
+                extent = []
+                for ax in (0, 1):
+                    hit = np.flatnonzero(mask.any(axis=1 - ax))
+                    extent.append((float(edges[ax][hit[0]]), float(edges[ax][hit[-1] + 1])) if hit.size else (np.nan, np.nan))
+                row["regions"].append(dict(mass=float(masses[i]), level=lv, cells=int(mask.sum()), held=int(cnt[mask].sum()), mask=mask,
+                                           area=float(mask.sum()) / float(mask.size), extent=tuple(extent)))
+            if scale is not None:
+                log = [bool((scale[s] if scale.ndim == 2 else scale)[pairs[q, ax]] == COORD_LOG) for ax in (0, 1)]
+                with np.errstate(all="ignore"):
+                    nat = lambda v, ax: np.exp(v) if log[ax] else v
+                    row.update(coordinate=tuple("log" if l else "linear" for l in log), natural_is_image=any(log),
+                               window_natural=tuple(tuple(float(nat(np.float64(e), ax)) for e in row["window"][ax]) for ax in (0, 1)),
+                               edges_natural=[nat(edges[ax], ax) for ax in (0, 1)],
+                               mode_centre_natural=tuple(float(nat(np.float64(centre[ax]), ax)) for ax in (0, 1)))
+                    for reg in row["regions"]:
+                        reg["extent_natural"] = tuple(tuple(float(nat(np.float64(e), ax)) for e in reg["extent"][ax]) for ax in (0, 1))
+            rows.append(row)
+        tables.append(rows)
+    return tables[0] if one else tables
+
+
 # ------------------------------------------------------------------------------- priors and log-scale coordinates ----
 # What a prior adds to the rules above and below (include/misti_hip.h, "priors and log-scale coordinates"; misti_prior.h): per
 # coordinate a SAMPLING COORDINATE (the engine's value or its logarithm) and a prior density on it.  Stated here once; the device result
