@@ -1071,6 +1071,67 @@ int misti_ensemble_sample_joint(misti_ctx* ctx, const misti_ens_t* sampler, cons
 int misti_tempered_sample_joint(misti_ctx* ctx, const misti_pt_t* sampler, const misti_ens_post_t* post /* or NULL */, const misti_prior_t* prior /* or NULL */,
                                 const misti_ens_joint_t* joint /* or NULL */);
 
+/* ---- trajectory bands: quantiles of the corrected rates per interval ----------------------------- */
+/* Everything above this line that speaks of uncertainty speaks of the PARAMETERS.  The method's other product is the pair of
+ * population-size trajectories below the split: the corrected coalescence rates .lc, which the reference's result file writes as
+ * 1 / lc and MiSTIPlot.py draws.  These entries answer "how wide is the band around the corrected rate of population 1 at interval
+ * 12" for a set of samples - the fits of a bootstrap table, the kept samples of a chain - without the rates leaving the device: lc
+ * [n_cand][numT+1][2] of misti_eval_batch_dev is reduced where it lies, and count, mean, quantiles and extremes per interval and
+ * population come back.  There are no reference lines to replace: the reference has no band.  The inputs are .lc and the grid rule of
+ * MigrationInference.py:89-99.  The rule is THE PROJECT'S OWN, stated once in NumPy (optimize.trajectory_bands_rule); the device
+ * result is that, bit for bit, and a series' result is a function of its own samples alone.
+ *
+ * G groups (the fits of a chain; 1 for a bootstrap table) of m samples: lc[G][m][numT+1][2], split[G][m], status[G][m] or NULL.
+ * All results are on the COMMON GRID, the context's own intervals j = 0 ... numT - 1.  A sample's own grid gains an interval at
+ * floor(split) when its split is fractional (:89-99); for every j with double(j) < split its own row j IS common interval j, and above
+ * that the populations have merged: no regridding is needed and row numT is never read.  Every operation is rounded on its own, no
+ * fused multiply-add.
+ *   - sample i is a MEMBER of series (g, j, pop) iff its status is MISTI_OK (or status is NULL), double(j) < split[g][i] (a NaN split
+ *     is a member of nothing) and lc[g][i][j][pop] is not NaN;
+ *   - count: the number n of members, so count / m is the share of samples whose populations are still separate at interval j;
+ *   - order: the members by the 64-bit key of the posterior summaries above: -0.0 before +0.0, +-inf ordinary members;
+ *   - quant of p in [0, 1]: h = double(n - 1) p, i = floor(h), g = h - i; g == 0 or i >= n - 1: x_(min(i, n - 1)) exactly, otherwise
+ *     x_(i) + g (x_(i+1) - x_(i)) - misti_ens_summary_dev's expression, with n the series' own;
+ *   - mean: lsum of the SORTED members (lsum as above) / double(n);
+ *   - lo, hi: x_(0) and x_(n-1), bits copied;
+ *   - n == 0: count = 0 and the canonical quiet NaN (0x7ff8000000000000) everywhere else; a NaN in quant or mean is stored as that.
+ * The results are RATES, not sizes 1 / lc: a quantile that falls on a sample maps through 1 / x exactly (with the order reversed), an
+ * interpolated one and the mean do not.
+ *
+ * misti_traj_bands_dev: the reduction alone.  d_lc, d_split, d_status and every output pointer are DEVICE memory (probs is HOST);
+ * asynchronous on the context's stream; the counterpart of misti_ens_summary_dev and misti_curvature_assemble_dev.  An output that is
+ * NULL is not computed.  The only memory that scales with m is the ping-pong pair of the sort (samples gathered per series through
+ * LDS, tiles of 2048 keys sorted there, merged through HBM): 2 x groups-per-pass x numT x 2 x m keys of 8 bytes from a growable buffer
+ * of the context; workspace_bytes bounds it (0: 256 MiB) by taking fewer groups per pass, at least one.
+ * misti_traj_bands: the points x[G m][n_param] and split_times[G m] are HOST memory, as band_bounds [G m][n_band][2] and pulse_times
+ * [G m][n_pulse] (or NULL: the model's).  They run through the engine in batches of at most batch_limit candidates (0: 16384) with
+ * n_rep = 0 and lc and status kept on the device, one pass of groups at a time, are reduced as above, and the outputs - HOST buffers
+ * here - are copied back.  Synchronous.  The result depends on neither workspace_bytes nor batch_limit.
+ * Errors, before anything touches the device, in this order: MISTI_E_ARG for a NULL descriptor or a size that is not this library's;
+ * n_prob outside 1 ... MISTI_POST_MAX_PROBS; a NULL probs; a p outside [0, 1] or NaN; a negative workspace_bytes or batch_limit;
+ * G < 0 or m < 1; a NULL lc or split (x or split_times; x only where the model has parameters) with G > 0; then a NULL context; then
+ * MISTI_E_LIMIT for m > INT32_MAX / 8, G m > INT32_MAX / 8 or G x 2 numT x ceil(m / 64) > INT32_MAX (the launch indices).  G == 0
+ * writes nothing.
+ * misti_bands_rank: the rank rule alone, on the host: for n >= 1 members and p in [0, 1] the two order statistics (lo == hi where the
+ * quantile is a sample) and the weight g.  MISTI_E_ARG for n < 1, a p outside [0, 1] or NaN, or a NULL output. */
+typedef struct {
+    uint32_t size;                   /* sizeof(misti_bands_t) */
+    int32_t n_prob;                  /* 1 ... MISTI_POST_MAX_PROBS */
+    const double* probs;             /* HOST [n_prob], each in [0, 1] */
+    int32_t* count;                  /* [G][numT][2] or NULL: the members */
+    double* mean;                    /* [G][numT][2] or NULL */
+    double* quant;                   /* [G][numT][2][n_prob] or NULL */
+    double* lo;                      /* [G][numT][2] or NULL: the smallest member */
+    double* hi;                      /* [G][numT][2] or NULL: the largest member */
+    int64_t workspace_bytes;         /* >= 0: the bound of the sort's workspace; 0: the library's default */
+    int64_t batch_limit;             /* >= 0: candidates per engine batch of misti_traj_bands; 0: the library's default */
+} misti_bands_t;
+int misti_traj_bands_dev(misti_ctx* ctx, int64_t G, int64_t m, const double* d_lc, const double* d_split, const int32_t* d_status /* or NULL */,
+                         const misti_bands_t* bands);
+int misti_traj_bands(misti_ctx* ctx, int64_t G, int64_t m, const double* x /* HOST [G m][n_param] */, const double* split_times /* HOST [G m] */,
+                     const int32_t* band_bounds /* or NULL */, const int32_t* pulse_times /* or NULL */, const misti_bands_t* bands);
+int misti_bands_rank(int64_t n, double p, int64_t* lo, int64_t* hi, double* g);
+
 /* ---- curvature at a fitted point ---------------------------------------------------------------- */
 /* The Hessian of the log-likelihood at a point, and what the sandwich (Godambe) covariance of a composite likelihood needs beside it,
  * WITHOUT a search per bootstrap row: for a fixed candidate the log-likelihood of row r is llh_const_r + sum_k d_{r,k} log S_k(theta)

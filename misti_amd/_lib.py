@@ -141,6 +141,15 @@ class EnsJoint(C.Structure):
                 ("mode", C.c_void_p), ("level", C.c_void_p), ("cells", C.c_void_p), ("held", C.c_void_p)]
 
 
+BANDS_TILE = 64                      # BANDS_TILE (csrc/misti_bands.h): the samples and the columns of the gather's LDS tile
+
+
+class Bands(C.Structure):
+    """``misti_bands_t``: trajectory bands of the corrected rates; the header documents the fields."""
+    _fields_ = [("size", C.c_uint32), ("n_prob", C.c_int32), ("probs", C.c_void_p), ("count", C.c_void_p), ("mean", C.c_void_p), ("quant", C.c_void_p),
+                ("lo", C.c_void_p), ("hi", C.c_void_p), ("workspace_bytes", C.c_int64), ("batch_limit", C.c_int64)]
+
+
 class MistiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libmisti_hip error %d: %s" % (code, msg))
@@ -181,6 +190,9 @@ SYMBOLS = {
     "misti_ens_joint_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(EnsJoint)]),
     "misti_ensemble_sample_joint": (C.c_int, [C.c_void_p, C.POINTER(EnsSample), C.POINTER(EnsPost), C.POINTER(Prior), C.POINTER(EnsJoint)]),
     "misti_tempered_sample_joint": (C.c_int, [C.c_void_p, C.POINTER(PtSample), C.POINTER(EnsPost), C.POINTER(Prior), C.POINTER(EnsJoint)]),
+    "misti_traj_bands_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Bands)]),
+    "misti_traj_bands": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Bands)]),
+    "misti_bands_rank": (C.c_int, [C.c_int64, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "misti_ens_log_prior": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misti_ens_accept_prior": (C.c_int, [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "misti_pt_swap": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

@@ -9,8 +9,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmisti_hip.so")
-SOURCES = ["misti_kernels.hip", "misti_score.hip", "misti_nm.hip", "misti_de.hip", "misti_ens.hip", "misti_pt.hip", "misti_post.hip", "misti_joint.hip", "misti_boot.hip", "misti_jack.hip", "misti_parametric.hip", "misti_api.cpp", "misti_search.cpp", "misti_sampler.cpp", "misti_curv.cpp", "misti_multi.cpp", "misti_lanes.cpp"]
-HEADERS = ["misti_kernel_tables.h", "misti_wave.h", "misti_model.h", "misti_lsq.h", "misti_pair.h", "misti_chain.h", "misti_twopop.h", "misti_device.h", "misti_ctx.h", "misti_fail.h", "misti_rows.h", "misti_score.h", "misti_boot.h", "misti_ens.h", "misti_pt.h", "misti_prior.h", "misti_post.h", "misti_joint.h", "misti_parametric.h", "misti_tables.hpp", "misti_consts.h", os.path.join("..", "..", "include", "misti_hip.h")]
+SOURCES = ["misti_kernels.hip", "misti_score.hip", "misti_nm.hip", "misti_de.hip", "misti_ens.hip", "misti_pt.hip", "misti_post.hip", "misti_joint.hip", "misti_bands.hip", "misti_boot.hip", "misti_jack.hip", "misti_parametric.hip", "misti_api.cpp", "misti_search.cpp", "misti_sampler.cpp", "misti_curv.cpp", "misti_bands.cpp", "misti_multi.cpp", "misti_lanes.cpp"]
+HEADERS = ["misti_kernel_tables.h", "misti_wave.h", "misti_model.h", "misti_lsq.h", "misti_pair.h", "misti_chain.h", "misti_twopop.h", "misti_device.h", "misti_ctx.h", "misti_fail.h", "misti_rows.h", "misti_score.h", "misti_boot.h", "misti_ens.h", "misti_pt.h", "misti_prior.h", "misti_post.h", "misti_joint.h", "misti_bands.h", "misti_parametric.h", "misti_tables.hpp", "misti_consts.h", os.path.join("..", "..", "include", "misti_hip.h")]
 
 
 def hipcc():

@@ -122,6 +122,16 @@ and the GNU-parallel recipe of ``README.md:110-115``):
                               --mcmc-log coordinate the line prints natural units, the IMAGE of a region that is highest-density on the log scale
     --mcmc-joint-mass P ...   with --mcmc-joint: the masses of the regions (1 ... 8, each in (0, 1]; default 0.95)
     --mcmc-joint-out FILE.npz with --mcmc-joint: the counts, ranges, bin edges and levels of every fit and pair, as NumPy arrays
+    --mcmc-bands [P ...]      with --mcmc: per fit the BAND of the corrected coalescence rates lc per interval and population (misti_traj_bands) over the
+                              kept samples behind the burn-in, in natural units, the split from the fitted coordinate where there is one: `bands:`
+                              lines with count / m (the share of samples whose populations are still separate there), lo, the quantiles of each P
+                              (default 0.025 0.5 0.975), hi - RATES, not sizes 1 / lc: an interpolated quantile does not map through 1 / x.  The
+                              chain is read back for this, as for --mcmc-out; with --mcmc-ladder the cold rung's
+    --mcmc-bands-thin T       with --mcmc-bands: every T-th kept step (default 1)
+    --bands [P ...]           with --all-bs and --grid-solve or --fit-st (with or without --hops, --de, --box): the same band over the bootstrap
+                              rows' fits - under --grid-solve each row at its best split; row 0, the point estimate, is reported beside it
+                              (`bands: point` lines) - a `bands:` line per interval below the largest fitted split
+    --bands-out FILE.npz      with --bands: count, mean, quant, lo, hi, probs, the point estimate's rates and the fits, as NumPy arrays
     --mcmc-log K [K ...]      with --mcmc: coordinate K (an index, or st - as --box names them) is SAMPLED ON THE LOG SCALE (misti_ensemble_sample_prior):
                               the stretch, the box test and the chain are in ln(value), the engine is handed the value.  Its --box is given in
                               natural units and needs LO > 0; flat on the log scale is the log-uniform prior.  The `mcmc:` / `post:` lines print
@@ -284,6 +294,14 @@ def build_parser():
                         "reduced on the device; one `joint:` line per fit and pair")
     p.add_argument("--mcmc-joint-mass", nargs="+", type=float, default=None, metavar="P", help="with --mcmc-joint: the masses of the regions (default 0.95)")
     p.add_argument("--mcmc-joint-out", default=None, metavar="FILE.npz", help="with --mcmc-joint: write counts, ranges, edges and levels")
+    p.add_argument("--mcmc-bands", nargs="*", type=float, default=None, metavar="P",
+                   help="with --mcmc: per fit the band of the corrected RATES per interval over the kept samples behind the burn-in (count / m, lo, "
+                        "the quantiles of each P, hi per population; default 0.025 0.5 0.975), reduced on the device; `bands:` lines per fit")
+    p.add_argument("--mcmc-bands-thin", type=int, default=None, metavar="T", help="with --mcmc-bands: every T-th kept step (default 1)")
+    p.add_argument("--bands", nargs="*", type=float, default=None, metavar="P",
+                   help="with --all-bs and --grid-solve or --fit-st: the band of the corrected RATES per interval over the bootstrap rows' fits (row 0: "
+                        "the point estimate, reported beside it; default 0.025 0.5 0.975), reduced on the device; a `bands:` line per interval")
+    p.add_argument("--bands-out", default=None, metavar="FILE.npz", help="with --bands: write count, mean, quant, lo, hi, probs, the point estimate's rates and the fits")
     p.add_argument("--mcmc-log", nargs="+", default=None, metavar="K", help="with --mcmc: coordinates (an index, or st) sampled on the log scale; their --box is in natural units, LO > 0")
     p.add_argument("--mcmc-prior", nargs="+", action="append", default=None, metavar="K",
                    help="with --mcmc: K normal MEAN SD | K exponential SCALE - a prior on coordinate K's sampling coordinate (repeatable)")
@@ -622,6 +640,8 @@ def mcmc_error(a):
             return "--mcmc-log / --mcmc-prior state the coordinates and priors of --mcmc W STEPS: give --mcmc W STEPS"
         if a.mcmc_joint is not None or a.mcmc_joint_mass is not None or a.mcmc_joint_out is not None:
             return "--mcmc-joint / --mcmc-joint-mass / --mcmc-joint-out give the joint regions of --mcmc W STEPS: give --mcmc W STEPS"
+        if a.mcmc_bands is not None or a.mcmc_bands_thin is not None:
+            return "--mcmc-bands / --mcmc-bands-thin give the trajectory bands of --mcmc W STEPS: give --mcmc W STEPS"
         return None
     W, steps = a.mcmc
     if not 4 <= W <= 256 or W % 2:
@@ -703,6 +723,12 @@ def mcmc_error(a):
         return "--mcmc-joint: at most 120 pairs (got %d)" % len(a.mcmc_joint)
     if a.mcmc_joint_mass is not None and (len(a.mcmc_joint_mass) > 8 or not all(0.0 < v <= 1.0 for v in a.mcmc_joint_mass)):
         return "--mcmc-joint-mass P ...: at most 8 masses, each in (0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_joint_mass)
+    if a.mcmc_bands is None and a.mcmc_bands_thin is not None:
+        return "--mcmc-bands-thin T belongs to --mcmc-bands [P ...]: give it"
+    if a.mcmc_bands is not None and (len(a.mcmc_bands) > 8 or not all(0.0 <= v <= 1.0 for v in a.mcmc_bands)):
+        return "--mcmc-bands [P ...]: at most 8 probabilities, each in [0, 1] (got %s)" % " ".join("%g" % v for v in a.mcmc_bands)
+    if a.mcmc_bands_thin is not None and a.mcmc_bands_thin < 1:
+        return "--mcmc-bands-thin T: T >= 1 (got %d)" % a.mcmc_bands_thin
     for name in a.mcmc_log or ():
         if name not in names:
             return "--mcmc-log K: %s is no coordinate of this run (%s)" % (name, ", ".join(names))
@@ -728,6 +754,79 @@ def mcmc_error(a):
         if not (np.isfinite(v).all() and v[-1] > 0):
             return "--mcmc-prior %s: %s" % (text, "MEAN must be finite, SD finite and > 0" if want == 2 else "SCALE must be finite and > 0")
     return None
+
+
+BANDS_PROBS = (0.025, 0.5, 0.975)
+
+
+def bands_error(a):
+    """Why ``--bands`` cannot run with these options (checked before any file is read or the GPU is touched), or None."""
+    if a.bands is None:
+        if a.bands_out is not None:
+            return "--bands-out FILE.npz belongs to --bands [P ...]: give it"
+        return None
+    if not a.all_bs or not (a.fit_st or a.grid_solve):
+        return "--bands is the band over the bootstrap rows' fits: it needs --all-bs with --grid-solve or --fit-st"
+    if len(a.bands) > 8 or not all(0.0 <= v <= 1.0 for v in a.bands):
+        return "--bands [P ...]: at most 8 probabilities, each in [0, 1] (got %s)" % " ".join("%g" % v for v in a.bands)
+    if a.sweep or a.sweep_pu:
+        return "--bands is the band of ONE model: --sweep / --sweep-pu are not offered with it"
+    if a.gpus > 1 or a.devices:
+        return "--bands runs on one GPU (--device); --gpus N > 1 and --devices are not offered with it"
+    return None
+
+
+def _probs(given):
+    """The probabilities of --bands / --mcmc-bands, or the default where the option stands alone."""
+    return tuple(given) if given else BANDS_PROBS
+
+
+def bands_lines(label, b, times, scale_time, m):
+    """The `bands:` lines of one group ``b`` (count[numT][2], lo, quant, hi): per interval with a member its index, its lower edge
+    (scaled as the result lines), and per population count / m, lo, the quantiles, hi - RATES, not sizes; %r, so the text carries the bits."""
+    from .optimize import trajectory_bands_table
+    out = []
+    for row in trajectory_bands_table(b, np.cumsum(np.asarray(times, dtype=float))):      # the grid is given as interval lengths
+        pops = " \t".join("pop%d: %d/%d lo = %r q = [%s] hi = %r" % (p + 1, row["count"][p], m, float(row["lo"][p]),
+                                                                    ", ".join(repr(float(v)) for v in row["quant"][p]), float(row["hi"][p])) for p in (0, 1))
+        out.append("bands: %s \tinterval = %d \ttime = %r \t%s" % (label, row["interval"], float(row["time"] * scale_time), pops))
+    return out
+
+
+def _captured(fun, *args):
+    """What ``fun`` prints, as text: the engine is open while the band is reduced, the lines belong behind the fits'."""
+    import contextlib
+    import io
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        fun(*args)
+    return buf.getvalue().rstrip("\n")
+
+
+def run_bands(a, e, x, split, inp):
+    """--bands behind the fits ``x[R][k]`` and ``split[R]`` of the R rows of --all-bs: rows 1 ... R - 1 are the samples of ONE group
+    (a row without a value: a split of -1, an empty slot to the engine and a member of nothing), row 0 the point estimate, whose own
+    rates are reported beside the band.  Prints the `bands:` lines below the largest fitted split and writes --bands-out."""
+    probs = _probs(a.bands)
+    x, split = np.asarray(x, dtype=float).reshape(len(split), e.n_param), np.asarray(split, dtype=float).copy()
+    bad = ~(np.isfinite(split) & np.isfinite(x).all(axis=1))
+    split[bad] = -1.0
+    x = np.where(bad[:, None], 0.0, x)
+    m = len(split) - 1
+    point = e.trajectory_bands(x[:1], split[:1], groups=1, probs=(0.5,), want=("count", "lo"))
+    rate = np.where(point["count"][0] > 0, point["lo"][0], np.nan)
+    print("bands: rates per interval over the fits of %d bootstrap rows (RATES lc, not sizes 1 / lc), probabilities %s" % (m, " ".join("%g" % v for v in probs)))
+    for j in np.flatnonzero(point["count"][0].any(axis=1)):
+        print("bands: point \tinterval = %d \ttime = %r \tpop1: %r \tpop2: %r" % (j, float(sum(inp.times[:j]) * inp.scaleTime), float(rate[j, 0]), float(rate[j, 1])))
+    b = None
+    if m >= 1:
+        b = e.trajectory_bands(x[1:], split[1:], groups=1, probs=probs)
+        for line in bands_lines("bootstrap", {k_: v[0] for k_, v in b.items() if k_ != "probs"}, inp.times, inp.scaleTime, m):
+            print(line)
+    if a.bands_out:
+        empty = np.empty((0,))
+        np.savez(a.bands_out, probs=np.asarray(probs), point=rate, x=x, split=split, times=np.asarray(inp.times, dtype=float),
+                 **{k_: (b[k_][0] if b is not None else empty) for k_ in ("count", "mean", "quant", "lo", "hi")})
 
 
 def _mcmc_prior(a, k):
@@ -817,7 +916,7 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     sampler = e.ensemble_sample
     if a.mcmc_post is not None:                            # the summaries on the device; the chain comes back only for --mcmc-out
         post = dict(_mcmc_post_options(a), masses=_mcmc_hpd_masses(a))
-        sampler = lambda *args, **kw: e.ensemble_posterior(*args, **kw, burn=o["burn"], keep_chain=bool(a.mcmc_out), **post)
+        sampler = lambda *args, **kw: e.ensemble_posterior(*args, **kw, burn=o["burn"], keep_chain=bool(a.mcmc_out) or a.mcmc_bands is not None, **post)
     common = dict(split_times=split_times, fit_split=split_times is None, n_step=o["n_step"], thin=o["thin"], seed=o["seed"], ids=np.asarray(j_of, dtype=np.uint64))
     if prior is not None:
         common["prior"] = prior
@@ -827,7 +926,7 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
     extra = {}
     if o["ladder"] is not None:
         ladder = temperature_ladder(T, o["ladder"][1], o["ladder"][0])
-        post = None if a.mcmc_post is None else dict(_mcmc_post_options(a), masses=_mcmc_hpd_masses(a), keep_chain=bool(a.mcmc_out))
+        post = None if a.mcmc_post is None else dict(_mcmc_post_options(a), masses=_mcmc_hpd_masses(a), keep_chain=bool(a.mcmc_out) or a.mcmc_bands is not None)
         res = e.tempered_sample(np.ascontiguousarray(np.repeat(init[:, None], ladder.size, axis=1)), np.asarray(r_of, dtype=np.int32), data, box, ladder,
                                 swap_every=o["swap_every"], burn=o["burn"], post=post, **common)
         res["ladder"] = ladder
@@ -838,6 +937,19 @@ def run_mcmc(a, e, x, r_of, j_of, data, box, split_times, unfolded, population=N
         np.savez(a.mcmc_out, chain=res["chain"], chain_llh=res["chain_llh"], accepted=res["accepted"], last=res["last"], last_llh=res["last_llh"],
                  row=np.asarray(r_of), split=np.asarray(split_times) if split_times is not None else np.empty(0), temperature=float(T), **extra,
                  **({} if prior is None else {"prior_" + k: v for k, v in prior.items()}))
+    if a.mcmc_bands is not None:
+        # the chain is read back (as for --mcmc-out), mapped to natural units, and its kept samples behind the burn-in - every T-th step -
+        # go through the engine once more with the rates kept on the device: a group per fit
+        from .optimize import from_sampling
+        kept = np.ascontiguousarray(res["chain"][:, o["burn"]::(a.mcmc_bands_thin or 1)])
+        nat = kept if prior is None else from_sampling(kept, prior)
+        S_, n_, W_, N_ = nat.shape
+        pts = nat.reshape(S_ * n_ * W_, N_)
+        o["bands_m"] = n_ * W_
+        if split_times is None:
+            res["bands"] = e.trajectory_bands(pts[:, :-1], pts[:, -1], groups=S_, probs=_probs(a.mcmc_bands))
+        else:
+            res["bands"] = e.trajectory_bands(pts, np.repeat(np.asarray(split_times, dtype=float), n_ * W_), groups=S_, probs=_probs(a.mcmc_bands))
     if a.mcmc_joint_out:
         from .optimize import joint_table
         j = res["joint"]
@@ -928,6 +1040,13 @@ def print_mcmc(label, o, res, s):
     for c in range(res["chain"].shape[3]):
         print("mcmc:", label, "\tcoordinate %d" % c, "\tmean =", m["mean"][c], "\tmedian =", m["median"][c], "\t2.5% =", m["q025"][c], "\t97.5% =", m["q975"][c],
               "\ttau =", m["tau"][c], "\taccepted =", m["acceptance"], *(["\t(short)"] if m["short"][c] else []), *_log_note(o, c))
+
+
+def print_mcmc_bands(label, mc, s, inp):
+    """The `bands:` lines of fit s of --mcmc-bands, behind its other lines."""
+    if mc and "bands" in mc[2]:
+        for line in bands_lines(label, {k: v[s] for k, v in mc[2]["bands"].items() if k != "probs"}, inp.times, inp.scaleTime, mc[0]["bands_m"]):
+            print(line)
 
 
 def _prior_text(o):
@@ -1343,6 +1462,13 @@ def grid_solve(a, inp, rows):
             R_, P_ = data.shape[0], len(splits)
             cur = e.curvature(prof["x"].reshape(R_ * P_, k), np.tile(np.asarray(splits, dtype=float), R_), np.repeat(np.arange(R_), P_), data,
                               rel_step=_se_step(a))
+        bands_text = None
+        if a.bands is not None:
+            # every row at its own best split (a row without a finite llh at any split: no sample)
+            has_ = np.isfinite(prof["llh"]).any(axis=1)
+            at_ = np.argmax(np.where(np.isfinite(prof["llh"]), prof["llh"], -np.inf), axis=1)
+            bands_text = _captured(run_bands, a, e, np.where(has_[:, None], prof["x"][np.arange(data.shape[0]), at_], np.nan),
+                                   np.where(has_, np.asarray(splits, dtype=float)[at_], np.nan), inp)
         mc, dt_mc = None, 0.0
         if a.mcmc:
             # one ensemble per printed fit: row outermost, split innermost, as the lines; the stream of a fit is its split's index
@@ -1361,12 +1487,15 @@ def grid_solve(a, inp, rows):
                   + (_hops_text(prof, r, p) if a.hops else ""))
             if mc:
                 print_mcmc("bs_id = %s \tsplitT = %s" % (ids[r], st), mc[0], mc[2], r * len(splits) + p)
+                print_mcmc_bands("bs_id = %s \tsplitT = %s" % (ids[r], st), mc, r * len(splits) + p, inp)
     if a.se:
         print()
         print_se(["bs_id = %s \tsplitT = %s" % (ids[r], st) for r in range(data.shape[0]) for st in splits], cur,
                  data if a.all_bs and data.shape[0] >= 4 else None, a.uf)
     iv = bootstrap_profile_interval(prof["llh"], splits, prof["x"])
     print()
+    if bands_text:
+        print(bands_text)
     if iv["data_split"] is None:
         print("grid-solve: bs_id =", ids[0], "has no finite llh at any split")
     else:
@@ -1420,6 +1549,9 @@ def fit_st(a, inp, rows):
             fit = split_fit_global(e, data, starts, splits, seed=hop_seed, niter=a.hops, T=0.5, stepsize=hop_step, box=_box(a, k))
         else:
             fit = split_fit(e, data, starts, splits, tol=a.tol, maxiter=1000, box=_box(a, k))
+        bands_text = None
+        if a.bands is not None:
+            bands_text = _captured(run_bands, a, e, np.where(np.isfinite(fit["llh"])[:, None], fit["x"][:, :k], np.nan), fit["split"], inp)
         mc, dt_mc = None, 0.0
         if a.mcmc:
             # one ensemble per row over (optimised parameters, split); the rows of a bootstrap share stream 0
@@ -1441,7 +1573,10 @@ def fit_st(a, inp, rows):
               + (_hops_text(fit, r) if a.hops else ""))
         if mc:
             print_mcmc("bs_id = %s \tsplitT = %s" % (ids[r], st), mc[0], mc[2], r)
+            print_mcmc_bands("bs_id = %s \tsplitT = %s" % (ids[r], st), mc, r, inp)
     print()
+    if bands_text:
+        print(bands_text)
     if a.jackknife is not None:
         has = np.isfinite(fit["llh"]) & np.isfinite(fit["split"])
         theta = np.where(has[:, None], np.hstack([fit["split"][:, None], fit["x"][:, :k]]), np.nan)
@@ -1595,7 +1730,7 @@ def sweep_solve(a, inp, rows):
 def main(argv=None):
     t0 = time.time()
     a = build_parser().parse_args(argv)
-    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or de_error(a) or mcmc_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
+    why = jackknife_error(a) or parametric_error(a) or bootstrap_error(a) or se_error(a) or profile_error(a) or top_error(a) or hops_error(a) or de_error(a) or mcmc_error(a) or bands_error(a) or fit_st_error(a) or sweep_error(a) or grid_solve_error(a) or box_error(a)
     if why:
         print(why, file=sys.stderr)
         return 2

@@ -597,7 +597,7 @@ int misti_destroy(misti_ctx* c) {
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     (void)hipGetLastError();
     for (auto* b : {&c->model_f64, &c->model_i32, &c->consts, &c->ws_jafs, &c->ws_status, &c->ws_chain_f64, &c->ws_chain_i32, &c->ws_order, &c->ws_diag, &c->ws_trunk, &c->ws_solver, &c->ws_iters, &c->ws_post,
-                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx, &c->curv_f64, &c->curv_i32, &c->boot_chunks, &c->param_totals, &c->post_ws, &c->joint_ws})
+                    &c->st_split, &c->st_params, &c->st_bounds, &c->st_pulses, &c->st_jsfs, &c->st_llk, &c->st_jafs, &c->st_lc, &c->st_pr, &c->st_status, &c->nm_f64, &c->nm_i32, &c->scan_v, &c->scan_i, &c->prof_v, &c->prof_i, &c->prof_idx, &c->curv_f64, &c->curv_i32, &c->boot_chunks, &c->param_totals, &c->post_ws, &c->joint_ws, &c->bands_ws, &c->bands_f64, &c->bands_i32})
         b->release();
     c->pin_in.release();
     c->pin_out.release();

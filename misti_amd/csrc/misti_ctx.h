@@ -98,6 +98,8 @@ struct misti_ctx {
     DevBuf param_totals;                // misti_parametric_rows_dev: the draw counts of one slice of replicates, [n][6] uint64
     DevBuf post_ws;                     // misti_ens_summary_dev: means [S][N] | the centred ensemble-mean series [S][N][n] | the sort's keys [2][S][N][m] (hpd / order)
     DevBuf joint_ws;                    // misti_ens_joint_dev: the windows [S][n_pair][2][2] | the histograms [S][cells], each only where the caller gives no buffer of its own
+    DevBuf bands_ws;                    // misti_traj_bands_dev: the sort's keys [2][groups of a pass][numT][2][m]
+    DevBuf bands_f64, bands_i32;        // misti_traj_bands: a pass's points, splits and rates, the call's outputs | statuses, bounds, pulse times, counts
     int32_t* nm_live_host = nullptr;    // pinned: live starts after the last two finished iterations
     int64_t nm_iterations = 0;          // iterations issued by the last misti_nm_solve
     int64_t nm_slots = 0;               // and the batch slots they had in total (live starts + the stale-count slack)

@@ -985,6 +985,80 @@ class Engine:
                                                    C.c_void_p(chain_llh.data_ptr()) if chain_llh is not None and chain_llh.data_ptr() else None, C.byref(p)))
         return out
 
+    _BANDS_OUTPUTS = ("count", "mean", "quant", "lo", "hi")
+
+    def _bands(self, G, probs, want, empty, workspace_bytes=0, batch_limit=0):
+        """``misti_bands_t`` for G groups on this engine's grid and the outputs of ``want`` (None: all five) it points into;
+        ``empty(shape, integer)`` as in ``_post``.  Returns (descriptor, outputs, what must stay alive until the call returns)."""
+        probs = _f64(probs).reshape(-1)
+        want = self._BANDS_OUTPUTS if want is None else tuple(want)
+        unknown = [k for k in want if k not in self._BANDS_OUTPUTS]
+        if unknown:
+            raise ValueError("trajectory bands: unknown outputs %s (there are %s)" % (unknown, ", ".join(self._BANDS_OUTPUTS)))
+        shape = (G, self.numT, 2)
+        made = {k: empty(shape + ((probs.size,) if k == "quant" else ()), k == "count") for k in self._BANDS_OUTPUTS if k in want}
+        b = _lib.Bands(size=C.sizeof(_lib.Bands), n_prob=probs.size, probs=probs.ctypes.data, workspace_bytes=int(workspace_bytes),
+                       batch_limit=int(batch_limit), **{k: at or None for k, (_, at) in made.items()})
+        out = {k: v for k, (v, _) in made.items()}
+        out["probs"] = probs
+        return b, out, (probs,)
+
+    def trajectory_bands_dev(self, lc, split, status=None, probs=(0.025, 0.5, 0.975), want=None, workspace_bytes=0):
+        """``misti_traj_bands_dev``: bands of the corrected rates that are already on the device - ``lc`` a contiguous float64 torch
+        tensor ``[G][m][numT + 1][2]`` (``d_lc`` of ``evaluate_dev`` for G groups of m samples) on this engine's device, ``split``
+        ``[G][m]`` float64, ``status`` ``[G][m]`` int32 or None (every sample counts as OK).  Per group, interval ``j < numT`` of the
+        common grid and population: the members (status OK, ``j < split``, not NaN), their ``count``, ``quant`` (``[...][len(probs)]``),
+        ``mean``, ``lo`` and ``hi`` - RATES, not sizes.  Asynchronous on the engine's stream; the rule is
+        ``optimize.trajectory_bands_rule``, bit for bit.  ``want``: the outputs to compute (default all five); one that is left out is
+        not computed and the others' bits do not change.  ``workspace_bytes`` bounds the sort's workspace (0: the library's default)
+        and does not change the result.  Returns a dict of torch tensors ``[G][numT][2]`` on the device, and ``probs`` as read."""
+        import torch
+        if lc.dim() != 4 or lc.dtype != torch.float64 or not lc.is_contiguous() or tuple(lc.shape[2:]) != (self.numT + 1, 2):
+            raise ValueError("trajectory_bands_dev: lc must be a contiguous float64 tensor [G][m][%d][2]" % (self.numT + 1))
+        G, m = lc.shape[:2]
+        for name, t in (("lc", lc), ("split", split), ("status", status)):           # a host pointer in a kernel would be a GPU fault
+            if t is not None and (not t.is_cuda or t.device.index != self.device):
+                raise ValueError("trajectory_bands_dev: %s must be a CUDA tensor on device %d (got %s)" % (name, self.device, t.device))
+        if tuple(split.shape) != (G, m) or split.dtype != torch.float64 or not split.is_contiguous():
+            raise ValueError("trajectory_bands_dev: split must be a contiguous float64 tensor [G][m]")
+        if status is not None and (tuple(status.shape) != (G, m) or status.dtype != torch.int32 or not status.is_contiguous()):
+            raise ValueError("trajectory_bands_dev: status must be a contiguous int32 tensor [G][m]")
+        def empty(shape, integer):
+            v = torch.empty(shape, dtype=torch.int32 if integer else torch.float64, device=lc.device)
+            return v, v.data_ptr()
+        b, out, keep = self._bands(G, probs, want, empty, workspace_bytes)
+        at = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.data_ptr() else None
+        _lib.check(self._lib.misti_traj_bands_dev(self._ctx, G, m, at(lc), at(split), at(status), C.byref(b)))
+        return out
+
+    def trajectory_bands(self, x, split_times, groups=1, probs=(0.025, 0.5, 0.975), want=None, band_bounds=None, pulse_times=None,
+                         workspace_bytes=0, batch_limit=0):
+        """``misti_traj_bands``: bands of the corrected rates over points given on the host - ``x[groups m][n_param]`` and
+        ``split_times[groups m]``, group g being the points ``g m ... (g + 1) m - 1`` (the fits of a bootstrap table: one group; the
+        kept samples of a chain: a group per fit).  The points run through the engine in batches of at most ``batch_limit`` (0: the
+        library's default) with the rates kept on the device, and only the bands come back; ``band_bounds`` / ``pulse_times`` as in
+        ``evaluate``.  The result is ``optimize.trajectory_bands_rule`` on ``evaluate(want_lc=True)`` of the same points, bit for bit,
+        whatever ``batch_limit`` and ``workspace_bytes``.  Returns a dict of NumPy arrays ``[groups][numT][2]`` (``quant``:
+        ``[...][len(probs)]``) - RATES, not sizes - and ``probs`` as read."""
+        split = _f64(np.atleast_1d(split_times)).reshape(-1)
+        G, n = int(groups), split.shape[0]
+        if G < 0 or (G == 0) != (n == 0) or (G and n % G):
+            raise ValueError("trajectory_bands: %d points do not make %d groups of equal size" % (n, G))
+        m = n // G if G else 1
+        par = _f64(x, (n, self.n_param)) if self.n_param else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        bb = pt = None
+        if band_bounds is not None and self.n_band:
+            bb = np.ascontiguousarray(band_bounds, dtype=np.int32).reshape(n, self.n_band, 2)
+        if pulse_times is not None and self.n_pulse:
+            pt = np.ascontiguousarray(pulse_times, dtype=np.int32).reshape(n, self.n_pulse)
+        def empty(shape, integer):
+            v = np.empty(shape, dtype=np.int32 if integer else np.float64)
+            return v, v.ctypes.data
+        b, out, keep = self._bands(G, probs, want, empty, workspace_bytes, batch_limit)
+        _lib.check(self._lib.misti_traj_bands(self._ctx, G, m, ptr(par), ptr(split), ptr(bb), ptr(pt), C.byref(b)))
+        return out
+
     def enable_solver_trace(self, on=True):
         """Record, for the following batches, SciPy-comparable solver statistics per candidate and interval
         (``misti_enable_solver_trace``; see ``solver_trace``)."""

@@ -2037,6 +2037,100 @@ def joint_table(result, prior=None):
     return tables[0] if one else tables
 
 
+# ------------------------------------------------------------------ trajectory bands of the corrected rates ----
+# The rule of misti_traj_bands_dev / misti_traj_bands stated on the host (include/misti_hip.h, "trajectory bands"): per group, interval
+# of the common grid and population the members among m samples of lc, their count, quantiles, mean and extremes.  The device result is
+# this, bit for bit.
+def bands_rank(n, p):
+    """The order statistics behind the quantile of probability ``p`` among ``n >= 1`` members: ``h = double(n - 1) p``, ``i =
+    floor(h)``, ``g = h - i``; ``g == 0`` or ``i >= n - 1``: ``x_(min(i, n - 1))`` exactly, otherwise ``x_(i) + g (x_(i+1) - x_(i))``.
+    Returns ``(lo, hi, g)`` with ``lo == hi`` where the quantile is a sample (``misti_bands_rank``)."""
+    h = float(n - 1) * float(p)
+    fl = float(np.floor(h))
+    i, g = int(fl), h - fl
+    if g == 0.0 or i >= n - 1:
+        i = min(i, n - 1)
+        return i, i, g
+    return i, i + 1, g
+
+
+def trajectory_bands_rule(lc, split, status=None, probs=(0.025, 0.5, 0.975), order=False):
+    """The rule of ``misti_traj_bands_dev``, operation for operation, for ``lc[G][m][numT+1][2]`` (the corrected coalescence rates of
+    ``evaluate(want_lc=True)``), ``split[G][m]`` and ``status[G][m]`` (int, or None: every sample is OK) - or one group without the
+    leading axis.  All results are on the COMMON grid ``j = 0 ... numT - 1``: a sample's own grid gains an interval at ``floor(split)``
+    when its split is fractional, but for every ``j`` with ``double(j) < split`` its own row ``j`` is common interval ``j`` and above
+    that the populations have merged, so nothing is regridded and row ``numT`` is never read.  Per series ``(g, j, pop)``:
+      member    sample i iff ``status == 0``, ``double(j) < split[g][i]`` (a NaN split is a member of nothing) and
+                ``lc[g][i][j][pop]`` is not NaN
+      count     the members, n: ``count / m`` is the share of samples whose populations are still separate at interval j
+      sorted    the members by ``post_order_key``: -0.0 before +0.0, +-inf ordinary members
+      quant     ``bands_rank(n, p)``: ``x_(lo)``, or ``x_(lo) + g (x_(hi) - x_(lo))`` - ``ensemble_posterior_rule``'s expression with
+                the series' own n
+      mean      ``lsum(sorted members) / double(n)``
+      lo, hi    ``x_(0)``, ``x_(n-1)``: bits copied
+    ``n == 0``: count 0 and the canonical quiet NaN everywhere else; a NaN in quant or mean is the canonical one.  The results are
+    RATES, not sizes ``1 / lc``: an order statistic maps through ``1 / x`` exactly (the order reversed), an interpolated quantile and
+    the mean do not.
+    Returns dict(count[G][numT][2] int32, mean, lo, hi [G][numT][2], quant[G][numT][2][P]) and with ``order`` also
+    ``sorted[G][numT][2][m]`` (the members first, NaN behind them) - without the leading axis for one group."""
+    x = np.asarray(lc, dtype=np.float64)
+    one = x.ndim == 3
+    if one:
+        x = x[None]
+    if x.ndim != 4 or x.shape[2] < 2 or x.shape[3] != 2 or x.shape[1] < 1:
+        raise ValueError("trajectory_bands_rule: lc must be [G][m][numT + 1][2] or [m][numT + 1][2], m >= 1")
+    G, m, T1, _ = x.shape
+    numT = T1 - 1
+    st = np.asarray(split, dtype=np.float64).reshape(G, m)
+    ok = np.ones((G, m), dtype=bool) if status is None else np.asarray(status).reshape(G, m) == 0
+    pr = np.asarray(probs, dtype=np.float64).reshape(-1)
+    P = pr.size
+    if not 1 <= P <= POST_MAX_PROBS or not ((pr >= 0) & (pr <= 1)).all():
+        raise ValueError("trajectory_bands_rule: 1 ... %d probabilities in [0, 1]" % POST_MAX_PROBS)
+    out = dict(count=np.zeros((G, numT, 2), dtype=np.int32), mean=np.full((G, numT, 2), np.nan), lo=np.full((G, numT, 2), np.nan),
+               hi=np.full((G, numT, 2), np.nan), quant=np.full((G, numT, 2, P), np.nan), sorted=np.full((G, numT, 2, m), np.nan))
+    with np.errstate(all="ignore"):
+        for g in range(G):
+            for j in range(numT):
+                below = ok[g] & (float(j) < st[g])                          # a NaN split compares false
+                for pop in range(2):
+                    v = np.ascontiguousarray(x[g, :, j, pop])
+                    v = v[below & ~np.isnan(v)]
+                    n = v.size
+                    out["count"][g, j, pop] = n
+                    if n == 0:
+                        continue
+                    o = v[np.argsort(post_order_key(v), kind="stable")]
+                    out["sorted"][g, j, pop, :n] = o
+                    out["lo"][g, j, pop], out["hi"][g, j, pop] = o[0], o[n - 1]
+                    out["mean"][g, j, pop] = lsum(o) / float(n)
+                    for p in range(P):
+                        a, b, w = bands_rank(n, pr[p])
+                        out["quant"][g, j, pop, p] = o[a] if a == b else o[a] + w * (o[b] - o[a])
+    for k_ in ("mean", "quant"):                                               # a NaN result: the canonical quiet NaN
+        out[k_][np.isnan(out[k_])] = np.nan
+    if not order:
+        del out["sorted"]
+    return {k_: v[0] for k_, v in out.items()} if one else out
+
+
+def trajectory_bands_table(result, times):
+    """What one prints and saves of ``trajectory_bands`` / ``trajectory_bands_rule`` for ONE group (``count[numT][2]`` ...; give
+    ``{k: v[g] ...}`` for group g of several): a row per interval of the common grid that has a member in either population, as
+    dict(interval, time (the interval's lower edge: 0, then ``times`` - edges, the running sum of a grid given as lengths), count[2], lo[2], quant[2][P], mean[2], hi[2]) - RATES, as the
+    rule says; ``1 / lo`` and ``1 / hi`` are the extremes of the size, the other way round."""
+    count = np.asarray(result["count"])
+    if count.ndim != 2:
+        raise ValueError("trajectory_bands_table: one group at a time (count[numT][2])")
+    edges = np.concatenate([[0.0], np.asarray(times, dtype=np.float64).reshape(-1)])
+    rows = []
+    for j in range(count.shape[0]):
+        if count[j].any():
+            rows.append(dict(interval=j, time=float(edges[j]) if j < edges.size else float("nan"), count=count[j].copy(),
+                             **{k: np.asarray(result[k])[j].copy() for k in ("lo", "quant", "mean", "hi") if k in result}))
+    return rows
+
+
 # ------------------------------------------------------------------------------- priors and log-scale coordinates ----
 # What a prior adds to the rules above and below (include/misti_hip.h, "priors and log-scale coordinates"; misti_prior.h): per
 # coordinate a SAMPLING COORDINATE (the engine's value or its logarithm) and a prior density on it.  Stated here once; the device result
